@@ -2,6 +2,14 @@
 """bench.py -- QPS of the exact / IVF-Flat k-NN hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--nprobe P] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
+
+A plain run builds the workload's index, runs W warm-up steps and K timed steps, and prints the headline line: `value`,
+`ms_per_step` (one timed step), `dtype`, and the roofline / pipeline figures the library records during those steps.
+Everything else described below -- `value_host_io`, the CPU baselines and oracle checks, recall, the `also.*` legs, the
+other nprobe points of an IVF workload, the side measurements and checks of an N > 1 line -- runs only with --full.
+--dump-outputs DIR writes what the timed path returned in its last step: DIR/distances.npy (float32, (queries, k)) and
+DIR/ids.npy (float64, (queries, k)); the inputs are seeded, so two builds given the same arguments can be compared.
 
 A "step" is one pass of the hot path over one 10 000-query batch already resident in HBM: libvdbhip's device
 pipeline (query prep -> MFMA scan + bin select -> exact refine), and for N > 1 the RCCL all-gather of the per-shard
@@ -46,6 +54,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 import time
 import zlib
 from pathlib import Path
@@ -220,6 +229,17 @@ def make_data(name: str, rank: int):
     return np.ascontiguousarray(X, np.float32), np.ascontiguousarray(Q, np.float32), k, metric
 
 
+def dump_outputs(out_dir, D_t, I_t) -> None:
+    """--dump-outputs: the (nq, k) distances and ids of the timed path's last step, as a caller receives them, to
+    DIR/distances.npy (float32) and DIR/ids.npy (float64: every id and the -1 padding are exact)."""
+    if not out_dir:
+        return
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "distances.npy", D_t.cpu().numpy().astype(np.float32))
+    np.save(d / "ids.npy", I_t.cpu().numpy().astype(np.float64))
+
+
 def recall_vs(ids_ref, ids_got, k) -> float:
     return float(np.mean([len(set(a[:k].tolist()) & set(b[:k].tolist())) / k for a, b in zip(ids_ref, ids_got)]))
 
@@ -373,10 +393,12 @@ def flat_leg(vdbhip, torch, name, dev, local_rank, stream, steps, warmup, cpu_bu
 
 
 def ivf_leg(vdbhip, torch, dev, local_rank, stream, steps, warmup, nprobes, name="ivf1024", nlist=1024, data=None,
-            cpu_budget_s=5.0, plugin_metric=None):
+            cpu_budget_s=5.0, plugin_metric=None, full=True, dump_dir=None):
     """BASELINE configs[3]: ONE IVF-Flat index (the library's own k-means: vdb_ivf_train 25 iterations, seed 1234),
     `set_nprobe` per point; each point with the list scan's roofline, recall@10 against the exact result of the same
-    queries, and the C restatement of the same search (same centroids, same lists) as the CPU leg and bit-level check."""
+    queries, and the C restatement of the same search (same centroids, same lists) as the CPU leg and bit-level check.
+    full=False (a plain bench run): the timed loop and its roofline only -- no list sizes, host-I/O timing, exact
+    reference or CPU leg."""
     from oracle import c_oracle
 
     X, Q, k, metric = data if data is not None else make_data(name, 0)
@@ -388,32 +410,34 @@ def ivf_leg(vdbhip, torch, dev, local_rank, stream, steps, warmup, nprobes, name
     train_s = time.perf_counter() - t0
     index.add(X)
     build_s = time.perf_counter() - t0
-    flat = vdbhip.FlatIndex(d, metric, local_rank)
-    flat.add(X)
-    _, exact_ids = flat.search(Q, k)
-    flat.close()
-    C, lor = index.centroids(), index.assignment()
-    sizes = np.bincount(lor, minlength=nlist)
     q_t = torch.from_numpy(Q).to(dev)
     D_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
     I_t = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    c_oracle.build()
-    cores = usable_cpus()
     out = {"config": f"{name}: {n} rows x {d} dims, {nq} queries, k={k}, {metric}; IVF-Flat nlist={nlist}, own k-means "
                      f"(25 iterations on {min(n, 256 * nlist)} sampled rows)",
-           "train_s": round(train_s, 3), "build_s": round(build_s, 3),
-           "list_rows": {"min": int(sizes.min()), "median": int(np.median(sizes)), "max": int(sizes.max())}}
+           "train_s": round(train_s, 3), "build_s": round(build_s, 3)}
+    if full:
+        flat = vdbhip.FlatIndex(d, metric, local_rank)
+        flat.add(X)
+        _, exact_ids = flat.search(Q, k)
+        flat.close()
+        C, lor = index.centroids(), index.assignment()
+        sizes = np.bincount(lor, minlength=nlist)
+        c_oracle.build()
+        cores = usable_cpus()
+        out["list_rows"] = {"min": int(sizes.min()), "median": int(np.median(sizes)), "max": int(sizes.max())}
     for p in nprobes:
         index.set_nprobe(p)
         host = {}
-        for _ in range(2):
-            index.search(Q, k)
-        ts = []
-        for _ in range(7):
-            t1 = time.time()
-            index.search(Q, k)
-            ts.append(time.time() - t1)
-        host["value_host_io"] = round(nq / float(np.median(ts)), 1)
+        if full:
+            for _ in range(2):
+                index.search(Q, k)
+            ts = []
+            for _ in range(7):
+                t1 = time.time()
+                index.search(Q, k)
+                ts.append(time.time() - t1)
+            host["value_host_io"] = round(nq / float(np.median(ts)), 1)
         el, st = timed_device_loop(index, q_t, nq, k, D_t, I_t, stream, steps, warmup, torch)
         ids = I_t.cpu().numpy()
         rows_probed = float(st.get("last_rows_scanned", 0)) or nq * p / float(nlist) * n
@@ -424,16 +448,17 @@ def ivf_leg(vdbhip, torch, dev, local_rank, stream, steps, warmup, nprobes, name
                                          "probed list once per group of query slots, so it is MFMA- (nprobe 32 / 128) or "
                                          "launch-bound (nprobe 8), not bound by these bytes"}
         point = {"value": round(nq * steps / el, 1), "unit": "queries/s", "ms_per_step": round(el / steps * 1e3, 4),
-                 "dtype": scan_dtype_name(st), **host, "roofline": roof,
-                 "recall@10_vs_exact": round(recall_vs(exact_ids, ids, min(k, 10)), 6),
-                 "pipeline": {"path": st["last_path_name"], "candidates_per_query": round(st["last_candidates"] / nq, 2),
-                              "rescan_bins": int(st["last_rescan_bins"]),
-                              "fallback_queries": int(st["last_fallback_queries"]),
-                              "rows_scanned_per_query": round(rows_probed / nq, 1),
-                              "hbm_resident_mb": round(st["bytes_resident"] / 2 ** 20, 1)}}
-        if k != 10:
+                 "dtype": scan_dtype_name(st), **host, "roofline": roof}
+        if full:
+            point["recall@10_vs_exact"] = round(recall_vs(exact_ids, ids, min(k, 10)), 6)
+        point["pipeline"] = {"path": st["last_path_name"], "candidates_per_query": round(st["last_candidates"] / nq, 2),
+                             "rescan_bins": int(st["last_rescan_bins"]),
+                             "fallback_queries": int(st["last_fallback_queries"]),
+                             "rows_scanned_per_query": round(rows_probed / nq, 1),
+                             "hbm_resident_mb": round(st["bytes_resident"] / 2 ** 20, 1)}
+        if full and k != 10:
             point[f"recall@{k}_vs_exact"] = round(recall_vs(exact_ids, ids, k), 6)
-        if cpu_budget_s > 0:
+        if full and cpu_budget_s > 0:
             probe = min(nq, 128)
             t1 = time.perf_counter()
             c_oracle.ivf_search(X, C, lor, Q[:probe], k, p, metric, threads=cores)
@@ -449,6 +474,7 @@ def ivf_leg(vdbhip, torch, dev, local_rank, stream, steps, warmup, nprobes, name
                                      "sample": f"first {sample} of {nq} queries, nprobe {p}, {dt:.1f} s"}
             point["ids_equal_cpu_oracle_sample"] = bool(np.array_equal(io_, ids[:sample]))
         out[f"nprobe{p}"] = point
+    dump_outputs(dump_dir, D_t, I_t)
     index.close()
     return out
 
@@ -636,17 +662,16 @@ def launch_ranks(args) -> int:
     if have < args.gpus and not shared_gpu():
         raise SystemExit(f"bench.py --gpus {args.gpus} needs {args.gpus} GPUs on this node, found {have}")
     port = int(os.environ.get("MASTER_PORT", 29400 + os.getpid() % 2000))
-    procs, out0 = [], ROOT / "gpurun_out" / f".bench_rank0_{os.getpid()}.out"
-    out0.parent.mkdir(exist_ok=True)
-    with open(out0, "wb") as f0:
+    procs = []
+    with tempfile.TemporaryFile() as f0:        # rank 0's stdout
         for rank in range(args.gpus):
             env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(args.gpus),
                        MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
             procs.append(subprocess.Popen([sys.executable, str(Path(__file__).resolve())] + sys.argv[1:], env=env,
                                           stdout=f0 if rank == 0 else sys.stderr))
         rcs = wait_all_or_kill(procs)
-    text = out0.read_text(errors="replace")
-    out0.unlink(missing_ok=True)
+        f0.seek(0)
+        text = f0.read().decode(errors="replace")
     if any(rcs):
         sys.stderr.write(f"bench.py: rank exit codes {rcs}\n")
         return 1
@@ -697,8 +722,13 @@ def main() -> int:
     ap.add_argument("--stream-panels", action="store_true",
                     help="device-generated D > 128 workloads: option stream_panels = 1 (the fp16 scan copy is converted per "
                          "search instead of kept resident: smaller footprint, one extra pass over the rows per batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline workload only: no also.* legs")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: host-I/O timing, CPU baselines, recall and oracle checks, the also.* "
+                         "legs, every nprobe point of an IVF workload, the side measurements of an N > 1 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's last-step result as DIR/distances.npy (float32) and DIR/ids.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline workload only, no also.* legs")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)
@@ -731,7 +761,7 @@ def main() -> int:
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     stream = torch.cuda.current_stream().cuda_stream
-    cpu_budget = 0.0 if args.no_cpu_baseline else 6.0
+    cpu_budget = 6.0 if args.full and not args.no_cpu_baseline else 0.0
 
     if world == 1 and os.environ.get("VDBHIP_BENCH_FORCE_SHARDED") != "1":
         out = single_gpu_line(args, workload, vdbhip, torch, dev, local_rank, stream, cpu_budget)
@@ -752,8 +782,10 @@ def single_gpu_line(args, workload, vdbhip, torch, dev, local_rank, stream, cpu_
     if workload in ("ivf1024", "msmarco_ivf"):       # an IVF workload on its own (profiling runs): one point is the line
         nlist = 1024 if workload == "ivf1024" else 100
         probes = [args.nprobe] if args.nprobe > 0 else ([8, 32, 128] if workload == "ivf1024" else [32])
+        if not args.full:
+            probes = probes[-1:]
         leg = ivf_leg(vdbhip, torch, dev, local_rank, stream, args.steps, args.warmup, probes, name=workload,
-                      nlist=nlist, cpu_budget_s=cpu_budget)
+                      nlist=nlist, cpu_budget_s=cpu_budget, full=args.full, dump_dir=args.dump_outputs)
         head = leg[f"nprobe{probes[-1]}"]
         out = {"metric": f"QPS ({workload} IVF-Flat nlist={nlist} nprobe={probes[-1]}, k={k})", "value": head["value"],
                "unit": "queries/s", **contract, "ms_per_step": head["ms_per_step"], "dtype": head["dtype"],
@@ -776,8 +808,10 @@ def single_gpu_line(args, workload, vdbhip, torch, dev, local_rank, stream, cpu_
         data = (Xr, Qr, 10, "l2")
         data_tag = f"sift1m (real TEXMEX files from {where})"
     head, kept = flat_leg(vdbhip, torch, workload, dev, local_rank, stream, args.steps, args.warmup,
-                          cpu_budget_s=cpu_budget * 1.6, data=data, keep_index=True, all_cpu_legs=(workload == "sift1m"))
+                          cpu_budget_s=cpu_budget * 1.6, host_io=args.full, data=data, keep_index=True,
+                          all_cpu_legs=(workload == "sift1m"))
     algo, index, q_t, D_t, I_t, X, Q, ids = kept
+    dump_outputs(args.dump_outputs, D_t, I_t)
     n, d = X.shape
     name = {"sift1m": "SIFT1M%s, 10k-query batch, k=10" % ("" if real else "-shaped")}.get(workload, f"{workload}, k={k}")
     out = {"metric": f"QPS @ recall@10 ({name})", "value": head["value"], "unit": "queries/s", **contract,
@@ -791,7 +825,8 @@ def single_gpu_line(args, workload, vdbhip, torch, dev, local_rank, stream, cpu_
     for key in ("value_host_io", "host_io_ms", "first_call_ms"):
         if key in head:
             out[key] = head[key]
-    out["value_note"] = HOST_IO_NOTE
+    if "value_host_io" in head:
+        out["value_note"] = HOST_IO_NOTE
     for key in ("roofline", "pipeline", "cpu_baseline", "cpu_baselines", "recall@10_vs_cpu_blas_sample",
                 "ids_equal_cpu_oracle_first32"):
         if key in head:
@@ -800,9 +835,9 @@ def single_gpu_line(args, workload, vdbhip, torch, dev, local_rank, stream, cpu_
         out["dtype_note"] = ("the int8 scan serves byte-valued corpora with integer queries only (SIFT descriptors are uint8); "
                              "one non-integer query value puts the batch on the fp16 scan of the same index: "
                              "also.gaussian1m is that case")
-    if GT is not None:
+    if GT is not None and args.full:
         out["recall@10_vs_sift_groundtruth"] = round(recall_vs(GT[:, :k], ids, k), 6)
-    if args.no_extras or workload != "sift1m":
+    if not args.full or args.no_extras or workload != "sift1m":
         index.close()
         return out
 
@@ -860,15 +895,18 @@ def device_corpus_line(args, workload, vdbhip, torch, dev, local_rank, stream):
     D_t = torch.empty((nq, k), dtype=torch.float32, device=dev)
     I_t = torch.empty((nq, k), dtype=torch.int64, device=dev)
     el, st = timed_device_loop(index, q_t, nq, k, D_t, I_t, stream, args.steps, args.warmup, torch)
+    dump_outputs(args.dump_outputs, D_t, I_t)
     out = {"metric": f"QPS ({workload}, k={k})", "value": round(nq * args.steps / el, 1), "unit": "queries/s",
            "ms_per_step": round(el / args.steps * 1e3, 4), "dtype": scan_dtype_name(st), "data": "synthetic",
            "config": {"workload": f"{workload}: {n} rows x {d} dims per GPU, {nq} queries, k={k}, {metric}; brute-force "
                                   f"exact k-NN; rows generated on device; inputs resident in HBM",
                       "rows_per_gpu": n, "dim": d, "queries": nq, "k": k, "metric": metric, "sharding": "none"},
            "roofline": roofline_of(st, nq, n, d, workload),
-           "pipeline": pipeline_of(st, nq, build_s, float(n) * d * 4),
-           "recall@10_vs_float64_torch_sample": round(device_check(X_t, q_t, I_t, k, metric, 0), 6),
-           "result_checksum": result_checksum(I_t), "stream_panels": bool(args.stream_panels)}
+           "pipeline": pipeline_of(st, nq, build_s, float(n) * d * 4)}
+    if args.full:
+        out["recall@10_vs_float64_torch_sample"] = round(device_check(X_t, q_t, I_t, k, metric, 0), 6)
+        out["result_checksum"] = result_checksum(I_t)
+    out["stream_panels"] = bool(args.stream_panels)
     index.close()
     return out
 
@@ -931,9 +969,10 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ranks, stream, steps, warmup):
+def sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ranks, stream, steps, warmup, dump_dir=None):
     """One row-sharded workload over the job's ranks: every rank scans ITS shard for the same query batch
-    (vdb_search_partial_device), ONE all-gather of the packed partials, merge on every rank."""
+    (vdb_search_partial_device), ONE all-gather of the packed partials, merge on every rank.  The side measurements
+    (shard scan alone, exchange alone), the recall check and the checksum run with --full only."""
     world = ranks.world
     n_total, d, nq, k, metric, gen = WORKLOADS[workload]
     if strong:
@@ -991,13 +1030,16 @@ def sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ra
 
     for _ in range(warmup):
         step()
-    # untimed side measurements: this rank's shard scan without the exchange, and the exchange (all-gather + merge) alone
-    shard_alone_ms = timed(local_step, 3) / 3 * 1e3
-    exchange_ms = timed(exchange_step, 10) / 10 * 1e3
+    if args.full:
+        # untimed side measurements: this rank's shard scan without the exchange, and the exchange (all-gather + merge) alone
+        shard_alone_ms = timed(local_step, 3) / 3 * 1e3
+        exchange_ms = timed(exchange_step, 10) / 10 * 1e3
     index.set_option("timing", 1)      # HIP events around the scan kernel, on the search stream, per step
     elapsed = timed(step, steps)
     st = index.stats()
     index.set_option("timing", 0)
+    if rank == 0:
+        dump_outputs(dump_dir, D_t, I_t)
 
     ms_per_step = elapsed / steps * 1e3
     qps_corpus = nq * steps / elapsed
@@ -1024,18 +1066,21 @@ def sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ra
         "roofline": roofline_of(st, nq, n, d, workload),
         "pipeline": pipeline_of(st, nq, build_s, float(n) * d * 4),
         "qps_whole_corpus": round(qps_corpus, 1),
-        "shard_scan_alone_ms": round(shard_alone_ms, 4),
-        "exchange_ms": round(exchange_ms, 4),
-        "exchange_note": f"all-gather of {my_pack.numel() * 8} bytes per rank + merge of {world} partial lists "
-                         f"per query, timed alone (10 repetitions, max over ranks)",
-        "result_checksum": result_checksum(I_t),
     }
-    if X is None:
-        leg["recall@10_vs_float64_torch_sample"] = round(device_check(X_t, q_t, I_t, k, metric, lo, ranks=ranks), 6)
-    else:      # host-generated shard: this rank's part of the merged result against the CPU oracle on its own rows is not the
-        # merged truth; check instead that every returned id of a query sample is the exact neighbour among ALL shards
-        leg["recall@10_vs_float64_torch_sample"] = round(
-            device_check(torch.from_numpy(X).to(dev), q_t, I_t, k, metric, lo, ranks=ranks), 6)
+    if args.full:
+        leg.update({
+            "shard_scan_alone_ms": round(shard_alone_ms, 4),
+            "exchange_ms": round(exchange_ms, 4),
+            "exchange_note": f"all-gather of {my_pack.numel() * 8} bytes per rank + merge of {world} partial lists "
+                             f"per query, timed alone (10 repetitions, max over ranks)",
+            "result_checksum": result_checksum(I_t),
+        })
+        if X is None:
+            leg["recall@10_vs_float64_torch_sample"] = round(device_check(X_t, q_t, I_t, k, metric, lo, ranks=ranks), 6)
+        else:      # host-generated shard: this rank's part of the merged result against the CPU oracle on its own rows is not the
+            # merged truth; check instead that every returned id of a query sample is the exact neighbour among ALL shards
+            leg["recall@10_vs_float64_torch_sample"] = round(
+                device_check(torch.from_numpy(X).to(dev), q_t, I_t, k, metric, lo, ranks=ranks), 6)
     index.close()
     del X_t
     torch.cuda.empty_cache()
@@ -1050,10 +1095,11 @@ def sharded_line(args, workload, vdbhip, torch, dev, rank, local_rank, world, st
     (N = 1 points: also["marco12.5m"] of the `--gpus 1` line)."""
     ranks = Ranks(torch, dev, world)
     strong = args.scaling == "strong"
-    out = sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ranks, stream, args.steps, args.warmup)
+    out = sharded_leg(args, workload, strong, vdbhip, torch, dev, rank, local_rank, ranks, stream, args.steps, args.warmup,
+                      dump_dir=args.dump_outputs)
     out["scaling_reference"] = ("N = 1 point: the `--gpus 1` line's `value` for sift1m (the same shard, searched without the "
                                 "gather + merge); for marco12.5m `also[\"marco12.5m\"]` of that line (value, result_checksum)")
-    if workload == "sift1m" and not args.no_extras:
+    if workload == "sift1m" and args.full and not args.no_extras:
         also = {}
         for mode in ("weak", "strong"):
             also[mode] = sharded_leg(args, "marco12.5m", mode == "strong", vdbhip, torch, dev, rank, local_rank, ranks, stream,

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 prof() {   # name, bench args...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o $name -- \
-      python3 $R/bench.py "$@" > $OUT/${name}_rocprof.json 2> $OUT/$name.err || echo "rocprof $name failed"
+      python3 $R/bench.py --full "$@" > $OUT/${name}_rocprof.json 2> $OUT/$name.err || echo "rocprof $name failed"
   local f=$(find $OUT/$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/${name}_kernel_stats.csv
 }
@@ -21,11 +21,11 @@ pmc() {    # name, counters..., then -- bench args
   while [ "$1" != "--" ]; do ctr+=("$1"); shift; done
   shift
   timeout -k 10 240 rocprofv3 --pmc "${ctr[@]}" --kernel-trace --output-format csv -d $OUT/pmc_$name -o $name -- \
-      python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras "$@" > $OUT/pmc_$name.log 2>&1 || echo "pmc pass $name failed"
+      python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras "$@" > $OUT/pmc_$name.log 2>&1 || echo "pmc pass $name failed"
 }
 python3 $R/__graft_entry__.py smoke > $OUT/smoke.txt 2>&1 || echo "smoke failed"
 echo "== bench (driver command)"; date
-timeout -k 10 500 python3 $R/bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
+timeout -k 10 500 python3 $R/bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
 echo "== kernel stats"; date
 prof sift1m --steps 20 --warmup 5 --no-cpu-baseline --no-extras
 python3 $R/scripts/trace_breakdown.py $(find $OUT/sift1m -name '*kernel_trace.csv' | head -1) > $OUT/sift1m_breakdown.txt 2>&1

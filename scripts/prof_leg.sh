@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$NAME
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- \
-    python3 $R/bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err || echo "rocprof failed"
+    python3 $R/bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err || echo "rocprof failed"
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/kernel_stats.csv
 t=$(find $OUT/trace -name "*kernel_trace.csv" | head -1)
 [ -n "$t" ] && python3 $R/scripts/trace_breakdown.py $t $FILTER > $OUT/breakdown.txt 2>&1

@@ -8,6 +8,6 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$NAME -o $NAME -- \
-    python3 $R/bench.py "$@" > $OUT/$NAME.json 2> $OUT/$NAME.err || echo "rocprof $NAME failed"
+    python3 $R/bench.py --full "$@" > $OUT/$NAME.json 2> $OUT/$NAME.err || echo "rocprof $NAME failed"
 f=$(find $OUT/$NAME -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $OUT/${NAME}_kernel_stats.csv && head -14 $OUT/${NAME}_kernel_stats.csv | cut -c1-150

@@ -29,9 +29,10 @@ def _bench(*args, env=None, timeout=600):
 
 def test_two_ranks_strong_scaling_equal_one_rank():
     shared = {"VDBHIP_BENCH_SHARED_GPU": "1"}
-    one = _bench("--gpus", "1", "--workload", "marco1m", "--scaling", "strong", "--steps", "3", "--warmup", "1",
+    one = _bench("--gpus", "1", "--workload", "marco1m", "--scaling", "strong", "--steps", "3", "--warmup", "1", "--full",
                  env={"VDBHIP_BENCH_FORCE_SHARDED": "1"})
-    two = _bench("--gpus", "2", "--workload", "marco1m", "--scaling", "strong", "--steps", "3", "--warmup", "1", env=shared)
+    two = _bench("--gpus", "2", "--workload", "marco1m", "--scaling", "strong", "--steps", "3", "--warmup", "1", "--full",
+                 env=shared)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["ranks"] == 2 and two["collective_backend"] == "gloo"
     assert two["scaling"] == "strong" and two["config"]["rows_per_gpu"] == 500_000 and two["config"]["corpus_rows"] == 1_000_000
     assert one["result_checksum"] == two["result_checksum"]          # same rows, same queries, same merged ids
@@ -43,8 +44,8 @@ def test_two_ranks_strong_scaling_equal_one_rank():
 
 def test_two_ranks_default_line_is_the_headline_workload_weak():
     """`--gpus 2` with no workload: the sift1m headline under weak scaling (every rank its own 1M x 128 shard), i.e. the same
-    workload as the `--gpus 1` line, with the config-5 shape riding along (here skipped: --no-extras keeps the test short)."""
-    two = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras", env={"VDBHIP_BENCH_SHARED_GPU": "1"})
+    workload as the `--gpus 1` line, with the config-5 shape riding along (here skipped: --no-extras keeps the --full line short)."""
+    two = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras", env={"VDBHIP_BENCH_SHARED_GPU": "1"})
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and "sift1m" in two["config"]["workload"]
     assert two["config"]["rows_per_gpu"] == 1_000_000 and two["config"]["corpus_rows"] == 2_000_000
     assert two["recall@10_vs_float64_torch_sample"] == 1.0
