@@ -206,8 +206,6 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "force_path"      0 auto | 1 exact kernels only | 2 MFMA scan whenever legal | 3 exact kernels, one query per wave
  *     "timing"          1: (re)start recording HIP-event times of every search on its stream, averaged by vdb_stats
  *     "list_cap"        work-list capacity per query (0 = default max(64, 2k + 32))
- *     "panel_layout"    0 auto (16-row-tile panels for D > 128) | 1 32-row tiles for every D | 2 16-row tiles for every D;
- *                       takes effect at the next vdb_add
  *     "panel_dtype"     0 auto: byte-valued integer corpora are ALSO kept as an int8 scan copy, and integer query batches
  *                       in the byte window are scanned with int8 MFMA | 1 fp16 scan only
  *     "int8_only"       flat index, D <= 128, more than 32 768 rows, takes effect at the next vdb_add: 0 (default) | 1: a byte-valued
@@ -275,7 +273,9 @@ int vdb_set_option(vdb_handle h, const char *key, double value);
 
 /* ---- test hooks (used by tests/ to validate the error bound of the fp16 scan) -------------- */
 /* raw scan scores (scaled units) for queries x rows [row0,row0+nrows), any D <= 4096: out (nq, nrows) float32,
- * together with the per-query bound eps (nq) and the scale cs so that score/cs ~ (||x||^2 - 2 q.x) or -q.x */
+ * together with the per-query bound eps (nq) and the scale cs so that score/cs ~ (||x||^2 - 2 q.x) or -q.x.
+ * Flat indexes whose fp16 panels are resident, in every layout the scans use (vdb_stats.scan_shape 16 / 32, p16 for
+ * D > 128); VDB_ERR_UNSUPPORTED for D > 128 on at most 2048 rows (no MFMA scan there) */
 int vdb_debug_scan_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t row0, int64_t nrows,
                           float *scores_host, float *eps_host, double *cscale);
 

@@ -409,14 +409,13 @@ def test_candidate_rerank_matches_reference_loop(vdb):
 
 
 @pytest.mark.parametrize("d,metric,kind", [(128, "l2", "sift"), (100, "l2", "gauss"), (50, "ip", "glove"), (64, "ip", "gauss")])
-def test_p16_panel_layout_for_small_dims_is_exact(vdb, oracle, d, metric, kind):
-    """Option panel_layout = 2: 16-row-tile panels + scan16_kernel (v_mfma_f32_16x16x32_f16) for D <= 128 -- the
-    measured-and-not-adopted alternative of DESIGN 4.3.  Same bins, ids and guard: bit-exact results, and the
-    per-query error bound holds on its raw scores."""
+def test_x16_layout_is_exact_and_its_error_bound_holds(vdb, oracle, d, metric, kind):
+    """The production layout of a D <= 128 flat index above the dense path's rows: layout "x16" (v_mfma_f32_16x16x32_f16,
+    DESIGN 4.7).  Bit-exact results, and the per-query error bound of the exactness guard holds on its raw scores."""
     X, Q = _make(40000, d, 150, kind, 21)
     idx = vdb.FlatIndex(d, metric, 0)
-    idx.set_option("panel_layout", 2)
     idx.add(X, id_base=5)
+    assert idx.stats()["scan_shape"] == 16
     for k in (1, 10, 37):
         D, I = idx.search(Q, k)
         Do, Io = oracle.knn(X, Q, k, metric, id_base=5)

@@ -36,13 +36,11 @@ __global__ __launch_bounds__(64) void debug_scores_kernel(const half8 *panels, c
     }
 }
 
-// p16 layout: one wave = one 16x16 score tile, the MFMA sequence of scan16_kernel
-template <int KS_T>
+// p16 layout (D > 128): one wave = one 16x16 score tile, the MFMA sequence of scan16_kloop_kernel (KS 32-dim k-steps)
 __global__ __launch_bounds__(64) void debug_scores16_kernel(const half8 *panels, const float *bias, const half8 *qpanels,
                                                             const QueryBatchInfo *info, int64_t tile0, int64_t ntiles,
                                                             int64_t nq, int64_t row0, int64_t nrows, int64_t N,
-                                                            float *out, int ks_rt) {
-    const int KS = KS_T ? KS_T : ks_rt;       // KS_T == 0: run-time k-step count (the K-loop path, D > 128)
+                                                            float *out, int KS) {
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int64_t tile = tile0 + blockIdx.x;
     const int64_t qb = blockIdx.y;
@@ -70,6 +68,42 @@ __global__ __launch_bounds__(64) void debug_scores16_kernel(const half8 *panels,
     }
 }
 
+// layout "x16" (D <= 128): one wave = one 32-row tile x one 16-query block, the MFMA sequence of scan_x16_body's mfma_phase
+// (KS2 32-dim k-steps) for each of the tile's two 16-row blocks rb.  Accumulator register i of lane l: query 16 qb + (l & 15),
+// corpus row 512 s + 128 (l >> 4) + 8 t + 4 rb + i (build_panels_kernel).
+__global__ __launch_bounds__(64) void debug_scores_x16_kernel(const half8 *panels, const float *bias, const half8 *qpanels,
+                                                              const QueryBatchInfo *info, int64_t tile0, int64_t ntiles,
+                                                              int64_t nq, int64_t row0, int64_t nrows, int64_t N,
+                                                              float *out, int KS2) {
+    const int lane = threadIdx.x & 63, g = lane >> 4;
+    const int64_t tile = tile0 + blockIdx.x;
+    const int64_t qb = blockIdx.y;
+    if (tile >= tile0 + ntiles) return;
+    const float cs = info->cs;
+    const int64_t span = tile / kTilesPerSpan;
+    const int t = (int)(tile - span * kTilesPerSpan);
+    const int64_t q = qb * 16 + (lane & 15);
+    for (int rb = 0; rb < 2; ++rb) {
+        const int64_t rbase = span * kSpanRows + (int64_t)g * 128 + 8 * t + 4 * rb;
+        float4v acc;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {      // (the scan's LDS bias staging: pad rows start from kPadBias)
+            const float bv = bias[rbase + i];
+            acc[i] = (bv >= 0.9e38f) ? kPadBias : bv * cs;
+        }
+        for (int ks2 = 0; ks2 < KS2; ++ks2) {
+            const half8 af = panels[((size_t)tile * 2 * KS2 + 2 * ks2 + rb) * 64 + lane];
+            const half8 bf = qpanels[((size_t)qb * KS2 + ks2) * 64 + lane];
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t row = rbase + i;
+            if (q < nq && row >= row0 && row < row0 + nrows && row < N) out[(size_t)q * nrows + (row - row0)] = acc[i];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -80,8 +114,9 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
         auto *h = check(hh);
         if (h->multi) multi_unsupported("vdb_debug_scan_scores");
         if (!h->built || !h->scan_ok || h->panels_streamed || !h->panels.p) throw Error(VDB_ERR_STATE, "scan copy not available for this index");
-        if (h->ksteps > kMaxKSteps && !h->tile16)
-            throw Error(VDB_ERR_UNSUPPORTED, "debug scores for D > 128 need the p16 panel layout");
+        // panel layouts with a kernel here: p16 (D > 128), "x16" and the 32x32 form (D <= 128)
+        const bool t32 = !h->tile16 && !h->x16;
+        if (t32 && h->ksteps > kMaxKSteps) throw Error(VDB_ERR_UNSUPPORTED, "debug scores for D > 128 need the p16 panel layout");
         if (nq <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > h->N) throw Error(VDB_ERR_INVALID, "bad range");
         set_device(h->device);
         hipStream_t st = nullptr;
@@ -100,30 +135,23 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
         query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq.as<float>(), total, info.as<QueryBatchInfo>(),
             FinalizeArgs{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0});
         const int64_t threads = (Qpad / 32) * h->ksteps * 64;
-        if (h->tile16)
-            build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq.as<float>(), nq, Dm, h->ksteps / 2, Qpad / 16, info.as<QueryBatchInfo>(), qpanels.as<half8>());
-        else
+        if (t32)
             build_qpanels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq.as<float>(), nq, Dm, h->D4, h->ksteps, Qpad / 32, info.as<QueryBatchInfo>(), qpanels.as<half8>());
+        else    // (p16 and "x16" take the same B fragments: [q / 16][32-dim k-step][lane])
+            build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq.as<float>(), nq, Dm, h->ksteps / 2, Qpad / 16, info.as<QueryBatchInfo>(), qpanels.as<half8>());
         EpsArgs ea{dq.as<float>(), nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
                    h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info.as<QueryBatchInfo>(),
                    eps.as<float>()};
         query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
-        if (h->tile16) {
-            const int64_t sp0 = row0 / kSpanRows16, sp1 = (row0 + nrows + kSpanRows16 - 1) / kSpanRows16;
-            const int64_t tile0 = sp0 * kTilesPerSpan16, ntiles = (sp1 - sp0) * kTilesPerSpan16;
-            dim3 grid((unsigned)ntiles, (unsigned)(Qpad / 16));
-            if (h->ksteps == 4)
-                debug_scores16_kernel<2><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), 0);
-            else if (h->ksteps == 8)
-                debug_scores16_kernel<4><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), 0);
-            else
-                debug_scores16_kernel<0><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
-        }
-        const int64_t sp0 = row0 / kSpanRows, sp1 = (row0 + nrows + kSpanRows - 1) / kSpanRows;
-        const int64_t tile0 = sp0 * kTilesPerSpan, ntiles = (sp1 - sp0) * kTilesPerSpan;
-        dim3 grid((unsigned)ntiles, (unsigned)(Qpad / 32));
-        if (h->tile16) {
-        } else if (h->ksteps == 4)
+        const int span_rows = h->tile16 ? kSpanRows16 : kSpanRows, tps = h->tile16 ? kTilesPerSpan16 : kTilesPerSpan;
+        const int64_t sp0 = row0 / span_rows, sp1 = (row0 + nrows + span_rows - 1) / span_rows;
+        const int64_t tile0 = sp0 * tps, ntiles = (sp1 - sp0) * tps;
+        const dim3 grid((unsigned)ntiles, (unsigned)(Qpad / (t32 ? 32 : 16)));
+        if (h->tile16)
+            debug_scores16_kernel<<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
+        else if (h->x16)
+            debug_scores_x16_kernel<<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
+        else if (h->ksteps == 4)
             debug_scores_kernel<4><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());
         else
             debug_scores_kernel<8><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void ivf_kloop_scan_kernel(IvfKloopArgs a) 
     }
 
     float4v acc[HTW][CB];
-    half8 bq[CB][2];          // B fragments of the current K-step, reloaded in place (see scan_kloop_kernel)
+    half8 bq[CB][2];          // B fragments of the current K-step, reloaded in place (see scan16_kloop_kernel)
     const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16 *>(a.qrows), 0, 0x7fffffff, 0x00020000);
     auto load_b = [&](int kk, int ks) {
 #pragma unroll

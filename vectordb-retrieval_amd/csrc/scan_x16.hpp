@@ -3,8 +3,8 @@
 // The fp16 twin of scan_i8x16.hpp (read that header first: same tiles, same row mapping, same bins): in the production loop
 // structure -- 4-tile stages by LDS-DMA, one barrier per stage, the two waves of a SIMD in anti-phase -- the 4-pass 16x16x32
 // instruction delivers 1.17x (D = 128) / 1.19x (D = 64) the FLOP/s of the 8-pass 32x32x16 one with the same oct select
-// (scripts/microbench/mfma_f16_staged.hip, profiles/r04_mfma_f16_staged.txt).  scan16_kernel (scan16.hpp), the earlier
-// 16x16x32 kernel for D <= 128, lost to scan_kernel because a 16-row tile gives a lane one QUAD per column block (6 vector
+// (scripts/microbench/mfma_f16_staged.hip, profiles/r04_mfma_f16_staged.txt).  The earlier 16x16x32 kernel for D <= 128, on
+// 16-row tiles (now retired), lost to scan_kernel because a 16-row tile gives a lane one QUAD per column block (6 vector
 // operations per 4 scores); here a 32-row tile is two 16-row blocks whose rows interleave in fours, so the lane's 4 + 4
 // accumulator registers are 8 consecutive corpus rows -- one oct, 7 operations per 8 scores.
 //   panels[tile][v = 2 ks2 + rb][lane][8 x fp16]: lane holds MFMA row m = lane & 15 of block rb -- corpus row

@@ -140,81 +140,42 @@ void launch_scan_k(int variant, ScanArgs &sa, int nchunks, int64_t Qpad, hipStre
 // option "f16_group" = 4
 bool f16_octs(const vdb_index_s *h, int direct_rows) {
     if (h->x16) return !direct_rows;  // (layout "x16": octs; direct-bin mode -- large k, the refine outweighs the scan -- takes the quads of the two blocks)
-    return h->f16_group == 8 && !direct_rows && !h->tile16 && h->ksteps <= kMaxKSteps && (h->scan_variant == 0 || h->scan_variant == 6);
+    return h->f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps && (h->scan_variant == 0 || h->scan_variant == 6);
 }
 
 inline int st_tiles_of(const vdb_index_s *h) { return h->f16_stage_tiles ? h->f16_stage_tiles : (h->ksteps == 4 ? 8 : 4); }
 
 void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int direct_rows = 0, int nw = 8) {
     const int bt = direct_rows ? direct_rows / 16 : 16;       // 32-row-tile layout: tiles per level-1 bin
-    if (h->ksteps > kMaxKSteps) {  // D > 128
-        // scan_variant: 0 = 4 row tiles x 2 query blocks per wave (512-query tiles), 1 = 8 x 1 (256-query tiles);
+    if (h->ksteps > kMaxKSteps) {  // D > 128: p16 panels, 512-query tiles
         // option kloop_qgroup = query tiles per group of the block order (0 -> default)
-        const bool wide = h->tile16 || (h->scan_variant != 1 && h->scan_variant != 4);   // 512-query tiles
-        sa.nqtiles = (int)(Qpad / (wide ? 512 : 256));
-        int qgroup = h->kloop_qgroup > 0 ? h->kloop_qgroup : (wide ? 4 : sa.nqtiles);
+        sa.nqtiles = (int)(Qpad / 512);
+        int qgroup = h->kloop_qgroup > 0 ? h->kloop_qgroup : 4;
         qgroup = std::min(qgroup, sa.nqtiles);
         const unsigned ngroups = (unsigned)((sa.nqtiles + qgroup - 1) / qgroup);
         const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * ngroups * (unsigned)qgroup;
         const ScanKloopExtra ex{h->ksteps, qgroup};
-        if (h->tile16 && direct_rows) {      // finer level-1 bins (production schedule only)
+        if (direct_rows) {      // finer level-1 bins (production schedule only)
             if (direct_rows == 128) scan16_kloop_kernel<0, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
             else scan16_kloop_kernel<0, 2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
             VDB_HIP(hipGetLastError());
             return;
         }
-        if (h->tile16) {
-            switch (h->scan_variant) {
-#ifdef VDB_ABLATIONS
-                case 2: scan16_kloop_kernel<0, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-                case 7: scan16_kloop_kernel<2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no MFMA
-                case 8: scan16_kloop_kernel<3, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no traffic
-                case 9: scan16_kloop_kernel<4, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no epilogue
-#endif
-                default:
-                    if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && !h->small_batch_off)
-                        scan16_kloop_kernel<0, 3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                    else if (sa.nq_valid > 0 && sa.nq_valid < 64 && !h->small_batch_off)
-                        scan16_kloop_kernel<0, 2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                    else
-                        scan16_kloop_kernel<0, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                    break;
-            }
-            VDB_HIP(hipGetLastError());
-            return;
-        }
         switch (h->scan_variant) {
 #ifdef VDB_ABLATIONS
-            case 1: scan_kloop_kernel<0, 8, 1, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-            case 2: scan_kloop_kernel<0, 4, 2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-            case 3: scan_kloop_kernel<0, 4, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-            case 4: scan_kloop_kernel<0, 4, 2, 1, true, 4><<<dim3(grid), dim3(256), 0, st>>>(sa, ex); break;
-            case 9: scan_kloop_kernel<4, 4, 2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no epilogue
-            case 7: scan_kloop_kernel<2, 4, 2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no MFMA
-            case 8: scan_kloop_kernel<3, 4, 2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no traffic
+            case 2: scan16_kloop_kernel<0, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
+            case 7: scan16_kloop_kernel<2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no MFMA
+            case 8: scan16_kloop_kernel<3, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no traffic
+            case 9: scan16_kloop_kernel<4, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no epilogue
 #endif
-            default: scan_kloop_kernel<0, 4, 2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-        }
-    } else if (h->tile16) {            // D <= 128 on p16 panels
-        sa.nqtiles = (int)(Qpad / 512);
-        const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-        const int v = h->scan_variant;
-        (void)v;
-        if (h->ksteps == 4) {
-#ifdef VDB_ABLATIONS
-            if (v == 7) scan16_kernel<2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else if (v == 8) scan16_kernel<2, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else
-#endif
-            scan16_kernel<2, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
-        } else {
-#ifdef VDB_ABLATIONS
-            if (v == 7) scan16_kernel<4, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else if (v == 8) scan16_kernel<4, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else if (v == 1) scan16_kernel<4, 4><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else
-#endif
-            scan16_kernel<4, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
+            default:
+                if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && !h->small_batch_off)
+                    scan16_kloop_kernel<0, 3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+                else if (sa.nq_valid > 0 && sa.nq_valid < 64 && !h->small_batch_off)
+                    scan16_kloop_kernel<0, 2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+                else
+                    scan16_kloop_kernel<0, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+                break;
         }
     } else if (h->x16) {               // D <= 128 on layout "x16" (scan_x16.hpp)
         [[maybe_unused]] const bool stamped = h->scan_variant == 6;

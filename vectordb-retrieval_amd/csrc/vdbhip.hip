@@ -244,7 +244,6 @@ struct vdb_index_s {
     int64_t last_upload_blocks = 0;          // blocks of the last host upload (vdb_stats: upload_blocks)
     // options
     int force_path = 0, timing = 0, list_cap = 0, scan_variant = 0, select_variant = 0, spc_override = 0, kloop_qgroup = 0;
-    int layout_override = 0;                 // option "panel_layout": 1 = keep 32-row tiles for D > 128 (A/B runs)
     bool small_clear_pending = false;        // search_device_impl left the clearing of ws.small to the first batch (serving-shaped calls)
     bool small_is_clean = false;             // ws.small was cleared for this call and no batch has used it yet
     bool small_preset = false;               // coarse quantizer of an IVF index: the parent has just cleared ws.small (it lives in
@@ -476,26 +475,24 @@ void build_rows_i8(vdb_index_s *h, hipStream_t st) {
 void graph_reset(vdb_index_s *h);
 
 // layout "x16" for the scan copies of a D <= 128 flat index, unless an option asks for what only the 32-row kernels have
-// (quads as the candidate group, the A/B schedules and ablations behind scan_variant, panel_layout 1)
+// (quads as the candidate group, the A/B schedules and ablations behind scan_variant)
 bool x16_wanted(const vdb_index_s *h) {
-    return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->layout_override != 1 && h->f16_group == 8 && h->i8_group == 8 &&
-           h->scan_variant == 0;
+    return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->f16_group == 8 && h->i8_group == 8 && h->scan_variant == 0;
 }
 
 // everything derived from the h->N rows in h->x32: statistics, scan copies, biases
 void build_derived(vdb_index_s *h, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
     const int64_t n = h->N;
-    // D > 128 (K-loop scan): p16 panels for v_mfma_f32_16x16x32_f16; D <= 128: 32-row tiles (scan_kernel, dense path)
-    // (panel_layout 2 = p16 for D <= 128 too, when the corpus is too large for the dense small-corpus kernel)
+    // D > 128 (K-loop scan): p16 panels for v_mfma_f32_16x16x32_f16; D <= 128: 32-row tiles, in layout "x16" above the dense
+    // path's rows (x16_wanted), else in the 32x32 form of scan_kernel and the dense path
     // (D > 128 with at most 2048 rows -- an IVF coarse quantizer over embeddings: 32-row tiles, served by the dense path's K-loop
     //  scores + register select instead of the float64 exhaustive kernel, search_flat.inc)
     constexpr int64_t kDenseRegRows = 2048;
-    h->tile16 = h->layout_override != 1 && ((h->ksteps > kMaxKSteps && (n > kDenseRegRows || h->layout_override == 2)) ||
-                                            (h->layout_override == 2 && n > kDenseMaxRows));
+    h->tile16 = h->ksteps > kMaxKSteps && n > kDenseRegRows;
     const int64_t span_rows = h->tile16 ? kSpanRows16 : kSpanRows;
     h->Npad = (n + span_rows - 1) / span_rows * span_rows;
-    h->x16 = x16_wanted(h) && !h->tile16 && h->Npad > kDenseMaxRows;
+    h->x16 = x16_wanted(h) && h->Npad > kDenseMaxRows;
     h->scan_ok = false;
     if (n == 0) {
         h->built = true;
@@ -1096,7 +1093,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         set_device(h->device);
         vdb_stats_t s = h->last;
         s.ndevices = 1;
-        s.scan_shape = (!h->scan_ok || h->ksteps > kMaxKSteps || h->N == 0) ? 0 : h->x16 ? 16 : h->tile16 ? 16 : 32;
+        s.scan_shape = (!h->scan_ok || h->ksteps > kMaxKSteps || h->N == 0) ? 0 : h->x16 ? 16 : 32;
         s.ntotal = h->N;
         s.dim = h->dim;
         s.metric = h->metric;
@@ -1213,9 +1210,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         } else if (k == "timing") {  // (re)starts the recording window
             h->timing = value != 0;
             h->ev_used = 0;
-        } else if (k == "panel_layout") {   // 0 auto, 1 = 32-row tiles for every D, 2 = p16 for every D (next add)
-            if (value != 0 && value != 1 && value != 2) throw Error(VDB_ERR_INVALID, "panel_layout must be 0, 1 or 2");
-            h->layout_override = (int)value;
         } else if (k == "stream_panels") {  // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
             if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "stream_panels must be 0 or 1");
             h->stream_panels_opt = (int)value;
