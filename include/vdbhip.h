@@ -73,7 +73,8 @@ typedef struct vdb_stats_s {
     float last_total_ms;       /* same for the whole device pipeline */
     int32_t nlist;             /* IVF: number of inverted lists (0 = flat index) */
     int32_t nprobe;
-    int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate) */
+    int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate),
+                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 index (f32 accumulate) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists) */
@@ -191,6 +192,31 @@ int vdb_ivf_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, f
  * partial top-k among the probed lists, same layout and merge as vdb_search_partial_device */
 int vdb_ivf_search_partial_device(vdb_handle h, const float *q_dev, int64_t nq, int k, double *keys_dev,
                                   int64_t *ids_dev, void *stream);
+
+/* ---- IVF<nlist>,SQ8 -- replaces faiss.index_factory(d, "IVF<nlist>,SQ8", metric) (IndexIVFScalarQuantizer, QT_8bit,
+ *      RS_minmax, by_residual; the reference's `ivf_sq8` config) ------------------------------------------------------
+ * One byte per dimension: the index keeps the codes, the ids and a list id per row, and NO float32 rows and no fp16 / int8
+ * scan copies.  Every step is float32, rounded as written (c_l = centroid of the row's list):
+ *   train   r = x - c_l over the training rows (all of them when n <= 100 000, else the rows floor(i * n / 100 000));
+ *           vmin[d] = min r[d];  vdiff[d] = max r[d] - vmin[d]
+ *   encode  u = vdiff[d] != 0 ? (r[d] - vmin[d]) / vdiff[d] : 0;  u = clamp(u, 0, 1);  code = (uint8) trunc(255 * u)
+ *   decode  x^[d] = c_l[d] + (vmin[d] + ((code + 0.5f) / 255.0f) * vdiff[d])
+ * A search returns, bit for bit, the IVF-Flat result over the float32 rows x^ under the same lists (canonical float64
+ * arithmetic above): every exact kernel (list scan, refine, flagged-query scan) decodes x^ from the codes.  D <= 128: batches
+ * the list-major path serves take the MFMA list scan on fp16 panels converted from the codes per batch (workspace; they equal
+ * IVF-Flat's panels of x^, so the same error bound holds; vdb_stats.scan_dtype = 2).  D > 128: the exact list scan.
+ * Not available (VDB_ERR_UNSUPPORTED): the codec on a vdb_create_multi handle, option "graph", options "int8_only" /
+ * "stream_panels", vdb_add / vdb_add_device (rows enter through vdb_ivf_add / vdb_ivf_add_assigned only). */
+/* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8.  Only before centroids or rows exist (VDB_ERR_STATE after) */
+int vdb_ivf_set_codec(vdb_handle h, int codec);
+/* SQ8: vdb_ivf_train trains the centroids and then the ranges on the same rows; this call trains the ranges only, against
+ * the installed centroids (vdb_ivf_set_centroids).  New ranges drop the rows encoded under the old ones at the next add. */
+int vdb_ivf_sq8_train_ranges(vdb_handle h, const float *x_host, int64_t n);
+/* inject / read the ranges, float32 (dim) each -- persistence and tests */
+int vdb_ivf_sq8_set_ranges(vdb_handle h, const float *vmin_host, const float *vdiff_host);
+int vdb_ivf_sq8_get_ranges(vdb_handle h, float *vmin_host, float *vdiff_host);
+/* codes of an SQ8 index, uint8 (ntotal, dim), in id (insertion) order */
+int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
 
 /* Sizes the search workspace for batches of up to nq queries and top-k NOW instead of inside the first search (works on
  * flat and IVF handles after add): one untimed search whose queries are corpus rows.  The reference times its very first

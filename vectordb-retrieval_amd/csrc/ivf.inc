@@ -98,6 +98,8 @@ void ivf_csr_build(vdb_index_s *h, const DevBuf &dI, int64_t n, int nlist, DevBu
     VDB_HIP(hipMemcpy(doff.p, offsets_host.data(), ((size_t)nlist + 1) * 8, hipMemcpyHostToDevice));
 }
 
+#include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
+
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
 // 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
 // (four 64-row bins) or, for lists of thousands of rows, 1024 rows (four 256-row bins).
@@ -158,7 +160,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
     IndexStats hs;
     VDB_HIP(hipMemcpy(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost));
     h->corpus_fp16_exact = hs.not_fp16_exact == 0;
-    h->i8_ok = h->i8_ok && !h->tile16;
+    h->i8_ok = h->i8_ok && !h->tile16 && h->ivf_codec == 0;   // (an SQ8 index keeps no int8 copies)
     if (h->i8_ok) {      // byte-valued rows: int8 copy of the same panel space (scan_i8.hpp)
         h->i8_ks = h->dim <= 64 ? 2 : 4;
         h->panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
@@ -360,6 +362,16 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
 
     ScanArgs sa{};
     sa.panels = h->panels.as<half8>();
+    if (sq8(h)) {      // SQ8: the fp16 panels of the whole panel space, converted from the codes for this batch (workspace)
+        const int64_t ntiles = h->ivf_pspans * kIvfTilesPerSpan;
+        ws.sq8_panels.reserve((size_t)ntiles * h->ksteps * 64 * sizeof(half8));
+        const int64_t threads = ntiles * h->ksteps * 64;
+        ivf_sq8_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
+            sq8_rows(h), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->ivf_span_row0.as<int32_t>(), h->ivf_span_valid.as<int32_t>(),
+            ws.sq8_panels.as<half8>());
+        VDB_HIP(hipGetLastError());
+        sa.panels = ws.sq8_panels.as<half8>();
+    }
     sa.bias = h->bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -520,6 +532,7 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
 
     RefineCommon rc{h->x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, h->ivf_ids.as<int64_t>()};
     rc.info = info;
+    if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
     if (use_i8 && h->rows8.p) {
         rc.X8 = h->rows8.as<signed char>();
         rc.rowstat = h->rowstat8.as<int>();
@@ -646,6 +659,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         S = std::min<int64_t>(S, cap);
         IvfScanArgs a{};
         a.c = RefineCommon{h->x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, h->ivf_ids.as<int64_t>()};
+        if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
         a.offsets = h->ivf_offsets.as<int64_t>();
         a.probes = h->ivf_probe_i.as<int64_t>();
         a.nq = nb;
@@ -791,6 +805,85 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         }
         ivf_install_centroids(h, cent.data(), nlist);
         h->ivf_built = false;
+        if (sq8(h)) sq8_train_ranges(h, x_host, n);      // SQ8: then the residual ranges, against these centroids
+    });
+}
+
+int vdb_ivf_set_codec(vdb_handle hh, int codec) {
+    return guarded([&] {
+        auto *h = check(hh);
+        ivf_require(codec == 0 || codec == 1, VDB_ERR_INVALID, "codec must be 0 (Flat) or 1 (SQ8)");
+        if (h->multi) {
+            if (codec == 1) multi_unsupported("the SQ8 codec");
+            return;
+        }
+        ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
+        if (codec == 1) {
+            ivf_require(!h->graph_mode, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");
+            ivf_require(!h->int8_only_opt && !h->stream_panels_opt, VDB_ERR_UNSUPPORTED,
+                        "options 'int8_only' and 'stream_panels' do not combine with the SQ8 codec");
+        }
+        h->ivf_codec = codec;
+    });
+}
+
+int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (h->multi) multi_unsupported("vdb_ivf_sq8_train_ranges");
+        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
+        ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
+        set_device(h->device);
+        sq8_train_ranges(h, x_host, n);
+        h->ivf_built = false;                           // (rows encoded under the old ranges are dropped by the next add)
+    });
+}
+
+int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *vdiff_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (h->multi) multi_unsupported("vdb_ivf_sq8_set_ranges");
+        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
+        for (int d = 0; d < h->dim; ++d)
+            ivf_require(std::isfinite(vmin_host[d]) && std::isfinite(vdiff_host[d]) && vdiff_host[d] >= 0.f, VDB_ERR_INVALID,
+                        "SQ8 ranges must be finite with vdiff >= 0");
+        h->sq8_vmin.assign(vmin_host, vmin_host + h->dim);
+        h->sq8_vdiff.assign(vdiff_host, vdiff_host + h->dim);
+        h->sq8_ranges = true;
+        h->ivf_built = false;
+    });
+}
+
+int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (h->multi) multi_unsupported("vdb_ivf_sq8_get_ranges");
+        ivf_require(sq8(h) && h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
+        ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
+        memcpy(vmin_host, h->sq8_vmin.data(), (size_t)h->dim * sizeof(float));
+        memcpy(vdiff_host, h->sq8_vdiff.data(), (size_t)h->dim * sizeof(float));
+    });
+}
+
+int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (h->multi) multi_unsupported("vdb_ivf_get_codes");
+        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
+        ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
+        if (h->N == 0) return;
+        set_device(h->device);
+        const int Dm = h->dim, D4 = h->D4;
+        std::vector<unsigned char> c((size_t)h->N * D4);
+        std::vector<int64_t> ids((size_t)h->N);
+        VDB_HIP(hipDeviceSynchronize());
+        VDB_HIP(hipMemcpy(c.data(), h->sq8_codes.p, c.size(), hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(ids.data(), h->ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
+            memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * Dm, &c[(size_t)r * D4], (size_t)Dm);
     });
 }
 
@@ -806,6 +899,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
     return guarded([&] {
         auto *h = check(hh);
         if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
+        if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
         const bool append = h->ivf_built && h->N > 0;
@@ -974,6 +1068,9 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
             if (h->int8_only)     // (no float32 rows: the int8 rows, converted)
                 rows_i8_to_float_kernel<<<dim3((unsigned)((m * h->dim + 255) / 256)), dim3(256), 0, st>>>(
                     h->rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, ws.stage_q.as<float>() + (size_t)q0 * h->dim);
+            else if (sq8(h))      // (codes: the decoded rows x^)
+                sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((m * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
+                    sq8_rows(h), m, h->dim, h->D4, h->dim, ws.stage_q.as<float>() + (size_t)q0 * h->dim);
             else
             VDB_HIP(hipMemcpy2DAsync(ws.stage_q.as<char>() + (size_t)q0 * row, row, h->x32.p, (size_t)h->D4 * sizeof(float), row,
                                      (size_t)m, hipMemcpyDeviceToDevice, st));

@@ -10,6 +10,21 @@
 
 namespace vdb {
 
+// the rows of an IVF<nlist>,SQ8 index (ivf_sq8.hpp, include/vdbhip.h): codes [N][D4] in list order (padding 0), the list
+// of every list-order row, centroids [nlist][D4] and {vmin, vdiff} [D4] each, zero padded (a padding dimension decodes to 0)
+struct Sq8Rows {
+    const unsigned char *codes = nullptr;
+    const int32_t *list = nullptr;
+    const float *cent = nullptr;
+    const float *vmin = nullptr;
+    const float *vdiff = nullptr;
+};
+
+// x^[d] = c_l[d] + (vmin[d] + ((code + 0.5f) / 255.0f) * vdiff[d]), float32, rounded as written (no contraction)
+__device__ __forceinline__ float sq8_decode(unsigned code, float c, float vmin, float vdiff) {
+    return c + (vmin + (((float)code + 0.5f) / 255.0f) * vdiff);
+}
+
 struct RefineCommon {
     const float *X;     // [N][D4] float32 rows, zero padded to a multiple of 4 dims
     const float *Q;     // [nq][D4]
@@ -29,6 +44,8 @@ struct RefineCommon {
     const signed char *Q8 = nullptr;
     int x8_pitch = 0, cx = 0, D = 0;
     const QueryBatchInfo *info = nullptr;
+    // IVF<nlist>,SQ8 (ivf_sq8.inc): X == nullptr and sq8.codes set -- the rows are 8-bit codes, decoded to x^ in float32
+    Sq8Rows sq8{};
 };
 
 typedef int refine_int4 __attribute__((ext_vector_type(4)));
@@ -96,10 +113,44 @@ __device__ __forceinline__ uint64_t exact_key_i8(const signed char *__restrict__
     return sortable_u64(metric == 0 ? acc : -acc);
 }
 
-// key of corpus row `row`: from the float32 rows, or (c.X == nullptr: int8-only index) from the int8 row copy
+// The same key from the codes of an SQ8 index: x^ decoded in float32, then the identical float64 chain -- the key of the
+// float32 row x^.  (4 dims per step, 4 steps in flight whatever U: the decode needs four operands per dimension.)
+__device__ __forceinline__ uint64_t sq8_key(const Sq8Rows &s, int64_t row, const float *__restrict__ q, int D4, int metric) {
+    const unsigned *cw = reinterpret_cast<const unsigned *>(s.codes + (size_t)row * D4);
+    const float4 *cv = reinterpret_cast<const float4 *>(s.cent + (size_t)s.list[row] * D4);
+    const float4 *mv = reinterpret_cast<const float4 *>(s.vmin);
+    const float4 *dv = reinterpret_cast<const float4 *>(s.vdiff);
+    const float4 *qv = reinterpret_cast<const float4 *>(q);
+    double acc = 0.0;
+#pragma unroll 4
+    for (int i = 0; i < D4 / 4; ++i) {
+        const unsigned w = cw[i];
+        const float4 c = cv[i], m = mv[i], d = dv[i], b = qv[i];
+        const double x0 = (double)sq8_decode(w & 0xffu, c.x, m.x, d.x);
+        const double x1 = (double)sq8_decode((w >> 8) & 0xffu, c.y, m.y, d.y);
+        const double x2 = (double)sq8_decode((w >> 16) & 0xffu, c.z, m.z, d.z);
+        const double x3 = (double)sq8_decode(w >> 24, c.w, m.w, d.w);
+        if (metric == 0) {
+            double t;
+            t = x0 - (double)b.x; acc = fma(t, t, acc);
+            t = x1 - (double)b.y; acc = fma(t, t, acc);
+            t = x2 - (double)b.z; acc = fma(t, t, acc);
+            t = x3 - (double)b.w; acc = fma(t, t, acc);
+        } else {
+            acc = fma((double)b.x, x0, acc);
+            acc = fma((double)b.y, x1, acc);
+            acc = fma((double)b.z, x2, acc);
+            acc = fma((double)b.w, x3, acc);
+        }
+    }
+    return sortable_u64(metric == 0 ? acc : -acc);
+}
+
+// key of corpus row `row`: from the float32 rows, or (c.X == nullptr) from the SQ8 codes or the int8 row copy (int8-only index)
 template <int U = 16>
 __device__ __forceinline__ uint64_t row_key(const RefineCommon &c, int64_t row, const float *__restrict__ q) {
     if (c.X) return exact_key<U>(c.X + (size_t)row * c.D4, q, c.D4, c.metric);
+    if (c.sq8.codes) return sq8_key(c.sq8, row, q, c.D4, c.metric);
     return exact_key_i8<U>(c.X8 + (size_t)row * c.x8_pitch, c.cx, q, c.D4, c.metric);
 }
 

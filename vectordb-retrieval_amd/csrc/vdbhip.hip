@@ -24,6 +24,7 @@
 #include "ivf.hpp"
 #include "ivf_mfma.hpp"
 #include "ivf_kloop.hpp"
+#include "ivf_sq8.hpp"
 #include "dense.hpp"
 
 using namespace vdb;
@@ -149,8 +150,9 @@ struct Workspace {
     DevBuf dense;            // nq x Npad raw scores of the small-corpus path
     DevBuf pkeys, pids;      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q, stage_d, stage_i;  // host-API staging
+    DevBuf sq8_panels;       // IVF-SQ8: the fp16 panels converted from the codes for the current batch
     size_t bytes() const {
-        const DevBuf *all[] = {&qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
+        const DevBuf *all[] = {&sq8_panels, &qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
                                &rescan, &counts, &fallback, &fb_list, &fb_done, &small, &pkeys, &pids, &stage_q, &stage_d,
                                &stage_i, &dense};
         size_t s = 0;
@@ -158,7 +160,7 @@ struct Workspace {
         return s;
     }
     void release() {
-        DevBuf *all[] = {&qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
+        DevBuf *all[] = {&sq8_panels, &qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
                          &rescan, &counts, &fallback, &fb_list, &fb_done, &small, &pkeys, &pids, &stage_q, &stage_d, &stage_i,
                          &dense};
         for (auto b : all) b->release();
@@ -288,6 +290,13 @@ struct vdb_index_s {
     // arrival counters of the flagged-query pass].  Both ws.small are views into it (DevBuf::borrow).
     DevBuf ivf_zero, ivf_slot_off, ivf_list_item0,
         ivf_item_list, ivf_item_slot0, ivf_item_bin0, ivf_plan, ivf_slot_of;
+    // codec of the inverted lists (vdb_ivf_set_codec): 0 Flat (float32 rows + scan copies) | 1 SQ8 (ivf_sq8.inc: 8-bit codes
+    // of the residuals, no float32 rows, no scan copies)
+    int ivf_codec = 0;
+    bool sq8_ranges = false;                 // vmin / vdiff trained or set
+    std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
+    DevBuf sq8_codes, sq8_list;              // [N][D4] codes and the list of every row, both in list order
+    DevBuf sq8_cent, sq8_param;              // centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
 };
 
 namespace {
@@ -844,7 +853,8 @@ int vdb_destroy(vdb_handle h) {
         DevBuf *all[] = {&h->x32, &h->xnorm2, &h->panels, &h->slab, &h->bias, &h->stats, &h->panels8, &h->bias8, &h->rows8, &h->rowstat8, &h->ivf_offsets, &h->ivf_ids,
                          &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
                          &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0, &h->ivf_item_list,
-                         &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of};
+                         &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of,
+                         &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param};
         for (auto b : all) b->release();
         graph_reset(h);
         if (h->graph_ev) (void)hipEventDestroy(h->graph_ev);
@@ -868,6 +878,7 @@ int vdb_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
         auto *h = check(hh);
         if (n > 0 && !x_host) throw Error(VDB_ERR_INVALID, "null corpus pointer");
         if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, false, nullptr);
+        if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
         set_device(h->device);
         append_rows(h, x_host, false, n, id_base, nullptr);
     });
@@ -890,7 +901,8 @@ int vdb_reset(vdb_handle hh) {
         // faiss.Index.reset frees its storage: so do we (rows, scan copies, CSR arrays; the workspace and an IVF index's
         // centroids stay) -- a caller that resets a 38 GB shard to load another corpus gets the memory back
         DevBuf *rows[] = {&h->x32, &h->xnorm2, &h->panels, &h->slab, &h->bias, &h->panels8, &h->bias8, &h->rows8, &h->rowstat8,
-                          &h->ivf_offsets, &h->ivf_ids, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid};
+                          &h->ivf_offsets, &h->ivf_ids, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
+                          &h->sq8_codes, &h->sq8_list};
         for (auto b : rows) b->release();
     });
 }
@@ -900,6 +912,7 @@ int vdb_add_device(vdb_handle hh, const float *x_dev, int64_t n, int64_t id_base
         auto *h = check(hh);
         if (n > 0 && !x_dev) throw Error(VDB_ERR_INVALID, "null corpus pointer");
         if (h->multi) return multi_add(h, x_dev, true, n, id_base, as_stream(stream), false, nullptr);
+        if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
         set_device(h->device);
         append_rows(h, x_dev, true, n, id_base, as_stream(stream));
     });
@@ -1103,7 +1116,8 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         {   // IVF: the CSR arrays, the per-batch plan buffers and the coarse quantizer's own index and workspace
             const DevBuf *ivf[] = {&h->ivf_offsets, &h->ivf_ids, &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0,
                                    &h->ivf_span_row0, &h->ivf_span_valid, &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0,
-                                   &h->ivf_item_list, &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of};
+                                   &h->ivf_item_list, &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of,
+                                   &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param};
             for (auto b : ivf) s.bytes_resident += (int64_t)b->cap;
             if (h->ivf_zero.cap) s.bytes_resident -= (int64_t)h->ws.small.cap;      // (a view into ivf_zero: counted once)
             if (h->coarse)
@@ -1130,6 +1144,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
+        if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit codes
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;
@@ -1198,6 +1213,8 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (h->multi) return multi_set_option(h, key, value);
         const std::string k(key);
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
+        if (h->ivf_codec == 1 && value != 0 && (k == "graph" || k == "int8_only" || k == "stream_panels"))
+            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an SQ8 index");
         if (k == "graph") {
             if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "graph must be 0 or 1");
             h->graph_mode = (int)value;

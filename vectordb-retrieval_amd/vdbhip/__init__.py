@@ -8,7 +8,7 @@ from .plugin_api import (ALGORITHM_REGISTRY, INDEXER_REGISTRY, SEARCHER_REGISTRY
                          get_searcher_class, register_algorithm, register_indexer, register_searcher)
 from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher, rerank_candidates
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
-from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex
+from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
 from . import sharded
 from .sharded import HipShardedApproximateSearch, HipShardedExactSearch, shard_bounds
 
@@ -17,6 +17,7 @@ __all__ = [
     "CompositeAlgorithm", "IndexArtifact", "get_algorithm_instance", "get_indexer_class", "get_searcher_class",
     "register_algorithm", "register_indexer", "register_searcher", "HipExactSearch", "HipBruteForceIndexer",
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
-    "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "HipShardedExactSearch",
+    "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
+    "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",
 ]

@@ -72,6 +72,11 @@ SIGNATURES = {
     "vdb_ivf_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "vdb_ivf_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_ivf_search_partial_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_set_codec": (c_int, [c_void_p, c_int]),
+    "vdb_ivf_sq8_train_ranges": (c_int, [c_void_p, c_void_p, c_int64]),
+    "vdb_ivf_sq8_set_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_sq8_get_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_get_codes": (c_int, [c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),

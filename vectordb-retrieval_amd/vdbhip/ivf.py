@@ -1,8 +1,8 @@
-"""IVF-Flat on the MI355X behind the reference's three IVF entry points.
+"""IVF-Flat and IVF-SQ8 on the MI355X behind the reference's three IVF entry points.
 
   HipApproximateSearch   drop-in for ApproximateSearch        (src/algorithms/approximate_search.py:6-87)
-                         -- `index_type` keys of the form "IVF<nlist>,Flat" only (PQ/SQ codecs are out of scope,
-                         SURVEY 2 row 6); 'l2' -> squared L2, anything else -> raw inner product; no sign flips.
+                         -- `index_type` keys of the form "IVF<nlist>,Flat" or "IVF<nlist>,SQ8" (PQ codecs are out of
+                         scope); 'l2' -> squared L2, anything else -> raw inner product; no sign flips.
   HipIVFIndexer          drop-in for FaissFactoryIndexer / FaissIVFIndexer (modular.py:224-309)
                          -- cosine = normalise + inner product (:253-262), runtime `nprobe` (:269-275)
   HipIVFSearcher         drop-in for FaissSearcher on IVF artifacts (modular.py:393-449, 536-548)
@@ -26,13 +26,24 @@ from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact
                          register_algorithm, register_indexer, register_searcher)
 
 _IVF_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*Flat\s*$")
+_IVF_CODEC_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*(Flat|SQ8)\s*$")
 
 
 def parse_ivf_key(key: str) -> int:
+    """nlist of an "IVF<nlist>,Flat" key (the row-sharded HipShardedApproximateSearch serves Flat lists only)."""
     m = _IVF_KEY.match(str(key))
     if not m:
         raise ValueError(f"unsupported index key {key!r}: only 'IVF<nlist>,Flat' is implemented on the HIP backend")
     return int(m.group(1))
+
+
+def parse_index_key(key: str) -> Tuple[int, str]:
+    """(nlist, codec) of "IVF<nlist>,Flat" / "IVF<nlist>,SQ8" (codec "Flat" or "SQ8"); every other key raises ValueError."""
+    m = _IVF_CODEC_KEY.match(str(key))
+    if not m:
+        raise ValueError(f"unsupported index key {key!r}: only 'IVF<nlist>,Flat' and 'IVF<nlist>,SQ8' are implemented "
+                         "on the HIP backend")
+    return int(m.group(1)), m.group(2)
 
 
 class IVFFlatIndex:
@@ -146,6 +157,50 @@ class IVFFlatIndex:
         _ffi.check(self._lib.vdb_set_option(self._h, key.encode(), float(value)), build_time=True)
 
 
+class IVFSQ8Index(IVFFlatIndex):
+    """Device-resident IVF<nlist>,SQ8 index (replaces faiss.index_factory(d, "IVFn,SQ8", metric): IndexIVFScalarQuantizer
+    with 8-bit codes of the residuals, per-dimension min / max ranges).  One byte per dimension and no float32 rows; the
+    results are exact over the decoded rows (include/vdbhip.h).  `train` fits the centroids and then the ranges on the same
+    rows; `set_centroids` + `train_ranges` / `set_ranges` inject them instead.  One GPU only."""
+
+    def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0):
+        from .index import normalize_devices
+
+        if isinstance(normalize_devices(device), list):
+            raise ValueError("IVF<nlist>,SQ8 runs on one GPU: a multi-device index (more than one device id) is not "
+                             "available for the SQ8 codec")
+        super().__init__(dim, nlist, metric, device)
+        _ffi.check(self._lib.vdb_ivf_set_codec(self._h, 1), build_time=True)
+
+    def train_ranges(self, x: np.ndarray) -> None:
+        """vmin / vdiff from the residuals of `x` against the installed centroids (at most 100 000 rows are read)."""
+        x = _ffi.as_f32_c(x)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        _ffi.check(self._lib.vdb_ivf_sq8_train_ranges(self._h, _ffi.ptr(x), x.shape[0]), build_time=True)
+        self.ntotal = 0
+
+    def set_ranges(self, vmin: np.ndarray, vdiff: np.ndarray) -> None:
+        vmin = np.ascontiguousarray(vmin, dtype=np.float32).reshape(-1)
+        vdiff = np.ascontiguousarray(vdiff, dtype=np.float32).reshape(-1)
+        if vmin.shape != (self.dim,) or vdiff.shape != (self.dim,):
+            raise ValueError(f"expected two ({self.dim},) range vectors, got {vmin.shape} and {vdiff.shape}")
+        _ffi.check(self._lib.vdb_ivf_sq8_set_ranges(self._h, _ffi.ptr(vmin), _ffi.ptr(vdiff)), build_time=True)
+        self.ntotal = 0
+
+    def ranges(self) -> Tuple[np.ndarray, np.ndarray]:
+        vmin = np.empty((self.dim,), np.float32)
+        vdiff = np.empty((self.dim,), np.float32)
+        _ffi.check(self._lib.vdb_ivf_sq8_get_ranges(self._h, _ffi.ptr(vmin), _ffi.ptr(vdiff)))
+        return vmin, vdiff
+
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, dim) codes in id (insertion) order."""
+        out = np.empty((self.ntotal, self.dim), np.uint8)
+        _ffi.check(self._lib.vdb_ivf_get_codes(self._h, _ffi.ptr(out)))
+        return out
+
+
 def _fingerprint(vectors: np.ndarray, centroids: np.ndarray, list_of_row: np.ndarray) -> dict:
     """What a persisted index records about its three files so that load_index can tell a vectors / centroids file that
     does not belong to list_of_row.npy (regenerated corpus, partial overwrite): SHA-256 of the centroids and of the lists
@@ -177,7 +232,8 @@ def _lists_match_sample(vectors, centroids, list_of_row, metric: str, rows: int 
 
 
 def _build_ivf(vectors: np.ndarray, dim: int, key: str, metric: str, device: int, params: dict) -> IVFFlatIndex:
-    index = IVFFlatIndex(dim, parse_ivf_key(key), metric, device)
+    nlist, codec = parse_index_key(key)
+    index = (IVFSQ8Index if codec == "SQ8" else IVFFlatIndex)(dim, nlist, metric, device)
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
     index.add(vectors)
@@ -185,8 +241,8 @@ def _build_ivf(vectors: np.ndarray, dim: int, key: str, metric: str, device: int
 
 
 class HipApproximateSearch(BaseAlgorithm):
-    """ApproximateSearch semantics for "IVF<nlist>,Flat": train -> add -> nprobe from kwargs; raw FAISS
-    conventions (no normalisation, no sign flip)."""
+    """ApproximateSearch semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8": train -> add -> nprobe from kwargs; raw
+    FAISS conventions (no normalisation, no sign flip)."""
 
     def __init__(self, name: str, dimension: int, index_type: str, metric: str = "l2", device: Optional[int] = None,
                  **kwargs: Any) -> None:
@@ -195,7 +251,7 @@ class HipApproximateSearch(BaseAlgorithm):
         self.metric = "l2" if metric == "l2" else "ip"      # approximate_search.py:25
         self.device = _resolve_device(device, kwargs.get("device_ids"))
         self.index: Optional[IVFFlatIndex] = None
-        parse_ivf_key(index_type)                            # fail at construction, like a bad factory string
+        parse_index_key(index_type)                          # fail at construction, like a bad factory string
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         self.vectors = np.asarray(vectors).astype(np.float32)
@@ -223,7 +279,14 @@ class HipApproximateSearch(BaseAlgorithm):
     # Layout and protocol follow the reference's only implementation (covertree_v2_2.py:101-182, 184-282):
     # temp dir + manifest.json + WRITE_COMPLETE sentinel written last + atomic rename; load refuses an
     # incomplete artifact or a manifest that does not match this instance.
+    # An SQ8 artifact stores the corpus, centroids and lists like a Flat one plus the ranges (ranges.npy: vmin, vdiff), under
+    # its own format string: it never reloads as IVF-Flat, and loading re-encodes the stored rows under the stored lists
+    # (encoding is deterministic: the codes come back bit-identical).
     _FORMAT = "vdbhip-ivfflat-v1"
+    _FORMAT_SQ8 = "vdbhip-ivfsq8-v1"
+
+    def _format(self) -> str:
+        return self._FORMAT_SQ8 if parse_index_key(self.index_type)[1] == "SQ8" else self._FORMAT
 
     def save_index(self, artifact_dir: str, context=None):
         import json
@@ -248,13 +311,20 @@ class HipApproximateSearch(BaseAlgorithm):
             np.save(tmp / "centroids.npy", centroids, allow_pickle=False)
             np.save(tmp / "list_of_row.npy", lists, allow_pickle=False)
             build_metrics = dict(context.get("build_metrics", {}))
-            manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
+            manifest = {"format": self._format(), "algorithm": type(self).__name__, "dimension": self.dimension,
                         "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist,
                         "nprobe": self.index.nprobe, "n_vectors": int(self.index.ntotal),
                         "config_hash": context.get("config_hash"),
                         "sha256": _fingerprint(self.vectors, centroids, lists),
                         "files": {"vectors": "vectors.npy", "centroids": "centroids.npy",
                                   "list_of_row": "list_of_row.npy"}}
+            if isinstance(self.index, IVFSQ8Index):
+                import hashlib
+
+                ranges = np.stack(self.index.ranges())
+                np.save(tmp / "ranges.npy", ranges, allow_pickle=False)
+                manifest["files"]["ranges"] = "ranges.npy"
+                manifest["sha256"]["ranges"] = hashlib.sha256(ranges.tobytes()).hexdigest()
             (tmp / "manifest.json").write_text(json.dumps(manifest, indent=2), encoding="utf-8")
             (tmp / "build_metrics.json").write_text(json.dumps(build_metrics, indent=2), encoding="utf-8")
             (tmp / "WRITE_COMPLETE").write_text("ok\n", encoding="utf-8")
@@ -275,7 +345,7 @@ class HipApproximateSearch(BaseAlgorithm):
         if not (path / "WRITE_COMPLETE").is_file():
             raise FileNotFoundError(f"Artifact is incomplete or corrupted (missing WRITE_COMPLETE): {path}")
         manifest = json.loads((path / "manifest.json").read_text(encoding="utf-8"))
-        for key, want in (("format", self._FORMAT), ("dimension", self.dimension), ("index_type", self.index_type),
+        for key, want in (("format", self._format()), ("dimension", self.dimension), ("index_type", self.index_type),
                           ("metric", self.metric)):
             if manifest.get(key) != want:
                 raise ValueError(f"Persisted index mismatch for '{key}': artifact has {manifest.get(key)!r}, "
@@ -286,8 +356,18 @@ class HipApproximateSearch(BaseAlgorithm):
         vectors = np.load(path / manifest["files"]["vectors"], mmap_mode="r")
         centroids = np.load(path / manifest["files"]["centroids"])
         self.vectors = vectors
-        self.index = IVFFlatIndex(self.dimension, int(manifest["nlist"]), self.metric, self.device)
+        sq8 = manifest["format"] == self._FORMAT_SQ8
+        self.index = (IVFSQ8Index if sq8 else IVFFlatIndex)(self.dimension, int(manifest["nlist"]), self.metric, self.device)
         self.index.set_centroids(centroids)       # no k-means: the stored quantizer is reused ...
+        if sq8:                                   # ... and so are the stored ranges
+            import hashlib
+
+            ranges = np.load(path / manifest["files"]["ranges"])
+            want_ranges = (manifest.get("sha256") or {}).get("ranges")
+            if ranges.shape != (2, self.dimension) or (
+                    want_ranges and hashlib.sha256(np.ascontiguousarray(ranges, np.float32).tobytes()).hexdigest() != want_ranges):
+                raise ValueError("Persisted SQ8 ranges do not belong to this artifact")
+            self.index.set_ranges(ranges[0], ranges[1])
         stored = np.load(path / manifest["files"]["list_of_row"])
         if stored.shape != (vectors.shape[0],) or (len(stored) and (stored.min() < 0 or stored.max() >= int(manifest["nlist"]))):
             raise ValueError("Persisted inverted lists do not match the persisted corpus")
@@ -313,7 +393,7 @@ class HipApproximateSearch(BaseAlgorithm):
 
 
 class HipIVFIndexer(BaseIndexer):
-    """FaissFactoryIndexer / FaissIVFIndexer semantics for IVF-Flat keys."""
+    """FaissFactoryIndexer / FaissIVFIndexer semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8" keys."""
 
     _RESERVED = {"index_key", "index_type", "device", "device_ids", "niter", "seed", "max_points_per_centroid"}
 
@@ -324,7 +404,7 @@ class HipIVFIndexer(BaseIndexer):
         params.setdefault("index_type", key)
         super().__init__(name, dimension, metric, **params)
         self.index_key = self.index_type = key
-        parse_ivf_key(key)
+        parse_index_key(key)
 
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
         data = _ffi.as_f32_c(vectors)
