@@ -274,7 +274,7 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "flat_shape"      (before vdb_add; alias "i8_shape") MFMA shape of the flat scans for D <= 128 and the layout of their scan
  *                       copies: 0 auto (16) | 16 | 32.  16 = v_mfma_f32_16x16x32_f16 / v_mfma_i32_16x16x64_i8 on layout "x16"
  *                       (octs only; +17 - 19 % on the scans); 32 = the 32x32 kernels (also taken when an option asks for quads
- *                       -- "f16_group" / "i8_group" = 4 -- or for an A/B schedule of "scan_variant")
+ *                       -- "f16_group" / "i8_group" = 4)
  *     "scan_pair"       layout "x16", index with an int8 copy: 1 (default) both scans in one launch (the device picks the body), 0 two
  *                       launches (the one not needed returns at once) -- A/B and diagnosis
  *     "f16_stage_tiles" / "f16_wide" / "scan_prio"   tuning of the x16 kernels (tiles per LDS stage of the fp16 batch scan: 0 auto | 4 | 8;
@@ -292,9 +292,7 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "ivf_tile"        D > 128, 256-row spans: workgroup tile of the list scan, 0 auto / 2 = 256 rows x 256 query slots | 1 = 128 x 512
  *     "ivf_part"        0 auto | spans (256 rows) per row part of the IVF list scan: long lists are cut into parts
  *                       scanned by one workgroup each (rounded up to a multiple of 4 bins)
- *     "select_variant"  0..2;  "spans_per_chunk", "kloop_qgroup": grid shaping of the flat scans
- *     "scan_variant"    and the timing-only ablations exist only in -DVDB_ABLATIONS builds (`make ablations`, WRONG
- *                       results by design); the shipped library rejects them. */
+ *     "select_variant"  0..2;  "spans_per_chunk", "kloop_qgroup": grid shaping of the flat scans */
 int vdb_set_option(vdb_handle h, const char *key, double value);
 
 /* ---- test hooks (used by tests/ to validate the error bound of the fp16 scan) -------------- */
@@ -304,10 +302,6 @@ int vdb_set_option(vdb_handle h, const char *key, double value);
  * D > 128); VDB_ERR_UNSUPPORTED for D > 128 on at most 2048 rows (no MFMA scan there) */
 int vdb_debug_scan_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t row0, int64_t nrows,
                           float *scores_host, float *eps_host, double *cscale);
-
-/* per-wave cycle stamps {head, mfma, select, barrier, total, late, stages, 0} left by the diagnostic scan build
- * (option scan_variant = 6; never used for results) -- scripts/stamp_scan.py */
-int vdb_debug_fetch_stamps(vdb_handle h, unsigned long long *out_host, int64_t max_words, int64_t *nwords);
 
 #ifdef __cplusplus
 }

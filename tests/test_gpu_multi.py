@@ -203,8 +203,11 @@ def test_what_a_multi_handle_refuses(vdb):
     m.set_option("force_path", 1)                        # forwarded to every shard
     m.search(Q, 3)
     assert m.stats()["last_path_name"] == "exact_scan"
-    with pytest.raises(ValueError, match="unknown option"):
-        m.set_option("no_such_option", 1)
+    for name in ("no_such_option", "scan_variant"):      # (scan_variant: retired with the ablation build)
+        with pytest.raises(ValueError, match="unknown option"):
+            m.set_option(name, 1)
+        with pytest.raises(ValueError, match="unknown option"):
+            m.set_option(name, 0)
     m.close()
     with pytest.raises(ValueError, match="no such GPU"):
         vdb.FlatIndex(16, "l2", [0, 99])

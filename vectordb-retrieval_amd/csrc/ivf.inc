@@ -402,7 +402,7 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
         }
         sa.part_spans = part >= h->ivf_max_pspans ? 0 : part;
         const dim3 grid((unsigned)max_items, (unsigned)(sa.part_spans ? (h->ivf_max_pspans + part - 1) / part : 1));
-#define VDB_IVF_SCAN(KS, NW, BT) scan_kernel<KS, NW, 2, 2, 0, BT, true><<<grid, dim3(NW * 64), 0, st>>>(sa)
+#define VDB_IVF_SCAN(KS, NW, BT) scan_kernel<KS, NW, 2, 2, BT, true><<<grid, dim3(NW * 64), 0, st>>>(sa)
         if (kloop) {
             IvfKloopArgs ka{};
             ka.panels = sa.panels; ka.bias = sa.bias; ka.qrows = sa.qrows; ka.info = info;
@@ -459,10 +459,10 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
             // staging ring of the work items (option "i8_ring"; 0 = auto): a work item streams its list once, and few of them
             // are resident per CU -- 4 stages of 2 (4 at two k-steps) tiles in flight instead of 1
 #define VDB_IVF_SCAN8(KS, ST, NW, BT) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
-            if (h->ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, false, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+            if (h->ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
             else if (r__ == 2) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-            else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, false, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-            else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, false, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
+            else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+            else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
 #define VDB_IVF_SCAN8_NW(KS, ST, BT) do { if (nw == 2) VDB_IVF_SCAN8(KS, ST, 2, BT); else if (nw == 4) VDB_IVF_SCAN8(KS, ST, 4, BT); \
                                           else VDB_IVF_SCAN8(KS, ST, 8, BT); } while (0)
             // (tiles per LDS stage: 2 -- 8 pieces per stage for 8 waves make it 4 at two k-steps; deeper stages measured

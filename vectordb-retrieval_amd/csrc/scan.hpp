@@ -52,7 +52,6 @@ struct ScanArgs {
     const int32_t *slot_query;   // [slots] query + 1 of every slot (0 = padding)
     const _Float16 *qrows;       // [nq][16*KSTEPS] scaled fp16 query rows (B fragments are gathered from them)
     int prio;                    // x16 kernels (option "scan_prio", tuning): 1 = the late half of a workgroup issues at priority 1, 2 = the early half
-    unsigned long long *dbg;     // ABL == 4 (diagnostic build): per-wave cycle sums {head, mfma, select, barrier, total, late}
 };
 
 // (score & ~mask) | id  -- one v_and_or_b32 when the mask lives in a VGPR (the id is wave-uniform)
@@ -94,30 +93,14 @@ __host__ __device__ inline int quad_row_offset(unsigned packed_bits) {
 constexpr unsigned kQuadIdMask = 0xFFFFFFC0u;
 constexpr int kQuadRows = 4;
 
-// in-kernel stamp for the diagnostic build (cdna guide, 'In-kernel stamps'): shader-cycle counter, with the
-// lgkmcnt(0) the s_memtime result needs inside the same statement, fenced against the scheduler
-__device__ __forceinline__ unsigned long long stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-
-template <int KSTEPS, int ABL>
+template <int KSTEPS>
 __device__ __forceinline__ void mfma_phase(const half8 (&fr)[KSTEPS], const half8 (&b0)[KSTEPS],
                                            const half8 (&b1)[KSTEPS], const float16v &cin, float16v &acc0,
                                            float16v &acc1) {
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ++ks) {
-        if (ABL != 2) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ks], b0[ks], ks == 0 ? cin : acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ks], b1[ks], ks == 0 ? cin : acc1, 0, 0, 0);
-        } else {
-            if (ks == 0) { acc0 = cin; acc1 = cin; }
-            acc0[ks] += (float)fr[ks][0] * (float)b0[ks][0];
-            acc1[ks] += (float)fr[ks][1] * (float)b1[ks][1];
-        }
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ks], b0[ks], ks == 0 ? cin : acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ks], b1[ks], ks == 0 ? cin : acc1, 0, 0, 0);
     }
 }
 
@@ -135,14 +118,10 @@ __device__ __forceinline__ void mfma_phase(const half8 (&fr)[KSTEPS], const half
 // scan: 4 min ops (v_min3 chains on the raw accumulators) + 1 + 2 = 7 VALU ops per 8 scores instead of 5 per 4.  The select is
 // what the D <= 64 scan is bound by (stamps, profiles/r04_stamps_scan_fp16.txt: 441 - 472 cycles of select against 256 of MFMA
 // per tile and wave) and a sixth of the D = 128 scan; the price is twice the rows per candidate in the exact refine.
-template <int ABL, bool M3 = false, bool OCT = false>
+template <bool M3 = false, bool OCT = false>
 __device__ __forceinline__ void select_phase(const float16v &acc0, const float16v &acc1, float (&m1)[2],
                                              float (&m2)[2], unsigned idmask, float neg_inf, unsigned id0,
                                              float *m3 = nullptr) {
-    if (ABL == 1) {
-        asm volatile("" ::"v"(acc0), "v"(acc1));
-        return;
-    }
     if (OCT) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -160,7 +139,7 @@ __device__ __forceinline__ void select_phase(const float16v &acc0, const float16
         return;
     }
 #pragma unroll
-    for (int g = 0; g < (ABL == 5 ? 2 : 4); ++g) {   // ABL 5: timing-only, half the select work
+    for (int g = 0; g < 4; ++g) {
         const float q0 = quad_min(acc0[4 * g], acc0[4 * g + 1], acc0[4 * g + 2], acc0[4 * g + 3], neg_inf);
         const float v0 = pack_score(q0, idmask, id0 + g);
         if (M3) m3[0] = __builtin_amdgcn_fmed3f(m2[0], m3[0], v0);
@@ -188,7 +167,6 @@ __device__ __forceinline__ void read_phase(const half8 *__restrict__ A_tile, con
 
 // KSTEPS: 16-dim MFMA k-steps (D padded to 16*KSTEPS); NWAVES: waves per workgroup (64 queries each);
 // ST: tiles per LDS stage (divides 16); WPS: waves per SIMD the register allocator must leave room for.
-// ABL: timing-only ablations (wrong results!): 1 = no select epilogue, 2 = no MFMA, 3 = no global loads
 //
 // Phase stagger: a tile costs a wave one MFMA phase (2*KSTEPS back-to-back MFMAs, matrix pipe) and one
 // select phase (96 VALU ops).  The two waves that share a SIMD (wave w and w + NWAVES/2) run them in
@@ -198,7 +176,7 @@ __device__ __forceinline__ void read_phase(const half8 *__restrict__ A_tile, con
 // so the per-stage barrier keeps the stagger locked.
 // BT: tiles per level-1 bin per lane half (16 -> 256-row bins for the flat index, 4 -> 64-row bins for IVF,
 // whose per-query row count is small); ITEMS: IVF work-item mode (see ScanArgs).
-template <int KSTEPS, int NWAVES, int ST, int WPS, int ABL = 0, int BT = 16, bool ITEMS = false, int PRIO = 0, bool G8 = false>
+template <int KSTEPS, int NWAVES, int ST, int WPS, int BT = 16, bool ITEMS = false, bool G8 = false>
 __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_kernel(ScanArgs a) {
     static_assert(!G8 || (!ITEMS && BT == 16), "octs: flat index, 256-row bins");
     constexpr int NT = NWAVES * 64;
@@ -218,7 +196,7 @@ __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_kernel(ScanArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5;
-    const bool late = (PRIO == 3) || ((NWAVES >= 2) && (wave >= NWAVES / 2));
+    const bool late = (NWAVES >= 2) && (wave >= NWAVES / 2);
     int chunk = 0;
     int64_t q0, span0, span1, out_pitch, out_col;
     int64_t lspan0 = 0, lspans = 0;                         // items mode: first span / span count of the whole list (bin indexing)
@@ -297,7 +275,7 @@ __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_kernel(ScanArgs a) {
 #pragma unroll
         for (int i = 0; i < kPieces / NWAVES; ++i) {
             const int p = wave + i * NWAVES;
-            const half8 *g = src + (ABL == 3 ? (p & 15) : p) * 64 + lane;
+            const half8 *g = src + p * 64 + lane;
             __builtin_amdgcn_global_load_lds(
                 reinterpret_cast<const __attribute__((address_space(1))) void *>(reinterpret_cast<uintptr_t>(g)),
                 reinterpret_cast<__attribute__((address_space(3))) void *>(
@@ -405,40 +383,27 @@ __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_kernel(ScanArgs a) {
 
     half8 fr[KSTEPS];
     float16v cin, acc0, acc1;
-    // static issue priority for one half of the SIMD partners keeps the phase stagger from collapsing into
-    // lockstep (equal-priority waves share the matrix pipe evenly, finish together and then both sit on the VALU)
-    if (PRIO == 1 && late) __builtin_amdgcn_s_setprio(1);
-    if (PRIO == 2 && !late) __builtin_amdgcn_s_setprio(1);
-
-    unsigned long long c_head = 0, c_mfma = 0, c_sel = 0, c_bar = 0, t_start = 0, ta = 0, tb = 0;
-    if (ABL == 4) t_start = stamp();
     if (!late) {
         // ================= early half: MFMA(t), then select(t) =======================================
         for (int st = 0; st < nstages; ++st) {
             const int buf = st & 1;
-            if (ABL == 4) ta = stamp();
             if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);  // buf^1 was last read before the previous barrier
             const half8 *A = lds_a(buf);
             const float4 *B4 = reinterpret_cast<const float4 *>(lds_b(buf)) + h * 4;
             const int ts0 = (st % SPS) * ST;                 // first tile of this stage inside its span
             read_phase<KSTEPS>(A, B4, fr, cin, lane);
-            if (ABL == 4) { tb = stamp(); c_head += tb - ta; ta = tb; }
 #pragma unroll
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
-                mfma_phase<KSTEPS, ABL>(fr, b0, b1, cin, acc0, acc1);
+                mfma_phase<KSTEPS>(fr, b0, b1, cin, acc0, acc1);
                 __builtin_amdgcn_sched_barrier(0);
-                if (ABL == 4) { asm volatile("s_nop 0" ::"v"(acc0), "v"(acc1)); tb = stamp(); c_mfma += tb - ta; ta = tb; }
                 if (t + 1 < ST) read_phase<KSTEPS>(A + (t + 1) * KSTEPS * 64, B4 + (t + 1) * 8, fr, cin, lane);
-                select_phase<ABL, ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)(((ts0 + t) % BT) << 2), m3);
-                if (ABL == 4) { tb = stamp(); c_sel += tb - ta; ta = tb; }
+                select_phase<ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)(((ts0 + t) % BT) << 2), m3);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (((ts0 + ST) % BT) == 0) flush_bin(span0 + st / SPS, (ts0 + ST) / BT - 1);  // BT % ST == 0
             if (st + 1 < nstages) stage_bias_store(buf ^ 1);
-            if (ABL == 4) { tb = stamp(); c_sel += tb - ta; ta = tb; }
             __syncthreads();
-            if (ABL == 4) { tb = stamp(); c_bar += tb - ta; }
         }
     } else {
         // ================= late half: select(t-1), then MFMA(t) =====================================
@@ -447,43 +412,31 @@ __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_kernel(ScanArgs a) {
         acc1 = acc0;
         for (int st = 0; st < nstages; ++st) {
             const int buf = st & 1;
-            if (ABL == 4) ta = stamp();
             if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);
             const half8 *A = lds_a(buf);
             const float4 *B4 = reinterpret_cast<const float4 *>(lds_b(buf)) + h * 4;
             const int ts0 = (st % SPS) * ST;
-            if (ABL == 4) { tb = stamp(); c_head += tb - ta; ta = tb; }
 #pragma unroll
             for (int t = 0; t < ST; ++t) {
-                if (PRIO != 3) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 read_phase<KSTEPS>(A + t * KSTEPS * 64, B4 + t * 8, fr, cin, lane);
                 // retire the previous tile: index tp inside its span (the span before this one when ts0 + t == 0)
                 const int tp = (ts0 + t + TPS - 1) % TPS;
-                select_phase<ABL, ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)((tp % BT) << 2), m3);
+                select_phase<ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)((tp % BT) << 2), m3);
                 if (t == 0 && st > 0 && (ts0 % BT) == 0)      // (BT % ST == 0: bins only end at stage starts)
                     flush_bin(span0 + (st * ST - 1) / TPS, tp / BT);
-                if (PRIO != 3) __builtin_amdgcn_sched_barrier(0);
-                if (ABL == 4) { tb = stamp(); c_sel += tb - ta; ta = tb; }
-                mfma_phase<KSTEPS, ABL>(fr, b0, b1, cin, acc0, acc1);
-                if (ABL == 4) { asm volatile("s_nop 0" ::"v"(acc0), "v"(acc1)); tb = stamp(); c_mfma += tb - ta; ta = tb; }
+                __builtin_amdgcn_sched_barrier(0);
+                mfma_phase<KSTEPS>(fr, b0, b1, cin, acc0, acc1);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (st + 1 < nstages) stage_bias_store(buf ^ 1);
-            if (ABL == 4) { tb = stamp(); c_sel += tb - ta; ta = tb; }
             __syncthreads();
-            if (ABL == 4) { tb = stamp(); c_bar += tb - ta; }
         }
-        select_phase<ABL, ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)((BT - 1) << 2), m3);  // drain the last tile
+        select_phase<ITEMS, G8>(acc0, acc1, m1, m2, idmask, NEG_INF, (unsigned)((BT - 1) << 2), m3);  // drain the last tile
         flush_bin(span1 - 1, BPS - 1);
     }
     if (ITEMS)       // fill the last vector of this part's run
         for (int r = (int)(span1 - lspan0) * BPS; r & 3; ++r) items_push(r);
-    if (ABL == 4 && a.dbg && lane == 0) {
-        const unsigned long long t_end = stamp();
-        unsigned long long *d = a.dbg + ((size_t)blockIdx.x * NWAVES + wave) * 8;
-        d[0] = c_head; d[1] = c_mfma; d[2] = c_sel; d[3] = c_bar; d[4] = t_end - t_start; d[5] = late ? 1 : 0;
-        d[6] = (unsigned long long)nstages;
-    }
     if (ITEMS) return;
 
     const size_t so = (size_t)(chunk * 2 + h) * a.Qpad + q0 + (lane & 31);

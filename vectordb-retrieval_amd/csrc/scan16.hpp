@@ -27,7 +27,6 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 // concurrently resident workgroups share QG B panels and each chunk stream is shared by QG blocks.
 // BS: K-steps between workgroup barriers.  The LDS holds a ring of 2*BS stages; K-step s+BS is requested during K-step s
 // into the slot that K-step s-BS used, which every wave left before the barrier that closed its group.
-// ABL: timing-only builds -- 2 no MFMA, 3 no L2 traffic, 4 no pass epilogue / bias init.
 // FP: passes per level-1 bin (8: the 256-row bins (span, g); 4 / 2: 128- / 64-row bins for the direct-bin select).
 // NARROW (batches below 64 queries: one wave per workgroup holds queries, and it alone on its SIMD cannot hide a global
 // load per K-step behind 16 MFMAs): 1 = MFMAs and select work only for the 16-query column blocks that hold queries
@@ -38,7 +37,7 @@ struct ScanKloopExtra {
     int ksteps;  // 16-dim k-steps, multiple of 4
     int qgroup;  // query tiles per group (>= 1)
 };
-template <int ABL, int BS, int FP = 8, int NARROW = 0>
+template <int BS, int FP = 8, int NARROW = 0>
 __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKloopExtra ex) {
     constexpr int NWAVES = 8, RING = 2 * BS, HT = 8, CB = 4;
     constexpr int PPS = kTilesPerSpan16 / HT;               // passes per span (8)
@@ -87,7 +86,7 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
     auto stage_issue = [&](int step, int buf) {             // A panels of K-step `step` -> LDS slot
         const int pass = step / nK, kk = step - pass * nK;
         const int64_t tile0 = (span0 + pass / PPS) * kTilesPerSpan16 + (pass % PPS) * HT;
-        const half8 *base = ABL == 3 ? a.panels : a.panels + ((size_t)tile0 * KS + kk * 2) * 64;
+        const half8 *base = a.panels + ((size_t)tile0 * KS + kk * 2) * 64;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<half8 *>(base), 0, 0x7fffffff, 0x00020000);
         half8 *dst = lds_a(buf);
 #pragma unroll
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
             __builtin_amdgcn_raw_ptr_buffer_load_lds(
                 rs, reinterpret_cast<__attribute__((address_space(3))) void *>(
                         static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst + p * 64))),
-                16, lane16, ABL == 3 ? p * 1024 : (t * KS + ks) * 1024, 0, NARROW ? 2 : 0);   // (NARROW: one query tile, panels read once per search -> non-temporal)
+                16, lane16, (t * KS + ks) * 1024, 0, NARROW ? 2 : 0);   // (NARROW: one query tile, panels read once per search -> non-temporal)
         }
     };
 
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
             bq[cb][ks] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       rsq, lane16, (cb * KS + (ABL == 3 ? 0 : kk * 2) + ks) * 1024, 0));
+                                                       rsq, lane16, (cb * KS + kk * 2 + ks) * 1024, 0));
     };
     if (NARROW == 2) {   // column block 0 of this query tile: KS contiguous 1-KiB fragments (every wave helps, wave 0 uses them)
         const half8 *src = a.qpanels + (size_t)((int64_t)qt * (NWAVES * CB)) * KS * 64;
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
         const int slice = pass % PPS;
         // accumulators start from the bias of their rows: row = 1024*span + 256*g + 4*(HT*slice + t) + i
 #pragma unroll
-        for (int t = 0; t < (ABL == 4 ? 0 : HT); ++t) {
+        for (int t = 0; t < HT; ++t) {
             const float4 c = *reinterpret_cast<const float4 *>(a.bias + span * kSpanRows16 + g * kBinRows +
                                                                (slice * HT + t) * 4);
             acc[t][0][0] = (c.x >= 0.9e38f) ? kPadBias : c.x * cs;
@@ -191,9 +190,8 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
                     for (int t = 0; t < 4; ++t)
 #pragma unroll
                         for (int cb = 0; cb < CB; ++cb)
-                            if (ABL != 2)
-                                acc[(grp & 1) * 4 + t][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                                    fr[grp & 1][t], bq[cb][grp >> 1], acc[(grp & 1) * 4 + t][cb], 0, 0, 0);
+                            acc[(grp & 1) * 4 + t][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                fr[grp & 1][t], bq[cb][grp >> 1], acc[(grp & 1) * 4 + t][cb], 0, 0, 0);
                 } else {
 #pragma unroll
                     for (int cb = 0; cb < CB; ++cb)
@@ -208,14 +206,8 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
                 if (grp == 1) load_b(kn, 0);
             }
         }
-        if (ABL == 4) {      // keep the accumulators alive with one cheap use
 #pragma unroll
-            for (int t = 0; t < HT; ++t)
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) m1[cb] = fast_min(m1[cb], acc[t][cb][0], NEG_INF);
-        }
-#pragma unroll
-        for (int t = 0; t < (ABL == 4 ? 0 : HT); ++t) {
+        for (int t = 0; t < HT; ++t) {
             const unsigned id = (unsigned)((slice % FP) * HT + t);   // quad number inside the level-1 bin
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) {

@@ -229,16 +229,8 @@ struct ScanI8Args {
     const signed char *qrows;    // [nq][32*KS] int8 query rows cq - q (B fragments are gathered from them)
     int part_spans;              // items mode: spans per row part (blockIdx.y), 0 = whole list (see ScanArgs)
     int prio;                    // x16 kernel (option "scan_prio", tuning): 1 = the late half issues at priority 1, 2 = the early half
-    int abl_no_bins;             // -DVDB_ABLATIONS builds only (timing, WRONG results): skip the level-1 bin stores
-    unsigned long long *dbg;     // DBG builds (-DVDB_ABLATIONS): per wave {head, mfma, select, tail, barrier, total} shader
-                                 // cycles, the s_memrealtime ticks of the same span, (stages << 1) | late
 };
 
-// a "use" of the accumulators that makes hipcc wait for the matrix pipe.  In a device-only function: the same asm written
-// inside the __global__ body makes the HOST pass drop the kernel's launch stub without a diagnostic (the "v" constraint on
-// an int16v is not a valid x86 operand, and in a template the failure is a silent substitution failure)
-__device__ __forceinline__ void wait_for_mfma(const int16v &acc) { asm volatile("s_nop 0" ::"v"(acc)); }
-__device__ __forceinline__ unsigned long long realtime_ticks() { return __builtin_amdgcn_s_memrealtime(); }   // 100 MHz
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int imed3(int a, int b, int c) { return imax(imin(a, b), imin(imax(a, b), c)); }   // v_med3_i32
@@ -298,8 +290,6 @@ __device__ __forceinline__ void mfma_phase_i8(const int4v (&fr)[KS], const int4v
 // runs MFMA(t) then select(t), the late half select(t-1) then MFMA(t).  BT: tiles per level-1 bin; ITEMS: IVF work-item
 // mode (one inverted list x one group of query slots, bins laid out [item][slot][bin], third minimum kept); G: rows per
 // select group (must match bit 2 of QueryBatchInfo.i8_mode, which the select and refine kernels read).
-// DBG (diagnostic build, -DVDB_ABLATIONS only): in-kernel cycle stamps around the phases of every stage (results stay
-// exact; the stamped kernel is ~10 % slower) -- scripts/stamp_scan_i8.py.
 // TB (pacing barriers, 0 = none): an s_barrier every TB tiles inside a stage.  The stamps of the unpaced kernel
 // (profiles/r03_stamps_scan_i8.txt) show the early half of a workgroup running its 8 tiles in ~60 % of the stage and then
 // waiting at the stage barrier, while the late half -- which loses the pipe arbitration while both are active -- works
@@ -312,7 +302,7 @@ __device__ __forceinline__ void mfma_phase_i8(const int4v (&fr)[KS], const int4v
 // the wave time parked in s_waitcnt).  RING > 2 keeps RING - 1 stages requested: the per-row accumulator inits travel by
 // LDS-DMA as well (no register staging), every wave issues the same number of requests per stage, and a stage is
 // awaited with s_waitcnt vmcnt((RING - 2) x requests per stage) + s_barrier instead of the vmcnt(0) of __syncthreads().
-template <int KS, int ST, int CB, int NWAVES = 8, int BT = 16, bool ITEMS = false, int G = 8, bool DBG = false, int TB = 0,
+template <int KS, int ST, int CB, int NWAVES = 8, int BT = 16, bool ITEMS = false, int G = 8, int TB = 0,
           int RING = 2, int AUX = 0>
 __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && NWAVES == 4 && RING <= 4) ? 3 : NWAVES >= 4 ? 2 : 1)) void scan_i8_kernel(ScanI8Args a) {
     constexpr int GPT = 16 / G;                           // groups per (tile, column block): quads 4, octs 2
@@ -491,16 +481,11 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && N
         const size_t o = (size_t)((span * 2 + h) * BPS + bt) * out_pitch + out_col;
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
-#ifdef VDB_ABLATIONS
-            if (!a.abl_no_bins)
-#endif
-            {
-                // (non-temporal: 339 MB of bins per 10k-query batch on 1M rows are written once and read sparsely by the select,
-                //  while the 128 MB of panels are re-read by every query tile from L2 / the Infinity Cache; A/B in alternating
-                //  processes on one box: 9.19 - 9.28 -> 9.27 - 9.34 M QPS)
-                __builtin_nontemporal_store(__int_as_float(m1[cb]), a.bin_m1 + o + cb * 32);
-                __builtin_nontemporal_store(__int_as_float(m2[cb]), a.bin_m2 + o + cb * 32);
-            }
+            // (non-temporal: 339 MB of bins per 10k-query batch on 1M rows are written once and read sparsely by the select,
+            //  while the 128 MB of panels are re-read by every query tile from L2 / the Infinity Cache; A/B in alternating
+            //  processes on one box: 9.19 - 9.28 -> 9.27 - 9.34 M QPS)
+            __builtin_nontemporal_store(__int_as_float(m1[cb]), a.bin_m1 + o + cb * 32);
+            __builtin_nontemporal_store(__int_as_float(m2[cb]), a.bin_m2 + o + cb * 32);
             M2[cb] = imin(imed3(M1[cb], M2[cb], m1[cb]), m2[cb]);
             if (m1[cb] < M1[cb]) Ms[cb] = (int)span;
             M1[cb] = imin(M1[cb], m1[cb]);
@@ -559,25 +544,6 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && N
 
     int4v fr[KS];
     int16v cin, acc[CB];
-    // DBG: cycle sums per phase; tick(x) charges the cycles since the previous stamp to x.  `done` makes the MFMA results
-    // "used" so that the stamp behind an MFMA phase waits for the matrix pipe, not just for the issue.
-    unsigned long long c_head = 0, c_mfma = 0, c_sel = 0, c_tail = 0, c_bar = 0, t_last = 0, t_first = 0, r_first = 0;
-#define tick(bucket)                                   \
-    do {                                               \
-        if (DBG) {                                     \
-            const unsigned long long t__ = stamp();    \
-            bucket += t__ - t_last;                    \
-            t_last = t__;                              \
-        }                                              \
-    } while (0)
-#define done()                          \
-    do {                                \
-        if (DBG) { _Pragma("unroll") for (int cb__ = 0; cb__ < CB; ++cb__) wait_for_mfma(acc[cb__]); } \
-    } while (0)
-    if (DBG) {
-        t_first = t_last = stamp();
-        r_first = realtime_ticks();
-    }
     if (!late) {
         for (int st = 0; st < nstages; ++st) {
             const int buf = kDeep ? st % RING : st & 1;
@@ -587,30 +553,23 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && N
             const int4v *B4 = reinterpret_cast<const int4v *>(lds_b(buf)) + h * 4;
             const int ts0 = (st % SPS) * ST;
             read_phase_i8<KS>(A, B4, fr, cin, lane);
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_phase_i8<KS, CB>(fr, bq, cin, acc);
                 __builtin_amdgcn_sched_barrier(0);
-                done();
-                tick(c_mfma);
                 if (t + 1 < ST) read_phase_i8<KS>(A + (t + 1) * KS * 64, B4 + (t + 1) * 8, fr, cin, lane);
                 select_phase_i8<CB, ITEMS, G>(acc, m1, m2, (unsigned)(((ts0 + t) % BT) * GPT), m3);
-                tick(c_sel);
                 if (TB > 0 && (t + 1) % (TB > 0 ? TB : 1) == 0 && t + 1 < ST) {
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_barrier();
-                    tick(c_bar);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
             if (((ts0 + ST) % BT) == 0) flush_bin(span0 + st / SPS, (ts0 + ST) / BT - 1);
             if (!kDeep && st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_tail);
             if (kDeep) ring_wait();
             else __syncthreads();
-            tick(c_bar);
         }
     } else {
 #pragma unroll
@@ -624,7 +583,6 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && N
             const int4v *A = lds_a(buf);
             const int4v *B4 = reinterpret_cast<const int4v *>(lds_b(buf)) + h * 4;
             const int ts0 = (st % SPS) * ST;
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -633,36 +591,22 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES > 8 ? NWAVES / 4 : (ITEMS && N
                 select_phase_i8<CB, ITEMS, G>(acc, m1, m2, (unsigned)((tp % BT) * GPT), m3);
                 if (t == 0 && st > 0 && (ts0 % BT) == 0) flush_bin(span0 + (st * ST - 1) / TPS, tp / BT);
                 __builtin_amdgcn_sched_barrier(0);
-                tick(c_sel);
                 mfma_phase_i8<KS, CB>(fr, bq, cin, acc);
-                done();
-                tick(c_mfma);
                 if (TB > 0 && (t + 1) % (TB > 0 ? TB : 1) == 0 && t + 1 < ST) {
                     __builtin_amdgcn_sched_barrier(0);
                     __builtin_amdgcn_s_barrier();
-                    tick(c_bar);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
             if (!kDeep && st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_tail);
             if (kDeep) ring_wait();
             else __syncthreads();
-            tick(c_bar);
         }
         select_phase_i8<CB, ITEMS, G>(acc, m1, m2, (unsigned)((BT - 1) * GPT), m3);
         flush_bin(span1 - 1, BPS - 1);
     }
     if (ITEMS)       // fill the last vector of this part's run
         for (int r = (int)(span1 - lspan0) * BPS; r & 3; ++r) items_push(r);
-    if (DBG && a.dbg && lane == 0) {
-        const unsigned long long t_end = stamp(), r_end = realtime_ticks();
-        unsigned long long *d = a.dbg + ((size_t)blockIdx.x * NWAVES + wave) * 8;
-        d[0] = c_head; d[1] = c_mfma; d[2] = c_sel; d[3] = c_tail; d[4] = c_bar; d[5] = t_end - t_first;
-        d[6] = r_end - r_first; d[7] = ((unsigned long long)nstages << 1) | (late ? 1ull : 0ull);
-    }
-#undef tick
-#undef done
     if (ITEMS) return;
 
     const size_t so = (size_t)(chunk * 2 + h) * a.Qpad + q0 + (lane & 31);

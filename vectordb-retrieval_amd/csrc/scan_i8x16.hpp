@@ -25,18 +25,17 @@ namespace vdb {
 // corpus row (offset inside its 512-row span) of MFMA row m (0..15) of block rb of tile t, layout "x16"
 __host__ __device__ inline int x16_row_in_span(int t, int rb, int m) { return (m >> 2) * 128 + t * 8 + rb * 4 + (m & 3); }
 
-__device__ __forceinline__ void wait_for_mfma4(const int4v &a, const int4v &b) { asm volatile("s_nop 0" ::"v"(a), "v"(b)); }   // (as wait_for_mfma)
 __device__ __forceinline__ int swap16(int v) { return __builtin_amdgcn_ds_swizzle(v, 0x401F); }   // lane ^ 16 (and 0x1f, xor 0x10)
 
 // KS2: 64-dim k-steps (D padded to 64 or 128); ST: 32-row tiles per LDS stage; CB: 16-query column blocks per wave (8 -> 128
-// queries per wave, 4 -> 64); NWAVES, RING, AUX, DBG as scan_i8_kernel.  Octs only (QueryBatchInfo.i8_mode bit 2 is set by
+// queries per wave, 4 -> 64); NWAVES, RING, AUX as scan_i8_kernel.  Octs only (QueryBatchInfo.i8_mode bit 2 is set by
 // the host for an index in this layout).
 template <int KS2, int ST, int RING>
 constexpr int scan_i8x16_lds_bytes() { return RING * (ST * 2 * KS2 * 64 * 16 + ST * 32 * 4); }
 
 // (the body is a device function over a caller-provided LDS block so that scan_pair_x16_kernel, scan_x16.hpp, can hold it
 //  next to the fp16 scan in ONE launch)
-template <int KS2, int ST, int CB, int NWAVES = 8, bool DBG = false, int RING = 2, int AUX = 0>
+template <int KS2, int ST, int CB, int NWAVES = 8, int RING = 2, int AUX = 0>
 __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned char *smem) {
     constexpr int NV = 2 * KS2;                           // 16-byte fragments per lane and tile
     constexpr int NT = NWAVES * 64;
@@ -158,13 +157,8 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
             const int p1 = swap16(odd ? m1[2 * j] : m1[2 * j + 1]), p2 = swap16(odd ? m2[2 * j] : m2[2 * j + 1]);
             const int a1 = odd ? m1[2 * j + 1] : m1[2 * j], a2 = odd ? m2[2 * j + 1] : m2[2 * j];
             const int b1 = imin(a1, p1), b2 = imin(imax(a1, p1), imin(a2, p2));
-#ifdef VDB_ABLATIONS
-            if (!a.abl_no_bins)
-#endif
-            {
-                __builtin_nontemporal_store(__int_as_float(b1), a.bin_m1 + o + j * 32);
-                __builtin_nontemporal_store(__int_as_float(b2), a.bin_m2 + o + j * 32);
-            }
+            __builtin_nontemporal_store(__int_as_float(b1), a.bin_m1 + o + j * 32);
+            __builtin_nontemporal_store(__int_as_float(b2), a.bin_m2 + o + j * 32);
             M2[j] = imin(imed3(M1[j], M2[j], b1), b2);
             if (b1 < M1[j]) Ms[j] = (int)span;
             M1[j] = imin(M1[j], b1);
@@ -229,25 +223,8 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
             m1[cb] = imin(m1[cb], v);
         }
     };
-    unsigned long long c_head = 0, c_mfma = 0, c_sel = 0, c_tail = 0, c_bar = 0, t_last = 0, t_first = 0, r_first = 0;
-#define tick(bucket)                                   \
-    do {                                               \
-        if (DBG) {                                     \
-            const unsigned long long t__ = stamp();    \
-            bucket += t__ - t_last;                    \
-            t_last = t__;                              \
-        }                                              \
-    } while (0)
-#define done()                                                                                                    \
-    do {                                                                                                          \
-        if (DBG) { _Pragma("unroll") for (int cb__ = 0; cb__ < CB; ++cb__) wait_for_mfma4(acc[0][cb__], acc[1][cb__]); } \
-    } while (0)
     if (a.prio == 1 && late) __builtin_amdgcn_s_setprio(1);
     else if (a.prio == 2 && !late) __builtin_amdgcn_s_setprio(1);
-    if (DBG) {
-        t_first = t_last = stamp();
-        r_first = realtime_ticks();
-    }
     if (!late) {
         for (int st = 0; st < nstages; ++st) {
             const int buf = kDeep ? st % RING : st & 1;
@@ -257,25 +234,19 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
             const int4v *B4 = reinterpret_cast<const int4v *>(lds_b(buf)) + g * 2;
             const int ts0 = (st % SPS) * ST;
             read_phase(A, B4);
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_phase();
                 __builtin_amdgcn_sched_barrier(0);
-                done();
-                tick(c_mfma);
                 if (t + 1 < ST) read_phase(A + (t + 1) * NV * 64, B4 + (t + 1) * 8);
                 select_phase(ts0 + t);
-                tick(c_sel);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (ts0 + ST == TPS) flush_bin(span0 + st / SPS);
             if (!kDeep && st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_tail);
             if (kDeep) ring_wait();
             else __syncthreads();
-            tick(c_bar);
         }
     } else {
 #pragma unroll
@@ -291,7 +262,6 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
             const int4v *A = lds_a(buf);
             const int4v *B4 = reinterpret_cast<const int4v *>(lds_b(buf)) + g * 2;
             const int ts0 = (st % SPS) * ST;
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -299,29 +269,16 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
                 select_phase((ts0 + t + TPS - 1) % TPS);
                 if (t == 0 && st > 0 && ts0 == 0) flush_bin(span0 + st / SPS - 1);
                 __builtin_amdgcn_sched_barrier(0);
-                tick(c_sel);
                 mfma_phase();
-                done();
-                tick(c_mfma);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (!kDeep && st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_tail);
             if (kDeep) ring_wait();
             else __syncthreads();
-            tick(c_bar);
         }
         select_phase(TPS - 1);
         flush_bin(span1 - 1);
     }
-    if (DBG && a.dbg && lane == 0) {
-        const unsigned long long t_end = stamp(), r_end = realtime_ticks();
-        unsigned long long *d = a.dbg + ((size_t)blockIdx.x * NWAVES + wave) * 8;
-        d[0] = c_head; d[1] = c_mfma; d[2] = c_sel; d[3] = c_tail; d[4] = c_bar; d[5] = t_end - t_first;
-        d[6] = r_end - r_first; d[7] = ((unsigned long long)nstages << 1) | (late ? 1ull : 0ull);
-    }
-#undef tick
-#undef done
 
     const size_t so = (size_t)(chunk * 2 + h) * a.Qpad + col0;
 #pragma unroll
@@ -332,10 +289,10 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
     }
 }
 
-template <int KS2, int ST, int CB, int NWAVES = 8, bool DBG = false, int RING = 2, int AUX = 0>
+template <int KS2, int ST, int CB, int NWAVES = 8, int RING = 2, int AUX = 0>
 __global__ __launch_bounds__(NWAVES * 64, (NWAVES >= 4 ? 2 : 1)) void scan_i8x16_kernel(ScanI8Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[scan_i8x16_lds_bytes<KS2, ST, RING>()];
-    scan_i8x16_body<KS2, ST, CB, NWAVES, DBG, RING, AUX>(a, smem);
+    scan_i8x16_body<KS2, ST, CB, NWAVES, RING, AUX>(a, smem);
 }
 
 }  // namespace vdb

@@ -25,7 +25,7 @@ constexpr int scan_x16_lds_bytes() { return 2 * (ST * 2 * KS2 * 64 * 16 + ST * 3
 // exact refine of the float32 rows outweighs the scan, so the smaller group wins: 10k queries, k = 100 on 50k rows 1.20 -> 0.97 ms)
 // CB: 16-query column blocks per wave: 4 (64 queries), or for D <= 64 also 8 (128 queries per wave, 1024-query workgroup tiles as
 // scan_i8x16_kernel: every A fragment read from LDS feeds 8 MFMAs; at D = 128 the B fragments of 128 queries would take 128 VGPRs)
-template <int KS2, int NWAVES, int ST, int BR = 256, bool DBG = false, int G = 8, int CB = 4>
+template <int KS2, int NWAVES, int ST, int BR = 256, int G = 8, int CB = 4>
 __device__ __forceinline__ void scan_x16_body(const ScanArgs &a, unsigned char *smem) {
     constexpr int NV = 2 * KS2;
     static_assert(CB == 4 || (CB == 8 && KS2 <= 2), "128 queries per wave: D <= 64");
@@ -205,49 +205,28 @@ __device__ __forceinline__ void scan_x16_body(const ScanArgs &a, unsigned char *
             m1[cb] = fast_min(m1[cb], v, NEG_INF);
         }
     };
-    unsigned long long c_head = 0, c_mfma = 0, c_sel = 0, c_bar = 0, t_start = 0, ta = 0, tb = 0;
-#define tick(bucket)                    \
-    do {                                \
-        if (DBG) {                      \
-            tb = stamp();               \
-            bucket += tb - ta;          \
-            ta = tb;                    \
-        }                               \
-    } while (0)
-#define done()                                                                                                        \
-    do {                                                                                                              \
-        if (DBG) { _Pragma("unroll") for (int cb__ = 0; cb__ < CB; ++cb__) asm volatile("s_nop 0" ::"v"(acc[0][cb__]), "v"(acc[1][cb__])); } \
-    } while (0)
     if (a.prio == 1 && late) __builtin_amdgcn_s_setprio(1);
     else if (a.prio == 2 && !late) __builtin_amdgcn_s_setprio(1);
-    if (DBG) t_start = stamp();
     if (!late) {
         for (int st = 0; st < nstages; ++st) {
             const int buf = st & 1;
-            if (DBG) ta = stamp();
             if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);
             const half8 *A = lds_a(buf);
             const float4v *B4 = reinterpret_cast<const float4v *>(lds_b(buf)) + g * 2;
             const int ts0 = (st % SPS) * ST;
             read_phase(A, B4);
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_phase();
                 __builtin_amdgcn_sched_barrier(0);
-                done();
-                tick(c_mfma);
                 if (t + 1 < ST) read_phase(A + (t + 1) * NV * 64, B4 + (t + 1) * 8);
                 select_phase(ts0 + t);
-                tick(c_sel);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (((ts0 + ST) % BT) == 0) flush_bin(span0 + st / SPS, (ts0 + ST) / BT - 1);
             if (st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_sel);
             __syncthreads();
-            tick(c_bar);
         }
     } else {
 #pragma unroll
@@ -256,12 +235,10 @@ __device__ __forceinline__ void scan_x16_body(const ScanArgs &a, unsigned char *
             for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = float4v{3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};   // dummy previous tile
         for (int st = 0; st < nstages; ++st) {
             const int buf = st & 1;
-            if (DBG) ta = stamp();
             if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);
             const half8 *A = lds_a(buf);
             const float4v *B4 = reinterpret_cast<const float4v *>(lds_b(buf)) + g * 2;
             const int ts0 = (st % SPS) * ST;
-            tick(c_head);
 #pragma unroll UNR
             for (int t = 0; t < ST; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -270,28 +247,15 @@ __device__ __forceinline__ void scan_x16_body(const ScanArgs &a, unsigned char *
                 select_phase(tp);
                 if (t == 0 && st > 0 && (ts0 % BT) == 0) flush_bin(span0 + (st * ST - 1) / TPS, tp / BT);
                 __builtin_amdgcn_sched_barrier(0);
-                tick(c_sel);
                 mfma_phase();
-                done();
-                tick(c_mfma);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (st + 1 < nstages) stage_bias_store(buf ^ 1);
-            tick(c_sel);
             __syncthreads();
-            tick(c_bar);
         }
         select_phase(TPS - 1);
         flush_bin(span1 - 1, TPS / BT - 1);
     }
-    if (DBG && a.dbg && lane == 0) {       // (record format of scan_kernel's stamped build: scripts/stamp_scan.py)
-        const unsigned long long t_end = stamp();
-        unsigned long long *d = a.dbg + ((size_t)blockIdx.x * NWAVES + wave) * 8;
-        d[0] = c_head; d[1] = c_mfma; d[2] = c_sel; d[3] = c_bar; d[4] = t_end - t_start; d[5] = late ? 1 : 0;
-        d[6] = (unsigned long long)nstages;
-    }
-#undef tick
-#undef done
 
     // superbins (chunk, h) of the 256-row geometry; in direct-bin mode the level-1 bins are the superbins and these go unread
     if (kMerge) {
@@ -305,10 +269,10 @@ __device__ __forceinline__ void scan_x16_body(const ScanArgs &a, unsigned char *
     }
 }
 
-template <int KS2, int NWAVES, int ST, int WPS, int BR = 256, bool DBG = false, int G = 8, int CB = 4>
+template <int KS2, int NWAVES, int ST, int WPS, int BR = 256, int G = 8, int CB = 4>
 __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_x16_kernel(ScanArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[scan_x16_lds_bytes<KS2, ST>()];
-    scan_x16_body<KS2, NWAVES, ST, BR, DBG, G, CB>(a, smem);
+    scan_x16_body<KS2, NWAVES, ST, BR, G, CB>(a, smem);
 }
 
 // Both scans of an index that holds the int8 copy, in ONE launch: which of them serves a batch is decided on the device
@@ -322,8 +286,8 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES >= 4 ? 2 : 1)) void scan_pair_
     constexpr int KF = W128 ? 4 : 2, KI = W128 ? 2 : 1;
     constexpr int kLds16 = scan_x16_lds_bytes<KF, STF>(), kLds8 = scan_i8x16_lds_bytes<KI, STI, RING>();
     __shared__ __attribute__((aligned(16))) unsigned char smem[kLds16 > kLds8 ? kLds16 : kLds8];
-    if (a8.info->i8_mode) scan_i8x16_body<KI, STI, CBI, NWAVES, false, RING, AUX>(a8, smem);
-    else scan_x16_body<KF, NWAVES, STF, 256, false>(a16, smem);
+    if (a8.info->i8_mode) scan_i8x16_body<KI, STI, CBI, NWAVES, RING, AUX>(a8, smem);
+    else scan_x16_body<KF, NWAVES, STF, 256>(a16, smem);
 }
 
 }  // namespace vdb

@@ -80,23 +80,16 @@ int scan_geometry_direct(const vdb_index_s *h, int k, ScanGeom &g) {
     return 0;
 }
 
-// scan kernel variants: {waves per workgroup, tiles per LDS stage, waves per SIMD}.  Variant 0 is the
-// production one; the others exist for the interleaved A/B in scripts/sweep_scan.py (7..9 are timing-only
-// ablations of variant 0 and return wrong results).
-struct ScanVariant { int nwaves, st, wps; };
-constexpr ScanVariant kScanVariants[] = {{8, 4, 2}, {4, 4, 2}, {8, 4, 2}, {8, 4, 2}, {8, 4, 2}, {4, 4, 2}, {8, 4, 2},
-                                         {8, 4, 2}, {8, 4, 2}, {8, 4, 2}};
-[[maybe_unused]] constexpr int kNumScanVariants = sizeof(kScanVariants) / sizeof(kScanVariants[0]);
-
+// 32-row-tile layout: 512-query workgroup tiles (8 waves, 4 tiles per LDS stage, 2 waves per SIMD) unless the batch is small
 template <int KSTEPS>
-void launch_scan_k(int variant, ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int bt = 16, int nw = 8, bool g8 = false) {
-    if (bt == 16 && variant == 0 && nw < 8) {   // small batch: 64 * nw queries per workgroup, only the tiles that hold queries
+void launch_scan_k(ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int bt = 16, int nw = 8, bool g8 = false) {
+    if (bt == 16 && nw < 8) {   // small batch: 64 * nw queries per workgroup, only the tiles that hold queries
         sa.nqtiles = (int)((sa.nq_valid + nw * 64 - 1) / (nw * 64));
         const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
         if (g8) {
-            if (nw == 1) scan_kernel<KSTEPS, 1, 4, 1, 0, 16, false, 0, true><<<dim3(grid), dim3(64), 0, st>>>(sa);
-            else if (nw == 2) scan_kernel<KSTEPS, 2, 4, 1, 0, 16, false, 0, true><<<dim3(grid), dim3(128), 0, st>>>(sa);
-            else scan_kernel<KSTEPS, 4, 4, 2, 0, 16, false, 0, true><<<dim3(grid), dim3(256), 0, st>>>(sa);
+            if (nw == 1) scan_kernel<KSTEPS, 1, 4, 1, 16, false, true><<<dim3(grid), dim3(64), 0, st>>>(sa);
+            else if (nw == 2) scan_kernel<KSTEPS, 2, 4, 1, 16, false, true><<<dim3(grid), dim3(128), 0, st>>>(sa);
+            else scan_kernel<KSTEPS, 4, 4, 2, 16, false, true><<<dim3(grid), dim3(256), 0, st>>>(sa);
             return;
         }
         if (nw == 1) scan_kernel<KSTEPS, 1, 4, 1><<<dim3(grid), dim3(64), 0, st>>>(sa);
@@ -104,43 +97,18 @@ void launch_scan_k(int variant, ScanArgs &sa, int nchunks, int64_t Qpad, hipStre
         else scan_kernel<KSTEPS, 4, 4, 2><<<dim3(grid), dim3(256), 0, st>>>(sa);
         return;
     }
-    if (bt != 16) {            // direct-bin mode: finer level-1 bins (8 or 4 tiles), production schedule only
-        sa.nqtiles = (int)(Qpad / 512);
-        const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-        if (bt == 8) scan_kernel<KSTEPS, 8, 4, 2, 0, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
-        else scan_kernel<KSTEPS, 8, 4, 2, 0, 4><<<dim3(grid), dim3(512), 0, st>>>(sa);
-        return;
-    }
-    const ScanVariant v = kScanVariants[variant];
-    sa.nqtiles = (int)(Qpad / (v.nwaves * 64));
+    sa.nqtiles = (int)(Qpad / 512);
     const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-    switch (variant) {
-#ifdef VDB_ABLATIONS   // A/B schedules and timing-only ablations (WRONG RESULTS for 4, 7..9): scripts/sweep_scan.py builds
-        case 1: scan_kernel<KSTEPS, 4, 4, 2><<<dim3(grid), dim3(256), 0, st>>>(sa); break;
-        case 4: scan_kernel<KSTEPS, 8, 4, 2, 5><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-        case 5: scan_kernel<KSTEPS, 4, 4, 2, 0, 16, false, 3><<<dim3(grid), dim3(256), 0, st>>>(sa); break;
-        case 2: scan_kernel<KSTEPS, 8, 4, 2, 0, 16, false, 1><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-        case 3: scan_kernel<KSTEPS, 8, 4, 2, 0, 16, false, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-        case 6:
-            if (g8) scan_kernel<KSTEPS, 8, 4, 2, 4, 16, false, 0, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else scan_kernel<KSTEPS, 8, 4, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            break;
-        case 7: scan_kernel<KSTEPS, 8, 4, 2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-        case 8: scan_kernel<KSTEPS, 8, 4, 2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-        case 9: scan_kernel<KSTEPS, 8, 4, 2, 3><<<dim3(grid), dim3(512), 0, st>>>(sa); break;
-#endif
-        default:
-            if (g8) scan_kernel<KSTEPS, 8, 4, 2, 0, 16, false, 0, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else scan_kernel<KSTEPS, 8, 4, 2><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            break;
-    }
+    if (bt == 8) scan_kernel<KSTEPS, 8, 4, 2, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);   // direct-bin mode: finer level-1 bins (8 or 4 tiles)
+    else if (bt != 16) scan_kernel<KSTEPS, 8, 4, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa);
+    else if (g8) scan_kernel<KSTEPS, 8, 4, 2, 16, false, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
+    else scan_kernel<KSTEPS, 8, 4, 2><<<dim3(grid), dim3(512), 0, st>>>(sa);
 }
 
-// candidate groups of the fp16 flat scan (D <= 128, 256-row bins, production schedule or the stamped build): octs unless
-// option "f16_group" = 4
+// candidate groups of the fp16 flat scan (D <= 128, 256-row bins): octs unless option "f16_group" = 4
 bool f16_octs(const vdb_index_s *h, int direct_rows) {
     if (h->x16) return !direct_rows;  // (layout "x16": octs; direct-bin mode -- large k, the refine outweighs the scan -- takes the quads of the two blocks)
-    return h->f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps && (h->scan_variant == 0 || h->scan_variant == 6);
+    return h->f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps;
 }
 
 inline int st_tiles_of(const vdb_index_s *h) { return h->f16_stage_tiles ? h->f16_stage_tiles : (h->ksteps == 4 ? 8 : 4); }
@@ -155,39 +123,23 @@ void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStr
         const unsigned ngroups = (unsigned)((sa.nqtiles + qgroup - 1) / qgroup);
         const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * ngroups * (unsigned)qgroup;
         const ScanKloopExtra ex{h->ksteps, qgroup};
-        if (direct_rows) {      // finer level-1 bins (production schedule only)
-            if (direct_rows == 128) scan16_kloop_kernel<0, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-            else scan16_kloop_kernel<0, 2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+        if (direct_rows) {      // finer level-1 bins
+            if (direct_rows == 128) scan16_kloop_kernel<2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+            else scan16_kloop_kernel<2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
             VDB_HIP(hipGetLastError());
             return;
         }
-        switch (h->scan_variant) {
-#ifdef VDB_ABLATIONS
-            case 2: scan16_kloop_kernel<0, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;
-            case 7: scan16_kloop_kernel<2, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no MFMA
-            case 8: scan16_kloop_kernel<3, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no traffic
-            case 9: scan16_kloop_kernel<4, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex); break;  // no epilogue
-#endif
-            default:
-                if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && !h->small_batch_off)
-                    scan16_kloop_kernel<0, 3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                else if (sa.nq_valid > 0 && sa.nq_valid < 64 && !h->small_batch_off)
-                    scan16_kloop_kernel<0, 2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                else
-                    scan16_kloop_kernel<0, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-                break;
-        }
+        if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && !h->small_batch_off)
+            scan16_kloop_kernel<3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+        else if (sa.nq_valid > 0 && sa.nq_valid < 64 && !h->small_batch_off)
+            scan16_kloop_kernel<2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
+        else
+            scan16_kloop_kernel<2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
     } else if (h->x16) {               // D <= 128 on layout "x16" (scan_x16.hpp)
-        [[maybe_unused]] const bool stamped = h->scan_variant == 6;
-#ifndef VDB_ABLATIONS
-        if (h->scan_variant != 0) throw Error(VDB_ERR_UNSUPPORTED, "scan_variant: the A/B schedules exist for the 32-row layout (option flat_shape = 32 before vdb_add)");
-#else
-        if (h->scan_variant != 0 && !stamped) throw Error(VDB_ERR_UNSUPPORTED, "scan_variant: the A/B schedules exist for the 32-row layout (option flat_shape = 32 before vdb_add)");
-#endif
-        const bool small = direct_rows == 0 && nw < 8 && !stamped;
+        const bool small = direct_rows == 0 && nw < 8;
         // D <= 64, batch shape: 1024-query workgroup tiles (8 column blocks = 128 queries per wave) when the batch is a multiple of 1024
         // and there are enough of them to cover the chip -- the rule of the int8 scan (option "f16_wide": 0 auto, 1 never)
-        const bool wide = !small && direct_rows == 0 && !stamped && h->ksteps == 4 && h->f16_wide != 1 && Qpad % 1024 == 0 &&
+        const bool wide = !small && direct_rows == 0 && h->ksteps == 4 && h->f16_wide != 1 && Qpad % 1024 == 0 &&
                           (int64_t)nchunks * (Qpad / 1024) >= 256;
         // tiles per LDS stage of the batch shape (option "f16_stage_tiles"): measured on the bench shapes (profiles/r04_sweeps.txt) D = 64:
         // 8 tiles 1.108 ms against 1.163 with 4 (a 4-tile stage is only 16 KiB of panels per barrier); D = 128: 1.730 against 1.722
@@ -195,8 +147,8 @@ void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStr
         sa.nqtiles = small ? (int)((sa.nq_valid + nw * 64 - 1) / (nw * 64)) : (int)(Qpad / (wide ? 1024 : 512));
         const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
         if (wide) {
-            if (st_tiles_of(h) == 8) scan_x16_kernel<2, 8, 8, 2, 256, false, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else scan_x16_kernel<2, 8, 4, 2, 256, false, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
+            if (st_tiles_of(h) == 8) scan_x16_kernel<2, 8, 8, 2, 256, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
+            else scan_x16_kernel<2, 8, 4, 2, 256, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
             VDB_HIP(hipGetLastError());
             return;
         }
@@ -204,23 +156,17 @@ void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStr
             if (small && nw == 1) scan_x16_kernel<KS2_, 1, 4, 1><<<dim3(grid), dim3(64), 0, st>>>(sa); \
             else if (small && nw == 2) scan_x16_kernel<KS2_, 2, 4, 1><<<dim3(grid), dim3(128), 0, st>>>(sa); \
             else if (small) scan_x16_kernel<KS2_, 4, 4, 2><<<dim3(grid), dim3(256), 0, st>>>(sa); \
-            else if (direct_rows == 128) scan_x16_kernel<KS2_, 8, 4, 2, 128, false, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
-            else if (direct_rows == 64) scan_x16_kernel<KS2_, 8, 4, 2, 64, false, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
+            else if (direct_rows == 128) scan_x16_kernel<KS2_, 8, 4, 2, 128, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
+            else if (direct_rows == 64) scan_x16_kernel<KS2_, 8, 4, 2, 64, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
             else if (st_tiles == 8) scan_x16_kernel<KS2_, 8, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); \
             else scan_x16_kernel<KS2_, 8, 4, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); } while (0)
-#ifdef VDB_ABLATIONS
-        if (stamped) {
-            if (h->ksteps == 4) scan_x16_kernel<2, 8, 4, 2, 256, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else scan_x16_kernel<4, 8, 4, 2, 256, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
-        } else
-#endif
         if (h->ksteps == 4) VDB_X16F(2);
         else VDB_X16F(4);
 #undef VDB_X16F
     } else if (h->ksteps == 4)
-        launch_scan_k<4>(h->scan_variant, sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
+        launch_scan_k<4>(sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
     else
-        launch_scan_k<8>(h->scan_variant, sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
+        launch_scan_k<8>(sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
     VDB_HIP(hipGetLastError());
 }
 
@@ -525,7 +471,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     const int cand_cap = h->list_cap > 0 ? h->list_cap : std::max(64, 2 * k + 32);
     const int rescan_cap = std::max(16, k / 2 + 8);
     // int8 scan for byte-valued corpora: offered to the device-side choice whenever the standard geometry is in use
-    const bool use_i8 = h->i8_ok && !i8_off && !direct_rows && !h->tile16 && h->scan_variant == 0;
+    const bool use_i8 = h->i8_ok && !i8_off && !direct_rows && !h->tile16;
     ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
     ws.eps.reserve((size_t)nq * sizeof(float));
     ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
@@ -602,19 +548,12 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     sa.Qpad = Qpad;
     sa.nq_valid = nq;
     sa.prio = h->scan_prio;
-    if (h->scan_variant == 6) {   // diagnostic build: per-wave cycle sums
-        const size_t nblocks = 8 * (size_t)((g.nchunks + 7) / 8) * (size_t)(Qpad / 512);
-        ws.dense.reserve(nblocks * 8 * 8 * sizeof(unsigned long long));
-        VDB_HIP(hipMemsetAsync(ws.dense.p, 0, nblocks * 8 * 8 * sizeof(unsigned long long), st));
-        sa.dbg = ws.dense.as<unsigned long long>();
-        h->dbg_words = nblocks * 8 * 8;
-    }
     timing_mark(h, tslot, 0, st);
     // small batches: as many waves per workgroup as there are 64-query column groups (1, 2, 4; 8 = the batch shape)
     const int nw_small = h->small_batch_off ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
     // layout "x16" with both scan copies resident: ONE launch holds both scans (scan_pair_x16_kernel, scan_x16.hpp) when every tuning
     // option is at its default; otherwise (and on the 32-row layout) both are enqueued and the one not needed returns at once
-    bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && direct_rows == 0 && h->scan_variant == 0 &&
+    bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && direct_rows == 0 &&
                           !h->scan_pair_off && h->i8_ring == 0 && h->i8_nt == 0 && h->f16_stage_tiles == 0 && h->i8_variant == 3;
     if (h->panels_streamed) {
         // streamed panels (option "stream_panels"): chunks are scanned slab by slab -- convert the slab's float32 rows into a
@@ -696,21 +635,11 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         // 4-tile stages; 1 = 8-tile stages; 2 = 1024-query tiles (4 column blocks per wave); 3 = both (default);
         // 4 / 5 = 16 waves per workgroup (4 per SIMD) with 8- / 16-tile stages.  Odd batch sizes keep 512-query tiles.
         int v8 = h->i8_variant;
-#ifdef VDB_ABLATIONS
-        s8.abl_no_bins = (v8 & 8) ? 1 : 0;      // +8: no level-1 bin stores (timing only, WRONG results)
-        v8 &= 7;
-#endif
         if (h->x16) {
             // layout "x16" (scan_i8x16.hpp, v_mfma_i32_16x16x64_i8): the same launch shapes -- batch: 512- or 1024-query tiles
             // (4 or 8 column blocks of 16 queries per wave), 4- or 8-tile stages (i8_variant bits as below, 4 / 5 -> 3);
             // serving: 1 / 2 / 4 waves of 64 queries, 4-stage staging ring (option "i8_ring": 2, 4, 8), non-temporal loads
             int v = h->i8_variant & 3;
-            [[maybe_unused]] bool stamp = false;
-#ifdef VDB_ABLATIONS
-            s8.abl_no_bins = (h->i8_variant & 8) ? 1 : 0;
-            stamp = h->i8_variant >= 16;
-            if (stamp) v = 3;
-#endif
             if (h->i8_variant == 4 || h->i8_variant == 5) v = 3;
             if (Qpad % 1024 != 0) v &= 1;
             if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v &= 1;
@@ -726,9 +655,9 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                 else scan_i8x16_kernel<KS2_, 4, 4><<<gridx, dim3(512), 0, st>>>(s8); } while (0)
 #define VDB_X16S(KS2_, NW_) do { \
                 if (ring == 2) scan_i8x16_kernel<KS2_, 4, 4, NW_><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else if (ring == 8 && NW_ >= 2) scan_i8x16_kernel<KS2_, 4, 4, NW_, false, (NW_ >= 2 ? 8 : 4)><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else if (nt) scan_i8x16_kernel<KS2_, 4, 4, NW_, false, 4, 2><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else scan_i8x16_kernel<KS2_, 4, 4, NW_, false, 4><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
+                else if (ring == 8 && NW_ >= 2) scan_i8x16_kernel<KS2_, 4, 4, NW_, (NW_ >= 2 ? 8 : 4)><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
+                else if (nt) scan_i8x16_kernel<KS2_, 4, 4, NW_, 4, 2><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
+                else scan_i8x16_kernel<KS2_, 4, 4, NW_, 4><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
 #define VDB_X16(KS2_) do { \
                 if (nw_small == 1) VDB_X16S(KS2_, 1); else if (nw_small == 2) VDB_X16S(KS2_, 2); \
                 else if (nw_small == 4) VDB_X16S(KS2_, 4); else VDB_X16B(KS2_); } while (0)
@@ -752,17 +681,6 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                 pair_candidate = false;
                 launch_scan(h, sa, g.nchunks, Qpad, st, direct_rows, nw_small);
             }
-#ifdef VDB_ABLATIONS
-            if (stamp) {
-                if (h->i8_ks != 4 || nw_small < 8 || v != 3) throw Error(VDB_ERR_UNSUPPORTED, "the stamped x16 scan exists for D in (64, 128], 1024-query tiles");
-                const size_t words = (size_t)gridx.x * 8 * 8;
-                ws.dense.reserve(words * sizeof(unsigned long long));
-                VDB_HIP(hipMemsetAsync(ws.dense.p, 0, words * sizeof(unsigned long long), st));
-                s8.dbg = ws.dense.as<unsigned long long>();
-                h->dbg_words = words;
-                scan_i8x16_kernel<2, 8, 8, 8, true><<<gridx, dim3(512), 0, st>>>(s8);
-            } else
-#endif
             if (h->i8_ks == 2) VDB_X16(1);
             else VDB_X16(2);
 #undef VDB_X16B
@@ -771,11 +689,6 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
             VDB_HIP(hipGetLastError());
             }
         } else {
-        [[maybe_unused]] bool stamp8 = false;
-#ifdef VDB_ABLATIONS
-        stamp8 = h->i8_variant >= 16;            // +16: in-kernel cycle stamps (exact results) of variant 3 or 6 (others: 1)
-        if (stamp8 && v8 != 6 && v8 != 1) v8 = 3;
-#endif
         const int tb8 = v8 == 6 ? 1 : v8 == 7 ? 2 : 0;             // 6 / 7: variant 3 with a pacing barrier per 1 / 2 tiles
         if (tb8) v8 = 3;
         if (Qpad % 1024 != 0) v8 &= 1;
@@ -784,31 +697,17 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         const int qtile = (v8 > 8) ? 64 * nw_small : (v8 >= 2) ? 1024 : 512;
         s8.nqtiles = (int)((v8 > 8 ? nq + qtile - 1 : Qpad) / qtile);
         const dim3 grid8(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-#ifdef VDB_ABLATIONS
-        if (stamp8) {
-            const size_t words = (size_t)grid8.x * 8 * 8;
-            ws.dense.reserve(words * sizeof(unsigned long long));
-            VDB_HIP(hipMemsetAsync(ws.dense.p, 0, words * sizeof(unsigned long long), st));
-            s8.dbg = ws.dense.as<unsigned long long>();
-            h->dbg_words = words;
-            if (v8 == 3 && h->i8_ks == 4 && h->i8_group == 8 && tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, true, 1><<<grid8, dim3(512), 0, st>>>(s8);
-            else if (v8 == 3 && h->i8_ks == 4 && h->i8_group == 8) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, true><<<grid8, dim3(512), 0, st>>>(s8);
-            else if (h->i8_ks == 4 && h->i8_group == 8) scan_i8_kernel<4, 8, 2, 8, 16, false, 8, true><<<grid8, dim3(512), 0, st>>>(s8);
-            else throw Error(VDB_ERR_UNSUPPORTED, "the stamped int8 scan exists for D in (64, 128] with select groups of 8 rows");
-        } else
-#endif
-        {
 #define VDB_I8G(KS_, ST_, CB_, NW_, G_) scan_i8_kernel<KS_, ST_, CB_, NW_, 16, false, G_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8)
 #define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
         // serving shapes (1 / 2 / 4 waves per workgroup): the scan streams the copy once -- 4- or 8-stage staging ring
         // (option "i8_ring": 0 = auto (4), 2 = the double buffer of the batch shape, 4, 8)
-#define VDB_I8R(KS_, NW_, R_) do { if (h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, false, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
-                                   else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, false, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
+#define VDB_I8R(KS_, NW_, R_) do { if (h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+                                   else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
         // (the wait for a stage is s_waitcnt vmcnt((ring - 2) x requests per wave and stage), a 6-bit counter: a one-wave
         //  workgroup issues all 16 + 2 requests of a 4-tile stage itself, which caps its ring at 4)
 #define VDB_I8S(KS_, NW_) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
                                if (r__ == 2) VDB_I8(KS_, 4, 2, NW_); else if (r__ == 8) VDB_I8R(KS_, NW_, (NW_ >= 2 ? 8 : 4)); \
-                               else if (nt8 && h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, false, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+                               else if (nt8 && h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
                                else VDB_I8R(KS_, NW_, 4); } while (0)
         // serving shapes read every panel byte once per search: non-temporal staging loads (option "i8_nt": 0 / 2 on, 1 off).
         // Measured in one process (scripts/sweep_serving_hbm.py): single-query scan of 4M x 128 (512 MB, HBM) 106.2 -> 96.7 us
@@ -816,11 +715,11 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         const bool nt8 = h->i8_nt != 1;
         if (tb8 && v8 == 3 && h->i8_group == 8) {
             if (h->i8_ks == 2) {
-                if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, false, 1><<<grid8, dim3(512), 0, st>>>(s8);
-                else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, false, 2><<<grid8, dim3(512), 0, st>>>(s8);
+                if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
+                else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
             } else {
-                if (tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, false, 1><<<grid8, dim3(512), 0, st>>>(s8);
-                else scan_i8_kernel<4, 8, 4, 8, 16, false, 8, false, 2><<<grid8, dim3(512), 0, st>>>(s8);
+                if (tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
+                else scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
             }
         } else if (h->i8_ks == 2) {
             switch (v8) { case 1: VDB_I8(2, 8, 2, 8); break; case 2: VDB_I8(2, 4, 4, 8); break; case 3: VDB_I8(2, 8, 4, 8); break;
@@ -837,7 +736,6 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 #undef VDB_I8
 #undef VDB_I8R
 #undef VDB_I8S
-        }
         VDB_HIP(hipGetLastError());
         }
     }

@@ -245,7 +245,7 @@ struct vdb_index_s {
     int upload_block_mb = 0;                 // option "upload_block_mb": staging block size (0 = default 64 MiB)
     int64_t last_upload_blocks = 0;          // blocks of the last host upload (vdb_stats: upload_blocks)
     // options
-    int force_path = 0, timing = 0, list_cap = 0, scan_variant = 0, select_variant = 0, spc_override = 0, kloop_qgroup = 0;
+    int force_path = 0, timing = 0, list_cap = 0, select_variant = 0, spc_override = 0, kloop_qgroup = 0;
     bool small_clear_pending = false;        // search_device_impl left the clearing of ws.small to the first batch (serving-shaped calls)
     bool small_is_clean = false;             // ws.small was cleared for this call and no batch has used it yet
     bool small_preset = false;               // coarse quantizer of an IVF index: the parent has just cleared ws.small (it lives in
@@ -279,7 +279,6 @@ struct vdb_index_s {
     DevBuf ivf_offsets, ivf_ids, ivf_probe_d, ivf_probe_i;
     // list-major MFMA scan (D <= 128): panel space = lists padded to whole 512-row spans
     bool ivf_mfma_ok = false, ivf_last_mfma = false;
-    size_t dbg_words = 0;                    // scan_variant 6: words of per-wave stamps left in ws.dense
     int64_t ivf_pspans = 0;
     int ivf_max_pspans = 0;
     int ivf_span_rows = kSpanRows;           // rows per panel span: 512 (32-row tiles, D <= 128) or 16 * ivf_tps (p16, D > 128)
@@ -484,9 +483,9 @@ void build_rows_i8(vdb_index_s *h, hipStream_t st) {
 void graph_reset(vdb_index_s *h);
 
 // layout "x16" for the scan copies of a D <= 128 flat index, unless an option asks for what only the 32-row kernels have
-// (quads as the candidate group, the A/B schedules and ablations behind scan_variant)
+// (quads as the candidate group)
 bool x16_wanted(const vdb_index_s *h) {
-    return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->f16_group == 8 && h->i8_group == 8 && h->scan_variant == 0;
+    return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->f16_group == 8 && h->i8_group == 8;
 }
 
 // everything derived from the h->N rows in h->x32: statistics, scan copies, biases
@@ -1191,21 +1190,6 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
     });
 }
 
-int vdb_debug_fetch_stamps(vdb_handle hh, unsigned long long *out_host, int64_t max_words, int64_t *nwords) {
-    return guarded([&] {
-        auto *h = check(hh);
-        if (!out_host || !nwords) throw Error(VDB_ERR_INVALID, "null pointer");
-        if (h->multi) multi_unsupported("vdb_debug_fetch_stamps");
-        set_device(h->device);
-        const int64_t n = std::min<int64_t>((int64_t)h->dbg_words, max_words);
-        *nwords = n;
-        if (n > 0) {
-            VDB_HIP(hipDeviceSynchronize());
-            VDB_HIP(hipMemcpy(out_host, h->ws.dense.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-        }
-    });
-}
-
 int vdb_set_option(vdb_handle hh, const char *key, double value) {
     return guarded([&] {
         auto *h = check(hh);
@@ -1294,11 +1278,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
             if (value != 0 && value != 2 && value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "i8_ring must be 0, 2, 4 or 8");
             h->i8_ring = (int)value;
         } else if (k == "i8_variant") {
-#ifdef VDB_ABLATIONS
-            if (value < 0 || value > 23) throw Error(VDB_ERR_INVALID, "i8_variant must be 0..7 (+8, +16)");
-#else
             if (value < 0 || value > 7) throw Error(VDB_ERR_INVALID, "i8_variant must be 0..7");
-#endif
             h->i8_variant = (int)value;
         } else if (k == "kloop_qgroup") {
             if (value < 0 || value > 1024) throw Error(VDB_ERR_INVALID, "kloop_qgroup out of range");
@@ -1315,15 +1295,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         } else if (k == "scan_prio") {
             if (value < 0 || value > 2) throw Error(VDB_ERR_INVALID, "scan_prio must be 0, 1 or 2");
             h->scan_prio = (int)value;
-        } else if (k == "scan_variant") {
-#ifdef VDB_ABLATIONS
-            if (value < 0 || value >= kNumScanVariants) throw Error(VDB_ERR_INVALID, "scan_variant out of range");
-#else
-            // the A/B schedules and the timing-only ablations (some return wrong neighbours) exist only in
-            // -DVDB_ABLATIONS builds (`make ablations`, scripts/sweep_*.py); the shipped library has the one schedule
-            if (value != 0) throw Error(VDB_ERR_UNSUPPORTED, "scan_variant needs a -DVDB_ABLATIONS build of libvdbhip");
-#endif
-            h->scan_variant = (int)value;
         } else if (k == "spans_per_chunk") {  // tuning: rows per workgroup chunk = 512 * value (0 = default 16)
             if (value < 0 || value > 4096) throw Error(VDB_ERR_INVALID, "spans_per_chunk out of range");
             h->spc_override = (int)value;

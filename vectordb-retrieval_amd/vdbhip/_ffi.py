@@ -80,7 +80,6 @@ SIGNATURES = {
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),
-    "vdb_debug_fetch_stamps": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     "vdb_debug_scan_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                       POINTER(c_double)]),
 }
