@@ -55,7 +55,7 @@ enum vdb_status {
 };
 
 /* which search path served the last call (vdb_stats_t.last_path) */
-enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3 };
+enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4 };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -67,7 +67,7 @@ typedef struct vdb_stats_s {
     int64_t last_nq;
     int64_t last_candidates;   /* candidate groups (4 consecutive rows each; 8 on the flat int8 scan) re-scored exactly */
     int64_t last_rescan_bins;  /* 256-row bins re-scanned exactly (collision guard) */
-    int64_t last_fallback_queries; /* queries whose work list overflowed -> exhaustive exact scan */
+    int64_t last_fallback_queries; /* queries whose work list overflowed -> exhaustive exact scan (LSH: exact fallback of the select) */
     float last_scan_ms;        /* mean HIP-event time of the dominant (scan) kernel over the searches recorded since
                                   timing was switched on; 0 if not timed */
     float last_total_ms;       /* same for the whole device pipeline */
@@ -218,6 +218,55 @@ int vdb_ivf_sq8_get_ranges(vdb_handle h, float *vmin_host, float *vdiff_host);
 /* codes of an SQ8 index, uint8 (ntotal, dim), in id (insertion) order */
 int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
 
+/* ---- sign-LSH codes + Hamming candidate scan + exact re-rank -- replaces faiss.IndexLSH(d, nbits) with its defaults as
+ *      FaissLSHIndexer / the LSH branch of FaissSearcher use it (modular.py:182-221, 455-548; the reference's `faiss_lsh`
+ *      config): query -> code -> Hamming top-ncand -> exact top-k, all on the device ------------------------------------------
+ * The entry points live on an ordinary flat handle of vdb_create: the index keeps its float32 rows and scan copies, and
+ * next to them one bit per projection row.  The contract is the library's own, exact and deterministic (FAISS' random
+ * matrix and its order among equal Hamming distances are not reproduced):
+ *   projection  R, float32 (nbits, dim) row-major, given by the caller (the library draws no random numbers); nbits a
+ *               multiple of 32 in [32, 1024]
+ *   bits        s_j(x) = sum_d (double)x[d] * (double)R[j][d], accumulated from 0.0 with d ascending, one rounding per step;
+ *               bit j = (s_j >= 0): -0.0 and 0.0 give 1, NaN gives 0.  (The product of two float32 values is exact in
+ *               float64, so an fma chain and a multiply-then-add chain give the same bits.)  Rows and queries alike; cosine is
+ *               the caller's normalisation, as everywhere in this ABI
+ *   codes       nbits / 32 little-endian uint32 words per row; bit j is bit j % 32 of word j / 32
+ *   candidates  per query the min(ncand, ntotal) rows smallest under (Hamming distance, id), both ascending, returned in
+ *               that order: ids int64 (with id_base), distances int32; missing slots are id -1, distance INT32_MAX
+ *   search      exactly vdb_rerank applied to those candidates (the k best in canonical float64 arithmetic under (key, id),
+ *               flat conventions and padding): bit for bit what "candidates, then vdb_rerank" returns
+ * The select counts instead of sorting (distances are integers in [0, nbits]): a histogram of a row sample bounds the cut
+ * distance from above; one xor + popcount scan counts the pairs below that bound per distance -- which fixes the cut t and the
+ * number m of rows up to it -- and appends them to the query's list (the next power of two >= min(4 ncand + 1024, ntotal)
+ * entries); the entries up to t are sorted by (distance, id).  A query whose list overflowed under the bound is scanned a second
+ * time with its exact t.  A query whose bound was too small, or whose m rows (ties at t included) exceed the list, takes an
+ * exact fallback (full histogram of its distances, then an ordered pass); vdb_stats.last_fallback_queries counts them, option
+ * "lsh_force_fallback" = 1 sends every query there.  vdb_stats.last_path = VDB_PATH_LSH; with option "timing",
+ * last_prep_ms = query codes + sample, last_scan_ms = the scans, last_tail_ms = select + re-rank.
+ * ncand is in [1, 65 536] (VDB_ERR_INVALID above; ncand > ntotal is legal and pads); k follows vdb_rerank (1 .. 2048; k >
+ * ncand pads).  VDB_ERR_STATE: an LSH call before a projection, or before rows.  VDB_ERR_UNSUPPORTED, with a message naming
+ * the reason: a vdb_create_multi handle; an IVF handle (centroids set or a codec chosen; and the IVF calls on a handle that
+ * carries a projection); options "int8_only" / "stream_panels" (no resident float32 rows to encode from or re-rank against),
+ * in either order of the two calls; option "graph" together with the candidate / search calls.
+ * A handle without a projection behaves exactly as before. */
+/* installs R.  With rows already present they are encoded from the resident float32 rows; with none R is only stored.
+ * Every later vdb_add / vdb_add_device encodes the rows it appends (appended codes equal those of one big add).  vdb_reset
+ * drops the codes and keeps R; vdb_destroy frees both; codes and R count in bytes_resident. */
+int vdb_lsh_set_projection(vdb_handle h, int nbits, const float *proj_host);
+/* proj_host may be NULL: nbits only (0 = no projection) */
+int vdb_lsh_get_projection(vdb_handle h, int *nbits, float *proj_host);
+/* codes of the indexed rows, uint32 (ntotal, nbits / 32), in id (insertion) order */
+int vdb_lsh_get_codes(vdb_handle h, uint32_t *codes_host);
+/* ham (nq, ncand) int32, ids (nq, ncand) int64, caller-allocated; host buffers, synchronous */
+int vdb_lsh_candidates(vdb_handle h, const float *q_host, int64_t nq, int ncand, int32_t *ham, int64_t *ids);
+/* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
+int vdb_lsh_candidates_device(vdb_handle h, const float *q_dev, int64_t nq, int ncand, int32_t *ham_dev, int64_t *ids_dev,
+                              void *stream);
+/* D (nq, k) float32, I (nq, k) int64 */
+int vdb_lsh_search(vdb_handle h, const float *q_host, int64_t nq, int k, int ncand, float *D, int64_t *I);
+int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, int ncand, float *D_dev, int64_t *I_dev,
+                          void *stream);
+
 /* Sizes the search workspace for batches of up to nq queries and top-k NOW instead of inside the first search (works on
  * flat and IVF handles after add): one untimed search whose queries are corpus rows.  The reference times its very first
  * batch_search, allocations included (experiment_runner.py:431-437; metrics_methodology.md:119-121: no warm-up) -- the
@@ -265,6 +314,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       rewrites the queries in place.  (The call that drops a stale graph always runs eagerly: on ROCm 7.x an
  *                       executable graph instantiated right behind the destruction of its predecessor faults on its second
  *                       replay -- a runtime defect in graph packet capture, profiles/r04_graph_fault_cause.txt.)
+ *     "lsh_force_fallback"  0 (default) | 1: every query of a vdb_lsh_candidates / vdb_lsh_search call takes the exact fallback
+ *                       of the select (tests; same results)
  *     "graph_recapture_at_once"  diagnostic, 0 (default) | 1: the pre-round-3 ordering, for re-checking that defect
  *                       ($VDBHIP_ALLOC_LOG=<file> logs every allocation / graph event for scripts/graph_fault_analyze.py)
  *   tuning knobs (scripts/sweep_*.py)

@@ -722,6 +722,7 @@ int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist)
         ivf_require(centroids_host != nullptr, VDB_ERR_INVALID, "null centroid pointer");
         ivf_require(nlist >= 1 && nlist <= (1 << 22), VDB_ERR_INVALID, "nlist out of range");
         if (h->multi) return multi_set_centroids(h, centroids_host, nlist);
+        lsh_refuse_ivf(h);
         set_device(h->device);
         graph_reset(h);
         ivf_install_centroids(h, centroids_host, nlist);
@@ -749,6 +750,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         ivf_require(niter >= 0 && niter <= 1000, VDB_ERR_INVALID, "niter out of range");
         if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
         if (h->multi) return multi_train(h, nlist, x_host, n, niter, seed, max_points_per_centroid);
+        lsh_refuse_ivf(h);
         graph_reset(h);
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;
@@ -817,6 +819,7 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
             if (codec == 1) multi_unsupported("the SQ8 codec");
             return;
         }
+        if (codec == 1) lsh_refuse_ivf(h);
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
         if (codec == 1) {
             ivf_require(!h->graph_mode, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");

@@ -1,0 +1,300 @@
+// lsh.inc -- host side of the sign-LSH codes (kernels: lsh.hpp): projection, encoding adds, candidate scan, search.
+// Included by vdbhip.hip; the handle's LSH state lives in vdb_index_s (lsh_*).
+
+namespace {
+
+inline bool lsh_on(const vdb_index_s *h) { return h->lsh_nbits > 0; }
+
+// handles that cannot carry LSH codes (no resident float32 rows in insertion order on ONE device)
+void lsh_refuse_handle(const vdb_index_s *h) {
+    if (h->multi) multi_unsupported("sign-LSH");
+    if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
+        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF index (centroids set or a codec chosen): its rows "
+                                         "sit in list order");
+    if (h->int8_only_opt || h->int8_only)
+        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes need the resident float32 rows: not available with option 'int8_only'");
+    if (h->stream_panels_opt || h->panels_streamed)
+        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available with option 'stream_panels'");
+}
+
+// an IVF entry point on a handle that carries a projection
+void lsh_refuse_ivf(const vdb_index_s *h) {
+    if (!h->multi && lsh_on(h))
+        throw Error(VDB_ERR_UNSUPPORTED, "this handle carries a sign-LSH projection (vdb_lsh_set_projection): it stays a flat index");
+}
+
+// n rows of x (device, `pitch` floats apart) -> codes (n x lsh_wp words)
+void lsh_encode(vdb_index_s *h, const float *x, int64_t n, int64_t pitch, uint32_t *codes, hipStream_t st) {
+    if (n <= 0) return;
+    VDB_HIP(hipMemsetAsync(codes, 0, (size_t)n * h->lsh_wp * sizeof(uint32_t), st));
+    const int64_t items = (n + kLshEncRows - 1) / kLshEncRows * ((h->lsh_nbits + 63) / 64);
+    lsh_encode_kernel<<<dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st>>>(x, n, h->dim, pitch, h->lsh_rt.as<float>(), h->lsh_nbits,
+                                                                             h->lsh_wp, codes);
+    VDB_HIP(hipGetLastError());
+}
+
+// codes of the rows [r0, N) of h->x32 (rows below r0 keep theirs): called behind every add, and by set_projection with r0 = 0
+void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
+    if (!lsh_on(h)) return;
+    if (r0 > h->lsh_rows || r0 > h->N) r0 = 0;
+    h->lsh_rows = 0;
+    if (h->N == 0 || !h->built) return;
+    const size_t row_bytes = (size_t)h->lsh_wp * sizeof(uint32_t);
+    if (r0 == 0) h->lsh_codes.reserve((size_t)h->N * row_bytes);
+    else h->lsh_codes.grow((size_t)h->N * row_bytes, (size_t)r0 * row_bytes);
+    lsh_encode(h, h->x32.as<float>() + (size_t)r0 * h->D4, h->N - r0, h->D4, h->lsh_codes.as<uint32_t>() + (size_t)r0 * h->lsh_wp, st);
+    VDB_HIP(hipStreamSynchronize(st));
+    h->lsh_rows = h->N;
+}
+
+void lsh_require_ready(vdb_index_s *h, const char *what) {
+    if (h->multi) multi_unsupported(what);
+    if (!lsh_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no projection (call vdb_lsh_set_projection first)");
+    if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
+    if (h->graph_mode) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
+    if (h->lsh_rows != h->N) throw Error(VDB_ERR_STATE, "the LSH codes do not cover the rows of this index (a failed add?): vdb_reset and add again");
+}
+
+template <int MODE>
+void launch_lsh_scan(const LshArgs &a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.n + kLshRowTile - 1) / kLshRowTile), (unsigned)((a.nq + kLshQTile - 1) / kLshQTile));
+    switch (a.wp) {
+        case 1: lsh_scan_kernel<MODE, 1><<<grid, dim3(256), 0, st>>>(a); break;
+        case 2: lsh_scan_kernel<MODE, 2><<<grid, dim3(256), 0, st>>>(a); break;
+        case 4: lsh_scan_kernel<MODE, 4><<<grid, dim3(256), 0, st>>>(a); break;
+        case 8: lsh_scan_kernel<MODE, 8><<<grid, dim3(256), 0, st>>>(a); break;
+        case 16: lsh_scan_kernel<MODE, 16><<<grid, dim3(256), 0, st>>>(a); break;
+        default: lsh_scan_kernel<MODE, 32><<<grid, dim3(256), 0, st>>>(a); break;
+    }
+    VDB_HIP(hipGetLastError());
+}
+
+void launch_lsh_sample(const LshArgs &a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.nq + kLshSampleQ - 1) / kLshSampleQ));
+    switch (a.wp) {
+        case 1: lsh_sample_kernel<1><<<grid, dim3(256), 0, st>>>(a); break;
+        case 2: lsh_sample_kernel<2><<<grid, dim3(256), 0, st>>>(a); break;
+        case 4: lsh_sample_kernel<4><<<grid, dim3(256), 0, st>>>(a); break;
+        case 8: lsh_sample_kernel<8><<<grid, dim3(256), 0, st>>>(a); break;
+        case 16: lsh_sample_kernel<16><<<grid, dim3(256), 0, st>>>(a); break;
+        default: lsh_sample_kernel<32><<<grid, dim3(256), 0, st>>>(a); break;
+    }
+    VDB_HIP(hipGetLastError());
+}
+
+constexpr size_t kLshListBudget = (size_t)512 << 20;     // bytes of per-query lists per pass: larger batches go in query chunks
+constexpr size_t kLshCandBudget = (size_t)256 << 20;     // bytes of candidate ids + distances between scan and re-rank
+
+// candidates of nq queries (device) -> ham / ids (device, (nq, ncand)); tslot / mark0: timing (events 0 and 1 around the scans)
+void lsh_candidates_core(vdb_index_s *h, const float *dq, int64_t nq, int ncand, int32_t *ham, int64_t *ids, hipStream_t st, long tslot,
+                         bool mark0) {
+    const int wp = h->lsh_wp, hb = h->lsh_nbits + 1;
+    const int c = (int)std::min<int64_t>(ncand, h->N);
+    int cap = 1;
+    while (cap < std::min<int64_t>(4 * (int64_t)c + 1024, h->N)) cap <<= 1;
+    const int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 1 << 20), (int64_t)(kLshListBudget / ((size_t)cap * 8))));
+    h->lsh_qcodes.reserve((size_t)nq * wp * sizeof(uint32_t));
+    h->lsh_hist.reserve((size_t)nqc * hb * sizeof(int));
+    h->lsh_small.reserve((size_t)nqc * 6 * sizeof(int));
+    h->lsh_list.reserve((size_t)nqc * cap * sizeof(unsigned long long));
+    lsh_encode(h, dq, nq, h->dim, h->lsh_qcodes.as<uint32_t>(), st);
+    LshArgs a{};
+    a.codes = h->lsh_codes.as<uint32_t>();
+    a.n = h->N;
+    a.wp = wp;
+    a.nbits = h->lsh_nbits;
+    a.hb = hb;
+    a.c = c;
+    a.cap = cap;
+    a.ncand = ncand;
+    a.sample_n = std::min<int64_t>(h->N, kLshSampleMax);                       // (N <= the sample: all rows, exact histogram)
+    a.sample_stride = a.sample_n == h->N ? 256 : h->N / (kLshSampleMax / 256);  // first rows of consecutive 256-row runs
+    a.force_fallback = h->lsh_force_fallback;
+    a.id_base = h->id_base;
+    a.hist = h->lsh_hist.as<int>();
+    a.thi = h->lsh_small.as<int>();
+    a.tq = a.thi + nqc;
+    a.cnt = a.tq + nqc;
+    a.flag = a.cnt + nqc;
+    a.tsel = a.flag + nqc;
+    a.msel = a.tsel + nqc;
+    a.scanned0 = a.sample_n != a.n;
+    a.list = h->lsh_list.as<unsigned long long>();
+    a.nflagged = h->lsh_stat.as<unsigned long long>();
+    for (int64_t q0 = 0; q0 < nq; q0 += nqc) {
+        a.nq = std::min<int64_t>(nqc, nq - q0);
+        a.qcodes = h->lsh_qcodes.as<uint32_t>() + (size_t)q0 * wp;
+        a.out_ham = ham + (size_t)q0 * ncand;
+        a.out_ids = ids + (size_t)q0 * ncand;
+        launch_lsh_sample(a, st);
+        if (mark0 && q0 == 0) timing_mark(h, tslot, 0, st);
+        if (a.sample_n != a.n) launch_lsh_scan<0>(a, st);
+        lsh_threshold_kernel<<<dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, st>>>(a);
+        VDB_HIP(hipGetLastError());
+        launch_lsh_scan<1>(a, st);
+        timing_mark(h, tslot, 1, st);
+        lsh_select_kernel<<<dim3((unsigned)a.nq), dim3(256), 0, st>>>(a);
+        VDB_HIP(hipGetLastError());
+    }
+}
+
+void lsh_check_args(vdb_index_s *h, const void *q, int64_t nq, int ncand, const void *o1, const void *o2) {
+    if (ncand < 1 || ncand > kLshMaxCand) throw Error(VDB_ERR_INVALID, "ncand must be in [1, 65536]");
+    if (nq < 0) throw Error(VDB_ERR_INVALID, "negative query count");
+    if (nq > 0 && (!q || !o1 || !o2)) throw Error(VDB_ERR_INVALID, "null pointer");
+    (void)h;
+}
+
+void lsh_begin_call(vdb_index_s *h, int64_t nq, hipStream_t st) {
+    h->lsh_stat.reserve((size_t)kStatShards * kStatStride * sizeof(unsigned long long));
+    VDB_HIP(hipMemsetAsync(h->lsh_stat.p, 0, (size_t)kStatShards * kStatStride * sizeof(unsigned long long), st));
+    h->last.last_nq = nq;
+    h->last.last_path = VDB_PATH_LSH;
+}
+
+void lsh_candidates_impl(vdb_index_s *h, const float *dq, int64_t nq, int ncand, int32_t *ham, int64_t *ids, hipStream_t st) {
+    lsh_begin_call(h, nq, st);
+    const long tslot = timing_begin(h, st);
+    lsh_candidates_core(h, dq, nq, ncand, ham, ids, st, tslot, true);
+    timing_mark(h, tslot, 2, st);
+}
+
+// query -> code -> Hamming top-ncand -> exact top-k (rerank_kernel), in query chunks that bound the candidate buffers
+void lsh_search_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, int ncand, float *D, int64_t *I, hipStream_t st) {
+    if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
+    const int64_t nqs = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(kLshCandBudget / ((size_t)ncand * 12))));
+    h->lsh_cand_i.reserve((size_t)nqs * ncand * sizeof(int64_t));
+    h->lsh_cand_h.reserve((size_t)nqs * ncand * sizeof(int32_t));
+    lsh_begin_call(h, nq, st);
+    const long tslot = timing_begin(h, st);
+    for (int64_t q0 = 0; q0 < nq; q0 += nqs) {
+        const int64_t n = std::min<int64_t>(nqs, nq - q0);
+        const float *qs = dq + (size_t)q0 * h->dim;
+        lsh_candidates_core(h, qs, n, ncand, h->lsh_cand_h.as<int32_t>(), h->lsh_cand_i.as<int64_t>(), st, tslot, q0 == 0);
+        rerank_device_impl(h, qs, n, h->lsh_cand_i.as<int64_t>(), ncand, k, D + (size_t)q0 * k, I + (size_t)q0 * k, st);
+    }
+    timing_mark(h, tslot, 2, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdb_lsh_set_projection(vdb_handle hh, int nbits, const float *proj_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        lsh_refuse_handle(h);
+        if (nbits < 32 || nbits > kLshMaxBits || nbits % 32) throw Error(VDB_ERR_INVALID, "nbits must be a multiple of 32 in [32, 1024]");
+        if (!proj_host) throw Error(VDB_ERR_INVALID, "null projection pointer");
+        set_device(h->device);
+        VDB_HIP(hipDeviceSynchronize());
+        graph_reset(h);
+        const int D = h->dim;
+        h->lsh_proj.assign(proj_host, proj_host + (size_t)nbits * D);
+        std::vector<float> rt((size_t)D * nbits);
+        for (int j = 0; j < nbits; ++j)
+            for (int d = 0; d < D; ++d) rt[(size_t)d * nbits + j] = proj_host[(size_t)j * D + d];
+        h->lsh_nbits = nbits;
+        h->lsh_wp = 1;
+        while (h->lsh_wp < nbits / 32) h->lsh_wp <<= 1;
+        h->lsh_rows = 0;
+        h->lsh_codes.release();
+        h->lsh_rt.reserve_exact(rt.size() * sizeof(float));
+        VDB_HIP(hipMemcpy(h->lsh_rt.p, rt.data(), rt.size() * sizeof(float), hipMemcpyHostToDevice));
+        lsh_encode_rows(h, 0, nullptr);
+    });
+}
+
+int vdb_lsh_get_projection(vdb_handle hh, int *nbits, float *proj_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (!nbits) throw Error(VDB_ERR_INVALID, "null pointer");
+        *nbits = h->multi ? 0 : h->lsh_nbits;
+        if (proj_host && *nbits > 0) memcpy(proj_host, h->lsh_proj.data(), h->lsh_proj.size() * sizeof(float));
+    });
+}
+
+int vdb_lsh_get_codes(vdb_handle hh, uint32_t *codes_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (h->multi) multi_unsupported("vdb_lsh_get_codes");
+        if (!lsh_on(h)) throw Error(VDB_ERR_STATE, "vdb_lsh_get_codes: no projection (call vdb_lsh_set_projection first)");
+        if (!h->built || h->N == 0 || h->lsh_rows != h->N) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
+        if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");
+        set_device(h->device);
+        const int w = h->lsh_nbits / 32, wp = h->lsh_wp;
+        if (w == wp) {
+            VDB_HIP(hipMemcpy(codes_host, h->lsh_codes.p, (size_t)h->N * w * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            return;
+        }
+        std::vector<uint32_t> tmp((size_t)h->N * wp);
+        VDB_HIP(hipMemcpy(tmp.data(), h->lsh_codes.p, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < h->N; ++r) memcpy(codes_host + (size_t)r * w, tmp.data() + (size_t)r * wp, (size_t)w * sizeof(uint32_t));
+    });
+}
+
+int vdb_lsh_candidates_device(vdb_handle hh, const float *q_dev, int64_t nq, int ncand, int32_t *ham_dev, int64_t *ids_dev,
+                              void *stream) {
+    return guarded([&] {
+        auto *h = check(hh);
+        lsh_require_ready(h, "vdb_lsh_candidates_device");
+        lsh_check_args(h, q_dev, nq, ncand, ham_dev, ids_dev);
+        if (nq == 0) return;
+        set_device(h->device);
+        lsh_candidates_impl(h, q_dev, nq, ncand, ham_dev, ids_dev, as_stream(stream));
+    });
+}
+
+int vdb_lsh_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncand, int32_t *ham, int64_t *ids) {
+    return guarded([&] {
+        auto *h = check(hh);
+        lsh_require_ready(h, "vdb_lsh_candidates");
+        lsh_check_args(h, q_host, nq, ncand, ham, ids);
+        if (nq == 0) return;
+        set_device(h->device);
+        ScopedDevBuf dh, di;
+        h->ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
+        dh.reserve((size_t)nq * ncand * sizeof(int32_t));
+        di.reserve((size_t)nq * ncand * sizeof(int64_t));
+        hipStream_t st = nullptr;
+        VDB_HIP(hipMemcpyAsync(h->ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
+        lsh_candidates_impl(h, h->ws.stage_q.as<float>(), nq, ncand, dh.as<int32_t>(), di.as<int64_t>(), st);
+        VDB_HIP(hipMemcpyAsync(ham, dh.p, (size_t)nq * ncand * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(ids, di.p, (size_t)nq * ncand * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+    });
+}
+
+int vdb_lsh_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, int ncand, float *D_dev, int64_t *I_dev, void *stream) {
+    return guarded([&] {
+        auto *h = check(hh);
+        lsh_require_ready(h, "vdb_lsh_search_device");
+        lsh_check_args(h, q_dev, nq, ncand, D_dev, I_dev);
+        if (nq == 0) return;
+        set_device(h->device);
+        lsh_search_impl(h, q_dev, nq, k, ncand, D_dev, I_dev, as_stream(stream));
+    });
+}
+
+int vdb_lsh_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int ncand, float *D, int64_t *I) {
+    return guarded([&] {
+        auto *h = check(hh);
+        lsh_require_ready(h, "vdb_lsh_search");
+        lsh_check_args(h, q_host, nq, ncand, D, I);
+        if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
+        if (nq == 0) return;
+        set_device(h->device);
+        Workspace &ws = h->ws;
+        ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
+        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
+        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
+        hipStream_t st = nullptr;
+        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
+        lsh_search_impl(h, ws.stage_q.as<float>(), nq, k, ncand, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), st);
+        VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+    });
+}
+
+}  // extern "C"

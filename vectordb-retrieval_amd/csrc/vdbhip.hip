@@ -26,6 +26,7 @@
 #include "ivf_kloop.hpp"
 #include "ivf_sq8.hpp"
 #include "dense.hpp"
+#include "lsh.hpp"
 
 using namespace vdb;
 
@@ -296,6 +297,16 @@ struct vdb_index_s {
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
     DevBuf sq8_codes, sq8_list;              // [N][D4] codes and the list of every row, both in list order
     DevBuf sq8_cent, sq8_param;              // centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
+    // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
+    int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
+    int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
+    int lsh_force_fallback = 0;              // option "lsh_force_fallback": every query takes the exact fallback of the select
+    std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
+    DevBuf lsh_rt, lsh_codes;                // R transposed [dim][nbits]; codes [N][lsh_wp]
+    DevBuf lsh_qcodes, lsh_hist, lsh_small, lsh_list, lsh_stat, lsh_cand_i, lsh_cand_h;   // per-search workspace
+    size_t lsh_ws_bytes() const {
+        return lsh_qcodes.cap + lsh_hist.cap + lsh_small.cap + lsh_list.cap + lsh_stat.cap + lsh_cand_i.cap + lsh_cand_h.cap;
+    }
 };
 
 namespace {
@@ -323,6 +334,7 @@ constexpr size_t kMaxTimedCalls = 1024;
 // returns the slot of this call, or -1 when timing is off / the ring is full
 long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
+void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
 
 int kpl_for(int k) {
     int kpl = 1;
@@ -853,7 +865,8 @@ int vdb_destroy(vdb_handle h) {
                          &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
                          &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0, &h->ivf_item_list,
                          &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of,
-                         &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param};
+                         &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param, &h->lsh_rt, &h->lsh_codes, &h->lsh_qcodes,
+                         &h->lsh_hist, &h->lsh_small, &h->lsh_list, &h->lsh_stat, &h->lsh_cand_i, &h->lsh_cand_h};
         for (auto b : all) b->release();
         graph_reset(h);
         if (h->graph_ev) (void)hipEventDestroy(h->graph_ev);
@@ -879,7 +892,9 @@ int vdb_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
         if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, false, nullptr);
         if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
         set_device(h->device);
+        const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
         append_rows(h, x_host, false, n, id_base, nullptr);
+        lsh_encode_rows(h, n0, nullptr);
     });
 }
 
@@ -901,8 +916,9 @@ int vdb_reset(vdb_handle hh) {
         // centroids stay) -- a caller that resets a 38 GB shard to load another corpus gets the memory back
         DevBuf *rows[] = {&h->x32, &h->xnorm2, &h->panels, &h->slab, &h->bias, &h->panels8, &h->bias8, &h->rows8, &h->rowstat8,
                           &h->ivf_offsets, &h->ivf_ids, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
-                          &h->sq8_codes, &h->sq8_list};
+                          &h->sq8_codes, &h->sq8_list, &h->lsh_codes};
         for (auto b : rows) b->release();
+        h->lsh_rows = 0;                       // (the projection stays)
     });
 }
 
@@ -913,7 +929,9 @@ int vdb_add_device(vdb_handle hh, const float *x_dev, int64_t n, int64_t id_base
         if (h->multi) return multi_add(h, x_dev, true, n, id_base, as_stream(stream), false, nullptr);
         if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
         set_device(h->device);
+        const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
         append_rows(h, x_dev, true, n, id_base, as_stream(stream));
+        lsh_encode_rows(h, n0, as_stream(stream));
     });
 }
 
@@ -1111,7 +1129,8 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.metric = h->metric;
         s.corpus_fp16_exact = h->corpus_fp16_exact ? 1 : 0;
         s.bytes_resident = (int64_t)(h->x32.cap + h->xnorm2.cap + h->panels.cap + h->slab.cap + h->bias.cap + h->stats.cap +
-                                     h->panels8.cap + h->bias8.cap + h->rows8.cap + h->rowstat8.cap + h->ws.bytes());
+                                     h->panels8.cap + h->bias8.cap + h->rows8.cap + h->rowstat8.cap + h->ws.bytes() +
+                                     h->lsh_rt.cap + h->lsh_codes.cap + h->lsh_ws_bytes());
         {   // IVF: the CSR arrays, the per-batch plan buffers and the coarse quantizer's own index and workspace
             const DevBuf *ivf[] = {&h->ivf_offsets, &h->ivf_ids, &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0,
                                    &h->ivf_span_row0, &h->ivf_span_valid, &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0,
@@ -1125,7 +1144,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
                                               (h->coarse->ws.small.borrowed ? h->coarse->ws.small.cap : 0));
         }
         s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
-        s.bytes_workspace = (int64_t)h->ws.bytes();
+        s.bytes_workspace = (int64_t)(h->ws.bytes() + h->lsh_ws_bytes());
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
@@ -1167,6 +1186,12 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_candidates = (int64_t)c[0];
             s.last_rescan_bins = (int64_t)c[1];
         }
+        if (h->last.last_path == VDB_PATH_LSH && h->lsh_stat.p) {      // queries of the last LSH call that took the exact fallback
+            std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
+            VDB_HIP(hipDeviceSynchronize());
+            VDB_HIP(hipMemcpy(c.data(), h->lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (int sh = 0; sh < kStatShards; ++sh) s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
+        }
         if (h->ev_used > 0) {  // averages over every search recorded since timing was switched on
             double scan = 0.0, total = 0.0, prep = 0.0, tail = 0.0;
             for (size_t i = 0; i < h->ev_used; ++i) {
@@ -1199,7 +1224,13 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
         if (h->ivf_codec == 1 && value != 0 && (k == "graph" || k == "int8_only" || k == "stream_panels"))
             throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an SQ8 index");
-        if (k == "graph") {
+        if (h->lsh_nbits > 0 && value != 0 && (k == "int8_only" || k == "stream_panels"))
+            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an index with sign-LSH codes (they are encoded from, and "
+                                             "re-ranked against, the resident float32 rows)");
+        if (k == "lsh_force_fallback") {       // 1: every query of an LSH call takes the exact fallback of the select (tests)
+            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "lsh_force_fallback must be 0 or 1");
+            h->lsh_force_fallback = (int)value;
+        } else if (k == "graph") {
             if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "graph must be 0 or 1");
             h->graph_mode = (int)value;
         } else if (k == "graph_recapture_at_once") {   // diagnostic: destroy a stale exec and capture its successor in ONE call
@@ -1312,5 +1343,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 
 }  // extern "C"
 
+#include "lsh.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

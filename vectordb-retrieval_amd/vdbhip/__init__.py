@@ -9,6 +9,7 @@ from .plugin_api import (ALGORITHM_REGISTRY, INDEXER_REGISTRY, SEARCHER_REGISTRY
 from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher, rerank_candidates
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
 from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
+from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
 from . import sharded
 from .sharded import HipShardedApproximateSearch, HipShardedExactSearch, shard_bounds
 
@@ -18,6 +19,6 @@ __all__ = [
     "register_algorithm", "register_indexer", "register_searcher", "HipExactSearch", "HipBruteForceIndexer",
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
     "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
-    "HipShardedExactSearch",
+    "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",
 ]

@@ -18,7 +18,7 @@ import numpy as np
 
 VDB_OK, VDB_ERR_INVALID, VDB_ERR_STATE, VDB_ERR_HIP, VDB_ERR_NOMEM, VDB_ERR_UNSUPPORTED = range(6)
 METRIC_L2, METRIC_IP = 0, 1
-PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf"}
+PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh"}
 
 _LIB_NAME = "libvdbhip.so"
 _lib: Optional[ctypes.CDLL] = None
@@ -77,6 +77,13 @@ SIGNATURES = {
     "vdb_ivf_sq8_set_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vdb_ivf_sq8_get_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vdb_ivf_get_codes": (c_int, [c_void_p, c_void_p]),
+    "vdb_lsh_set_projection": (c_int, [c_void_p, c_int, c_void_p]),
+    "vdb_lsh_get_projection": (c_int, [c_void_p, POINTER(c_int), c_void_p]),
+    "vdb_lsh_get_codes": (c_int, [c_void_p, c_void_p]),
+    "vdb_lsh_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "vdb_lsh_candidates_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_lsh_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "vdb_lsh_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),

@@ -124,6 +124,65 @@ class FlatIndex:
                                         _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
+    # -- sign-LSH codes (vdb_lsh_*): Hamming candidates + exact re-rank -------------------------------
+    def lsh_set_projection(self, projection: np.ndarray) -> None:
+        """Install R (nbits, dim) float32; rows already indexed are encoded now, later adds encode what they append."""
+        r = _ffi.as_f32_c(projection)
+        if r.ndim != 2 or r.shape[1] != self.dim:
+            raise ValueError(f"expected a (nbits, {self.dim}) projection, got {r.shape}")
+        _ffi.check(self._lib.vdb_lsh_set_projection(self._handle(), int(r.shape[0]), _ffi.ptr(r)), build_time=True)
+
+    def lsh_get_projection(self) -> Optional[np.ndarray]:
+        nbits = ctypes.c_int(0)
+        _ffi.check(self._lib.vdb_lsh_get_projection(self._handle(), ctypes.byref(nbits), None))
+        if nbits.value == 0:
+            return None
+        r = np.empty((nbits.value, self.dim), np.float32)
+        _ffi.check(self._lib.vdb_lsh_get_projection(self._handle(), ctypes.byref(nbits), _ffi.ptr(r)))
+        return r
+
+    def lsh_codes(self) -> np.ndarray:
+        """Codes of the indexed rows, uint32 (ntotal, nbits / 32): bit j of a row is bit j % 32 of word j / 32."""
+        nbits = ctypes.c_int(0)
+        _ffi.check(self._lib.vdb_lsh_get_projection(self._handle(), ctypes.byref(nbits), None))
+        codes = np.empty((self.ntotal, nbits.value // 32), np.uint32)
+        _ffi.check(self._lib.vdb_lsh_get_codes(self._handle(), _ffi.ptr(codes)))
+        return codes
+
+    def _lsh_queries(self, queries: np.ndarray) -> np.ndarray:
+        q = _ffi.as_f32_c(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
+        return q
+
+    def lsh_candidates(self, queries: np.ndarray, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Per query the min(ncand, ntotal) rows smallest under (Hamming distance, id): (int32 (nq, ncand), int64 (nq, ncand)),
+        padded with INT32_MAX / -1."""
+        q = self._lsh_queries(queries)
+        ham = np.empty((q.shape[0], int(ncand)), np.int32)
+        ids = np.empty((q.shape[0], int(ncand)), np.int64)
+        _ffi.check(self._lib.vdb_lsh_candidates(self._handle(), _ffi.ptr(q), q.shape[0], int(ncand), _ffi.ptr(ham), _ffi.ptr(ids)))
+        return ham, ids
+
+    def lsh_candidates_device(self, q_ptr: int, nq: int, ncand: int, ham_ptr: int, ids_ptr: int, stream: int = 0) -> None:
+        _ffi.check(self._lib.vdb_lsh_candidates_device(self._handle(), q_ptr, int(nq), int(ncand), ham_ptr, ids_ptr, stream or None))
+
+    def lsh_search(self, queries: np.ndarray, k: int, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-k among the `ncand` Hamming candidates of every query (flat conventions and padding)."""
+        q = self._lsh_queries(queries)
+        D = np.empty((q.shape[0], int(k)), np.float32)
+        I = np.empty((q.shape[0], int(k)), np.int64)
+        _ffi.check(self._lib.vdb_lsh_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), int(ncand), _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+    def lsh_search_device(self, q_ptr: int, nq: int, k: int, ncand: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        _ffi.check(self._lib.vdb_lsh_search_device(self._handle(), q_ptr, int(nq), int(k), int(ncand), d_ptr, i_ptr, stream or None))
+
+    def rerank_device(self, q_ptr: int, nq: int, cand_ptr: int, ncand: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        _ffi.check(self._lib.vdb_rerank_device(self._handle(), q_ptr, int(nq), cand_ptr, int(ncand), int(k), d_ptr, i_ptr, stream or None))
+
     # -- introspection --------------------------------------------------------------------------------
     def stats(self) -> dict:
         s = _ffi.Stats()
