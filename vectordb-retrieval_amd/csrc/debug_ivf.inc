@@ -113,7 +113,7 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
     return guarded([&] {
         auto *h = check(hh);
         if (h->multi) multi_unsupported("vdb_debug_scan_scores");
-        if (!h->built || !h->scan_ok || h->panels_streamed || !h->panels.p) throw Error(VDB_ERR_STATE, "scan copy not available for this index");
+        if (!h->built || !h->scan_ok || h->panels_streamed || !h->scan.panels.p) throw Error(VDB_ERR_STATE, "scan copy not available for this index");
         // panel layouts with a kernel here: p16 (D > 128), "x16" and the 32x32 form (D <= 128)
         const bool t32 = !h->tile16 && !h->x16;
         if (t32 && h->ksteps > kMaxKSteps) throw Error(VDB_ERR_UNSUPPORTED, "debug scores for D > 128 need the p16 panel layout");
@@ -148,13 +148,13 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
         const int64_t tile0 = sp0 * tps, ntiles = (sp1 - sp0) * tps;
         const dim3 grid((unsigned)ntiles, (unsigned)(Qpad / (t32 ? 32 : 16)));
         if (h->tile16)
-            debug_scores16_kernel<<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
+            debug_scores16_kernel<<<grid, dim3(64), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
         else if (h->x16)
-            debug_scores_x16_kernel<<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
+            debug_scores_x16_kernel<<<grid, dim3(64), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>(), h->ksteps / 2);
         else if (h->ksteps == 4)
-            debug_scores_kernel<4><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());
+            debug_scores_kernel<4><<<grid, dim3(64), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());
         else
-            debug_scores_kernel<8><<<grid, dim3(64), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());
+            debug_scores_kernel<8><<<grid, dim3(64), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(), qpanels.as<half8>(), info.as<QueryBatchInfo>(), tile0, ntiles, nq, row0, nrows, h->N, out.as<float>());
         VDB_HIP(hipGetLastError());
         QueryBatchInfo hi;
         VDB_HIP(hipMemcpyAsync(scores_host, out.p, (size_t)nq * nrows * 4, hipMemcpyDeviceToHost, st));
@@ -162,7 +162,6 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
         VDB_HIP(hipMemcpyAsync(&hi, info.p, sizeof(hi), hipMemcpyDeviceToHost, st));
         VDB_HIP(hipStreamSynchronize(st));
         if (cscale) *cscale = (double)hi.cs;
-        dq.release(); info.release(); qpanels.release(); eps.release(); out.release();
     });
 }
 

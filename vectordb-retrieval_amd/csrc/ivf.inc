@@ -36,7 +36,7 @@ void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
 
 // nearest centroid of n device-resident rows (row stride = dim): int64 list ids, left on the device in dI
 void ivf_assign_rows(vdb_index_s *h, const float *x_dev, int64_t n, DevBuf &dI) {
-    ScopedDevBuf dD;
+    DevBuf dD;
     dD.reserve((size_t)n * sizeof(float));
     dI.reserve((size_t)n * sizeof(int64_t));
     search_device_impl(h->coarse, x_dev, n, 1, dD.as<float>(), dI.as<int64_t>(), nullptr, nullptr, nullptr);
@@ -69,7 +69,7 @@ void ivf_csr_build(vdb_index_s *h, const DevBuf &dI, int64_t n, int nlist, DevBu
     while ((double)((n + chunk_rows - 1) / chunk_rows) * nlist > 1.0e8 && chunk_rows < (1 << 20)) chunk_rows *= 2;
     const int64_t nchunks = (n + chunk_rows - 1) / chunk_rows;
     if (nlist <= kCsrMaxLists && (double)nchunks * nlist <= 1.0e8 && n > 0) {
-        ScopedDevBuf hist, total, bad;
+        DevBuf hist, total, bad;
         hist.reserve((size_t)nchunks * nlist * 4);
         total.reserve((size_t)nlist * 4);
         bad.reserve(4);
@@ -133,46 +133,46 @@ void ivf_build_panel_space(vdb_index_s *h) {
     h->ivf_pspans = P;
     h->ivf_max_pspans = maxp;
     if (P == 0) return;
-    h->ivf_list_pspan0.reserve(((size_t)nlist + 1) * 4);
-    h->ivf_span_row0.reserve((size_t)P * 4);
-    h->ivf_span_valid.reserve((size_t)P * 4);
-    VDB_HIP(hipMemcpy(h->ivf_list_pspan0.p, pspan0.data(), ((size_t)nlist + 1) * 4, hipMemcpyHostToDevice));
-    VDB_HIP(hipMemcpy(h->ivf_span_row0.p, row0.data(), (size_t)P * 4, hipMemcpyHostToDevice));
-    VDB_HIP(hipMemcpy(h->ivf_span_valid.p, valid.data(), (size_t)P * 4, hipMemcpyHostToDevice));
+    h->lists.ivf_list_pspan0.reserve(((size_t)nlist + 1) * 4);
+    h->lists.ivf_span_row0.reserve((size_t)P * 4);
+    h->lists.ivf_span_valid.reserve((size_t)P * 4);
+    VDB_HIP(hipMemcpy(h->lists.ivf_list_pspan0.p, pspan0.data(), ((size_t)nlist + 1) * 4, hipMemcpyHostToDevice));
+    VDB_HIP(hipMemcpy(h->lists.ivf_span_row0.p, row0.data(), (size_t)P * 4, hipMemcpyHostToDevice));
+    VDB_HIP(hipMemcpy(h->lists.ivf_span_valid.p, valid.data(), (size_t)P * 4, hipMemcpyHostToDevice));
     const int64_t ntiles = h->tile16 ? P * h->ivf_tps : P * kIvfTilesPerSpan;
     const int ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;           // k-steps of the layout (32 or 16 dims)
-    h->panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
+    h->scan.panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
     const int64_t threads = ntiles * ksl * 64;
     if (h->tile16)
         ivf_build_panels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-            h->x32.as<float>(), h->dim, h->D4, ksl, h->ivf_tps, ntiles, h->sx, h->ivf_span_row0.as<int32_t>(),
-            h->ivf_span_valid.as<int32_t>(), h->panels.as<half8>(), h->stats.as<IndexStats>());
+            h->rows.x32.as<float>(), h->dim, h->D4, ksl, h->ivf_tps, ntiles, h->sx, h->lists.ivf_span_row0.as<int32_t>(),
+            h->lists.ivf_span_valid.as<int32_t>(), h->scan.panels.as<half8>(), h->kept.stats.as<IndexStats>());
     else
         ivf_build_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-            h->x32.as<float>(), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->ivf_span_row0.as<int32_t>(),
-            h->ivf_span_valid.as<int32_t>(), h->panels.as<half8>(), h->stats.as<IndexStats>());
+            h->rows.x32.as<float>(), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->lists.ivf_span_row0.as<int32_t>(),
+            h->lists.ivf_span_valid.as<int32_t>(), h->scan.panels.as<half8>(), h->kept.stats.as<IndexStats>());
     VDB_HIP(hipGetLastError());
-    h->bias.reserve((size_t)P * span_rows * sizeof(float));
+    h->scan.bias.reserve((size_t)P * span_rows * sizeof(float));
     ivf_build_bias_kernel<<<dim3((unsigned)((P * span_rows + 255) / 256)), dim3(256), 0, st>>>(
-        h->xnorm2.as<float>(), P, span_rows, h->metric, h->ivf_span_row0.as<int32_t>(), h->ivf_span_valid.as<int32_t>(),
-        h->bias.as<float>());
+        h->rows.xnorm2.as<float>(), P, span_rows, h->metric, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
+        h->scan.bias.as<float>());
     VDB_HIP(hipGetLastError());
     IndexStats hs;
-    VDB_HIP(hipMemcpy(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost));
+    VDB_HIP(hipMemcpy(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost));
     h->corpus_fp16_exact = hs.not_fp16_exact == 0;
     h->i8_ok = h->i8_ok && !h->tile16 && h->ivf_codec == 0;   // (an SQ8 index keeps no int8 copies)
     if (h->i8_ok) {      // byte-valued rows: int8 copy of the same panel space (scan_i8.hpp)
         h->i8_ks = h->dim <= 64 ? 2 : 4;
-        h->panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
+        h->scan.panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
         const int64_t t8 = ntiles * h->i8_ks * 64;
         ivf_build_panels_i8_kernel<<<dim3((unsigned)((t8 + 255) / 256)), dim3(256), 0, st>>>(
-            h->x32.as<float>(), h->dim, h->D4, h->i8_ks, ntiles, h->i8_cx, h->ivf_span_row0.as<int32_t>(),
-            h->ivf_span_valid.as<int32_t>(), h->panels8.as<int4v>());
-        h->bias8.reserve((size_t)2 * P * kIvfSpanRows * sizeof(int32_t));
-        h->rowstat8.reserve((size_t)h->N * 2 * sizeof(int));
+            h->rows.x32.as<float>(), h->dim, h->D4, h->i8_ks, ntiles, h->i8_cx, h->lists.ivf_span_row0.as<int32_t>(),
+            h->lists.ivf_span_valid.as<int32_t>(), h->scan.panels8.as<int4v>());
+        h->scan.bias8.reserve((size_t)2 * P * kIvfSpanRows * sizeof(int32_t));
+        h->scan.rowstat8.reserve((size_t)h->N * 2 * sizeof(int));
         ivf_build_bias_i8_kernel<<<dim3((unsigned)((P * kIvfSpanRows + 255) / 256)), dim3(256), 0, st>>>(
-            h->x32.as<float>(), P, h->dim, h->D4, h->metric, h->ivf_span_row0.as<int32_t>(),
-            h->ivf_span_valid.as<int32_t>(), h->bias8.as<int32_t>(), h->rowstat8.as<int>());
+            h->rows.x32.as<float>(), P, h->dim, h->D4, h->metric, h->lists.ivf_span_row0.as<int32_t>(),
+            h->lists.ivf_span_valid.as<int32_t>(), h->scan.bias8.as<int32_t>(), h->scan.rowstat8.as<int>());
         build_rows_i8(h, st);
         VDB_HIP(hipGetLastError());
         VDB_HIP(hipStreamSynchronize(st));
@@ -273,7 +273,7 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     const int rescan_cap = std::max(16, k / 2 + 8);
     ws.eps.reserve((size_t)nb * sizeof(float));
     ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
-    const bool use_i8 = h->i8_ok && !h->i8_disable && h->panels8.p != nullptr;
+    const bool use_i8 = h->i8_ok && !h->i8_disable && h->scan.panels8.p != nullptr;
     if (use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);          // int8 query rows
     ws.bin_m1.reserve(bin_bytes);
     ws.bin_m2.reserve(bin_bytes);
@@ -289,16 +289,16 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     int32_t *d_cursor = d_cnt + nlist, *d_slot_query = d_cursor + nlist;
     int32_t *d_fb_done = d_slot_query + max_slots;
     ws.fb_list.reserve((size_t)nb * sizeof(int32_t));
-    h->ivf_slot_off.reserve(((size_t)nlist + 1) * 4);
-    h->ivf_list_item0.reserve(((size_t)nlist + 1) * 4);
-    h->ivf_item_list.reserve((size_t)max_items * 4);
-    h->ivf_item_slot0.reserve((size_t)max_items * 4);
-    h->ivf_item_bin0.reserve((size_t)max_items * 4);
-    h->ivf_plan.reserve(sizeof(IvfPlan));
-    h->ivf_slot_of.reserve((size_t)pairs * 4);
+    h->plan.ivf_slot_off.reserve(((size_t)nlist + 1) * 4);
+    h->plan.ivf_list_item0.reserve(((size_t)nlist + 1) * 4);
+    h->plan.ivf_item_list.reserve((size_t)max_items * 4);
+    h->plan.ivf_item_slot0.reserve((size_t)max_items * 4);
+    h->plan.ivf_item_bin0.reserve((size_t)max_items * 4);
+    h->plan.ivf_plan.reserve(sizeof(IvfPlan));
+    h->plan.ivf_slot_of.reserve((size_t)pairs * 4);
 
-    const int64_t *probes = h->ivf_probe_i.as<int64_t>();
-    IvfPlan *plan = h->ivf_plan.as<IvfPlan>();
+    const int64_t *probes = h->plan.ivf_probe_i.as<int64_t>();
+    IvfPlan *plan = h->plan.ivf_plan.as<IvfPlan>();
     const bool small_ppb = pairs < 256 * (int64_t)kIvfPairsPerBlock && nlist <= 2048;   // (fewer than 256 workgroups otherwise)
     const int ppb = small_ppb ? kIvfPairsPerBlock / 4 : kIvfPairsPerBlock;
     const unsigned pblocks = (unsigned)((pairs + ppb - 1) / ppb);
@@ -333,46 +333,46 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     if (hist_bytes) {      // plan + scatter in one dispatch (every workgroup recomputes the slot prefix in LDS)
         if (small_ppb)
             ivf_plan_scatter_kernel<kIvfPairsPerBlock / 4><<<dim3(pblocks), dim3(256), 2 * hist_bytes, st>>>(
-                probes, nb, nprobe, nlist, d_cnt, h->ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
-                (int)max_items, (int)max_slots, (int)max_bins, h->ivf_offsets.as<int64_t>(), h->ivf_slot_off.as<int32_t>(),
-                h->ivf_list_item0.as<int32_t>(), h->ivf_item_list.as<int32_t>(), h->ivf_item_slot0.as<int32_t>(),
-                h->ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->ivf_slot_of.as<int32_t>());
+                probes, nb, nprobe, nlist, d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
+                (int)max_items, (int)max_slots, (int)max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
+                h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
+                h->plan.ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
         else
             ivf_plan_scatter_kernel<kIvfPairsPerBlock><<<dim3(pblocks), dim3(256), 2 * hist_bytes, st>>>(
-                probes, nb, nprobe, nlist, d_cnt, h->ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
-                (int)max_items, (int)max_slots, (int)max_bins, h->ivf_offsets.as<int64_t>(), h->ivf_slot_off.as<int32_t>(),
-                h->ivf_list_item0.as<int32_t>(), h->ivf_item_list.as<int32_t>(), h->ivf_item_slot0.as<int32_t>(),
-                h->ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->ivf_slot_of.as<int32_t>());
+                probes, nb, nprobe, nlist, d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
+                (int)max_items, (int)max_slots, (int)max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
+                h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
+                h->plan.ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     } else {
-    ivf_plan_kernel<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, h->ivf_list_pspan0.as<int32_t>(), nlist,
+    ivf_plan_kernel<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), nlist,
                                                  group, bins_per_span, run_groups, (int)max_items, (int)max_slots, (int)max_bins,
-                                                 h->ivf_slot_off.as<int32_t>(), h->ivf_list_item0.as<int32_t>(),
-                                                 h->ivf_item_list.as<int32_t>(), h->ivf_item_slot0.as<int32_t>(),
-                                                 h->ivf_item_bin0.as<int32_t>(), plan, h->ivf_offsets.as<int64_t>());
+                                                 h->plan.ivf_slot_off.as<int32_t>(), h->plan.ivf_list_item0.as<int32_t>(),
+                                                 h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
+                                                 h->plan.ivf_item_bin0.as<int32_t>(), plan, h->lists.ivf_offsets.as<int64_t>());
     if (small_ppb)
         ivf_scatter_kernel<kIvfPairsPerBlock / 4><<<dim3(pblocks), dim3(256), hist_bytes, st>>>(
-            probes, nb, nprobe, nlist, h->ivf_slot_off.as<int32_t>(), h->ivf_list_pspan0.as<int32_t>(),
-            d_cursor, plan, d_slot_query, h->ivf_slot_of.as<int32_t>());
+            probes, nb, nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(),
+            d_cursor, plan, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     else
         ivf_scatter_kernel<kIvfPairsPerBlock><<<dim3(pblocks), dim3(256), hist_bytes, st>>>(
-            probes, nb, nprobe, nlist, h->ivf_slot_off.as<int32_t>(), h->ivf_list_pspan0.as<int32_t>(),
-            d_cursor, plan, d_slot_query, h->ivf_slot_of.as<int32_t>());
+            probes, nb, nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(),
+            d_cursor, plan, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     }
     VDB_HIP(hipGetLastError());
 
     ScanArgs sa{};
-    sa.panels = h->panels.as<half8>();
+    sa.panels = h->scan.panels.as<half8>();
     if (sq8(h)) {      // SQ8: the fp16 panels of the whole panel space, converted from the codes for this batch (workspace)
         const int64_t ntiles = h->ivf_pspans * kIvfTilesPerSpan;
         ws.sq8_panels.reserve((size_t)ntiles * h->ksteps * 64 * sizeof(half8));
         const int64_t threads = ntiles * h->ksteps * 64;
         ivf_sq8_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-            sq8_rows(h), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->ivf_span_row0.as<int32_t>(), h->ivf_span_valid.as<int32_t>(),
+            sq8_rows(h), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
             ws.sq8_panels.as<half8>());
         VDB_HIP(hipGetLastError());
         sa.panels = ws.sq8_panels.as<half8>();
     }
-    sa.bias = h->bias.as<float>();
+    sa.bias = h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
     sa.slot_query = d_slot_query;
@@ -380,11 +380,11 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     sa.bin_m1 = ws.bin_m1.as<float>();
     sa.bin_m2 = ws.bin_m2.as<float>();
     sa.bin_m3 = ws.bin_m3.as<float>();
-    sa.item_list = h->ivf_item_list.as<int32_t>();
-    sa.item_slot0 = h->ivf_item_slot0.as<int32_t>();
-    sa.item_bin0 = h->ivf_item_bin0.as<int32_t>();
+    sa.item_list = h->plan.ivf_item_list.as<int32_t>();
+    sa.item_slot0 = h->plan.ivf_item_slot0.as<int32_t>();
+    sa.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
     sa.n_items = &plan->n_items;
-    sa.list_pspan0 = h->ivf_list_pspan0.as<int32_t>();
+    sa.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
     timing_mark(h, tslot, 0, st);
     {
         // long lists are cut into row parts of `part` spans (256 rows each), one workgroup per (item, part): the scan's
@@ -445,8 +445,8 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
         VDB_HIP(hipGetLastError());
         if (use_i8) {      // the int8 form of the same scan; whichever the finalize kernel did not choose returns at once
             ScanI8Args s8{};
-            s8.panels = h->panels8.as<int4v>();
-            s8.bias8 = h->bias8.as<int32_t>();
+            s8.panels = h->scan.panels8.as<int4v>();
+            s8.bias8 = h->scan.bias8.as<int32_t>();
             s8.info = info;
             s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2; s8.bin_m3 = sa.bin_m3;
             s8.Npad = h->ivf_pspans * kIvfSpanRows;
@@ -490,13 +490,13 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     se.info = info;
     se.plan = plan;
     se.probes = probes;
-    se.slot_of = h->ivf_slot_of.as<int32_t>();
-    se.slot_off = h->ivf_slot_off.as<int32_t>();
-    se.list_item0 = h->ivf_list_item0.as<int32_t>();
-    se.item_bin0 = h->ivf_item_bin0.as<int32_t>();
-    se.list_pspan0 = h->ivf_list_pspan0.as<int32_t>();
-    se.span_row0 = h->ivf_span_row0.as<int32_t>();
-    se.span_valid = h->ivf_span_valid.as<int32_t>();
+    se.slot_of = h->plan.ivf_slot_of.as<int32_t>();
+    se.slot_off = h->plan.ivf_slot_off.as<int32_t>();
+    se.list_item0 = h->plan.ivf_list_item0.as<int32_t>();
+    se.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
+    se.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
+    se.span_row0 = h->lists.ivf_span_row0.as<int32_t>();
+    se.span_valid = h->lists.ivf_span_valid.as<int32_t>();
     se.nq = nb;
     se.nprobe = nprobe;
     se.group = group;
@@ -530,12 +530,12 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
                         (size_t)2 * ivf_select_lds_words(se.vals_entries, se.probe_cap, se.act_cap, se.nm) * 4, st>>>(se);
     VDB_HIP(hipGetLastError());
 
-    RefineCommon rc{h->x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, h->ivf_ids.as<int64_t>()};
+    RefineCommon rc{h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     rc.info = info;
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
-    if (use_i8 && h->rows8.p) {
-        rc.X8 = h->rows8.as<signed char>();
-        rc.rowstat = h->rowstat8.as<int>();
+    if (use_i8 && h->scan.rows8.p) {
+        rc.X8 = h->scan.rows8.as<signed char>();
+        rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
         rc.x8_pitch = h->rows8_pitch;
         rc.cx = h->i8_cx;
@@ -559,7 +559,7 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
     // split on the device
     IvfFallbackArgs a{};
     a.c = rc;
-    a.offsets = h->ivf_offsets.as<int64_t>();
+    a.offsets = h->lists.ivf_offsets.as<int64_t>();
     a.probes = probes;
     a.nprobe = nprobe;
     a.fb_list = se.fb_list;
@@ -585,15 +585,15 @@ void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const f
 // (re)size ivf_zero and point both ws.small at it: [coarse small | own small | counter block of `cnt_words` ints]
 int32_t *ivf_bind_zero(vdb_index_s *h, size_t cnt_words) {
     const size_t need = 2 * kZeroSmall + cnt_words * 4;
-    if (need > h->ivf_zero.cap || h->ws.small.p != (char *)h->ivf_zero.p + kZeroSmall) {
+    if (need > h->plan.ivf_zero.cap || h->ws.small.p != (char *)h->plan.ivf_zero.p + kZeroSmall) {
         // (dropping the views first: reserve() may free the memory they point into)
         h->ws.small.release();
         if (h->coarse) h->coarse->ws.small.release();
-        h->ivf_zero.reserve(need);
-        h->ws.small.borrow((char *)h->ivf_zero.p + kZeroSmall, kSmallBytes);
+        h->plan.ivf_zero.reserve(need);
+        h->ws.small.borrow((char *)h->plan.ivf_zero.p + kZeroSmall, kSmallBytes);
     }
-    if (h->coarse && h->coarse->ws.small.p != h->ivf_zero.p) h->coarse->ws.small.borrow(h->ivf_zero.p, kSmallBytes);
-    return reinterpret_cast<int32_t *>((char *)h->ivf_zero.p + 2 * kZeroSmall);
+    if (h->coarse && h->coarse->ws.small.p != h->plan.ivf_zero.p) h->coarse->ws.small.borrow(h->plan.ivf_zero.p, kSmallBytes);
+    return reinterpret_cast<int32_t *>((char *)h->plan.ivf_zero.p + 2 * kZeroSmall);
 }
 
 void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *PK,
@@ -621,16 +621,16 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         const IvfGeom geom = ivf_geometry(h, nb, k, nprobe);
         int32_t *d_cnt = ivf_bind_zero(h, geom.ok ? geom.cnt_words : 0);
         if (b0 == 0) {
-            VDB_HIP(hipMemsetAsync(h->ivf_zero.p, 0, 2 * kZeroSmall + (geom.ok ? geom.cnt_words * 4 : 0), st));
+            VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (geom.ok ? geom.cnt_words * 4 : 0), st));
         } else {
-            VDB_HIP(hipMemsetAsync(h->ivf_zero.p, 0, kZeroSmall + 64, st));
+            VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, kZeroSmall + 64, st));
             if (geom.ok) VDB_HIP(hipMemsetAsync(d_cnt, 0, geom.cnt_words * 4, st));
         }
         h->coarse->small_preset = true;
         const long tslot = timing_begin(h, st);
-        h->ivf_probe_d.reserve((size_t)nb * nprobe * sizeof(float));
-        h->ivf_probe_i.reserve((size_t)nb * nprobe * sizeof(int64_t));
-        search_device_impl(h->coarse, q, nb, nprobe, h->ivf_probe_d.as<float>(), h->ivf_probe_i.as<int64_t>(), nullptr,
+        h->plan.ivf_probe_d.reserve((size_t)nb * nprobe * sizeof(float));
+        h->plan.ivf_probe_i.reserve((size_t)nb * nprobe * sizeof(int64_t));
+        search_device_impl(h->coarse, q, nb, nprobe, h->plan.ivf_probe_d.as<float>(), h->plan.ivf_probe_i.as<int64_t>(), nullptr,
                            nullptr, st);
         const float *qpad = q;
         if (D4 != Dm) {
@@ -658,10 +658,10 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nb * k * 16));
         S = std::min<int64_t>(S, cap);
         IvfScanArgs a{};
-        a.c = RefineCommon{h->x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, h->ivf_ids.as<int64_t>()};
+        a.c = RefineCommon{h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
         if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
-        a.offsets = h->ivf_offsets.as<int64_t>();
-        a.probes = h->ivf_probe_i.as<int64_t>();
+        a.offsets = h->lists.ivf_offsets.as<int64_t>();
+        a.probes = h->plan.ivf_probe_i.as<int64_t>();
         a.nq = nb;
         a.nprobe = nprobe;
         a.S = (int)S;
@@ -766,7 +766,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         std::vector<float> sample((size_t)ns * Dm);
         for (int64_t i = 0; i < ns; ++i)
             memcpy(&sample[(size_t)i * Dm], x_host + (size_t)pick[(size_t)i] * Dm, (size_t)Dm * sizeof(float));
-        ScopedDevBuf raw, padded, dperm, doff, dcent;
+        DevBuf raw, padded, dperm, doff, dcent;
         raw.reserve((size_t)ns * Dm * 4);
         padded.reserve((size_t)ns * D4 * 4);
         VDB_HIP(hipMemcpy(raw.p, sample.data(), (size_t)ns * Dm * 4, hipMemcpyHostToDevice));
@@ -777,7 +777,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         std::vector<float> cent(sample.begin(), sample.begin() + (size_t)nlist * Dm);  // init: first nlist draws
         const int spherical = h->metric == VDB_METRIC_IP ? 1 : 0;
         std::vector<int64_t> offsets;
-        ScopedDevBuf dassign;
+        DevBuf dassign;
         for (int it = 0; it < niter; ++it) {
             ivf_install_centroids(h, cent.data(), nlist);
             ivf_assign_rows(h, raw.as<float>(), ns, dassign);
@@ -883,8 +883,8 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
         std::vector<unsigned char> c((size_t)h->N * D4);
         std::vector<int64_t> ids((size_t)h->N);
         VDB_HIP(hipDeviceSynchronize());
-        VDB_HIP(hipMemcpy(c.data(), h->sq8_codes.p, c.size(), hipMemcpyDeviceToHost));
-        VDB_HIP(hipMemcpy(ids.data(), h->ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(c.data(), h->codes.sq8_codes.p, c.size(), hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
             memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * Dm, &c[(size_t)r * D4], (size_t)Dm);
     });
@@ -918,11 +918,11 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         h->built = false;
         std::vector<int64_t> assign_new((size_t)n);
         if (N1 > 0) {
-            ScopedDevBuf raw, src, src_ids, dperm, dassign, doff;
+            DevBuf raw, src, src_ids, dperm, dassign, doff;
             // ONE pass over the host rows (row blocks through the pinned staging buffers); the unpadded copy the coarse
             // assignment reads is made on the device
             src.reserve((size_t)N1 * D4 * 4);
-            if (N0) VDB_HIP(hipMemcpy(src.p, h->x32.p, (size_t)N0 * D4 * 4, hipMemcpyDeviceToDevice));
+            if (N0) VDB_HIP(hipMemcpy(src.p, h->rows.x32.p, (size_t)N0 * D4 * 4, hipMemcpyDeviceToDevice));
             float *fresh = src.as<float>() + (size_t)N0 * D4;
             if (D4 != Dm) VDB_HIP(hipMemset(fresh, 0, (size_t)n * D4 * 4));
             upload_rows(h, fresh, D4, x_host, n, Dm, nullptr);
@@ -936,7 +936,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
                                         hipMemcpyDeviceToDevice));
                     unpadded = raw.as<float>();
                 }
-                ScopedDevBuf dnew;
+                DevBuf dnew;
                 ivf_assign_rows(h, unpadded, n, dnew);
                 VDB_HIP(hipMemcpy(assign_new.data(), dnew.p, (size_t)n * 8, hipMemcpyDeviceToHost));
                 raw.release();
@@ -953,17 +953,17 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
                 std::vector<int64_t> ids_new((size_t)n);
                 for (int64_t i = 0; i < n; ++i) ids_new[(size_t)i] = h->id_base + N0 + i;
                 src_ids.reserve((size_t)N1 * 8);
-                VDB_HIP(hipMemcpy(src_ids.p, h->ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
+                VDB_HIP(hipMemcpy(src_ids.p, h->lists.ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
                 VDB_HIP(hipMemcpy(src_ids.as<int64_t>() + N0, ids_new.data(), (size_t)n * 8, hipMemcpyHostToDevice));
             }
             ivf_csr_build(h, dassign, N1, h->nlist, dperm, doff, h->ivf_offsets_host);
             dassign.release();
-            h->x32.reserve((size_t)N1 * D4 * 4);
-            h->ivf_ids.reserve((size_t)N1 * 8);
+            h->rows.x32.reserve((size_t)N1 * D4 * 4);
+            h->lists.ivf_ids.reserve((size_t)N1 * 8);
             const int64_t total = N1 * (D4 / 4);
             gather_rows_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr>>>(
                 src.as<float>(), dperm.as<int32_t>(), N1, D4, id_base, N0 ? src_ids.as<int64_t>() : nullptr,
-                h->x32.as<float>(), h->ivf_ids.as<int64_t>());
+                h->rows.x32.as<float>(), h->lists.ivf_ids.as<int64_t>());
             VDB_HIP(hipGetLastError());
             VDB_HIP(hipDeviceSynchronize());
         } else {
@@ -971,8 +971,8 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         }
         h->N = N1;
         h->id_base = id_base;
-        h->ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
-        VDB_HIP(hipMemcpy(h->ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8,
+        h->lists.ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
+        VDB_HIP(hipMemcpy(h->lists.ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8,
                           hipMemcpyHostToDevice));
         h->ivf_list_of_row.resize((size_t)N1);              // (in insertion order: the stored part stays)
         for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
@@ -1056,38 +1056,28 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
         ivf_require(nq >= 0 && nq <= (1ll << 24), VDB_ERR_INVALID, "query count out of range");
         if (nq == 0 || h->N == 0) return;
         set_device(h->device);
-        Workspace &ws = h->ws;
-        const size_t row = (size_t)h->dim * sizeof(float);
-        ws.stage_q.reserve((size_t)nq * row);
-        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
-        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
-        hipStream_t st = nullptr;
         // the host-API transfers of that batch once, from / to a scratch host buffer: the runtime sets up its staging for
         // pageable copies of this size on first use
-        std::vector<char> host(std::max((size_t)nq * row, (size_t)nq * k * sizeof(int64_t)));
-        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, host.data(), (size_t)nq * row, hipMemcpyHostToDevice, st));
-        for (int64_t q0 = 0; q0 < nq; q0 += h->N) {      // queries = corpus rows (wrapping around a corpus smaller than the batch)
-            const int64_t m = std::min<int64_t>(h->N, nq - q0);
-            if (h->int8_only)     // (no float32 rows: the int8 rows, converted)
-                rows_i8_to_float_kernel<<<dim3((unsigned)((m * h->dim + 255) / 256)), dim3(256), 0, st>>>(
-                    h->rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, ws.stage_q.as<float>() + (size_t)q0 * h->dim);
-            else if (sq8(h))      // (codes: the decoded rows x^)
-                sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((m * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
-                    sq8_rows(h), m, h->dim, h->D4, h->dim, ws.stage_q.as<float>() + (size_t)q0 * h->dim);
-            else
-            VDB_HIP(hipMemcpy2DAsync(ws.stage_q.as<char>() + (size_t)q0 * row, row, h->x32.p, (size_t)h->D4 * sizeof(float), row,
-                                     (size_t)m, hipMemcpyDeviceToDevice, st));
-        }
-        if (h->ivf_built)
-            ivf_search_device_impl(h, ws.stage_q.as<float>(), nq, k, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), nullptr,
-                                   nullptr, st);
-        else
-            search_device_impl(h, ws.stage_q.as<float>(), nq, k, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), nullptr,
-                               nullptr, st);
-        VDB_HIP(hipMemcpyAsync(host.data(), ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
-        VDB_HIP(hipMemcpyAsync(host.data(), ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        const size_t row = (size_t)h->dim * sizeof(float);
+        std::vector<char> host(std::max((size_t)nq * row, (size_t)nq * k * (sizeof(int64_t) + sizeof(float))));
+        int64_t *I = reinterpret_cast<int64_t *>(host.data());
+        float *D = reinterpret_cast<float *>(host.data() + (size_t)nq * k * sizeof(int64_t));
+        run_staged(h, reinterpret_cast<const float *>(host.data()), nq, k, D, I, [&](float *dq, float *dD, int64_t *dI, hipStream_t st) {
+            for (int64_t q0 = 0; q0 < nq; q0 += h->N) {      // queries = corpus rows (wrapping around a corpus smaller than the batch)
+                const int64_t m = std::min<int64_t>(h->N, nq - q0);
+                if (h->int8_only)     // (no float32 rows: the int8 rows, converted)
+                    rows_i8_to_float_kernel<<<dim3((unsigned)((m * h->dim + 255) / 256)), dim3(256), 0, st>>>(
+                        h->scan.rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, dq + (size_t)q0 * h->dim);
+                else if (sq8(h))      // (codes: the decoded rows x^)
+                    sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((m * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
+                        sq8_rows(h), m, h->dim, h->D4, h->dim, dq + (size_t)q0 * h->dim);
+                else
+                    VDB_HIP(hipMemcpy2DAsync(reinterpret_cast<char *>(dq) + (size_t)q0 * row, row, h->rows.x32.p, (size_t)h->D4 * sizeof(float), row,
+                                             (size_t)m, hipMemcpyDeviceToDevice, st));
+            }
+            if (h->ivf_built) ivf_search_device_impl(h, dq, nq, k, dD, dI, nullptr, nullptr, st);
+            else search_device_impl(h, dq, nq, k, dD, dI, nullptr, nullptr, st);
+        });
     });
 }
 
@@ -1103,17 +1093,9 @@ int vdb_ivf_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float 
         ivf_require(q_host && D && I, VDB_ERR_INVALID, "null pointer");
         if (h->multi) return multi_search(h, q_host, false, nq, k, D, I, nullptr, nullptr, nullptr, true);
         set_device(h->device);
-        Workspace &ws = h->ws;
-        ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
-        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
-        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
-        hipStream_t st = nullptr;
-        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-        ivf_search_device_impl(h, ws.stage_q.as<float>(), nq, k, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), nullptr,
-                               nullptr, st);
-        VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
+            ivf_search_device_impl(h, dq, nq, k, dD, dI, nullptr, nullptr, st);
+        });
     });
 }
 

@@ -11,8 +11,8 @@ constexpr int64_t kSq8TrainRows = 100000;      // rows the range training reads 
 inline bool sq8(const vdb_index_s *h) { return h->ivf_codec == 1; }
 
 Sq8Rows sq8_rows(const vdb_index_s *h) {
-    return Sq8Rows{h->sq8_codes.as<unsigned char>(), h->sq8_list.as<int32_t>(), h->sq8_cent.as<float>(),
-                   h->sq8_param.as<float>(), h->sq8_param.as<float>() + h->D4};
+    return Sq8Rows{h->codes.sq8_codes.as<unsigned char>(), h->codes.sq8_list.as<int32_t>(), h->kept.sq8_cent.as<float>(),
+                   h->kept.sq8_param.as<float>(), h->kept.sq8_param.as<float>() + h->D4};
 }
 
 // the installed centroids, zero padded to D4 (host)
@@ -30,16 +30,16 @@ void sq8_upload_params(vdb_index_s *h) {
     std::vector<float> p((size_t)2 * D4, 0.f);
     memcpy(&p[0], h->sq8_vmin.data(), (size_t)Dm * sizeof(float));
     memcpy(&p[(size_t)D4], h->sq8_vdiff.data(), (size_t)Dm * sizeof(float));
-    h->sq8_cent.reserve(c.size() * sizeof(float));
-    h->sq8_param.reserve(p.size() * sizeof(float));
-    VDB_HIP(hipMemcpy(h->sq8_cent.p, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
-    VDB_HIP(hipMemcpy(h->sq8_param.p, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->kept.sq8_cent.reserve(c.size() * sizeof(float));
+    h->kept.sq8_param.reserve(p.size() * sizeof(float));
+    VDB_HIP(hipMemcpy(h->kept.sq8_cent.p, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
+    VDB_HIP(hipMemcpy(h->kept.sq8_param.p, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
 // the coarse quantizer's workspace of a build-time assignment pass (one k = 1 search of every row) is given back: an SQ8
 // index is chosen for its footprint, and the next search sizes that workspace for its own batch
 void sq8_release_coarse_ws(vdb_index_s *h) {
-    h->coarse->ws.release();
+    group_release(h->coarse->ws);
     h->coarse->info_valid_nq = -1;
 }
 
@@ -56,7 +56,7 @@ void sq8_train_ranges(vdb_index_s *h, const float *x_host, int64_t n) {
             memcpy(&sample[(size_t)i * Dm], x_host + (size_t)((i * n) / ns) * Dm, (size_t)Dm * sizeof(float));
         rows = sample.data();
     }
-    ScopedDevBuf dx, dassign, dcent, pmin, pmax;
+    DevBuf dx, dassign, dcent, pmin, pmax;
     dx.reserve((size_t)ns * Dm * sizeof(float));
     VDB_HIP(hipMemcpy(dx.p, rows, (size_t)ns * Dm * sizeof(float), hipMemcpyHostToDevice));
     ivf_assign_rows(h, dx.as<float>(), ns, dassign);
@@ -98,23 +98,23 @@ void sq8_build_panel_space(vdb_index_s *h) {
     h->ivf_mfma_ok = false;
     if (h->N == 0 || h->ksteps > kMaxKSteps) return;      // D > 128: the exact list scan serves every batch
     const size_t bytes = (size_t)h->N * h->D4 * sizeof(float);
-    h->x32.reserve_exact(bytes);
+    h->rows.x32.reserve_exact(bytes);
     try {
-        VDB_HIP(hipMemset(h->x32.p, 0, bytes));
+        VDB_HIP(hipMemset(h->rows.x32.p, 0, bytes));
         sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((h->N * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, nullptr>>>(
-            sq8_rows(h), h->N, h->dim, h->D4, h->D4, h->x32.as<float>());
+            sq8_rows(h), h->N, h->dim, h->D4, h->D4, h->rows.x32.as<float>());
         VDB_HIP(hipGetLastError());
         ivf_build_panel_space(h);
         VDB_HIP(hipDeviceSynchronize());
     } catch (...) {
-        h->x32.release();
-        h->panels.release();
+        h->rows.x32.release();
+        h->scan.panels.release();
         h->ivf_mfma_ok = false;
         throw;
     }
-    h->x32.release();
-    h->panels.release();
-    h->xnorm2.release();                                  // (the norms only fed the bias)
+    h->rows.x32.release();
+    h->scan.panels.release();
+    h->rows.xnorm2.release();                                  // (the norms only fed the bias)
 }
 
 // vdb_ivf_add(_assigned) on an SQ8 handle: the same lists as ivf_add_impl (APPEND; stable by list, insertion order inside
@@ -139,9 +139,9 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
     sq8_upload_params(h);
     std::vector<int64_t> assign_new((size_t)n);
     if (N1 > 0) {
-        ScopedDevBuf fresh, raw, dnew, src_codes, src_ids, dperm, dassign, doff;
+        DevBuf fresh, raw, dnew, src_codes, src_ids, dperm, dassign, doff;
         src_codes.reserve((size_t)N1 * D4);
-        if (N0) VDB_HIP(hipMemcpy(src_codes.p, h->sq8_codes.p, (size_t)N0 * D4, hipMemcpyDeviceToDevice));
+        if (N0) VDB_HIP(hipMemcpy(src_codes.p, h->codes.sq8_codes.p, (size_t)N0 * D4, hipMemcpyDeviceToDevice));
         if (n > 0) {
             // the new rows through the pinned staging blocks, then their lists, then their codes (the float32 rows live
             // only for the duration of this call)
@@ -166,8 +166,8 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
                 sq8_release_coarse_ws(h);
             }
             sq8_encode_kernel<<<dim3((unsigned)std::min<int64_t>((n * D4 + 255) / 256, 1 << 20)), dim3(256), 0, nullptr>>>(
-                fresh.as<float>(), n, D4, h->sq8_cent.as<float>(), dnew.as<int64_t>(), h->sq8_param.as<float>(),
-                h->sq8_param.as<float>() + D4, src_codes.as<unsigned char>() + (size_t)N0 * D4);
+                fresh.as<float>(), n, D4, h->kept.sq8_cent.as<float>(), dnew.as<int64_t>(), h->kept.sq8_param.as<float>(),
+                h->kept.sq8_param.as<float>() + D4, src_codes.as<unsigned char>() + (size_t)N0 * D4);
             VDB_HIP(hipGetLastError());
             VDB_HIP(hipDeviceSynchronize());
             fresh.release();
@@ -185,31 +185,31 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
             std::vector<int64_t> ids_new((size_t)n);
             for (int64_t i = 0; i < n; ++i) ids_new[(size_t)i] = h->id_base + N0 + i;
             src_ids.reserve((size_t)N1 * 8);
-            VDB_HIP(hipMemcpy(src_ids.p, h->ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
+            VDB_HIP(hipMemcpy(src_ids.p, h->lists.ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
             if (n) VDB_HIP(hipMemcpy(src_ids.as<int64_t>() + N0, ids_new.data(), (size_t)n * 8, hipMemcpyHostToDevice));
         }
         ivf_csr_build(h, dassign, N1, h->nlist, dperm, doff, h->ivf_offsets_host);
         dassign.release();
-        h->sq8_codes.reserve((size_t)N1 * D4);
-        h->ivf_ids.reserve((size_t)N1 * 8);
+        h->codes.sq8_codes.reserve((size_t)N1 * D4);
+        h->lists.ivf_ids.reserve((size_t)N1 * 8);
         const int64_t total = N1 * (D4 / 4);
         sq8_gather_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr>>>(
             src_codes.as<unsigned char>(), dperm.as<int32_t>(), N1, D4, id_base, N0 ? src_ids.as<int64_t>() : nullptr,
-            h->sq8_codes.as<unsigned char>(), h->ivf_ids.as<int64_t>());
+            h->codes.sq8_codes.as<unsigned char>(), h->lists.ivf_ids.as<int64_t>());
         VDB_HIP(hipGetLastError());
         std::vector<int32_t> list_of((size_t)N1);       // list of every list-order row (the accessor's centroid)
         for (int l = 0; l < h->nlist; ++l)
             std::fill(list_of.begin() + h->ivf_offsets_host[(size_t)l], list_of.begin() + h->ivf_offsets_host[(size_t)l + 1], l);
-        h->sq8_list.reserve((size_t)N1 * 4);
-        VDB_HIP(hipMemcpy(h->sq8_list.p, list_of.data(), (size_t)N1 * 4, hipMemcpyHostToDevice));
+        h->codes.sq8_list.reserve((size_t)N1 * 4);
+        VDB_HIP(hipMemcpy(h->codes.sq8_list.p, list_of.data(), (size_t)N1 * 4, hipMemcpyHostToDevice));
         VDB_HIP(hipDeviceSynchronize());
     } else {
         h->ivf_offsets_host.assign((size_t)h->nlist + 1, 0);
     }
     h->N = N1;
     h->id_base = id_base;
-    h->ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
-    VDB_HIP(hipMemcpy(h->ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8, hipMemcpyHostToDevice));
+    h->lists.ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
+    VDB_HIP(hipMemcpy(h->lists.ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8, hipMemcpyHostToDevice));
     h->ivf_list_of_row.resize((size_t)N1);              // (in insertion order: the stored part stays)
     for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
     sq8_build_panel_space(h);

@@ -28,21 +28,21 @@ void lsh_encode(vdb_index_s *h, const float *x, int64_t n, int64_t pitch, uint32
     if (n <= 0) return;
     VDB_HIP(hipMemsetAsync(codes, 0, (size_t)n * h->lsh_wp * sizeof(uint32_t), st));
     const int64_t items = (n + kLshEncRows - 1) / kLshEncRows * ((h->lsh_nbits + 63) / 64);
-    lsh_encode_kernel<<<dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st>>>(x, n, h->dim, pitch, h->lsh_rt.as<float>(), h->lsh_nbits,
+    lsh_encode_kernel<<<dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st>>>(x, n, h->dim, pitch, h->kept.lsh_rt.as<float>(), h->lsh_nbits,
                                                                              h->lsh_wp, codes);
     VDB_HIP(hipGetLastError());
 }
 
-// codes of the rows [r0, N) of h->x32 (rows below r0 keep theirs): called behind every add, and by set_projection with r0 = 0
+// codes of the rows [r0, N) of h->rows.x32 (rows below r0 keep theirs): called behind every add, and by set_projection with r0 = 0
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
     if (!lsh_on(h)) return;
     if (r0 > h->lsh_rows || r0 > h->N) r0 = 0;
     h->lsh_rows = 0;
     if (h->N == 0 || !h->built) return;
     const size_t row_bytes = (size_t)h->lsh_wp * sizeof(uint32_t);
-    if (r0 == 0) h->lsh_codes.reserve((size_t)h->N * row_bytes);
-    else h->lsh_codes.grow((size_t)h->N * row_bytes, (size_t)r0 * row_bytes);
-    lsh_encode(h, h->x32.as<float>() + (size_t)r0 * h->D4, h->N - r0, h->D4, h->lsh_codes.as<uint32_t>() + (size_t)r0 * h->lsh_wp, st);
+    if (r0 == 0) h->codes.lsh_codes.reserve((size_t)h->N * row_bytes);
+    else h->codes.lsh_codes.grow((size_t)h->N * row_bytes, (size_t)r0 * row_bytes);
+    lsh_encode(h, h->rows.x32.as<float>() + (size_t)r0 * h->D4, h->N - r0, h->D4, h->codes.lsh_codes.as<uint32_t>() + (size_t)r0 * h->lsh_wp, st);
     VDB_HIP(hipStreamSynchronize(st));
     h->lsh_rows = h->N;
 }
@@ -93,13 +93,13 @@ void lsh_candidates_core(vdb_index_s *h, const float *dq, int64_t nq, int ncand,
     int cap = 1;
     while (cap < std::min<int64_t>(4 * (int64_t)c + 1024, h->N)) cap <<= 1;
     const int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 1 << 20), (int64_t)(kLshListBudget / ((size_t)cap * 8))));
-    h->lsh_qcodes.reserve((size_t)nq * wp * sizeof(uint32_t));
-    h->lsh_hist.reserve((size_t)nqc * hb * sizeof(int));
-    h->lsh_small.reserve((size_t)nqc * 6 * sizeof(int));
-    h->lsh_list.reserve((size_t)nqc * cap * sizeof(unsigned long long));
-    lsh_encode(h, dq, nq, h->dim, h->lsh_qcodes.as<uint32_t>(), st);
+    h->lsh_ws.lsh_qcodes.reserve((size_t)nq * wp * sizeof(uint32_t));
+    h->lsh_ws.lsh_hist.reserve((size_t)nqc * hb * sizeof(int));
+    h->lsh_ws.lsh_small.reserve((size_t)nqc * 6 * sizeof(int));
+    h->lsh_ws.lsh_list.reserve((size_t)nqc * cap * sizeof(unsigned long long));
+    lsh_encode(h, dq, nq, h->dim, h->lsh_ws.lsh_qcodes.as<uint32_t>(), st);
     LshArgs a{};
-    a.codes = h->lsh_codes.as<uint32_t>();
+    a.codes = h->codes.lsh_codes.as<uint32_t>();
     a.n = h->N;
     a.wp = wp;
     a.nbits = h->lsh_nbits;
@@ -111,19 +111,19 @@ void lsh_candidates_core(vdb_index_s *h, const float *dq, int64_t nq, int ncand,
     a.sample_stride = a.sample_n == h->N ? 256 : h->N / (kLshSampleMax / 256);  // first rows of consecutive 256-row runs
     a.force_fallback = h->lsh_force_fallback;
     a.id_base = h->id_base;
-    a.hist = h->lsh_hist.as<int>();
-    a.thi = h->lsh_small.as<int>();
+    a.hist = h->lsh_ws.lsh_hist.as<int>();
+    a.thi = h->lsh_ws.lsh_small.as<int>();
     a.tq = a.thi + nqc;
     a.cnt = a.tq + nqc;
     a.flag = a.cnt + nqc;
     a.tsel = a.flag + nqc;
     a.msel = a.tsel + nqc;
     a.scanned0 = a.sample_n != a.n;
-    a.list = h->lsh_list.as<unsigned long long>();
-    a.nflagged = h->lsh_stat.as<unsigned long long>();
+    a.list = h->lsh_ws.lsh_list.as<unsigned long long>();
+    a.nflagged = h->lsh_ws.lsh_stat.as<unsigned long long>();
     for (int64_t q0 = 0; q0 < nq; q0 += nqc) {
         a.nq = std::min<int64_t>(nqc, nq - q0);
-        a.qcodes = h->lsh_qcodes.as<uint32_t>() + (size_t)q0 * wp;
+        a.qcodes = h->lsh_ws.lsh_qcodes.as<uint32_t>() + (size_t)q0 * wp;
         a.out_ham = ham + (size_t)q0 * ncand;
         a.out_ids = ids + (size_t)q0 * ncand;
         launch_lsh_sample(a, st);
@@ -146,8 +146,8 @@ void lsh_check_args(vdb_index_s *h, const void *q, int64_t nq, int ncand, const 
 }
 
 void lsh_begin_call(vdb_index_s *h, int64_t nq, hipStream_t st) {
-    h->lsh_stat.reserve((size_t)kStatShards * kStatStride * sizeof(unsigned long long));
-    VDB_HIP(hipMemsetAsync(h->lsh_stat.p, 0, (size_t)kStatShards * kStatStride * sizeof(unsigned long long), st));
+    h->lsh_ws.lsh_stat.reserve((size_t)kStatShards * kStatStride * sizeof(unsigned long long));
+    VDB_HIP(hipMemsetAsync(h->lsh_ws.lsh_stat.p, 0, (size_t)kStatShards * kStatStride * sizeof(unsigned long long), st));
     h->last.last_nq = nq;
     h->last.last_path = VDB_PATH_LSH;
 }
@@ -163,15 +163,15 @@ void lsh_candidates_impl(vdb_index_s *h, const float *dq, int64_t nq, int ncand,
 void lsh_search_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, int ncand, float *D, int64_t *I, hipStream_t st) {
     if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
     const int64_t nqs = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(kLshCandBudget / ((size_t)ncand * 12))));
-    h->lsh_cand_i.reserve((size_t)nqs * ncand * sizeof(int64_t));
-    h->lsh_cand_h.reserve((size_t)nqs * ncand * sizeof(int32_t));
+    h->lsh_ws.lsh_cand_i.reserve((size_t)nqs * ncand * sizeof(int64_t));
+    h->lsh_ws.lsh_cand_h.reserve((size_t)nqs * ncand * sizeof(int32_t));
     lsh_begin_call(h, nq, st);
     const long tslot = timing_begin(h, st);
     for (int64_t q0 = 0; q0 < nq; q0 += nqs) {
         const int64_t n = std::min<int64_t>(nqs, nq - q0);
         const float *qs = dq + (size_t)q0 * h->dim;
-        lsh_candidates_core(h, qs, n, ncand, h->lsh_cand_h.as<int32_t>(), h->lsh_cand_i.as<int64_t>(), st, tslot, q0 == 0);
-        rerank_device_impl(h, qs, n, h->lsh_cand_i.as<int64_t>(), ncand, k, D + (size_t)q0 * k, I + (size_t)q0 * k, st);
+        lsh_candidates_core(h, qs, n, ncand, h->lsh_ws.lsh_cand_h.as<int32_t>(), h->lsh_ws.lsh_cand_i.as<int64_t>(), st, tslot, q0 == 0);
+        rerank_device_impl(h, qs, n, h->lsh_ws.lsh_cand_i.as<int64_t>(), ncand, k, D + (size_t)q0 * k, I + (size_t)q0 * k, st);
     }
     timing_mark(h, tslot, 2, st);
 }
@@ -198,9 +198,9 @@ int vdb_lsh_set_projection(vdb_handle hh, int nbits, const float *proj_host) {
         h->lsh_wp = 1;
         while (h->lsh_wp < nbits / 32) h->lsh_wp <<= 1;
         h->lsh_rows = 0;
-        h->lsh_codes.release();
-        h->lsh_rt.reserve_exact(rt.size() * sizeof(float));
-        VDB_HIP(hipMemcpy(h->lsh_rt.p, rt.data(), rt.size() * sizeof(float), hipMemcpyHostToDevice));
+        h->codes.lsh_codes.release();
+        h->kept.lsh_rt.reserve_exact(rt.size() * sizeof(float));
+        VDB_HIP(hipMemcpy(h->kept.lsh_rt.p, rt.data(), rt.size() * sizeof(float), hipMemcpyHostToDevice));
         lsh_encode_rows(h, 0, nullptr);
     });
 }
@@ -224,11 +224,11 @@ int vdb_lsh_get_codes(vdb_handle hh, uint32_t *codes_host) {
         set_device(h->device);
         const int w = h->lsh_nbits / 32, wp = h->lsh_wp;
         if (w == wp) {
-            VDB_HIP(hipMemcpy(codes_host, h->lsh_codes.p, (size_t)h->N * w * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            VDB_HIP(hipMemcpy(codes_host, h->codes.lsh_codes.p, (size_t)h->N * w * sizeof(uint32_t), hipMemcpyDeviceToHost));
             return;
         }
         std::vector<uint32_t> tmp((size_t)h->N * wp);
-        VDB_HIP(hipMemcpy(tmp.data(), h->lsh_codes.p, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(tmp.data(), h->codes.lsh_codes.p, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < h->N; ++r) memcpy(codes_host + (size_t)r * w, tmp.data() + (size_t)r * wp, (size_t)w * sizeof(uint32_t));
     });
 }
@@ -252,7 +252,7 @@ int vdb_lsh_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncand
         lsh_check_args(h, q_host, nq, ncand, ham, ids);
         if (nq == 0) return;
         set_device(h->device);
-        ScopedDevBuf dh, di;
+        DevBuf dh, di;
         h->ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
         dh.reserve((size_t)nq * ncand * sizeof(int32_t));
         di.reserve((size_t)nq * ncand * sizeof(int64_t));
@@ -284,16 +284,9 @@ int vdb_lsh_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int nc
         if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
         if (nq == 0) return;
         set_device(h->device);
-        Workspace &ws = h->ws;
-        ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
-        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
-        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
-        hipStream_t st = nullptr;
-        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-        lsh_search_impl(h, ws.stage_q.as<float>(), nq, k, ncand, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), st);
-        VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
+            lsh_search_impl(h, dq, nq, k, ncand, dD, dI, st);
+        });
     });
 }
 

@@ -267,20 +267,12 @@ void multi_destroy(vdb_index_s *m) {
     for (int s = 0; s < S; ++s) {
         set_device(M->shards[(size_t)s]->device);
         (void)hipDeviceSynchronize();
-        M->q_stage[(size_t)s].release();
-        M->pack[(size_t)s].release();
-        M->cand_stage[(size_t)s].release();
-        M->seg_shard[(size_t)s].release();
         if (M->streams[(size_t)s]) (void)hipStreamDestroy(M->streams[(size_t)s]);
         if (M->done[(size_t)s]) (void)hipEventDestroy(M->done[(size_t)s]);
     }
     {
         set_device(m->device);
         (void)hipDeviceSynchronize();
-        M->gather.release();
-        M->seg_dev.release();
-        M->out_d.release();
-        M->out_i.release();
         if (M->main_stream) (void)hipStreamDestroy(M->main_stream);
         if (M->q_ready) (void)hipEventDestroy(M->q_ready);
     }
@@ -347,7 +339,7 @@ void multi_add(vdb_index_s *m, const float *x, bool on_device, int64_t n, int64_
             append_rows(c, rows, true, hi - lo, 0, M->streams[(size_t)s]);
             VDB_HIP(hipStreamSynchronize(M->streams[(size_t)s]));
         } else {                                            // rows on the primary device: peer copy, then a device add
-            ScopedDevBuf tmp;
+            DevBuf tmp;
             if (hi > lo) {
                 tmp.reserve((size_t)(hi - lo) * m->dim * sizeof(float));
                 VDB_HIP(hipMemcpyPeer(tmp.p, c->device, rows, primary, (size_t)(hi - lo) * m->dim * sizeof(float)));

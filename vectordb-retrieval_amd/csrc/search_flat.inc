@@ -210,12 +210,12 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         VDB_HIP(hipGetLastError());
         qpad = ws.qpad.as<float>();
     }
-    RefineCommon rc{h->int8_only ? nullptr : h->x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, nullptr};
+    RefineCommon rc{h->int8_only ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, nullptr};
     rc.info = batch_info(ws);                             // (group size of the candidates: 4 rows, 8 on the int8 scan)
     const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
-    if (h->i8_ok && h->rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
-        rc.X8 = h->rows8.as<signed char>();
-        rc.rowstat = h->rowstat8.as<int>();
+    if (h->i8_ok && h->scan.rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
+        rc.X8 = h->scan.rows8.as<signed char>();
+        rc.rowstat = h->scan.rowstat8.as<int>();
         rc.x8_pitch = h->rows8_pitch;
         rc.cx = h->i8_cx;
         rc.D = Dm;
@@ -259,7 +259,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 
     // small corpora: dense fp16 scores + per-query guard + exact re-score of the few surviving rows
     // (D > 128: corpora of <= 2048 rows keep 32-row tiles for exactly this path -- build_derived -- and take the K-loop form)
-    const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
+    const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->scan.panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
                            h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= h->N &&
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
     if (use_dense) {
@@ -297,15 +297,15 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         {
             const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)(Qp / 64));
             if (h->ksteps > kMaxKSteps)
-                dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(),
+                dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
                                                                      ws.qpanels.as<half8>(), info, ntiles, h->Npad, h->N,
                                                                      h->ksteps, ws.dense.as<float>());
             else if (h->ksteps == 4)
-                dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(),
+                dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
                                                                   ws.qpanels.as<half8>(), info, ntiles, h->Npad,
                                                                   ws.dense.as<float>());
             else
-                dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->panels.as<half8>(), h->bias.as<float>(),
+                dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
                                                                   ws.qpanels.as<half8>(), info, ntiles, h->Npad,
                                                                   ws.dense.as<float>());
         }
@@ -532,8 +532,8 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     }
 
     ScanArgs sa{};
-    sa.panels = h->panels.as<half8>();
-    sa.bias = h->bias.as<float>();
+    sa.panels = h->scan.panels.as<half8>();
+    sa.bias = h->scan.bias.as<float>();
     sa.qpanels = ws.qpanels.as<half8>();
     sa.info = info;
     sa.bin_m1 = ws.bin_m1.as<float>();
@@ -579,14 +579,14 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
             if (fit >= 8 && fit <= slab_chunks) { slab_chunks = fit; break; }
         }
         slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
-        h->slab.reserve((size_t)slab_chunks * chunk_rows / kTileRows16 * KS * 64 * sizeof(half8));
+        h->scan.slab.reserve((size_t)slab_chunks * chunk_rows / kTileRows16 * KS * 64 * sizeof(half8));
         for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
             const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
             const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
             const int64_t tile_a = span_a * kTilesPerSpan16, ntiles = (span_b - span_a) * kTilesPerSpan16;
-            half8 *buf = h->slab.as<half8>();
+            half8 *buf = h->scan.slab.as<half8>();
             convert_slab16_kernel<<<dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st>>>(
-                h->x32.as<float>(), h->N, Dm, D4, (int)KS, tile_a, ntiles, h->sx, buf);
+                h->rows.x32.as<float>(), h->N, Dm, D4, (int)KS, tile_a, ntiles, h->sx, buf);
             ScanArgs ss = sa;
             ss.panels = buf - (size_t)tile_a * KS * 64;
             ss.chunk0 = (int)c0;
@@ -602,16 +602,16 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         const int64_t tiles_per_span = kTilesPerSpan;
         const int64_t slab_chunks = std::max<int64_t>(1, std::min<int64_t>(h->int8_slab_chunks > 0 ? h->int8_slab_chunks : 8, g.nchunks));
         const int64_t max_spans = (int64_t)(g.spc + 1) * slab_chunks;
-        if (h->slab.cap < (size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8))
-            h->slab.reserve_exact((size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8));
+        if (h->scan.slab.cap < (size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8))
+            h->scan.slab.reserve_exact((size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8));
         for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
             const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
             const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
             const int64_t tile_a = span_a * tiles_per_span, ntiles = (span_b - span_a) * tiles_per_span;
-            half8 *buf = h->slab.as<half8>();
+            half8 *buf = h->scan.slab.as<half8>();
             const int64_t threads = ntiles * h->ksteps * 64;
             convert_slab_from_i8_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-                h->panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, info, buf, h->x16 ? 1 : 0);
+                h->scan.panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, info, buf, h->x16 ? 1 : 0);
             ScanArgs ss = sa;
             ss.panels = buf - (size_t)tile_a * h->ksteps * 64;
             ss.chunk0 = (int)c0;
@@ -622,8 +622,8 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     launch_scan(h, sa, g.nchunks, Qpad, st, direct_rows, nw_small);   // (fp16: returns at once when the int8 scan serves the batch)
     if (use_i8) {
         ScanI8Args s8{};
-        s8.panels = h->panels8.as<int4v>();
-        s8.bias8 = h->bias8.as<int32_t>();
+        s8.panels = h->scan.panels8.as<int4v>();
+        s8.bias8 = h->scan.bias8.as<int32_t>();
         s8.qpanels = ws.qpanels8.as<int4v>();
         s8.info = info;
         s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
@@ -916,16 +916,13 @@ void graph_or_run(vdb_index_s *h, const vdb_index_s::GraphKey &key, F &&run) {
         if (alloc_log()) {        // what the graph bakes in: the caller's buffers and every buffer of the handle (by name)
             alloc_note("GRAPH_INSTANTIATE", ex, 0);
             alloc_note("  arg.q", key.q, 0); alloc_note("  arg.o1", key.o1, 0); alloc_note("  arg.o2", key.o2, 0);
-            const Workspace &w = h->ws;
-            const std::pair<const char *, const DevBuf *> named[] = {
-                {"  x32", &h->x32}, {"  xnorm2", &h->xnorm2}, {"  panels", &h->panels}, {"  bias", &h->bias}, {"  panels8", &h->panels8},
-                {"  bias8", &h->bias8}, {"  rows8", &h->rows8}, {"  rowstat8", &h->rowstat8}, {"  ws.qpad", &w.qpad},
-                {"  ws.qpanels", &w.qpanels}, {"  ws.qpanels8", &w.qpanels8}, {"  ws.qrows8", &w.qrows8}, {"  ws.eps", &w.eps},
-                {"  ws.bin_m1", &w.bin_m1}, {"  ws.bin_m2", &w.bin_m2}, {"  ws.sb_m1", &w.sb_m1}, {"  ws.sb_m2", &w.sb_m2},
-                {"  ws.sb_span", &w.sb_span}, {"  ws.cand", &w.cand}, {"  ws.rescan", &w.rescan}, {"  ws.counts", &w.counts},
-                {"  ws.fallback", &w.fallback}, {"  ws.fb_list", &w.fb_list}, {"  ws.fb_done", &w.fb_done}, {"  ws.small", &w.small},
-                {"  ws.dense", &w.dense}, {"  ws.pkeys", &w.pkeys}, {"  ws.pids", &w.pids}};
-            for (const auto &nb : named) alloc_note(nb.first, nb.second->p, nb.second->cap);
+            const auto dump = [](vdb_index_s *x, const char *owner) {
+                for_each_group(x, [&](auto &g) {
+                    for_each_buf(g, [&](const char *name, DevBuf &b) { alloc_note((std::string("  ") + owner + name).c_str(), b.p, b.cap); });
+                });
+            };
+            dump(h, "");
+            if (h->coarse) dump(h->coarse, "coarse.");
         }
         (void)hipGraphDestroy(g);
         h->graph_exec = ex;

@@ -10,6 +10,7 @@
 #include <functional>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vdbhip.h"
@@ -56,11 +57,22 @@ void alloc_note(const char *what, const void *p, size_t bytes) {
     }
 }
 
-// growable device buffer
+// growable device buffer that owns its memory: freed when it goes out of scope (a temporary of one API call is freed on every
+// exit path, an Error thrown by a later hipMalloc included) or with the handle it is a member of.  `name` is what the
+// $VDBHIP_ALLOC_LOG dump of a captured graph calls a member of a buffer group (for_each_buf below); temporaries have none.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
     bool borrowed = false;      // a view into another DevBuf's memory (borrow): never freed here, cannot grow
+    const char *name = nullptr;
+    DevBuf() = default;
+    explicit DevBuf(const char *member_name) : name(member_name) {}
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap), borrowed(o.borrowed), name(o.name) {      // (move-only: std::vector<DevBuf> in multi.inc)
+        o.p = nullptr;
+        o.cap = 0;
+        o.borrowed = false;
+    }
+    ~DevBuf() { release(); }
     void borrow(void *ptr, size_t bytes) {
         if (!borrowed) release();
         p = ptr;
@@ -69,50 +81,25 @@ struct DevBuf {
     }
     void reserve(size_t bytes) {
         if (bytes <= cap) return;
-        if (borrowed) throw Error(VDB_ERR_INVALID, "internal: a borrowed device buffer cannot grow");
-        g_alloc_epoch.fetch_add(1, std::memory_order_relaxed);
-        if (p) {
-            alloc_note("F", p, cap);
-            VDB_HIP(hipFree(p));
-        }
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + std::min<size_t>(bytes >> 3, (size_t)256 << 20);   // (growth slack: 1/8, at most 256 MiB)
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) throw Error(VDB_ERR_NOMEM, "hipMalloc of " + std::to_string(want) + " bytes failed");
-        cap = want;
-        alloc_note("A", p, cap);
+        require_owned();
+        release();
+        allocate(with_slack(bytes));
     }
     // exactly `bytes` (no growth slack): buffers of an index that is built once and never grows (int8-only build)
     void reserve_exact(size_t bytes) {
         if (bytes == cap && p) return;
-        if (borrowed) throw Error(VDB_ERR_INVALID, "internal: a borrowed device buffer cannot grow");
+        require_owned();
         release();
-        g_alloc_epoch.fetch_add(1, std::memory_order_relaxed);
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-        if (e != hipSuccess) { p = nullptr; throw Error(VDB_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed"); }
-        cap = bytes ? bytes : 16;
-        alloc_note("A", p, cap);
+        allocate(bytes ? bytes : 16);
     }
     // reserve that keeps the first `keep` bytes (append): old and new allocation coexist for the copy
     void grow(size_t bytes, size_t keep) {
         if (bytes <= cap) return;
-        if (borrowed) throw Error(VDB_ERR_INVALID, "internal: a borrowed device buffer cannot grow");
+        require_owned();
         void *old = p;
         const size_t old_cap = cap;
-        g_alloc_epoch.fetch_add(1, std::memory_order_relaxed);
-        const size_t want = bytes + std::min<size_t>(bytes >> 3, (size_t)256 << 20);
-        void *fresh = nullptr;
-        hipError_t e = hipMalloc(&fresh, want);
-        if (e != hipSuccess) {              // the old buffer stays as it was: a failed append leaves the index intact
-            (void)hipGetLastError();
-            p = old;
-            cap = old_cap;
-            throw Error(VDB_ERR_NOMEM, "hipMalloc of " + std::to_string(want) + " bytes failed");
-        }
-        p = fresh;
-        cap = want;
-        alloc_note("A", p, cap);
+        allocate(with_slack(bytes));         // (throws with the old buffer as it was: a failed append leaves the index intact)
+        hipError_t e = hipSuccess;
         if (old && keep) e = hipMemcpy(p, old, keep, hipMemcpyDeviceToDevice);
         if (old) {
             alloc_note("F", old, old_cap);
@@ -132,41 +119,105 @@ struct DevBuf {
     }
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p); }
+
+  private:
+    static size_t with_slack(size_t bytes) { return bytes + std::min<size_t>(bytes >> 3, (size_t)256 << 20); }   // (growth slack: 1/8, at most 256 MiB)
+    void require_owned() const {
+        if (borrowed) throw Error(VDB_ERR_INVALID, "internal: a borrowed device buffer cannot grow");
+    }
+    // the one place that allocates device memory: epoch bump, hipMalloc, error text, log line; throws with p / cap untouched
+    void allocate(size_t bytes) {
+        g_alloc_epoch.fetch_add(1, std::memory_order_relaxed);
+        void *fresh = nullptr;
+        if (hipMalloc(&fresh, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            throw Error(VDB_ERR_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
+        }
+        p = fresh;
+        cap = bytes;
+        alloc_note("A", p, cap);
+    }
 };
 
-// temporary of one API call: freed on every exit path (an Error thrown by a later hipMalloc included)
-struct ScopedDevBuf : DevBuf {
-    ScopedDevBuf() = default;
-    ScopedDevBuf(const ScopedDevBuf &) = delete;
-    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
-    ~ScopedDevBuf() { release(); }
+// ---- buffer groups ---------------------------------------------------------------------------------------------------------
+// The device buffers of a handle sit in a few plain structs, one per LIFETIME (what frees them together), whose only data
+// members are DevBufs declared with their name.  for_each_buf walks such a struct as the array of DevBufs it is, so a new
+// buffer is one declaration: its bytes are counted (vdb_stats), it is freed with its group (vdb_reset, a rebuild) and with
+// the handle, and the graph dump of $VDBHIP_ALLOC_LOG names it, without a list anywhere to add it to.
+template <class G, class F>
+void for_each_buf(G &g, F &&f) {
+    static_assert(std::is_standard_layout<G>::value && sizeof(G) % sizeof(DevBuf) == 0, "a buffer group holds DevBuf members only");
+    DevBuf *b = reinterpret_cast<DevBuf *>(&g);
+    for (size_t i = 0; i < sizeof(G) / sizeof(DevBuf); ++i) f(b[i].name, b[i]);
+}
+template <class G>
+size_t group_bytes(G &g) {
+    size_t s = 0;
+    for_each_buf(g, [&](const char *, DevBuf &b) { s += b.cap; });
+    return s;
+}
+template <class G>
+void group_release(G &g) {
+    for_each_buf(g, [](const char *, DevBuf &b) { b.release(); });
+}
+
+// the float32 rows and their norms                                                            (freed by vdb_reset)
+struct RowBufs {
+    DevBuf x32{"x32"}, xnorm2{"xnorm2"};
 };
-
-struct Workspace;
-inline QueryBatchInfo *batch_info(Workspace &ws);
-
+// the scan copies derived from the rows (an append frees and re-derives them): fp16 panels and bias, the scratch slab of a
+// streamed index, and the int8 copy (scan_i8.hpp) of byte-valued integer corpora with D <= 128, kept NEXT TO the fp16 panels
+// (a batch of non-integer queries still takes the fp16 scan)                                  (freed by vdb_reset)
+struct ScanBufs {
+    DevBuf panels{"panels"}, slab{"slab"}, bias{"bias"};
+    DevBuf panels8{"panels8"}, bias8{"bias8"}, rows8{"rows8"}, rowstat8{"rowstat8"};  // rows8 / rowstat8: row-major int8 copy + {sum x^2, sum x} for the list refine
+};
+// what outlives the rows: the corpus statistics block, and what vdb_ivf_train / set_* installed   (freed with the handle)
+struct KeptBufs {
+    DevBuf stats{"stats"};
+    DevBuf sq8_cent{"sq8_cent"}, sq8_param{"sq8_param"};     // SQ8: centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
+    DevBuf lsh_rt{"lsh_rt"};                                 // sign-LSH: R transposed [dim][nbits]
+};
+// IVF: the CSR arrays and the panel space (lists padded to whole spans) of the filed rows      (freed by vdb_reset)
+struct IvfListBufs {
+    DevBuf ivf_offsets{"ivf_offsets"}, ivf_ids{"ivf_ids"};
+    DevBuf ivf_list_pspan0{"ivf_list_pspan0"}, ivf_span_row0{"ivf_span_row0"}, ivf_span_valid{"ivf_span_valid"};
+};
+// IVF: the per-batch plan of the list-major scan and the coarse result                        (freed with the handle)
+struct IvfPlanBufs {
+    DevBuf ivf_probe_d{"ivf_probe_d"}, ivf_probe_i{"ivf_probe_i"};
+    // everything an IVF search needs zeroed, in ONE buffer cleared by ONE memset per batch (each memset is a ~4 us dispatch
+    // of its own): [coarse quantizer's ws.small | this handle's ws.small | per-list counts | cursors | slot -> query map |
+    // arrival counters of the flagged-query pass].  Both ws.small are views into it (DevBuf::borrow).
+    DevBuf ivf_zero{"ivf_zero"};
+    DevBuf ivf_slot_off{"ivf_slot_off"}, ivf_list_item0{"ivf_list_item0"}, ivf_item_list{"ivf_item_list"};
+    DevBuf ivf_item_slot0{"ivf_item_slot0"}, ivf_item_bin0{"ivf_item_bin0"}, ivf_plan{"ivf_plan"}, ivf_slot_of{"ivf_slot_of"};
+};
+// compressed codes of the rows                                                                (freed by vdb_reset)
+struct CodeBufs {
+    DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row, both in list order
+    DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
+};
+// per-search workspace of the LSH calls                                                       (freed with the handle)
+struct LshWorkspace {
+    DevBuf lsh_qcodes{"lsh_qcodes"}, lsh_hist{"lsh_hist"}, lsh_small{"lsh_small"}, lsh_list{"lsh_list"}, lsh_stat{"lsh_stat"};
+    DevBuf lsh_cand_i{"lsh_cand_i"}, lsh_cand_h{"lsh_cand_h"};
+};
+// per-search workspace                                                                        (freed with the handle)
 struct Workspace {
-    DevBuf qpad, qpanels, qpanels8, qrows8, info, eps, bin_m1, bin_m2, bin_m3, bin_m4, bin_m5, sb_m1, sb_m2, sb_span;
-    DevBuf cand, rescan, counts, fallback, fb_list, fb_done /* arrival counters of refine_fallback_body (refine_tail_kernel) */, small;  // small: fb_count (int) + 2 stat counters
-    DevBuf dense;            // nq x Npad raw scores of the small-corpus path
-    DevBuf pkeys, pids;      // partial lists of the exhaustive / fallback passes
-    DevBuf stage_q, stage_d, stage_i;  // host-API staging
-    DevBuf sq8_panels;       // IVF-SQ8: the fp16 panels converted from the codes for the current batch
-    size_t bytes() const {
-        const DevBuf *all[] = {&sq8_panels, &qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
-                               &rescan, &counts, &fallback, &fb_list, &fb_done, &small, &pkeys, &pids, &stage_q, &stage_d,
-                               &stage_i, &dense};
-        size_t s = 0;
-        for (auto b : all) s += b->cap;
-        return s;
-    }
-    void release() {
-        DevBuf *all[] = {&sq8_panels, &qpad, &qpanels, &qpanels8, &qrows8, &info, &eps, &bin_m1, &bin_m2, &bin_m3, &bin_m4, &bin_m5, &sb_m1, &sb_m2, &sb_span, &cand,
-                         &rescan, &counts, &fallback, &fb_list, &fb_done, &small, &pkeys, &pids, &stage_q, &stage_d, &stage_i,
-                         &dense};
-        for (auto b : all) b->release();
-    }
+    DevBuf qpad{"ws.qpad"}, qpanels{"ws.qpanels"}, qpanels8{"ws.qpanels8"}, qrows8{"ws.qrows8"}, info{"ws.info"}, eps{"ws.eps"};
+    DevBuf bin_m1{"ws.bin_m1"}, bin_m2{"ws.bin_m2"}, bin_m3{"ws.bin_m3"}, bin_m4{"ws.bin_m4"}, bin_m5{"ws.bin_m5"};
+    DevBuf sb_m1{"ws.sb_m1"}, sb_m2{"ws.sb_m2"}, sb_span{"ws.sb_span"};
+    DevBuf cand{"ws.cand"}, rescan{"ws.rescan"}, counts{"ws.counts"}, fallback{"ws.fallback"}, fb_list{"ws.fb_list"};
+    DevBuf fb_done{"ws.fb_done"};           // arrival counters of refine_fallback_body (refine_tail_kernel)
+    DevBuf small{"ws.small"};               // fb_count (int) + 2 stat counters
+    DevBuf dense{"ws.dense"};               // nq x Npad raw scores of the small-corpus path
+    DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
+    DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
+    DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8: the fp16 panels converted from the codes for the current batch
 };
+
+void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
 
 inline QueryBatchInfo *batch_info(Workspace &ws) {        // inside ws.small (common.hpp, kInfoOffset)
     return reinterpret_cast<QueryBatchInfo *>(ws.small.as<char>() + kInfoOffset);
@@ -183,11 +234,15 @@ struct vdb_index_s {
     int dim = 0, D4 = 0, ksteps = 0, metric = 0;
     int64_t N = 0, Npad = 0, id_base = 0;
     bool built = false;
-    // index arrays
-    DevBuf x32, xnorm2, panels, bias, stats;
-    // int8 scan copy (scan_i8.hpp): byte-valued integer corpora with D <= 128, kept NEXT TO the fp16 panels (a batch of
-    // non-integer queries still takes the fp16 scan)
-    DevBuf panels8, bias8, rows8, rowstat8;  // rows8 / rowstat8: row-major int8 copy + {sum x^2, sum x} for the list refine
+    // device memory, grouped by lifetime (buffer groups above); every group is listed ONCE more, in for_each_group below
+    RowBufs rows;
+    ScanBufs scan;
+    KeptBufs kept;
+    IvfListBufs lists;                       // (flat handles leave the IVF / SQ8 / LSH groups empty)
+    IvfPlanBufs plan;
+    CodeBufs codes;
+    LshWorkspace lsh_ws;
+    Workspace ws;
     int rows8_pitch = 0;
     bool i8_ok = false;
     int ivf_bt = 0;                          // option "ivf_bt": tiles per level-1 bin of the IVF scan (0 auto, 4, 16)
@@ -260,11 +315,8 @@ struct vdb_index_s {
     int stream_panels_opt = 0;
     int64_t stream_slab_rows = 0;            // option "stream_slab_rows" (0 = default)
     bool panels_streamed = false;
-    DevBuf slab;                             // the scratch slab of a streamed index
     bool set_only = false;                   // coarse quantizer of an IVF index: callers use the SET of the k nearest rows,
                                              // not their order or distances (dense.hpp, DenseSelectArgs.set_only)
-    // per-search
-    Workspace ws;
     vdb_stats_t last{};
     // timing mode: HIP-event pairs recorded on the search stream around the dominant kernel and the whole
     // device pipeline of every search since timing was switched on (read back by vdb_stats)
@@ -277,39 +329,57 @@ struct vdb_index_s {
     std::vector<float> ivf_centroids;        // host copy [nlist][dim]
     std::vector<int64_t> ivf_offsets_host;   // [nlist+1]
     std::vector<int32_t> ivf_list_of_row;    // [N] list of every indexed row (original order)
-    DevBuf ivf_offsets, ivf_ids, ivf_probe_d, ivf_probe_i;
     // list-major MFMA scan (D <= 128): panel space = lists padded to whole 512-row spans
     bool ivf_mfma_ok = false, ivf_last_mfma = false;
     int64_t ivf_pspans = 0;
     int ivf_max_pspans = 0;
     int ivf_span_rows = kSpanRows;           // rows per panel span: 512 (32-row tiles, D <= 128) or 16 * ivf_tps (p16, D > 128)
     int ivf_tps = 0, ivf_tps_override = 0;   // p16 tiles per span of the IVF panel space (16 / 64); option "ivf_tps"
-    DevBuf ivf_list_pspan0, ivf_span_row0, ivf_span_valid;
-    // everything an IVF search needs zeroed, in ONE buffer cleared by ONE memset per batch (each memset is a ~4 us dispatch
-    // of its own): [coarse quantizer's ws.small | this handle's ws.small | per-list counts | cursors | slot -> query map |
-    // arrival counters of the flagged-query pass].  Both ws.small are views into it (DevBuf::borrow).
-    DevBuf ivf_zero, ivf_slot_off, ivf_list_item0,
-        ivf_item_list, ivf_item_slot0, ivf_item_bin0, ivf_plan, ivf_slot_of;
     // codec of the inverted lists (vdb_ivf_set_codec): 0 Flat (float32 rows + scan copies) | 1 SQ8 (ivf_sq8.inc: 8-bit codes
     // of the residuals, no float32 rows, no scan copies)
     int ivf_codec = 0;
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
-    DevBuf sq8_codes, sq8_list;              // [N][D4] codes and the list of every row, both in list order
-    DevBuf sq8_cent, sq8_param;              // centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
     int lsh_force_fallback = 0;              // option "lsh_force_fallback": every query takes the exact fallback of the select
     std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
-    DevBuf lsh_rt, lsh_codes;                // R transposed [dim][nbits]; codes [N][lsh_wp]
-    DevBuf lsh_qcodes, lsh_hist, lsh_small, lsh_list, lsh_stat, lsh_cand_i, lsh_cand_h;   // per-search workspace
-    size_t lsh_ws_bytes() const {
-        return lsh_qcodes.cap + lsh_hist.cap + lsh_small.cap + lsh_list.cap + lsh_stat.cap + lsh_cand_i.cap + lsh_cand_h.cap;
+    // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
+    // plan.ivf_zero); the buffer groups free themselves after this body
+    ~vdb_index_s() {
+        ws.small.release();                  // (our own view into plan.ivf_zero goes before that does)
+        if (graph_ev) (void)hipEventDestroy(graph_ev);
+        release_pins(this);
+        for (auto e : pin_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto e : ev_scan) (void)hipEventDestroy(e);
+        for (auto e : ev_total) (void)hipEventDestroy(e);
     }
 };
 
 namespace {
+
+template <class F>
+void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->ws); }
+
+// every byte of device memory the handle holds (its ws.small may be a view into plan.ivf_zero: not counted twice)
+size_t handle_bytes(vdb_index_s *h) {
+    size_t s = 0;
+    for_each_group(h, [&](auto &g) { s += group_bytes(g); });
+    return s - (h->ws.small.borrowed ? h->ws.small.cap : 0);
+}
+
+void release_pins(vdb_index_s *h) {
+    for (int i = 0; i < 2; ++i) {
+        if (h->pin[i]) {
+            alloc_note("HF", h->pin[i], h->pin_bytes);
+            (void)hipHostFree(h->pin[i]);
+        }
+        h->pin[i] = nullptr;
+    }
+    h->pin_bytes = 0;
+}
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -414,14 +484,7 @@ void upload_rows(vdb_index_s *h, float *dst, int D4, const float *src, int64_t n
     const int64_t rows_per_block = std::max<int64_t>(1, (int64_t)(block_bytes / row_bytes));
     const size_t need = (size_t)std::min<int64_t>(rows_per_block, n) * row_bytes;
     if (h->pin_bytes < need) {
-        for (int i = 0; i < 2; ++i) {
-            if (h->pin[i]) {
-                alloc_note("HF", h->pin[i], h->pin_bytes);
-                (void)hipHostFree(h->pin[i]);
-            }
-            h->pin[i] = nullptr;
-        }
-        h->pin_bytes = 0;
+        release_pins(h);
         if (hipHostMalloc(&h->pin[0], need, hipHostMallocDefault) == hipSuccess &&
             hipHostMalloc(&h->pin[1], need, hipHostMallocDefault) == hipSuccess) {
             h->pin_bytes = need;
@@ -456,18 +519,18 @@ void upload_rows(vdb_index_s *h, float *dst, int D4, const float *src, int64_t n
 }
 
 // ---- index build ---------------------------------------------------------------------------------
-// exact row norms + corpus statistics of h->x32 (N rows) -> scales of the fp16 scan copy
+// exact row norms + corpus statistics of h->rows.x32 (N rows) -> scales of the fp16 scan copy
 void index_stats(vdb_index_s *h, hipStream_t st) {
     const int64_t n = h->N;
-    h->xnorm2.reserve((size_t)n * sizeof(float));
-    h->stats.reserve(sizeof(IndexStats));
-    VDB_HIP(hipMemsetAsync(h->stats.p, 0, sizeof(IndexStats), st));
-    corpus_stats_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->x32.as<float>(), n, h->D4,
-                                                                                h->xnorm2.as<float>(),
-                                                                                h->stats.as<IndexStats>());
+    h->rows.xnorm2.reserve((size_t)n * sizeof(float));
+    h->kept.stats.reserve(sizeof(IndexStats));
+    VDB_HIP(hipMemsetAsync(h->kept.stats.p, 0, sizeof(IndexStats), st));
+    corpus_stats_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(h->rows.x32.as<float>(), n, h->D4,
+                                                                                h->rows.xnorm2.as<float>(),
+                                                                                h->kept.stats.as<IndexStats>());
     VDB_HIP(hipGetLastError());
     IndexStats hs;
-    VDB_HIP(hipMemcpyAsync(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+    VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
     VDB_HIP(hipStreamSynchronize(st));
     memcpy(&h->absmax, &hs.absmax_bits, 4);
     memcpy(&h->maxnorm2, &hs.maxnorm2_bits, 4);
@@ -483,13 +546,13 @@ void index_stats(vdb_index_s *h, hipStream_t st) {
     }
 }
 
-// row-major int8 copy of h->x32 (byte-valued corpora only) for the list refine
+// row-major int8 copy of h->rows.x32 (byte-valued corpora only) for the list refine
 void build_rows_i8(vdb_index_s *h, hipStream_t st) {
     h->rows8_pitch = h->i8_ks * 32;                        // = the pitch of the int8 query rows (64 or 128 bytes)
-    h->rows8.reserve((size_t)h->N * h->rows8_pitch);
+    h->scan.rows8.reserve((size_t)h->N * h->rows8_pitch);
     const int64_t words = h->N * (h->rows8_pitch / 4);
     build_rows_i8_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st>>>(
-        h->x32.as<float>(), h->N, h->dim, h->D4, h->rows8_pitch, h->i8_cx, h->rows8.as<signed char>());
+        h->rows.x32.as<float>(), h->N, h->dim, h->D4, h->rows8_pitch, h->i8_cx, h->scan.rows8.as<signed char>());
 }
 
 void graph_reset(vdb_index_s *h);
@@ -500,7 +563,7 @@ bool x16_wanted(const vdb_index_s *h) {
     return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->f16_group == 8 && h->i8_group == 8;
 }
 
-// everything derived from the h->N rows in h->x32: statistics, scan copies, biases
+// everything derived from the h->N rows in h->rows.x32: statistics, scan copies, biases
 void build_derived(vdb_index_s *h, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
     const int64_t n = h->N;
@@ -524,33 +587,33 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
         const int64_t ntiles = h->Npad / (h->tile16 ? kTileRows16 : kTileRows);
         const int ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;          // k-steps of the layout (32 or 16 dims)
         h->panels_streamed = h->tile16 && h->stream_panels_opt != 0;
-        if (h->panels_streamed) h->panels.release();
-        else h->panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
+        if (h->panels_streamed) h->scan.panels.release();
+        else h->scan.panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
         const int64_t threads = ntiles * ksl * 64;
         if (h->tile16)    // (streamed: the pass only takes the fp16-exactness flag)
-            build_panels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->x32.as<float>(), n, D, D4, ksl, ntiles, h->sx, h->panels_streamed ? nullptr : h->panels.as<half8>(), h->stats.as<IndexStats>());
+            build_panels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->rows.x32.as<float>(), n, D, D4, ksl, ntiles, h->sx, h->panels_streamed ? nullptr : h->scan.panels.as<half8>(), h->kept.stats.as<IndexStats>());
         else
-            build_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->x32.as<float>(), n, D, D4, h->ksteps, ntiles, h->sx, h->panels.as<half8>(), h->stats.as<IndexStats>(), h->x16 ? 1 : 0);
+            build_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(h->rows.x32.as<float>(), n, D, D4, h->ksteps, ntiles, h->sx, h->scan.panels.as<half8>(), h->kept.stats.as<IndexStats>(), h->x16 ? 1 : 0);
         VDB_HIP(hipGetLastError());
-        h->bias.reserve((size_t)h->Npad * sizeof(float));
-        build_bias_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(h->xnorm2.as<float>(), n, h->Npad, h->metric, h->bias.as<float>());
+        h->scan.bias.reserve((size_t)h->Npad * sizeof(float));
+        build_bias_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(h->rows.xnorm2.as<float>(), n, h->Npad, h->metric, h->scan.bias.as<float>());
         VDB_HIP(hipGetLastError());
         IndexStats hs;
-        VDB_HIP(hipMemcpyAsync(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
         VDB_HIP(hipStreamSynchronize(st));
         h->corpus_fp16_exact = hs.not_fp16_exact == 0;
         h->scan_ok = true;
         h->i8_ok = h->i8_ok && !h->tile16;
         if (h->i8_ok) {
             h->i8_ks = D <= 64 ? 2 : 4;
-            h->panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
+            h->scan.panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
             const int64_t t8 = ntiles * h->i8_ks * 64;
             build_panels_i8_kernel<<<dim3((unsigned)((t8 + 255) / 256)), dim3(256), 0, st>>>(
-                h->x32.as<float>(), n, D, D4, h->i8_ks, ntiles, h->i8_cx, h->panels8.as<int4v>(), 0, h->x16 ? 1 : 0);
-            h->bias8.reserve((size_t)2 * h->Npad * sizeof(int32_t));
-            h->rowstat8.reserve((size_t)n * 2 * sizeof(int));
+                h->rows.x32.as<float>(), n, D, D4, h->i8_ks, ntiles, h->i8_cx, h->scan.panels8.as<int4v>(), 0, h->x16 ? 1 : 0);
+            h->scan.bias8.reserve((size_t)2 * h->Npad * sizeof(int32_t));
+            h->scan.rowstat8.reserve((size_t)n * 2 * sizeof(int));
             build_bias_i8_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(
-                h->x32.as<float>(), n, h->Npad, D, D4, h->metric, h->bias8.as<int32_t>(), h->rowstat8.as<int>());
+                h->rows.x32.as<float>(), n, h->Npad, D, D4, h->metric, h->scan.bias8.as<int32_t>(), h->scan.rowstat8.as<int>());
             build_rows_i8(h, st);
             VDB_HIP(hipGetLastError());
             VDB_HIP(hipStreamSynchronize(st));
@@ -561,10 +624,10 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
     h->built = true;
 }
 
-// rows [row0, row0 + n) of h->x32 from host or device memory (h->x32 already holds room for them)
+// rows [row0, row0 + n) of h->rows.x32 from host or device memory (h->rows.x32 already holds room for them)
 void ingest_rows(vdb_index_s *h, int64_t row0, const float *x_dev_or_host, bool on_device, int64_t n, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
-    float *dst = h->x32.as<float>() + (size_t)row0 * D4;
+    float *dst = h->rows.x32.as<float>() + (size_t)row0 * D4;
     if (D4 != D) VDB_HIP(hipMemsetAsync(dst, 0, (size_t)n * D4 * sizeof(float), st));
     if (on_device)
         VDB_HIP(hipMemcpy2DAsync(dst, (size_t)D4 * 4, x_dev_or_host, (size_t)D * 4, (size_t)D * 4, (size_t)n,
@@ -582,29 +645,29 @@ void ingest_rows(vdb_index_s *h, int64_t row0, const float *x_dev_or_host, bool 
 constexpr int64_t kInt8OnlyMinRows = 32768;
 bool build_int8_only(vdb_index_s *h, const float *x, bool on_device, int64_t n, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
-    DevBuf *gone[] = {&h->x32, &h->panels, &h->slab};
+    DevBuf *gone[] = {&h->rows.x32, &h->scan.panels, &h->scan.slab};      // (not a whole group: the int8 copies are about to be sized)
     for (auto b : gone) b->release();
     h->Npad = (n + kSpanRows - 1) / kSpanRows * kSpanRows;
     h->i8_ks = D <= 64 ? 2 : 4;
     h->x16 = x16_wanted(h);                 // (more than 32 768 rows: never the dense path's)
     h->rows8_pitch = h->i8_ks * 32;
     const int64_t ntiles = h->Npad / kTileRows;
-    h->rows8.reserve_exact((size_t)n * h->rows8_pitch);
-    h->rowstat8.reserve_exact((size_t)n * 2 * sizeof(int));
-    h->xnorm2.reserve((size_t)n * sizeof(float));
-    h->stats.reserve(sizeof(IndexStats));
-    h->bias8.reserve_exact((size_t)2 * h->Npad * sizeof(int32_t));
-    h->panels8.reserve_exact((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
-    h->bias.reserve_exact((size_t)h->Npad * sizeof(float));
+    h->scan.rows8.reserve_exact((size_t)n * h->rows8_pitch);
+    h->scan.rowstat8.reserve_exact((size_t)n * 2 * sizeof(int));
+    h->rows.xnorm2.reserve((size_t)n * sizeof(float));
+    h->kept.stats.reserve(sizeof(IndexStats));
+    h->scan.bias8.reserve_exact((size_t)2 * h->Npad * sizeof(int32_t));
+    h->scan.panels8.reserve_exact((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
+    h->scan.bias.reserve_exact((size_t)h->Npad * sizeof(float));
     const bool direct = on_device && D4 == D && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     const int64_t block_want = h->int8_block_rows > 0 ? (h->int8_block_rows + kSpanRows - 1) / kSpanRows * kSpanRows : (int64_t)4 << 20;
     const int64_t block_rows = std::min<int64_t>((n + kSpanRows - 1) / kSpanRows * kSpanRows, block_want);
-    ScopedDevBuf tmp;
+    DevBuf tmp;
     if (!direct) tmp.reserve((size_t)std::min<int64_t>(block_rows, n) * D4 * sizeof(float));
     IndexStats hs{};
     int cx = -1;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        VDB_HIP(hipMemsetAsync(h->stats.p, 0, sizeof(IndexStats), st));
+        VDB_HIP(hipMemsetAsync(h->kept.stats.p, 0, sizeof(IndexStats), st));
         for (int64_t r0 = 0; r0 < n; r0 += block_rows) {
             const int64_t r1 = std::min<int64_t>(n, r0 + block_rows), nb = r1 - r0;
             const bool last = r1 == n;
@@ -621,29 +684,29 @@ bool build_int8_only(vdb_index_s *h, const float *x, bool on_device, int64_t n, 
                     upload_rows(h, dst, D4, x + (size_t)r0 * D, nb, D, st);
                 blk = dst;
             }
-            corpus_stats_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st>>>(blk, nb, D4, h->xnorm2.as<float>() + r0,
-                                                                                        h->stats.as<IndexStats>());
+            corpus_stats_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st>>>(blk, nb, D4, h->rows.xnorm2.as<float>() + r0,
+                                                                                        h->kept.stats.as<IndexStats>());
             if (cx < 0) {           // the window: from the first block's flags
-                VDB_HIP(hipMemcpyAsync(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+                VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
                 VDB_HIP(hipStreamSynchronize(st));
                 if (hs.nonfinite || (hs.not_u8 && hs.not_s8)) return false;
                 cx = !hs.not_u8 ? 128 : 0;
             }
             const int64_t words = nb * (h->rows8_pitch / 4);
             build_rows_i8_kernel<<<dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st>>>(
-                blk, nb, D, D4, h->rows8_pitch, cx, h->rows8.as<signed char>() + (size_t)r0 * h->rows8_pitch);
+                blk, nb, D, D4, h->rows8_pitch, cx, h->scan.rows8.as<signed char>() + (size_t)r0 * h->rows8_pitch);
             // (panels and accumulator inits index rows globally: base pointer moved back by the rows in front of the block)
             const float *fake = blk - (size_t)r0 * D4;
             const int64_t row_end = last ? h->Npad : r1;
             const int64_t t0 = r0 / kTileRows, nt = (row_end - r0) / kTileRows;
             build_panels_i8_kernel<<<dim3((unsigned)((nt * h->i8_ks * 64 + 255) / 256)), dim3(256), 0, st>>>(
-                fake, r1, D, D4, h->i8_ks, nt, cx, h->panels8.as<int4v>(), t0, h->x16 ? 1 : 0);
+                fake, r1, D, D4, h->i8_ks, nt, cx, h->scan.panels8.as<int4v>(), t0, h->x16 ? 1 : 0);
             build_bias_i8_kernel<<<dim3((unsigned)((row_end - r0 + 255) / 256)), dim3(256), 0, st>>>(
-                fake, r1, h->Npad, D, D4, h->metric, h->bias8.as<int32_t>(), h->rowstat8.as<int>(), r0, row_end);
+                fake, r1, h->Npad, D, D4, h->metric, h->scan.bias8.as<int32_t>(), h->scan.rowstat8.as<int>(), r0, row_end);
             VDB_HIP(hipGetLastError());
             if (!direct) VDB_HIP(hipStreamSynchronize(st));     // (the temporary is refilled by the next block)
         }
-        VDB_HIP(hipMemcpyAsync(&hs, h->stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
         VDB_HIP(hipStreamSynchronize(st));
         if (hs.nonfinite) return false;
         const bool fits = cx == 128 ? !hs.not_u8 : !hs.not_s8;
@@ -662,11 +725,11 @@ bool build_int8_only(vdb_index_s *h, const float *x, bool on_device, int64_t n, 
     h->i8_ok = true;
     h->tile16 = false;
     h->panels_streamed = false;
-    build_bias_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(h->xnorm2.as<float>(), n, h->Npad, h->metric,
-                                                                                    h->bias.as<float>());
+    build_bias_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(h->rows.xnorm2.as<float>(), n, h->Npad, h->metric,
+                                                                                    h->scan.bias.as<float>());
     VDB_HIP(hipGetLastError());
     VDB_HIP(hipStreamSynchronize(st));
-    h->xnorm2.release();                // (the float norms only fed `bias`)
+    h->rows.xnorm2.release();                // (the float norms only fed `bias`)
     h->int8_only = true;
     h->scan_ok = true;
     h->built = true;
@@ -698,12 +761,12 @@ void build_index(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
         }
         if (ok) return;
         h->int8_only = false;          // not byte-valued: the default layout (vdb_stats: has_i8_copy says which one it is)
-        DevBuf *i8[] = {&h->rows8, &h->rowstat8, &h->bias8, &h->panels8};
+        DevBuf *i8[] = {&h->scan.rows8, &h->scan.rowstat8, &h->scan.bias8, &h->scan.panels8};   // (not the whole scan group: the bias stays, as it did)
         for (auto b : i8) b->release();
     }
     try {
         if (n > 0) {
-            h->x32.reserve((size_t)n * h->D4 * sizeof(float));
+            h->rows.x32.reserve((size_t)n * h->D4 * sizeof(float));
             ingest_rows(h, 0, x_dev_or_host, on_device, n, st);
         }
         build_derived(h, st);
@@ -741,11 +804,10 @@ void append_rows(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
     // the scan copies are re-derived from the float32 rows anyway: free them first, so that the peak is old rows + grown rows
     // (not that plus the copies), and on failure rebuild them from the old rows -- the append is atomic (N, ids and results
     // as before the call)
-    DevBuf *derived[] = {&h->panels, &h->panels8, &h->rows8, &h->rowstat8, &h->bias, &h->bias8, &h->slab};
-    for (auto b : derived) b->release();
+    group_release(h->scan);
     h->built = false;
     try {
-        h->x32.grow((size_t)(N0 + n) * h->D4 * sizeof(float), (size_t)N0 * h->D4 * sizeof(float));
+        h->rows.x32.grow((size_t)(N0 + n) * h->D4 * sizeof(float), (size_t)N0 * h->D4 * sizeof(float));
         ingest_rows(h, N0, x_dev_or_host, on_device, n, st);
     } catch (...) {
         (void)hipGetLastError();
@@ -764,6 +826,22 @@ void append_rows(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
 }
 
 #include "search_flat.inc"   // scan geometry, launchers, search_batch, graph replay, search_device_impl
+
+// A host-API call: the queries go up through the staging buffers of the workspace, `run(dq, dD, dI, st)` works on the device
+// copies, (D, I) come back, and the call returns when they have -- all on the null stream.
+template <class F>
+void run_staged(vdb_index_s *h, const float *q_host, int64_t nq, int k, float *D, int64_t *I, F &&run) {
+    Workspace &ws = h->ws;
+    ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
+    ws.stage_d.reserve((size_t)nq * k * sizeof(float));
+    ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
+    hipStream_t st = nullptr;
+    VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    run(ws.stage_q.as<float>(), ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), st);
+    VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    VDB_HIP(hipStreamSynchronize(st));
+}
 
 template <class F>
 int guarded(F &&f) {
@@ -861,26 +939,8 @@ int vdb_destroy(vdb_handle h) {
         }
         set_device(h->device);
         (void)hipDeviceSynchronize();
-        DevBuf *all[] = {&h->x32, &h->xnorm2, &h->panels, &h->slab, &h->bias, &h->stats, &h->panels8, &h->bias8, &h->rows8, &h->rowstat8, &h->ivf_offsets, &h->ivf_ids,
-                         &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
-                         &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0, &h->ivf_item_list,
-                         &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of,
-                         &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param, &h->lsh_rt, &h->lsh_codes, &h->lsh_qcodes,
-                         &h->lsh_hist, &h->lsh_small, &h->lsh_list, &h->lsh_stat, &h->lsh_cand_i, &h->lsh_cand_h};
-        for (auto b : all) b->release();
         graph_reset(h);
-        if (h->graph_ev) (void)hipEventDestroy(h->graph_ev);
         if (h->coarse) (void)vdb_destroy(h->coarse);
-        h->ws.release();
-        for (int i = 0; i < 2; ++i) {
-            if (h->pin[i]) {
-                alloc_note("HF", h->pin[i], h->pin_bytes);
-                (void)hipHostFree(h->pin[i]);
-            }
-            if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]);
-        }
-        for (auto e : h->ev_scan) (void)hipEventDestroy(e);
-        for (auto e : h->ev_total) (void)hipEventDestroy(e);
         delete h;
     });
 }
@@ -914,10 +974,10 @@ int vdb_reset(vdb_handle hh) {
         h->ivf_offsets_host.clear();
         // faiss.Index.reset frees its storage: so do we (rows, scan copies, CSR arrays; the workspace and an IVF index's
         // centroids stay) -- a caller that resets a 38 GB shard to load another corpus gets the memory back
-        DevBuf *rows[] = {&h->x32, &h->xnorm2, &h->panels, &h->slab, &h->bias, &h->panels8, &h->bias8, &h->rows8, &h->rowstat8,
-                          &h->ivf_offsets, &h->ivf_ids, &h->ivf_list_pspan0, &h->ivf_span_row0, &h->ivf_span_valid,
-                          &h->sq8_codes, &h->sq8_list, &h->lsh_codes};
-        for (auto b : rows) b->release();
+        group_release(h->rows);
+        group_release(h->scan);
+        group_release(h->lists);
+        group_release(h->codes);
         h->lsh_rows = 0;                       // (the projection stays)
     });
 }
@@ -947,17 +1007,9 @@ int vdb_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float *D, 
         }
         if (h->multi) return multi_search(h, q_host, false, nq, k, D, I, nullptr, nullptr, nullptr, false);
         set_device(h->device);
-        Workspace &ws = h->ws;
-        ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
-        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
-        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
-        hipStream_t st = nullptr;
-        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-        search_device_impl(h, ws.stage_q.as<float>(), nq, k, ws.stage_d.as<float>(), ws.stage_i.as<int64_t>(), nullptr,
-                           nullptr, st);
-        VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
+            search_device_impl(h, dq, nq, k, dD, dI, nullptr, nullptr, st);
+        });
     });
 }
 
@@ -1053,9 +1105,9 @@ void rerank_device_impl(vdb_index_s *h, const float *dq, int64_t nq, const int64
         qpad = h->ws.qpad.as<float>();
     }
     RerankArgs a{};
-    a.c = RefineCommon{h->int8_only ? nullptr : h->x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, nullptr};
+    a.c = RefineCommon{h->int8_only ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, nullptr};
     if (h->int8_only) {
-        a.c.X8 = h->rows8.as<signed char>();
+        a.c.X8 = h->scan.rows8.as<signed char>();
         a.c.x8_pitch = h->rows8_pitch;
         a.c.cx = h->i8_cx;
     }
@@ -1097,21 +1149,13 @@ int vdb_rerank(vdb_handle hh, const float *q_host, int64_t nq, const int64_t *ca
         if (!q_host || !D || !I || (ncand > 0 && !cand_host) || ncand < 0) throw Error(VDB_ERR_INVALID, "bad argument");
         if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
         set_device(h->device);
-        Workspace &ws = h->ws;
-        ScopedDevBuf dc;
-        ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
-        ws.stage_d.reserve((size_t)nq * k * sizeof(float));
-        ws.stage_i.reserve((size_t)nq * k * sizeof(int64_t));
-        dc.reserve((size_t)nq * std::max(ncand, 1) * sizeof(int64_t));
-        hipStream_t st = nullptr;
-        VDB_HIP(hipMemcpyAsync(ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-        if (ncand > 0)
-            VDB_HIP(hipMemcpyAsync(dc.p, cand_host, (size_t)nq * ncand * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        rerank_device_impl(h, ws.stage_q.as<float>(), nq, dc.as<int64_t>(), ncand, k, ws.stage_d.as<float>(),
-                           ws.stage_i.as<int64_t>(), st);
-        VDB_HIP(hipMemcpyAsync(D, ws.stage_d.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipMemcpyAsync(I, ws.stage_i.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        DevBuf dc;                             // the candidate ids (freed when the call returns, results copied back)
+        run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
+            dc.reserve((size_t)nq * std::max(ncand, 1) * sizeof(int64_t));
+            if (ncand > 0)
+                VDB_HIP(hipMemcpyAsync(dc.p, cand_host, (size_t)nq * ncand * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            rerank_device_impl(h, dq, nq, dc.as<int64_t>(), ncand, k, dD, dI, st);
+        });
     });
 }
 
@@ -1128,30 +1172,17 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.dim = h->dim;
         s.metric = h->metric;
         s.corpus_fp16_exact = h->corpus_fp16_exact ? 1 : 0;
-        s.bytes_resident = (int64_t)(h->x32.cap + h->xnorm2.cap + h->panels.cap + h->slab.cap + h->bias.cap + h->stats.cap +
-                                     h->panels8.cap + h->bias8.cap + h->rows8.cap + h->rowstat8.cap + h->ws.bytes() +
-                                     h->lsh_rt.cap + h->lsh_codes.cap + h->lsh_ws_bytes());
-        {   // IVF: the CSR arrays, the per-batch plan buffers and the coarse quantizer's own index and workspace
-            const DevBuf *ivf[] = {&h->ivf_offsets, &h->ivf_ids, &h->ivf_probe_d, &h->ivf_probe_i, &h->ivf_list_pspan0,
-                                   &h->ivf_span_row0, &h->ivf_span_valid, &h->ivf_zero, &h->ivf_slot_off, &h->ivf_list_item0,
-                                   &h->ivf_item_list, &h->ivf_item_slot0, &h->ivf_item_bin0, &h->ivf_plan, &h->ivf_slot_of,
-                                   &h->sq8_codes, &h->sq8_list, &h->sq8_cent, &h->sq8_param};
-            for (auto b : ivf) s.bytes_resident += (int64_t)b->cap;
-            if (h->ivf_zero.cap) s.bytes_resident -= (int64_t)h->ws.small.cap;      // (a view into ivf_zero: counted once)
-            if (h->coarse)
-                s.bytes_resident += (int64_t)(h->coarse->x32.cap + h->coarse->xnorm2.cap + h->coarse->panels.cap +
-                                              h->coarse->bias.cap + h->coarse->ws.bytes() -
-                                              (h->coarse->ws.small.borrowed ? h->coarse->ws.small.cap : 0));
-        }
+        // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
+        s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
         s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
-        s.bytes_workspace = (int64_t)(h->ws.bytes() + h->lsh_ws_bytes());
+        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws));
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
-        if (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->ivf_plan.p) {   // (of the last batch of the call)
+        if (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->plan.ivf_plan.p) {   // (of the last batch of the call)
             IvfPlan pl;
             VDB_HIP(hipDeviceSynchronize());
-            VDB_HIP(hipMemcpy(&pl, h->ivf_plan.p, sizeof(pl), hipMemcpyDeviceToHost));
+            VDB_HIP(hipMemcpy(&pl, h->plan.ivf_plan.p, sizeof(pl), hipMemcpyDeviceToHost));
             s.last_rows_scanned = (int64_t)pl.rows_scanned;
         }
         s.scan_dtype = 0;
@@ -1186,10 +1217,10 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_candidates = (int64_t)c[0];
             s.last_rescan_bins = (int64_t)c[1];
         }
-        if (h->last.last_path == VDB_PATH_LSH && h->lsh_stat.p) {      // queries of the last LSH call that took the exact fallback
+        if (h->last.last_path == VDB_PATH_LSH && h->lsh_ws.lsh_stat.p) {      // queries of the last LSH call that took the exact fallback
             std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
             VDB_HIP(hipDeviceSynchronize());
-            VDB_HIP(hipMemcpy(c.data(), h->lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             for (int sh = 0; sh < kStatShards; ++sh) s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
         }
         if (h->ev_used > 0) {  // averages over every search recorded since timing was switched on
