@@ -74,7 +74,7 @@ typedef struct vdb_stats_s {
     int32_t nlist;             /* IVF: number of inverted lists (0 = flat index) */
     int32_t nprobe;
     int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate),
-                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 index (f32 accumulate) */
+                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists) */
@@ -84,7 +84,8 @@ typedef struct vdb_stats_s {
     int32_t scan_shape;        /* rows of the MFMA tile the flat scan copies (D <= 128) are laid out for: 16 = layout "x16"
                                   (v_mfma_*_16x16x32_f16 / 16x16x64_i8, the default above 15 360 rows), 32 = 32x32x16 / 32x32x32
                                   (option "flat_shape" = 32, small corpora, quads); 0 = no such copy (D > 128, empty index) */
-    int64_t bytes_workspace;   /* the part of bytes_resident that is per-search workspace (bin arrays, work lists, staging) */
+    int64_t bytes_workspace;   /* the part of bytes_resident that is per-search workspace (bin arrays, work lists, staging; PQ: and
+                                  the slab of fp16 panels made per search) */
     float last_prep_ms;        /* timing on: mean time from the start of the device pipeline to the start of the dominant kernel
                                   (query statistics / operands; IVF: + coarse search, plan) ... */
     float last_tail_ms;        /* ... and from its end to the end of the pipeline (bin select + exact refine): with last_scan_ms
@@ -266,6 +267,39 @@ int vdb_lsh_candidates_device(vdb_handle h, const float *q_dev, int64_t nq, int 
 int vdb_lsh_search(vdb_handle h, const float *q_host, int64_t nq, int k, int ncand, float *D, int64_t *I);
 int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, int ncand, float *D_dev, int64_t *I_dev,
                           void *stream);
+
+/* ---- flat PQ<M> -- replaces faiss.index_factory(d, "PQ<M>", metric) (IndexPQ(d, M, 8); the reference's `pq` config) --------
+ * M sub-vectors of dsub = dim / M dimensions, 256 centroids each, one byte per sub-vector.  The entry points live on an ordinary
+ * handle of vdb_create; once codebooks exist the handle is a PQ index: it keeps the codes (M bytes per row), one float32 of scan
+ * statistics per padded row and the codebooks -- NO float32 rows, no fp16 / int8 scan copies.  The contract is the library's own
+ * (FAISS' k-means, its float32 table sums and its tie order are not reproduced):
+ *   codebooks  float32 [M][256][dsub].  vdb_pq_train: one row sample (at most 256 * max_points_per_centroid rows, drawn with
+ *              `seed`) shared by all sub-spaces; sub-space m is clustered by the k-means of vdb_ivf_train (L2, 256 centroids,
+ *              niter iterations) with seed + m.  Same seed, same codebooks.  Fewer than 256 training rows: VDB_ERR_INVALID
+ *   codes      code[i][m] = argmin over c of the canonical float64 L2 key (above) between x[i][m dsub .. (m + 1) dsub) and
+ *              codebook[m][c]; ties to the smaller c, whatever the index metric
+ *   x^         x^[i] = concatenation of codebook[m][code[i][m]]: a lookup, no arithmetic
+ *   search     vdb_search / _device / _partial_device, vdb_rerank(_device), vdb_reserve, vdb_stats return, bit for bit, what a
+ *              flat index over the float32 rows x^ returns (ids, distances, ties by id; cosine is the caller's normalisation)
+ * Small corpora and batches below option "pq_scan_min_batch" take the exact kernels, which look x^ up from the codes; otherwise
+ * every search makes the fp16 panels of the scan from the codes, slab by slab ("pq_slab_chunks" scan chunks per slab; default
+ * the chunks of 524 288 rows, whatever ntotal), as (half)(codebook * sx) -- the rounding a flat build applies to x^ -- so the
+ * scan statistics and the error bound are those of the flat index over x^ (vdb_stats.scan_dtype = 2).
+ * VDB_ERR_STATE: codebooks (train / set) while the handle holds rows; add / get_codes before codebooks.  VDB_ERR_UNSUPPORTED, with
+ * a message: vdb_add / vdb_add_device on a PQ handle; a vdb_create_multi handle; options "int8_only", "stream_panels", "graph" and
+ * the layout options "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -- the panels of a PQ index are made in layout "x16" only --
+ * (in either order); vdb_lsh_* and vdb_ivf_* on a PQ handle, vdb_pq_* on an IVF handle or one with a projection.  dim % M != 0
+ * or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  vdb_reset drops the codes and keeps the codebooks. */
+int vdb_pq_train(vdb_handle h, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid);
+/* inject / read the codebooks, float32 (M, 256, dim / M) -- persistence and tests.  codebooks_host may be NULL: M only (0 = none) */
+int vdb_pq_set_codebooks(vdb_handle h, int M, const float *codebooks_host);
+int vdb_pq_get_codebooks(vdb_handle h, int *M, float *codebooks_host);
+/* encode n rows (row-major float32, host memory) and APPEND their codes; ids and id_base as vdb_add */
+int vdb_pq_add(vdb_handle h, const float *x_host, int64_t n, int64_t id_base);
+/* same with the codes given, uint8 (n, M) -- what loading a persisted index does */
+int vdb_pq_add_codes(vdb_handle h, const uint8_t *codes_host, int64_t n, int64_t id_base);
+/* codes of the indexed rows, uint8 (ntotal, M), in id (insertion) order */
+int vdb_pq_get_codes(vdb_handle h, uint8_t *codes_host);
 
 /* Sizes the search workspace for batches of up to nq queries and top-k NOW instead of inside the first search (works on
  * flat and IVF handles after add): one untimed search whose queries are corpus rows.  The reference times its very first

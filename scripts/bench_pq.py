@@ -1,0 +1,200 @@
+"""Flat PQ<M> against the flat fp16 search over the same reconstructed rows, on one workload per process.
+
+    --workload gauss128_pq16 | gauss128_pq64   Gaussian 1M x 128, l2, PQ16 / PQ64
+    --workload unit384_pq64                    unit vectors 1M x 384, inner product, PQ64
+
+10 000 queries, k = 10, everything device-resident.  Three indexes in one process:
+  (a) the PQ index (codes only; every search makes its fp16 panels from the codes, slab by slab),
+  (b) an ordinary flat index built from reconstruct() of the same codes -- the yardstick: PQ does this work plus the panel pass,
+  (c) the exact flat index of the original rows, for recall.
+(a), (b), (c) are timed alternately, one search each per round, between two device synchronisations, after `warmup` untimed
+rounds; every figure is the median over `steps` rounds.  Reported: QPS and ms per batch of each, (a) / (b), the result checksums
+of (a) and (b) (they must be equal: exit status 1 otherwise), recall@10 of (a) and (b) against (c), resident and workspace
+bytes over the float32 corpus, the stage times the library records for (a) and (b) (option "timing": prep, scan -- for (a) the
+panel pass and the scan together --, tail = select + refine; the library's timers do not split further: the per-kernel times
+of pq_panels_kernel, the scan, the select and the refine come from the kernel trace below), the panel pass as scan(a) - scan(b)
+with the bytes it writes and its rate, the same for the `stream_panels` conversion pass at D > 128 (convert_slab16_kernel, the rate the panel pass is
+measured against), the flagged queries, slab sizes ("pq_slab_chunks"), and the small-batch table: nq in {1, 8, 64, 512} on the
+panel pass + MFMA scan against the exact kernels on the codes ("force_path" 2 / 1).  The result is merged under the workload's
+name into --out (default profiles/r07_bench_pq.json) and printed as one line.  Each GPU step under its own time limit:
+
+    timeout -k 10 900 python scripts/bench_pq.py --workload gauss128_pq16 && \\
+    timeout -k 10 900 python scripts/bench_pq.py --workload gauss128_pq64 && \\
+    timeout -k 10 900 python scripts/bench_pq.py --workload unit384_pq64 && \\
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d build/pq_trace -o pq -- \\
+        python scripts/bench_pq.py --workload gauss128_pq16 --steps 5 --niter 4 --no-tables --out build/pq_trace/bench.json
+"""
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+for p in (str(ROOT), str(ROOT / "vectordb-retrieval_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+K = 10
+WORKLOADS = {"gauss128_pq16": (128, 16, "l2"), "gauss128_pq64": (128, 64, "l2"), "unit384_pq64": (384, 64, "ip")}
+
+
+def recall(exact, got, k):
+    return float(np.mean([len(set(a[:k]) & set(b[:k])) / k for a, b in zip(exact, got)]))
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=sorted(WORKLOADS), required=True)
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--nq", type=int, default=10_000)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--niter", type=int, default=25)
+    ap.add_argument("--no-tables", action="store_true", help="skip the slab-size and small-batch tables")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "r07_bench_pq.json"))
+    args = ap.parse_args()
+    import torch
+
+    import vdbhip
+
+    dev = torch.device("cuda:0")
+    d, M, metric = WORKLOADS[args.workload]
+    n, nq = args.n, args.nq
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    X_t = torch.randn((n, d), generator=g, device=dev, dtype=torch.float32)
+    Q_t = torch.randn((nq, d), generator=g, device=dev, dtype=torch.float32)
+    if metric == "ip":
+        X_t /= X_t.norm(dim=1, keepdim=True)
+        Q_t /= Q_t.norm(dim=1, keepdim=True)
+    X = X_t.cpu().numpy()
+    del X_t
+    stream = torch.cuda.current_stream().cuda_stream
+
+    pq = vdbhip.PQIndex(d, M, metric, 0)
+    t0 = time.perf_counter()
+    pq.train(X, niter=args.niter, seed=1234)
+    train_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    pq.add(X)
+    add_s = time.perf_counter() - t0
+    xh = pq.reconstruct()
+    flat = vdbhip.FlatIndex(d, metric, 0)
+    flat.add(xh)
+    del xh
+    exact = vdbhip.FlatIndex(d, metric, 0)
+    exact.add(X)
+    streamed = None
+    if d > 128:                       # the conversion pass the panel pass is measured against, in the same run
+        streamed = vdbhip.FlatIndex(d, metric, 0)
+        streamed.set_option("stream_panels", 1)
+        streamed.add(pq.reconstruct())
+    del X
+
+    out = {name: (torch.empty((nq, K), dtype=torch.float32, device=dev), torch.empty((nq, K), dtype=torch.int64, device=dev))
+           for name in ("pq", "flat", "exact", "streamed")}
+    indexes = {"pq": pq, "flat": flat, "exact": exact}
+    if streamed is not None:
+        indexes["streamed"] = streamed
+
+    def search(name, m=nq):
+        D_t, I_t = out[name]
+        indexes[name].search_device(Q_t.data_ptr(), m, K, D_t.data_ptr(), I_t.data_ptr(), stream)
+
+    def timed_alternately(names, m=nq, steps=args.steps):
+        for _ in range(args.warmup):
+            for name in names:
+                search(name, m)
+        torch.cuda.synchronize()
+        ms = {name: [] for name in names}
+        for _ in range(steps):
+            for name in names:
+                t0 = time.perf_counter()
+                search(name, m)
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+        return {name: statistics.median(v) for name, v in ms.items()}
+
+    def stages(name):
+        idx = indexes[name]
+        idx.set_option("timing", 1)
+        for _ in range(args.steps):
+            search(name)
+        torch.cuda.synchronize()
+        st = idx.stats()
+        idx.set_option("timing", 0)
+        return {"prep_ms": round(st["last_prep_ms"], 4), "scan_ms": round(st["last_scan_ms"], 4), "tail_ms": round(st["last_tail_ms"], 4),
+                "total_ms": round(st["last_total_ms"], 4)}
+
+    res = {"config": f"{args.workload}: {n} x {d}, PQ{M}, {metric}, {nq} queries, k={K}, median of {args.steps} alternating rounds",
+           "train_s": round(train_s, 2), "add_s": round(add_s, 2), "niter": args.niter}
+    ms = timed_alternately(list(indexes))
+    host = {name: (out[name][0].cpu().numpy(), out[name][1].cpu().numpy()) for name in indexes}
+    for name in indexes:
+        res[name] = {"ms_per_batch": round(ms[name], 4), "qps": round(nq / ms[name] * 1e3, 1)}
+    for name in ("pq", "flat"):
+        res[name]["result_checksum"] = hashlib.sha256(host[name][1].tobytes() + host[name][0].tobytes()).hexdigest()[:16]
+        res[name]["recall@10"] = round(recall(host["exact"][1], host[name][1], K), 6)
+    same = res["pq"]["result_checksum"] == res["flat"]["result_checksum"]
+    res["pq_equals_flat_over_reconstruction"] = same
+    res["pq_over_flat_time"] = round(ms["pq"] / ms["flat"], 4)
+    st = pq.stats()
+    res["pq"].update({"path": st["last_path_name"], "scan_dtype": st["scan_dtype"], "flagged_queries": st["last_fallback_queries"],
+                      "candidates": st["last_candidates"], "bytes_resident": st["bytes_resident"], "bytes_workspace": st["bytes_workspace"],
+                      "index_over_fp32_corpus": round((st["bytes_resident"] - st["bytes_workspace"]) / (4.0 * n * d), 5),
+                      "workspace_over_fp32_corpus": round(st["bytes_workspace"] / (4.0 * n * d), 5)})
+    sf = flat.stats()
+    res["flat"].update({"flagged_queries": sf["last_fallback_queries"], "bytes_resident": sf["bytes_resident"],
+                        "index_over_fp32_corpus": round((sf["bytes_resident"] - sf["bytes_workspace"]) / (4.0 * n * d), 5)})
+    for name in indexes:
+        if name != "exact":
+            res[name]["stages"] = stages(name)
+    dims_padded = 64 if d <= 64 else 128 if d <= 128 else (d + 63) // 64 * 64
+    rows_padded = -(-n // (512 if d <= 128 else 1024)) * (512 if d <= 128 else 1024)
+    panel_bytes = 2 * rows_padded * dims_padded
+    pass_ms = res["pq"]["stages"]["scan_ms"] - res["flat"]["stages"]["scan_ms"]
+    res["panel_pass"] = {"bytes_written": panel_bytes, "ms": round(pass_ms, 4),
+                         "tb_per_s": round(panel_bytes / max(pass_ms, 1e-6) / 1e9, 3),
+                         "share_of_pq_search": round(pass_ms / res["pq"]["stages"]["total_ms"], 4)}
+    if streamed is not None:
+        conv_ms = res["streamed"]["stages"]["scan_ms"] - res["flat"]["stages"]["scan_ms"]
+        res["convert_slab16_pass"] = {"bytes_written": panel_bytes, "ms": round(conv_ms, 4),
+                                      "tb_per_s": round(panel_bytes / max(conv_ms, 1e-6) / 1e9, 3)}
+        res["panel_pass"]["over_convert_slab16"] = round(pass_ms / max(conv_ms, 1e-6), 3)
+    if not args.no_tables:
+        slabs = {}
+        for chunks in (4, 8, 16, 32, 64, 4096):
+            pq.set_option("pq_slab_chunks", chunks)
+            slabs[str(chunks)] = round(timed_alternately(["pq"], steps=max(5, args.steps // 2))["pq"], 4)
+        pq.set_option("pq_slab_chunks", 0)
+        res["slab_chunks_ms_per_batch"] = slabs
+        table = {}
+        for m in (1, 8, 64, 512):
+            row = {}
+            for label, fp in (("panel_pass_mfma_ms", 2), ("exact_on_codes_ms", 1)):
+                pq.set_option("force_path", fp)
+                row[label] = round(timed_alternately(["pq"], m=m, steps=max(5, args.steps // 2))["pq"], 4)
+            pq.set_option("force_path", 0)
+            row["flat_resident_panels_ms"] = round(timed_alternately(["flat"], m=m, steps=max(5, args.steps // 2))["flat"], 4)
+            table[str(m)] = row
+        res["small_batches"] = table
+    for idx in indexes.values():
+        idx.close()
+    path = Path(args.out)
+    allres = json.loads(path.read_text()) if path.exists() else {}
+    allres[args.workload] = res
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(allres, indent=1) + "\n")
+    print(json.dumps({args.workload: res}))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

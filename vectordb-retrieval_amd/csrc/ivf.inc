@@ -719,6 +719,7 @@ extern "C" {
 int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(centroids_host != nullptr, VDB_ERR_INVALID, "null centroid pointer");
         ivf_require(nlist >= 1 && nlist <= (1 << 22), VDB_ERR_INVALID, "nlist out of range");
         if (h->multi) return multi_set_centroids(h, centroids_host, nlist);
@@ -733,6 +734,7 @@ int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist)
 int vdb_ivf_get_centroids(vdb_handle hh, float *centroids_host) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(h->nlist > 0, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(centroids_host != nullptr, VDB_ERR_INVALID, "null pointer");
         if (h->multi) h = multi_first_shard(h);
@@ -744,6 +746,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
                   int max_points_per_centroid) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
         ivf_require(nlist >= 1 && nlist <= (1 << 22), VDB_ERR_INVALID, "nlist out of range");
         ivf_require(n >= nlist, VDB_ERR_INVALID, "need at least nlist training vectors");
@@ -814,6 +817,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
 int vdb_ivf_set_codec(vdb_handle hh, int codec) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(codec == 0 || codec == 1, VDB_ERR_INVALID, "codec must be 0 (Flat) or 1 (SQ8)");
         if (h->multi) {
             if (codec == 1) multi_unsupported("the SQ8 codec");
@@ -833,6 +837,7 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
 int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_train_ranges");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
@@ -846,6 +851,7 @@ int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
 int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *vdiff_host) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_set_ranges");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
@@ -862,6 +868,7 @@ int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *v
 int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_get_ranges");
         ivf_require(sq8(h) && h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
@@ -873,6 +880,7 @@ int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
 int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_get_codes");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
@@ -901,6 +909,7 @@ namespace {
 int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base, const int32_t *given) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
         if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
@@ -999,6 +1008,7 @@ int vdb_ivf_add_assigned(vdb_handle hh, const float *x_host, int64_t n, int64_t 
 int vdb_ivf_set_nprobe(vdb_handle hh, int nprobe) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(nprobe >= 1, VDB_ERR_INVALID, "nprobe must be >= 1");
         h->nprobe = std::min(nprobe, 2048);
         if (h->multi) {
@@ -1012,6 +1022,7 @@ int vdb_ivf_set_nprobe(vdb_handle hh, int nprobe) {
 int vdb_ivf_get_assignment(vdb_handle hh, int32_t *list_of_row_host) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(list_of_row_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
         if (h->multi) return multi_get_assignment(h, list_of_row_host);
@@ -1023,6 +1034,7 @@ int vdb_ivf_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, 
                           void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) return multi_search(h, q_dev, true, nq, k, D_dev, I_dev, nullptr, nullptr, as_stream(stream), true);
         set_device(h->device);
         vdb_index_s::GraphKey key;
@@ -1035,6 +1047,7 @@ int vdb_ivf_search_partial_device(vdb_handle hh, const float *q_dev, int64_t nq,
                                   int64_t *ids_dev, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         if (h->multi) return multi_search(h, q_dev, true, nq, k, nullptr, nullptr, keys_dev, ids_dev, as_stream(stream), true);
         set_device(h->device);
         vdb_index_s::GraphKey key;
@@ -1068,6 +1081,8 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
                 if (h->int8_only)     // (no float32 rows: the int8 rows, converted)
                     rows_i8_to_float_kernel<<<dim3((unsigned)((m * h->dim + 255) / 256)), dim3(256), 0, st>>>(
                         h->scan.rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, dq + (size_t)q0 * h->dim);
+                else if (pq_on(h))    // (product codes: the looked-up rows x^)
+                    pq_decode_rows(h, 0, m, h->dim, dq + (size_t)q0 * h->dim, st);
                 else if (sq8(h))      // (codes: the decoded rows x^)
                     sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((m * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
                         sq8_rows(h), m, h->dim, h->D4, h->dim, dq + (size_t)q0 * h->dim);
@@ -1084,6 +1099,7 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
 int vdb_ivf_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float *D, int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
+        pq_refuse_ivf(h);
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(k >= 1 && k <= 2048, VDB_ERR_INVALID, "k must be in [1, 2048]");
         if (nq <= 0) {

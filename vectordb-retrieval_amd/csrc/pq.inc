@@ -1,0 +1,335 @@
+// pq.inc -- host side of the flat PQ<M> index (kernels: pq.hpp): codebooks, encoding adds, the derived scan statistics,
+// the per-slab panel pass of a search.  Included by vdbhip.hip; the handle's PQ state lives in vdb_index_s (pq_*).
+
+namespace {
+
+PqRows pq_rows(const vdb_index_s *h) {
+    PqRows p;
+    p.codes = h->codes.pq_codes.as<unsigned char>();
+    p.cb = h->kept.pq_cb.as<float>();
+    p.M = h->pq_M;
+    p.dsub = h->pq_dsub;
+    return p;
+}
+
+// handles that cannot become a PQ index (one device, no other row store, no option that needs resident rows or panels)
+void pq_refuse_handle(const vdb_index_s *h, const char *what) {
+    if (h->multi) multi_unsupported(what);
+    if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index (IVF<nlist>,PQ<M> is not implemented)");
+    if (h->lsh_nbits > 0)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a sign-LSH projection");
+    if (h->int8_only_opt || h->stream_panels_opt || h->graph_mode)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'int8_only', 'stream_panels' and 'graph'");
+    if (h->flat_shape_opt == 32 || h->f16_group != 8 || h->i8_group != 8)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'flat_shape' = 32, 'f16_group' = 4 and 'i8_group' "
+                                         "= 4: the panels of a PQ index are made in layout \"x16\" (octs) only");
+}
+
+void pq_require_codebooks(const vdb_index_s *h, const char *what) {
+    if (h->multi) multi_unsupported(what);
+    if (!pq_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no codebooks (call vdb_pq_train or vdb_pq_set_codebooks first)");
+}
+
+void pq_check_M(const vdb_index_s *h, int M) {
+    if (M < 1 || M > std::min(h->dim, 256)) throw Error(VDB_ERR_INVALID, "M must be in [1, min(dim, 256)]");
+    if (h->dim % M) throw Error(VDB_ERR_INVALID, "dim must be a multiple of M");
+}
+
+void pq_install_codebooks(vdb_index_s *h, int M, const float *cb_host) {
+    const size_t total = (size_t)256 * h->dim;
+    for (size_t i = 0; i < total; ++i)
+        if (!std::isfinite(cb_host[i])) throw Error(VDB_ERR_INVALID, "codebook entries must be finite");
+    graph_reset(h);
+    h->kept.pq_cb.reserve_exact(total * sizeof(float));
+    VDB_HIP(hipMemcpy(h->kept.pq_cb.p, cb_host, total * sizeof(float), hipMemcpyHostToDevice));
+    h->pq_cb_host.assign(cb_host, cb_host + total);
+    h->pq_M = M;
+    h->pq_dsub = h->dim / M;
+}
+
+// x^ of the code rows [r0, r0 + n): float32, `pitch` floats per row (zero beyond dim)
+void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st) {
+    if (n <= 0) return;
+    const int64_t blocks = std::min<int64_t>((n * pitch + 255) / 256, 1 << 16);
+    pq_decode_rows_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(h->codes.pq_codes.as<unsigned char>() + (size_t)r0 * h->pq_M,
+                                                                      h->kept.pq_cb.as<float>(), n, h->dim, h->pq_M, h->pq_dsub, pitch, out);
+    VDB_HIP(hipGetLastError());
+}
+
+// Everything a search needs besides the codes, from the h->N code rows: the flat build's statistics (row norms -> bias, max
+// norm, scale sx, fp16-exactness, integer flags) taken on a TRANSIENT float32 copy x^ -- bit for bit those of a flat index
+// over x^ -- the span / tile geometry, and the scaled fp16 table of the panel pass.  The copy and the norms are freed again.
+void pq_rebuild(vdb_index_s *h, hipStream_t st) {
+    const int D = h->dim, D4 = h->D4;
+    const int64_t n = h->N;
+    h->built = false;
+    h->scan_ok = false;
+    h->int8_only = false;
+    h->panels_streamed = false;
+    h->i8_ok = false;
+    h->tile16 = h->ksteps > kMaxKSteps;          // (D > 128: p16 panels; D <= 128: layout "x16" -- the slab is made per search either way)
+    h->x16 = !h->tile16;
+    const int64_t span_rows = h->tile16 ? kSpanRows16 : kSpanRows;
+    h->Npad = (n + span_rows - 1) / span_rows * span_rows;
+    if (n == 0) {
+        h->built = true;
+        return;
+    }
+    try {
+        h->rows.x32.reserve_exact((size_t)n * D4 * sizeof(float));
+        pq_decode_rows(h, 0, n, D4, h->rows.x32.as<float>(), st);
+        index_stats(h, st);
+        h->i8_ok = false;                        // (x^ is not kept in any integer form: the fp16 scan serves every batch)
+        if (D <= 4096 && !h->nonfinite) {
+            const int64_t total = n * D4;
+            pq_fp16_flag_kernel<<<dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 16)), dim3(256), 0, st>>>(
+                h->rows.x32.as<float>(), total, h->sx, h->kept.stats.as<IndexStats>());
+            const int64_t tab_n = (int64_t)256 * D;
+            h->scan.pq_tab.reserve_exact((size_t)tab_n * sizeof(_Float16));
+            pq_table_kernel<<<dim3((unsigned)((tab_n + 255) / 256)), dim3(256), 0, st>>>(h->kept.pq_cb.as<float>(), tab_n, h->sx,
+                                                                                       h->scan.pq_tab.as<_Float16>());
+            h->scan.bias.reserve((size_t)h->Npad * sizeof(float));
+            build_bias_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(h->rows.xnorm2.as<float>(), n, h->Npad, h->metric,
+                                                                                            h->scan.bias.as<float>());
+            VDB_HIP(hipGetLastError());
+            IndexStats hs;
+            VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+            VDB_HIP(hipStreamSynchronize(st));
+            h->corpus_fp16_exact = hs.not_fp16_exact == 0;
+            h->scan_ok = true;
+        }
+    } catch (...) {
+        h->rows.x32.release();
+        h->rows.xnorm2.release();
+        throw;
+    }
+    VDB_HIP(hipStreamSynchronize(st));
+    h->rows.x32.release();
+    h->rows.xnorm2.release();                    // (the norms only fed `bias`)
+    h->built = true;
+}
+
+// the index holds N0 + n code rows afterwards, or (on failure) the N0 it held before
+template <class F>
+void pq_append(vdb_index_s *h, int64_t n, int64_t id_base, F &&fill) {
+    if (n < 0) throw Error(VDB_ERR_INVALID, "negative row count");
+    const int64_t N0 = h->N;
+    if (N0 > 0) require_same_id_base(h, id_base);
+    if (N0 + n > 2147483647ll - 1024) throw Error(VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
+    graph_reset(h);
+    VDB_HIP(hipDeviceSynchronize());             // (searches of the codes about to move may still run)
+    if (N0 == 0) h->id_base = id_base;
+    if (n == 0) {
+        if (!h->built) pq_rebuild(h, nullptr);
+        return;
+    }
+    const size_t M = (size_t)h->pq_M;
+    h->codes.pq_codes.grow((size_t)(N0 + n) * M + 16, (size_t)N0 * M);      // (16 spare bytes: the 16-byte code loads of the panel pass)
+    fill(h->codes.pq_codes.as<unsigned char>() + (size_t)N0 * M);
+    h->N = N0 + n;
+    try {
+        pq_rebuild(h, nullptr);
+    } catch (...) {
+        (void)hipGetLastError();
+        h->N = N0;
+        try {
+            pq_rebuild(h, nullptr);
+        } catch (...) {                          // not even the old state fits any more: the index is emptied, loudly
+            h->N = 0;
+            h->built = false;
+            h->scan_ok = false;
+        }
+        throw;
+    }
+}
+
+// rows (host) -> codes (device), through a float32 block of at most ~256 MiB
+void pq_encode_host_rows(vdb_index_s *h, const float *x_host, int64_t n, unsigned char *codes, hipStream_t st) {
+    const int D = h->dim, D4 = h->D4, M = h->pq_M, dsub = h->pq_dsub;
+    const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)256 << 20) / ((int64_t)D4 * 4)));
+    DevBuf blk;
+    blk.reserve((size_t)block_rows * D4 * sizeof(float));
+    const bool in_lds = (size_t)256 * dsub * sizeof(float) <= 49152;
+    for (int64_t r0 = 0; r0 < n; r0 += block_rows) {
+        const int64_t nb = std::min<int64_t>(block_rows, n - r0);
+        if (D4 != D) VDB_HIP(hipMemsetAsync(blk.p, 0, (size_t)nb * D4 * sizeof(float), st));
+        upload_rows(h, blk.as<float>(), D4, x_host + (size_t)r0 * D, nb, D, st);
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nb + 255) / 256, 2048));
+        pq_encode_kernel<<<dim3(gx, (unsigned)M), dim3(256), in_lds ? (size_t)256 * dsub * sizeof(float) : 0, st>>>(
+            blk.as<float>(), nb, D4, h->kept.pq_cb.as<float>(), M, dsub, in_lds ? 256 * dsub : 0, codes + (size_t)r0 * M);
+        VDB_HIP(hipGetLastError());
+        VDB_HIP(hipStreamSynchronize(st));       // (the block is refilled by the next one)
+    }
+}
+
+// The panel pass of one slab: tiles [tile0, tile0 + ntiles) of the scan layout -> fp16 panels at `panels`.
+// LDS: 4 waves x the staged code rows of a tile, then the table slice.  A workgroup gets at most half a CU's 160 KiB, so
+// two run per CU; at D = 128 the whole table (64 KiB) fits, above that the 32-dim k-steps are dealt to blockIdx.y in
+// slices whose dims are whole sub-spaces.  A table no slice of which fits is read through the cache.
+constexpr int kPqLdsBudget = 80 * 1024;
+void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st) {
+    if (ntiles <= 0) return;
+    PqPanelArgs a{};
+    a.codes = h->codes.pq_codes.as<unsigned char>();
+    a.tab = h->scan.pq_tab.as<_Float16>();
+    a.panels = panels;
+    a.N = h->N;
+    a.tile0 = tile0;
+    a.ntiles = ntiles;
+    a.D = h->dim;
+    a.M = h->pq_M;
+    a.dsub = h->pq_dsub;
+    a.p16 = h->tile16 ? 1 : 0;
+    a.ksteps = h->tile16 ? h->ksteps / 2 : h->ksteps;
+    int pitch = (a.M + 3) & ~3;
+    if ((pitch / 4) % 2 == 0) pitch += 4;
+    a.code_pitch = pitch;
+    const int R = a.p16 ? 16 : 32;
+    const int stage = 4 * ((R * pitch + 15) & ~15);
+    const int ks32_n = a.p16 ? a.ksteps : a.ksteps / 2;
+    const int dsub = a.dsub;
+    int unit = dsub;                             // k-steps per slice unit: lcm(32, dsub) / 32
+    for (int gdiv = 32; gdiv >= 1; gdiv >>= 1)
+        if (dsub % gdiv == 0) { unit = dsub / gdiv; break; }
+    bool lds = false;
+    a.slice_ks = ks32_n;
+    const int64_t full = (int64_t)256 * a.D * 2;
+    size_t lds_bytes = (size_t)stage;
+    if (stage + full + (int64_t)a.M * kPqTabSkew * 2 <= kPqLdsBudget) {
+        lds = true;
+        lds_bytes += (size_t)full + (size_t)a.M * kPqTabSkew * 2;
+    } else {
+        const int64_t unit_bytes = (int64_t)unit * 32 * 512 + (int64_t)(unit * 32 / dsub) * kPqTabSkew * 2;      // (table + skew of its sub-spaces)
+        const int64_t units = (kPqLdsBudget - stage) / unit_bytes;
+        if (units >= 1 && a.p16) {
+            lds = true;
+            a.slice_ks = (int)(units * unit);
+            lds_bytes += (size_t)(units * unit_bytes);
+        }
+    }
+    const unsigned gy = (unsigned)((ks32_n + a.slice_ks - 1) / a.slice_ks);
+    if (h->pq_n_cus == 0) {                      // (of THIS handle's device)
+        int cus = 0;
+        h->pq_n_cus = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0 ? cus : 256;
+    }
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntiles + 3) / 4, (int64_t)2 * h->pq_n_cus));
+    const int W = dsub % 8 == 0 ? 8 : dsub % 4 == 0 ? 4 : dsub % 2 == 0 ? 2 : 1;
+#define VDB_PQ_PANELS(W_) do { \
+        if (lds) { \
+            if (lds_bytes > 65536)       /* (more than the default 64 KiB of dynamic LDS: opt in, on the current device, every time) */ \
+                VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_panels_kernel<W_, true>), \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, kPqLdsBudget)); \
+            pq_panels_kernel<W_, true><<<dim3(gx, gy), dim3(256), lds_bytes, st>>>(a); \
+        } else { \
+            pq_panels_kernel<W_, false><<<dim3(gx, gy), dim3(256), (size_t)stage, st>>>(a); \
+        } } while (0)
+    if (W == 8) VDB_PQ_PANELS(8);
+    else if (W == 4) VDB_PQ_PANELS(4);
+    else if (W == 2) VDB_PQ_PANELS(2);
+    else VDB_PQ_PANELS(1);
+#undef VDB_PQ_PANELS
+    VDB_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int vdb_pq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_handle(h, "vdb_pq_set_codebooks");
+        pq_check_M(h, M);
+        if (!codebooks_host) throw Error(VDB_ERR_INVALID, "null codebook pointer");
+        if (h->N > 0) throw Error(VDB_ERR_STATE, "the codebooks are set before rows exist (vdb_reset first): the codes of the " +
+                                                     std::to_string(h->N) + " rows held would lose their meaning");
+        set_device(h->device);
+        VDB_HIP(hipDeviceSynchronize());
+        pq_install_codebooks(h, M, codebooks_host);
+    });
+}
+
+int vdb_pq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        if (!M) throw Error(VDB_ERR_INVALID, "null pointer");
+        *M = h->multi ? 0 : h->pq_M;
+        if (codebooks_host && *M > 0) memcpy(codebooks_host, h->pq_cb_host.data(), h->pq_cb_host.size() * sizeof(float));
+    });
+}
+
+int vdb_pq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_handle(h, "vdb_pq_train");
+        pq_check_M(h, M);
+        if (!x_host || n <= 0) throw Error(VDB_ERR_INVALID, "no training vectors");
+        if (n < 256) throw Error(VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
+        if (niter < 0 || niter > 1000) throw Error(VDB_ERR_INVALID, "niter out of range");
+        if (h->N > 0) throw Error(VDB_ERR_STATE, "the codebooks are trained before rows exist (vdb_reset first)");
+        if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
+        const int D = h->dim, dsub = D / M;
+        // one row sample for every sub-space, drawn with `seed` (seeded partial Fisher-Yates, in draw order: vdb_ivf_train's)
+        const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
+        std::vector<int64_t> pick((size_t)n);
+        std::iota(pick.begin(), pick.end(), (int64_t)0);
+        std::mt19937_64 rng(seed);
+        for (int64_t i = 0; i < std::min<int64_t>(ns, n - 1); ++i) {
+            const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
+            std::swap(pick[(size_t)i], pick[(size_t)j]);
+        }
+        // sub-space m: the library's k-means (vdb_ivf_train on a flat L2 handle of dsub dims) over the sample, seed + m
+        std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
+        for (int m = 0; m < M; ++m) {
+            for (int64_t i = 0; i < ns; ++i)
+                memcpy(&sub[(size_t)i * dsub], x_host + (size_t)pick[(size_t)i] * D + (size_t)m * dsub, (size_t)dsub * sizeof(float));
+            vdb_handle t = nullptr;
+            int rc = vdb_create(dsub, VDB_METRIC_L2, h->device, &t);
+            if (rc == VDB_OK) rc = vdb_ivf_train(t, 256, sub.data(), ns, niter, seed + (uint64_t)m, max_points_per_centroid);
+            if (rc == VDB_OK) rc = vdb_ivf_get_centroids(t, &cb[(size_t)m * 256 * dsub]);
+            const std::string msg = rc == VDB_OK ? std::string() : g_last_error;
+            if (t) (void)vdb_destroy(t);
+            if (rc != VDB_OK) throw Error(rc, "k-means of sub-space " + std::to_string(m) + ": " + msg);
+        }
+        set_device(h->device);
+        VDB_HIP(hipDeviceSynchronize());
+        pq_install_codebooks(h, M, cb.data());
+    });
+}
+
+int vdb_pq_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_require_codebooks(h, "vdb_pq_add");
+        if (n > 0 && !x_host) throw Error(VDB_ERR_INVALID, "null corpus pointer");
+        set_device(h->device);
+        pq_append(h, n, id_base, [&](unsigned char *codes) { pq_encode_host_rows(h, x_host, n, codes, nullptr); });
+    });
+}
+
+int vdb_pq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_t id_base) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_require_codebooks(h, "vdb_pq_add_codes");
+        if (n > 0 && !codes_host) throw Error(VDB_ERR_INVALID, "null code pointer");
+        set_device(h->device);
+        pq_append(h, n, id_base, [&](unsigned char *codes) {
+            VDB_HIP(hipMemcpy(codes, codes_host, (size_t)n * h->pq_M, hipMemcpyHostToDevice));
+        });
+    });
+}
+
+int vdb_pq_get_codes(vdb_handle hh, uint8_t *codes_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_require_codebooks(h, "vdb_pq_get_codes");
+        if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
+        if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");
+        set_device(h->device);
+        VDB_HIP(hipDeviceSynchronize());
+        VDB_HIP(hipMemcpy(codes_host, h->codes.pq_codes.p, (size_t)h->N * h->pq_M, hipMemcpyDeviceToHost));
+    });
+}
+
+}  // extern "C"

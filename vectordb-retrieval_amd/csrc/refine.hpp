@@ -25,6 +25,13 @@ __device__ __forceinline__ float sq8_decode(unsigned code, float c, float vmin, 
     return c + (vmin + (((float)code + 0.5f) / 255.0f) * vdiff);
 }
 
+// the rows of a PQ<M> index (pq.hpp, include/vdbhip.h): codes [N][M], codebooks float32 [M][256][dsub]; x^ is a pure lookup
+struct PqRows {
+    const unsigned char *codes = nullptr;
+    const float *cb = nullptr;
+    int M = 0, dsub = 0;
+};
+
 struct RefineCommon {
     const float *X;     // [N][D4] float32 rows, zero padded to a multiple of 4 dims
     const float *Q;     // [nq][D4]
@@ -46,6 +53,8 @@ struct RefineCommon {
     const QueryBatchInfo *info = nullptr;
     // IVF<nlist>,SQ8 (ivf_sq8.inc): X == nullptr and sq8.codes set -- the rows are 8-bit codes, decoded to x^ in float32
     Sq8Rows sq8{};
+    // PQ<M> (pq.inc): X == nullptr and pq.codes set -- the rows are product codes, x^ looked up in the codebooks
+    PqRows pq{};
 };
 
 typedef int refine_int4 __attribute__((ext_vector_type(4)));
@@ -146,11 +155,42 @@ __device__ __forceinline__ uint64_t sq8_key(const Sq8Rows &s, int64_t row, const
     return sortable_u64(metric == 0 ? acc : -acc);
 }
 
-// key of corpus row `row`: from the float32 rows, or (c.X == nullptr) from the SQ8 codes or the int8 row copy (int8-only index)
+// The same key from the codes of a PQ index: x^[m dsub + j] = cb[m][code[m]][j] (no arithmetic), then the identical float64
+// chain over the D4 padded dimensions (a padding step is fma(0, 0, acc), as on the zero-padded float32 row) -- the key of
+// the float32 row x^.
+__device__ __forceinline__ uint64_t pq_key(const PqRows &p, int64_t row, const float *__restrict__ q, int D4, int metric) {
+    const unsigned char *cr = p.codes + (size_t)row * p.M;
+    double acc = 0.0;
+    int d = 0;
+    for (int m = 0; m < p.M; ++m) {
+        const float *cv = p.cb + ((size_t)m * 256 + cr[m]) * p.dsub;
+        for (int j = 0; j < p.dsub; ++j, ++d) {
+            const double x = (double)cv[j];
+            if (metric == 0) {
+                const double t = x - (double)q[d];
+                acc = fma(t, t, acc);
+            } else {
+                acc = fma((double)q[d], x, acc);
+            }
+        }
+    }
+    for (; d < D4; ++d) {
+        if (metric == 0) {
+            const double t = 0.0 - (double)q[d];
+            acc = fma(t, t, acc);
+        } else {
+            acc = fma((double)q[d], 0.0, acc);
+        }
+    }
+    return sortable_u64(metric == 0 ? acc : -acc);
+}
+
+// key of corpus row `row`: from the float32 rows, or (c.X == nullptr) from the SQ8 / PQ codes or the int8 row copy (int8-only index)
 template <int U = 16>
 __device__ __forceinline__ uint64_t row_key(const RefineCommon &c, int64_t row, const float *__restrict__ q) {
     if (c.X) return exact_key<U>(c.X + (size_t)row * c.D4, q, c.D4, c.metric);
     if (c.sq8.codes) return sq8_key(c.sq8, row, q, c.D4, c.metric);
+    if (c.pq.codes) return pq_key(c.pq, row, q, c.D4, c.metric);
     return exact_key_i8<U>(c.X8 + (size_t)row * c.x8_pitch, c.cx, q, c.D4, c.metric);
 }
 
@@ -526,7 +566,9 @@ __global__ __launch_bounds__(256) void refine_full_kernel(RefineFullArgs a) {
 // Query-blocked form of the exhaustive scan: one wave owns QB consecutive slots and one row range, fetches every row
 // ONCE and scores it against the QB queries (the single-query form re-reads the whole corpus per query and runs at the
 // HBM roofline: 512 MB per query per 1M x 128 rows).  Same outputs and layouts as refine_full_kernel.
-template <int KPL, int QB>
+// PQ = true: the instantiation that serves a PQ index (rows looked up from the codes, pq_key); the flat and int8-only form keeps
+// the registers it had before the PQ accessor existed.
+template <int KPL, int QB, bool PQ = false>
 __global__ __launch_bounds__(256) void refine_full_blocked_kernel(RefineFullArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t waves_total = (int64_t)gridDim.x * 4;
@@ -558,7 +600,10 @@ __global__ __launch_bounds__(256) void refine_full_blocked_kernel(RefineFullArgs
 #pragma unroll
             for (int j = 0; j < QB; ++j) key[j] = ~0ull;
             if (valid) {
-                if (a.c.X) {
+                if (PQ) {           // PQ index: the codes' row, once per query (same chains, same keys)
+#pragma unroll
+                    for (int j = 0; j < QB; ++j) key[j] = pq_key(a.c.pq, row, qptr[j], a.c.D4, a.c.metric);
+                } else if (a.c.X) {
                     exact_keys<QB>(a.c.X + (size_t)row * a.c.D4, qptr, a.c.D4, a.c.metric, key);
                 } else {            // int8-only index: the int8 row, once per query (same chains, same keys)
 #pragma unroll

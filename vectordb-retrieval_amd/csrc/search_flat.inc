@@ -196,6 +196,11 @@ void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st) {
     VDB_HIP(hipEventRecord(e, st));
 }
 
+// PQ index (pq.inc): rows per slab of per-search panels, and the smallest batch that takes the panel pass + MFMA scan
+// (measured, profiles/r07_bench_pq.json)
+constexpr int64_t kPqSlabRows = 524288;
+constexpr int64_t kPqScanMinBatch = 1;
+
 // ---- one query batch ---------------------------------------------------------------------------------
 // outputs: final (D,I) or partial (pk,pi); all device pointers for rows [0,nq) of this batch
 void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *pk, int64_t *pi,
@@ -210,7 +215,9 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         VDB_HIP(hipGetLastError());
         qpad = ws.qpad.as<float>();
     }
-    RefineCommon rc{h->int8_only ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, nullptr};
+    const bool pq = pq_on(h);
+    RefineCommon rc{(h->int8_only || pq) ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, nullptr};
+    if (pq) rc.pq = pq_rows(h);                            // (PQ: the exact kernels look x^ up from the codes, refine.hpp pq_key)
     rc.info = batch_info(ws);                             // (group size of the candidates: 4 rows, 8 on the int8 scan)
     const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
     if (h->i8_ok && h->scan.rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
@@ -224,7 +231,9 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     }
 
     ScanGeom g;
-    const bool exact_only = h->force_path == 1 || h->force_path == 3;   // 3: also without query blocking (A/B runs)
+    // (PQ: a batch below "pq_scan_min_batch" takes the exact kernels on the codes instead of decoding the corpus for it -- DESIGN 4.9)
+    const bool pq_small = pq && h->force_path != 2 && nq < (h->pq_scan_min_batch > 0 ? h->pq_scan_min_batch : kPqScanMinBatch);
+    const bool exact_only = h->force_path == 1 || h->force_path == 3 || pq_small;   // 3: also without query blocking (A/B runs)
     bool use_scan = h->scan_ok && !exact_only && k <= 1024;
     int direct_rows = 0;
     if (use_scan) {
@@ -614,6 +623,35 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                 h->scan.panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, info, buf, h->x16 ? 1 : 0);
             ScanArgs ss = sa;
             ss.panels = buf - (size_t)tile_a * h->ksteps * 64;
+            ss.chunk0 = (int)c0;
+            ss.nchunks = (int)(c1 - c0);
+            launch_scan(h, ss, (int)(c1 - c0), Qpad, st, direct_rows, nw_small);
+        }
+    } else if (pq) {
+        // PQ index: nothing but the codes is resident.  pq_panels_kernel turns the code rows of the slab's tiles into the fp16 panels
+        // a flat index over x^ would hold (same rounding, so the same bias, scales and error bound serve), the scan runs on those
+        // chunks with `panels` rebased.  Slab size: option "pq_slab_chunks", default the chunks of 524 288 rows (128 MiB at D = 128;
+        // 64 chunks measured 11 % faster than 32 and as fast as one slab, profiles/r07_bench_pq.json); it does not grow with N (chunks are <= 8192 rows below 8M rows).
+        const int64_t tiles_per_span = h->tile16 ? kTilesPerSpan16 : kTilesPerSpan;
+        const int64_t ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;
+        const int64_t chunk_rows = (int64_t)(g.spc + 1) * (h->tile16 ? kSpanRows16 : kSpanRows);
+        int64_t slab_chunks = h->pq_slab_chunks > 0 ? h->pq_slab_chunks : std::max<int64_t>(1, kPqSlabRows / chunk_rows);
+        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
+        // (default size: the slab is allocated for its full 524 288 rows whatever the corpus holds -- the workspace of a search does
+        //  not depend on N; vdb_stats counts it in bytes_workspace)
+        const int64_t max_spans = h->pq_slab_chunks > 0 ? (int64_t)(g.spc + 1) * slab_chunks
+                                                        : std::max<int64_t>(kPqSlabRows, chunk_rows) / (h->tile16 ? kSpanRows16 : kSpanRows);
+        const size_t slab_bytes = (size_t)max_spans * tiles_per_span * ksl * 64 * sizeof(half8);
+        if (h->scan.slab.cap < slab_bytes) h->scan.slab.reserve_exact(slab_bytes);
+        for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
+            const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
+            const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
+            const int64_t tile_a = span_a * tiles_per_span, ntiles = (span_b - span_a) * tiles_per_span;
+            if (span_b - span_a > max_spans) throw Error(VDB_ERR_STATE, "internal: a PQ slab exceeds its buffer");
+            half8 *buf = h->scan.slab.as<half8>();
+            launch_pq_panels(h, tile_a, ntiles, buf, st);
+            ScanArgs ss = sa;
+            ss.panels = buf - (size_t)tile_a * ksl * 64;
             ss.chunk0 = (int)c0;
             ss.nchunks = (int)(c1 - c0);
             launch_scan(h, ss, (int)(c1 - c0), Qpad, st, direct_rows, nw_small);

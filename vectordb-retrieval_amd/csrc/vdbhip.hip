@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <atomic>
 #include <functional>
+#include <numeric>
+#include <random>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -28,6 +30,7 @@
 #include "ivf_sq8.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
+#include "pq.hpp"
 
 using namespace vdb;
 
@@ -171,12 +174,14 @@ struct RowBufs {
 struct ScanBufs {
     DevBuf panels{"panels"}, slab{"slab"}, bias{"bias"};
     DevBuf panels8{"panels8"}, bias8{"bias8"}, rows8{"rows8"}, rowstat8{"rowstat8"};  // rows8 / rowstat8: row-major int8 copy + {sum x^2, sum x} for the list refine
+    DevBuf pq_tab{"pq_tab"};                                 // PQ: the codebooks scaled by sx and rounded to fp16, [M][256][dsub] (pq.hpp)
 };
 // what outlives the rows: the corpus statistics block, and what vdb_ivf_train / set_* installed   (freed with the handle)
 struct KeptBufs {
     DevBuf stats{"stats"};
     DevBuf sq8_cent{"sq8_cent"}, sq8_param{"sq8_param"};     // SQ8: centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
     DevBuf lsh_rt{"lsh_rt"};                                 // sign-LSH: R transposed [dim][nbits]
+    DevBuf pq_cb{"pq_cb"};                                   // PQ: codebooks float32 [M][256][dsub]
 };
 // IVF: the CSR arrays and the panel space (lists padded to whole spans) of the filed rows      (freed by vdb_reset)
 struct IvfListBufs {
@@ -197,6 +202,7 @@ struct IvfPlanBufs {
 struct CodeBufs {
     DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row, both in list order
     DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
+    DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
 };
 // per-search workspace of the LSH calls                                                       (freed with the handle)
 struct LshWorkspace {
@@ -345,6 +351,13 @@ struct vdb_index_s {
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
     int lsh_force_fallback = 0;              // option "lsh_force_fallback": every query takes the exact fallback of the select
     std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
+    // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
+    // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
+    int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
+    std::vector<float> pq_cb_host;           // host copy of the codebooks [M][256][dsub]
+    int pq_n_cus = 0;                        // compute units of the handle's device (grid of the panel pass; 0 = not asked yet)
+    int64_t pq_slab_chunks = 0;              // option "pq_slab_chunks": scan chunks per slab of panels (0 = default: 524 288 rows' worth)
+    int64_t pq_scan_min_batch = 0;           // option "pq_scan_min_batch": smallest batch the panel pass + MFMA scan serves (0 = default)
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -405,6 +418,17 @@ constexpr size_t kMaxTimedCalls = 1024;
 long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
+inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
+PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
+void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
+void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
+inline void pq_refuse_ivf(const vdb_index_s *h) {       // an IVF entry point on a PQ handle
+    if (!h->multi && pq_on(h))
+        throw Error(VDB_ERR_UNSUPPORTED, "this handle is a flat PQ index (vdb_pq_*): IVF<nlist>,PQ<M> is not implemented");
+}
+[[noreturn]] inline void pq_rows_are_codes() {
+    throw Error(VDB_ERR_UNSUPPORTED, "a PQ index holds its rows as codes: fill it with vdb_pq_add / vdb_pq_add_codes");
+}
 
 int kpl_for(int k) {
     int kpl = 1;
@@ -436,10 +460,14 @@ constexpr int kRefineQB = 4;
 void launch_refine_full_blocked(const RefineFullArgs &a, int64_t max_units, hipStream_t st) {
     int64_t blocks = (max_units + 3) / 4;
     blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, 8192));
-    if (kpl_for(a.c.k) == 1)
-        refine_full_blocked_kernel<1, kRefineQB><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
-    else
-        refine_full_blocked_kernel<2, kRefineQB><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
+    const bool pq = a.c.X == nullptr && a.c.pq.codes != nullptr;        // (a PQ index: the instantiation with the codes' accessor)
+    if (kpl_for(a.c.k) == 1) {
+        if (pq) refine_full_blocked_kernel<1, kRefineQB, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
+        else refine_full_blocked_kernel<1, kRefineQB><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
+    } else {
+        if (pq) refine_full_blocked_kernel<2, kRefineQB, true><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
+        else refine_full_blocked_kernel<2, kRefineQB><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(a);
+    }
     VDB_HIP(hipGetLastError());
 }
 
@@ -951,6 +979,7 @@ int vdb_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
         if (n > 0 && !x_host) throw Error(VDB_ERR_INVALID, "null corpus pointer");
         if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, false, nullptr);
         if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
+        if (pq_on(h)) pq_rows_are_codes();
         set_device(h->device);
         const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
         append_rows(h, x_host, false, n, id_base, nullptr);
@@ -988,6 +1017,7 @@ int vdb_add_device(vdb_handle hh, const float *x_dev, int64_t n, int64_t id_base
         if (n > 0 && !x_dev) throw Error(VDB_ERR_INVALID, "null corpus pointer");
         if (h->multi) return multi_add(h, x_dev, true, n, id_base, as_stream(stream), false, nullptr);
         if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
+        if (pq_on(h)) pq_rows_are_codes();
         set_device(h->device);
         const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
         append_rows(h, x_dev, true, n, id_base, as_stream(stream));
@@ -1105,7 +1135,8 @@ void rerank_device_impl(vdb_index_s *h, const float *dq, int64_t nq, const int64
         qpad = h->ws.qpad.as<float>();
     }
     RerankArgs a{};
-    a.c = RefineCommon{h->int8_only ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, nullptr};
+    a.c = RefineCommon{(h->int8_only || pq_on(h)) ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, nullptr};
+    if (pq_on(h)) a.c.pq = pq_rows(h);     // (PQ: no float32 rows -- x^ is looked up from the codes)
     if (h->int8_only) {
         a.c.X8 = h->scan.rows8.as<signed char>();
         a.c.x8_pitch = h->rows8_pitch;
@@ -1175,7 +1206,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
         s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
-        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws));
+        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
@@ -1194,6 +1225,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
         if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit codes
+        if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;
@@ -1258,7 +1290,20 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (h->lsh_nbits > 0 && value != 0 && (k == "int8_only" || k == "stream_panels"))
             throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an index with sign-LSH codes (they are encoded from, and "
                                              "re-ranked against, the resident float32 rows)");
-        if (k == "lsh_force_fallback") {       // 1: every query of an LSH call takes the exact fallback of the select (tests)
+        if (pq_on(h) && value != 0 && (k == "graph" || k == "int8_only" || k == "stream_panels"))
+            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on a PQ index (its rows are codes; every search makes "
+                                             "its panels from them)");
+        if (pq_on(h) && ((k == "flat_shape" && value == 32) || (k == "i8_shape" && value == 32) || (k == "f16_group" && value == 4) ||
+                         (k == "i8_group" && value == 4)))
+            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' = " + std::to_string((int)value) + " is not available on a PQ index: its panels are "
+                                             "made in layout \"x16\" (octs) only");
+        if (k == "pq_slab_chunks") {           // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
+            if (value < 0 || value > 4096) throw Error(VDB_ERR_INVALID, "pq_slab_chunks out of range");
+            h->pq_slab_chunks = (int64_t)value;
+        } else if (k == "pq_scan_min_batch") { // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default); smaller
+            if (value < 0 || value > 1e9) throw Error(VDB_ERR_INVALID, "pq_scan_min_batch out of range");   // ones: exact kernels on the codes
+            h->pq_scan_min_batch = (int64_t)value;
+        } else if (k == "lsh_force_fallback") {       // 1: every query of an LSH call takes the exact fallback of the select (tests)
             if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "lsh_force_fallback must be 0 or 1");
             h->lsh_force_fallback = (int)value;
         } else if (k == "graph") {
@@ -1374,6 +1419,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 
 }  // extern "C"
 
+#include "pq.inc"
 #include "lsh.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

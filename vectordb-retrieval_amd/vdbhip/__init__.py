@@ -10,6 +10,7 @@ from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher,
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
 from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
 from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
+from .pq import HipPQIndexer, HipPQSearch, HipPQSearcher, PQIndex, parse_pq_key
 from . import sharded
 from .sharded import HipShardedApproximateSearch, HipShardedExactSearch, shard_bounds
 
@@ -19,6 +20,7 @@ __all__ = [
     "register_algorithm", "register_indexer", "register_searcher", "HipExactSearch", "HipBruteForceIndexer",
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
     "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
-    "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipShardedExactSearch",
+    "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipPQIndexer", "HipPQSearcher", "HipPQSearch", "PQIndex",
+    "parse_pq_key", "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",
 ]

@@ -84,6 +84,12 @@ SIGNATURES = {
     "vdb_lsh_candidates_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_lsh_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "vdb_lsh_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_pq_train": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_uint64, c_int]),
+    "vdb_pq_set_codebooks": (c_int, [c_void_p, c_int, c_void_p]),
+    "vdb_pq_get_codebooks": (c_int, [c_void_p, POINTER(c_int), c_void_p]),
+    "vdb_pq_add": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
+    "vdb_pq_add_codes": (c_int, [c_void_p, c_void_p, c_int64, c_int64]),
+    "vdb_pq_get_codes": (c_int, [c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),
