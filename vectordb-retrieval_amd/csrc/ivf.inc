@@ -25,6 +25,7 @@ void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
     if (!h->coarse) {
         h->coarse = new vdb_index_s();
         h->coarse->device = h->device;
+        h->coarse->n_cus = h->n_cus;
         h->coarse->dim = h->dim;
         h->coarse->D4 = h->D4;
         h->coarse->ksteps = h->ksteps;
@@ -759,13 +760,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         const int Dm = h->dim, D4 = h->D4;
         // ---- sample (seeded partial Fisher-Yates), in draw order -----------------------------------
         const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * nlist);
-        std::vector<int64_t> pick((size_t)n);
-        std::iota(pick.begin(), pick.end(), (int64_t)0);
-        std::mt19937_64 rng(seed);
-        for (int64_t i = 0; i < std::min<int64_t>(ns, n - 1); ++i) {
-            const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
-            std::swap(pick[(size_t)i], pick[(size_t)j]);
-        }
+        const std::vector<int64_t> pick = sample_rows(n, ns, seed);
         std::vector<float> sample((size_t)ns * Dm);
         for (int64_t i = 0; i < ns; ++i)
             memcpy(&sample[(size_t)i * Dm], x_host + (size_t)pick[(size_t)i] * Dm, (size_t)Dm * sizeof(float));

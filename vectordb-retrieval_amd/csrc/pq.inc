@@ -209,11 +209,7 @@ void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *pane
         }
     }
     const unsigned gy = (unsigned)((ks32_n + a.slice_ks - 1) / a.slice_ks);
-    if (h->pq_n_cus == 0) {                      // (of THIS handle's device)
-        int cus = 0;
-        h->pq_n_cus = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0 ? cus : 256;
-    }
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntiles + 3) / 4, (int64_t)2 * h->pq_n_cus));
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntiles + 3) / 4, (int64_t)2 * h->n_cus));
     const int W = dsub % 8 == 0 ? 8 : dsub % 4 == 0 ? 4 : dsub % 2 == 0 ? 2 : 1;
 #define VDB_PQ_PANELS(W_) do { \
         if (lds) { \
@@ -270,15 +266,9 @@ int vdb_pq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter
         if (h->N > 0) throw Error(VDB_ERR_STATE, "the codebooks are trained before rows exist (vdb_reset first)");
         if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
         const int D = h->dim, dsub = D / M;
-        // one row sample for every sub-space, drawn with `seed` (seeded partial Fisher-Yates, in draw order: vdb_ivf_train's)
+        // one row sample for every sub-space, drawn with `seed` (vdb_ivf_train's draws)
         const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
-        std::vector<int64_t> pick((size_t)n);
-        std::iota(pick.begin(), pick.end(), (int64_t)0);
-        std::mt19937_64 rng(seed);
-        for (int64_t i = 0; i < std::min<int64_t>(ns, n - 1); ++i) {
-            const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
-            std::swap(pick[(size_t)i], pick[(size_t)j]);
-        }
+        const std::vector<int64_t> pick = sample_rows(n, ns, seed);
         // sub-space m: the library's k-means (vdb_ivf_train on a flat L2 handle of dsub dims) over the sample, seed + m
         std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
         for (int m = 0; m < M; ++m) {

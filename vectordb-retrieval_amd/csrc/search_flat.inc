@@ -202,7 +202,677 @@ constexpr int64_t kPqSlabRows = 524288;
 constexpr int64_t kPqScanMinBatch = 1;
 
 // ---- one query batch ---------------------------------------------------------------------------------
+// What the three paths of a batch share: search_batch fills it, search_dense / search_exact / search_scan read it.
 // outputs: final (D,I) or partial (pk,pi); all device pointers for rows [0,nq) of this batch
+struct Batch {
+    vdb_index_s *h;
+    Workspace &ws;
+    const float *dq;
+    int64_t nq;
+    int k;
+    float *D; int64_t *I; double *pk; int64_t *pi;
+    hipStream_t st;
+    RefineCommon rc;
+    ScanGeom g;
+    int direct_rows;
+    int32_t *fb_count;
+    unsigned long long *stat_counters;
+    long tslot;                  // timing_begin
+    bool clear_in_prep;          // workgroup 0 of query_prep_kernel clears ws.small (search_batch)
+};
+
+// the S partial lists per slot that an exhaustive pass (fa) left in its (pkeys, pids), merged into the outputs of the batch
+void merge_splits(const Batch &b, const RefineFullArgs &fa, int64_t max_slots) {
+    MergeArgs ma{};
+    ma.pkeys = fa.pkeys; ma.pids = fa.pids;
+    ma.part_stride = b.k; ma.slot_stride = (int64_t)fa.S * b.k; ma.nparts = fa.S;
+    ma.k = b.k; ma.metric = b.h->metric;
+    ma.qlist = fa.qlist; ma.count_ptr = fa.count_ptr; ma.count = fa.count;       // (the slots of the pass)
+    ma.D = b.D; ma.I = b.I; ma.okeys = b.pk; ma.oids = b.pi;
+    launch_merge(ma, max_slots, b.st);
+}
+
+// small corpora: dense fp16 scores + per-query guard + exact re-score of the few surviving rows
+// (D > 128: corpora of <= 2048 rows keep 32-row tiles for exactly this path -- build_derived -- and take the K-loop form)
+void search_dense(const Batch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const float *dq = b.dq;
+    const int64_t nq = b.nq;
+    const int k = b.k, Dm = h->dim, D4 = h->D4;
+    hipStream_t st = b.st;
+    const int64_t Qp = (nq + 63) / 64 * 64;
+    const int cand_cap = std::max(128, 2 * k + 64);
+    ws.qpanels.reserve((size_t)(Qp / 32) * h->ksteps * 64 * sizeof(half8));
+    ws.eps.reserve((size_t)nq * sizeof(float));
+    ws.dense.reserve((size_t)Qp * h->Npad * sizeof(float));
+    ws.fallback.reserve((size_t)nq * sizeof(int32_t));
+    ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
+    QueryBatchInfo *info = batch_info(ws);          // (zeroed with fb_count above)
+    const int64_t total = nq * Dm;
+    const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0};
+    const bool fused_stats = total <= kFusedStatsMax && !h->no_fused_stats;     // (serving shapes: statistics inside the prep kernel)
+    if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
+    h->info_valid_nq = nq;
+    const int64_t threads = (Qp / 32) * h->ksteps * 64;
+    EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
+               h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
+    {   // fp16 fragments and error bounds in ONE dispatch (query_prep_kernel without its int8 regions)
+        QueryPrepArgs qp{};
+        qp.Q = dq; qp.nq = nq; qp.nqtiles = Qp / 32;
+        qp.D = Dm; qp.D4 = D4; qp.ksteps = h->ksteps;
+        qp.info = info;
+        qp.qpanels = ws.qpanels.as<half8>();
+        qp.eps = ea;
+        qp.nA = qp.nB = qp.nC = (unsigned)((threads + 255) / 256);
+        qp.fused_stats = fused_stats ? 1 : 0; qp.fin = fin; qp.info_out = info;
+        query_prep_kernel<<<dim3(qp.nC + (unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(qp);
+    }
+    // (<= 256 rows sit in the lower half of the one span: tiles past them hold padding only and the register select never reads
+    //  their columns)
+    const int64_t ntiles = (h->N <= 256 && h->Npad <= 2048 && kpl_for(k) <= 4) ? ((h->N + 63) / 64 * 64) / 16 : h->Npad / kTileRows;
+    timing_mark(h, b.tslot, 0, st);
+    {
+        const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)(Qp / 64));
+        if (h->ksteps > kMaxKSteps)
+            dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+                                                                 ws.qpanels.as<half8>(), info, ntiles, h->Npad, h->N,
+                                                                 h->ksteps, ws.dense.as<float>());
+        else if (h->ksteps == 4)
+            dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+                                                              ws.qpanels.as<half8>(), info, ntiles, h->Npad,
+                                                              ws.dense.as<float>());
+        else
+            dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+                                                              ws.qpanels.as<half8>(), info, ntiles, h->Npad,
+                                                              ws.dense.as<float>());
+    }
+    timing_mark(h, b.tslot, 1, st);
+    DenseSelectArgs da{};
+    da.c = b.rc;
+    da.scores = ws.dense.as<float>();
+    da.eps = ws.eps.as<float>();
+    da.info = info;
+    da.nq = nq;
+    da.Npad = h->Npad;
+    da.cand_cap = cand_cap;
+    da.fallback = ws.fallback.as<int32_t>();
+    da.fb_list = ws.fb_list.as<int32_t>();
+    da.fb_count = b.fb_count;
+    da.stat_counters = b.stat_counters;
+    da.D = b.D;
+    da.I = b.I;
+    da.pkeys = b.pk;
+    da.pids = b.pi;
+    da.set_only = (h->set_only && b.D != nullptr) ? 1 : 0;
+    const bool reg_select = h->Npad <= 2048 && kpl_for(k) <= 4;
+    da.inline_fallback = reg_select ? 1 : 0;
+    // columns the register select reads: rows of the index rounded up to a lane row (<= 256 rows: all in the lower half of
+    // the one span, so the columns beyond hold padding scores only)
+    const int64_t ncols = h->N <= 256 ? (h->N + 63) / 64 * 64 : h->Npad;
+    da.ncols = reg_select ? ncols : 0;
+    {
+        const int kpl = kpl_for(k);
+        if (reg_select) {       // scores in registers, 4 queries per workgroup (dense.hpp)
+            const dim3 g4((unsigned)((nq + 3) / 4));
+            const size_t lds4 = (size_t)4 * 2 * cand_cap * 4;       // per wave: candidate rows + their keys
+            if (ncols <= 256 && kpl <= 2) {
+                DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 2 ? KPL : 2), 4><<<g4, dim3(256), lds4, st>>>(da)));
+            } else if (ncols <= 512) {
+                DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 8><<<g4, dim3(256), lds4, st>>>(da)));
+            } else if (h->Npad <= 1024) {
+                DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 16><<<g4, dim3(256), lds4, st>>>(da)));
+            } else {
+                DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 32><<<g4, dim3(256), lds4, st>>>(da)));
+            }
+        } else {
+            const size_t lds = (size_t)(h->Npad + cand_cap) * 4;
+            DISPATCH_KPL(kpl, (dense_select_kernel<KPL><<<dim3((unsigned)nq), dim3(64), lds, st>>>(da)));
+        }
+        VDB_HIP(hipGetLastError());
+    }
+    if (reg_select) {       // (flagged queries were served inside the select kernel)
+        timing_mark(h, b.tslot, 2, st);
+        h->last.last_path = VDB_PATH_MFMA_SCAN;
+        return;
+    }
+    // queries whose candidate list overflowed (or unusable scales): exhaustive exact pass
+    int64_t S = std::min<int64_t>(16, std::max<int64_t>(1, h->N / 1024));
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nq * k * 16));
+    S = std::max<int64_t>(1, std::min<int64_t>(S, cap));
+    ws.pkeys.reserve((size_t)nq * S * k * sizeof(double));
+    ws.pids.reserve((size_t)nq * S * k * sizeof(int64_t));
+    RefineFullArgs fa{};
+    fa.c = b.rc;
+    fa.qlist = da.fb_list;
+    fa.count_ptr = b.fb_count;
+    fa.S = (int)S;
+    fa.rows_per_split = (h->N + S - 1) / S;
+    if (S == 1 && b.D) {       // one split: the exhaustive pass writes the final rows itself, nothing to merge
+        fa.D = b.D;
+        fa.I = b.I;
+        launch_refine_full(fa, 1024, st);
+    } else {
+        fa.pkeys = ws.pkeys.as<double>();
+        fa.pids = ws.pids.as<int64_t>();
+        launch_refine_full(fa, 1024, st);
+        merge_splits(b, fa, 256);
+    }
+    timing_mark(h, b.tslot, 2, st);
+    h->last.last_path = VDB_PATH_MFMA_SCAN;
+}
+
+// exhaustive exact scan, split over S waves per query (per group of 4 queries in the query-blocked form,
+// which fetches every row once for the four: k <= 128, at least 4 queries)
+// (it needs enough (group, split) units to fill the chip: small corpora and tiny batches keep the one-query form)
+void search_exact(const Batch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const int64_t nq = b.nq;
+    hipStream_t st = b.st;
+    const int k = b.k;
+    bool blocked = kpl_for(k) <= 2 && nq >= 2 * kRefineQB && h->force_path != 3;
+    if (blocked) {
+        const int64_t g4 = (nq + kRefineQB - 1) / kRefineQB;
+        const int64_t s4 = std::min<int64_t>((4096 + g4 - 1) / g4, std::max<int64_t>(1, h->N / 2048));
+        blocked = g4 * s4 >= 1024;
+    }
+    const int64_t ngroups = blocked ? (nq + kRefineQB - 1) / kRefineQB : nq;
+    auto launch_full = [&](const RefineFullArgs &fa) {
+        if (blocked) launch_refine_full_blocked(fa, ngroups * fa.S, st);
+        else launch_refine_full(fa, nq * fa.S, st);
+    };
+    int64_t S = ((blocked ? 4096 : 8192) + ngroups - 1) / ngroups;
+    // (a split is worth >= 1024 rows; the blocked form merges 4x the partial lists per unit, so its splits are larger)
+    S = std::min<int64_t>(S, std::max<int64_t>(1, h->N / (blocked ? 2048 : 1024)));
+    // a handful of queries on a small corpus (an IVF coarse quantizer asked for 1..63 queries): one wave per query
+    // would walk all rows alone (92 us for 8 queries x 1024 centroids) -- up to 64 splits of >= 128 rows instead
+    if (!blocked && nq < 64) S = std::max<int64_t>(S, std::min<int64_t>(64, h->N / 128));
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nq * k * 16));
+    S = std::max<int64_t>(1, std::min<int64_t>(S, cap));
+    RefineFullArgs fa{};
+    fa.c = b.rc;
+    fa.count = nq;
+    fa.S = (int)S;
+    fa.rows_per_split = ((h->N + S - 1) / S + 63) / 64 * 64;     // whole 64-row wave iterations
+    if (fa.rows_per_split < 64) fa.rows_per_split = 64;
+    timing_mark(h, b.tslot, 0, st);
+    if (S == 1 && b.D) {
+        fa.D = b.D;
+        fa.I = b.I;
+        launch_full(fa);
+    } else if (S == 1) {
+        fa.pkeys = b.pk;
+        fa.pids = b.pi;
+        launch_full(fa);
+    } else {
+        ws.pkeys.reserve((size_t)nq * S * k * sizeof(double));
+        ws.pids.reserve((size_t)nq * S * k * sizeof(int64_t));
+        fa.pkeys = ws.pkeys.as<double>();
+        fa.pids = ws.pids.as<int64_t>();
+        launch_full(fa);
+        merge_splits(b, fa, nq);
+    }
+    h->last.last_path = VDB_PATH_EXACT_SCAN;
+    timing_mark(h, b.tslot, 1, st);
+    timing_mark(h, b.tslot, 2, st);
+}
+
+// ---- MFMA scan path ------------------------------------------------------------------------------
+// step 1: batch statistics, B fragments of both scans, int8 query rows, error bounds
+void scan_query_prep(const Batch &b, int64_t Qpad, bool use_i8, QueryBatchInfo *info) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const float *dq = b.dq;
+    const int64_t nq = b.nq;
+    const int Dm = h->dim, D4 = h->D4;
+    hipStream_t st = b.st;
+    const int64_t total = nq * Dm;
+    const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
+                           use_i8 ? (1 | ((h->i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only)
+    const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && !h->no_fused_stats;   // (serving shapes, scan_i8.hpp)
+    if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
+    h->info_valid_nq = nq;
+    EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
+               h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
+    const int64_t threads = (Qpad / 32) * h->ksteps * 64;      // (same element count in both layouts)
+    if (h->tile16) {
+        build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->ksteps / 2, Qpad / 16, info, ws.qpanels.as<half8>());
+        query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
+    } else {            // one dispatch: fp16 fragments | int8 fragments | int8 query rows | error bounds (scan_i8.hpp)
+        QueryPrepArgs qp{};
+        qp.Q = dq; qp.nq = nq; qp.nqtiles = Qpad / 32;
+        qp.D = Dm; qp.D4 = D4; qp.ksteps = h->ksteps; qp.ks32 = h->i8_ks; qp.pitch8 = h->rows8_pitch;
+        qp.info = info;
+        qp.qpanels = ws.qpanels.as<half8>();
+        qp.x16 = h->x16 ? 1 : 0;          // (both B-fragment forms follow the layout of the scan copies)
+        qp.eps = ea;
+        unsigned nblk = (unsigned)((threads + 255) / 256);
+        qp.nA = nblk;
+        if (use_i8) {   // (the int8 regions return at once unless the device chose the int8 scan for this batch)
+            ws.qpanels8.reserve((size_t)(Qpad / 32) * h->i8_ks * 64 * sizeof(int4v));
+            qp.qpanels8 = ws.qpanels8.as<int4v>();
+            nblk += (unsigned)(((Qpad / 32) * h->i8_ks * 64 + 255) / 256);
+        }
+        qp.nB = nblk;
+        if (use_i8 && b.rc.Q8) {
+            qp.qrows8 = ws.qrows8.as<signed char>();
+            nblk += (unsigned)((nq * h->rows8_pitch + 255) / 256);
+        }
+        qp.nC = nblk;
+        nblk += (unsigned)((nq * 16 + 255) / 256);
+        qp.fused_stats = fused_stats ? 1 : 0; qp.fin = fin; qp.info_out = info;
+        if (b.clear_in_prep) {
+            if (!fused_stats) throw Error(VDB_ERR_STATE, "ws.small was left to a prep kernel that does not take the statistics");
+            qp.clear_small = ws.small.as<unsigned>();
+        }
+        query_prep_kernel<<<dim3(nblk), dim3(256), 0, st>>>(qp);
+    }
+    VDB_HIP(hipGetLastError());
+}
+
+// Per-search panels (streamed, int8-only and PQ indexes): the chunks are scanned slab by slab.  `fill(tile_a, ntiles, buf)` makes the
+// fp16 panels of the slab's tiles [tile_a, tile_a + ntiles) in h->scan.slab (sized by the caller for `slab_chunks` chunks), then the
+// scan runs on those chunks with `panels` rebased to the slab.  Layout: tiles per span, k-steps per tile.
+template <class Fill>
+void scan_in_slabs(const Batch &b, const ScanArgs &sa, int64_t Qpad, int nw_small, int64_t tiles_per_span, int64_t ksl,
+                   int64_t slab_chunks, Fill &&fill) {
+    vdb_index_s *h = b.h;
+    const ScanGeom &g = b.g;
+    half8 *buf = h->scan.slab.as<half8>();
+    for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
+        const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
+        const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
+        const int64_t tile_a = span_a * tiles_per_span, ntiles = (span_b - span_a) * tiles_per_span;
+        if ((size_t)ntiles * ksl * 64 * sizeof(half8) > h->scan.slab.cap) throw Error(VDB_ERR_STATE, "internal: a slab of panels exceeds its buffer");
+        fill(tile_a, ntiles, buf);
+        ScanArgs ss = sa;
+        ss.panels = buf - (size_t)tile_a * ksl * 64;
+        ss.chunk0 = (int)c0;
+        ss.nchunks = (int)(c1 - c0);
+        launch_scan(h, ss, (int)(c1 - c0), Qpad, b.st, b.direct_rows, nw_small);
+    }
+}
+
+// step 2: the fp16 scan -- resident panels in one launch (or left to the paired launch of scan_i8: pair_candidate), per-search
+// panels slab by slab
+void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair_candidate) {
+    vdb_index_s *h = b.h;
+    const ScanGeom &g = b.g;
+    hipStream_t st = b.st;
+    const int Dm = h->dim, D4 = h->D4;
+    if (h->panels_streamed) {
+        // streamed panels (option "stream_panels"): chunks are scanned slab by slab -- convert the slab's float32 rows into a
+        // scratch slab (p16 panels), then launch the scan on those chunks with `panels` rebased to the slab.  Same bins, same
+        // results; one extra pass over the float32 rows per batch (0.65 ms per 786k x 768 rows, 5.5 TB/s).  Two slabs on two
+        // streams (the next slab's workgroups filling the tail of the current one) measured 171.6 ms against 178.0 ms for
+        // this single slab on a 12.5M x 768 shard, at 1.9 GB more: not kept.
+        const int64_t KS = h->ksteps / 2;
+        const int64_t chunk_rows = (int64_t)(g.spc + 1) * kSpanRows16;                  // (chunks are spc or spc + 1 spans)
+        const int64_t wgs_per_chunk = std::max<int64_t>(1, Qpad / 512);
+        // Slab size (option "stream_slab_rows", 0 = 1 280 000): the K-loop scan runs two 512-thread workgroups per CU and a
+        // workgroup of a 12.5M-row shard takes ~14.5 ms (chunks are ~50k rows: the select takes <= 1024 superbins), so a
+        // launch whose workgroup count PER XCD (chunk c runs on XCD c % 8) is not just below a multiple of 2 x 32 idles the
+        // chip for most of a round (measured, 10 000 queries = 20 workgroups per chunk: 16-chunk slabs 14.5 ms per launch,
+        // 25-chunk slabs -- four chunks on XCD 0 -- 23 ms).  Take the largest chunk count within `slab_rows` whose workgroups
+        // fill whole rounds; small query batches (few workgroups per chunk) go by rows alone.
+        const int64_t slab_rows = h->stream_slab_rows > 0 ? h->stream_slab_rows : 1280000;
+        int64_t slab_chunks = std::max<int64_t>(1, slab_rows / chunk_rows);
+        for (int r = 8; r >= 1; --r) {                       // (chunk c of a launch runs on XCD c % 8: count per XCD)
+            const int64_t fit = 8 * ((int64_t)2 * (h->n_cus / 8) * r / wgs_per_chunk);
+            if (fit >= 8 && fit <= slab_chunks) { slab_chunks = fit; break; }
+        }
+        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
+        h->scan.slab.reserve((size_t)slab_chunks * chunk_rows / kTileRows16 * KS * 64 * sizeof(half8));
+        scan_in_slabs(b, sa, Qpad, nw_small, kTilesPerSpan16, KS, slab_chunks, [&](int64_t tile_a, int64_t ntiles, half8 *buf) {
+            convert_slab16_kernel<<<dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st>>>(
+                h->rows.x32.as<float>(), h->N, Dm, D4, (int)KS, tile_a, ntiles, h->sx, buf);
+        });
+    } else if (h->int8_only) {
+        // int8-only index: there is no resident fp16 copy.  Which scan serves the batch is decided on the device, so the fp16 scan
+        // is enqueued all the same, slab by slab: convert_slab_from_i8_kernel turns the slab's int8 panels into fp16 panels (and
+        // returns at once, like the scan behind it, when the batch is integer -- the usual case), scan_kernel runs on those chunks
+        // with `panels` rebased.  The slab is small by default (option "int8_slab_chunks", 8 chunks = 16 MiB at D = 128): it is
+        // resident whether or not a non-integer batch ever comes.
+        const int64_t tiles_per_span = kTilesPerSpan;
+        const int64_t slab_chunks = std::max<int64_t>(1, std::min<int64_t>(h->int8_slab_chunks > 0 ? h->int8_slab_chunks : 8, g.nchunks));
+        const int64_t max_spans = (int64_t)(g.spc + 1) * slab_chunks;
+        if (h->scan.slab.cap < (size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8))
+            h->scan.slab.reserve_exact((size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8));
+        scan_in_slabs(b, sa, Qpad, nw_small, tiles_per_span, h->ksteps, slab_chunks, [&](int64_t tile_a, int64_t ntiles, half8 *buf) {
+            const int64_t threads = ntiles * h->ksteps * 64;
+            convert_slab_from_i8_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
+                h->scan.panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, sa.info, buf, h->x16 ? 1 : 0);
+        });
+    } else if (pq_on(h)) {
+        // PQ index: nothing but the codes is resident.  pq_panels_kernel turns the code rows of the slab's tiles into the fp16 panels
+        // a flat index over x^ would hold (same rounding, so the same bias, scales and error bound serve), the scan runs on those
+        // chunks with `panels` rebased.  Slab size: option "pq_slab_chunks", default the chunks of 524 288 rows (128 MiB at D = 128;
+        // 64 chunks measured 11 % faster than 32 and as fast as one slab, profiles/r07_bench_pq.json); it does not grow with N (chunks are <= 8192 rows below 8M rows).
+        const int64_t tiles_per_span = h->tile16 ? kTilesPerSpan16 : kTilesPerSpan;
+        const int64_t ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;
+        const int64_t chunk_rows = (int64_t)(g.spc + 1) * (h->tile16 ? kSpanRows16 : kSpanRows);
+        int64_t slab_chunks = h->pq_slab_chunks > 0 ? h->pq_slab_chunks : std::max<int64_t>(1, kPqSlabRows / chunk_rows);
+        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
+        // (default size: the slab is allocated for its full 524 288 rows whatever the corpus holds -- the workspace of a search does
+        //  not depend on N; vdb_stats counts it in bytes_workspace)
+        const int64_t max_spans = h->pq_slab_chunks > 0 ? (int64_t)(g.spc + 1) * slab_chunks
+                                                        : std::max<int64_t>(kPqSlabRows, chunk_rows) / (h->tile16 ? kSpanRows16 : kSpanRows);
+        const size_t slab_bytes = (size_t)max_spans * tiles_per_span * ksl * 64 * sizeof(half8);
+        if (h->scan.slab.cap < slab_bytes) h->scan.slab.reserve_exact(slab_bytes);
+        scan_in_slabs(b, sa, Qpad, nw_small, tiles_per_span, ksl, slab_chunks,
+                      [&](int64_t tile_a, int64_t ntiles, half8 *buf) { launch_pq_panels(h, tile_a, ntiles, buf, st); });
+    } else if (!pair_candidate)
+        launch_scan(h, sa, g.nchunks, Qpad, st, b.direct_rows, nw_small);   // (fp16: returns at once when the int8 scan serves the batch)
+}
+
+// step 3: the int8 scan (byte-valued corpora), or the paired launch of both scans; the one the device did not choose for the
+// batch returns at once
+void scan_i8(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair_candidate) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const ScanGeom &g = b.g;
+    const int64_t nq = b.nq;
+    hipStream_t st = b.st;
+    ScanI8Args s8{};
+    s8.panels = h->scan.panels8.as<int4v>();
+    s8.bias8 = h->scan.bias8.as<int32_t>();
+    s8.qpanels = ws.qpanels8.as<int4v>();
+    s8.info = sa.info;
+    s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
+    s8.sb_m1 = sa.sb_m1; s8.sb_m2 = sa.sb_m2; s8.sb_span = sa.sb_span;
+    s8.nspans = g.nspans; s8.Npad = h->Npad; s8.Qpad = Qpad; s8.nq_valid = nq;
+    s8.prio = h->scan_prio;
+    s8.spans_per_chunk = g.spc; s8.chunk_rem = g.rem; s8.nchunks = g.nchunks;
+    // i8_variant (tuning, every variant exact; scripts/sweep_i8.py): 0 = 512-query tiles (2 column blocks per wave),
+    // 4-tile stages; 1 = 8-tile stages; 2 = 1024-query tiles (4 column blocks per wave); 3 = both (default);
+    // 4 / 5 = 16 waves per workgroup (4 per SIMD) with 8- / 16-tile stages.  Odd batch sizes keep 512-query tiles.
+    int v8 = h->i8_variant;
+    if (h->x16) {
+        // layout "x16" (scan_i8x16.hpp, v_mfma_i32_16x16x64_i8): the same launch shapes -- batch: 512- or 1024-query tiles
+        // (4 or 8 column blocks of 16 queries per wave), 4- or 8-tile stages (i8_variant bits as below, 4 / 5 -> 3);
+        // serving: 1 / 2 / 4 waves of 64 queries, 4-stage staging ring (option "i8_ring": 2, 4, 8), non-temporal loads
+        int v = h->i8_variant & 3;
+        if (h->i8_variant == 4 || h->i8_variant == 5) v = 3;
+        if (Qpad % 1024 != 0) v &= 1;
+        if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v &= 1;
+        const int qtile = nw_small < 8 ? 64 * nw_small : (v >= 2) ? 1024 : 512;
+        s8.nqtiles = (int)((nw_small < 8 ? nq + qtile - 1 : Qpad) / qtile);
+        const dim3 gridx(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
+        const bool nt = h->i8_nt != 1;
+        const int ring = h->i8_ring == 0 ? 4 : h->i8_ring;
+#define VDB_X16B(KS2_) do { \
+            if (v == 3) scan_i8x16_kernel<KS2_, 8, 8><<<gridx, dim3(512), 0, st>>>(s8); \
+            else if (v == 2) scan_i8x16_kernel<KS2_, 4, 8><<<gridx, dim3(512), 0, st>>>(s8); \
+            else if (v == 1) scan_i8x16_kernel<KS2_, 8, 4><<<gridx, dim3(512), 0, st>>>(s8); \
+            else scan_i8x16_kernel<KS2_, 4, 4><<<gridx, dim3(512), 0, st>>>(s8); } while (0)
+#define VDB_X16S(KS2_, NW_) do { \
+            if (ring == 2) scan_i8x16_kernel<KS2_, 4, 4, NW_><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
+            else if (ring == 8 && NW_ >= 2) scan_i8x16_kernel<KS2_, 4, 4, NW_, (NW_ >= 2 ? 8 : 4)><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
+            else if (nt) scan_i8x16_kernel<KS2_, 4, 4, NW_, 4, 2><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
+            else scan_i8x16_kernel<KS2_, 4, 4, NW_, 4><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
+#define VDB_X16(KS2_) do { \
+            if (nw_small == 1) VDB_X16S(KS2_, 1); else if (nw_small == 2) VDB_X16S(KS2_, 2); \
+            else if (nw_small == 4) VDB_X16S(KS2_, 4); else VDB_X16B(KS2_); } while (0)
+        if (pair_candidate && (nw_small < 8 || v == 3 || v == 1)) {
+            const bool small = nw_small < 8;
+            sa.nqtiles = small ? (int)((nq + nw_small * 64 - 1) / (nw_small * 64)) : (int)(Qpad / 512);
+            const unsigned grid16 = 8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)sa.nqtiles;
+            const dim3 gridp(std::max(grid16, gridx.x));
+#define VDB_PAIR(W_) do { \
+                if (nw_small == 1) scan_pair_x16_kernel<W_, 1, 4, 4, 4, 4, 2><<<gridp, dim3(64), 0, st>>>(sa, s8); \
+                else if (nw_small == 2) scan_pair_x16_kernel<W_, 2, 4, 4, 4, 4, 2><<<gridp, dim3(128), 0, st>>>(sa, s8); \
+                else if (nw_small == 4) scan_pair_x16_kernel<W_, 4, 4, 4, 4, 4, 2><<<gridp, dim3(256), 0, st>>>(sa, s8); \
+                else if (v == 3) scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 8, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); \
+                else scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 4, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); } while (0)
+            if (h->i8_ks == 4) VDB_PAIR(true);
+            else VDB_PAIR(false);
+#undef VDB_PAIR
+            VDB_HIP(hipGetLastError());
+        } else {
+        if (pair_candidate) {      // (a shape the paired kernel is not built for: the fp16 scan as its own launch, as ever)
+            pair_candidate = false;
+            launch_scan(h, sa, g.nchunks, Qpad, st, b.direct_rows, nw_small);
+        }
+        if (h->i8_ks == 2) VDB_X16(1);
+        else VDB_X16(2);
+#undef VDB_X16B
+#undef VDB_X16S
+#undef VDB_X16
+        VDB_HIP(hipGetLastError());
+        }
+    } else {
+    const int tb8 = v8 == 6 ? 1 : v8 == 7 ? 2 : 0;             // 6 / 7: variant 3 with a pacing barrier per 1 / 2 tiles
+    if (tb8) v8 = 3;
+    if (Qpad % 1024 != 0) v8 &= 1;
+    if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v8 &= 1;     // too few 1024-query tiles to cover the chip: 512-query tiles
+    if (nw_small < 8) v8 = 8 + nw_small;
+    const int qtile = (v8 > 8) ? 64 * nw_small : (v8 >= 2) ? 1024 : 512;
+    s8.nqtiles = (int)((v8 > 8 ? nq + qtile - 1 : Qpad) / qtile);
+    const dim3 grid8(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
+#define VDB_I8G(KS_, ST_, CB_, NW_, G_) scan_i8_kernel<KS_, ST_, CB_, NW_, 16, false, G_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8)
+#define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
+    // serving shapes (1 / 2 / 4 waves per workgroup): the scan streams the copy once -- 4- or 8-stage staging ring
+    // (option "i8_ring": 0 = auto (4), 2 = the double buffer of the batch shape, 4, 8)
+#define VDB_I8R(KS_, NW_, R_) do { if (h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+                               else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
+    // (the wait for a stage is s_waitcnt vmcnt((ring - 2) x requests per wave and stage), a 6-bit counter: a one-wave
+    //  workgroup issues all 16 + 2 requests of a 4-tile stage itself, which caps its ring at 4)
+#define VDB_I8S(KS_, NW_) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
+                           if (r__ == 2) VDB_I8(KS_, 4, 2, NW_); else if (r__ == 8) VDB_I8R(KS_, NW_, (NW_ >= 2 ? 8 : 4)); \
+                           else if (nt8 && h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+                           else VDB_I8R(KS_, NW_, 4); } while (0)
+    // serving shapes read every panel byte once per search: non-temporal staging loads (option "i8_nt": 0 / 2 on, 1 off).
+    // Measured in one process (scripts/sweep_serving_hbm.py): single-query scan of 4M x 128 (512 MB, HBM) 106.2 -> 96.7 us
+    // = 4.8 -> 5.3 TB/s; of 1M x 128 (128 MB, Infinity-Cache resident between searches) 33.9 -> 33.3 us
+    const bool nt8 = h->i8_nt != 1;
+    if (tb8 && v8 == 3 && h->i8_group == 8) {
+        if (h->i8_ks == 2) {
+            if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
+            else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
+        } else {
+            if (tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
+            else scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
+        }
+    } else if (h->i8_ks == 2) {
+        switch (v8) { case 1: VDB_I8(2, 8, 2, 8); break; case 2: VDB_I8(2, 4, 4, 8); break; case 3: VDB_I8(2, 8, 4, 8); break;
+                      case 4: VDB_I8(2, 8, 2, 16); break; case 5: VDB_I8(2, 16, 2, 16); break;
+                      case 9: VDB_I8S(2, 1); break; case 10: VDB_I8S(2, 2); break; case 12: VDB_I8S(2, 4); break;
+                      default: VDB_I8(2, 4, 2, 8); }
+    } else {
+        switch (v8) { case 1: VDB_I8(4, 8, 2, 8); break; case 2: VDB_I8(4, 4, 4, 8); break; case 3: VDB_I8(4, 8, 4, 8); break;
+                      case 4: VDB_I8(4, 8, 2, 16); break; case 5: VDB_I8(4, 16, 2, 16); break;
+                      case 9: VDB_I8S(4, 1); break; case 10: VDB_I8S(4, 2); break; case 12: VDB_I8S(4, 4); break;
+                      default: VDB_I8(4, 4, 2, 8); }
+    }
+#undef VDB_I8G
+#undef VDB_I8
+#undef VDB_I8R
+#undef VDB_I8S
+    VDB_HIP(hipGetLastError());
+    }
+}
+
+// step 4: candidates per query from the bin minima
+SelectArgs scan_select(const Batch &b, const ScanArgs &sa, int64_t Qpad, int cand_cap, int rescan_cap) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const ScanGeom &g = b.g;
+    const int64_t nq = b.nq;
+    const int k = b.k, G = h->tile16 ? 4 : 2;
+    hipStream_t st = b.st;
+    SelectArgs se{};
+    se.bin_m1 = sa.bin_m1;
+    se.bin_m2 = sa.bin_m2;
+    se.sb_m1 = sa.sb_m1;
+    se.sb_m2 = sa.sb_m2;
+    se.sb_span = sa.sb_span;
+    se.eps = ws.eps.as<float>();
+    se.info = sa.info;
+    se.nq = nq;
+    se.Qpad = Qpad;
+    se.nspans = g.nspans;
+    se.N = h->N;
+    se.spans_per_chunk = g.spc;
+    se.chunk_rem = g.rem;
+    se.nchunks = g.nchunks;
+    se.k = k;
+    se.groups = G;
+    se.direct_rows = b.direct_rows;
+    if (b.direct_rows) {        // the level-1 bins are the superbins
+        se.sb_m1 = sa.bin_m1;
+        se.sb_m2 = sa.bin_m2;
+    }
+    se.cand_cap = cand_cap;
+    se.rescan_cap = rescan_cap;
+    se.f16_gmode = f16_octs(h, b.direct_rows) ? 4 : 0;
+    se.cand_rows = ws.cand.as<int32_t>();
+    se.rescan_rows = ws.rescan.as<int32_t>();
+    se.counts = ws.counts.as<int32_t>();
+    se.fallback = ws.fallback.as<int32_t>();
+    se.fb_list = ws.fb_list.as<int32_t>();
+    se.fb_count = b.fb_count;
+    se.stat_counters = b.stat_counters;
+    const int nsb_i = G * g.nchunks;
+    if (nsb_i > 128 && nsb_i <= 256 && h->select_variant == 2 && !b.direct_rows) {   // 32 lanes per query, 2 queries per wave
+        select_kernel_v2<8, 32><<<dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, st>>>(se);
+    } else if (nsb_i <= 256 && h->select_variant != 1 && !b.direct_rows) {  // multi-lane form: 16 lanes per query, 4 queries per wave
+        const unsigned sgrid = (unsigned)((nq + 15) / 16);
+        if (nsb_i <= 64)
+            select_kernel_v2<4, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
+        else if (nsb_i <= 128)
+            select_kernel_v2<8, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
+        else
+            select_kernel_v2<16, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
+    } else {
+        switch (g.vpl) {
+            case 1: launch_select<1>(se, st); break;
+            case 2: launch_select<2>(se, st); break;
+            case 4: launch_select<4>(se, st); break;
+            case 8: launch_select<8>(se, st); break;
+            case 16: launch_select<16>(se, st); break;
+            default: launch_select<32>(se, st); break;
+        }
+    }
+    VDB_HIP(hipGetLastError());
+    return se;
+}
+
+// step 5: the refine tail -- exact re-score of every query's candidates ...
+void scan_refine_tail(const Batch &b, const SelectArgs &se) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const int64_t nq = b.nq;
+    const int k = b.k;
+    hipStream_t st = b.st;
+    RefineListArgs la{};
+    la.c = b.rc;
+    la.nq = nq;
+    la.cand_rows = se.cand_rows;
+    la.rescan_rows = se.rescan_rows;
+    la.counts = se.counts;
+    la.fallback = se.fallback;
+    la.cand_cap = se.cand_cap;
+    la.rescan_cap = se.rescan_cap;
+    la.D = b.D;
+    la.I = b.I;
+    la.pkeys = b.pk;
+    la.pids = b.pi;
+    la.f16_shift = se.f16_gmode ? 3 : 2;
+    // ... and the queries whose work list overflowed (or whose scales were unusable): exhaustive exact pass, split and merged
+    // on the device, in the same launch (refine.hpp, refine_tail_kernel)
+    {
+        RefineFallbackArgs fa{};
+        fa.c = b.rc;
+        fa.fb_list = se.fb_list;
+        fa.fb_count = b.fb_count;
+        fa.max_split = (int)std::min<int64_t>(64, std::max<int64_t>(1, h->N / 4096));
+        fa.cap_units = std::max<int64_t>(nq, 4096);
+        ws.pkeys.reserve((size_t)fa.cap_units * k * sizeof(double));
+        ws.pids.reserve((size_t)fa.cap_units * k * sizeof(int64_t));
+        const size_t done_cap = ws.fb_done.cap;
+        ws.fb_done.reserve((size_t)nq * sizeof(int32_t));
+        if (ws.fb_done.cap != done_cap) VDB_HIP(hipMemsetAsync(ws.fb_done.p, 0, ws.fb_done.cap, st));   // (zero between searches)
+        fa.pkeys = ws.pkeys.as<double>();
+        fa.pids = ws.pids.as<int64_t>();
+        fa.done = ws.fb_done.as<int32_t>();
+        fa.D = b.D;
+        fa.I = b.I;
+        fa.okeys = b.pk;
+        fa.oids = b.pi;
+        const int kpl = kpl_for(k);
+        DISPATCH_KPL(kpl, (refine_tail_kernel<KPL><<<dim3(256 + (unsigned)((nq + 3) / 4)), dim3(256), 0, st>>>(la, fa, 256u)));
+        VDB_HIP(hipGetLastError());
+    }
+}
+
+// the steps in the order they are enqueued
+void search_scan(const Batch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const ScanGeom &g = b.g;
+    const int64_t nq = b.nq;
+    const int k = b.k;
+    hipStream_t st = b.st;
+    const int64_t Qpad = (nq + 511) / 512 * 512;
+    const int G = h->tile16 ? 4 : 2;
+    const int64_t nbins = g.nspans * G * (b.direct_rows ? kBinRows / b.direct_rows : 1), nsb = (int64_t)g.nchunks * G;
+    const int cand_cap = h->list_cap > 0 ? h->list_cap : std::max(64, 2 * k + 32);
+    const int rescan_cap = std::max(16, k / 2 + 8);
+    // int8 scan for byte-valued corpora: offered to the device-side choice whenever the standard geometry is in use
+    const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
+    const bool use_i8 = h->i8_ok && !i8_off && !b.direct_rows && !h->tile16;
+    ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
+    ws.eps.reserve((size_t)nq * sizeof(float));
+    ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
+    ws.bin_m2.reserve((size_t)nbins * Qpad * sizeof(float));
+    ws.sb_m1.reserve((size_t)nsb * Qpad * sizeof(float));
+    ws.sb_m2.reserve((size_t)nsb * Qpad * sizeof(float));
+    ws.sb_span.reserve((size_t)nsb * Qpad * sizeof(int32_t));
+    ws.cand.reserve((size_t)nq * cand_cap * sizeof(int32_t));
+    ws.rescan.reserve((size_t)nq * rescan_cap * 2 * sizeof(int32_t));
+    ws.counts.reserve((size_t)nq * 2 * sizeof(int32_t));
+    ws.fallback.reserve((size_t)nq * sizeof(int32_t));
+    ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
+
+    QueryBatchInfo *info = batch_info(ws);              // (zeroed with fb_count above)
+    scan_query_prep(b, Qpad, use_i8, info);
+
+    ScanArgs sa{};
+    sa.panels = h->scan.panels.as<half8>();
+    sa.bias = h->scan.bias.as<float>();
+    sa.qpanels = ws.qpanels.as<half8>();
+    sa.info = info;
+    sa.bin_m1 = ws.bin_m1.as<float>();
+    sa.bin_m2 = ws.bin_m2.as<float>();
+    sa.sb_m1 = ws.sb_m1.as<float>();
+    sa.sb_m2 = ws.sb_m2.as<float>();
+    sa.sb_span = ws.sb_span.as<int32_t>();
+    sa.nspans = g.nspans;
+    sa.spans_per_chunk = g.spc;
+    sa.chunk_rem = g.rem;
+    sa.nchunks = g.nchunks;
+    sa.Qpad = Qpad;
+    sa.nq_valid = nq;
+    sa.prio = h->scan_prio;
+    timing_mark(h, b.tslot, 0, st);
+    // small batches: as many waves per workgroup as there are 64-query column groups (1, 2, 4; 8 = the batch shape)
+    const int nw_small = h->small_batch_off ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
+    // layout "x16" with both scan copies resident: ONE launch holds both scans (scan_pair_x16_kernel, scan_x16.hpp) when every tuning
+    // option is at its default; otherwise (and on the 32-row layout) both are enqueued and the one not needed returns at once
+    const bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && b.direct_rows == 0 &&
+                          !h->scan_pair_off && h->i8_ring == 0 && h->i8_nt == 0 && h->f16_stage_tiles == 0 && h->i8_variant == 3;
+    scan_fp16(b, sa, Qpad, nw_small, pair_candidate);
+    if (use_i8) scan_i8(b, sa, Qpad, nw_small, pair_candidate);
+    timing_mark(h, b.tslot, 1, st);
+    const SelectArgs se = scan_select(b, sa, Qpad, cand_cap, rescan_cap);
+    scan_refine_tail(b, se);
+    timing_mark(h, b.tslot, 2, st);
+    h->last.last_path = VDB_PATH_MFMA_SCAN;
+}
+
+// what all paths share -- padded queries, where the rows live, geometry and path choice, the clearing of ws.small, timing_begin --
+// then the path
 void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *pk, int64_t *pi,
                   hipStream_t st) {
     Workspace &ws = h->ws;
@@ -215,9 +885,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
         VDB_HIP(hipGetLastError());
         qpad = ws.qpad.as<float>();
     }
-    const bool pq = pq_on(h);
-    RefineCommon rc{(h->int8_only || pq) ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, nullptr};
-    if (pq) rc.pq = pq_rows(h);                            // (PQ: the exact kernels look x^ up from the codes, refine.hpp pq_key)
+    RefineCommon rc = flat_rows(h, qpad, k);
     rc.info = batch_info(ws);                             // (group size of the candidates: 4 rows, 8 on the int8 scan)
     const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
     if (h->i8_ok && h->scan.rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
@@ -232,7 +900,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 
     ScanGeom g;
     // (PQ: a batch below "pq_scan_min_batch" takes the exact kernels on the codes instead of decoding the corpus for it -- DESIGN 4.9)
-    const bool pq_small = pq && h->force_path != 2 && nq < (h->pq_scan_min_batch > 0 ? h->pq_scan_min_batch : kPqScanMinBatch);
+    const bool pq_small = pq_on(h) && h->force_path != 2 && nq < (h->pq_scan_min_batch > 0 ? h->pq_scan_min_batch : kPqScanMinBatch);
     const bool exact_only = h->force_path == 1 || h->force_path == 3 || pq_small;   // 3: also without query blocking (A/B runs)
     bool use_scan = h->scan_ok && !exact_only && k <= 1024;
     int direct_rows = 0;
@@ -266,615 +934,14 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 
     const long tslot = timing_begin(h, st);
 
-    // small corpora: dense fp16 scores + per-query guard + exact re-score of the few surviving rows
-    // (D > 128: corpora of <= 2048 rows keep 32-row tiles for exactly this path -- build_derived -- and take the K-loop form)
+    // small corpora: the dense path (search_dense)
     const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->scan.panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
                            h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= h->N &&
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
-    if (use_dense) {
-        const int64_t Qp = (nq + 63) / 64 * 64;
-        const int cand_cap = std::max(128, 2 * k + 64);
-        ws.qpanels.reserve((size_t)(Qp / 32) * h->ksteps * 64 * sizeof(half8));
-        ws.eps.reserve((size_t)nq * sizeof(float));
-        ws.dense.reserve((size_t)Qp * h->Npad * sizeof(float));
-        ws.fallback.reserve((size_t)nq * sizeof(int32_t));
-        ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
-        QueryBatchInfo *info = batch_info(ws);          // (zeroed with fb_count above)
-        const int64_t total = nq * Dm;
-        const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0};
-        const bool fused_stats = total <= kFusedStatsMax && !h->no_fused_stats;     // (serving shapes: statistics inside the prep kernel)
-        if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
-        h->info_valid_nq = nq;
-        const int64_t threads = (Qp / 32) * h->ksteps * 64;
-        EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
-                   h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
-        {   // fp16 fragments and error bounds in ONE dispatch (query_prep_kernel without its int8 regions)
-            QueryPrepArgs qp{};
-            qp.Q = dq; qp.nq = nq; qp.nqtiles = Qp / 32;
-            qp.D = Dm; qp.D4 = D4; qp.ksteps = h->ksteps;
-            qp.info = info;
-            qp.qpanels = ws.qpanels.as<half8>();
-            qp.eps = ea;
-            qp.nA = qp.nB = qp.nC = (unsigned)((threads + 255) / 256);
-            qp.fused_stats = fused_stats ? 1 : 0; qp.fin = fin; qp.info_out = info;
-            query_prep_kernel<<<dim3(qp.nC + (unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(qp);
-        }
-        // (<= 256 rows sit in the lower half of the one span: tiles past them hold padding only and the register select never reads
-        //  their columns)
-        const int64_t ntiles = (h->N <= 256 && h->Npad <= 2048 && kpl_for(k) <= 4) ? ((h->N + 63) / 64 * 64) / 16 : h->Npad / kTileRows;
-        timing_mark(h, tslot, 0, st);
-        {
-            const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)(Qp / 64));
-            if (h->ksteps > kMaxKSteps)
-                dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
-                                                                     ws.qpanels.as<half8>(), info, ntiles, h->Npad, h->N,
-                                                                     h->ksteps, ws.dense.as<float>());
-            else if (h->ksteps == 4)
-                dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
-                                                                  ws.qpanels.as<half8>(), info, ntiles, h->Npad,
-                                                                  ws.dense.as<float>());
-            else
-                dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
-                                                                  ws.qpanels.as<half8>(), info, ntiles, h->Npad,
-                                                                  ws.dense.as<float>());
-        }
-        timing_mark(h, tslot, 1, st);
-        DenseSelectArgs da{};
-        da.c = rc;
-        da.scores = ws.dense.as<float>();
-        da.eps = ws.eps.as<float>();
-        da.info = info;
-        da.nq = nq;
-        da.Npad = h->Npad;
-        da.cand_cap = cand_cap;
-        da.fallback = ws.fallback.as<int32_t>();
-        da.fb_list = ws.fb_list.as<int32_t>();
-        da.fb_count = fb_count;
-        da.stat_counters = stat_counters;
-        da.D = D;
-        da.I = I;
-        da.pkeys = pk;
-        da.pids = pi;
-        da.set_only = (h->set_only && D != nullptr) ? 1 : 0;
-        const bool reg_select = h->Npad <= 2048 && kpl_for(k) <= 4;
-        da.inline_fallback = reg_select ? 1 : 0;
-        // columns the register select reads: rows of the index rounded up to a lane row (<= 256 rows: all in the lower half of
-        // the one span, so the columns beyond hold padding scores only)
-        const int64_t ncols = h->N <= 256 ? (h->N + 63) / 64 * 64 : h->Npad;
-        da.ncols = reg_select ? ncols : 0;
-        {
-            const int kpl = kpl_for(k);
-            if (reg_select) {       // scores in registers, 4 queries per workgroup (dense.hpp)
-                const dim3 g4((unsigned)((nq + 3) / 4));
-                const size_t lds4 = (size_t)4 * 2 * cand_cap * 4;       // per wave: candidate rows + their keys
-                if (ncols <= 256 && kpl <= 2) {
-                    DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 2 ? KPL : 2), 4><<<g4, dim3(256), lds4, st>>>(da)));
-                } else if (ncols <= 512) {
-                    DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 8><<<g4, dim3(256), lds4, st>>>(da)));
-                } else if (h->Npad <= 1024) {
-                    DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 16><<<g4, dim3(256), lds4, st>>>(da)));
-                } else {
-                    DISPATCH_KPL(kpl, (dense_select_reg_kernel<(KPL <= 4 ? KPL : 4), 32><<<g4, dim3(256), lds4, st>>>(da)));
-                }
-            } else {
-                const size_t lds = (size_t)(h->Npad + cand_cap) * 4;
-                DISPATCH_KPL(kpl, (dense_select_kernel<KPL><<<dim3((unsigned)nq), dim3(64), lds, st>>>(da)));
-            }
-            VDB_HIP(hipGetLastError());
-        }
-        if (reg_select) {       // (flagged queries were served inside the select kernel)
-            timing_mark(h, tslot, 2, st);
-            h->last.last_path = VDB_PATH_MFMA_SCAN;
-            return;
-        }
-        // queries whose candidate list overflowed (or unusable scales): exhaustive exact pass
-        int64_t S = std::min<int64_t>(16, std::max<int64_t>(1, h->N / 1024));
-        const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nq * k * 16));
-        S = std::max<int64_t>(1, std::min<int64_t>(S, cap));
-        ws.pkeys.reserve((size_t)nq * S * k * sizeof(double));
-        ws.pids.reserve((size_t)nq * S * k * sizeof(int64_t));
-        RefineFullArgs fa{};
-        fa.c = rc;
-        fa.qlist = da.fb_list;
-        fa.count_ptr = fb_count;
-        fa.S = (int)S;
-        fa.rows_per_split = (h->N + S - 1) / S;
-        if (S == 1 && D) {       // one split: the exhaustive pass writes the final rows itself, nothing to merge
-            fa.D = D;
-            fa.I = I;
-            launch_refine_full(fa, 1024, st);
-        } else {
-            fa.pkeys = ws.pkeys.as<double>();
-            fa.pids = ws.pids.as<int64_t>();
-            launch_refine_full(fa, 1024, st);
-            MergeArgs ma{};
-            ma.pkeys = fa.pkeys;
-            ma.pids = fa.pids;
-            ma.part_stride = k;
-            ma.slot_stride = S * k;
-            ma.nparts = (int)S;
-            ma.k = k;
-            ma.metric = h->metric;
-            ma.qlist = da.fb_list;
-            ma.count_ptr = fb_count;
-            ma.D = D;
-            ma.I = I;
-            ma.okeys = pk;
-            ma.oids = pi;
-            launch_merge(ma, 256, st);
-        }
-        timing_mark(h, tslot, 2, st);
-        h->last.last_path = VDB_PATH_MFMA_SCAN;
-        return;
-    }
-
-    if (!use_scan) {
-        // exhaustive exact scan, split over S waves per query (per group of 4 queries in the query-blocked form,
-        // which fetches every row once for the four: k <= 128, at least 4 queries)
-        // (it needs enough (group, split) units to fill the chip: small corpora and tiny batches keep the one-query form)
-        bool blocked = kpl_for(k) <= 2 && nq >= 2 * kRefineQB && h->force_path != 3;
-        if (blocked) {
-            const int64_t g4 = (nq + kRefineQB - 1) / kRefineQB;
-            const int64_t s4 = std::min<int64_t>((4096 + g4 - 1) / g4, std::max<int64_t>(1, h->N / 2048));
-            blocked = g4 * s4 >= 1024;
-        }
-        const int64_t ngroups = blocked ? (nq + kRefineQB - 1) / kRefineQB : nq;
-        auto launch_full = [&](const RefineFullArgs &fa) {
-            if (blocked) launch_refine_full_blocked(fa, ngroups * fa.S, st);
-            else launch_refine_full(fa, nq * fa.S, st);
-        };
-        int64_t S = ((blocked ? 4096 : 8192) + ngroups - 1) / ngroups;
-        // (a split is worth >= 1024 rows; the blocked form merges 4x the partial lists per unit, so its splits are larger)
-        S = std::min<int64_t>(S, std::max<int64_t>(1, h->N / (blocked ? 2048 : 1024)));
-        // a handful of queries on a small corpus (an IVF coarse quantizer asked for 1..63 queries): one wave per query
-        // would walk all rows alone (92 us for 8 queries x 1024 centroids) -- up to 64 splits of >= 128 rows instead
-        if (!blocked && nq < 64) S = std::max<int64_t>(S, std::min<int64_t>(64, h->N / 128));
-        const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nq * k * 16));
-        S = std::max<int64_t>(1, std::min<int64_t>(S, cap));
-        RefineFullArgs fa{};
-        fa.c = rc;
-        fa.count = nq;
-        fa.S = (int)S;
-        fa.rows_per_split = ((h->N + S - 1) / S + 63) / 64 * 64;     // whole 64-row wave iterations
-        if (fa.rows_per_split < 64) fa.rows_per_split = 64;
-        timing_mark(h, tslot, 0, st);
-        if (S == 1 && D) {
-            fa.D = D;
-            fa.I = I;
-            launch_full(fa);
-        } else if (S == 1) {
-            fa.pkeys = pk;
-            fa.pids = pi;
-            launch_full(fa);
-        } else {
-            ws.pkeys.reserve((size_t)nq * S * k * sizeof(double));
-            ws.pids.reserve((size_t)nq * S * k * sizeof(int64_t));
-            fa.pkeys = ws.pkeys.as<double>();
-            fa.pids = ws.pids.as<int64_t>();
-            launch_full(fa);
-            MergeArgs ma{};
-            ma.pkeys = fa.pkeys;
-            ma.pids = fa.pids;
-            ma.part_stride = k;
-            ma.slot_stride = S * k;
-            ma.nparts = (int)S;
-            ma.k = k;
-            ma.metric = h->metric;
-            ma.count = nq;
-            ma.D = D;
-            ma.I = I;
-            ma.okeys = pk;
-            ma.oids = pi;
-            launch_merge(ma, nq, st);
-        }
-        h->last.last_path = VDB_PATH_EXACT_SCAN;
-        timing_mark(h, tslot, 1, st);
-        timing_mark(h, tslot, 2, st);
-        return;
-    }
-
-    // ---- MFMA scan path ------------------------------------------------------------------------------
-    const int64_t Qpad = (nq + 511) / 512 * 512;
-    const int G = h->tile16 ? 4 : 2;
-    const int64_t nbins = g.nspans * G * (direct_rows ? kBinRows / direct_rows : 1), nsb = (int64_t)g.nchunks * G;
-    const int cand_cap = h->list_cap > 0 ? h->list_cap : std::max(64, 2 * k + 32);
-    const int rescan_cap = std::max(16, k / 2 + 8);
-    // int8 scan for byte-valued corpora: offered to the device-side choice whenever the standard geometry is in use
-    const bool use_i8 = h->i8_ok && !i8_off && !direct_rows && !h->tile16;
-    ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
-    ws.eps.reserve((size_t)nq * sizeof(float));
-    ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
-    ws.bin_m2.reserve((size_t)nbins * Qpad * sizeof(float));
-    ws.sb_m1.reserve((size_t)nsb * Qpad * sizeof(float));
-    ws.sb_m2.reserve((size_t)nsb * Qpad * sizeof(float));
-    ws.sb_span.reserve((size_t)nsb * Qpad * sizeof(int32_t));
-    ws.cand.reserve((size_t)nq * cand_cap * sizeof(int32_t));
-    ws.rescan.reserve((size_t)nq * rescan_cap * 2 * sizeof(int32_t));
-    ws.counts.reserve((size_t)nq * 2 * sizeof(int32_t));
-    ws.fallback.reserve((size_t)nq * sizeof(int32_t));
-    ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
-
-    QueryBatchInfo *info = batch_info(ws);              // (zeroed with fb_count above)
-    {
-        const int64_t total = nq * Dm;
-        const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                               use_i8 ? (1 | ((h->i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only)
-        const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && !h->no_fused_stats;   // (serving shapes, scan_i8.hpp)
-        if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
-        h->info_valid_nq = nq;
-        EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
-                   h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
-        const int64_t threads = (Qpad / 32) * h->ksteps * 64;      // (same element count in both layouts)
-        if (h->tile16) {
-            build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->ksteps / 2, Qpad / 16, info, ws.qpanels.as<half8>());
-            query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
-        } else {            // one dispatch: fp16 fragments | int8 fragments | int8 query rows | error bounds (scan_i8.hpp)
-            QueryPrepArgs qp{};
-            qp.Q = dq; qp.nq = nq; qp.nqtiles = Qpad / 32;
-            qp.D = Dm; qp.D4 = D4; qp.ksteps = h->ksteps; qp.ks32 = h->i8_ks; qp.pitch8 = h->rows8_pitch;
-            qp.info = info;
-            qp.qpanels = ws.qpanels.as<half8>();
-            qp.x16 = h->x16 ? 1 : 0;          // (both B-fragment forms follow the layout of the scan copies)
-            qp.eps = ea;
-            unsigned nblk = (unsigned)((threads + 255) / 256);
-            qp.nA = nblk;
-            if (use_i8) {   // (the int8 regions return at once unless the device chose the int8 scan for this batch)
-                ws.qpanels8.reserve((size_t)(Qpad / 32) * h->i8_ks * 64 * sizeof(int4v));
-                qp.qpanels8 = ws.qpanels8.as<int4v>();
-                nblk += (unsigned)(((Qpad / 32) * h->i8_ks * 64 + 255) / 256);
-            }
-            qp.nB = nblk;
-            if (use_i8 && rc.Q8) {
-                qp.qrows8 = ws.qrows8.as<signed char>();
-                nblk += (unsigned)((nq * h->rows8_pitch + 255) / 256);
-            }
-            qp.nC = nblk;
-            nblk += (unsigned)((nq * 16 + 255) / 256);
-            qp.fused_stats = fused_stats ? 1 : 0; qp.fin = fin; qp.info_out = info;
-            if (clear_in_prep) {
-                if (!fused_stats) throw Error(VDB_ERR_STATE, "ws.small was left to a prep kernel that does not take the statistics");
-                qp.clear_small = ws.small.as<unsigned>();
-            }
-            query_prep_kernel<<<dim3(nblk), dim3(256), 0, st>>>(qp);
-        }
-        VDB_HIP(hipGetLastError());
-    }
-
-    ScanArgs sa{};
-    sa.panels = h->scan.panels.as<half8>();
-    sa.bias = h->scan.bias.as<float>();
-    sa.qpanels = ws.qpanels.as<half8>();
-    sa.info = info;
-    sa.bin_m1 = ws.bin_m1.as<float>();
-    sa.bin_m2 = ws.bin_m2.as<float>();
-    sa.sb_m1 = ws.sb_m1.as<float>();
-    sa.sb_m2 = ws.sb_m2.as<float>();
-    sa.sb_span = ws.sb_span.as<int32_t>();
-    sa.nspans = g.nspans;
-    sa.spans_per_chunk = g.spc;
-    sa.chunk_rem = g.rem;
-    sa.nchunks = g.nchunks;
-    sa.Qpad = Qpad;
-    sa.nq_valid = nq;
-    sa.prio = h->scan_prio;
-    timing_mark(h, tslot, 0, st);
-    // small batches: as many waves per workgroup as there are 64-query column groups (1, 2, 4; 8 = the batch shape)
-    const int nw_small = h->small_batch_off ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
-    // layout "x16" with both scan copies resident: ONE launch holds both scans (scan_pair_x16_kernel, scan_x16.hpp) when every tuning
-    // option is at its default; otherwise (and on the 32-row layout) both are enqueued and the one not needed returns at once
-    bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && direct_rows == 0 &&
-                          !h->scan_pair_off && h->i8_ring == 0 && h->i8_nt == 0 && h->f16_stage_tiles == 0 && h->i8_variant == 3;
-    if (h->panels_streamed) {
-        // streamed panels (option "stream_panels"): chunks are scanned slab by slab -- convert the slab's float32 rows into a
-        // scratch slab (p16 panels), then launch the scan on those chunks with `panels` rebased to the slab.  Same bins, same
-        // results; one extra pass over the float32 rows per batch (0.65 ms per 786k x 768 rows, 5.5 TB/s).  Two slabs on two
-        // streams (the next slab's workgroups filling the tail of the current one) measured 171.6 ms against 178.0 ms for
-        // this single slab on a 12.5M x 768 shard, at 1.9 GB more: not kept.
-        const int64_t KS = h->ksteps / 2;
-        const int64_t chunk_rows = (int64_t)(g.spc + 1) * kSpanRows16;                  // (chunks are spc or spc + 1 spans)
-        const int64_t wgs_per_chunk = std::max<int64_t>(1, Qpad / 512);
-        // Slab size (option "stream_slab_rows", 0 = 1 280 000): the K-loop scan runs two 512-thread workgroups per CU and a
-        // workgroup of a 12.5M-row shard takes ~14.5 ms (chunks are ~50k rows: the select takes <= 1024 superbins), so a
-        // launch whose workgroup count PER XCD (chunk c runs on XCD c % 8) is not just below a multiple of 2 x 32 idles the
-        // chip for most of a round (measured, 10 000 queries = 20 workgroups per chunk: 16-chunk slabs 14.5 ms per launch,
-        // 25-chunk slabs -- four chunks on XCD 0 -- 23 ms).  Take the largest chunk count within `slab_rows` whose workgroups
-        // fill whole rounds; small query batches (few workgroups per chunk) go by rows alone.
-        static const int n_cus = [] { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev);
-                                      return hipGetDeviceProperties(&p, dev) == hipSuccess ? p.multiProcessorCount : 256; }();
-        const int64_t slab_rows = h->stream_slab_rows > 0 ? h->stream_slab_rows : 1280000;
-        int64_t slab_chunks = std::max<int64_t>(1, slab_rows / chunk_rows);
-        for (int r = 8; r >= 1; --r) {                       // (chunk c of a launch runs on XCD c % 8: count per XCD)
-            const int64_t fit = 8 * ((int64_t)2 * (n_cus / 8) * r / wgs_per_chunk);
-            if (fit >= 8 && fit <= slab_chunks) { slab_chunks = fit; break; }
-        }
-        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
-        h->scan.slab.reserve((size_t)slab_chunks * chunk_rows / kTileRows16 * KS * 64 * sizeof(half8));
-        for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
-            const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
-            const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
-            const int64_t tile_a = span_a * kTilesPerSpan16, ntiles = (span_b - span_a) * kTilesPerSpan16;
-            half8 *buf = h->scan.slab.as<half8>();
-            convert_slab16_kernel<<<dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st>>>(
-                h->rows.x32.as<float>(), h->N, Dm, D4, (int)KS, tile_a, ntiles, h->sx, buf);
-            ScanArgs ss = sa;
-            ss.panels = buf - (size_t)tile_a * KS * 64;
-            ss.chunk0 = (int)c0;
-            ss.nchunks = (int)(c1 - c0);
-            launch_scan(h, ss, (int)(c1 - c0), Qpad, st, direct_rows, nw_small);
-        }
-    } else if (h->int8_only) {
-        // int8-only index: there is no resident fp16 copy.  Which scan serves the batch is decided on the device, so the fp16 scan
-        // is enqueued all the same, slab by slab: convert_slab_from_i8_kernel turns the slab's int8 panels into fp16 panels (and
-        // returns at once, like the scan behind it, when the batch is integer -- the usual case), scan_kernel runs on those chunks
-        // with `panels` rebased.  The slab is small by default (option "int8_slab_chunks", 8 chunks = 16 MiB at D = 128): it is
-        // resident whether or not a non-integer batch ever comes.
-        const int64_t tiles_per_span = kTilesPerSpan;
-        const int64_t slab_chunks = std::max<int64_t>(1, std::min<int64_t>(h->int8_slab_chunks > 0 ? h->int8_slab_chunks : 8, g.nchunks));
-        const int64_t max_spans = (int64_t)(g.spc + 1) * slab_chunks;
-        if (h->scan.slab.cap < (size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8))
-            h->scan.slab.reserve_exact((size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8));
-        for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
-            const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
-            const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
-            const int64_t tile_a = span_a * tiles_per_span, ntiles = (span_b - span_a) * tiles_per_span;
-            half8 *buf = h->scan.slab.as<half8>();
-            const int64_t threads = ntiles * h->ksteps * 64;
-            convert_slab_from_i8_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-                h->scan.panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, info, buf, h->x16 ? 1 : 0);
-            ScanArgs ss = sa;
-            ss.panels = buf - (size_t)tile_a * h->ksteps * 64;
-            ss.chunk0 = (int)c0;
-            ss.nchunks = (int)(c1 - c0);
-            launch_scan(h, ss, (int)(c1 - c0), Qpad, st, direct_rows, nw_small);
-        }
-    } else if (pq) {
-        // PQ index: nothing but the codes is resident.  pq_panels_kernel turns the code rows of the slab's tiles into the fp16 panels
-        // a flat index over x^ would hold (same rounding, so the same bias, scales and error bound serve), the scan runs on those
-        // chunks with `panels` rebased.  Slab size: option "pq_slab_chunks", default the chunks of 524 288 rows (128 MiB at D = 128;
-        // 64 chunks measured 11 % faster than 32 and as fast as one slab, profiles/r07_bench_pq.json); it does not grow with N (chunks are <= 8192 rows below 8M rows).
-        const int64_t tiles_per_span = h->tile16 ? kTilesPerSpan16 : kTilesPerSpan;
-        const int64_t ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;
-        const int64_t chunk_rows = (int64_t)(g.spc + 1) * (h->tile16 ? kSpanRows16 : kSpanRows);
-        int64_t slab_chunks = h->pq_slab_chunks > 0 ? h->pq_slab_chunks : std::max<int64_t>(1, kPqSlabRows / chunk_rows);
-        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
-        // (default size: the slab is allocated for its full 524 288 rows whatever the corpus holds -- the workspace of a search does
-        //  not depend on N; vdb_stats counts it in bytes_workspace)
-        const int64_t max_spans = h->pq_slab_chunks > 0 ? (int64_t)(g.spc + 1) * slab_chunks
-                                                        : std::max<int64_t>(kPqSlabRows, chunk_rows) / (h->tile16 ? kSpanRows16 : kSpanRows);
-        const size_t slab_bytes = (size_t)max_spans * tiles_per_span * ksl * 64 * sizeof(half8);
-        if (h->scan.slab.cap < slab_bytes) h->scan.slab.reserve_exact(slab_bytes);
-        for (int64_t c0 = 0; c0 < g.nchunks; c0 += slab_chunks) {
-            const int64_t c1 = std::min<int64_t>(g.nchunks, c0 + slab_chunks);
-            const int64_t span_a = chunk_span0((int)c0, g.spc, g.rem), span_b = std::min<int64_t>(g.nspans, chunk_span0((int)c1, g.spc, g.rem));
-            const int64_t tile_a = span_a * tiles_per_span, ntiles = (span_b - span_a) * tiles_per_span;
-            if (span_b - span_a > max_spans) throw Error(VDB_ERR_STATE, "internal: a PQ slab exceeds its buffer");
-            half8 *buf = h->scan.slab.as<half8>();
-            launch_pq_panels(h, tile_a, ntiles, buf, st);
-            ScanArgs ss = sa;
-            ss.panels = buf - (size_t)tile_a * ksl * 64;
-            ss.chunk0 = (int)c0;
-            ss.nchunks = (int)(c1 - c0);
-            launch_scan(h, ss, (int)(c1 - c0), Qpad, st, direct_rows, nw_small);
-        }
-    } else if (!pair_candidate)
-    launch_scan(h, sa, g.nchunks, Qpad, st, direct_rows, nw_small);   // (fp16: returns at once when the int8 scan serves the batch)
-    if (use_i8) {
-        ScanI8Args s8{};
-        s8.panels = h->scan.panels8.as<int4v>();
-        s8.bias8 = h->scan.bias8.as<int32_t>();
-        s8.qpanels = ws.qpanels8.as<int4v>();
-        s8.info = info;
-        s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
-        s8.sb_m1 = sa.sb_m1; s8.sb_m2 = sa.sb_m2; s8.sb_span = sa.sb_span;
-        s8.nspans = g.nspans; s8.Npad = h->Npad; s8.Qpad = Qpad; s8.nq_valid = nq;
-        s8.prio = h->scan_prio;
-        s8.spans_per_chunk = g.spc; s8.chunk_rem = g.rem; s8.nchunks = g.nchunks;
-        // i8_variant (tuning, every variant exact; scripts/sweep_i8.py): 0 = 512-query tiles (2 column blocks per wave),
-        // 4-tile stages; 1 = 8-tile stages; 2 = 1024-query tiles (4 column blocks per wave); 3 = both (default);
-        // 4 / 5 = 16 waves per workgroup (4 per SIMD) with 8- / 16-tile stages.  Odd batch sizes keep 512-query tiles.
-        int v8 = h->i8_variant;
-        if (h->x16) {
-            // layout "x16" (scan_i8x16.hpp, v_mfma_i32_16x16x64_i8): the same launch shapes -- batch: 512- or 1024-query tiles
-            // (4 or 8 column blocks of 16 queries per wave), 4- or 8-tile stages (i8_variant bits as below, 4 / 5 -> 3);
-            // serving: 1 / 2 / 4 waves of 64 queries, 4-stage staging ring (option "i8_ring": 2, 4, 8), non-temporal loads
-            int v = h->i8_variant & 3;
-            if (h->i8_variant == 4 || h->i8_variant == 5) v = 3;
-            if (Qpad % 1024 != 0) v &= 1;
-            if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v &= 1;
-            const int qtile = nw_small < 8 ? 64 * nw_small : (v >= 2) ? 1024 : 512;
-            s8.nqtiles = (int)((nw_small < 8 ? nq + qtile - 1 : Qpad) / qtile);
-            const dim3 gridx(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-            const bool nt = h->i8_nt != 1;
-            const int ring = h->i8_ring == 0 ? 4 : h->i8_ring;
-#define VDB_X16B(KS2_) do { \
-                if (v == 3) scan_i8x16_kernel<KS2_, 8, 8><<<gridx, dim3(512), 0, st>>>(s8); \
-                else if (v == 2) scan_i8x16_kernel<KS2_, 4, 8><<<gridx, dim3(512), 0, st>>>(s8); \
-                else if (v == 1) scan_i8x16_kernel<KS2_, 8, 4><<<gridx, dim3(512), 0, st>>>(s8); \
-                else scan_i8x16_kernel<KS2_, 4, 4><<<gridx, dim3(512), 0, st>>>(s8); } while (0)
-#define VDB_X16S(KS2_, NW_) do { \
-                if (ring == 2) scan_i8x16_kernel<KS2_, 4, 4, NW_><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else if (ring == 8 && NW_ >= 2) scan_i8x16_kernel<KS2_, 4, 4, NW_, (NW_ >= 2 ? 8 : 4)><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else if (nt) scan_i8x16_kernel<KS2_, 4, 4, NW_, 4, 2><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-                else scan_i8x16_kernel<KS2_, 4, 4, NW_, 4><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
-#define VDB_X16(KS2_) do { \
-                if (nw_small == 1) VDB_X16S(KS2_, 1); else if (nw_small == 2) VDB_X16S(KS2_, 2); \
-                else if (nw_small == 4) VDB_X16S(KS2_, 4); else VDB_X16B(KS2_); } while (0)
-            if (pair_candidate && (nw_small < 8 || v == 3 || v == 1)) {
-                const bool small = nw_small < 8;
-                sa.nqtiles = small ? (int)((nq + nw_small * 64 - 1) / (nw_small * 64)) : (int)(Qpad / 512);
-                const unsigned grid16 = 8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-                const dim3 gridp(std::max(grid16, gridx.x));
-#define VDB_PAIR(W_) do { \
-                    if (nw_small == 1) scan_pair_x16_kernel<W_, 1, 4, 4, 4, 4, 2><<<gridp, dim3(64), 0, st>>>(sa, s8); \
-                    else if (nw_small == 2) scan_pair_x16_kernel<W_, 2, 4, 4, 4, 4, 2><<<gridp, dim3(128), 0, st>>>(sa, s8); \
-                    else if (nw_small == 4) scan_pair_x16_kernel<W_, 4, 4, 4, 4, 4, 2><<<gridp, dim3(256), 0, st>>>(sa, s8); \
-                    else if (v == 3) scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 8, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); \
-                    else scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 4, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); } while (0)
-                if (h->i8_ks == 4) VDB_PAIR(true);
-                else VDB_PAIR(false);
-#undef VDB_PAIR
-                VDB_HIP(hipGetLastError());
-            } else {
-            if (pair_candidate) {      // (a shape the paired kernel is not built for: the fp16 scan as its own launch, as ever)
-                pair_candidate = false;
-                launch_scan(h, sa, g.nchunks, Qpad, st, direct_rows, nw_small);
-            }
-            if (h->i8_ks == 2) VDB_X16(1);
-            else VDB_X16(2);
-#undef VDB_X16B
-#undef VDB_X16S
-#undef VDB_X16
-            VDB_HIP(hipGetLastError());
-            }
-        } else {
-        const int tb8 = v8 == 6 ? 1 : v8 == 7 ? 2 : 0;             // 6 / 7: variant 3 with a pacing barrier per 1 / 2 tiles
-        if (tb8) v8 = 3;
-        if (Qpad % 1024 != 0) v8 &= 1;
-        if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v8 &= 1;     // too few 1024-query tiles to cover the chip: 512-query tiles
-        if (nw_small < 8) v8 = 8 + nw_small;
-        const int qtile = (v8 > 8) ? 64 * nw_small : (v8 >= 2) ? 1024 : 512;
-        s8.nqtiles = (int)((v8 > 8 ? nq + qtile - 1 : Qpad) / qtile);
-        const dim3 grid8(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-#define VDB_I8G(KS_, ST_, CB_, NW_, G_) scan_i8_kernel<KS_, ST_, CB_, NW_, 16, false, G_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8)
-#define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
-        // serving shapes (1 / 2 / 4 waves per workgroup): the scan streams the copy once -- 4- or 8-stage staging ring
-        // (option "i8_ring": 0 = auto (4), 2 = the double buffer of the batch shape, 4, 8)
-#define VDB_I8R(KS_, NW_, R_) do { if (h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
-                                   else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
-        // (the wait for a stage is s_waitcnt vmcnt((ring - 2) x requests per wave and stage), a 6-bit counter: a one-wave
-        //  workgroup issues all 16 + 2 requests of a 4-tile stage itself, which caps its ring at 4)
-#define VDB_I8S(KS_, NW_) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
-                               if (r__ == 2) VDB_I8(KS_, 4, 2, NW_); else if (r__ == 8) VDB_I8R(KS_, NW_, (NW_ >= 2 ? 8 : 4)); \
-                               else if (nt8 && h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
-                               else VDB_I8R(KS_, NW_, 4); } while (0)
-        // serving shapes read every panel byte once per search: non-temporal staging loads (option "i8_nt": 0 / 2 on, 1 off).
-        // Measured in one process (scripts/sweep_serving_hbm.py): single-query scan of 4M x 128 (512 MB, HBM) 106.2 -> 96.7 us
-        // = 4.8 -> 5.3 TB/s; of 1M x 128 (128 MB, Infinity-Cache resident between searches) 33.9 -> 33.3 us
-        const bool nt8 = h->i8_nt != 1;
-        if (tb8 && v8 == 3 && h->i8_group == 8) {
-            if (h->i8_ks == 2) {
-                if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
-                else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
-            } else {
-                if (tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
-                else scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
-            }
-        } else if (h->i8_ks == 2) {
-            switch (v8) { case 1: VDB_I8(2, 8, 2, 8); break; case 2: VDB_I8(2, 4, 4, 8); break; case 3: VDB_I8(2, 8, 4, 8); break;
-                          case 4: VDB_I8(2, 8, 2, 16); break; case 5: VDB_I8(2, 16, 2, 16); break;
-                          case 9: VDB_I8S(2, 1); break; case 10: VDB_I8S(2, 2); break; case 12: VDB_I8S(2, 4); break;
-                          default: VDB_I8(2, 4, 2, 8); }
-        } else {
-            switch (v8) { case 1: VDB_I8(4, 8, 2, 8); break; case 2: VDB_I8(4, 4, 4, 8); break; case 3: VDB_I8(4, 8, 4, 8); break;
-                          case 4: VDB_I8(4, 8, 2, 16); break; case 5: VDB_I8(4, 16, 2, 16); break;
-                          case 9: VDB_I8S(4, 1); break; case 10: VDB_I8S(4, 2); break; case 12: VDB_I8S(4, 4); break;
-                          default: VDB_I8(4, 4, 2, 8); }
-        }
-#undef VDB_I8G
-#undef VDB_I8
-#undef VDB_I8R
-#undef VDB_I8S
-        VDB_HIP(hipGetLastError());
-        }
-    }
-    timing_mark(h, tslot, 1, st);
-
-    SelectArgs se{};
-    se.bin_m1 = sa.bin_m1;
-    se.bin_m2 = sa.bin_m2;
-    se.sb_m1 = sa.sb_m1;
-    se.sb_m2 = sa.sb_m2;
-    se.sb_span = sa.sb_span;
-    se.eps = ws.eps.as<float>();
-    se.info = info;
-    se.nq = nq;
-    se.Qpad = Qpad;
-    se.nspans = g.nspans;
-    se.N = h->N;
-    se.spans_per_chunk = g.spc;
-    se.chunk_rem = g.rem;
-    se.nchunks = g.nchunks;
-    se.k = k;
-    se.groups = G;
-    se.direct_rows = direct_rows;
-    if (direct_rows) {        // the level-1 bins are the superbins
-        se.sb_m1 = sa.bin_m1;
-        se.sb_m2 = sa.bin_m2;
-    }
-    se.cand_cap = cand_cap;
-    se.rescan_cap = rescan_cap;
-    se.f16_gmode = f16_octs(h, direct_rows) ? 4 : 0;
-    se.cand_rows = ws.cand.as<int32_t>();
-    se.rescan_rows = ws.rescan.as<int32_t>();
-    se.counts = ws.counts.as<int32_t>();
-    se.fallback = ws.fallback.as<int32_t>();
-    se.fb_list = ws.fb_list.as<int32_t>();
-    se.fb_count = fb_count;
-    se.stat_counters = stat_counters;
-    const int nsb_i = G * g.nchunks;
-    if (nsb_i > 128 && nsb_i <= 256 && h->select_variant == 2 && !direct_rows) {   // 32 lanes per query, 2 queries per wave
-        select_kernel_v2<8, 32><<<dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, st>>>(se);
-    } else if (nsb_i <= 256 && h->select_variant != 1 && !direct_rows) {  // multi-lane form: 16 lanes per query, 4 queries per wave
-        const unsigned sgrid = (unsigned)((nq + 15) / 16);
-        if (nsb_i <= 64)
-            select_kernel_v2<4, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
-        else if (nsb_i <= 128)
-            select_kernel_v2<8, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
-        else
-            select_kernel_v2<16, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
-    } else {
-        switch (g.vpl) {
-            case 1: launch_select<1>(se, st); break;
-            case 2: launch_select<2>(se, st); break;
-            case 4: launch_select<4>(se, st); break;
-            case 8: launch_select<8>(se, st); break;
-            case 16: launch_select<16>(se, st); break;
-            default: launch_select<32>(se, st); break;
-        }
-    }
-    VDB_HIP(hipGetLastError());
-
-    RefineListArgs la{};
-    la.c = rc;
-    la.nq = nq;
-    la.cand_rows = se.cand_rows;
-    la.rescan_rows = se.rescan_rows;
-    la.counts = se.counts;
-    la.fallback = se.fallback;
-    la.cand_cap = cand_cap;
-    la.rescan_cap = rescan_cap;
-    la.D = D;
-    la.I = I;
-    la.pkeys = pk;
-    la.pids = pi;
-    la.f16_shift = se.f16_gmode ? 3 : 2;
-    // ... and the queries whose work list overflowed (or whose scales were unusable): exhaustive exact pass, split and merged
-    // on the device, in the same launch (refine.hpp, refine_tail_kernel)
-    {
-        RefineFallbackArgs fa{};
-        fa.c = rc;
-        fa.fb_list = se.fb_list;
-        fa.fb_count = fb_count;
-        fa.max_split = (int)std::min<int64_t>(64, std::max<int64_t>(1, h->N / 4096));
-        fa.cap_units = std::max<int64_t>(nq, 4096);
-        ws.pkeys.reserve((size_t)fa.cap_units * k * sizeof(double));
-        ws.pids.reserve((size_t)fa.cap_units * k * sizeof(int64_t));
-        const size_t done_cap = ws.fb_done.cap;
-        ws.fb_done.reserve((size_t)nq * sizeof(int32_t));
-        if (ws.fb_done.cap != done_cap) VDB_HIP(hipMemsetAsync(ws.fb_done.p, 0, ws.fb_done.cap, st));   // (zero between searches)
-        fa.pkeys = ws.pkeys.as<double>();
-        fa.pids = ws.pids.as<int64_t>();
-        fa.done = ws.fb_done.as<int32_t>();
-        fa.D = D;
-        fa.I = I;
-        fa.okeys = pk;
-        fa.oids = pi;
-        const int kpl = kpl_for(k);
-        DISPATCH_KPL(kpl, (refine_tail_kernel<KPL><<<dim3(256 + (unsigned)((nq + 3) / 4)), dim3(256), 0, st>>>(la, fa, 256u)));
-        VDB_HIP(hipGetLastError());
-    }
-    timing_mark(h, tslot, 2, st);
-    h->last.last_path = VDB_PATH_MFMA_SCAN;
+    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, direct_rows, fb_count, stat_counters, tslot, clear_in_prep};
+    if (use_dense) search_dense(b);
+    else if (!use_scan) search_exact(b);
+    else search_scan(b);
 }
 
 // ---- hipGraph replay of a repeated device-resident search -----------------------------------------------------------

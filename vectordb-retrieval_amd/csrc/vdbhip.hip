@@ -237,6 +237,7 @@ struct vdb_index_s {
     vdb_multi_s *multi = nullptr;            // non-null: a multi-device handle (vdb_create_multi); device = the primary device,
                                              // N / id_base / built / ivf_built / nlist / nprobe describe the whole index
     int device = 0;
+    int n_cus = 256;                         // compute units of `device` (vdb_create; a coarse quantizer takes its parent's)
     int dim = 0, D4 = 0, ksteps = 0, metric = 0;
     int64_t N = 0, Npad = 0, id_base = 0;
     bool built = false;
@@ -355,7 +356,6 @@ struct vdb_index_s {
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
     int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
     std::vector<float> pq_cb_host;           // host copy of the codebooks [M][256][dsub]
-    int pq_n_cus = 0;                        // compute units of the handle's device (grid of the panel pass; 0 = not asked yet)
     int64_t pq_slab_chunks = 0;              // option "pq_slab_chunks": scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int64_t pq_scan_min_batch = 0;           // option "pq_scan_min_batch": smallest batch the panel pass + MFMA scan serves (0 = default)
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
@@ -422,6 +422,18 @@ inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
+// Where the rows of a flat handle live, for the exact kernels: float32 rows, or (int8-only) int8 rows + their byte window, or
+// (PQ) product codes that refine.hpp's pq_key looks x^ up from.  q: the batch's queries padded to D4.
+inline RefineCommon flat_rows(const vdb_index_s *h, const float *q, int k) {
+    RefineCommon c{(h->int8_only || pq_on(h)) ? nullptr : h->rows.x32.as<float>(), q, h->N, h->id_base, h->D4, h->metric, k, nullptr};
+    if (pq_on(h)) c.pq = pq_rows(h);
+    if (h->int8_only) {
+        c.X8 = h->scan.rows8.as<signed char>();
+        c.x8_pitch = h->rows8_pitch;
+        c.cx = h->i8_cx;
+    }
+    return c;
+}
 inline void pq_refuse_ivf(const vdb_index_s *h) {       // an IVF entry point on a PQ handle
     if (!h->multi && pq_on(h))
         throw Error(VDB_ERR_UNSUPPORTED, "this handle is a flat PQ index (vdb_pq_*): IVF<nlist>,PQ<M> is not implemented");
@@ -652,10 +664,10 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
     h->built = true;
 }
 
-// rows [row0, row0 + n) of h->rows.x32 from host or device memory (h->rows.x32 already holds room for them)
-void ingest_rows(vdb_index_s *h, int64_t row0, const float *x_dev_or_host, bool on_device, int64_t n, hipStream_t st) {
+// n rows from host or device memory to dst (device, D4 floats apart): rows [row0, row0 + n) of h->rows.x32, which already holds
+// room for them, or a block of the int8-only build
+void ingest_rows(vdb_index_s *h, float *dst, const float *x_dev_or_host, bool on_device, int64_t n, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
-    float *dst = h->rows.x32.as<float>() + (size_t)row0 * D4;
     if (D4 != D) VDB_HIP(hipMemsetAsync(dst, 0, (size_t)n * D4 * sizeof(float), st));
     if (on_device)
         VDB_HIP(hipMemcpy2DAsync(dst, (size_t)D4 * 4, x_dev_or_host, (size_t)D * 4, (size_t)D * 4, (size_t)n,
@@ -703,14 +715,8 @@ bool build_int8_only(vdb_index_s *h, const float *x, bool on_device, int64_t n, 
             if (direct) {
                 blk = x + (size_t)r0 * D;
             } else {
-                float *dst = tmp.as<float>();
-                if (D4 != D) VDB_HIP(hipMemsetAsync(dst, 0, (size_t)nb * D4 * sizeof(float), st));
-                if (on_device)
-                    VDB_HIP(hipMemcpy2DAsync(dst, (size_t)D4 * 4, x + (size_t)r0 * D, (size_t)D * 4, (size_t)D * 4, (size_t)nb,
-                                             hipMemcpyDeviceToDevice, st));
-                else
-                    upload_rows(h, dst, D4, x + (size_t)r0 * D, nb, D, st);
-                blk = dst;
+                ingest_rows(h, tmp.as<float>(), x + (size_t)r0 * D, on_device, nb, st);
+                blk = tmp.as<float>();
             }
             corpus_stats_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st>>>(blk, nb, D4, h->rows.xnorm2.as<float>() + r0,
                                                                                         h->kept.stats.as<IndexStats>());
@@ -795,7 +801,7 @@ void build_index(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
     try {
         if (n > 0) {
             h->rows.x32.reserve((size_t)n * h->D4 * sizeof(float));
-            ingest_rows(h, 0, x_dev_or_host, on_device, n, st);
+            ingest_rows(h, h->rows.x32.as<float>(), x_dev_or_host, on_device, n, st);
         }
         build_derived(h, st);
     } catch (...) {                    // a failed build leaves an EMPTY index (the next add starts over; a search says "not built")
@@ -836,7 +842,7 @@ void append_rows(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
     h->built = false;
     try {
         h->rows.x32.grow((size_t)(N0 + n) * h->D4 * sizeof(float), (size_t)N0 * h->D4 * sizeof(float));
-        ingest_rows(h, N0, x_dev_or_host, on_device, n, st);
+        ingest_rows(h, h->rows.x32.as<float>() + (size_t)N0 * h->D4, x_dev_or_host, on_device, n, st);
     } catch (...) {
         (void)hipGetLastError();
         h->N = N0;
@@ -914,6 +920,55 @@ void multi_for_each_shard(vdb_index_s *m, const std::function<void(vdb_index_s *
     throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a multi-device index (vdb_create_multi)");
 }
 
+// ns of the rows 0 .. n-1 (ns <= n) without replacement, in draw order, as the first ns entries of the result: seeded partial
+// Fisher-Yates (the training samples of vdb_ivf_train and vdb_pq_train)
+std::vector<int64_t> sample_rows(int64_t n, int64_t ns, uint64_t seed) {
+    std::vector<int64_t> pick((size_t)n);
+    std::iota(pick.begin(), pick.end(), (int64_t)0);
+    std::mt19937_64 rng(seed);
+    for (int64_t i = 0; i < std::min<int64_t>(ns, n - 1); ++i) {
+        const int64_t j = i + (int64_t)(rng() % (uint64_t)(n - i));
+        std::swap(pick[(size_t)i], pick[(size_t)j]);
+    }
+    return pick;
+}
+
+// vdb_add (host rows, null stream) and vdb_add_device (device rows, the caller's stream)
+void add_rows(vdb_index_s *h, const float *x, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
+    if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
+    if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
+    if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
+    if (pq_on(h)) pq_rows_are_codes();
+    set_device(h->device);
+    const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
+    append_rows(h, x, on_device, n, id_base, st);
+    lsh_encode_rows(h, n0, st);
+}
+
+// vdb_merge_partials_device (keys and ids in two arrays, parts nq * k apart) and vdb_merge_packed_partials_device (one array of
+// [keys | ids] blocks per part): `stride` = elements between the parts
+void merge_partials(int metric, int device, const double *keys_dev, const int64_t *ids_dev, int64_t stride, int nparts, int64_t nq,
+                    int k, float *D_dev, int64_t *I_dev, hipStream_t st) {
+    if (metric != VDB_METRIC_L2 && metric != VDB_METRIC_IP) throw Error(VDB_ERR_INVALID, "unknown metric");
+    if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
+    if (nparts < 0 || nq < 0) throw Error(VDB_ERR_INVALID, "negative size");
+    if (nq == 0) return;
+    if (!D_dev || !I_dev || (nparts > 0 && (!keys_dev || !ids_dev))) throw Error(VDB_ERR_INVALID, "null pointer");
+    set_device(device);
+    MergeArgs ma{};
+    ma.pkeys = keys_dev;
+    ma.pids = ids_dev;
+    ma.part_stride = stride;
+    ma.slot_stride = k;
+    ma.nparts = nparts;
+    ma.k = k;
+    ma.metric = metric;
+    ma.count = nq;
+    ma.D = D_dev;
+    ma.I = I_dev;
+    launch_merge(ma, nq, st);
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -949,6 +1004,7 @@ int vdb_create(int dim, int metric, int device, vdb_handle *out) {
                                                  prop.gcnArchName);
         auto *h = new vdb_index_s();
         h->device = device;
+        h->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         h->dim = dim;
         h->D4 = (dim + 3) / 4 * 4;
         h->ksteps = dim <= 64 ? 4 : (dim <= 128 ? 8 : (dim + 63) / 64 * 4);  // D > 128: K-loop kernel, 64-dim steps
@@ -974,17 +1030,7 @@ int vdb_destroy(vdb_handle h) {
 }
 
 int vdb_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
-    return guarded([&] {
-        auto *h = check(hh);
-        if (n > 0 && !x_host) throw Error(VDB_ERR_INVALID, "null corpus pointer");
-        if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, false, nullptr);
-        if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
-        if (pq_on(h)) pq_rows_are_codes();
-        set_device(h->device);
-        const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
-        append_rows(h, x_host, false, n, id_base, nullptr);
-        lsh_encode_rows(h, n0, nullptr);
-    });
+    return guarded([&] { add_rows(check(hh), x_host, false, n, id_base, nullptr); });
 }
 
 int vdb_reset(vdb_handle hh) {
@@ -1012,17 +1058,7 @@ int vdb_reset(vdb_handle hh) {
 }
 
 int vdb_add_device(vdb_handle hh, const float *x_dev, int64_t n, int64_t id_base, void *stream) {
-    return guarded([&] {
-        auto *h = check(hh);
-        if (n > 0 && !x_dev) throw Error(VDB_ERR_INVALID, "null corpus pointer");
-        if (h->multi) return multi_add(h, x_dev, true, n, id_base, as_stream(stream), false, nullptr);
-        if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
-        if (pq_on(h)) pq_rows_are_codes();
-        set_device(h->device);
-        const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
-        append_rows(h, x_dev, true, n, id_base, as_stream(stream));
-        lsh_encode_rows(h, n0, as_stream(stream));
-    });
+    return guarded([&] { add_rows(check(hh), x_dev, true, n, id_base, as_stream(stream)); });
 }
 
 int vdb_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float *D, int64_t *I) {
@@ -1071,49 +1107,15 @@ int vdb_search_partial_device(vdb_handle hh, const float *q_dev, int64_t nq, int
 
 int vdb_merge_partials_device(int metric, int device, const double *keys_dev, const int64_t *ids_dev, int nparts,
                               int64_t nq, int k, float *D_dev, int64_t *I_dev, void *stream) {
-    return guarded([&] {
-        if (metric != VDB_METRIC_L2 && metric != VDB_METRIC_IP) throw Error(VDB_ERR_INVALID, "unknown metric");
-        if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
-        if (nparts < 0 || nq < 0) throw Error(VDB_ERR_INVALID, "negative size");
-        if (nq == 0) return;
-        if (!D_dev || !I_dev || (nparts > 0 && (!keys_dev || !ids_dev))) throw Error(VDB_ERR_INVALID, "null pointer");
-        set_device(device);
-        MergeArgs ma{};
-        ma.pkeys = keys_dev;
-        ma.pids = ids_dev;
-        ma.part_stride = nq * k;
-        ma.slot_stride = k;
-        ma.nparts = nparts;
-        ma.k = k;
-        ma.metric = metric;
-        ma.count = nq;
-        ma.D = D_dev;
-        ma.I = I_dev;
-        launch_merge(ma, nq, as_stream(stream));
-    });
+    return guarded([&] { merge_partials(metric, device, keys_dev, ids_dev, nq * k, nparts, nq, k, D_dev, I_dev, as_stream(stream)); });
 }
 
 int vdb_merge_packed_partials_device(int metric, int device, const void *packed_dev, int nparts, int64_t nq, int k,
                                      float *D_dev, int64_t *I_dev, void *stream) {
     return guarded([&] {
-        if (metric != VDB_METRIC_L2 && metric != VDB_METRIC_IP) throw Error(VDB_ERR_INVALID, "unknown metric");
-        if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
-        if (nparts < 0 || nq < 0) throw Error(VDB_ERR_INVALID, "negative size");
-        if (nq == 0) return;
-        if (!D_dev || !I_dev || (nparts > 0 && !packed_dev)) throw Error(VDB_ERR_INVALID, "null pointer");
-        set_device(device);
-        MergeArgs ma{};
-        ma.pkeys = reinterpret_cast<const double *>(packed_dev);
-        ma.pids = reinterpret_cast<const int64_t *>(packed_dev) + nq * k;
-        ma.part_stride = 2 * nq * k;
-        ma.slot_stride = k;
-        ma.nparts = nparts;
-        ma.k = k;
-        ma.metric = metric;
-        ma.count = nq;
-        ma.D = D_dev;
-        ma.I = I_dev;
-        launch_merge(ma, nq, as_stream(stream));
+        const double *keys = reinterpret_cast<const double *>(packed_dev);
+        const int64_t *ids = packed_dev ? reinterpret_cast<const int64_t *>(packed_dev) + nq * k : nullptr;
+        merge_partials(metric, device, keys, ids, 2 * nq * k, nparts, nq, k, D_dev, I_dev, as_stream(stream));
     });
 }
 
@@ -1135,13 +1137,7 @@ void rerank_device_impl(vdb_index_s *h, const float *dq, int64_t nq, const int64
         qpad = h->ws.qpad.as<float>();
     }
     RerankArgs a{};
-    a.c = RefineCommon{(h->int8_only || pq_on(h)) ? nullptr : h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, nullptr};
-    if (pq_on(h)) a.c.pq = pq_rows(h);     // (PQ: no float32 rows -- x^ is looked up from the codes)
-    if (h->int8_only) {
-        a.c.X8 = h->scan.rows8.as<signed char>();
-        a.c.x8_pitch = h->rows8_pitch;
-        a.c.cx = h->i8_cx;
-    }
+    a.c = flat_rows(h, qpad, k);
     a.nq = nq;
     a.cand = cand;
     a.ncand = ncand;
