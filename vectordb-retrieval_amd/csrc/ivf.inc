@@ -99,6 +99,67 @@ void ivf_csr_build(vdb_index_s *h, const DevBuf &dI, int64_t n, int nlist, DevBu
     VDB_HIP(hipMemcpy(doff.p, offsets_host.data(), ((size_t)nlist + 1) * 8, hipMemcpyHostToDevice));
 }
 
+// ---- the bookkeeping of vdb_ivf_add(_assigned) that both codecs share (ivf_add_impl: float32 rows; sq8_add: codes) ----
+// APPEND to a built, non-empty index (same id base), else build anew: N0 rows stay, N1 rows after the add; false = empty append
+bool ivf_add_range(const vdb_index_s *h, int64_t n, int64_t id_base, int64_t &N0, int64_t &N1) {
+    const bool append = h->ivf_built && h->N > 0;
+    if (append) require_same_id_base(h, id_base);
+    if (append && n == 0) return false;
+    N0 = append ? h->N : 0;
+    N1 = N0 + n;
+    ivf_require(N1 <= 2147483647ll - 1024, VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
+    return true;
+}
+
+// The lists are rebuilt from (stored rows in list order ++ new rows) with a stable sort by list, so inside a list the rows stay
+// in insertion order and the index is the one a single add of the concatenated corpus builds.  dperm = source row of every
+// list-order row; src_ids (N0 > 0 only) = ids of the source rows; the offsets land in h->ivf_offsets_host
+void ivf_add_lists(vdb_index_s *h, const std::vector<int64_t> &assign_new, int64_t N0, DevBuf &src_ids, DevBuf &dperm, DevBuf &doff) {
+    const int64_t n = (int64_t)assign_new.size(), N1 = N0 + n;
+    // list of every source row: the stored rows are in list order (offsets), the new ones follow
+    std::vector<int64_t> assign_all((size_t)N1);
+    if (N0)
+        for (int l = 0; l < h->nlist; ++l)
+            std::fill(assign_all.begin() + h->ivf_offsets_host[(size_t)l], assign_all.begin() + h->ivf_offsets_host[(size_t)l + 1], (int64_t)l);
+    std::copy(assign_new.begin(), assign_new.end(), assign_all.begin() + N0);
+    DevBuf dassign;
+    dassign.reserve((size_t)N1 * 8);
+    VDB_HIP(hipMemcpy(dassign.p, assign_all.data(), (size_t)N1 * 8, hipMemcpyHostToDevice));
+    if (N0) {           // ids of the source rows: the stored ones keep theirs (an append has n > 0)
+        std::vector<int64_t> ids_new((size_t)n);
+        for (int64_t i = 0; i < n; ++i) ids_new[(size_t)i] = h->id_base + N0 + i;
+        src_ids.reserve((size_t)N1 * 8);
+        VDB_HIP(hipMemcpy(src_ids.p, h->lists.ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
+        VDB_HIP(hipMemcpy(src_ids.as<int64_t>() + N0, ids_new.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    ivf_csr_build(h, dassign, N1, h->nlist, dperm, doff, h->ivf_offsets_host);
+}
+
+// the list of each of n new rows on the device (`fresh`, row stride D4): the nearest centroid, read from an unpadded copy;
+// left on the device in dnew and copied to assign_new
+void ivf_add_assign(vdb_index_s *h, const float *fresh, int64_t n, DevBuf &dnew, std::vector<int64_t> &assign_new) {
+    const int Dm = h->dim, D4 = h->D4;
+    DevBuf raw;
+    if (D4 != Dm) {
+        raw.reserve((size_t)n * Dm * 4);
+        VDB_HIP(hipMemcpy2D(raw.p, (size_t)Dm * 4, fresh, (size_t)D4 * 4, (size_t)Dm * 4, (size_t)n, hipMemcpyDeviceToDevice));
+    }
+    ivf_assign_rows(h, D4 != Dm ? raw.as<float>() : fresh, n, dnew);
+    VDB_HIP(hipMemcpy(assign_new.data(), dnew.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+}
+
+// once the rows are in list order: the counts, the offsets on the device, the list of every row in insertion order
+void ivf_add_finish(vdb_index_s *h, const std::vector<int64_t> &assign_new, int64_t N0, int64_t id_base) {
+    const int64_t n = (int64_t)assign_new.size();
+    if (N0 + n == 0) h->ivf_offsets_host.assign((size_t)h->nlist + 1, 0);      // (no rows, no CSR build)
+    h->N = N0 + n;
+    h->id_base = id_base;
+    h->lists.ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
+    VDB_HIP(hipMemcpy(h->lists.ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8, hipMemcpyHostToDevice));
+    h->ivf_list_of_row.resize((size_t)h->N);            // (the stored part stays)
+    for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
+}
+
 #include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
 
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
@@ -253,334 +314,362 @@ IvfGeom ivf_geometry(const vdb_index_s *h, int64_t nb, int k, int nprobe) {
     return g;
 }
 
-// one batch through the list-major MFMA path.  probes = coarse result (nb x nprobe list ids) already on the device;
-// cnt = the zeroed counter block of this batch (ivf_zero).
-// (D, I) = final rows, or D == nullptr and (pk, pi) = per-shard partial rows (float64 order keys + ids)
-void ivf_mfma_batch(vdb_index_s *h, const IvfGeom &geom, int32_t *d_cnt, const float *q, const float *qpad, int64_t nb, int k,
-                    int nprobe, float *D, int64_t *I, double *pk, int64_t *pi, long tslot, hipStream_t st) {
-    const int nlist = h->nlist;
-    const bool kloop = geom.kloop;
-    const int bt = geom.bt, bps = geom.bps, bins_per_span = geom.bins_per_span, bin_rows = geom.bin_rows, nw = geom.nw, group = geom.group;
-    const int run_groups = geom.run_groups;
-    // rows per candidate group of the K-loop scan (option "ivf_group": 0 auto, 1, 2, 4): 64-row bins can name single rows
-    const int kgroup = (kloop && h->ivf_tps == 16) ? (h->ivf_group > 0 ? h->ivf_group : kIvfKloopGroupRows) : 4;
-    const int64_t pairs = geom.pairs, max_items = geom.max_items, max_slots = geom.max_slots, max_bins = geom.max_bins;
-    const size_t bin_bytes = geom.bin_bytes;
-    (void)bps;
+// one batch of an IVF search, as ivf_search_device_impl hands it to its path.  The coarse result (nb x nprobe list ids) is
+// already on the device (plan.ivf_probe_i).  (D, I) = final rows, or D == nullptr and (pk, pi) = per-shard partial rows
+// (float64 order keys + ids): all four at this batch's offset
+struct IvfBatch {
+    vdb_index_s *h;
+    const float *q, *qpad;
+    int64_t nb;
+    int k, nprobe;
+    float *D; int64_t *I; double *pk; int64_t *pi;
+    long tslot;
+    hipStream_t st;
+    IvfGeom g;              // list-major path only: the geometry, and the zeroed counter block of this batch (ivf_zero)
+    int32_t *d_cnt;
+};
+
+// what the steps of ivf_search_lists share: capacities, the plan's launch shape, views into the counter block and the plan
+struct IvfLists {
+    bool use_i8, small_ppb;
+    int kgroup, cand_cap, rescan_cap, ppb;
+    unsigned pblocks;
+    size_t hist_bytes;
+    int32_t *d_cursor, *d_slot_query, *d_fb_done;
+    const int64_t *probes;
+    IvfPlan *plan;
+    QueryBatchInfo *info;
+};
+
+IvfLists ivf_lists_reserve(const IvfBatch &b) {
+    vdb_index_s *h = b.h;
     Workspace &ws = h->ws;
-    const int Dm = h->dim;
+    const int nlist = h->nlist, k = b.k;
+    const int64_t nb = b.nb;
+    IvfLists L{};
+    // rows per candidate group of the K-loop scan (option "ivf_group": 0 auto, 1, 2, 4): 64-row bins can name single rows
+    L.kgroup = (b.g.kloop && h->ivf_tps == 16) ? (h->ivf_group > 0 ? h->ivf_group : kIvfKloopGroupRows) : 4;
     // (five minima per bin: a dense bin hands over up to four candidate quads instead of one re-scan)
-    const int cand_cap = h->list_cap > 0 ? h->list_cap : (kloop ? std::max(96, 4 * k + 32) : std::max(64, 2 * k + 32));
-    const int rescan_cap = std::max(16, k / 2 + 8);
+    L.cand_cap = h->list_cap > 0 ? h->list_cap : (b.g.kloop ? std::max(96, 4 * k + 32) : std::max(64, 2 * k + 32));
+    L.rescan_cap = std::max(16, k / 2 + 8);
     ws.eps.reserve((size_t)nb * sizeof(float));
     ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
-    const bool use_i8 = h->i8_ok && !h->i8_disable && h->scan.panels8.p != nullptr;
-    if (use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);          // int8 query rows
-    ws.bin_m1.reserve(bin_bytes);
-    ws.bin_m2.reserve(bin_bytes);
-    ws.bin_m3.reserve(bin_bytes);
-    if (kloop) {
-        ws.bin_m4.reserve(bin_bytes);
-        ws.bin_m5.reserve(bin_bytes);
+    L.use_i8 = h->i8_ok && !h->i8_disable && h->scan.panels8.p != nullptr;
+    if (L.use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);        // int8 query rows
+    ws.bin_m1.reserve(b.g.bin_bytes);
+    ws.bin_m2.reserve(b.g.bin_bytes);
+    ws.bin_m3.reserve(b.g.bin_bytes);
+    if (b.g.kloop) {
+        ws.bin_m4.reserve(b.g.bin_bytes);
+        ws.bin_m5.reserve(b.g.bin_bytes);
     }
-    ws.cand.reserve((size_t)nb * cand_cap * sizeof(int32_t));
-    ws.rescan.reserve((size_t)nb * rescan_cap * 2 * sizeof(int32_t));
+    ws.cand.reserve((size_t)nb * L.cand_cap * sizeof(int32_t));
+    ws.rescan.reserve((size_t)nb * L.rescan_cap * 2 * sizeof(int32_t));
     ws.counts.reserve((size_t)nb * 2 * sizeof(int32_t));
     ws.fallback.reserve((size_t)nb * sizeof(int32_t));
-    int32_t *d_cursor = d_cnt + nlist, *d_slot_query = d_cursor + nlist;
-    int32_t *d_fb_done = d_slot_query + max_slots;
+    L.d_cursor = b.d_cnt + nlist;
+    L.d_slot_query = L.d_cursor + nlist;
+    L.d_fb_done = L.d_slot_query + b.g.max_slots;
     ws.fb_list.reserve((size_t)nb * sizeof(int32_t));
     h->plan.ivf_slot_off.reserve(((size_t)nlist + 1) * 4);
     h->plan.ivf_list_item0.reserve(((size_t)nlist + 1) * 4);
-    h->plan.ivf_item_list.reserve((size_t)max_items * 4);
-    h->plan.ivf_item_slot0.reserve((size_t)max_items * 4);
-    h->plan.ivf_item_bin0.reserve((size_t)max_items * 4);
+    h->plan.ivf_item_list.reserve((size_t)b.g.max_items * 4);
+    h->plan.ivf_item_slot0.reserve((size_t)b.g.max_items * 4);
+    h->plan.ivf_item_bin0.reserve((size_t)b.g.max_items * 4);
     h->plan.ivf_plan.reserve(sizeof(IvfPlan));
-    h->plan.ivf_slot_of.reserve((size_t)pairs * 4);
+    h->plan.ivf_slot_of.reserve((size_t)b.g.pairs * 4);
+    L.probes = h->plan.ivf_probe_i.as<int64_t>();
+    L.plan = h->plan.ivf_plan.as<IvfPlan>();
+    L.small_ppb = b.g.pairs < 256 * (int64_t)kIvfPairsPerBlock && nlist <= 2048;   // (fewer than 256 workgroups otherwise)
+    L.ppb = L.small_ppb ? kIvfPairsPerBlock / 4 : kIvfPairsPerBlock;
+    L.pblocks = (unsigned)((b.g.pairs + L.ppb - 1) / L.ppb);
+    L.hist_bytes = nlist <= kIvfLdsLists ? (size_t)nlist * 4 : 0;
+    L.info = batch_info(ws);      // (cleared by the dispatcher with the rest of ivf_zero)
+    return L;
+}
 
-    const int64_t *probes = h->plan.ivf_probe_i.as<int64_t>();
-    IvfPlan *plan = h->plan.ivf_plan.as<IvfPlan>();
-    const bool small_ppb = pairs < 256 * (int64_t)kIvfPairsPerBlock && nlist <= 2048;   // (fewer than 256 workgroups otherwise)
-    const int ppb = small_ppb ? kIvfPairsPerBlock / 4 : kIvfPairsPerBlock;
-    const unsigned pblocks = (unsigned)((pairs + ppb - 1) / ppb);
-    const size_t hist_bytes = nlist <= kIvfLdsLists ? (size_t)nlist * 4 : 0;
-    QueryBatchInfo *info = batch_info(ws);      // (cleared by the caller with the rest of ivf_zero)
-    unsigned long long *stat_counters = reinterpret_cast<unsigned long long *>(ws.small.as<char>() + 64);
-    {
-        const int64_t total = nb * Dm;
-        const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                               use_i8 ? (1 | (h->ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see below)
-        const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
-        if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(q, total, info, fin);
-        // scales (from the coarse statistics) + error bounds + query rows of either form: one dispatch
-        IvfPrepArgs pa{};
-        pa.eps = EpsArgs{q, nb, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
-                         h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
-        pa.Q = q; pa.nq = nb; pa.D = Dm; pa.Dpad = h->ksteps * 16;      // (= i8_ks * 32: both query-row forms have the same pitch)
-        pa.qrows = reinterpret_cast<_Float16 *>(ws.qpanels.p);
-        pa.q8 = use_i8 ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
-        pa.info = info;
-        pa.src = from_coarse ? batch_info(h->coarse->ws) : nullptr;
-        pa.fin = fin;
-        pa.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
-        pa.n_row_blocks = (unsigned)((nb * pa.Dpad / 8 + 255) / 256);     // (8 dims per thread)
-        pa.probes = probes;
-        pa.npairs = pairs;
-        pa.nlist = nlist;
-        pa.ppb = ppb;
-        pa.cnt = d_cnt;
-        ivf_prep_kernel<<<dim3(pa.n_eps_blocks + pa.n_row_blocks + pblocks), dim3(256), hist_bytes, st>>>(pa);
-    }
-    if (hist_bytes) {      // plan + scatter in one dispatch (every workgroup recomputes the slot prefix in LDS)
-        if (small_ppb)
-            ivf_plan_scatter_kernel<kIvfPairsPerBlock / 4><<<dim3(pblocks), dim3(256), 2 * hist_bytes, st>>>(
-                probes, nb, nprobe, nlist, d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
-                (int)max_items, (int)max_slots, (int)max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
-                h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
-                h->plan.ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
-        else
-            ivf_plan_scatter_kernel<kIvfPairsPerBlock><<<dim3(pblocks), dim3(256), 2 * hist_bytes, st>>>(
-                probes, nb, nprobe, nlist, d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), group, bins_per_span, run_groups,
-                (int)max_items, (int)max_slots, (int)max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
-                h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
-                h->plan.ivf_item_bin0.as<int32_t>(), plan, d_cursor, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
+// query statistics (unless the coarse search of this batch took them), then scales + error bounds + query rows of either
+// form + the per-list pair counts: one dispatch
+void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = h->ws;
+    const int Dm = h->dim;
+    const int64_t nb = b.nb, total = nb * Dm;
+    const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
+                           L.use_i8 ? (1 | (h->ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see ivf_scan_i8)
+    const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
+    if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, b.st>>>(b.q, total, L.info, fin);
+    IvfPrepArgs pa{};
+    pa.eps = EpsArgs{b.q, nb, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
+                     h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, L.info, ws.eps.as<float>()};
+    pa.Q = b.q; pa.nq = nb; pa.D = Dm; pa.Dpad = h->ksteps * 16;      // (= i8_ks * 32: both query-row forms have the same pitch)
+    pa.qrows = reinterpret_cast<_Float16 *>(ws.qpanels.p);
+    pa.q8 = L.use_i8 ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
+    pa.info = L.info; pa.src = from_coarse ? batch_info(h->coarse->ws) : nullptr; pa.fin = fin;
+    pa.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
+    pa.n_row_blocks = (unsigned)((nb * pa.Dpad / 8 + 255) / 256);     // (8 dims per thread)
+    pa.probes = L.probes; pa.npairs = b.g.pairs; pa.nlist = h->nlist; pa.ppb = L.ppb; pa.cnt = b.d_cnt;
+    ivf_prep_kernel<<<dim3(pa.n_eps_blocks + pa.n_row_blocks + L.pblocks), dim3(256), L.hist_bytes, b.st>>>(pa);
+}
+
+// work items of every probed list and the slot of every (query, probe) pair.  nlist <= kIvfLdsLists: plan + scatter in one
+// dispatch (every workgroup recomputes the slot prefix in LDS), else a kernel each
+void ivf_lists_plan(const IvfBatch &b, const IvfLists &L) {
+    vdb_index_s *h = b.h;
+    const int nlist = h->nlist;
+    const auto plan_scatter = L.small_ppb ? ivf_plan_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_plan_scatter_kernel<kIvfPairsPerBlock>;
+    const auto scatter = L.small_ppb ? ivf_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_scatter_kernel<kIvfPairsPerBlock>;
+    if (L.hist_bytes) {
+        plan_scatter<<<dim3(L.pblocks), dim3(256), 2 * L.hist_bytes, b.st>>>(
+            L.probes, b.nb, b.nprobe, nlist, b.d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), b.g.group, b.g.bins_per_span, b.g.run_groups,
+            (int)b.g.max_items, (int)b.g.max_slots, (int)b.g.max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
+            h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
+            h->plan.ivf_item_bin0.as<int32_t>(), L.plan, L.d_cursor, L.d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     } else {
-    ivf_plan_kernel<<<dim3(1), dim3(1024), 0, st>>>(d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), nlist,
-                                                 group, bins_per_span, run_groups, (int)max_items, (int)max_slots, (int)max_bins,
-                                                 h->plan.ivf_slot_off.as<int32_t>(), h->plan.ivf_list_item0.as<int32_t>(),
-                                                 h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
-                                                 h->plan.ivf_item_bin0.as<int32_t>(), plan, h->lists.ivf_offsets.as<int64_t>());
-    if (small_ppb)
-        ivf_scatter_kernel<kIvfPairsPerBlock / 4><<<dim3(pblocks), dim3(256), hist_bytes, st>>>(
-            probes, nb, nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(),
-            d_cursor, plan, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
-    else
-        ivf_scatter_kernel<kIvfPairsPerBlock><<<dim3(pblocks), dim3(256), hist_bytes, st>>>(
-            probes, nb, nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(),
-            d_cursor, plan, d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
+        ivf_plan_kernel<<<dim3(1), dim3(1024), 0, b.st>>>(
+            b.d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), nlist, b.g.group, b.g.bins_per_span, b.g.run_groups, (int)b.g.max_items,
+            (int)b.g.max_slots, (int)b.g.max_bins, h->plan.ivf_slot_off.as<int32_t>(), h->plan.ivf_list_item0.as<int32_t>(),
+            h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(), h->plan.ivf_item_bin0.as<int32_t>(), L.plan,
+            h->lists.ivf_offsets.as<int64_t>());
+        scatter<<<dim3(L.pblocks), dim3(256), L.hist_bytes, b.st>>>(
+            L.probes, b.nb, b.nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(), L.d_cursor, L.plan,
+            L.d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     }
     VDB_HIP(hipGetLastError());
+}
 
-    ScanArgs sa{};
-    sa.panels = h->scan.panels.as<half8>();
-    if (sq8(h)) {      // SQ8: the fp16 panels of the whole panel space, converted from the codes for this batch (workspace)
-        const int64_t ntiles = h->ivf_pspans * kIvfTilesPerSpan;
-        ws.sq8_panels.reserve((size_t)ntiles * h->ksteps * 64 * sizeof(half8));
-        const int64_t threads = ntiles * h->ksteps * 64;
-        ivf_sq8_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
-            sq8_rows(h), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
-            ws.sq8_panels.as<half8>());
-        VDB_HIP(hipGetLastError());
-        sa.panels = ws.sq8_panels.as<half8>();
-    }
-    sa.bias = h->scan.bias.as<float>();
-    sa.qpanels = nullptr;
-    sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
-    sa.slot_query = d_slot_query;
-    sa.info = info;
-    sa.bin_m1 = ws.bin_m1.as<float>();
-    sa.bin_m2 = ws.bin_m2.as<float>();
-    sa.bin_m3 = ws.bin_m3.as<float>();
-    sa.item_list = h->plan.ivf_item_list.as<int32_t>();
-    sa.item_slot0 = h->plan.ivf_item_slot0.as<int32_t>();
-    sa.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
-    sa.n_items = &plan->n_items;
-    sa.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
-    timing_mark(h, tslot, 0, st);
-    {
-        // long lists are cut into row parts of `part` spans (256 rows each), one workgroup per (item, part): the scan's
-        // duration is otherwise the LONGEST list's (k-means lists are far from even: 5x the median on SIFT-like data)
-        // (measured, scripts/sweep_ivf.py --option ivf_part: nprobe 8 / 32 / 128 at nlist 1024, 10k queries -> 1 / 2 / 4 spans;
-        //  the fewer work items there are, the finer the parts)
-        const int part_auto = (kSpanRows / kIvfSpanRows) * (max_items <= 2048 ? 1 : max_items <= 4096 ? 2 : 4);   // (the measurements were in 512-row units)
-        // (at most 64 parts per item: every (item, part) is a workgroup, and the parts beyond a short list's end only exit --
-        //  one giant list must not turn the launch into millions of empty workgroups)
-        int part = std::min(std::max(h->ivf_part > 0 ? h->ivf_part : part_auto, (h->ivf_max_pspans + 63) / 64),
-                            h->ivf_max_pspans);
-        {   // a row part starts at a multiple of 4 bins of the lane's run (the bins leave as 16-byte vectors)
-            const int unit = 4 / bps;          // bps = bins of a span half: 1 or 2
-            part = (part + unit - 1) / unit * unit;
-        }
-        sa.part_spans = part >= h->ivf_max_pspans ? 0 : part;
-        const dim3 grid((unsigned)max_items, (unsigned)(sa.part_spans ? (h->ivf_max_pspans + part - 1) / part : 1));
+// SQ8: the fp16 panels of the whole panel space, converted from the codes for this batch (workspace)
+const half8 *ivf_sq8_panels(const IvfBatch &b) {
+    vdb_index_s *h = b.h;
+    const int64_t ntiles = h->ivf_pspans * kIvfTilesPerSpan;
+    h->ws.sq8_panels.reserve((size_t)ntiles * h->ksteps * 64 * sizeof(half8));
+    const int64_t threads = ntiles * h->ksteps * 64;
+    ivf_sq8_panels_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, b.st>>>(
+        sq8_rows(h), h->dim, h->D4, h->ksteps, ntiles, h->sx, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
+        h->ws.sq8_panels.as<half8>());
+    VDB_HIP(hipGetLastError());
+    return h->ws.sq8_panels.as<half8>();
+}
+
+// Long lists are cut into row parts of some spans each, one workgroup per (item, part): the scan's duration is otherwise the
+// LONGEST list's (k-means lists are far from even: 5x the median on SIFT-like data).  `base` = the scan's own choice of the
+// part size (option "ivf_part" overrides it), rounded up to `unit` spans.  At most 64 parts per item: every (item, part) is
+// a workgroup, and the parts beyond a short list's end only exit -- one giant list must not turn the launch into millions of
+// empty workgroups.  Returns the part size (0 = whole lists) and the grid
+struct IvfParts { int part_spans; dim3 grid; };
+IvfParts ivf_part_spans(const vdb_index_s *h, int64_t max_items, int base, int unit = 1) {
+    int part = std::min(std::max(h->ivf_part > 0 ? h->ivf_part : base, (h->ivf_max_pspans + 63) / 64), h->ivf_max_pspans);
+    part = (part + unit - 1) / unit * unit;
+    const int part_spans = part >= h->ivf_max_pspans ? 0 : part;
+    return {part_spans, dim3((unsigned)max_items, (unsigned)(part_spans ? (h->ivf_max_pspans + part - 1) / part : 1))};
+}
+
+// D > 128: the K-loop scan on p16 panels (ivf_kloop.hpp)
+void ivf_scan_kloop(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    hipStream_t st = b.st;
+    IvfKloopArgs ka{};
+    ka.panels = sa.panels; ka.bias = sa.bias; ka.qrows = sa.qrows; ka.info = sa.info;
+    ka.bin_m[0] = sa.bin_m1; ka.bin_m[1] = sa.bin_m2; ka.bin_m[2] = sa.bin_m3;
+    ka.bin_m[3] = h->ws.bin_m4.as<float>(); ka.bin_m[4] = h->ws.bin_m5.as<float>();
+    ka.item_list = sa.item_list; ka.item_slot0 = sa.item_slot0; ka.item_bin0 = sa.item_bin0;
+    ka.n_items = sa.n_items; ka.list_pspan0 = sa.list_pspan0; ka.slot_query = sa.slot_query;
+    ka.ksteps = h->ksteps;
+    // row parts: 128 rows x 512 slots x D of matrix work per pass -- a part of ~1024 rows keeps a workgroup busy for
+    // tens of microseconds at 384 dims; few work items -> finer parts (down to one span) to cover the chip
+    // (measured on the msmarco shape, 725 items of ~4 spans: scripts/sweep_ivf.py --workload msmarco_ivf --option ivf_part:
+    //  whole lists (8 spans) 0.612 ms, 4 spans 0.525, 2 spans 0.510, 1 span 0.528 -- ~1500 workgroups for the chip's 512
+    //  slots, and never less than 512 rows per workgroup: every part gathers its B fragments and fills its pipeline anew)
+    const int spans_512 = std::max(1, 512 / h->ivf_span_rows);
+    const double item_spans = (double)b.g.max_items * (double)h->ivf_pspans / (double)h->nlist;
+    const IvfParts parts = ivf_part_spans(
+        h, b.g.max_items, (int)std::min<double>(8.0 * spans_512, std::max<double>(spans_512, std::floor(item_spans / 1536.0))));
+    ka.part_spans = parts.part_spans;
+    const dim3 kgrid = parts.grid;
+    if (h->ivf_tps == 16 && b.g.group == kIvfKloopGroup / 2) {        // square tile: 256 rows x 256 slots
+        if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+        else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+        else ivf_kloop_scan_kernel<16, 2, 4, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+    } else if (h->ivf_tps == 16) {
+        if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1><<<kgrid, dim3(512), 0, st>>>(ka);
+        else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+        else ivf_kloop_scan_kernel<16, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+    } else ivf_kloop_scan_kernel<64, 2><<<kgrid, dim3(512), 0, st>>>(ka);
+    VDB_HIP(hipGetLastError());
+}
+
+// D <= 128: scan_kernel in ITEMS mode on 32-row tiles.  Sets sa.part_spans; returns the grid (the int8 scan launches the same)
+dim3 ivf_scan_fp16(const IvfBatch &b, ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    hipStream_t st = b.st;
+    const int nw = b.g.nw, bt = b.g.bt;
+    // row parts of 256-row spans (measured in 512-row units, scripts/sweep_ivf.py --option ivf_part: nprobe 8 / 32 / 128 at
+    //  nlist 1024, 10k queries -> 1 / 2 / 4 spans; the fewer work items there are, the finer the parts)
+    const int part_auto = (kSpanRows / kIvfSpanRows) * (b.g.max_items <= 2048 ? 1 : b.g.max_items <= 4096 ? 2 : 4);
+    // a row part starts at a multiple of 4 bins of the lane's run (the bins leave as 16-byte vectors; bps = bins of a span half)
+    const IvfParts parts = ivf_part_spans(h, b.g.max_items, part_auto, 4 / b.g.bps);
+    sa.part_spans = parts.part_spans;
+    const dim3 grid = parts.grid;
 #define VDB_IVF_SCAN(KS, NW, BT) scan_kernel<KS, NW, 2, 2, BT, true><<<grid, dim3(NW * 64), 0, st>>>(sa)
-        if (kloop) {
-            IvfKloopArgs ka{};
-            ka.panels = sa.panels; ka.bias = sa.bias; ka.qrows = sa.qrows; ka.info = info;
-            ka.bin_m[0] = sa.bin_m1; ka.bin_m[1] = sa.bin_m2; ka.bin_m[2] = sa.bin_m3;
-            ka.bin_m[3] = ws.bin_m4.as<float>(); ka.bin_m[4] = ws.bin_m5.as<float>();
-            ka.item_list = sa.item_list; ka.item_slot0 = sa.item_slot0; ka.item_bin0 = sa.item_bin0;
-            ka.n_items = sa.n_items; ka.list_pspan0 = sa.list_pspan0; ka.slot_query = sa.slot_query;
-            ka.ksteps = h->ksteps;
-            // row parts: 128 rows x 512 slots x D of matrix work per pass -- a part of ~1024 rows keeps a workgroup busy for
-            // tens of microseconds at 384 dims; few work items -> finer parts (down to one span) to cover the chip
-            // (measured on the msmarco shape, 725 items of ~4 spans: scripts/sweep_ivf.py --workload msmarco_ivf --option ivf_part:
-            //  whole lists (8 spans) 0.612 ms, 4 spans 0.525, 2 spans 0.510, 1 span 0.528 -- ~1500 workgroups for the chip's 512
-            //  slots, and never less than 512 rows per workgroup: every part gathers its B fragments and fills its pipeline anew)
-            const int spans_512 = std::max(1, 512 / h->ivf_span_rows);
-            const double item_spans = (double)max_items * (double)h->ivf_pspans / (double)nlist;
-            int kpart = h->ivf_part > 0 ? h->ivf_part
-                                        : (int)std::min<double>(8.0 * spans_512, std::max<double>(spans_512, std::floor(item_spans / 1536.0)));
-            kpart = std::min(std::max(kpart, (h->ivf_max_pspans + 63) / 64), h->ivf_max_pspans);
-            ka.part_spans = kpart >= h->ivf_max_pspans ? 0 : kpart;
-            const dim3 kgrid((unsigned)max_items, (unsigned)(ka.part_spans ? (h->ivf_max_pspans + kpart - 1) / kpart : 1));
-            if (h->ivf_tps == 16 && group == kIvfKloopGroup / 2) {        // square tile: 256 rows x 256 slots
-                if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-                else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-                else ivf_kloop_scan_kernel<16, 2, 4, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-            } else if (h->ivf_tps == 16) {
-                if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1><<<kgrid, dim3(512), 0, st>>>(ka);
-                else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-                else ivf_kloop_scan_kernel<16, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-            } else ivf_kloop_scan_kernel<64, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-        } else if (h->ksteps == 4) {
-            if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(4, 2, 4); else VDB_IVF_SCAN(4, 2, 8); }
-            else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(4, 4, 4); else VDB_IVF_SCAN(4, 4, 8); }
-            else              { if (bt == 4) VDB_IVF_SCAN(4, 8, 4); else VDB_IVF_SCAN(4, 8, 8); }
-        } else {
-            if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(8, 2, 4); else VDB_IVF_SCAN(8, 2, 8); }
-            else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(8, 4, 4); else VDB_IVF_SCAN(8, 4, 8); }
-            else              { if (bt == 4) VDB_IVF_SCAN(8, 8, 4); else VDB_IVF_SCAN(8, 8, 8); }
-        }
+    if (h->ksteps == 4) {
+        if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(4, 2, 4); else VDB_IVF_SCAN(4, 2, 8); }
+        else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(4, 4, 4); else VDB_IVF_SCAN(4, 4, 8); }
+        else              { if (bt == 4) VDB_IVF_SCAN(4, 8, 4); else VDB_IVF_SCAN(4, 8, 8); }
+    } else {
+        if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(8, 2, 4); else VDB_IVF_SCAN(8, 2, 8); }
+        else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(8, 4, 4); else VDB_IVF_SCAN(8, 4, 8); }
+        else              { if (bt == 4) VDB_IVF_SCAN(8, 8, 4); else VDB_IVF_SCAN(8, 8, 8); }
+    }
 #undef VDB_IVF_SCAN
-        VDB_HIP(hipGetLastError());
-        if (use_i8) {      // the int8 form of the same scan; whichever the finalize kernel did not choose returns at once
-            ScanI8Args s8{};
-            s8.panels = h->scan.panels8.as<int4v>();
-            s8.bias8 = h->scan.bias8.as<int32_t>();
-            s8.info = info;
-            s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2; s8.bin_m3 = sa.bin_m3;
-            s8.Npad = h->ivf_pspans * kIvfSpanRows;
-            s8.item_list = sa.item_list; s8.item_slot0 = sa.item_slot0; s8.item_bin0 = sa.item_bin0;
-            s8.n_items = sa.n_items; s8.list_pspan0 = sa.list_pspan0; s8.slot_query = sa.slot_query;
-            s8.qrows = reinterpret_cast<const signed char *>(ws.qpanels8.p);
-            s8.part_spans = sa.part_spans;
-            // (select groups stay quads here: measured with octs the list scan gains 5 % and the refine loses more -- the
-            //  probed lists are dense in near neighbours, so an 8-row group drags in more re-scans and twice the rows)
-            // staging ring of the work items (option "i8_ring"; 0 = auto): a work item streams its list once, and few of them
-            // are resident per CU -- 4 stages of 2 (4 at two k-steps) tiles in flight instead of 1
+    VDB_HIP(hipGetLastError());
+    return grid;
+}
+
+// the int8 form of the same scan; whichever the finalize kernel did not choose returns at once
+void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa, dim3 grid) {
+    vdb_index_s *h = b.h;
+    hipStream_t st = b.st;
+    const int nw = b.g.nw, bt = b.g.bt;
+    ScanI8Args s8{};
+    s8.panels = h->scan.panels8.as<int4v>();
+    s8.bias8 = h->scan.bias8.as<int32_t>();
+    s8.info = sa.info;
+    s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2; s8.bin_m3 = sa.bin_m3;
+    s8.Npad = h->ivf_pspans * kIvfSpanRows;
+    s8.item_list = sa.item_list; s8.item_slot0 = sa.item_slot0; s8.item_bin0 = sa.item_bin0;
+    s8.n_items = sa.n_items; s8.list_pspan0 = sa.list_pspan0; s8.slot_query = sa.slot_query;
+    s8.qrows = reinterpret_cast<const signed char *>(h->ws.qpanels8.p);
+    s8.part_spans = sa.part_spans;
+    // (select groups stay quads here: measured with octs the list scan gains 5 % and the refine loses more -- the
+    //  probed lists are dense in near neighbours, so an 8-row group drags in more re-scans and twice the rows)
+    // staging ring of the work items (option "i8_ring"; 0 = auto): a work item streams its list once, and few of them
+    // are resident per CU -- 4 stages of 2 (4 at two k-steps) tiles in flight instead of 1
 #define VDB_IVF_SCAN8(KS, ST, NW, BT) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
-            if (h->ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-            else if (r__ == 2) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-            else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-            else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
+    if (h->ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+    else if (r__ == 2) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+    else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+    else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
 #define VDB_IVF_SCAN8_NW(KS, ST, BT) do { if (nw == 2) VDB_IVF_SCAN8(KS, ST, 2, BT); else if (nw == 4) VDB_IVF_SCAN8(KS, ST, 4, BT); \
                                           else VDB_IVF_SCAN8(KS, ST, 8, BT); } while (0)
-            // (tiles per LDS stage: 2 -- 8 pieces per stage for 8 waves make it 4 at two k-steps; deeper stages measured
-            //  slower at nprobe 32 / 128 and equal at 8 once the lists are scanned in row parts)
-            if (h->i8_ks == 2) {
-                if (bt == 4) VDB_IVF_SCAN8_NW(2, 4, 4); else VDB_IVF_SCAN8_NW(2, 4, 8);
-            } else {
-                if (bt == 4) VDB_IVF_SCAN8_NW(4, 2, 4); else VDB_IVF_SCAN8_NW(4, 2, 8);
-            }
+    // (tiles per LDS stage: 2 -- 8 pieces per stage for 8 waves make it 4 at two k-steps; deeper stages measured
+    //  slower at nprobe 32 / 128 and equal at 8 once the lists are scanned in row parts)
+    if (h->i8_ks == 2) {
+        if (bt == 4) VDB_IVF_SCAN8_NW(2, 4, 4); else VDB_IVF_SCAN8_NW(2, 4, 8);
+    } else {
+        if (bt == 4) VDB_IVF_SCAN8_NW(4, 2, 4); else VDB_IVF_SCAN8_NW(4, 2, 8);
+    }
 #undef VDB_IVF_SCAN8_NW
 #undef VDB_IVF_SCAN8
-            VDB_HIP(hipGetLastError());
-        }
-    }
-    timing_mark(h, tslot, 1, st);
+    VDB_HIP(hipGetLastError());
+}
 
+IvfSelectArgs ivf_lists_select(const IvfBatch &b, const IvfLists &L, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = h->ws;
+    const int k = b.k, nprobe = b.nprobe;
     IvfSelectArgs se{};
-    se.bin_m[0] = sa.bin_m1;
-    se.bin_m[1] = sa.bin_m2;
-    se.bin_m[2] = sa.bin_m3;
-    se.bin_m[3] = kloop ? ws.bin_m4.as<float>() : nullptr;
-    se.bin_m[4] = kloop ? ws.bin_m5.as<float>() : nullptr;
-    se.nm = kloop ? kIvfKloopMinima : 3;
+    se.bin_m[0] = sa.bin_m1; se.bin_m[1] = sa.bin_m2; se.bin_m[2] = sa.bin_m3;
+    se.bin_m[3] = b.g.kloop ? ws.bin_m4.as<float>() : nullptr;
+    se.bin_m[4] = b.g.kloop ? ws.bin_m5.as<float>() : nullptr;
+    se.nm = b.g.kloop ? kIvfKloopMinima : 3;
     se.eps = ws.eps.as<float>();
-    se.info = info;
-    se.plan = plan;
-    se.probes = probes;
-    se.slot_of = h->plan.ivf_slot_of.as<int32_t>();
-    se.slot_off = h->plan.ivf_slot_off.as<int32_t>();
-    se.list_item0 = h->plan.ivf_list_item0.as<int32_t>();
-    se.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
+    se.info = L.info; se.plan = L.plan; se.probes = L.probes;
+    se.slot_of = h->plan.ivf_slot_of.as<int32_t>(); se.slot_off = h->plan.ivf_slot_off.as<int32_t>();
+    se.list_item0 = h->plan.ivf_list_item0.as<int32_t>(); se.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
     se.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
-    se.span_row0 = h->lists.ivf_span_row0.as<int32_t>();
-    se.span_valid = h->lists.ivf_span_valid.as<int32_t>();
-    se.nq = nb;
-    se.nprobe = nprobe;
-    se.group = group;
-    se.k = k;
-    se.cand_cap = cand_cap;
-    se.rescan_cap = rescan_cap;
+    se.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); se.span_valid = h->lists.ivf_span_valid.as<int32_t>();
+    se.nq = b.nb; se.nprobe = nprobe; se.group = b.g.group; se.k = k;
+    se.cand_cap = L.cand_cap; se.rescan_cap = L.rescan_cap;
     // a query can meet at most nprobe * (bins of the longest list) entries
-    {
-        const int64_t worst = (int64_t)nprobe * (h->ivf_max_pspans * bins_per_span + run_groups * 3);
-        se.max_entries = (int)std::min<int64_t>(kIvfMaxEntries, (worst + 63) / 64 * 64);
-        se.probe_cap = (nprobe + 63) / 64 * 64;
-    }
-    se.group_rows = kloop ? kgroup : 0;
-    se.bins_per_span = bins_per_span;
-    se.bin_rows = bin_rows;
-    se.run_groups = run_groups;
-    se.cand_rows = ws.cand.as<int32_t>();
-    se.rescan_rows = ws.rescan.as<int32_t>();
-    se.counts = ws.counts.as<int32_t>();
-    se.fallback = ws.fallback.as<int32_t>();
-    se.fb_list = ws.fb_list.as<int32_t>();
+    const int64_t worst = (int64_t)nprobe * (h->ivf_max_pspans * b.g.bins_per_span + b.g.run_groups * 3);
+    se.max_entries = (int)std::min<int64_t>(kIvfMaxEntries, (worst + 63) / 64 * 64);
+    se.probe_cap = (nprobe + 63) / 64 * 64;
+    se.group_rows = b.g.kloop ? L.kgroup : 0;
+    se.bins_per_span = b.g.bins_per_span; se.bin_rows = b.g.bin_rows; se.run_groups = b.g.run_groups;
+    se.cand_rows = ws.cand.as<int32_t>(); se.rescan_rows = ws.rescan.as<int32_t>();
+    se.counts = ws.counts.as<int32_t>(); se.fallback = ws.fallback.as<int32_t>(); se.fb_list = ws.fb_list.as<int32_t>();
     se.fb_count = ws.small.as<int32_t>();            // (zeroed with the batch info: the first 64 bytes of ws.small)
-    se.stat_counters = stat_counters;
+    se.stat_counters = reinterpret_cast<unsigned long long *>(ws.small.as<char>() + 64);
     se.vals_entries = k > 64 ? se.max_entries : 0;
-    se.act_cap = std::min(cand_cap + rescan_cap, se.max_entries);       // (entry numbers are packed into 16 bits: <= 4096)
+    se.act_cap = std::min(L.cand_cap + L.rescan_cap, se.max_entries);       // (entry numbers are packed into 16 bits: <= 4096)
     {   // two waves per workgroup within the 64 KiB a kernel gets without opting in: 8192 words per wave
         const int fixed = se.vals_entries + 4 * se.probe_cap + 64;
         se.act_cap = std::max(64, std::min(se.act_cap, (8192 - fixed) / (1 + se.nm)));
     }
-    ivf_select_kernel<<<dim3((unsigned)((nb + 1) / 2)), dim3(128),
-                        (size_t)2 * ivf_select_lds_words(se.vals_entries, se.probe_cap, se.act_cap, se.nm) * 4, st>>>(se);
+    ivf_select_kernel<<<dim3((unsigned)((b.nb + 1) / 2)), dim3(128),
+                        (size_t)2 * ivf_select_lds_words(se.vals_entries, se.probe_cap, se.act_cap, se.nm) * 4, b.st>>>(se);
     VDB_HIP(hipGetLastError());
+    return se;
+}
 
-    RefineCommon rc{h->rows.x32.as<float>(), qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
-    rc.info = info;
+// the refine of the selected candidates and, in the same launch, the flagged queries (work list overflow, unusable scales,
+// plan overflow): exact list scan, split on the device
+void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &se) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = h->ws;
+    const int k = b.k;
+    const int64_t nb = b.nb;
+    RefineCommon rc{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
+    rc.info = L.info;
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
-    if (use_i8 && h->scan.rows8.p) {
-        rc.X8 = h->scan.rows8.as<signed char>();
-        rc.rowstat = h->scan.rowstat8.as<int>();
+    if (L.use_i8 && h->scan.rows8.p) {
+        rc.X8 = h->scan.rows8.as<signed char>(); rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
-        rc.x8_pitch = h->rows8_pitch;
-        rc.cx = h->i8_cx;
-        rc.D = h->dim;
+        rc.x8_pitch = h->rows8_pitch; rc.cx = h->i8_cx; rc.D = h->dim;
     }
     RefineListArgs la{};
     la.c = rc;
     la.nq = nb;
-    la.cand_rows = se.cand_rows;
-    la.rescan_rows = se.rescan_rows;
-    la.counts = se.counts;
-    la.fallback = se.fallback;
-    la.cand_cap = cand_cap;
-    la.rescan_cap = rescan_cap;
-    la.D = D;
-    la.I = I;
-    la.pkeys = pk;
-    la.pids = pi;
-    if (kloop) la.group_shift = kgroup == 1 ? 0 : kgroup == 2 ? 1 : 2;
-    // ... and, in the same launch, the flagged queries (work list overflow, unusable scales, plan overflow): exact list scan,
-    // split on the device
+    la.cand_rows = se.cand_rows; la.rescan_rows = se.rescan_rows; la.counts = se.counts; la.fallback = se.fallback;
+    la.cand_cap = L.cand_cap; la.rescan_cap = L.rescan_cap;
+    la.D = b.D; la.I = b.I; la.pkeys = b.pk; la.pids = b.pi;
+    if (b.g.kloop) la.group_shift = L.kgroup == 1 ? 0 : L.kgroup == 2 ? 1 : 2;
     IvfFallbackArgs a{};
     a.c = rc;
     a.offsets = h->lists.ivf_offsets.as<int64_t>();
-    a.probes = probes;
-    a.nprobe = nprobe;
-    a.fb_list = se.fb_list;
-    a.fb_count = se.fb_count;
-    a.max_split = std::min(nprobe, 64);
+    a.probes = L.probes; a.nprobe = b.nprobe;
+    a.fb_list = se.fb_list; a.fb_count = se.fb_count;
+    a.max_split = std::min(b.nprobe, 64);
     a.cap_units = std::max<int64_t>(nb, 4096);
     ws.pkeys.reserve((size_t)a.cap_units * k * sizeof(double));
     ws.pids.reserve((size_t)a.cap_units * k * sizeof(int64_t));
-    a.pkeys = ws.pkeys.as<double>();
-    a.pids = ws.pids.as<int64_t>();
-    a.done = d_fb_done;
-    a.D = D;
-    a.I = I;
-    a.okeys = pk;
-    a.oids = pi;
-    {
-        const int kpl = kpl_for(k);
-        DISPATCH_KPL(kpl, (ivf_tail_kernel<KPL><<<dim3(512 + (unsigned)((nb + 3) / 4)), dim3(256), 0, st>>>(la, a, 512u)));
-        VDB_HIP(hipGetLastError());
+    a.pkeys = ws.pkeys.as<double>(); a.pids = ws.pids.as<int64_t>();
+    a.done = L.d_fb_done;
+    a.D = b.D; a.I = b.I; a.okeys = b.pk; a.oids = b.pi;
+    const int kpl = kpl_for(k);
+    DISPATCH_KPL(kpl, (ivf_tail_kernel<KPL><<<dim3(512 + (unsigned)((nb + 3) / 4)), dim3(256), 0, b.st>>>(la, a, 512u)));
+    VDB_HIP(hipGetLastError());
+}
+
+// the list-major MFMA path: the steps in the order they are enqueued
+void ivf_search_lists(const IvfBatch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = h->ws;
+    const IvfLists L = ivf_lists_reserve(b);
+    ivf_lists_prep(b, L);
+    ivf_lists_plan(b, L);
+    ScanArgs sa{};
+    sa.panels = sq8(h) ? ivf_sq8_panels(b) : h->scan.panels.as<half8>();
+    sa.bias = h->scan.bias.as<float>();
+    sa.qpanels = nullptr;
+    sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
+    sa.slot_query = L.d_slot_query;
+    sa.info = L.info;
+    sa.bin_m1 = ws.bin_m1.as<float>(); sa.bin_m2 = ws.bin_m2.as<float>(); sa.bin_m3 = ws.bin_m3.as<float>();
+    sa.item_list = h->plan.ivf_item_list.as<int32_t>(); sa.item_slot0 = h->plan.ivf_item_slot0.as<int32_t>();
+    sa.item_bin0 = h->plan.ivf_item_bin0.as<int32_t>();
+    sa.n_items = &L.plan->n_items;
+    sa.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
+    timing_mark(h, b.tslot, 0, b.st);
+    if (b.g.kloop) {
+        ivf_scan_kloop(b, L.kgroup, sa);
+    } else {
+        const dim3 grid = ivf_scan_fp16(b, sa);
+        if (L.use_i8) ivf_scan_i8(b, sa, grid);
     }
+    timing_mark(h, b.tslot, 1, b.st);
+    const IvfSelectArgs se = ivf_lists_select(b, L, sa);
+    ivf_lists_tail(b, L, se);
 }
 
 // (re)size ivf_zero and point both ws.small at it: [coarse small | own small | counter block of `cnt_words` ints]
@@ -597,6 +686,50 @@ int32_t *ivf_bind_zero(vdb_index_s *h, size_t cnt_words) {
     return reinterpret_cast<int32_t *>((char *)h->plan.ivf_zero.p + 2 * kZeroSmall);
 }
 
+// the exact list scan: every query's probed lists in S splits (one wave each), merged when S > 1
+void ivf_search_exact(const IvfBatch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = h->ws;
+    const int64_t nb = b.nb;
+    const int k = b.k, nprobe = b.nprobe;
+    hipStream_t st = b.st;
+    // waves per query: keep each wave's share of rows moderate and the GPU full
+    const double rows_per_query = (double)nprobe * (double)h->N / (double)h->nlist;
+    int64_t S = (int64_t)std::ceil(rows_per_query / 4096.0);
+    S = std::max<int64_t>(S, (8192 + nb - 1) / nb);
+    S = std::max<int64_t>(1, std::min<int64_t>(S, nprobe));
+    const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nb * k * 16));
+    S = std::min<int64_t>(S, cap);
+    IvfScanArgs a{};
+    a.c = RefineCommon{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
+    if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
+    a.offsets = h->lists.ivf_offsets.as<int64_t>();
+    a.probes = h->plan.ivf_probe_i.as<int64_t>();
+    a.nq = nb; a.nprobe = nprobe; a.S = (int)S;
+    if (S == 1) {
+        a.D = b.D; a.I = b.I; a.pkeys = b.pk; a.pids = b.pi;
+    } else {
+        ws.pkeys.reserve((size_t)nb * S * k * sizeof(double));
+        ws.pids.reserve((size_t)nb * S * k * sizeof(int64_t));
+        a.pkeys = ws.pkeys.as<double>(); a.pids = ws.pids.as<int64_t>();
+    }
+    timing_mark(h, b.tslot, 0, st);
+    const int kpl = kpl_for(k);
+    const unsigned grid = (unsigned)((nb * S + 3) / 4);
+    DISPATCH_KPL(kpl, (ivf_scan_kernel<KPL><<<dim3(grid), dim3(256), 0, st>>>(a)));
+    VDB_HIP(hipGetLastError());
+    timing_mark(h, b.tslot, 1, st);
+    if (S > 1) {
+        MergeArgs ma{};
+        ma.pkeys = a.pkeys; ma.pids = a.pids;
+        ma.part_stride = k; ma.slot_stride = S * k; ma.nparts = (int)S;
+        ma.k = k; ma.metric = h->metric; ma.count = nb;
+        ma.D = b.D; ma.I = b.I; ma.okeys = b.pk; ma.oids = b.pi;
+        launch_merge(ma, nb, st);
+    }
+}
+
+// what both paths share -- the clearing of ivf_zero, timing_begin, the coarse search, padded queries -- then the path, per batch
 void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *PK,
                             int64_t *PI, hipStream_t st) {
     ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
@@ -615,95 +748,38 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
     const size_t ev_mark = h->ev_used;
     try {
     for (int64_t b0 = 0; b0 < nq; b0 += kBatch) {
-        const int64_t nb = std::min<int64_t>(kBatch, nq - b0);
-        const float *q = dq + (size_t)b0 * Dm;
+        IvfBatch b{};
+        b.h = h; b.k = k; b.nprobe = nprobe; b.st = st;
+        b.nb = std::min<int64_t>(kBatch, nq - b0);
+        b.q = dq + (size_t)b0 * Dm;
         // everything this batch needs zeroed sits in ivf_zero: ONE memset (first batch of a call: both ws.small whole and
         // the counter block; later batches keep this handle's statistics counters, which accumulate over the call)
-        const IvfGeom geom = ivf_geometry(h, nb, k, nprobe);
-        int32_t *d_cnt = ivf_bind_zero(h, geom.ok ? geom.cnt_words : 0);
+        b.g = ivf_geometry(h, b.nb, k, b.nprobe);
+        b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
-            VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (geom.ok ? geom.cnt_words * 4 : 0), st));
+            VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (b.g.ok ? b.g.cnt_words * 4 : 0), st));
         } else {
             VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, kZeroSmall + 64, st));
-            if (geom.ok) VDB_HIP(hipMemsetAsync(d_cnt, 0, geom.cnt_words * 4, st));
+            if (b.g.ok) VDB_HIP(hipMemsetAsync(b.d_cnt, 0, b.g.cnt_words * 4, st));
         }
         h->coarse->small_preset = true;
-        const long tslot = timing_begin(h, st);
-        h->plan.ivf_probe_d.reserve((size_t)nb * nprobe * sizeof(float));
-        h->plan.ivf_probe_i.reserve((size_t)nb * nprobe * sizeof(int64_t));
-        search_device_impl(h->coarse, q, nb, nprobe, h->plan.ivf_probe_d.as<float>(), h->plan.ivf_probe_i.as<int64_t>(), nullptr,
+        b.tslot = timing_begin(h, st);
+        h->plan.ivf_probe_d.reserve((size_t)b.nb * b.nprobe * sizeof(float));
+        h->plan.ivf_probe_i.reserve((size_t)b.nb * b.nprobe * sizeof(int64_t));
+        search_device_impl(h->coarse, b.q, b.nb, b.nprobe, h->plan.ivf_probe_d.as<float>(), h->plan.ivf_probe_i.as<int64_t>(), nullptr,
                            nullptr, st);
-        const float *qpad = q;
+        b.qpad = b.q;
         if (D4 != Dm) {
-            ws.qpad.reserve((size_t)nb * D4 * sizeof(float));
-            pad_rows_kernel<<<dim3((unsigned)((nb * D4 + 255) / 256)), dim3(256), 0, st>>>(q, nb, Dm, D4,
-                                                                                          ws.qpad.as<float>());
-            qpad = ws.qpad.as<float>();
+            ws.qpad.reserve((size_t)b.nb * D4 * sizeof(float));
+            pad_rows_kernel<<<dim3((unsigned)((b.nb * D4 + 255) / 256)), dim3(256), 0, st>>>(b.q, b.nb, Dm, D4, ws.qpad.as<float>());
+            b.qpad = ws.qpad.as<float>();
         }
-        float *Db0 = partial ? nullptr : D + (size_t)b0 * k;
-        int64_t *Ib0 = partial ? nullptr : I + (size_t)b0 * k;
-        double *Pk0 = partial ? PK + (size_t)b0 * k : nullptr;
-        int64_t *Pi0 = partial ? PI + (size_t)b0 * k : nullptr;
-        if (geom.ok) {
-            ivf_mfma_batch(h, geom, d_cnt, q, qpad, nb, k, nprobe, Db0, Ib0, Pk0, Pi0, tslot, st);
-            timing_mark(h, tslot, 2, st);
-            h->last.last_path = VDB_PATH_IVF;
-            any_mfma = true;
-            continue;
-        }
-        // waves per query: keep each wave's share of rows moderate and the GPU full
-        const double rows_per_query = (double)nprobe * (double)h->N / (double)h->nlist;
-        int64_t S = (int64_t)std::ceil(rows_per_query / 4096.0);
-        S = std::max<int64_t>(S, (8192 + nb - 1) / nb);
-        S = std::max<int64_t>(1, std::min<int64_t>(S, nprobe));
-        const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nb * k * 16));
-        S = std::min<int64_t>(S, cap);
-        IvfScanArgs a{};
-        a.c = RefineCommon{h->rows.x32.as<float>(), qpad, h->N, h->id_base, D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
-        if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
-        a.offsets = h->lists.ivf_offsets.as<int64_t>();
-        a.probes = h->plan.ivf_probe_i.as<int64_t>();
-        a.nq = nb;
-        a.nprobe = nprobe;
-        a.S = (int)S;
-        float *Db = Db0;
-        int64_t *Ib = Ib0;
-        if (S == 1) {
-            a.D = Db;
-            a.I = Ib;
-            a.pkeys = Pk0;
-            a.pids = Pi0;
-        } else {
-            ws.pkeys.reserve((size_t)nb * S * k * sizeof(double));
-            ws.pids.reserve((size_t)nb * S * k * sizeof(int64_t));
-            a.pkeys = ws.pkeys.as<double>();
-            a.pids = ws.pids.as<int64_t>();
-        }
-        timing_mark(h, tslot, 0, st);
-        {
-            const int kpl = kpl_for(k);
-            const unsigned grid = (unsigned)((nb * S + 3) / 4);
-            DISPATCH_KPL(kpl, (ivf_scan_kernel<KPL><<<dim3(grid), dim3(256), 0, st>>>(a)));
-            VDB_HIP(hipGetLastError());
-        }
-        timing_mark(h, tslot, 1, st);
-        if (S > 1) {
-            MergeArgs ma{};
-            ma.pkeys = a.pkeys;
-            ma.pids = a.pids;
-            ma.part_stride = k;
-            ma.slot_stride = S * k;
-            ma.nparts = (int)S;
-            ma.k = k;
-            ma.metric = h->metric;
-            ma.count = nb;
-            ma.D = Db;
-            ma.I = Ib;
-            ma.okeys = Pk0;
-            ma.oids = Pi0;
-            launch_merge(ma, nb, st);
-        }
-        timing_mark(h, tslot, 2, st);
+        b.D = partial ? nullptr : D + (size_t)b0 * k; b.I = partial ? nullptr : I + (size_t)b0 * k;
+        b.pk = partial ? PK + (size_t)b0 * k : nullptr; b.pi = partial ? PI + (size_t)b0 * k : nullptr;
+        if (b.g.ok) ivf_search_lists(b);
+        else ivf_search_exact(b);
+        timing_mark(h, b.tslot, 2, st);
+        any_mfma = any_mfma || b.g.ok;
     }
     } catch (...) {
         h->ev_used = ev_mark;
@@ -896,11 +972,9 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
 }  // extern "C"
 
 namespace {
-// vdb_ivf_add / vdb_ivf_add_assigned: `given` (optional, host, int32 [n]) = the list of every row, as stored by a
-// persisted index; without it the rows are assigned to their nearest centroid here.
-// vdb_ivf_add / vdb_ivf_add_assigned: APPEND to the inverted lists, as faiss.IndexIVF.add does.  The lists are rebuilt from
-// (stored rows in list order ++ new rows) with a stable sort by list, so inside a list the rows stay in insertion order
-// and the index is the one a single add of the concatenated corpus builds.
+// vdb_ivf_add / vdb_ivf_add_assigned: APPEND to the inverted lists, as faiss.IndexIVF.add does (ivf_add_lists).  `given`
+// (optional, host, int32 [n]) = the list of every row, as stored by a persisted index; without it the rows are assigned to
+// their nearest centroid here.
 int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base, const int32_t *given) {
     return guarded([&] {
         auto *h = check(hh);
@@ -909,11 +983,8 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
-        const bool append = h->ivf_built && h->N > 0;
-        if (append) require_same_id_base(h, id_base);
-        if (append && n == 0) return;
-        const int64_t N0 = append ? h->N : 0, N1 = N0 + n;
-        ivf_require(N1 <= 2147483647ll - 1024, VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
+        int64_t N0, N1;
+        if (!ivf_add_range(h, n, id_base, N0, N1)) return;
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;
         graph_reset(h);
@@ -922,7 +993,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         h->built = false;
         std::vector<int64_t> assign_new((size_t)n);
         if (N1 > 0) {
-            DevBuf raw, src, src_ids, dperm, dassign, doff;
+            DevBuf src, src_ids, dperm, doff;
             // ONE pass over the host rows (row blocks through the pinned staging buffers); the unpadded copy the coarse
             // assignment reads is made on the device
             src.reserve((size_t)N1 * D4 * 4);
@@ -933,35 +1004,10 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
             if (given) {        // stored assignment: no coarse search at all
                 for (int64_t i = 0; i < n; ++i) assign_new[(size_t)i] = given[i];
             } else if (n > 0) {
-                const float *unpadded = fresh;
-                if (D4 != Dm) {
-                    raw.reserve((size_t)n * Dm * 4);
-                    VDB_HIP(hipMemcpy2D(raw.p, (size_t)Dm * 4, fresh, (size_t)D4 * 4, (size_t)Dm * 4, (size_t)n,
-                                        hipMemcpyDeviceToDevice));
-                    unpadded = raw.as<float>();
-                }
                 DevBuf dnew;
-                ivf_assign_rows(h, unpadded, n, dnew);
-                VDB_HIP(hipMemcpy(assign_new.data(), dnew.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-                raw.release();
+                ivf_add_assign(h, fresh, n, dnew, assign_new);
             }
-            // list of every source row: the stored rows are in list order (offsets), the new ones follow
-            std::vector<int64_t> assign_all((size_t)N1);
-            if (N0)
-                for (int l = 0; l < h->nlist; ++l)
-                    std::fill(assign_all.begin() + h->ivf_offsets_host[(size_t)l], assign_all.begin() + h->ivf_offsets_host[(size_t)l + 1], (int64_t)l);
-            std::copy(assign_new.begin(), assign_new.end(), assign_all.begin() + N0);
-            dassign.reserve((size_t)N1 * 8);
-            VDB_HIP(hipMemcpy(dassign.p, assign_all.data(), (size_t)N1 * 8, hipMemcpyHostToDevice));
-            if (N0) {           // ids of the source rows: the stored ones keep theirs
-                std::vector<int64_t> ids_new((size_t)n);
-                for (int64_t i = 0; i < n; ++i) ids_new[(size_t)i] = h->id_base + N0 + i;
-                src_ids.reserve((size_t)N1 * 8);
-                VDB_HIP(hipMemcpy(src_ids.p, h->lists.ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
-                VDB_HIP(hipMemcpy(src_ids.as<int64_t>() + N0, ids_new.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-            }
-            ivf_csr_build(h, dassign, N1, h->nlist, dperm, doff, h->ivf_offsets_host);
-            dassign.release();
+            ivf_add_lists(h, assign_new, N0, src_ids, dperm, doff);
             h->rows.x32.reserve((size_t)N1 * D4 * 4);
             h->lists.ivf_ids.reserve((size_t)N1 * 8);
             const int64_t total = N1 * (D4 / 4);
@@ -970,18 +1016,23 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
                 h->rows.x32.as<float>(), h->lists.ivf_ids.as<int64_t>());
             VDB_HIP(hipGetLastError());
             VDB_HIP(hipDeviceSynchronize());
-        } else {
-            h->ivf_offsets_host.assign((size_t)h->nlist + 1, 0);
         }
-        h->N = N1;
-        h->id_base = id_base;
-        h->lists.ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
-        VDB_HIP(hipMemcpy(h->lists.ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8,
-                          hipMemcpyHostToDevice));
-        h->ivf_list_of_row.resize((size_t)N1);              // (in insertion order: the stored part stays)
-        for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
+        ivf_add_finish(h, assign_new, N0, id_base);
         ivf_build_panel_space(h);
         h->ivf_built = true;
+    });
+}
+// vdb_ivf_search_device (graph key kind 3: final rows D, I) and vdb_ivf_search_partial_device (kind 4: partial rows pk, pi)
+int ivf_search_device_entry(vdb_handle hh, const float *q_dev, int64_t nq, int k, int kind, float *D, int64_t *I, double *pk,
+                            int64_t *pi, void *stream) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_ivf(h);
+        if (h->multi) return multi_search(h, q_dev, true, nq, k, D, I, pk, pi, as_stream(stream), true);
+        set_device(h->device);
+        vdb_index_s::GraphKey key;
+        key.q = q_dev; key.o1 = D ? (const void *)D : pk; key.o2 = D ? I : pi; key.nq = nq; key.k = k; key.kind = kind; key.nprobe = h->nprobe; key.st = as_stream(stream);
+        graph_or_run(h, key, [&] { ivf_search_device_impl(h, q_dev, nq, k, D, I, pk, pi, as_stream(stream)); });
     });
 }
 }  // namespace
@@ -1027,28 +1078,12 @@ int vdb_ivf_get_assignment(vdb_handle hh, int32_t *list_of_row_host) {
 
 int vdb_ivf_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                           void *stream) {
-    return guarded([&] {
-        auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) return multi_search(h, q_dev, true, nq, k, D_dev, I_dev, nullptr, nullptr, as_stream(stream), true);
-        set_device(h->device);
-        vdb_index_s::GraphKey key;
-        key.q = q_dev; key.o1 = D_dev; key.o2 = I_dev; key.nq = nq; key.k = k; key.kind = 3; key.nprobe = h->nprobe; key.st = as_stream(stream);
-        graph_or_run(h, key, [&] { ivf_search_device_impl(h, q_dev, nq, k, D_dev, I_dev, nullptr, nullptr, as_stream(stream)); });
-    });
+    return ivf_search_device_entry(hh, q_dev, nq, k, 3, D_dev, I_dev, nullptr, nullptr, stream);
 }
 
 int vdb_ivf_search_partial_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, double *keys_dev,
                                   int64_t *ids_dev, void *stream) {
-    return guarded([&] {
-        auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) return multi_search(h, q_dev, true, nq, k, nullptr, nullptr, keys_dev, ids_dev, as_stream(stream), true);
-        set_device(h->device);
-        vdb_index_s::GraphKey key;
-        key.q = q_dev; key.o1 = keys_dev; key.o2 = ids_dev; key.nq = nq; key.k = k; key.kind = 4; key.nprobe = h->nprobe; key.st = as_stream(stream);
-        graph_or_run(h, key, [&] { ivf_search_device_impl(h, q_dev, nq, k, nullptr, nullptr, keys_dev, ids_dev, as_stream(stream)); });
-    });
+    return ivf_search_device_entry(hh, q_dev, nq, k, 4, nullptr, nullptr, keys_dev, ids_dev, stream);
 }
 
 // vdb_reserve: size the workspace of an nq-query, top-k search NOW (index build time) instead of inside the first search:

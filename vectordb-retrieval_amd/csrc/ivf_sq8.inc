@@ -4,7 +4,7 @@
 // copies: the codes [N][D4] in list order, the list of every list-order row, the int64 ids, and the centroids and
 // {vmin, vdiff} zero padded to D4, and (D <= 128) the panel-space bias and scales.  Every row is scored as its decoded x^
 // (refine.hpp, sq8_key); D <= 128 batches take the list-major MFMA scan on fp16 panels converted from the codes per search
-// (ivf_mfma_batch), D > 128 and small batches the exact list scan -- the result is the IVF-Flat result over x^ either way.
+// (ivf_search_lists), D > 128 and small batches the exact list scan -- the result is the IVF-Flat result over x^ either way.
 
 constexpr int64_t kSq8TrainRows = 100000;      // rows the range training reads at most (evenly spaced beyond that)
 
@@ -117,17 +117,14 @@ void sq8_build_panel_space(vdb_index_s *h) {
     h->rows.xnorm2.release();                                  // (the norms only fed the bias)
 }
 
-// vdb_ivf_add(_assigned) on an SQ8 handle: the same lists as ivf_add_impl (APPEND; stable by list, insertion order inside
-// a list), but the new rows are encoded as soon as they are on the device and only their codes are kept
+// vdb_ivf_add(_assigned) on an SQ8 handle: the same lists as ivf_add_impl (ivf_add_lists), but the new rows are encoded as
+// soon as they are on the device and only their codes are kept
 void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, const int32_t *given) {
     ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
     ivf_require(h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
     ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
-    const bool append = h->ivf_built && h->N > 0;
-    if (append) require_same_id_base(h, id_base);
-    if (append && n == 0) return;
-    const int64_t N0 = append ? h->N : 0, N1 = N0 + n;
-    ivf_require(N1 <= 2147483647ll - 1024, VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
+    int64_t N0, N1;
+    if (!ivf_add_range(h, n, id_base, N0, N1)) return;
     if (given)
         for (int64_t i = 0; i < n; ++i)
             ivf_require(given[i] >= 0 && given[i] < h->nlist, VDB_ERR_INVALID, "row could not be assigned to a list");
@@ -139,7 +136,7 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
     sq8_upload_params(h);
     std::vector<int64_t> assign_new((size_t)n);
     if (N1 > 0) {
-        DevBuf fresh, raw, dnew, src_codes, src_ids, dperm, dassign, doff;
+        DevBuf fresh, dnew, src_codes, src_ids, dperm, doff;
         src_codes.reserve((size_t)N1 * D4);
         if (N0) VDB_HIP(hipMemcpy(src_codes.p, h->codes.sq8_codes.p, (size_t)N0 * D4, hipMemcpyDeviceToDevice));
         if (n > 0) {
@@ -153,16 +150,7 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
                 for (int64_t i = 0; i < n; ++i) assign_new[(size_t)i] = given[i];
                 VDB_HIP(hipMemcpy(dnew.p, assign_new.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
             } else {
-                const float *unpadded = fresh.as<float>();
-                if (D4 != Dm) {
-                    raw.reserve((size_t)n * Dm * sizeof(float));
-                    VDB_HIP(hipMemcpy2D(raw.p, (size_t)Dm * 4, fresh.p, (size_t)D4 * 4, (size_t)Dm * 4, (size_t)n,
-                                        hipMemcpyDeviceToDevice));
-                    unpadded = raw.as<float>();
-                }
-                ivf_assign_rows(h, unpadded, n, dnew);
-                VDB_HIP(hipMemcpy(assign_new.data(), dnew.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-                raw.release();
+                ivf_add_assign(h, fresh.as<float>(), n, dnew, assign_new);
                 sq8_release_coarse_ws(h);
             }
             sq8_encode_kernel<<<dim3((unsigned)std::min<int64_t>((n * D4 + 255) / 256, 1 << 20)), dim3(256), 0, nullptr>>>(
@@ -173,23 +161,7 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
             fresh.release();
             dnew.release();
         }
-        // list of every source row: the stored rows are in list order (offsets), the new ones follow
-        std::vector<int64_t> assign_all((size_t)N1);
-        if (N0)
-            for (int l = 0; l < h->nlist; ++l)
-                std::fill(assign_all.begin() + h->ivf_offsets_host[(size_t)l], assign_all.begin() + h->ivf_offsets_host[(size_t)l + 1], (int64_t)l);
-        std::copy(assign_new.begin(), assign_new.end(), assign_all.begin() + N0);
-        dassign.reserve((size_t)N1 * 8);
-        VDB_HIP(hipMemcpy(dassign.p, assign_all.data(), (size_t)N1 * 8, hipMemcpyHostToDevice));
-        if (N0) {           // ids of the source rows: the stored ones keep theirs
-            std::vector<int64_t> ids_new((size_t)n);
-            for (int64_t i = 0; i < n; ++i) ids_new[(size_t)i] = h->id_base + N0 + i;
-            src_ids.reserve((size_t)N1 * 8);
-            VDB_HIP(hipMemcpy(src_ids.p, h->lists.ivf_ids.p, (size_t)N0 * 8, hipMemcpyDeviceToDevice));
-            if (n) VDB_HIP(hipMemcpy(src_ids.as<int64_t>() + N0, ids_new.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        }
-        ivf_csr_build(h, dassign, N1, h->nlist, dperm, doff, h->ivf_offsets_host);
-        dassign.release();
+        ivf_add_lists(h, assign_new, N0, src_ids, dperm, doff);
         h->codes.sq8_codes.reserve((size_t)N1 * D4);
         h->lists.ivf_ids.reserve((size_t)N1 * 8);
         const int64_t total = N1 * (D4 / 4);
@@ -203,15 +175,8 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
         h->codes.sq8_list.reserve((size_t)N1 * 4);
         VDB_HIP(hipMemcpy(h->codes.sq8_list.p, list_of.data(), (size_t)N1 * 4, hipMemcpyHostToDevice));
         VDB_HIP(hipDeviceSynchronize());
-    } else {
-        h->ivf_offsets_host.assign((size_t)h->nlist + 1, 0);
     }
-    h->N = N1;
-    h->id_base = id_base;
-    h->lists.ivf_offsets.reserve((size_t)(h->nlist + 1) * 8);
-    VDB_HIP(hipMemcpy(h->lists.ivf_offsets.p, h->ivf_offsets_host.data(), (size_t)(h->nlist + 1) * 8, hipMemcpyHostToDevice));
-    h->ivf_list_of_row.resize((size_t)N1);              // (in insertion order: the stored part stays)
-    for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
+    ivf_add_finish(h, assign_new, N0, id_base);
     sq8_build_panel_space(h);
     h->ivf_built = true;
 }
