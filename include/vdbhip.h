@@ -310,7 +310,9 @@ int vdb_reserve(vdb_handle h, int64_t nq, int k);
 
 /* ---- introspection / tuning ---------------------------------------------------------------- */
 int vdb_stats(vdb_handle h, vdb_stats_t *out);
-/* Options (vdb_set_option; every setting returns exact results unless it says otherwise):
+/* Options (vdb_set_option; every setting returns exact results unless it says otherwise).  A value outside what is listed is
+ * VDB_ERR_INVALID, an unknown name too; an option given as a list of values takes exactly those, one given as a range takes every
+ * number in it (truncated toward zero).  Every option named here is a row of kOptions (csrc/vdbhip.hip) and the other way round:
  *   behaviour
  *     "force_path"      0 auto | 1 exact kernels only | 2 MFMA scan whenever legal | 3 exact kernels, one query per wave
  *     "timing"          1: (re)start recording HIP-event times of every search on its stream, averaged by vdb_stats
@@ -327,6 +329,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       100M x 128 shard never exists in float32 inside the library).  Built by ONE add: appending is
  *                       VDB_ERR_UNSUPPORTED; a corpus that is not byte-valued silently gets the default layout
  *                       (vdb_stats.has_i8_copy tells: 2 = int8 only)
+ *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
+ *                       spans (tests: several blocks on a small corpus)
  *     "stream_panels"   D > 128, takes effect at the next vdb_add: 0 (default) the fp16 scan copy stays resident next to the
  *                       float32 rows | 1 it is NOT kept: every search converts the float32 rows slab by slab into one
  *                       scratch slab and scans that (same results; 1.8x -> ~1.15x the corpus bytes resident for a corpus that
@@ -350,6 +354,11 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       replay -- a runtime defect in graph packet capture, profiles/r04_graph_fault_cause.txt.)
  *     "lsh_force_fallback"  0 (default) | 1: every query of a vdb_lsh_candidates / vdb_lsh_search call takes the exact fallback
  *                       of the select (tests; same results)
+ *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
+ *                       kernels on the codes (0 = default .. 1e9)
+ *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)
+ *     "multi_stage_all" multi-device handles only (vdb_create_multi; every other option is forwarded to each shard, and "graph"
+ *                       = 1 is VDB_ERR_UNSUPPORTED there): 1 (tests) shards on devices[0] take the remote-shard path too
  *     "graph_recapture_at_once"  diagnostic, 0 (default) | 1: the pre-round-3 ordering, for re-checking that defect
  *                       ($VDBHIP_ALLOC_LOG=<file> logs every allocation / graph event for scripts/graph_fault_analyze.py)
  *   tuning knobs (scripts/sweep_*.py)
@@ -357,10 +366,10 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       per 1 / 2 tiles)
  *     "i8_group"        8 (default) | 4 rows per select group of the flat int8 scan
  *     "flat_shape"      (before vdb_add; alias "i8_shape") MFMA shape of the flat scans for D <= 128 and the layout of their scan
- *                       copies: 0 auto (16) | 16 | 32.  16 = v_mfma_f32_16x16x32_f16 / v_mfma_i32_16x16x64_i8 on layout "x16"
+ *                       copies: 0 auto (16) | 16 | 32.  16 = v_mfma_f32_16x16x32_f16 / v_mfma_i32_16x16x64_i8 on layout x16
  *                       (octs only; +17 - 19 % on the scans); 32 = the 32x32 kernels (also taken when an option asks for quads
  *                       -- "f16_group" / "i8_group" = 4)
- *     "scan_pair"       layout "x16", index with an int8 copy: 1 (default) both scans in one launch (the device picks the body), 0 two
+ *     "scan_pair"       layout x16, index with an int8 copy: 1 (default) both scans in one launch (the device picks the body), 0 two
  *                       launches (the one not needed returns at once) -- A/B and diagnosis
  *     "f16_stage_tiles" / "f16_wide" / "scan_prio"   tuning of the x16 kernels (tiles per LDS stage of the fp16 batch scan: 0 auto | 4 | 8;
  *                       1024-query workgroup tiles of the fp16 scan at D <= 64: 0 auto | 1 never; issue priority of one half of a
@@ -374,6 +383,7 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       (1024-row spans, 256-row bins) of the p16 panel space
  *     "ivf_group"       D > 128, 64-row bins: rows per candidate group of the list scan, 0 auto | 1 | 2 | 4 (smaller groups cost
  *                       select instructions in the scan and save gathered rows in the exact refine)
+ *     "ivf_i8_group"    4 (default) | 8 rows per candidate group of the int8 list scan (D <= 128, byte-valued corpus)
  *     "ivf_tile"        D > 128, 256-row spans: workgroup tile of the list scan, 0 auto / 2 = 256 rows x 256 query slots | 1 = 128 x 512
  *     "ivf_part"        0 auto | spans (256 rows) per row part of the IVF list scan: long lists are cut into parts
  *                       scanned by one workgroup each (rounded up to a multiple of 4 bins)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One fixed sequence of IVF searches through every branch of the IVF search host code (fp16 list scan: 4 / 8 k-steps, 64- /
-128-row bins, 2 / 4 / 8 waves; int8 list scan: integer and non-integer batches; K-loop: 256- and 1024-row spans, the square
-tile, groups of 1 / 2 / 4 rows; SQ8 at D <= 128 and D > 128; exact list scan with one and several splits; the flagged-query
+128-row bins, 2 / 4 / 8 waves; int8 list scan: integer and non-integer batches, and switched off by
+"panel_dtype"; K-loop: 256- and 1024-row spans, the square tile, groups of 1 / 2 / 4 rows; SQ8 at D <= 128 and D > 128; exact list scan with one and several splits; the flagged-query
 fallback; a second batch inside one call; partial results through a two-shard index; the plan with and without the LDS
 histogram), for a run under `rocprofv3 --kernel-trace --stats`: two builds of the library that enqueue the same work give
 the same kernel names and call counts.  Prints a running checksum of every result so that the outputs can be compared too.
@@ -59,7 +59,8 @@ for d in (64, 128):                          # fp16 list scan
         run("two_batches", idx, np.tile(Q, (56, 1))[:16500], 8, list_cap=0)
     idx.close()
 X, Qi = byte_rows(20000, 64), byte_rows(300, 64)          # int8 list scan
-idx = ivf(X, 64); run("i8_int", idx, Qi, 8); run("i8_float", idx, Qi + 3 * gauss(300, 64), 8); idx.close()
+idx = ivf(X, 64); run("i8_int", idx, Qi, 8); run("i8_float", idx, Qi + 3 * gauss(300, 64), 8)
+run("i8_off", idx, Qi, 8, panel_dtype=1); idx.close()
 X, Q = gauss(30000, 256), gauss(200, 256)                 # K-loop
 idx = ivf(X, 16, "ip", ivf_tps=64); run("kloop_tps64", idx, Q, 8); idx.close()
 idx = ivf(X, 16, "ip", ivf_tps=16)

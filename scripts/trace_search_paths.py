@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One fixed sequence of flat searches through every branch of search_batch (dense, exhaustive, MFMA scan: resident fp16,
-paired with int8, streamed slabs, int8-only slabs, PQ slabs; direct bins; serving shapes), for a run under
+paired with int8, streamed slabs, int8-only slabs, PQ slabs; direct bins; serving shapes; the options "scan_pair", "small_batch",
+"fused_stats" and "panel_dtype" at their non-default value), for a run under
 `rocprofv3 --kernel-trace --stats`: two builds of the library that enqueue the same work give the same kernel names and
 call counts.  Prints a checksum of every result so that the outputs can be compared as well.
 Usage: rocprofv3 --kernel-trace --stats -d DIR -- python scripts/trace_search_paths.py"""
@@ -50,10 +51,14 @@ idx.set_option("force_path", 0); idx.set_option("list_cap", 1); run("fallback", 
 X, Qi = byte_rows(40000, 128), byte_rows(1024, 128)
 Qf = Qi + gauss(1024, 128) * 3
 idx = flat(X); run("pair_int", idx, Qi, batches=(1024, 600, 64, 3)); run("pair_float", idx, Qf, ks=(10,))
-idx.set_option("scan_pair", 0); run("two_launches", idx, Qi, ks=(10,)); idx.close()
+idx.set_option("scan_pair", 0); run("two_launches", idx, Qi, ks=(10,)); idx.set_option("scan_pair", 1)
+for opt, off in (("small_batch", 0), ("fused_stats", 0), ("panel_dtype", 1)):      # each at its other value, the rest at their defaults
+    idx.set_option(opt, off); run(f"{opt}={off}", idx, Qi, batches=(64, 3), ks=(10,)); idx.set_option(opt, 1 - off)
+idx.close()
 idx = flat(X, flat_shape=32); run("i8_32", idx, Qi, ks=(10,)); idx.close()
 X, Q = gauss(47000, 136), gauss(600, 136)
-idx = flat(X, stream_panels=1, stream_slab_rows=20480); run("streamed", idx, Q); idx.close()
+idx = flat(X, stream_panels=1, stream_slab_rows=20480); run("streamed", idx, Q)
+idx.set_option("small_batch", 0); run("streamed_small_batch=0", idx, Q, batches=(64, 3), ks=(10,)); idx.close()
 X, Qi = byte_rows(40000, 50), byte_rows(600, 50)
 idx = flat(X, int8_only=1, int8_slab_chunks=3); run("int8_only_float", idx, Qi + gauss(600, 50) * 3); run("int8_only_int", idx, Qi, ks=(10,))
 cand = rng.integers(0, 40000, size=(20, 30)).astype(np.int64)

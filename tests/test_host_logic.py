@@ -409,3 +409,22 @@ def test_ivf_artifact_fingerprint_and_sampled_reassignment():
     assert not ivf._lists_match_sample(rng.standard_normal(X.shape).astype(np.float32), C, lists, "l2")
     ip = np.argmax(X.astype(np.float64) @ C.T.astype(np.float64), axis=1).astype(np.int32)
     assert ivf._lists_match_sample(X, C, ip, "ip") and not ivf._lists_match_sample(X, C, lists, "ip")
+
+
+def test_header_lists_every_option_of_the_table():
+    """The option list above vdb_set_option in include/vdbhip.h and the rows of kOptions (csrc/vdbhip.hip) name the same
+    options: every row is documented, and nothing is documented that the library would answer with `unknown option`."""
+    src = (ROOT / "vectordb-retrieval_amd" / "csrc" / "vdbhip.hip").read_text()
+    table = re.search(r"constexpr OptionRow kOptions\[\] = \{\n(.*?)\n\};", src, re.S)
+    assert table, "kOptions not found"
+    rows = re.findall(r'^\s*\{"([a-z0-9_]+)",', table.group(1), re.M)
+    assert len(rows) > 30 and len(rows) == len(set(rows)) == table.group(1).count("\n") + 1, rows
+    multi_only = {"graph", "multi_stage_all"}            # multi_set_option's own keys ("graph" is a row as well)
+    multi_src = (ROOT / "vectordb-retrieval_amd" / "csrc" / "multi.inc").read_text()
+    assert all(f'== "{name}"' in multi_src for name in multi_only)
+    header = (ROOT / "include" / "vdbhip.h").read_text()
+    comment = re.search(r"/\* Options \(vdb_set_option;.*?\*/\nint vdb_set_option\(", header, re.S)
+    assert comment, "the option list of include/vdbhip.h was not found"
+    documented = set(re.findall(r'"([a-z][a-z0-9_]*)"', comment.group(0)))
+    assert set(rows) <= documented, sorted(set(rows) - documented)
+    assert documented <= set(rows) | multi_only, sorted(documented - set(rows) - multi_only)

@@ -175,7 +175,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
     if (h->nonfinite) return;
     const int nlist = h->nlist;
     h->ivf_tps = 0;
-    if (h->tile16) h->ivf_tps = (h->ivf_tps_override == 16 || h->ivf_tps_override == 64) ? h->ivf_tps_override
+    if (h->tile16) h->ivf_tps = (h->opt.ivf_tps == 16 || h->opt.ivf_tps == 64) ? h->opt.ivf_tps
                                 : ((double)h->N / nlist > 2048.0 ? 64 : 16);
     const int span_rows = h->tile16 ? h->ivf_tps * 16 : kIvfSpanRows;
     h->ivf_span_rows = span_rows;
@@ -256,7 +256,7 @@ constexpr size_t kZeroSmall = (kSmallBytes + 127) / 128 * 128;     // stride of 
 
 IvfGeom ivf_geometry(const vdb_index_s *h, int64_t nb, int k, int nprobe) {
     IvfGeom g;
-    if (!h->ivf_mfma_ok || h->force_path == 1 || h->force_path == 3 || nb < h->ivf_min_batch || k > 256 || nprobe > kIvfMaxProbes) return g;
+    if (!h->ivf_mfma_ok || h->opt.force_path == 1 || h->opt.force_path == 3 || nb < h->opt.ivf_min_batch || k > 256 || nprobe > kIvfMaxProbes) return g;
     const int nlist = h->nlist;
     const double avg_pspans = (double)h->ivf_pspans / (double)nlist;
     const bool kloop = h->tile16;                                 // D > 128: ivf_kloop_scan_kernel on p16 panels
@@ -264,8 +264,8 @@ IvfGeom ivf_geometry(const vdb_index_s *h, int64_t nb, int k, int nprobe) {
     // query, else 64 rows (bt = 4)
     int bt = kIvfTilesPerSpan;
     if ((double)nprobe * (double)h->ivf_span_rows / 128.0 * avg_pspans < 8.0 * k) bt = 4;
-    if (h->ivf_bt == 4) bt = 4;                                    // option "ivf_bt" (A/B, both exact): 4, or 16 = the largest
-    else if (h->ivf_bt == 16) bt = kIvfTilesPerSpan;
+    if (h->opt.ivf_bt == 4) bt = 4;                                    // option "ivf_bt" (A/B, both exact): 4, or 16 = the largest
+    else if (h->opt.ivf_bt == 16) bt = kIvfTilesPerSpan;
     const int bps = kIvfTilesPerSpan / bt;
     // level-1 bins of a panel span and rows per bin (p16: one bin per lane group, fixed by the span size of the build)
     const int bins_per_span = kloop ? 4 : 2 * bps;
@@ -290,10 +290,10 @@ IvfGeom ivf_geometry(const vdb_index_s *h, int64_t nb, int k, int nprobe) {
             }
         }
     }
-    if (h->ivf_nw == 2 || h->ivf_nw == 4 || h->ivf_nw == 8) nw = h->ivf_nw;
+    if (h->opt.ivf_nw == 2 || h->opt.ivf_nw == 4 || h->opt.ivf_nw == 8) nw = h->opt.ivf_nw;
     // (K-loop scan: 8 waves share the A staging; 512 slots per item, or 256 with the square workgroup tile -- 256-row spans,
     //  option "ivf_tile" = 2; measured equal within 3 %, so 128 x 512 stays the default: ivf_kloop.hpp)
-    if (kloop) nw = (h->ivf_tps == 16 && h->ivf_tile == 2 ? kIvfKloopGroup / 2 : kIvfKloopGroup) / 64;
+    if (kloop) nw = (h->ivf_tps == 16 && h->opt.ivf_tile == 2 ? kIvfKloopGroup / 2 : kIvfKloopGroup) / 64;
     const int group = 64 * nw;
     const int64_t max_items = (pairs + group - 1) / group + std::min<int64_t>(nlist, pairs);
     const int64_t max_slots = max_items * group;
@@ -348,13 +348,13 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     const int64_t nb = b.nb;
     IvfLists L{};
     // rows per candidate group of the K-loop scan (option "ivf_group": 0 auto, 1, 2, 4): 64-row bins can name single rows
-    L.kgroup = (b.g.kloop && h->ivf_tps == 16) ? (h->ivf_group > 0 ? h->ivf_group : kIvfKloopGroupRows) : 4;
+    L.kgroup = (b.g.kloop && h->ivf_tps == 16) ? (h->opt.ivf_group > 0 ? h->opt.ivf_group : kIvfKloopGroupRows) : 4;
     // (five minima per bin: a dense bin hands over up to four candidate quads instead of one re-scan)
-    L.cand_cap = h->list_cap > 0 ? h->list_cap : (b.g.kloop ? std::max(96, 4 * k + 32) : std::max(64, 2 * k + 32));
+    L.cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : (b.g.kloop ? std::max(96, 4 * k + 32) : std::max(64, 2 * k + 32));
     L.rescan_cap = std::max(16, k / 2 + 8);
     ws.eps.reserve((size_t)nb * sizeof(float));
     ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
-    L.use_i8 = h->i8_ok && !h->i8_disable && h->scan.panels8.p != nullptr;
+    L.use_i8 = h->i8_ok && !h->opt.panel_dtype && h->scan.panels8.p != nullptr;
     if (L.use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);        // int8 query rows
     ws.bin_m1.reserve(b.g.bin_bytes);
     ws.bin_m2.reserve(b.g.bin_bytes);
@@ -396,7 +396,7 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
     const int Dm = h->dim;
     const int64_t nb = b.nb, total = nb * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                           L.use_i8 ? (1 | (h->ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see ivf_scan_i8)
+                           L.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see ivf_scan_i8)
     const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
     if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, b.st>>>(b.q, total, L.info, fin);
     IvfPrepArgs pa{};
@@ -458,7 +458,7 @@ const half8 *ivf_sq8_panels(const IvfBatch &b) {
 // empty workgroups.  Returns the part size (0 = whole lists) and the grid
 struct IvfParts { int part_spans; dim3 grid; };
 IvfParts ivf_part_spans(const vdb_index_s *h, int64_t max_items, int base, int unit = 1) {
-    int part = std::min(std::max(h->ivf_part > 0 ? h->ivf_part : base, (h->ivf_max_pspans + 63) / 64), h->ivf_max_pspans);
+    int part = std::min(std::max(h->opt.ivf_part > 0 ? h->opt.ivf_part : base, (h->ivf_max_pspans + 63) / 64), h->ivf_max_pspans);
     part = (part + unit - 1) / unit * unit;
     const int part_spans = part >= h->ivf_max_pspans ? 0 : part;
     return {part_spans, dim3((unsigned)max_items, (unsigned)(part_spans ? (h->ivf_max_pspans + part - 1) / part : 1))};
@@ -544,8 +544,8 @@ void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa, dim3 grid) {
     //  probed lists are dense in near neighbours, so an 8-row group drags in more re-scans and twice the rows)
     // staging ring of the work items (option "i8_ring"; 0 = auto): a work item streams its list once, and few of them
     // are resident per CU -- 4 stages of 2 (4 at two k-steps) tiles in flight instead of 1
-#define VDB_IVF_SCAN8(KS, ST, NW, BT) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
-    if (h->ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
+#define VDB_IVF_SCAN8(KS, ST, NW, BT) do { const int r__ = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring; \
+    if (h->opt.ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
     else if (r__ == 2) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
     else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
     else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
@@ -897,8 +897,8 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
         if (codec == 1) lsh_refuse_ivf(h);
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
         if (codec == 1) {
-            ivf_require(!h->graph_mode, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");
-            ivf_require(!h->int8_only_opt && !h->stream_panels_opt, VDB_ERR_UNSUPPORTED,
+            ivf_require(!h->opt.graph, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");
+            ivf_require(!h->opt.int8_only && !h->opt.stream_panels, VDB_ERR_UNSUPPORTED,
                         "options 'int8_only' and 'stream_panels' do not combine with the SQ8 codec");
         }
         h->ivf_codec = codec;

@@ -12,9 +12,9 @@ void lsh_refuse_handle(const vdb_index_s *h) {
     if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
         throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF index (centroids set or a codec chosen): its rows "
                                          "sit in list order");
-    if (h->int8_only_opt || h->int8_only)
+    if (h->opt.int8_only || h->int8_only)
         throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes need the resident float32 rows: not available with option 'int8_only'");
-    if (h->stream_panels_opt || h->panels_streamed)
+    if (h->opt.stream_panels || h->panels_streamed)
         throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available with option 'stream_panels'");
 }
 
@@ -53,7 +53,7 @@ void lsh_require_ready(vdb_index_s *h, const char *what) {
     if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a PQ index");
     if (!lsh_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no projection (call vdb_lsh_set_projection first)");
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
-    if (h->graph_mode) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
+    if (h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
     if (h->lsh_rows != h->N) throw Error(VDB_ERR_STATE, "the LSH codes do not cover the rows of this index (a failed add?): vdb_reset and add again");
 }
 
@@ -111,7 +111,7 @@ void lsh_candidates_core(vdb_index_s *h, const float *dq, int64_t nq, int ncand,
     a.ncand = ncand;
     a.sample_n = std::min<int64_t>(h->N, kLshSampleMax);                       // (N <= the sample: all rows, exact histogram)
     a.sample_stride = a.sample_n == h->N ? 256 : h->N / (kLshSampleMax / 256);  // first rows of consecutive 256-row runs
-    a.force_fallback = h->lsh_force_fallback;
+    a.force_fallback = h->opt.lsh_force_fallback;
     a.id_base = h->id_base;
     a.hist = h->lsh_ws.lsh_hist.as<int>();
     a.thi = h->lsh_ws.lsh_small.as<int>();

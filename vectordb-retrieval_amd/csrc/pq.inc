@@ -19,9 +19,9 @@ void pq_refuse_handle(const vdb_index_s *h, const char *what) {
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index (IVF<nlist>,PQ<M> is not implemented)");
     if (h->lsh_nbits > 0)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a sign-LSH projection");
-    if (h->int8_only_opt || h->stream_panels_opt || h->graph_mode)
+    if (h->opt.int8_only || h->opt.stream_panels || h->opt.graph)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'int8_only', 'stream_panels' and 'graph'");
-    if (h->flat_shape_opt == 32 || h->f16_group != 8 || h->i8_group != 8)
+    if (h->opt.flat_shape == 32 || h->opt.f16_group != 8 || h->opt.i8_group != 8)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'flat_shape' = 32, 'f16_group' = 4 and 'i8_group' "
                                          "= 4: the panels of a PQ index are made in layout \"x16\" (octs) only");
 }

@@ -22,8 +22,8 @@ ScanGeom scan_geometry(const vdb_index_s *h, int k, int64_t nq) {
     if (spc_hi < 1 || spc_hi < spc_lo) return g;
     int64_t spc_want = 32 / G;                              // 8192 rows per chunk
     // (one query tile only: from 1024 queries on the batch shape is as fast or faster -- scripts/throughput_vs_batch.py)
-    if (nq <= 512 && !h->small_batch_off) spc_want = std::max<int64_t>(1, std::min<int64_t>(spc_want, g.nspans / 512));
-    int64_t spc = std::min<int64_t>(h->spc_override > 0 ? h->spc_override : spc_want, spc_hi);
+    if (nq <= 512 && h->opt.small_batch) spc_want = std::max<int64_t>(1, std::min<int64_t>(spc_want, g.nspans / 512));
+    int64_t spc = std::min<int64_t>(h->opt.spans_per_chunk > 0 ? h->opt.spans_per_chunk : spc_want, spc_hi);
     spc = std::max<int64_t>(spc, spc_lo);
     if (spc < 2 && g.nspans * G >= 128) spc = std::min<int64_t>(2, spc_hi);
     int64_t nchunks = (g.nspans + spc - 1) / spc;
@@ -37,7 +37,7 @@ ScanGeom scan_geometry(const vdb_index_s *h, int k, int64_t nq) {
     // length buy that for corpora of up to 2M rows
     {
         const int64_t cap = 256 / G;
-        if (nq > 512 && h->spc_override == 0 && nchunks > cap && nchunks <= 2 * cap && cap * G >= 4 * (int64_t)k) nchunks = cap;
+        if (nq > 512 && h->opt.spans_per_chunk == 0 && nchunks > cap && nchunks <= 2 * cap && cap * G >= 4 * (int64_t)k) nchunks = cap;
     }
     g.nchunks = (int)nchunks;
     g.spc = (int)(g.nspans / nchunks);
@@ -108,17 +108,17 @@ void launch_scan_k(ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int 
 // candidate groups of the fp16 flat scan (D <= 128, 256-row bins): octs unless option "f16_group" = 4
 bool f16_octs(const vdb_index_s *h, int direct_rows) {
     if (h->x16) return !direct_rows;  // (layout "x16": octs; direct-bin mode -- large k, the refine outweighs the scan -- takes the quads of the two blocks)
-    return h->f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps;
+    return h->opt.f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps;
 }
 
-inline int st_tiles_of(const vdb_index_s *h) { return h->f16_stage_tiles ? h->f16_stage_tiles : (h->ksteps == 4 ? 8 : 4); }
+inline int st_tiles_of(const vdb_index_s *h) { return h->opt.f16_stage_tiles ? h->opt.f16_stage_tiles : (h->ksteps == 4 ? 8 : 4); }
 
 void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int direct_rows = 0, int nw = 8) {
     const int bt = direct_rows ? direct_rows / 16 : 16;       // 32-row-tile layout: tiles per level-1 bin
     if (h->ksteps > kMaxKSteps) {  // D > 128: p16 panels, 512-query tiles
         // option kloop_qgroup = query tiles per group of the block order (0 -> default)
         sa.nqtiles = (int)(Qpad / 512);
-        int qgroup = h->kloop_qgroup > 0 ? h->kloop_qgroup : 4;
+        int qgroup = h->opt.kloop_qgroup > 0 ? h->opt.kloop_qgroup : 4;
         qgroup = std::min(qgroup, sa.nqtiles);
         const unsigned ngroups = (unsigned)((sa.nqtiles + qgroup - 1) / qgroup);
         const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * ngroups * (unsigned)qgroup;
@@ -129,9 +129,9 @@ void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStr
             VDB_HIP(hipGetLastError());
             return;
         }
-        if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && !h->small_batch_off)
+        if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && h->opt.small_batch)
             scan16_kloop_kernel<3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-        else if (sa.nq_valid > 0 && sa.nq_valid < 64 && !h->small_batch_off)
+        else if (sa.nq_valid > 0 && sa.nq_valid < 64 && h->opt.small_batch)
             scan16_kloop_kernel<2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
         else
             scan16_kloop_kernel<2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
@@ -139,7 +139,7 @@ void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStr
         const bool small = direct_rows == 0 && nw < 8;
         // D <= 64, batch shape: 1024-query workgroup tiles (8 column blocks = 128 queries per wave) when the batch is a multiple of 1024
         // and there are enough of them to cover the chip -- the rule of the int8 scan (option "f16_wide": 0 auto, 1 never)
-        const bool wide = !small && direct_rows == 0 && h->ksteps == 4 && h->f16_wide != 1 && Qpad % 1024 == 0 &&
+        const bool wide = !small && direct_rows == 0 && h->ksteps == 4 && h->opt.f16_wide != 1 && Qpad % 1024 == 0 &&
                           (int64_t)nchunks * (Qpad / 1024) >= 256;
         // tiles per LDS stage of the batch shape (option "f16_stage_tiles"): measured on the bench shapes (profiles/r04_sweeps.txt) D = 64:
         // 8 tiles 1.108 ms against 1.163 with 4 (a 4-tile stage is only 16 KiB of panels per barrier); D = 128: 1.730 against 1.722
@@ -176,7 +176,7 @@ void launch_select(const SelectArgs &a, hipStream_t st) {
 }
 
 long timing_begin(vdb_index_s *h, hipStream_t st) {
-    if (!h->timing || h->ev_used >= kMaxTimedCalls) return -1;
+    if (!h->opt.timing || h->ev_used >= kMaxTimedCalls) return -1;
     const size_t slot = h->ev_used++;
     while (h->ev_scan.size() < 2 * (slot + 1)) {
         hipEvent_t e;
@@ -251,7 +251,7 @@ void search_dense(const Batch &b) {
     QueryBatchInfo *info = batch_info(ws);          // (zeroed with fb_count above)
     const int64_t total = nq * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0};
-    const bool fused_stats = total <= kFusedStatsMax && !h->no_fused_stats;     // (serving shapes: statistics inside the prep kernel)
+    const bool fused_stats = total <= kFusedStatsMax && h->opt.fused_stats;     // (serving shapes: statistics inside the prep kernel)
     if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
     h->info_valid_nq = nq;
     const int64_t threads = (Qp / 32) * h->ksteps * 64;
@@ -371,7 +371,7 @@ void search_exact(const Batch &b) {
     const int64_t nq = b.nq;
     hipStream_t st = b.st;
     const int k = b.k;
-    bool blocked = kpl_for(k) <= 2 && nq >= 2 * kRefineQB && h->force_path != 3;
+    bool blocked = kpl_for(k) <= 2 && nq >= 2 * kRefineQB && h->opt.force_path != 3;
     if (blocked) {
         const int64_t g4 = (nq + kRefineQB - 1) / kRefineQB;
         const int64_t s4 = std::min<int64_t>((4096 + g4 - 1) / g4, std::max<int64_t>(1, h->N / 2048));
@@ -429,8 +429,8 @@ void scan_query_prep(const Batch &b, int64_t Qpad, bool use_i8, QueryBatchInfo *
     hipStream_t st = b.st;
     const int64_t total = nq * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                           use_i8 ? (1 | ((h->i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only)
-    const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && !h->no_fused_stats;   // (serving shapes, scan_i8.hpp)
+                           use_i8 ? (1 | ((h->opt.i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only)
+    const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;   // (serving shapes, scan_i8.hpp)
     if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
     h->info_valid_nq = nq;
     EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
@@ -516,7 +516,7 @@ void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pa
         // chip for most of a round (measured, 10 000 queries = 20 workgroups per chunk: 16-chunk slabs 14.5 ms per launch,
         // 25-chunk slabs -- four chunks on XCD 0 -- 23 ms).  Take the largest chunk count within `slab_rows` whose workgroups
         // fill whole rounds; small query batches (few workgroups per chunk) go by rows alone.
-        const int64_t slab_rows = h->stream_slab_rows > 0 ? h->stream_slab_rows : 1280000;
+        const int64_t slab_rows = h->opt.stream_slab_rows > 0 ? h->opt.stream_slab_rows : 1280000;
         int64_t slab_chunks = std::max<int64_t>(1, slab_rows / chunk_rows);
         for (int r = 8; r >= 1; --r) {                       // (chunk c of a launch runs on XCD c % 8: count per XCD)
             const int64_t fit = 8 * ((int64_t)2 * (h->n_cus / 8) * r / wgs_per_chunk);
@@ -535,7 +535,7 @@ void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pa
         // with `panels` rebased.  The slab is small by default (option "int8_slab_chunks", 8 chunks = 16 MiB at D = 128): it is
         // resident whether or not a non-integer batch ever comes.
         const int64_t tiles_per_span = kTilesPerSpan;
-        const int64_t slab_chunks = std::max<int64_t>(1, std::min<int64_t>(h->int8_slab_chunks > 0 ? h->int8_slab_chunks : 8, g.nchunks));
+        const int64_t slab_chunks = std::max<int64_t>(1, std::min<int64_t>(h->opt.int8_slab_chunks > 0 ? h->opt.int8_slab_chunks : 8, g.nchunks));
         const int64_t max_spans = (int64_t)(g.spc + 1) * slab_chunks;
         if (h->scan.slab.cap < (size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8))
             h->scan.slab.reserve_exact((size_t)max_spans * tiles_per_span * h->ksteps * 64 * sizeof(half8));
@@ -552,11 +552,11 @@ void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pa
         const int64_t tiles_per_span = h->tile16 ? kTilesPerSpan16 : kTilesPerSpan;
         const int64_t ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;
         const int64_t chunk_rows = (int64_t)(g.spc + 1) * (h->tile16 ? kSpanRows16 : kSpanRows);
-        int64_t slab_chunks = h->pq_slab_chunks > 0 ? h->pq_slab_chunks : std::max<int64_t>(1, kPqSlabRows / chunk_rows);
+        int64_t slab_chunks = h->opt.pq_slab_chunks > 0 ? h->opt.pq_slab_chunks : std::max<int64_t>(1, kPqSlabRows / chunk_rows);
         slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
         // (default size: the slab is allocated for its full 524 288 rows whatever the corpus holds -- the workspace of a search does
         //  not depend on N; vdb_stats counts it in bytes_workspace)
-        const int64_t max_spans = h->pq_slab_chunks > 0 ? (int64_t)(g.spc + 1) * slab_chunks
+        const int64_t max_spans = h->opt.pq_slab_chunks > 0 ? (int64_t)(g.spc + 1) * slab_chunks
                                                         : std::max<int64_t>(kPqSlabRows, chunk_rows) / (h->tile16 ? kSpanRows16 : kSpanRows);
         const size_t slab_bytes = (size_t)max_spans * tiles_per_span * ksl * 64 * sizeof(half8);
         if (h->scan.slab.cap < slab_bytes) h->scan.slab.reserve_exact(slab_bytes);
@@ -582,25 +582,25 @@ void scan_i8(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair
     s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
     s8.sb_m1 = sa.sb_m1; s8.sb_m2 = sa.sb_m2; s8.sb_span = sa.sb_span;
     s8.nspans = g.nspans; s8.Npad = h->Npad; s8.Qpad = Qpad; s8.nq_valid = nq;
-    s8.prio = h->scan_prio;
+    s8.prio = h->opt.scan_prio;
     s8.spans_per_chunk = g.spc; s8.chunk_rem = g.rem; s8.nchunks = g.nchunks;
     // i8_variant (tuning, every variant exact; scripts/sweep_i8.py): 0 = 512-query tiles (2 column blocks per wave),
     // 4-tile stages; 1 = 8-tile stages; 2 = 1024-query tiles (4 column blocks per wave); 3 = both (default);
     // 4 / 5 = 16 waves per workgroup (4 per SIMD) with 8- / 16-tile stages.  Odd batch sizes keep 512-query tiles.
-    int v8 = h->i8_variant;
+    int v8 = h->opt.i8_variant;
     if (h->x16) {
         // layout "x16" (scan_i8x16.hpp, v_mfma_i32_16x16x64_i8): the same launch shapes -- batch: 512- or 1024-query tiles
         // (4 or 8 column blocks of 16 queries per wave), 4- or 8-tile stages (i8_variant bits as below, 4 / 5 -> 3);
         // serving: 1 / 2 / 4 waves of 64 queries, 4-stage staging ring (option "i8_ring": 2, 4, 8), non-temporal loads
-        int v = h->i8_variant & 3;
-        if (h->i8_variant == 4 || h->i8_variant == 5) v = 3;
+        int v = h->opt.i8_variant & 3;
+        if (h->opt.i8_variant == 4 || h->opt.i8_variant == 5) v = 3;
         if (Qpad % 1024 != 0) v &= 1;
         if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v &= 1;
         const int qtile = nw_small < 8 ? 64 * nw_small : (v >= 2) ? 1024 : 512;
         s8.nqtiles = (int)((nw_small < 8 ? nq + qtile - 1 : Qpad) / qtile);
         const dim3 gridx(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-        const bool nt = h->i8_nt != 1;
-        const int ring = h->i8_ring == 0 ? 4 : h->i8_ring;
+        const bool nt = h->opt.i8_nt != 1;
+        const int ring = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring;
 #define VDB_X16B(KS2_) do { \
             if (v == 3) scan_i8x16_kernel<KS2_, 8, 8><<<gridx, dim3(512), 0, st>>>(s8); \
             else if (v == 2) scan_i8x16_kernel<KS2_, 4, 8><<<gridx, dim3(512), 0, st>>>(s8); \
@@ -651,22 +651,22 @@ void scan_i8(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair
     s8.nqtiles = (int)((v8 > 8 ? nq + qtile - 1 : Qpad) / qtile);
     const dim3 grid8(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
 #define VDB_I8G(KS_, ST_, CB_, NW_, G_) scan_i8_kernel<KS_, ST_, CB_, NW_, 16, false, G_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8)
-#define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
+#define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->opt.i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
     // serving shapes (1 / 2 / 4 waves per workgroup): the scan streams the copy once -- 4- or 8-stage staging ring
     // (option "i8_ring": 0 = auto (4), 2 = the double buffer of the batch shape, 4, 8)
-#define VDB_I8R(KS_, NW_, R_) do { if (h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+#define VDB_I8R(KS_, NW_, R_) do { if (h->opt.i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
                                else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
     // (the wait for a stage is s_waitcnt vmcnt((ring - 2) x requests per wave and stage), a 6-bit counter: a one-wave
     //  workgroup issues all 16 + 2 requests of a 4-tile stage itself, which caps its ring at 4)
-#define VDB_I8S(KS_, NW_) do { const int r__ = h->i8_ring == 0 ? 4 : h->i8_ring; \
+#define VDB_I8S(KS_, NW_) do { const int r__ = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring; \
                            if (r__ == 2) VDB_I8(KS_, 4, 2, NW_); else if (r__ == 8) VDB_I8R(KS_, NW_, (NW_ >= 2 ? 8 : 4)); \
-                           else if (nt8 && h->i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
+                           else if (nt8 && h->opt.i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
                            else VDB_I8R(KS_, NW_, 4); } while (0)
     // serving shapes read every panel byte once per search: non-temporal staging loads (option "i8_nt": 0 / 2 on, 1 off).
     // Measured in one process (scripts/sweep_serving_hbm.py): single-query scan of 4M x 128 (512 MB, HBM) 106.2 -> 96.7 us
     // = 4.8 -> 5.3 TB/s; of 1M x 128 (128 MB, Infinity-Cache resident between searches) 33.9 -> 33.3 us
-    const bool nt8 = h->i8_nt != 1;
-    if (tb8 && v8 == 3 && h->i8_group == 8) {
+    const bool nt8 = h->opt.i8_nt != 1;
+    if (tb8 && v8 == 3 && h->opt.i8_group == 8) {
         if (h->i8_ks == 2) {
             if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
             else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
@@ -734,9 +734,9 @@ SelectArgs scan_select(const Batch &b, const ScanArgs &sa, int64_t Qpad, int can
     se.fb_count = b.fb_count;
     se.stat_counters = b.stat_counters;
     const int nsb_i = G * g.nchunks;
-    if (nsb_i > 128 && nsb_i <= 256 && h->select_variant == 2 && !b.direct_rows) {   // 32 lanes per query, 2 queries per wave
+    if (nsb_i > 128 && nsb_i <= 256 && h->opt.select_variant == 2 && !b.direct_rows) {   // 32 lanes per query, 2 queries per wave
         select_kernel_v2<8, 32><<<dim3((unsigned)((nq + 7) / 8)), dim3(256), 0, st>>>(se);
-    } else if (nsb_i <= 256 && h->select_variant != 1 && !b.direct_rows) {  // multi-lane form: 16 lanes per query, 4 queries per wave
+    } else if (nsb_i <= 256 && h->opt.select_variant != 1 && !b.direct_rows) {  // multi-lane form: 16 lanes per query, 4 queries per wave
         const unsigned sgrid = (unsigned)((nq + 15) / 16);
         if (nsb_i <= 64)
             select_kernel_v2<4, 16><<<dim3(sgrid), dim3(256), 0, st>>>(se);
@@ -817,10 +817,10 @@ void search_scan(const Batch &b) {
     const int64_t Qpad = (nq + 511) / 512 * 512;
     const int G = h->tile16 ? 4 : 2;
     const int64_t nbins = g.nspans * G * (b.direct_rows ? kBinRows / b.direct_rows : 1), nsb = (int64_t)g.nchunks * G;
-    const int cand_cap = h->list_cap > 0 ? h->list_cap : std::max(64, 2 * k + 32);
+    const int cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : std::max(64, 2 * k + 32);
     const int rescan_cap = std::max(16, k / 2 + 8);
     // int8 scan for byte-valued corpora: offered to the device-side choice whenever the standard geometry is in use
-    const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
+    const bool i8_off = h->opt.panel_dtype && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
     const bool use_i8 = h->i8_ok && !i8_off && !b.direct_rows && !h->tile16;
     ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
     ws.eps.reserve((size_t)nq * sizeof(float));
@@ -854,14 +854,14 @@ void search_scan(const Batch &b) {
     sa.nchunks = g.nchunks;
     sa.Qpad = Qpad;
     sa.nq_valid = nq;
-    sa.prio = h->scan_prio;
+    sa.prio = h->opt.scan_prio;
     timing_mark(h, b.tslot, 0, st);
     // small batches: as many waves per workgroup as there are 64-query column groups (1, 2, 4; 8 = the batch shape)
-    const int nw_small = h->small_batch_off ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
+    const int nw_small = !h->opt.small_batch ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
     // layout "x16" with both scan copies resident: ONE launch holds both scans (scan_pair_x16_kernel, scan_x16.hpp) when every tuning
     // option is at its default; otherwise (and on the 32-row layout) both are enqueued and the one not needed returns at once
     const bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && b.direct_rows == 0 &&
-                          !h->scan_pair_off && h->i8_ring == 0 && h->i8_nt == 0 && h->f16_stage_tiles == 0 && h->i8_variant == 3;
+                          h->opt.scan_pair && h->opt.i8_ring == 0 && h->opt.i8_nt == 0 && h->opt.f16_stage_tiles == 0 && h->opt.i8_variant == 3;
     scan_fp16(b, sa, Qpad, nw_small, pair_candidate);
     if (use_i8) scan_i8(b, sa, Qpad, nw_small, pair_candidate);
     timing_mark(h, b.tslot, 1, st);
@@ -887,7 +887,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     }
     RefineCommon rc = flat_rows(h, qpad, k);
     rc.info = batch_info(ws);                             // (group size of the candidates: 4 rows, 8 on the int8 scan)
-    const bool i8_off = h->i8_disable && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
+    const bool i8_off = h->opt.panel_dtype && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
     if (h->i8_ok && h->scan.rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
         rc.X8 = h->scan.rows8.as<signed char>();
         rc.rowstat = h->scan.rowstat8.as<int>();
@@ -900,8 +900,8 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 
     ScanGeom g;
     // (PQ: a batch below "pq_scan_min_batch" takes the exact kernels on the codes instead of decoding the corpus for it -- DESIGN 4.9)
-    const bool pq_small = pq_on(h) && h->force_path != 2 && nq < (h->pq_scan_min_batch > 0 ? h->pq_scan_min_batch : kPqScanMinBatch);
-    const bool exact_only = h->force_path == 1 || h->force_path == 3 || pq_small;   // 3: also without query blocking (A/B runs)
+    const bool pq_small = pq_on(h) && h->opt.force_path != 2 && nq < (h->opt.pq_scan_min_batch > 0 ? h->opt.pq_scan_min_batch : kPqScanMinBatch);
+    const bool exact_only = h->opt.force_path == 1 || h->opt.force_path == 3 || pq_small;   // 3: also without query blocking (A/B runs)
     bool use_scan = h->scan_ok && !exact_only && k <= 1024;
     int direct_rows = 0;
     if (use_scan) {
@@ -913,7 +913,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     // Between the dense small-corpus path (<= 8192 rows) and 32768 rows the scan pays off once the batch carries
     // enough (query, row) pairs: ~0.3 ms of fixed pipeline cost against ~7e-8 ms per pair in the exhaustive kernel.
     use_scan = use_scan && g.ok &&
-               (h->force_path == 2 || h->N >= 32768 || (h->Npad > 8192 && (double)nq * (double)h->N >= 4.0e6));
+               (h->opt.force_path == 2 || h->N >= 32768 || (h->Npad > 8192 && (double)nq * (double)h->N >= 4.0e6));
     // (corpora of 8193..15360 rows whose chunking cannot give 4k superbins still have the dense path below)
 
     h->info_valid_nq = -1;
@@ -925,7 +925,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     if (h->small_clear_pending) {
         h->small_clear_pending = false;
         h->small_is_clean = false;
-        clear_in_prep = use_scan && nq * Dm <= kFusedStatsMax && !h->tile16 && !h->no_fused_stats;
+        clear_in_prep = use_scan && nq * Dm <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;
         if (!clear_in_prep) VDB_HIP(hipMemsetAsync(ws.small.p, 0, kSmallBytes, st));
     } else if (h->small_is_clean) h->small_is_clean = false;      // the first batch of a call: search_device_impl has just cleared all of it
     else VDB_HIP(hipMemsetAsync(ws.small.p, 0, 64, st));
@@ -977,7 +977,7 @@ constexpr int64_t kGraphMaxQueries = 4096;
 
 template <class F>
 void graph_or_run(vdb_index_s *h, const vdb_index_s::GraphKey &key, F &&run) {
-    const bool eligible = h->graph_mode && key.st != nullptr && !h->timing && key.nq > 0 && key.nq <= kGraphMaxQueries;
+    const bool eligible = h->opt.graph && key.st != nullptr && !h->opt.timing && key.nq > 0 && key.nq <= kGraphMaxQueries;
     if (!eligible) {
         run();
         return;
@@ -998,7 +998,7 @@ void graph_or_run(vdb_index_s *h, const vdb_index_s::GraphKey &key, F &&run) {
         graph_drop_exec(h);
         h->graph_key = vdb_index_s::GraphKey{};
         h->graph_warm = vdb_index_s::GraphKey{};
-        if (h->graph_recapture_at_once && same_key) h->graph_warm = key;     // (diagnostic: the old ordering)
+        if (h->opt.graph_recapture_at_once && same_key) h->graph_warm = key;     // (diagnostic: the old ordering)
     }
     if (!(key == h->graph_warm)) {
         run();
@@ -1075,7 +1075,7 @@ void search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, floa
     h->ws.small.reserve(kSmallBytes);
     h->small_clear_pending = false;
     if (h->small_preset) h->small_preset = false;        // (an IVF parent cleared it together with its own buffers)
-    else if (nq <= kBatch && nq * h->dim <= kFusedStatsMax && !h->no_fused_stats && !h->tile16)
+    else if (nq <= kBatch && nq * h->dim <= kFusedStatsMax && h->opt.fused_stats && !h->tile16)
         h->small_clear_pending = true;                   // serving-shaped call: the first batch's prep kernel clears it (search_batch), or a memset there
     else VDB_HIP(hipMemsetAsync(h->ws.small.p, 0, kSmallBytes, st));
     h->small_is_clean = true;

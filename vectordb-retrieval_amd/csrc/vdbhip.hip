@@ -223,6 +223,59 @@ struct Workspace {
     DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8: the fp16 panels converted from the codes for the current batch
 };
 
+// ---- options -----------------------------------------------------------------------------------------------------------------
+// Everything vdb_set_option writes and nothing else: one member per option, under the name the caller passes, holding the
+// value the caller passed; the initializer is the value of an option never set.  What the library derives from an option at
+// the next add (int8_only, panels_streamed, x16, ivf_tps ...) is state of vdb_index_s.  kOptions (in front of vdb_set_option)
+// has one row per member: what each accepts is written there, what each does in include/vdbhip.h.
+struct Options {
+    // behaviour
+    int force_path = 0, timing = 0, list_cap = 0;
+    int panel_dtype = 0;                     // 1: the int8 scan copy is not used (NOT inverted: non-zero switches the int8 scan off)
+    // "int8_only" (takes effect at the next add; flat index, D <= 128, > 32768 rows, byte-valued corpus): only the int8 copies
+    // are kept -- rows8 + panels8 + their biases, 0.55x the float32 corpus instead of 3x.  Integer query batches run as on the
+    // default index; a batch with a non-integer value is scanned in fp16 over slabs converted from the int8 panels per search;
+    // the exact kernels read x = byte + cx from the int8 rows (same float64 chains, same keys).  One add builds it (no append).
+    int int8_only = 0;
+    int int8_slab_chunks = 0;                // scan chunks per converted fp16 slab (0 = default 8)
+    int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests)
+    // "stream_panels" (D > 128, takes effect at the next add): the fp16 panels are NOT kept -- every search converts the
+    // float32 rows slab by slab into one scratch slab and scans it (search_flat.inc).  Halves the footprint of a non-fp16-exact
+    // corpus (the float32 rows must stay for the exact refine) at the price of one conversion pass per batch.
+    int stream_panels = 0;
+    int64_t stream_slab_rows = 0;            // rows of that slab (0 = default); the one option without an upper bound
+    int upload_block_mb = 0;                 // staging block of upload_rows (0 = default 64 MiB)
+    int small_batch = 1;                     // 0: batches <= 512 queries keep the batch-shaped grid
+    int fused_stats = 1;                     // 0 (A/B): small batches keep the separate statistics dispatch
+    int ivf_min_batch = 1;                   // smallest query batch the list-major MFMA scan serves
+    // "graph": a device-resident search that repeats with the same shape and buffers (a serving loop) is captured into a
+    // hipGraph on its second call and replayed from the third (graph_or_run)
+    int graph = 0;
+    int graph_recapture_at_once = 0;         // diagnostic: the pre-round-3 ordering (see graph_or_run)
+    int lsh_force_fallback = 0;              // every query of an LSH call takes the exact fallback of the select
+    int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
+    int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
+    // tuning of the flat scans
+    int i8_variant = 3;                      // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)
+    int i8_group = 8, f16_group = 8;         // rows per select group of the int8 / fp16 flat scan (4 or 8)
+    int flat_shape = 0;                      // (alias "i8_shape"; before vdb_add) MFMA shape of the flat scans for D <= 128: 0 auto (16) | 16 | 32
+    int scan_pair = 1;                       // 0: never the paired launch of the two x16 scans (A/B, diagnosis)
+    int scan_prio = 0;                       // x16 kernels: issue priority of one half of the workgroup's waves
+    int f16_wide = 0;                        // x16 fp16 batch scan, D <= 64: 0 auto (1024-query tiles when they fit), 1 never
+    int f16_stage_tiles = 0;                 // x16 fp16 batch scan: tiles per LDS stage, 0 auto | 4 | 8
+    int i8_nt = 0;                           // non-temporal staging loads of the serving-shaped int8 scan (0 auto, 1 never, 2 always)
+    int i8_ring = 0;                         // LDS staging stages of the streaming-shaped int8 scans (0 auto, 2, 4, 8)
+    int select_variant = 0, spans_per_chunk = 0, kloop_qgroup = 0;      // grid shaping
+    // tuning of the IVF list scans
+    int ivf_bt = 0;                          // tiles per level-1 bin (0 auto, 4, 16)
+    int ivf_part = 0;                        // spans per row part (0 auto)
+    int ivf_tps = 0;                         // D > 128, next add: p16 tiles per span of the panel space (0 auto, 16, 64)
+    int ivf_tile = 0;                        // workgroup tile of the D > 128 scan on 256-row spans (0 / 2 square, 1 = 128 x 512)
+    int ivf_i8_group = 4;                    // rows per candidate group of the int8 list scan (4 | 8)
+    int ivf_group = 0;                       // rows per candidate group of the D > 128 list scan (0 auto, 1, 2, 4)
+    int ivf_nw = 0;                          // waves per IVF work item (0 auto, 2 / 4 / 8)
+};
+
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
 
 inline QueryBatchInfo *batch_info(Workspace &ws) {        // inside ws.small (common.hpp, kInfoOffset)
@@ -250,39 +303,13 @@ struct vdb_index_s {
     CodeBufs codes;
     LshWorkspace lsh_ws;
     Workspace ws;
+    Options opt;                             // what vdb_set_option has set; every other member is the library's own state
     int rows8_pitch = 0;
     bool i8_ok = false;
-    int ivf_bt = 0;                          // option "ivf_bt": tiles per level-1 bin of the IVF scan (0 auto, 4, 16)
-    int ivf_part = 0;                        // option "ivf_part": spans per row part of the IVF list scan (0 auto)
-    int ivf_min_batch = 1;                   // option "ivf_min_batch": smallest query batch the list-major MFMA scan serves
-    int ivf_tile = 0;                        // option "ivf_tile": workgroup tile of the D > 128 list scan on 256-row spans (0 / 2 square, 1 = 128 x 512)
-    int ivf_i8_group = 4;                    // option "ivf_i8_group": rows per candidate group of the int8 list scan (4 | 8)
-    int ivf_group = 0;                       // option "ivf_group": rows per candidate group of the D > 128 list scan (0 auto, 1, 2, 4)
-    int ivf_nw = 0;                          // option "ivf_nw": waves per IVF work item (0 auto, 2 / 4 / 8)
-    int i8_group = 8;                        // rows per select group of the int8 scan (option "i8_group": 4 or 8)
-    int f16_wide = 0;                        // option "f16_wide" (tuning, x16 fp16 batch scan, D <= 64): 0 auto (1024-query tiles when they fit), 1 never
-    int f16_stage_tiles = 0;                 // option "f16_stage_tiles" (tuning, x16 fp16 batch scan): tiles per LDS stage, 0 auto | 4 | 8
-    int scan_pair_off = 0;                   // option "scan_pair" = 0: never the paired launch of the two x16 scans (A/B, diagnosis)
-    int scan_prio = 0;                       // option "scan_prio" (tuning, x16 kernels): issue priority of one half of the workgroup's waves
-    int flat_shape_opt = 0;                  // option "flat_shape" (alias "i8_shape"; before vdb_add): MFMA shape of the flat scans for D <= 128,
-                                             // 0 auto (16) | 16 | 32
     bool x16 = false;                        // the flat scan copies (fp16 and int8, D <= 128) are in layout "x16": 16x16x32 f16 / 16x16x64 i8 MFMA,
                                              // octs only (scan_x16.hpp, scan_i8x16.hpp); corpora the dense small-corpus path serves keep 32-row tiles
-    int f16_group = 8;                       // ... and of the fp16 flat scan (option "f16_group": 4 or 8)
-    // option "int8_only" (takes effect at the next add; flat index, D <= 128, > 32768 rows, byte-valued corpus): only the int8
-    // copies are kept -- rows8 + panels8 + their biases, 0.55x the float32 corpus instead of 3x.  Integer query batches run as on
-    // the default index; a batch with a non-integer value is scanned in fp16 over slabs converted from the int8 panels per search;
-    // the exact kernels read x = byte + cx from the int8 rows (same float64 chains, same keys).  One add builds it (no append).
-    int int8_only_opt = 0;
-    bool int8_only = false;
-    int64_t int8_slab_chunks = 0;            // option "int8_slab_chunks": scan chunks per converted fp16 slab (0 = default 8)
-    int64_t int8_block_rows = 0;             // option "int8_block_rows": rows per ingestion block of the int8-only build (0 = 4M; tests)
-    int i8_nt = 0;                           // option "i8_nt": non-temporal staging loads of the serving-shaped int8 scan (0 auto, 1 never, 2 always)
-    int i8_ring = 0;                         // option "i8_ring": LDS staging stages of the streaming-shaped int8 scans (0 auto, 2, 4, 8)
-    // option "graph": a device-resident search that repeats with the same shape and buffers (a serving loop) is captured
-    // into a hipGraph on its second call and replayed from the third (graph_or_run)
-    int graph_mode = 0;
-    int graph_recapture_at_once = 0;         // diagnostic option of the same name: the pre-round-3 ordering (see graph_or_run)
+    bool int8_only = false;                  // option "int8_only" took effect at the last add: only the int8 copies are kept (build_int8_only)
+    // a captured device-resident search (option "graph", graph_or_run)
     struct GraphKey {
         const void *q = nullptr, *o1 = nullptr, *o2 = nullptr;
         int64_t nq = 0;
@@ -296,8 +323,7 @@ struct vdb_index_s {
     hipEvent_t graph_ev = nullptr;           // recorded behind every launch of graph_exec (graph_drop_exec waits for it)
     uint64_t graph_epoch = 0;                // g_alloc_epoch when the graph was captured
     int64_t graph_replays = 0;
-    int small_batch_off = 0;                 // option "small_batch" = 0: batches <= 512 queries keep the batch-shaped grid
-    int i8_cx = 0, i8_ks = 0, i8_disable = 0, i8_variant = 3;   // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)
+    int i8_cx = 0, i8_ks = 0;
     // host copies of the corpus statistics
     float absmax = 0.f, maxnorm2 = 0.f, sx = 1.f;
     bool nonfinite = false, corpus_int_unscaled = false, corpus_fp16_exact = false, scan_ok = false;
@@ -305,23 +331,14 @@ struct vdb_index_s {
     void *pin[2] = {nullptr, nullptr};
     size_t pin_bytes = 0;
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
-    int upload_block_mb = 0;                 // option "upload_block_mb": staging block size (0 = default 64 MiB)
     int64_t last_upload_blocks = 0;          // blocks of the last host upload (vdb_stats: upload_blocks)
-    // options
-    int force_path = 0, timing = 0, list_cap = 0, select_variant = 0, spc_override = 0, kloop_qgroup = 0;
     bool small_clear_pending = false;        // search_device_impl left the clearing of ws.small to the first batch (serving-shaped calls)
     bool small_is_clean = false;             // ws.small was cleared for this call and no batch has used it yet
     bool small_preset = false;               // coarse quantizer of an IVF index: the parent has just cleared ws.small (it lives in
                                              // the parent's ivf_zero buffer) -- the next search_device_impl skips its own memset
     int64_t info_valid_nq = -1;              // queries whose statistics the last search_batch left in batch_info(ws) (-1: none)
     bool tile16 = false;                     // panels in the p16 layout (16-row tiles, 1024-row spans, 4 bins per span)
-    // option "stream_panels" (D > 128, takes effect at the next add): the fp16 panels are NOT kept -- every search converts
-    // the float32 rows slab by slab into one scratch slab and scans it (search_flat.inc).  Halves the footprint of a
-    // non-fp16-exact corpus (the float32 rows must stay for the exact refine) at the price of one conversion pass per batch.
-    int no_fused_stats = 0;                  // option "fused_stats" = 0 (A/B): small batches keep the separate statistics dispatch
-    int stream_panels_opt = 0;
-    int64_t stream_slab_rows = 0;            // option "stream_slab_rows" (0 = default)
-    bool panels_streamed = false;
+    bool panels_streamed = false;            // option "stream_panels" took effect at the last add (D > 128): the fp16 panels are not kept
     bool set_only = false;                   // coarse quantizer of an IVF index: callers use the SET of the k nearest rows,
                                              // not their order or distances (dense.hpp, DenseSelectArgs.set_only)
     vdb_stats_t last{};
@@ -341,7 +358,7 @@ struct vdb_index_s {
     int64_t ivf_pspans = 0;
     int ivf_max_pspans = 0;
     int ivf_span_rows = kSpanRows;           // rows per panel span: 512 (32-row tiles, D <= 128) or 16 * ivf_tps (p16, D > 128)
-    int ivf_tps = 0, ivf_tps_override = 0;   // p16 tiles per span of the IVF panel space (16 / 64); option "ivf_tps"
+    int ivf_tps = 0;                         // p16 tiles per span of the IVF panel space (16 / 64; option "ivf_tps" or the rule of ivf.inc)
     // codec of the inverted lists (vdb_ivf_set_codec): 0 Flat (float32 rows + scan copies) | 1 SQ8 (ivf_sq8.inc: 8-bit codes
     // of the residuals, no float32 rows, no scan copies)
     int ivf_codec = 0;
@@ -350,14 +367,11 @@ struct vdb_index_s {
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
-    int lsh_force_fallback = 0;              // option "lsh_force_fallback": every query takes the exact fallback of the select
     std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
     // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
     int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
     std::vector<float> pq_cb_host;           // host copy of the codebooks [M][256][dsub]
-    int64_t pq_slab_chunks = 0;              // option "pq_slab_chunks": scan chunks per slab of panels (0 = default: 524 288 rows' worth)
-    int64_t pq_scan_min_batch = 0;           // option "pq_scan_min_batch": smallest batch the panel pass + MFMA scan serves (0 = default)
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -520,7 +534,7 @@ void upload_rows(vdb_index_s *h, float *dst, int D4, const float *src, int64_t n
     h->last_upload_blocks = 0;
     if (n <= 0) return;
     const size_t row_bytes = (size_t)D * 4;
-    const size_t block_bytes = h->upload_block_mb > 0 ? (size_t)h->upload_block_mb << 20 : kUploadBlockBytes;
+    const size_t block_bytes = h->opt.upload_block_mb > 0 ? (size_t)h->opt.upload_block_mb << 20 : kUploadBlockBytes;
     const int64_t rows_per_block = std::max<int64_t>(1, (int64_t)(block_bytes / row_bytes));
     const size_t need = (size_t)std::min<int64_t>(rows_per_block, n) * row_bytes;
     if (h->pin_bytes < need) {
@@ -600,7 +614,7 @@ void graph_reset(vdb_index_s *h);
 // layout "x16" for the scan copies of a D <= 128 flat index, unless an option asks for what only the 32-row kernels have
 // (quads as the candidate group)
 bool x16_wanted(const vdb_index_s *h) {
-    return h->ksteps <= kMaxKSteps && h->flat_shape_opt != 32 && h->f16_group == 8 && h->i8_group == 8;
+    return h->ksteps <= kMaxKSteps && h->opt.flat_shape != 32 && h->opt.f16_group == 8 && h->opt.i8_group == 8;
 }
 
 // everything derived from the h->N rows in h->rows.x32: statistics, scan copies, biases
@@ -626,7 +640,7 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
     if (dims_ok && !h->nonfinite) {
         const int64_t ntiles = h->Npad / (h->tile16 ? kTileRows16 : kTileRows);
         const int ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;          // k-steps of the layout (32 or 16 dims)
-        h->panels_streamed = h->tile16 && h->stream_panels_opt != 0;
+        h->panels_streamed = h->tile16 && h->opt.stream_panels != 0;
         if (h->panels_streamed) h->scan.panels.release();
         else h->scan.panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
         const int64_t threads = ntiles * ksl * 64;
@@ -700,7 +714,7 @@ bool build_int8_only(vdb_index_s *h, const float *x, bool on_device, int64_t n, 
     h->scan.panels8.reserve_exact((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
     h->scan.bias.reserve_exact((size_t)h->Npad * sizeof(float));
     const bool direct = on_device && D4 == D && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const int64_t block_want = h->int8_block_rows > 0 ? (h->int8_block_rows + kSpanRows - 1) / kSpanRows * kSpanRows : (int64_t)4 << 20;
+    const int64_t block_want = h->opt.int8_block_rows > 0 ? ((int64_t)h->opt.int8_block_rows + kSpanRows - 1) / kSpanRows * kSpanRows : (int64_t)4 << 20;
     const int64_t block_rows = std::min<int64_t>((n + kSpanRows - 1) / kSpanRows * kSpanRows, block_want);
     DevBuf tmp;
     if (!direct) tmp.reserve((size_t)std::min<int64_t>(block_rows, n) * D4 * sizeof(float));
@@ -782,7 +796,7 @@ void build_index(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int
     h->N = n;
     h->id_base = id_base;
     h->int8_only = false;
-    if (h->int8_only_opt && h->dim <= 128 && n > kInt8OnlyMinRows && !h->coarse) {
+    if (h->opt.int8_only && h->dim <= 128 && n > kInt8OnlyMinRows && !h->coarse) {
         bool ok = false;
         try {
             ok = build_int8_only(h, x_dev_or_host, on_device, n, st);
@@ -1206,6 +1220,8 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
+        // the last search ran an MFMA scan (flat, or the list-major one of an IVF index): ws.small holds its choice and its counters
+        const bool mfma_scanned = h->last.last_path == VDB_PATH_MFMA_SCAN || (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma);
         if (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->plan.ivf_plan.p) {   // (of the last batch of the call)
             IvfPlan pl;
             VDB_HIP(hipDeviceSynchronize());
@@ -1213,8 +1229,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_rows_scanned = (int64_t)pl.rows_scanned;
         }
         s.scan_dtype = 0;
-        if (h->i8_ok && h->ws.small.p &&
-            (h->last.last_path == VDB_PATH_MFMA_SCAN || (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma))) {   // which scan the device chose
+        if (h->i8_ok && h->ws.small.p && mfma_scanned) {   // which scan the device chose
             QueryBatchInfo qi;
             VDB_HIP(hipDeviceSynchronize());
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));
@@ -1226,7 +1241,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;
         s.last_scan_ms = s.last_total_ms = s.last_prep_ms = s.last_tail_ms = 0.f;
-        if (h->ws.small.p && (h->last.last_path == VDB_PATH_MFMA_SCAN || (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma))) {
+        if (h->ws.small.p && mfma_scanned) {
             std::vector<unsigned char> buf(kSmallBytes);
             VDB_HIP(hipDeviceSynchronize());
             VDB_HIP(hipMemcpy(buf.data(), h->ws.small.p, kSmallBytes, hipMemcpyDeviceToHost));
@@ -1274,6 +1289,66 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
     });
 }
 
+namespace {
+// kinds of index that refuse a non-zero value of an option, in the order they are asked
+constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4;
+constexpr struct { unsigned kind; const char *what; } kRefusals[] = {
+    {kSq8, "an SQ8 index"},
+    {kLsh, "an index with sign-LSH codes (they are encoded from, and re-ranked against, the resident float32 rows)"},
+    {kPq, "a PQ index (its rows are codes; every search makes its panels from them)"}};
+
+struct OptionRow {
+    const char *name;
+    int Options::*m;
+    int n;                     // > 0: one of v[0 .. n), integers only | 0: v[0] <= value <= v[1], truncated toward zero | < 0: any value, stored as value != 0
+    double v[4];
+    unsigned not_on = 0;       // kinds of index that refuse a non-zero value
+    int not_on_pq = 0;         // a value that a PQ index refuses as well: its panels are made in layout "x16" (octs) only
+    int64_t Options::*m64 = nullptr;       // instead of m
+};
+constexpr OptionRow kOptions[] = {
+    {"force_path", &Options::force_path, 4, {0, 1, 2, 3}},
+    {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
+    {"list_cap", &Options::list_cap, 0, {0, 65536}},
+    {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
+    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq},
+    {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
+    {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
+    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
+    {"stream_slab_rows", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::stream_slab_rows},   // rows of the scratch slab of a streamed index (0 = default 1 280 000)
+    {"upload_block_mb", &Options::upload_block_mb, 0, {0, 4096}},    // staging block of the row-block ingestion (0 = default 64 MiB)
+    {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
+    {"fused_stats", &Options::fused_stats, 2, {0, 1}},               // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
+    {"ivf_min_batch", &Options::ivf_min_batch, 0, {1, 1e9}},
+    {"graph", &Options::graph, 2, {0, 1}, kSq8 | kPq},
+    {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
+    {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
+    {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
+    {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
+    {"i8_variant", &Options::i8_variant, 0, {0, 7}},
+    {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
+    {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
+    {"flat_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},     // MFMA shape of the flat scans, D <= 128 (layout of the scan copies: set before vdb_add)
+    {"i8_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},       // (alias)
+    {"scan_pair", &Options::scan_pair, 2, {0, 1}},                   // 1 (default): both x16 scans of an index with an int8 copy in one launch; 0: two launches
+    {"scan_prio", &Options::scan_prio, 0, {0, 2}},
+    {"f16_wide", &Options::f16_wide, 2, {0, 1}},
+    {"f16_stage_tiles", &Options::f16_stage_tiles, 3, {0, 4, 8}},
+    {"i8_nt", &Options::i8_nt, 3, {0, 1, 2}},
+    {"i8_ring", &Options::i8_ring, 4, {0, 2, 4, 8}},                 // staging ring of the serving-shaped / IVF int8 scans: 0 auto, 2 (double buffer), 4, 8
+    {"select_variant", &Options::select_variant, 0, {0, 2}},
+    {"spans_per_chunk", &Options::spans_per_chunk, 0, {0, 4096}},    // tuning: rows per workgroup chunk = 512 * value (0 = default 16)
+    {"kloop_qgroup", &Options::kloop_qgroup, 0, {0, 1024}},
+    {"ivf_bt", &Options::ivf_bt, 3, {0, 4, 16}},
+    {"ivf_part", &Options::ivf_part, 0, {0, 1024}},                  // 0 (auto) or 1..1024 spans
+    {"ivf_tps", &Options::ivf_tps, 3, {0, 16, 64}},                  // D > 128, next add: tiles per panel span (0 auto, 16 = 64-row bins, 64 = 256-row bins)
+    {"ivf_tile", &Options::ivf_tile, 3, {0, 1, 2}},
+    {"ivf_i8_group", &Options::ivf_i8_group, 2, {4, 8}},
+    {"ivf_group", &Options::ivf_group, 4, {0, 1, 2, 4}},
+    {"ivf_nw", &Options::ivf_nw, 4, {0, 2, 4, 8}},
+};
+}  // namespace
+
 int vdb_set_option(vdb_handle hh, const char *key, double value) {
     return guarded([&] {
         auto *h = check(hh);
@@ -1281,135 +1356,28 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (h->multi) return multi_set_option(h, key, value);
         const std::string k(key);
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
-        if (h->ivf_codec == 1 && value != 0 && (k == "graph" || k == "int8_only" || k == "stream_panels"))
-            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an SQ8 index");
-        if (h->lsh_nbits > 0 && value != 0 && (k == "int8_only" || k == "stream_panels"))
-            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on an index with sign-LSH codes (they are encoded from, and "
-                                             "re-ranked against, the resident float32 rows)");
-        if (pq_on(h) && value != 0 && (k == "graph" || k == "int8_only" || k == "stream_panels"))
-            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on a PQ index (its rows are codes; every search makes "
-                                             "its panels from them)");
-        if (pq_on(h) && ((k == "flat_shape" && value == 32) || (k == "i8_shape" && value == 32) || (k == "f16_group" && value == 4) ||
-                         (k == "i8_group" && value == 4)))
+        const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
+        const bool known = r != std::end(kOptions);
+        // what this kind of index refuses comes first, whatever the value is otherwise
+        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0);
+        for (const auto &x : kRefusals)
+            if (known && value != 0 && (kinds & r->not_on & x.kind))
+                throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on " + x.what);
+        if (known && (kinds & kPq) && r->not_on_pq && value == r->not_on_pq)
             throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' = " + std::to_string((int)value) + " is not available on a PQ index: its panels are "
                                              "made in layout \"x16\" (octs) only");
-        if (k == "pq_slab_chunks") {           // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
-            if (value < 0 || value > 4096) throw Error(VDB_ERR_INVALID, "pq_slab_chunks out of range");
-            h->pq_slab_chunks = (int64_t)value;
-        } else if (k == "pq_scan_min_batch") { // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default); smaller
-            if (value < 0 || value > 1e9) throw Error(VDB_ERR_INVALID, "pq_scan_min_batch out of range");   // ones: exact kernels on the codes
-            h->pq_scan_min_batch = (int64_t)value;
-        } else if (k == "lsh_force_fallback") {       // 1: every query of an LSH call takes the exact fallback of the select (tests)
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "lsh_force_fallback must be 0 or 1");
-            h->lsh_force_fallback = (int)value;
-        } else if (k == "graph") {
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "graph must be 0 or 1");
-            h->graph_mode = (int)value;
-        } else if (k == "graph_recapture_at_once") {   // diagnostic: destroy a stale exec and capture its successor in ONE call
-            h->graph_recapture_at_once = value != 0;
-        } else if (k == "force_path") {
-            if (value != 0 && value != 1 && value != 2 && value != 3)
-                throw Error(VDB_ERR_INVALID, "force_path must be 0, 1, 2 or 3");
-            h->force_path = (int)value;
-        } else if (k == "timing") {  // (re)starts the recording window
-            h->timing = value != 0;
-            h->ev_used = 0;
-        } else if (k == "stream_panels") {  // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "stream_panels must be 0 or 1");
-            h->stream_panels_opt = (int)value;
-        } else if (k == "fused_stats") {     // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "fused_stats must be 0 or 1");
-            h->no_fused_stats = value == 0;
-        } else if (k == "stream_slab_rows") {  // rows of the scratch slab of a streamed index (0 = default 1 280 000)
-            if (value < 0) throw Error(VDB_ERR_INVALID, "stream_slab_rows must be >= 0");
-            h->stream_slab_rows = value;
-        } else if (k == "panel_dtype") {    // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "panel_dtype must be 0 or 1");
-            h->i8_disable = (int)value;
-        } else if (k == "upload_block_mb") {   // staging block of the row-block ingestion (0 = default 64 MiB)
-            if (value < 0 || value > 4096) throw Error(VDB_ERR_INVALID, "upload_block_mb out of range");
-            h->upload_block_mb = (int)value;
-        } else if (k == "ivf_bt") {
-            if (value != 0 && value != 4 && value != 16) throw Error(VDB_ERR_INVALID, "ivf_bt must be 0, 4 or 16");
-            h->ivf_bt = (int)value;
-        } else if (k == "ivf_tps") {           // D > 128, next add: tiles per panel span (0 auto, 16 = 64-row bins, 64 = 256-row bins)
-            if (value != 0 && value != 16 && value != 64) throw Error(VDB_ERR_INVALID, "ivf_tps must be 0, 16 or 64");
-            h->ivf_tps_override = (int)value;
-        } else if (k == "ivf_part") {
-            if (value < 0 || value > 1024) throw Error(VDB_ERR_INVALID, "ivf_part must be 0 (auto) or 1..1024 spans");
-            h->ivf_part = (int)value;
-        } else if (k == "ivf_min_batch") {
-            if (value < 1 || value > 1e9) throw Error(VDB_ERR_INVALID, "ivf_min_batch must be >= 1");
-            h->ivf_min_batch = (int)value;
-        } else if (k == "ivf_tile") {
-            if (value != 0 && value != 1 && value != 2) throw Error(VDB_ERR_INVALID, "ivf_tile must be 0, 1 or 2");
-            h->ivf_tile = (int)value;
-        } else if (k == "ivf_i8_group") {
-            if (value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "ivf_i8_group must be 4 or 8");
-            h->ivf_i8_group = (int)value;
-        } else if (k == "ivf_group") {
-            if (value != 0 && value != 1 && value != 2 && value != 4) throw Error(VDB_ERR_INVALID, "ivf_group must be 0, 1, 2 or 4");
-            h->ivf_group = (int)value;
-        } else if (k == "ivf_nw") {
-            if (value != 0 && value != 2 && value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "ivf_nw must be 0, 2, 4 or 8");
-            h->ivf_nw = (int)value;
-        } else if (k == "small_batch") {       // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "small_batch must be 0 or 1");
-            h->small_batch_off = value == 0;
-        } else if (k == "i8_group") {          // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
-            if (value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "i8_group must be 4 or 8");
-            h->i8_group = (int)value;
-        } else if (k == "flat_shape" || k == "i8_shape") {   // MFMA shape of the flat scans, D <= 128 (layout of the scan copies: set before vdb_add)
-            if (value != 0 && value != 16 && value != 32) throw Error(VDB_ERR_INVALID, "flat_shape must be 0 (auto), 16 or 32");
-            h->flat_shape_opt = (int)value;
-        } else if (k == "int8_only") {
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "int8_only must be 0 or 1");
-            h->int8_only_opt = (int)value;
-        } else if (k == "int8_block_rows") {
-            if (value < 0 || value > 2147483647.0) throw Error(VDB_ERR_INVALID, "int8_block_rows out of range");
-            h->int8_block_rows = (int64_t)value;
-        } else if (k == "int8_slab_chunks") {
-            if (value < 0 || value > 1024) throw Error(VDB_ERR_INVALID, "int8_slab_chunks out of range");
-            h->int8_slab_chunks = (int64_t)value;
-        } else if (k == "f16_group") {         // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
-            if (value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "f16_group must be 4 or 8");
-            h->f16_group = (int)value;
-        } else if (k == "i8_nt") {
-            if (value != 0 && value != 1 && value != 2) throw Error(VDB_ERR_INVALID, "i8_nt must be 0, 1 or 2");
-            h->i8_nt = (int)value;
-        } else if (k == "i8_ring") {           // staging ring of the serving-shaped / IVF int8 scans: 0 auto, 2 (double buffer), 4, 8
-            if (value != 0 && value != 2 && value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "i8_ring must be 0, 2, 4 or 8");
-            h->i8_ring = (int)value;
-        } else if (k == "i8_variant") {
-            if (value < 0 || value > 7) throw Error(VDB_ERR_INVALID, "i8_variant must be 0..7");
-            h->i8_variant = (int)value;
-        } else if (k == "kloop_qgroup") {
-            if (value < 0 || value > 1024) throw Error(VDB_ERR_INVALID, "kloop_qgroup out of range");
-            h->kloop_qgroup = (int)value;
-        } else if (k == "f16_wide") {
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "f16_wide must be 0 or 1");
-            h->f16_wide = (int)value;
-        } else if (k == "f16_stage_tiles") {
-            if (value != 0 && value != 4 && value != 8) throw Error(VDB_ERR_INVALID, "f16_stage_tiles must be 0, 4 or 8");
-            h->f16_stage_tiles = (int)value;
-        } else if (k == "scan_pair") {         // 1 (default): both x16 scans of an index with an int8 copy in one launch; 0: two launches
-            if (value != 0 && value != 1) throw Error(VDB_ERR_INVALID, "scan_pair must be 0 or 1");
-            h->scan_pair_off = value == 0;
-        } else if (k == "scan_prio") {
-            if (value < 0 || value > 2) throw Error(VDB_ERR_INVALID, "scan_prio must be 0, 1 or 2");
-            h->scan_prio = (int)value;
-        } else if (k == "spans_per_chunk") {  // tuning: rows per workgroup chunk = 512 * value (0 = default 16)
-            if (value < 0 || value > 4096) throw Error(VDB_ERR_INVALID, "spans_per_chunk out of range");
-            h->spc_override = (int)value;
-        } else if (k == "select_variant") {
-            if (value < 0 || value > 2) throw Error(VDB_ERR_INVALID, "select_variant must be 0, 1 or 2");
-            h->select_variant = (int)value;
-        } else if (k == "list_cap") {
-            if (value < 0 || value > 65536) throw Error(VDB_ERR_INVALID, "list_cap out of range");
-            h->list_cap = (int)value;
-        } else {
-            throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
+        if (!known) throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
+        auto number = [](double v) { return v == HUGE_VAL ? std::string("inf") : std::to_string((long)v); };
+        if (r->n > 0 && std::find(r->v, r->v + r->n, value) == r->v + r->n) {
+            std::string list = number(r->v[0]);
+            for (int i = 1; i < r->n; ++i) list += ", " + number(r->v[i]);
+            throw Error(VDB_ERR_INVALID, "option '" + k + "' must be one of " + std::move(list));
         }
+        if (r->n == 0 && (value < r->v[0] || value > r->v[1]))
+            throw Error(VDB_ERR_INVALID, "option '" + k + "' must be in [" + number(r->v[0]) + ", " + number(r->v[1]) + "]");
+        if (r->m64) h->opt.*r->m64 = (int64_t)value;
+        else h->opt.*r->m = r->n < 0 ? value != 0 : (int)value;
+        if (r->m == &Options::timing) h->ev_used = 0;          // (a new recording window)
     });
 }
 

@@ -26,29 +26,14 @@ def normalize_devices(device):
     return int(device)
 
 
-class FlatIndex:
-    """Device-resident brute-force index (replaces faiss.IndexFlat(d, metric)).  `device`: one GPU ordinal, or a list of
-    them -- ONE index row-sharded over those MI355X inside this process (vdb_create_multi): same calls, same results."""
+class _Handle:
+    """What every index object shares: the library, the C-ABI handle it owns (one GPU ordinal or a list of them, see
+    _ffi.create_handle) and the calls that are the same on every kind of index."""
 
-    def __init__(self, dim: int, metric: str = "l2", device=0):
-        if metric not in _METRICS:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
-        self.dim, self.metric, self.device = int(dim), metric, normalize_devices(device)
+    def __init__(self, dim: int, metric: int, device):
         self._lib = _ffi.load()
-        self._h = _ffi.create_handle(self.dim, _METRICS[metric], self.device)
-        self.ntotal = 0
+        self._h = _ffi.create_handle(dim, metric, device)
 
-    @property
-    def devices(self):
-        return list(self.device) if isinstance(self.device, list) else [self.device]
-
-    def _sync_ntotal(self) -> None:
-        """The row count is the library's: an add may have replaced rows instead of appending (e.g. after a failed add)."""
-        s = _ffi.Stats()
-        _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
-        self.ntotal = int(s.ntotal)
-
-    # -- lifetime ---------------------------------------------------------------------------------
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.vdb_destroy(self._h)
@@ -61,9 +46,44 @@ class FlatIndex:
             pass
 
     def _handle(self):
-        if not self._h:
+        if not getattr(self, "_h", None):
             raise RuntimeError("index handle already destroyed")
         return self._h
+
+    def stats(self) -> dict:
+        s = _ffi.Stats()
+        _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
+        return s.as_dict()
+
+    def reserve(self, nq: int, k: int = 10) -> None:
+        """Size the search workspace for batches of up to `nq` queries now (vdb_reserve): the reference harness times its
+        very first batch_search, allocations included (experiment_runner.py:431-437)."""
+        _ffi.check(self._lib.vdb_reserve(self._handle(), int(nq), int(k)), build_time=True)
+
+    def set_option(self, key: str, value: float) -> None:
+        _ffi.check(self._lib.vdb_set_option(self._handle(), key.encode(), float(value)), build_time=True)
+
+
+class FlatIndex(_Handle):
+    """Device-resident brute-force index (replaces faiss.IndexFlat(d, metric)).  `device`: one GPU ordinal, or a list of
+    them -- ONE index row-sharded over those MI355X inside this process (vdb_create_multi): same calls, same results."""
+
+    def __init__(self, dim: int, metric: str = "l2", device=0):
+        if metric not in _METRICS:
+            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        self.dim, self.metric, self.device = int(dim), metric, normalize_devices(device)
+        super().__init__(self.dim, _METRICS[metric], self.device)
+        self.ntotal = 0
+
+    @property
+    def devices(self):
+        return list(self.device) if isinstance(self.device, list) else [self.device]
+
+    def _sync_ntotal(self) -> None:
+        """The row count is the library's: an add may have replaced rows instead of appending (e.g. after a failed add)."""
+        s = _ffi.Stats()
+        _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
+        self.ntotal = int(s.ntotal)
 
     # -- build --------------------------------------------------------------------------------------
     def add(self, vectors: np.ndarray, id_base: int = 0) -> None:
@@ -184,19 +204,6 @@ class FlatIndex:
         _ffi.check(self._lib.vdb_rerank_device(self._handle(), q_ptr, int(nq), cand_ptr, int(ncand), int(k), d_ptr, i_ptr, stream or None))
 
     # -- introspection --------------------------------------------------------------------------------
-    def stats(self) -> dict:
-        s = _ffi.Stats()
-        _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
-        return s.as_dict()
-
-    def reserve(self, nq: int, k: int = 10) -> None:
-        """Size the search workspace for batches of up to `nq` queries now (vdb_reserve): the reference harness times its
-        very first batch_search, allocations included (experiment_runner.py:431-437)."""
-        _ffi.check(self._lib.vdb_reserve(self._handle(), int(nq), int(k)), build_time=True)
-
-    def set_option(self, key: str, value: float) -> None:
-        _ffi.check(self._lib.vdb_set_option(self._handle(), key.encode(), float(value)), build_time=True)
-
     def debug_scan_scores(self, queries: np.ndarray, row0: int, nrows: int):
         q = _ffi.as_f32_c(queries)
         nq = q.shape[0]

@@ -21,6 +21,7 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _ffi
+from .index import _Handle, normalize_devices
 from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
 from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
                          register_algorithm, register_indexer, register_searcher)
@@ -46,37 +47,23 @@ def parse_index_key(key: str) -> Tuple[int, str]:
     return int(m.group(1)), m.group(2)
 
 
-class IVFFlatIndex:
+class IVFFlatIndex(_Handle):
     """Device-resident IVF-Flat index (replaces faiss.index_factory(d, "IVFn,Flat", metric))."""
 
     def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0):
         """`device`: one GPU ordinal or a list of them (rows of every list split over those GPUs, coarse quantizer
         replicated: vdb_create_multi)."""
-        from .index import normalize_devices
-
         if metric not in ("l2", "ip"):
             raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
         self.dim, self.nlist, self.metric, self.device = int(dim), int(nlist), metric, normalize_devices(device)
-        self._lib = _ffi.load()
-        self._h = _ffi.create_handle(self.dim, 0 if metric == "l2" else 1, self.device)
+        super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
         self.is_trained = False
         self.ntotal = 0
         self.nprobe = 1
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.vdb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
         x = _ffi.as_f32_c(x)
-        _ffi.check(self._lib.vdb_ivf_train(self._h, self.nlist, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
+        _ffi.check(self._lib.vdb_ivf_train(self._handle(), self.nlist, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                            int(max_points_per_centroid)), build_time=True)
         self.is_trained = True
         self.ntotal = 0             # (new centroids: rows filed under the old ones are dropped)
@@ -85,13 +72,13 @@ class IVFFlatIndex:
         c = _ffi.as_f32_c(centroids)
         if c.shape != (self.nlist, self.dim):
             raise ValueError(f"expected ({self.nlist}, {self.dim}) centroids, got {c.shape}")
-        _ffi.check(self._lib.vdb_ivf_set_centroids(self._h, _ffi.ptr(c), self.nlist), build_time=True)
+        _ffi.check(self._lib.vdb_ivf_set_centroids(self._handle(), _ffi.ptr(c), self.nlist), build_time=True)
         self.is_trained = True
         self.ntotal = 0
 
     def centroids(self) -> np.ndarray:
         out = np.empty((self.nlist, self.dim), np.float32)
-        _ffi.check(self._lib.vdb_ivf_get_centroids(self._h, _ffi.ptr(out)))
+        _ffi.check(self._lib.vdb_ivf_get_centroids(self._handle(), _ffi.ptr(out)))
         return out
 
     def add(self, x: np.ndarray, id_base: int = 0, list_of_row: Optional[np.ndarray] = None) -> None:
@@ -102,27 +89,27 @@ class IVFFlatIndex:
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
         if list_of_row is None:
-            _ffi.check(self._lib.vdb_ivf_add(self._h, _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
+            _ffi.check(self._lib.vdb_ivf_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
         else:
             lor = np.ascontiguousarray(list_of_row, dtype=np.int32)
             if lor.shape != (x.shape[0],):
                 raise ValueError(f"expected {x.shape[0]} list ids, got {lor.shape}")
-            _ffi.check(self._lib.vdb_ivf_add_assigned(self._h, _ffi.ptr(x), x.shape[0], int(id_base), _ffi.ptr(lor)),
+            _ffi.check(self._lib.vdb_ivf_add_assigned(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base), _ffi.ptr(lor)),
                        build_time=True)
         self.ntotal = int(self.stats()["ntotal"])      # (the library's count: an add may replace instead of append)
 
     def reset(self) -> None:
         """Drop every row; the centroids stay (faiss.IndexIVF.reset)."""
-        _ffi.check(self._lib.vdb_reset(self._h), build_time=True)
+        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
         self.ntotal = 0
 
     def assignment(self) -> np.ndarray:
         out = np.empty((self.ntotal,), np.int32)
-        _ffi.check(self._lib.vdb_ivf_get_assignment(self._h, _ffi.ptr(out)))
+        _ffi.check(self._lib.vdb_ivf_get_assignment(self._handle(), _ffi.ptr(out)))
         return out
 
     def set_nprobe(self, nprobe: int) -> None:
-        _ffi.check(self._lib.vdb_ivf_set_nprobe(self._h, int(nprobe)), build_time=True)
+        _ffi.check(self._lib.vdb_ivf_set_nprobe(self._handle(), int(nprobe)), build_time=True)
         self.nprobe = int(nprobe)
 
     def search(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -133,28 +120,16 @@ class IVFFlatIndex:
             raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
         D = np.empty((q.shape[0], k), np.float32)
         I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_ivf_search(self._h, _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        _ffi.check(self._lib.vdb_ivf_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
     def search_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
-        _ffi.check(self._lib.vdb_ivf_search_device(self._h, q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
+        _ffi.check(self._lib.vdb_ivf_search_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
 
     def search_partial_device(self, q_ptr: int, nq: int, k: int, keys_ptr: int, ids_ptr: int, stream: int = 0) -> None:
         """Per-shard partial top-k (float64 order keys + global ids) among the probed lists; device pointers."""
-        _ffi.check(self._lib.vdb_ivf_search_partial_device(self._h, q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
+        _ffi.check(self._lib.vdb_ivf_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
                                                            stream or None))
-
-    def stats(self) -> dict:
-        s = _ffi.Stats()
-        _ffi.check(self._lib.vdb_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
-
-    def reserve(self, nq: int, k: int = 10) -> None:
-        """Size the search workspace for batches of up to `nq` queries now (vdb_reserve)."""
-        _ffi.check(self._lib.vdb_reserve(self._h, int(nq), int(k)), build_time=True)
-
-    def set_option(self, key: str, value: float) -> None:
-        _ffi.check(self._lib.vdb_set_option(self._h, key.encode(), float(value)), build_time=True)
 
 
 class IVFSQ8Index(IVFFlatIndex):
@@ -164,20 +139,18 @@ class IVFSQ8Index(IVFFlatIndex):
     rows; `set_centroids` + `train_ranges` / `set_ranges` inject them instead.  One GPU only."""
 
     def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0):
-        from .index import normalize_devices
-
         if isinstance(normalize_devices(device), list):
             raise ValueError("IVF<nlist>,SQ8 runs on one GPU: a multi-device index (more than one device id) is not "
                              "available for the SQ8 codec")
         super().__init__(dim, nlist, metric, device)
-        _ffi.check(self._lib.vdb_ivf_set_codec(self._h, 1), build_time=True)
+        _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 1), build_time=True)
 
     def train_ranges(self, x: np.ndarray) -> None:
         """vmin / vdiff from the residuals of `x` against the installed centroids (at most 100 000 rows are read)."""
         x = _ffi.as_f32_c(x)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
-        _ffi.check(self._lib.vdb_ivf_sq8_train_ranges(self._h, _ffi.ptr(x), x.shape[0]), build_time=True)
+        _ffi.check(self._lib.vdb_ivf_sq8_train_ranges(self._handle(), _ffi.ptr(x), x.shape[0]), build_time=True)
         self.ntotal = 0
 
     def set_ranges(self, vmin: np.ndarray, vdiff: np.ndarray) -> None:
@@ -185,19 +158,19 @@ class IVFSQ8Index(IVFFlatIndex):
         vdiff = np.ascontiguousarray(vdiff, dtype=np.float32).reshape(-1)
         if vmin.shape != (self.dim,) or vdiff.shape != (self.dim,):
             raise ValueError(f"expected two ({self.dim},) range vectors, got {vmin.shape} and {vdiff.shape}")
-        _ffi.check(self._lib.vdb_ivf_sq8_set_ranges(self._h, _ffi.ptr(vmin), _ffi.ptr(vdiff)), build_time=True)
+        _ffi.check(self._lib.vdb_ivf_sq8_set_ranges(self._handle(), _ffi.ptr(vmin), _ffi.ptr(vdiff)), build_time=True)
         self.ntotal = 0
 
     def ranges(self) -> Tuple[np.ndarray, np.ndarray]:
         vmin = np.empty((self.dim,), np.float32)
         vdiff = np.empty((self.dim,), np.float32)
-        _ffi.check(self._lib.vdb_ivf_sq8_get_ranges(self._h, _ffi.ptr(vmin), _ffi.ptr(vdiff)))
+        _ffi.check(self._lib.vdb_ivf_sq8_get_ranges(self._handle(), _ffi.ptr(vmin), _ffi.ptr(vdiff)))
         return vmin, vdiff
 
     def codes(self) -> np.ndarray:
         """uint8 (ntotal, dim) codes in id (insertion) order."""
         out = np.empty((self.ntotal, self.dim), np.uint8)
-        _ffi.check(self._lib.vdb_ivf_get_codes(self._h, _ffi.ptr(out)))
+        _ffi.check(self._lib.vdb_ivf_get_codes(self._handle(), _ffi.ptr(out)))
         return out
 
 

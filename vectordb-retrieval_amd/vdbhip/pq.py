@@ -19,6 +19,7 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _ffi
+from .index import _Handle, normalize_devices
 from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
 from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
                          register_algorithm, register_indexer, register_searcher)
@@ -34,12 +35,10 @@ def parse_pq_key(key: str) -> int:
     return int(m.group(1))
 
 
-class PQIndex:
+class PQIndex(_Handle):
     """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only."""
 
     def __init__(self, dim: int, M: int, metric: str = "l2", device=0):
-        from .index import normalize_devices
-
         if metric not in ("l2", "ip"):
             raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
         device = normalize_devices(device)
@@ -49,21 +48,9 @@ class PQIndex:
         if M < 1 or M > min(dim, 256) or dim % M:
             raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
         self.dim, self.M, self.dsub, self.metric, self.device = dim, M, dim // M, metric, device
-        self._lib = _ffi.load()
-        self._h = _ffi.create_handle(self.dim, 0 if metric == "l2" else 1, self.device)
+        super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
         self.is_trained = False
         self.ntotal = 0
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.vdb_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _sync_ntotal(self) -> None:
         self.ntotal = int(self.stats()["ntotal"])
@@ -73,7 +60,7 @@ class PQIndex:
         x = _ffi.as_f32_c(x)
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
-        _ffi.check(self._lib.vdb_pq_train(self._h, self.M, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
+        _ffi.check(self._lib.vdb_pq_train(self._handle(), self.M, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                           int(max_points_per_centroid)), build_time=True)
         self.is_trained = True
 
@@ -81,16 +68,16 @@ class PQIndex:
         c = _ffi.as_f32_c(codebooks)
         if c.shape != (self.M, 256, self.dsub):
             raise ValueError(f"expected ({self.M}, 256, {self.dsub}) codebooks, got {c.shape}")
-        _ffi.check(self._lib.vdb_pq_set_codebooks(self._h, self.M, _ffi.ptr(c)), build_time=True)
+        _ffi.check(self._lib.vdb_pq_set_codebooks(self._handle(), self.M, _ffi.ptr(c)), build_time=True)
         self.is_trained = True
 
     def codebooks(self) -> np.ndarray:
         m = ctypes.c_int(0)
         out = np.empty((self.M, 256, self.dsub), np.float32)
-        _ffi.check(self._lib.vdb_pq_get_codebooks(self._h, ctypes.byref(m), None))
+        _ffi.check(self._lib.vdb_pq_get_codebooks(self._handle(), ctypes.byref(m), None))
         if m.value != self.M:
             raise RuntimeError("no codebooks: train the index or set them first")
-        _ffi.check(self._lib.vdb_pq_get_codebooks(self._h, ctypes.byref(m), _ffi.ptr(out)))
+        _ffi.check(self._lib.vdb_pq_get_codebooks(self._handle(), ctypes.byref(m), _ffi.ptr(out)))
         return out
 
     # -- rows -----------------------------------------------------------------------------------------------
@@ -100,7 +87,7 @@ class PQIndex:
         if x.ndim != 2 or x.shape[1] != self.dim:
             raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
         try:
-            _ffi.check(self._lib.vdb_pq_add(self._h, _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
+            _ffi.check(self._lib.vdb_pq_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
         finally:
             self._sync_ntotal()
 
@@ -110,14 +97,14 @@ class PQIndex:
         if c.ndim != 2 or c.shape[1] != self.M:
             raise ValueError(f"expected (n, {self.M}) codes, got {c.shape}")
         try:
-            _ffi.check(self._lib.vdb_pq_add_codes(self._h, _ffi.ptr(c), c.shape[0], int(id_base)), build_time=True)
+            _ffi.check(self._lib.vdb_pq_add_codes(self._handle(), _ffi.ptr(c), c.shape[0], int(id_base)), build_time=True)
         finally:
             self._sync_ntotal()
 
     def codes(self) -> np.ndarray:
         """uint8 (ntotal, M) codes in id (insertion) order."""
         out = np.empty((self.ntotal, self.M), np.uint8)
-        _ffi.check(self._lib.vdb_pq_get_codes(self._h, _ffi.ptr(out)))
+        _ffi.check(self._lib.vdb_pq_get_codes(self._handle(), _ffi.ptr(out)))
         return out
 
     def reconstruct(self, codes: Optional[np.ndarray] = None) -> np.ndarray:
@@ -128,7 +115,7 @@ class PQIndex:
 
     def reset(self) -> None:
         """Drop every row; the codebooks stay (faiss.IndexPQ.reset)."""
-        _ffi.check(self._lib.vdb_reset(self._h), build_time=True)
+        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
         self.ntotal = 0
 
     # -- search ---------------------------------------------------------------------------------------------
@@ -140,35 +127,24 @@ class PQIndex:
             raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
         D = np.empty((q.shape[0], k), np.float32)
         I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_search(self._h, _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        _ffi.check(self._lib.vdb_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
     def search_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
         """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
-        _ffi.check(self._lib.vdb_search_device(self._h, q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
+        _ffi.check(self._lib.vdb_search_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
 
     def search_partial_device(self, q_ptr: int, nq: int, k: int, keys_ptr: int, ids_ptr: int, stream: int = 0) -> None:
         """Partial top-k (float64 order keys + ids, device pointers), as FlatIndex.search_partial_device."""
-        _ffi.check(self._lib.vdb_search_partial_device(self._h, q_ptr, int(nq), int(k), keys_ptr, ids_ptr, stream or None))
+        _ffi.check(self._lib.vdb_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr, stream or None))
 
     def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
         q = _ffi.as_f32_c(queries)
         c = np.ascontiguousarray(candidate_ids, dtype=np.int64)
         D = np.empty((q.shape[0], k), np.float32)
         I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_rerank(self._h, _ffi.ptr(q), q.shape[0], _ffi.ptr(c), c.shape[1], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        _ffi.check(self._lib.vdb_rerank(self._handle(), _ffi.ptr(q), q.shape[0], _ffi.ptr(c), c.shape[1], int(k), _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
-
-    def stats(self) -> dict:
-        s = _ffi.Stats()
-        _ffi.check(self._lib.vdb_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
-
-    def reserve(self, nq: int, k: int = 10) -> None:
-        _ffi.check(self._lib.vdb_reserve(self._h, int(nq), int(k)), build_time=True)
-
-    def set_option(self, key: str, value: float) -> None:
-        _ffi.check(self._lib.vdb_set_option(self._h, key.encode(), float(value)), build_time=True)
 
 
 def _build_pq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> PQIndex:
