@@ -162,7 +162,9 @@ int vdb_merge_packed_partials_device(int metric, int device, const void *packed_
  *      (modular.py:483-532: gather candidate rows by id -> exact L2 / inner product -> top-k) and
  *      LSHSearcher._compute_distances (lsh.py:242-250) ------------------------------------------------ */
 /* cand (nq, ncand) int64 row ids (id_base-relative ids as returned by search; -1 = empty slot, ids of one
- * query must be distinct).  Output: the k best candidates of every query, flat conventions and padding. */
+ * query must be distinct).  Output: the k best candidates of every query, flat conventions and padding.
+ * A handle whose rows were filed by vdb_ivf_add(_assigned) (IVF-Flat or IVF-SQ8, one device or vdb_create_multi) is refused
+ * with VDB_ERR_STATE before any kernel runs: its rows sit in list order (SQ8 keeps no float32 rows at all), not in id order. */
 int vdb_rerank(vdb_handle h, const float *q_host, int64_t nq, const int64_t *cand_host, int ncand, int k, float *D,
                int64_t *I);
 int vdb_rerank_device(vdb_handle h, const float *q_dev, int64_t nq, const int64_t *cand_dev, int ncand, int k,

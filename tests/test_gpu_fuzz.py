@@ -6,31 +6,9 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from tests.helpers import values as _values
+
 pytestmark = pytest.mark.gpu
-
-
-def _values(rng, kind, shape):
-    if kind == "gauss":
-        return rng.standard_normal(shape)
-    if kind == "ints":            # SIFT-like: exact in fp16, unscaled
-        return np.clip(np.rint(rng.gamma(0.6, 40.0, size=shape)), 0, 218)
-    if kind == "bigints":         # integers beyond the unscaled fp16 range
-        return np.rint(rng.standard_normal(shape) * 3000.0)
-    if kind == "tiny":
-        return rng.standard_normal(shape) * 1e-4
-    if kind == "huge":
-        return rng.standard_normal(shape) * 1e5
-    if kind == "heavy":           # heavy tails: a few coordinates dominate the norms
-        return np.clip(rng.standard_cauchy(shape), -1e3, 1e3)
-    if kind == "sparse":          # mostly zeros
-        return rng.standard_normal(shape) * (rng.random(shape) < 0.05)
-    if kind == "offset":          # large common offset, small spread (cancellation in ||x||^2 - 2 q.x)
-        return 50.0 + rng.standard_normal(shape) * 0.1
-    if kind == "bytes":           # the whole uint8 range: int8 scan copy, largest accumulator magnitudes
-        return rng.integers(0, 256, size=shape).astype(np.float64)
-    if kind == "sbytes":          # the whole int8 range (s8 window)
-        return rng.integers(-128, 128, size=shape).astype(np.float64)
-    raise AssertionError(kind)
 
 
 KINDS = ["gauss", "ints", "bigints", "tiny", "huge", "heavy", "sparse", "offset", "bytes", "sbytes"]

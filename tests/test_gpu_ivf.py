@@ -110,6 +110,70 @@ def test_small_lists_padding_and_errors(vdb, oracle):
     np.testing.assert_array_equal(I, Io)
     np.testing.assert_array_equal(D, Do)
     assert (I == -1).any() and np.all(D[I == -1] == np.finfo(np.float32).max)
+    # a list id out of range in `add_assigned` is refused before the add touches the handle: same lists, same results
+    bad = np.zeros(5, np.int32)
+    bad[2] = 64
+    with pytest.raises(ValueError, match="row could not be assigned to a list"):
+        idx.add(X[:5], list_of_row=bad)
+    assert idx.stats()["ntotal"] == len(X)
+    D2, I2 = idx.search(Q, 30)
+    np.testing.assert_array_equal(I2, I)
+    np.testing.assert_array_equal(D2, D)
+    idx.close()
+
+
+@pytest.mark.parametrize("codec", ["flat", "sq8"])
+def test_rerank_refuses_rows_in_list_order(vdb, codec):
+    """vdb_rerank / vdb_rerank_device score rows by id; an index filed by vdb_ivf_add keeps them in list order (SQ8: no float32
+    rows at all).  Both calls return VDB_ERR_STATE before any kernel runs, on one device and on a multi-device handle, and the
+    index searches as before."""
+    import torch
+    from vdbhip import _ffi
+
+    lib = _ffi.load()
+    X, Q = _data(3000, 32, 8, 6)
+    C = X[:16].copy()
+    cand = np.tile(np.arange(20, dtype=np.int64), (len(Q), 1))
+    D = np.empty((len(Q), 5), np.float32)
+    I = np.empty((len(Q), 5), np.int64)
+    q_t, c_t = torch.from_numpy(Q).cuda(), torch.from_numpy(cand).cuda()
+    D_t = torch.empty((len(Q), 5), dtype=torch.float32, device="cuda")
+    I_t = torch.empty((len(Q), 5), dtype=torch.int64, device="cuda")
+    handles = [(vdb.IVFSQ8Index if codec == "sq8" else vdb.IVFFlatIndex)(32, 16, "l2", 0)]
+    if codec == "flat":
+        handles.append(vdb.IVFFlatIndex(32, 16, "l2", [0, 0]))
+    for idx in handles:
+        idx.set_centroids(C)
+        if codec == "sq8":
+            idx.train_ranges(X)
+        idx.add(X)
+        idx.set_nprobe(4)
+        before = idx.search(Q, 5)
+        rc = lib.vdb_rerank(idx._h, _ffi.ptr(Q), len(Q), _ffi.ptr(cand), 20, 5, _ffi.ptr(D), _ffi.ptr(I))
+        assert rc == _ffi.VDB_ERR_STATE and "not been built" in _ffi.last_error(), (rc, _ffi.last_error())
+        rc = lib.vdb_rerank_device(idx._h, q_t.data_ptr(), len(Q), c_t.data_ptr(), 20, 5, D_t.data_ptr(), I_t.data_ptr(), None)
+        assert rc == _ffi.VDB_ERR_STATE and "not been built" in _ffi.last_error(), (rc, _ffi.last_error())
+        after = idx.search(Q, 5)
+        np.testing.assert_array_equal(after[1], before[1])
+        np.testing.assert_array_equal(after[0], before[0])
+        idx.close()
+
+
+def test_multi_device_add_assigned_refuses_a_bad_list_id_up_front(vdb):
+    X, Q = _data(3000, 32, 8, 7)
+    idx = vdb.IVFFlatIndex(32, 16, "l2", [0, 0])
+    idx.set_centroids(X[:16].copy())
+    idx.add(X)
+    idx.set_nprobe(4)
+    before = idx.search(Q, 5)
+    bad = np.zeros(10, np.int32)
+    bad[8] = 16                         # (in the second shard's block of the add)
+    with pytest.raises(ValueError, match="row could not be assigned to a list"):
+        idx.add(X[:10], list_of_row=bad)
+    assert idx.stats()["ntotal"] == len(X)
+    after = idx.search(Q, 5)
+    np.testing.assert_array_equal(after[1], before[1])
+    np.testing.assert_array_equal(after[0], before[0])
     idx.close()
 
 

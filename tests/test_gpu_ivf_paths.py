@@ -222,31 +222,28 @@ def test_split_and_assigned_adds_equal_one_add(adds):
 
 
 def test_refused_appends(adds):
-    """What each codec does today with an append it refuses.  Another id base: refused before anything changes, both codecs.
-    A list id out of range in `add_assigned`: the same error text from both, but SQ8 checks the ids before it touches the
-    handle (still built, same results), while Flat finds the bad id in the CSR build, after it has marked the index unbuilt:
-    it no longer searches, and the next add starts over."""
-    from vdbhip import _ffi
-
+    """An append that is refused leaves the index as it was, both codecs.  Another id base, and a list id out of range in
+    `add_assigned` (checked before the add touches the handle): still built, same lists, same results."""
     codec, X, Q, new, whole, ref = adds
     idx = new()
     idx.add(X, id_base=40)
     with pytest.raises(ValueError, match="id.base"):
         idx.add(X[:10], id_base=41)
     _same_index(idx, whole, codec, Q, ref)
-    bad = np.zeros(10, np.int32)
-    bad[7] = 24
-    with pytest.raises(ValueError, match="row could not be assigned to a list"):
-        idx.add(X[:10], id_base=40, list_of_row=bad)
-    assert idx.stats()["ntotal"] == len(X)
-    if codec == "sq8":
+    for where, value in ((7, 24), (0, -1), (9, 2**31 - 1)):
+        bad = np.zeros(10, np.int32)
+        bad[where] = value
+        with pytest.raises(ValueError, match="row could not be assigned to a list"):
+            idx.add(X[:10], id_base=40, list_of_row=bad)
+        assert idx.stats()["ntotal"] == len(X)
         _same_index(idx, whole, codec, Q, ref)
-    else:
-        with pytest.raises(_ffi.VdbError, match="not been built"):
-            idx.search(Q, K)
-        with pytest.raises(_ffi.VdbError, match="not been built"):
-            idx.assignment()
-        idx.add(X, id_base=40)              # (not an append: the lists are built anew)
-        assert idx.ntotal == len(X)
-        _same_index(idx, whole, codec, Q, ref)
+    idx.add(X[:0], id_base=40, list_of_row=np.zeros(0, np.int32))      # (nothing to check, nothing to add)
+    _same_index(idx, whole, codec, Q, ref)
     idx.close()
+    fresh = new()                       # the first add of an index: refused as well, and the next add builds it
+    with pytest.raises(ValueError, match="row could not be assigned to a list"):
+        fresh.add(X[:10], id_base=40, list_of_row=np.full(10, 24, np.int32))
+    assert fresh.stats()["ntotal"] == 0
+    fresh.add(X, id_base=40)
+    _same_index(fresh, whole, codec, Q, ref)
+    fresh.close()

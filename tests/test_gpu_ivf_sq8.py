@@ -10,28 +10,11 @@ import json
 import numpy as np
 import pytest
 
+from tests.helpers import np_decode, np_encode, np_ranges
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-
-
-# ---- NumPy restatement of the codec (every operation float32, rounded as written) --------------------------------------
-def np_ranges(X, C, lor):
-    R = X - C[lor]
-    vmin = R.min(axis=0)
-    return vmin, R.max(axis=0) - vmin
-
-
-def np_encode(X, C, lor, vmin, vdiff):
-    R = X - C[lor]
-    safe = np.where(vdiff != 0, vdiff, F32(1))
-    U = np.where(vdiff != 0, (R - vmin) / safe, F32(0)).astype(F32)
-    U = np.clip(U, F32(0), F32(1))
-    return (F32(255) * U).astype(np.uint8)
-
-
-def np_decode(codes, C, lor, vmin, vdiff):
-    return C[lor] + (vmin + ((codes.astype(F32) + F32(0.5)) / F32(255)) * vdiff)
 
 
 def _data(n, d, nq, seed):
@@ -294,6 +277,10 @@ def test_refusals_leave_the_index_usable(vdb):
     with pytest.raises(ValueError, match="id_base"):
         idx.add(X[:10], id_base=5)                                          # appends keep the index's id base
     assert lib.vdb_add(idx._h, _ffi.ptr(X), 10, 0) == _ffi.VDB_ERR_UNSUPPORTED
+    bad = np.zeros(10, np.int32)
+    bad[3] = 16
+    with pytest.raises(ValueError, match="row could not be assigned to a list"):    # (checked before the add touches the handle)
+        idx.add(X[:10], id_base=1000, list_of_row=bad)
     D1, I1 = idx.search(Q, 5)
     np.testing.assert_array_equal(I1, I0)
     np.testing.assert_array_equal(D1, D0)

@@ -449,6 +449,74 @@ def test_fp16_scan_error_bound_holds_on_the_kloop_layout(vdb, d, metric):
     idx.close()
 
 
+# Harder inputs for the premise of the guard, on the three panel layouts the tests above cover (32x32 tiles below the x16
+# rows, layout "x16", p16 panels of the K-loop scan).  (n, d) per layout; every (query, row) pair of the index is scored.
+_BOUND_LAYOUTS = {"t32": (4096, 128, 32), "x16": (16384, 128, 16), "kloop": (3000, 200, 0)}
+_BOUND_FUZZ = ["huge", "tiny", "heavy", "offset", "bigints", "sparse"]
+_BOUND_EDGES = ["int2048", "mag_lo", "mag_hi", "one_frac_query", "amax_above", "subnormal"]
+
+
+def _bound_inputs(case, n, d, nq, metric, seed):
+    """(X, Q, exact_expected): exact_expected says whether the exact-integer shortcut of query_eps_kernel (`int_exact`: integer
+    corpus stored unscaled, integer batch with fm * amax <= 2048, mag < 2^24) holds for every query, i.e. eps carries no
+    accumulation term and the scan must reproduce the integers."""
+    from tests.helpers import values
+
+    rng = np.random.default_rng(seed)
+    fm = 2 if metric == "l2" else 1
+    if case in _BOUND_FUZZ:
+        return values(rng, case, (n, d)).astype(np.float32), values(rng, case, (nq, d)).astype(np.float32), False
+    if case == "int2048":          # absmax exactly 2048 (still stored unscaled): one such entry in every 16th row, small values else
+        X = rng.integers(-8, 9, size=(n, d)).astype(np.float32)
+        X[::16, 5] = 2048.0
+        X[8::16, 7] = -2048.0
+        return X, rng.integers(-8, 9, size=(nq, d)).astype(np.float32), True
+    if case in ("mag_lo", "mag_hi"):    # ||x||^2 + 2 ||q|| ||x|| on either side of 2^24 (d = 128: 9.3e6 against 3.8e7 and more)
+        top = 250 if case == "mag_lo" else 600
+        X = rng.integers(0, top + 1, size=(n, d)).astype(np.float32)
+        Q = rng.integers(0, top + 1, size=(nq, d)).astype(np.float32)
+        return X, Q, case == "mag_lo" and d <= 128
+    X = rng.integers(0, 201, size=(n, d)).astype(np.float32)
+    Q = rng.integers(0, 201, size=(nq, d)).astype(np.float32)
+    if case == "one_frac_query":   # one non-integer value in the batch: the whole batch is scaled
+        Q[5, 3] += np.float32(0.5)
+        return X, Q, False
+    if case == "amax_above":       # integer queries with fm * amax = 2050 (L2) / 2049 (IP): just past the unscaled range
+        Q[7, 2] = np.float32(2050 // fm if metric == "l2" else 2049)
+        return X, Q, False
+    assert case == "subnormal"     # after scaling: one coordinate at the top of the fp16 range, the rest from normal values
+    X = (10.0 ** rng.uniform(-10.0, -5.0, size=(n, d)) * rng.choice([-1.0, 1.0], size=(n, d))).astype(np.float32)   # down to flushed ones
+    X[:, 0] = 1.0
+    return X, rng.standard_normal((nq, d)).astype(np.float32), False
+
+
+@pytest.mark.parametrize("case", _BOUND_FUZZ + _BOUND_EDGES)
+@pytest.mark.parametrize("layout", list(_BOUND_LAYOUTS))
+def test_fp16_scan_error_bound_holds_on_hard_inputs(vdb, layout, case):
+    """|score / cs - exact| <= eps / cs for every (query, row) pair -- the assertion of the three tests above -- on the value
+    distributions of the fuzz sweep and at the edges of the exact-integer shortcut; zero error where that shortcut holds."""
+    n, d, shape = _BOUND_LAYOUTS[layout]
+    nq = 32
+    for metric in ("l2", "ip"):
+        X, Q, exact_expected = _bound_inputs(case, n, d, nq, metric, seed=1000 * (_BOUND_FUZZ + _BOUND_EDGES).index(case) + d)
+        idx = vdb.FlatIndex(d, metric, 0)
+        idx.add(X)
+        assert idx.stats()["scan_shape"] == shape
+        scores, eps, cs = idx.debug_scan_scores(Q, 0, n)
+        idx.close()
+        X64, Q64 = X.astype(np.float64), Q.astype(np.float64)
+        dots = Q64 @ X64.T
+        exact = ((X64 * X64).sum(1)[None, :] - 2.0 * dots) if metric == "l2" else -dots
+        assert cs > 0 and np.isfinite(scores).all() and np.isfinite(eps).all(), (layout, case, metric, cs)
+        err = np.abs(scores.astype(np.float64) / cs - exact)
+        bound = (eps.astype(np.float64) / cs)[:, None]
+        print(f"{layout} {case} {metric}: cs {cs:g}, max err {err.max():.6g}, min bound {bound.min():.6g}, "
+              f"max err / bound {(err / bound).max():.4f}")
+        assert np.all(err <= bound), (layout, case, metric, float(err.max()), float(bound.min()))
+        if exact_expected:
+            assert cs == 1.0 and float(err.max()) == 0.0, (layout, case, metric, cs, float(err.max()))
+
+
 def test_search_statistics_are_summed_over_the_counter_shards(vdb):
     """vdb_stats after an MFMA-scan search: candidate quads / re-scanned bins / fallbacks are counted per query in
     sharded device counters (common.hpp stat_add) and summed on the host."""

@@ -160,6 +160,14 @@ void ivf_add_finish(vdb_index_s *h, const std::vector<int64_t> &assign_new, int6
     for (int64_t i = 0; i < n; ++i) h->ivf_list_of_row[(size_t)(N0 + i)] = (int32_t)assign_new[(size_t)i];
 }
 
+// vdb_ivf_add_assigned: every given list id names a list -- checked before the add touches the handle (both codecs), so a
+// refused add leaves the index as it was
+void ivf_check_given(const vdb_index_s *h, const int32_t *given, int64_t n) {
+    if (!given) return;
+    for (int64_t i = 0; i < n; ++i)
+        ivf_require(given[i] >= 0 && given[i] < h->nlist, VDB_ERR_INVALID, "row could not be assigned to a list");
+}
+
 #include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
 
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
@@ -979,12 +987,16 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
     return guarded([&] {
         auto *h = check(hh);
         pq_refuse_ivf(h);
-        if (h->multi) return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
+        if (h->multi) {
+            if (h->nlist > 0 && n > 0) ivf_check_given(h, given, n);      // (a shard that refused its block would empty the whole index)
+            return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
+        }
         if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
         int64_t N0, N1;
         if (!ivf_add_range(h, n, id_base, N0, N1)) return;
+        ivf_check_given(h, given, n);
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;
         graph_reset(h);

@@ -125,9 +125,7 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
     ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
     int64_t N0, N1;
     if (!ivf_add_range(h, n, id_base, N0, N1)) return;
-    if (given)
-        for (int64_t i = 0; i < n; ++i)
-            ivf_require(given[i] >= 0 && given[i] < h->nlist, VDB_ERR_INVALID, "row could not be assigned to a list");
+    ivf_check_given(h, given, n);
     set_device(h->device);
     const int Dm = h->dim, D4 = h->D4;
     VDB_HIP(hipDeviceSynchronize());
