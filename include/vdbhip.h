@@ -210,7 +210,8 @@ int vdb_ivf_search_partial_device(vdb_handle h, const float *q_dev, int64_t nq, 
  * IVF-Flat's panels of x^, so the same error bound holds; vdb_stats.scan_dtype = 2).  D > 128: the exact list scan.
  * Not available (VDB_ERR_UNSUPPORTED): the codec on a vdb_create_multi handle, option "graph", options "int8_only" /
  * "stream_panels", vdb_add / vdb_add_device (rows enter through vdb_ivf_add / vdb_ivf_add_assigned only). */
-/* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8.  Only before centroids or rows exist (VDB_ERR_STATE after) */
+/* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8, 2 = PQ (IVF<nlist>,PQ<M>, below).  Only before centroids or
+ * rows exist (VDB_ERR_STATE after) */
 int vdb_ivf_set_codec(vdb_handle h, int codec);
 /* SQ8: vdb_ivf_train trains the centroids and then the ranges on the same rows; this call trains the ranges only, against
  * the installed centroids (vdb_ivf_set_centroids).  New ranges drop the rows encoded under the old ones at the next add. */
@@ -220,6 +221,41 @@ int vdb_ivf_sq8_set_ranges(vdb_handle h, const float *vmin_host, const float *vd
 int vdb_ivf_sq8_get_ranges(vdb_handle h, float *vmin_host, float *vdiff_host);
 /* codes of an SQ8 index, uint8 (ntotal, dim), in id (insertion) order */
 int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
+
+/* ---- IVF<nlist>,PQ<M> -- replaces faiss.index_factory(d, "IVF<nlist>,PQ<M>", metric) (IndexIVFPQ, 8 bits, by_residual; the
+ *      reference's `ivf_pq` configs) -- codec 2 of vdb_ivf_set_codec ---------------------------------------------------------
+ * M bytes per row: the index keeps the codes in list order, a list id and an id per row, the centroids, the codebooks and
+ * (dim <= 128) the panel-space bias -- NO float32 rows and no fp16 / int8 scan copies.  The contract is the library's own, as
+ * for SQ8 and flat PQ (FAISS' k-means, its float32 table sums and its tie order are not reproduced).  Every step is float32,
+ * rounded as written; c_l = centroid of the row's list, dsub = dim / M:
+ *   train   codebooks float32 [M][256][dsub], trained on the residuals r = x - c_l of ONE row sample (at most
+ *           256 * max_points_per_centroid rows, drawn with `seed` as the flat PQ training draws them) against the installed
+ *           centroids; sub-space m is clustered by the k-means of vdb_ivf_train with seed + m.  Same seed, same codebooks.
+ *           Fewer than 256 rows: VDB_ERR_INVALID.  vdb_ivf_train keeps training the centroids only
+ *   encode  code[i][m] = argmin over c of the canonical float64 L2 key between r[i][m dsub .. (m + 1) dsub) and
+ *           codebook[m][c]; ties to the smaller c, whatever the index metric
+ *   decode  x^[d] = c_l[d] + codebook[m][code[m]][j]: one float32 add (a padding dimension decodes to exactly 0)
+ *   search  vdb_ivf_search / _device / _partial_device and vdb_reserve return, bit for bit, the IVF-Flat result over the
+ *           float32 rows x^ under the same lists and nprobe (ids, distances, ties by id)
+ * dim <= 128: batches the list-major path serves make the fp16 panels of the whole panel space from the codes per batch, as
+ * (half)((c_l[d] + codebook entry) * sx) -- IVF-Flat's panels of x^, so the same error bound holds (vdb_stats.scan_dtype = 2) --
+ * and run the MFMA list scan on them; dim > 128, small batches and "force_path" 1 / 3 take the exact list scan over the codes.
+ * vdb_ivf_add / vdb_ivf_add_assigned encode and append.  New codebooks (or centroids) drop the rows encoded under the old ones
+ * at the next add; vdb_reset drops the rows and keeps centroids and codebooks.
+ * VDB_ERR_STATE: these calls on a handle whose codec is not 2; an add before codebooks.  dim % M != 0 or M outside
+ * 1 .. min(dim, 256): VDB_ERR_INVALID.  Refused with a message that names IVF-PQ: the codec on a vdb_create_multi handle, options
+ * "graph" / "int8_only" / "stream_panels" (in either order), vdb_add / vdb_add_device, vdb_rerank(_device) (VDB_ERR_STATE: the
+ * rows sit in list order), the sign-LSH calls, the flat PQ calls (VDB_ERR_UNSUPPORTED on any IVF handle) and the SQ8 range and
+ * code calls. */
+int vdb_ivfpq_train(vdb_handle h, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid);
+/* inject / read the codebooks, float32 (M, 256, dim / M) -- persistence and tests.  codebooks_host may be NULL: M only (0 = none) */
+int vdb_ivfpq_set_codebooks(vdb_handle h, int M, const float *codebooks_host);
+int vdb_ivfpq_get_codebooks(vdb_handle h, int *M, float *codebooks_host);
+/* APPEND n rows given as codes, uint8 (n, M), with the list of every row (int32, as vdb_ivf_get_assignment returned it) -- what
+ * loading a persisted index does; ids and id_base as vdb_ivf_add */
+int vdb_ivfpq_add_codes(vdb_handle h, const uint8_t *codes_host, int64_t n, int64_t id_base, const int32_t *list_of_row_host);
+/* codes of the indexed rows, uint8 (ntotal, M), in id (insertion) order */
+int vdb_ivfpq_get_codes(vdb_handle h, uint8_t *codes_host);
 
 /* ---- sign-LSH codes + Hamming candidate scan + exact re-rank -- replaces faiss.IndexLSH(d, nbits) with its defaults as
  *      FaissLSHIndexer / the LSH branch of FaissSearcher use it (modular.py:182-221, 455-548; the reference's `faiss_lsh`

@@ -169,6 +169,7 @@ void ivf_check_given(const vdb_index_s *h, const int32_t *given, int64_t n) {
 }
 
 #include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
+#include "ivf_pq.inc"       // IVF<nlist>,PQ<M>: residual product codes, encoding add, the per-batch panel pass
 
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
 // 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
@@ -230,7 +231,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
     IndexStats hs;
     VDB_HIP(hipMemcpy(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost));
     h->corpus_fp16_exact = hs.not_fp16_exact == 0;
-    h->i8_ok = h->i8_ok && !h->tile16 && h->ivf_codec == 0;   // (an SQ8 index keeps no int8 copies)
+    h->i8_ok = h->i8_ok && !h->tile16 && h->ivf_codec == 0;   // (an SQ8 / IVF-PQ index keeps no int8 copies)
     if (h->i8_ok) {      // byte-valued rows: int8 copy of the same panel space (scan_i8.hpp)
         h->i8_ks = h->dim <= 64 ? 2 : 4;
         h->scan.panels8.reserve((size_t)ntiles * h->i8_ks * 64 * sizeof(int4v));
@@ -620,6 +621,7 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     RefineCommon rc{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     rc.info = L.info;
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
+    if (ivfpq(h)) rc.ivfpq = ivfpq_rows(h);
     if (L.use_i8 && h->scan.rows8.p) {
         rc.X8 = h->scan.rows8.as<signed char>(); rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
@@ -657,7 +659,7 @@ void ivf_search_lists(const IvfBatch &b) {
     ivf_lists_prep(b, L);
     ivf_lists_plan(b, L);
     ScanArgs sa{};
-    sa.panels = sq8(h) ? ivf_sq8_panels(b) : h->scan.panels.as<half8>();
+    sa.panels = sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
     sa.bias = h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -711,6 +713,7 @@ void ivf_search_exact(const IvfBatch &b) {
     IvfScanArgs a{};
     a.c = RefineCommon{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
+    if (ivfpq(h)) a.c.ivfpq = ivfpq_rows(h);  // (IVF-PQ: likewise, centroid + codebook entry)
     a.offsets = h->lists.ivf_offsets.as<int64_t>();
     a.probes = h->plan.ivf_probe_i.as<int64_t>();
     a.nq = nb; a.nprobe = nprobe; a.S = (int)S;
@@ -897,17 +900,26 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
     return guarded([&] {
         auto *h = check(hh);
         pq_refuse_ivf(h);
-        ivf_require(codec == 0 || codec == 1, VDB_ERR_INVALID, "codec must be 0 (Flat) or 1 (SQ8)");
+        ivf_require(codec >= 0 && codec <= 2, VDB_ERR_INVALID, "codec must be 0 (Flat), 1 (SQ8) or 2 (PQ)");
         if (h->multi) {
             if (codec == 1) multi_unsupported("the SQ8 codec");
+            if (codec == 2) multi_unsupported("the IVF-PQ codec");
             return;
         }
-        if (codec == 1) lsh_refuse_ivf(h);
+        if (codec != 0) lsh_refuse_ivf(h);
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
         if (codec == 1) {
             ivf_require(!h->opt.graph, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");
             ivf_require(!h->opt.int8_only && !h->opt.stream_panels, VDB_ERR_UNSUPPORTED,
                         "options 'int8_only' and 'stream_panels' do not combine with the SQ8 codec");
+        }
+        if (codec == 2)
+            ivf_require(!h->opt.graph && !h->opt.int8_only && !h->opt.stream_panels, VDB_ERR_UNSUPPORTED,
+                        "options 'graph', 'int8_only' and 'stream_panels' are not available on an IVF-PQ index");
+        if (codec != 2) {                       // (codebooks belong to codec 2)
+            h->ivfpq_M = h->ivfpq_dsub = 0;
+            h->ivfpq_cb_host.clear();
+            h->kept.ivfpq_cb.release();
         }
         h->ivf_codec = codec;
     });
@@ -918,6 +930,7 @@ int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
         auto *h = check(hh);
         pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_train_ranges");
+        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_train_ranges");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
@@ -932,6 +945,7 @@ int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *v
         auto *h = check(hh);
         pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_set_ranges");
+        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_set_ranges");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
         for (int d = 0; d < h->dim; ++d)
@@ -949,6 +963,7 @@ int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
         auto *h = check(hh);
         pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_sq8_get_ranges");
+        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_get_ranges");
         ivf_require(sq8(h) && h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
         memcpy(vmin_host, h->sq8_vmin.data(), (size_t)h->dim * sizeof(float));
@@ -961,6 +976,7 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
         auto *h = check(hh);
         pq_refuse_ivf(h);
         if (h->multi) multi_unsupported("vdb_ivf_get_codes");
+        sq8_refuse_ivfpq(h, "vdb_ivf_get_codes");
         ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
@@ -974,6 +990,107 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
         VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
         for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
             memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * Dm, &c[(size_t)r * D4], (size_t)Dm);
+    });
+}
+
+int vdb_ivfpq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_ivf(h);
+        ivfpq_require(h, "vdb_ivfpq_set_codebooks");
+        ivfpq_check_M(h, M);
+        ivf_require(codebooks_host != nullptr, VDB_ERR_INVALID, "null codebook pointer");
+        set_device(h->device);
+        ivfpq_install_codebooks(h, M, codebooks_host);
+    });
+}
+
+int vdb_ivfpq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        ivf_require(M != nullptr, VDB_ERR_INVALID, "null pointer");
+        *M = (h->multi || !ivfpq(h)) ? 0 : h->ivfpq_M;
+        if (codebooks_host && *M > 0) memcpy(codebooks_host, h->ivfpq_cb_host.data(), h->ivfpq_cb_host.size() * sizeof(float));
+    });
+}
+
+int vdb_ivfpq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_ivf(h);
+        ivfpq_require(h, "vdb_ivfpq_train");
+        ivfpq_check_M(h, M);
+        ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
+        ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
+        ivf_require(n >= 256, VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
+        ivf_require(niter >= 0 && niter <= 1000, VDB_ERR_INVALID, "niter out of range");
+        if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
+        set_device(h->device);
+        const int D = h->dim, dsub = D / M;
+        // one row sample for every sub-space, drawn with `seed` (vdb_pq_train's draws), and its residuals against the
+        // installed centroids: r = x - c_l, one float32 subtraction per dimension
+        const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
+        const std::vector<int64_t> pick = sample_rows(n, ns, seed);
+        std::vector<float> res((size_t)ns * D);
+        for (int64_t i = 0; i < ns; ++i) memcpy(&res[(size_t)i * D], x_host + (size_t)pick[(size_t)i] * D, (size_t)D * sizeof(float));
+        {
+            DevBuf dx, dassign;
+            dx.reserve((size_t)ns * D * sizeof(float));
+            VDB_HIP(hipMemcpy(dx.p, res.data(), (size_t)ns * D * sizeof(float), hipMemcpyHostToDevice));
+            ivf_assign_rows(h, dx.as<float>(), ns, dassign);
+            std::vector<int64_t> assign((size_t)ns);
+            VDB_HIP(hipMemcpy(assign.data(), dassign.p, (size_t)ns * sizeof(int64_t), hipMemcpyDeviceToHost));
+            sq8_release_coarse_ws(h);
+            for (int64_t i = 0; i < ns; ++i) {
+                ivf_require(assign[(size_t)i] >= 0 && assign[(size_t)i] < h->nlist, VDB_ERR_INVALID, "row could not be assigned to a list");
+                const float *c = &h->ivf_centroids[(size_t)assign[(size_t)i] * D];
+                float *r = &res[(size_t)i * D];
+                for (int d = 0; d < D; ++d) r[d] = r[d] - c[d];
+            }
+        }
+        // sub-space m: the library's k-means (vdb_ivf_train on a flat L2 handle of dsub dims) over the residuals, seed + m
+        std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
+        for (int m = 0; m < M; ++m) {
+            for (int64_t i = 0; i < ns; ++i) memcpy(&sub[(size_t)i * dsub], &res[(size_t)i * D + (size_t)m * dsub], (size_t)dsub * sizeof(float));
+            vdb_handle t = nullptr;
+            int rc = vdb_create(dsub, VDB_METRIC_L2, h->device, &t);
+            if (rc == VDB_OK) rc = vdb_ivf_train(t, 256, sub.data(), ns, niter, seed + (uint64_t)m, max_points_per_centroid);
+            if (rc == VDB_OK) rc = vdb_ivf_get_centroids(t, &cb[(size_t)m * 256 * dsub]);
+            const std::string msg = rc == VDB_OK ? std::string() : g_last_error;
+            if (t) (void)vdb_destroy(t);
+            if (rc != VDB_OK) throw Error(rc, "k-means of sub-space " + std::to_string(m) + ": " + msg);
+        }
+        ivfpq_install_codebooks(h, M, cb.data());
+    });
+}
+
+int vdb_ivfpq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_t id_base, const int32_t *list_of_row_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_ivf(h);
+        ivfpq_require(h, "vdb_ivfpq_add_codes");
+        ivf_require(n >= 0 && (n == 0 || (codes_host && list_of_row_host)), VDB_ERR_INVALID, "null code or assignment pointer");
+        ivfpq_add(h, nullptr, codes_host, n, id_base, list_of_row_host);
+    });
+}
+
+int vdb_ivfpq_get_codes(vdb_handle hh, uint8_t *codes_host) {
+    return guarded([&] {
+        auto *h = check(hh);
+        pq_refuse_ivf(h);
+        ivfpq_require(h, "vdb_ivfpq_get_codes");
+        ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
+        ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
+        if (h->N == 0) return;
+        set_device(h->device);
+        const size_t M = (size_t)h->ivfpq_M;
+        std::vector<unsigned char> c((size_t)h->N * M);
+        std::vector<int64_t> ids((size_t)h->N);
+        VDB_HIP(hipDeviceSynchronize());
+        VDB_HIP(hipMemcpy(c.data(), h->codes.ivfpq_codes.p, c.size(), hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
+            memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * M, &c[(size_t)r * M], M);
     });
 }
 
@@ -992,6 +1109,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
             return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
         }
         if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
+        if (ivfpq(h)) return ivfpq_add(h, x_host, nullptr, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
         int64_t N0, N1;
@@ -1125,6 +1243,8 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
                         h->scan.rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, dq + (size_t)q0 * h->dim);
                 else if (pq_on(h))    // (product codes: the looked-up rows x^)
                     pq_decode_rows(h, 0, m, h->dim, dq + (size_t)q0 * h->dim, st);
+                else if (ivfpq(h))    // (residual product codes: the decoded rows x^)
+                    ivfpq_decode_rows(h, m, h->dim, dq + (size_t)q0 * h->dim, st);
                 else if (sq8(h))      // (codes: the decoded rows x^)
                     sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((m * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
                         sq8_rows(h), m, h->dim, h->D4, h->dim, dq + (size_t)q0 * h->dim);

@@ -9,6 +9,7 @@ inline bool lsh_on(const vdb_index_s *h) { return h->lsh_nbits > 0; }
 void lsh_refuse_handle(const vdb_index_s *h) {
     if (h->multi) multi_unsupported("sign-LSH");
     if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on a PQ index (it keeps no float32 rows)");
+    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF-PQ index (it keeps no float32 rows)");
     if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
         throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF index (centroids set or a codec chosen): its rows "
                                          "sit in list order");
@@ -51,6 +52,7 @@ void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
 void lsh_require_ready(vdb_index_s *h, const char *what) {
     if (h->multi) multi_unsupported(what);
     if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a PQ index");
+    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF-PQ index");
     if (!lsh_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no projection (call vdb_lsh_set_projection first)");
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
@@ -221,6 +223,7 @@ int vdb_lsh_get_codes(vdb_handle hh, uint32_t *codes_host) {
         auto *h = check(hh);
         if (h->multi) multi_unsupported("vdb_lsh_get_codes");
         if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "vdb_lsh_get_codes is not available on a PQ index");
+        if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "vdb_lsh_get_codes is not available on an IVF-PQ index");
         if (!lsh_on(h)) throw Error(VDB_ERR_STATE, "vdb_lsh_get_codes: no projection (call vdb_lsh_set_projection first)");
         if (!h->built || h->N == 0 || h->lsh_rows != h->N) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");

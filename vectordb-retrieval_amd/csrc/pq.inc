@@ -15,8 +15,12 @@ PqRows pq_rows(const vdb_index_s *h) {
 // handles that cannot become a PQ index (one device, no other row store, no option that needs resident rows or panels)
 void pq_refuse_handle(const vdb_index_s *h, const char *what) {
     if (h->multi) multi_unsupported(what);
+    if (h->ivf_codec == 2)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index: an IVF-PQ index takes its codebooks and codes "
+                                         "through vdb_ivfpq_*");
     if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index (IVF<nlist>,PQ<M> is not implemented)");
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index (IVF<nlist>,PQ<M> is a codec of the lists: "
+                                         "vdb_ivf_set_codec, vdb_ivfpq_*)");
     if (h->lsh_nbits > 0)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a sign-LSH projection");
     if (h->opt.int8_only || h->opt.stream_panels || h->opt.graph)
@@ -28,6 +32,9 @@ void pq_refuse_handle(const vdb_index_s *h, const char *what) {
 
 void pq_require_codebooks(const vdb_index_s *h, const char *what) {
     if (h->multi) multi_unsupported(what);
+    if (h->ivf_codec == 2)
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index: an IVF-PQ index takes its codebooks and codes "
+                                         "through vdb_ivfpq_*");
     if (!pq_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no codebooks (call vdb_pq_train or vdb_pq_set_codebooks first)");
 }
 

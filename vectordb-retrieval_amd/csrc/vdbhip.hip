@@ -28,6 +28,7 @@
 #include "ivf_mfma.hpp"
 #include "ivf_kloop.hpp"
 #include "ivf_sq8.hpp"
+#include "ivf_pq.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
 #include "pq.hpp"
@@ -179,9 +180,10 @@ struct ScanBufs {
 // what outlives the rows: the corpus statistics block, and what vdb_ivf_train / set_* installed   (freed with the handle)
 struct KeptBufs {
     DevBuf stats{"stats"};
-    DevBuf sq8_cent{"sq8_cent"}, sq8_param{"sq8_param"};     // SQ8: centroids [nlist][D4] and {vmin, vdiff} [2][D4], zero padded
+    DevBuf sq8_cent{"sq8_cent"}, sq8_param{"sq8_param"};     // SQ8: centroids [nlist][D4] (IVF-PQ too) and {vmin, vdiff} [2][D4], zero padded
     DevBuf lsh_rt{"lsh_rt"};                                 // sign-LSH: R transposed [dim][nbits]
     DevBuf pq_cb{"pq_cb"};                                   // PQ: codebooks float32 [M][256][dsub]
+    DevBuf ivfpq_cb{"ivfpq_cb"};                             // IVF-PQ: codebooks of the residuals, float32 [M][256][dsub]
 };
 // IVF: the CSR arrays and the panel space (lists padded to whole spans) of the filed rows      (freed by vdb_reset)
 struct IvfListBufs {
@@ -200,9 +202,10 @@ struct IvfPlanBufs {
 };
 // compressed codes of the rows                                                                (freed by vdb_reset)
 struct CodeBufs {
-    DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row, both in list order
+    DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row (IVF-PQ too), both in list order
     DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
     DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
+    DevBuf ivfpq_codes{"ivfpq_codes"};                       // IVF-PQ: codes [N][M] in list order
 };
 // per-search workspace of the LSH calls                                                       (freed with the handle)
 struct LshWorkspace {
@@ -220,7 +223,7 @@ struct Workspace {
     DevBuf dense{"ws.dense"};               // nq x Npad raw scores of the small-corpus path
     DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
-    DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8: the fp16 panels converted from the codes for the current batch
+    DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ: the fp16 panels converted from the codes for the current batch
 };
 
 // ---- options -----------------------------------------------------------------------------------------------------------------
@@ -360,10 +363,12 @@ struct vdb_index_s {
     int ivf_span_rows = kSpanRows;           // rows per panel span: 512 (32-row tiles, D <= 128) or 16 * ivf_tps (p16, D > 128)
     int ivf_tps = 0;                         // p16 tiles per span of the IVF panel space (16 / 64; option "ivf_tps" or the rule of ivf.inc)
     // codec of the inverted lists (vdb_ivf_set_codec): 0 Flat (float32 rows + scan copies) | 1 SQ8 (ivf_sq8.inc: 8-bit codes
-    // of the residuals, no float32 rows, no scan copies)
+    // of the residuals, no float32 rows, no scan copies) | 2 PQ (ivf_pq.inc: M-byte product codes of the residuals, likewise)
     int ivf_codec = 0;
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
+    int ivfpq_M = 0, ivfpq_dsub = 0;         // IVF-PQ: sub-spaces (0 = no codebooks yet) and dims of each -- NOT pq_M: that marks a flat PQ handle
+    std::vector<float> ivfpq_cb_host;        // host copy of the codebooks [M][256][dsub]
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
@@ -450,7 +455,8 @@ inline RefineCommon flat_rows(const vdb_index_s *h, const float *q, int k) {
 }
 inline void pq_refuse_ivf(const vdb_index_s *h) {       // an IVF entry point on a PQ handle
     if (!h->multi && pq_on(h))
-        throw Error(VDB_ERR_UNSUPPORTED, "this handle is a flat PQ index (vdb_pq_*): IVF<nlist>,PQ<M> is not implemented");
+        throw Error(VDB_ERR_UNSUPPORTED, "this handle is a flat PQ index (vdb_pq_*): an IVF-PQ index starts from vdb_ivf_set_codec on a "
+                                         "handle without codebooks");
 }
 [[noreturn]] inline void pq_rows_are_codes() {
     throw Error(VDB_ERR_UNSUPPORTED, "a PQ index holds its rows as codes: fill it with vdb_pq_add / vdb_pq_add_codes");
@@ -952,6 +958,7 @@ void add_rows(vdb_index_s *h, const float *x, bool on_device, int64_t n, int64_t
     if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
     if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
+    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "an IVF-PQ index holds its rows as codes: fill it with vdb_ivf_add");
     if (pq_on(h)) pq_rows_are_codes();
     set_device(h->device);
     const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
@@ -1138,6 +1145,7 @@ namespace {
 void rerank_device_impl(vdb_index_s *h, const float *dq, int64_t nq, const int64_t *cand, int ncand, int k, float *D,
                         int64_t *I, hipStream_t st, double *pk = nullptr, int64_t *pi = nullptr, const int64_t *segs = nullptr,
                         int nseg = 0) {
+    if (h->ivf_codec == 2) throw Error(VDB_ERR_STATE, "vdb_rerank is not available on an IVF-PQ index: its rows are codes in list order");
     if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
     if (nq < 0 || ncand < 0) throw Error(VDB_ERR_INVALID, "negative size");
@@ -1182,6 +1190,7 @@ int vdb_rerank(vdb_handle hh, const float *q_host, int64_t nq, const int64_t *ca
     return guarded([&] {
         auto *h = check(hh);
         if (h->multi) return multi_rerank(h, q_host, false, nq, cand_host, ncand, k, D, I, nullptr);
+        if (h->ivf_codec == 2) throw Error(VDB_ERR_STATE, "vdb_rerank is not available on an IVF-PQ index: its rows are codes in list order");
         if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (nq <= 0) {
             if (nq < 0) throw Error(VDB_ERR_INVALID, "negative query count");
@@ -1235,7 +1244,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
-        if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit codes
+        if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
@@ -1291,11 +1300,12 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
 
 namespace {
 // kinds of index that refuse a non-zero value of an option, in the order they are asked
-constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4;
+constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4, kIvfPq = 8;
 constexpr struct { unsigned kind; const char *what; } kRefusals[] = {
     {kSq8, "an SQ8 index"},
     {kLsh, "an index with sign-LSH codes (they are encoded from, and re-ranked against, the resident float32 rows)"},
-    {kPq, "a PQ index (its rows are codes; every search makes its panels from them)"}};
+    {kPq, "a PQ index (its rows are codes; every search makes its panels from them)"},
+    {kIvfPq, "an IVF-PQ index (its rows are codes; every batch makes its panels from them)"}};
 
 struct OptionRow {
     const char *name;
@@ -1311,16 +1321,16 @@ constexpr OptionRow kOptions[] = {
     {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
     {"list_cap", &Options::list_cap, 0, {0, 65536}},
     {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
-    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq},
+    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq},
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
-    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
+    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
     {"stream_slab_rows", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::stream_slab_rows},   // rows of the scratch slab of a streamed index (0 = default 1 280 000)
     {"upload_block_mb", &Options::upload_block_mb, 0, {0, 4096}},    // staging block of the row-block ingestion (0 = default 64 MiB)
     {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
     {"fused_stats", &Options::fused_stats, 2, {0, 1}},               // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
     {"ivf_min_batch", &Options::ivf_min_batch, 0, {1, 1e9}},
-    {"graph", &Options::graph, 2, {0, 1}, kSq8 | kPq},
+    {"graph", &Options::graph, 2, {0, 1}, kSq8 | kPq | kIvfPq},
     {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
@@ -1359,7 +1369,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
         const bool known = r != std::end(kOptions);
         // what this kind of index refuses comes first, whatever the value is otherwise
-        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0);
+        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0) | (h->ivf_codec == 2 ? kIvfPq : 0);
         for (const auto &x : kRefusals)
             if (known && value != 0 && (kinds & r->not_on & x.kind))
                 throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on " + x.what);

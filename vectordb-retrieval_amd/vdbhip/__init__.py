@@ -1,4 +1,4 @@
-"""vdbhip -- MI355X-native exact / IVF-Flat k-NN behind the vectordb-retrieval plugin API.
+"""vdbhip -- MI355X-native exact / IVF k-NN behind the vectordb-retrieval plugin API.
 
 Importing the package does not touch the GPU and does not import torch; the shared library
 (libvdbhip.so, hand-written HIP for gfx950) is dlopen'ed on first use and there is no CPU fallback.
@@ -9,6 +9,7 @@ from .plugin_api import (ALGORITHM_REGISTRY, INDEXER_REGISTRY, SEARCHER_REGISTRY
 from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher, rerank_candidates
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
 from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
+from .ivf_pq import HipIVFPQIndexer, HipIVFPQSearch, IVFPQIndex, parse_ivfpq_key
 from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
 from .pq import HipPQIndexer, HipPQSearch, HipPQSearcher, PQIndex, parse_pq_key
 from . import sharded
@@ -20,6 +21,7 @@ __all__ = [
     "register_algorithm", "register_indexer", "register_searcher", "HipExactSearch", "HipBruteForceIndexer",
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
     "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
+    "HipIVFPQIndexer", "HipIVFPQSearch", "IVFPQIndex", "parse_ivfpq_key",
     "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipPQIndexer", "HipPQSearcher", "HipPQSearch", "PQIndex",
     "parse_pq_key", "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",

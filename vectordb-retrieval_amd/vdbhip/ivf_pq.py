@@ -1,0 +1,301 @@
+"""IVF<nlist>,PQ<M> on the MI355X behind the reference's `FaissFactoryIndexer index_key: IVF...,PQ...` entries.
+
+  HipIVFPQIndexer   drop-in for FaissFactoryIndexer with an "IVF<nlist>,PQ<M>" key   (src/algorithms/modular.py:224-309);
+                    its artifact is the 'hip_ivf' one HipIVFSearcher attaches to (searcher `nprobe` override, cosine =
+                    normalise + inner product, distances negated for cosine / ip)
+  HipIVFPQSearch    BaseAlgorithm form for `type:` entries (`index_type="IVF256,PQ64"`), raw conventions of
+                    HipApproximateSearch, with save_index / load_index
+
+The inverted lists hold 8-bit product codes of the residuals x - c_l: M bytes per row, no float32 rows.  A search returns,
+bit for bit, the IVF-Flat result of this library over the decoded rows x^ = c_l + codebook entries under the same lists and
+nprobe (include/vdbhip.h, vdb_ivfpq_*).  FAISS' k-means, its float32 table sums and its order among equal distances are not
+reproduced: centroids and codebooks come from the library's own k-means (FAISS' defaults: 25 iterations, at most 256
+training points per centroid) and ties go to the smaller id.
+
+The IVF and flat-PQ parsers and classes (parse_index_key, parse_ivf_key, parse_pq_key, HipApproximateSearch, HipIVFIndexer,
+HipPQSearch) keep refusing these keys: the codec lives behind the names of this module only.
+"""
+from __future__ import annotations
+
+import ctypes
+import re
+from typing import Any, Optional, Tuple
+
+import numpy as np
+
+from . import _ffi
+from .index import normalize_devices
+from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
+from .ivf import IVFFlatIndex
+from .plugin_api import (BaseAlgorithm, BaseIndexer, IndexArtifact, Metadata, SearchResult, register_algorithm,
+                         register_indexer)
+
+_IVFPQ_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*PQ(\d+)(?:x8)?\s*$")
+_ONE_GPU = "IVF<nlist>,PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available"
+
+
+def parse_ivfpq_key(key: str) -> Tuple[int, int]:
+    """(nlist, M) of an "IVF<nlist>,PQ<M>" / "IVF<nlist>,PQ<M>x8" key; every other key (any other bit width, OPQ, a flat
+    "PQ<M>", the Flat and SQ8 codecs) raises ValueError."""
+    m = _IVFPQ_KEY.match(str(key))
+    if not m or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+        raise ValueError(f"unsupported index key {key!r}: only 'IVF<nlist>,PQ<M>' (8 bits per sub-vector) is implemented here")
+    return int(m.group(1)), int(m.group(2))
+
+
+def _check_m(dim: int, M: int) -> None:
+    if M < 1 or M > min(dim, 256) or dim % M:
+        raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
+
+
+class IVFPQIndex(IVFFlatIndex):
+    """Device-resident IVF<nlist>,PQ<M> index (replaces faiss.index_factory(d, "IVFn,PQm", metric)).  `train` fits the
+    centroids and then the codebooks of the residuals on the same rows; `set_centroids` + `train_codebooks` /
+    `set_codebooks` inject them instead.  One GPU only."""
+
+    def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0):
+        if isinstance(normalize_devices(device), list):
+            raise ValueError(_ONE_GPU)
+        _check_m(int(dim), int(M))
+        super().__init__(dim, nlist, metric, device)
+        self.M, self.dsub = int(M), int(dim) // int(M)
+        _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 2), build_time=True)
+
+    def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
+        super().train(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid)
+        self.train_codebooks(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid)
+
+    def train_codebooks(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
+        """Codebooks from the residuals of a row sample of `x` against the installed centroids."""
+        x = _ffi.as_f32_c(x)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        _ffi.check(self._lib.vdb_ivfpq_train(self._handle(), self.M, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
+                                             int(max_points_per_centroid)), build_time=True)
+        self.ntotal = 0             # (new codebooks: rows encoded under the old ones are dropped)
+
+    def set_codebooks(self, codebooks: np.ndarray) -> None:
+        c = _ffi.as_f32_c(codebooks)
+        if c.shape != (self.M, 256, self.dsub):
+            raise ValueError(f"expected ({self.M}, 256, {self.dsub}) codebooks, got {c.shape}")
+        _ffi.check(self._lib.vdb_ivfpq_set_codebooks(self._handle(), self.M, _ffi.ptr(c)), build_time=True)
+        self.ntotal = 0
+
+    def codebooks(self) -> np.ndarray:
+        m = ctypes.c_int(0)
+        _ffi.check(self._lib.vdb_ivfpq_get_codebooks(self._handle(), ctypes.byref(m), None))
+        if m.value != self.M:
+            raise RuntimeError("no codebooks: train the index or set them first")
+        out = np.empty((self.M, 256, self.dsub), np.float32)
+        _ffi.check(self._lib.vdb_ivfpq_get_codebooks(self._handle(), ctypes.byref(m), _ffi.ptr(out)))
+        return out
+
+    def add_codes(self, codes: np.ndarray, list_of_row: np.ndarray, id_base: int = 0) -> None:
+        """Append rows given as codes, uint8 (n, M), under the given lists: what loading a persisted index does."""
+        c = np.ascontiguousarray(codes, dtype=np.uint8)
+        if c.ndim != 2 or c.shape[1] != self.M:
+            raise ValueError(f"expected (n, {self.M}) codes, got {c.shape}")
+        lor = np.ascontiguousarray(list_of_row, dtype=np.int32)
+        if lor.shape != (c.shape[0],):
+            raise ValueError(f"expected {c.shape[0]} list ids, got {lor.shape}")
+        try:
+            _ffi.check(self._lib.vdb_ivfpq_add_codes(self._handle(), _ffi.ptr(c), c.shape[0], int(id_base), _ffi.ptr(lor)),
+                       build_time=True)
+        finally:
+            self.ntotal = int(self.stats()["ntotal"])
+
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, M) codes in id (insertion) order."""
+        out = np.empty((self.ntotal, self.M), np.uint8)
+        _ffi.check(self._lib.vdb_ivfpq_get_codes(self._handle(), _ffi.ptr(out)))
+        return out
+
+    def reconstruct(self) -> np.ndarray:
+        """float32 (ntotal, dim) rows x^ in id order: centroid of the row's list + codebook entries, one float32 add."""
+        codes, cb, cent, lor = self.codes(), self.codebooks(), self.centroids(), self.assignment()
+        look = np.concatenate([cb[m][codes[:, m]] for m in range(self.M)], axis=1).astype(np.float32)
+        return np.ascontiguousarray(cent[lor] + look, dtype=np.float32)
+
+
+def _build_ivfpq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> IVFPQIndex:
+    nlist, M = parse_ivfpq_key(key)
+    index = IVFPQIndex(dim, nlist, M, metric, device)
+    index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
+                max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
+    index.add(vectors)
+    return index
+
+
+def _check_key(dimension: int, key: str, device) -> Tuple[int, int]:
+    nlist, m = parse_ivfpq_key(key)
+    if dimension % m or m > min(dimension, 256):
+        raise ValueError(f"PQ{m} needs a dimension that is a multiple of {m} (and M <= 256); got {dimension}")
+    if isinstance(device, list):
+        raise ValueError(_ONE_GPU)
+    return nlist, m
+
+
+class HipIVFPQIndexer(BaseIndexer):
+    """FaissFactoryIndexer semantics for an "IVF<nlist>,PQ<M>" key; the artifact is HipIVFSearcher's ('hip_ivf')."""
+
+    def __init__(self, name: str, dimension: int, metric: str = "l2", index_type: Optional[str] = None,
+                 index_key: Optional[str] = None, **kwargs: Any) -> None:
+        key = index_key or index_type or "IVF100,PQ8"
+        params = dict(kwargs)
+        params.setdefault("index_type", key)
+        super().__init__(name, dimension, metric, **params)
+        self.index_key = self.index_type = key
+        _check_key(dimension, key, _resolve_device(self.params.get("device"), self.params.get("device_ids")))
+
+    def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
+        if vectors.shape[1] != self.dimension:
+            raise ValueError(f"Expected dimension {self.dimension}, got {vectors.shape[1]}")
+        data = _ffi.as_f32_c(vectors)
+        meta = {"metric": self.metric, "index_key": self.index_key, "faiss_metric": "l2"}
+        metric = "l2"
+        if self.metric == "cosine":
+            data = _safe_normalize(data)
+            metric = "ip"
+            meta.update({"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True})
+        elif self.metric == "ip":
+            metric = "ip"
+            meta["faiss_metric"] = "ip"
+        device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
+        index = _build_ivfpq(data, self.dimension, self.index_key, metric, device, self.params)
+        if "nprobe" in self.params:                       # runtime attribute of the index (modular.py:269-275)
+            index.set_nprobe(int(self.params["nprobe"]))
+            meta["nprobe"] = self.params["nprobe"]
+        reserve_workspace(index, self.params)
+        return IndexArtifact(kind="hip_ivf", data=index, metadata=meta)
+
+
+class HipIVFPQSearch(BaseAlgorithm):
+    """ApproximateSearch semantics for `index_type="IVF<nlist>,PQ<M>"`: train -> add -> nprobe from kwargs; raw FAISS
+    conventions (no normalisation, no sign flip: 'l2' -> squared L2, anything else -> raw inner product)."""
+
+    _FORMAT = "vdbhip-ivfpq-v1"
+
+    def __init__(self, name: str, dimension: int, index_type: str = "IVF100,PQ8", metric: str = "l2",
+                 device: Optional[int] = None, **kwargs: Any) -> None:
+        super().__init__(name, dimension, **kwargs)
+        self.index_type = index_type
+        self.metric = "l2" if metric == "l2" else "ip"
+        self.device = _resolve_device(device, kwargs.get("device_ids"))
+        self.index: Optional[IVFPQIndex] = None
+        _check_key(dimension, index_type, self.device)        # fail at construction, like a bad factory string
+
+    def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
+        data = np.asarray(vectors).astype(np.float32)
+        self.index = _build_ivfpq(data, self.dimension, self.index_type, self.metric, self.device, self.config)
+        self.index_built = True
+        if "nprobe" in self.config:
+            self.index.set_nprobe(int(self.config["nprobe"]))
+        reserve_workspace(self.index, self.config)
+
+    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
+        if not self.index_built:
+            raise RuntimeError("Index has not been built yet.")
+        d, i = self.index.search(np.array([query], dtype=np.float32), k)
+        return d[0], i[0]
+
+    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
+        if not self.index_built:
+            raise RuntimeError("Index has not been built yet.")
+        return self.index.search(np.asarray(queries).astype(np.float32), k)
+
+    def get_memory_usage(self) -> float:
+        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+
+    # ---- persistence (protocol of HipApproximateSearch: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ----------
+    # An IVF-PQ artifact is the index itself: centroids, codebooks, codes and the list of every row.  No corpus file -- the
+    # index holds no float32 rows -- and loading neither clusters nor encodes.
+    _FILES = ("centroids", "codebooks", "codes", "list_of_row")
+
+    def save_index(self, artifact_dir: str, context=None):
+        import hashlib
+        import json
+        import shutil
+        import tempfile
+        from pathlib import Path
+
+        if not self.index_built or self.index is None:
+            raise RuntimeError("Cannot persist HipIVFPQSearch before build_index has completed.")
+        context = context or {}
+        target = Path(artifact_dir)
+        target.parent.mkdir(parents=True, exist_ok=True)
+        if target.exists():
+            if not bool(context.get("force_rebuild", False)):
+                raise FileExistsError(f"Artifact directory already exists: {target}. "
+                                      "Set persistence.force_rebuild=true to overwrite.")
+            shutil.rmtree(target)
+        tmp = Path(tempfile.mkdtemp(prefix=f".{target.name}.tmp.", dir=str(target.parent)))
+        try:
+            arrays = {"centroids": self.index.centroids(), "codebooks": self.index.codebooks(), "codes": self.index.codes(),
+                      "list_of_row": self.index.assignment()}
+            for name, arr in arrays.items():
+                np.save(tmp / f"{name}.npy", arr, allow_pickle=False)
+            build_metrics = dict(context.get("build_metrics", {}))
+            manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
+                        "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist, "M": self.index.M,
+                        "nprobe": self.index.nprobe, "id_base": 0, "n_vectors": int(self.index.ntotal),
+                        "config_hash": context.get("config_hash"),
+                        "sha256": {name: hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest()
+                                   for name, arr in arrays.items()},
+                        "files": {name: f"{name}.npy" for name in arrays}}
+            (tmp / "manifest.json").write_text(json.dumps(manifest, indent=2), encoding="utf-8")
+            (tmp / "build_metrics.json").write_text(json.dumps(build_metrics, indent=2), encoding="utf-8")
+            (tmp / "WRITE_COMPLETE").write_text("ok\n", encoding="utf-8")
+            tmp.rename(target)
+        except Exception:
+            shutil.rmtree(tmp, ignore_errors=True)
+            raise
+        return {"artifact_dir": str(target), "manifest_path": str(target / "manifest.json"),
+                "build_time_s": float(build_metrics.get("build_time_s", 0.0) or 0.0)}
+
+    def load_index(self, artifact_dir: str, context=None):
+        import hashlib
+        import json
+        from pathlib import Path
+
+        path = Path(artifact_dir)
+        if not path.is_dir():
+            raise FileNotFoundError(f"Persisted HipIVFPQSearch artifact directory not found: {path}")
+        if not (path / "WRITE_COMPLETE").is_file():
+            raise FileNotFoundError(f"Artifact is incomplete or corrupted (missing WRITE_COMPLETE): {path}")
+        manifest = json.loads((path / "manifest.json").read_text(encoding="utf-8"))
+        for key, want in (("format", self._FORMAT), ("dimension", self.dimension), ("index_type", self.index_type),
+                          ("metric", self.metric)):
+            if manifest.get(key) != want:
+                raise ValueError(f"Persisted index mismatch for '{key}': artifact has {manifest.get(key)!r}, "
+                                 f"this instance expects {want!r}")
+        expected_hash = (context or {}).get("config_hash")
+        if expected_hash and manifest.get("config_hash") and manifest["config_hash"] != expected_hash:
+            raise ValueError("Persisted index was built with a different configuration (config_hash mismatch)")
+        nlist, m = parse_ivfpq_key(self.index_type)
+        arrays = {name: np.load(path / manifest["files"][name]) for name in self._FILES}
+        n = int(manifest.get("n_vectors", arrays["codes"].shape[0]))
+        lists = arrays["list_of_row"]
+        if arrays["centroids"].shape != (nlist, self.dimension) or arrays["codebooks"].shape != (m, 256, self.dimension // m) \
+                or arrays["codes"].shape != (n, m) or arrays["codes"].dtype != np.uint8 or lists.shape != (n,) \
+                or (n and (lists.min() < 0 or lists.max() >= nlist)):
+            raise ValueError("Persisted IVF-PQ files do not match the manifest")
+        want = manifest.get("sha256") or {}
+        for name in self._FILES:
+            if want.get(name) and hashlib.sha256(np.ascontiguousarray(arrays[name]).tobytes()).hexdigest() != want[name]:
+                raise ValueError(f"Persisted index files do not belong together (fingerprint mismatch: {name})")
+        self.index = IVFPQIndex(self.dimension, nlist, m, self.metric, self.device)
+        self.index.set_centroids(arrays["centroids"])      # no k-means, no assignment and no encoding pass: the stored
+        self.index.set_codebooks(arrays["codebooks"])      # index is reused as it is
+        self.index.add_codes(arrays["codes"], lists, id_base=int(manifest.get("id_base", 0)))
+        self.index.set_nprobe(int(self.config.get("nprobe", manifest.get("nprobe", 1))))
+        self.index_built = True
+        metrics = {}
+        bm = path / "build_metrics.json"
+        if bm.is_file():
+            metrics = json.loads(bm.read_text(encoding="utf-8"))
+        return {"artifact_dir": str(path), "manifest_path": str(path / "manifest.json"),
+                "build_time_s": float(metrics.get("build_time_s", 0.0) or 0.0)}
+
+
+register_algorithm("HipIVFPQSearch", HipIVFPQSearch)
+register_indexer("HipIVFPQIndexer", HipIVFPQIndexer)
