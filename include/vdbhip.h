@@ -55,7 +55,7 @@ enum vdb_status {
 };
 
 /* which search path served the last call (vdb_stats_t.last_path) */
-enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4 };
+enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5 };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -339,6 +339,48 @@ int vdb_pq_add_codes(vdb_handle h, const uint8_t *codes_host, int64_t n, int64_t
 /* codes of the indexed rows, uint8 (ntotal, M), in id (insertion) order */
 int vdb_pq_get_codes(vdb_handle h, uint8_t *codes_host);
 
+/* ---- k-NN graph ("knng"; "graph" already names hipGraph replay in this ABI) -- the slot the reference fills with HNSW
+ *      (HNSWIndexer + FaissSearcher and the stand-alone HNSW class of its benchmark configs): an exact k-NN graph of the corpus,
+ *      pruned by the HNSW neighbour heuristic, searched by a beam search ----------------------------------------------------------
+ * The entry points live on an ordinary flat handle of vdb_create that holds float32 rows; the graph is ntotal x degree int32 next
+ * to them (it counts in bytes_resident).  The contract is the library's own, deterministic (FAISS' level draw, its float32
+ * distances and its tie order are not reproduced; tests/knng_restatement.py restates it in NumPy):
+ *   key(u, v)   the canonical float64 order key above (L2 or IP by the index metric), row u's float32 values as the query, row v as
+ *               the row.  Every order is by (key, local row number), ascending
+ *   candidates  of row i: the first ncand entries of the sorted list of all rows j != i (fewer when ntotal - 1 < ncand)
+ *   neighbours  of row i: walk the candidates in order with an empty selected list S; candidate e is selected if |S| < degree and no
+ *               s in S has key(e, s) < key(i, e) (strict: a tie accepts), else rejected.  The stored row is S, then the rejected
+ *               candidates in candidate order until degree entries exist, then -1.  ncand == degree: the plain k-NN graph, reordered
+ *   search      k <= ef <= 512.  L: at most ef entries (key, id, expanded), ordered by (key, id).  Init: score the distinct rows
+ *               floor(j ntotal / nentry), j < min(nentry, ef, ntotal), and insert them.  Step: take the first unexpanded entry of L
+ *               (none: stop), mark it expanded, score every neighbour of it that is not in L now, L <- best ef of (L u scored).
+ *               Stop also after max_iters steps.  Result: the first k of L, flat conventions (id_base added, -1 / +-FLT_MAX padding,
+ *               distances = the float32 rounding of the key)
+ * A row scored earlier that is not in L now was rejected or evicted against a last key that has only decreased since: scoring it
+ * again rejects it again.  So the kernel's per-query "seen" filter is a cache (whole ids, a collision forgets; option
+ * "knng_visited_bits" never changes a result), and only the de-duplication against L is exact.
+ * vdb_add, vdb_add_device and vdb_reset drop the graph: vdb_knng_get then reports degree 0 and a search returns VDB_ERR_STATE.  The
+ * flat search of the handle is untouched.  VDB_ERR_UNSUPPORTED, with a message naming the k-NN graph, in either order of the two
+ * calls: a vdb_create_multi handle; an IVF handle (centroids or a codec); a PQ handle; a handle with an LSH projection (and the LSH
+ * calls on a handle with a graph); options "int8_only" / "stream_panels"; option "graph" = 1 together with the search calls; a
+ * dimension whose padded query does not fit a workgroup's LDS (above roughly 14 000).  VDB_ERR_INVALID: k < 1, k > ef, ef > 512, a degree or
+ * ncand out of range.  vdb_stats after a search: last_path = VDB_PATH_KNNG, last_candidates = rows scored (summed over the
+ * queries), last_fallback_queries = queries the step cap stopped with an unexpanded entry left; with option "timing" the three stages
+ * run as three launches: last_prep_ms = entry scoring, last_scan_ms = the traversal, last_tail_ms = writing the results. */
+/* builds the graph of the rows present: degree in 4..64, ncand in degree..128, ntotal below 2^31.  Blocks of "knng_build_block" rows go
+ * through the partial device search as queries (k = min(ncand + 1, ntotal)); the row itself is stripped, the rest pruned */
+int vdb_knng_build(vdb_handle h, int degree, int ncand);
+/* injects a graph: nbrs_host (ntotal, degree) local row numbers, degree in 1..64, -1 only as a row's tail.  Checked on the host:
+ * VDB_ERR_INVALID for an entry out of range, a self loop, a duplicate within a row, an entry after a -1 */
+int vdb_knng_set(vdb_handle h, int degree, const int32_t *nbrs_host);
+/* nbrs_host may be NULL: degree only (0 = no graph) */
+int vdb_knng_get(vdb_handle h, int *degree, int32_t *nbrs_host);
+/* host buffers, synchronous: D (nq, k) float32, I (nq, k) int64 */
+int vdb_knng_search(vdb_handle h, const float *q_host, int64_t nq, int k, int ef, float *D, int64_t *I);
+/* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised (the first search, and one whose (ntotal, knng_nentry, ef)
+ * give another list of entry rows, waits for `stream` once and uploads that list) */
+int vdb_knng_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, int ef, float *D_dev, int64_t *I_dev, void *stream);
+
 /* Sizes the search workspace for batches of up to nq queries and top-k NOW instead of inside the first search (works on
  * flat and IVF handles after add): one untimed search whose queries are corpus rows.  The reference times its very first
  * batch_search, allocations included (experiment_runner.py:431-437; metrics_methodology.md:119-121: no warm-up) -- the
@@ -395,6 +437,12 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
  *                       kernels on the codes (0 = default .. 1e9)
  *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)
+ *     "knng_nentry"     k-NN graph: entry points of a search, 0 (default: 32) .. 512
+ *     "knng_max_iters"  k-NN graph: step cap of a search, 0 (default: 8 ef) .. 2^31 - 1
+ *     "knng_visited_bits"  k-NN graph: log2 slots of the per-query seen filter, 0 (default: up to 12, the largest that keeps a query
+ *                       within 20 KiB of LDS -- 8 waves per CU) .. 14; a filter that does not fit a workgroup's 64 KiB is made
+ *                       smaller.  1 is legal; no value changes a result
+ *     "knng_build_block"  k-NN graph: rows per self-search block of vdb_knng_build, 0 (default: 65 536) .. 1e9
  *     "multi_stage_all" multi-device handles only (vdb_create_multi; every other option is forwarded to each shard, and "graph"
  *                       = 1 is VDB_ERR_UNSUPPORTED there): 1 (tests) shards on devices[0] take the remote-shard path too
  *     "graph_recapture_at_once"  diagnostic, 0 (default) | 1: the pre-round-3 ordering, for re-checking that defect

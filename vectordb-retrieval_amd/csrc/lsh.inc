@@ -8,6 +8,7 @@ inline bool lsh_on(const vdb_index_s *h) { return h->lsh_nbits > 0; }
 // handles that cannot carry LSH codes (no resident float32 rows in insertion order on ONE device)
 void lsh_refuse_handle(const vdb_index_s *h) {
     if (h->multi) multi_unsupported("sign-LSH");
+    knng_refuse_other(h, "a sign-LSH projection");
     if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on a PQ index (it keeps no float32 rows)");
     if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF-PQ index (it keeps no float32 rows)");
     if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
@@ -21,6 +22,7 @@ void lsh_refuse_handle(const vdb_index_s *h) {
 
 // an IVF entry point on a handle that carries a projection
 void lsh_refuse_ivf(const vdb_index_s *h) {
+    knng_refuse_other(h, "an IVF index");
     if (!h->multi && lsh_on(h))
         throw Error(VDB_ERR_UNSUPPORTED, "this handle carries a sign-LSH projection (vdb_lsh_set_projection): it stays a flat index");
 }
@@ -53,6 +55,7 @@ void lsh_require_ready(vdb_index_s *h, const char *what) {
     if (h->multi) multi_unsupported(what);
     if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a PQ index");
     if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF-PQ index");
+    knng_refuse_other(h, what);
     if (!lsh_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no projection (call vdb_lsh_set_projection first)");
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");

@@ -23,6 +23,7 @@ void pq_refuse_handle(const vdb_index_s *h, const char *what) {
                                          "vdb_ivf_set_codec, vdb_ivfpq_*)");
     if (h->lsh_nbits > 0)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a sign-LSH projection");
+    knng_refuse_other(h, what);
     if (h->opt.int8_only || h->opt.stream_panels || h->opt.graph)
         throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'int8_only', 'stream_panels' and 'graph'");
     if (h->opt.flat_shape == 32 || h->opt.f16_group != 8 || h->opt.i8_group != 8)

@@ -32,6 +32,7 @@
 #include "dense.hpp"
 #include "lsh.hpp"
 #include "pq.hpp"
+#include "knng.hpp"
 
 using namespace vdb;
 
@@ -206,11 +207,16 @@ struct CodeBufs {
     DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
     DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
     DevBuf ivfpq_codes{"ivfpq_codes"};                       // IVF-PQ: codes [N][M] in list order
+    DevBuf knng_nbrs{"knng_nbrs"};                           // k-NN graph: local row numbers [N][knng_degree], -1 tails
 };
 // per-search workspace of the LSH calls                                                       (freed with the handle)
 struct LshWorkspace {
     DevBuf lsh_qcodes{"lsh_qcodes"}, lsh_hist{"lsh_hist"}, lsh_small{"lsh_small"}, lsh_list{"lsh_list"}, lsh_stat{"lsh_stat"};
     DevBuf lsh_cand_i{"lsh_cand_i"}, lsh_cand_h{"lsh_cand_h"};
+};
+// per-search workspace of the k-NN graph search: the counters, and L between the launches of a timed call   (freed with the handle)
+struct KnngWorkspace {
+    DevBuf knng_stat{"knng_stat"}, knng_state_k{"knng_state_k"}, knng_state_i{"knng_state_i"}, knng_entry{"knng_entry"};
 };
 // per-search workspace                                                                        (freed with the handle)
 struct Workspace {
@@ -258,6 +264,11 @@ struct Options {
     int lsh_force_fallback = 0;              // every query of an LSH call takes the exact fallback of the select
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
+    // k-NN graph (knng.inc)
+    int knng_nentry = 0;                     // entry points of a search (0 = default 32)
+    int knng_max_iters = 0;                  // step cap of a search (0 = default 8 ef)
+    int knng_visited_bits = 0;               // log2 slots of the per-query seen filter (0 = default)
+    int knng_build_block = 0;                // rows per self-search block of the build (0 = default)
     // tuning of the flat scans
     int i8_variant = 3;                      // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)
     int i8_group = 8, f16_group = 8;         // rows per select group of the int8 / fp16 flat scan (4 or 8)
@@ -305,6 +316,7 @@ struct vdb_index_s {
     IvfPlanBufs plan;
     CodeBufs codes;
     LshWorkspace lsh_ws;
+    KnngWorkspace knng_ws;
     Workspace ws;
     Options opt;                             // what vdb_set_option has set; every other member is the library's own state
     int rows8_pitch = 0;
@@ -377,6 +389,9 @@ struct vdb_index_s {
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
     int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
     std::vector<float> pq_cb_host;           // host copy of the codebooks [M][256][dsub]
+    // k-NN graph of a flat index (knng.inc; vdb_knng_build / vdb_knng_set): ntotal x degree local row numbers next to the float32 rows
+    int knng_degree = 0;                     // 0 = no graph (any add and vdb_reset drop it)
+    std::vector<int32_t> knng_entries;       // the entry rows knng_ws.knng_entry holds (knng_search_impl)
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -393,7 +408,7 @@ struct vdb_index_s {
 namespace {
 
 template <class F>
-void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->ws); }
+void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); }
 
 // every byte of device memory the handle holds (its ws.small may be a view into plan.ivf_zero: not counted twice)
 size_t handle_bytes(vdb_index_s *h) {
@@ -438,6 +453,14 @@ long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
 inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
+inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
+void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
+// another kind of index (IVF, PQ, sign-LSH) asked for on a handle that carries a k-NN graph
+inline void knng_refuse_other(const vdb_index_s *h, const char *what) {
+    if (!h->multi && knng_on(h))
+        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a k-NN graph (vdb_knng_build / "
+                                                             "vdb_knng_set): it stays a flat index");
+}
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
@@ -961,6 +984,10 @@ void add_rows(vdb_index_s *h, const float *x, bool on_device, int64_t n, int64_t
     if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "an IVF-PQ index holds its rows as codes: fill it with vdb_ivf_add");
     if (pq_on(h)) pq_rows_are_codes();
     set_device(h->device);
+    if (knng_on(h)) {                          // (the graph describes the rows as they were)
+        VDB_HIP(hipDeviceSynchronize());
+        knng_drop(h);
+    }
     const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
     append_rows(h, x, on_device, n, id_base, st);
     lsh_encode_rows(h, n0, st);
@@ -1075,6 +1102,7 @@ int vdb_reset(vdb_handle hh) {
         group_release(h->lists);
         group_release(h->codes);
         h->lsh_rows = 0;                       // (the projection stays)
+        h->knng_degree = 0;                    // (the graph went with the codes group)
     });
 }
 
@@ -1225,7 +1253,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
         s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
-        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
+        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
@@ -1275,6 +1303,15 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             for (int sh = 0; sh < kStatShards; ++sh) s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
         }
+        if (h->last.last_path == VDB_PATH_KNNG && h->knng_ws.knng_stat.p) {   // rows scored / queries the step cap stopped, last k-NN graph search
+            std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
+            VDB_HIP(hipDeviceSynchronize());
+            VDB_HIP(hipMemcpy(c.data(), h->knng_ws.knng_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (int sh = 0; sh < kStatShards; ++sh) {
+                s.last_candidates += (int64_t)c[(size_t)sh * kStatStride];
+                s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride + 1];
+            }
+        }
         if (h->ev_used > 0) {  // averages over every search recorded since timing was switched on
             double scan = 0.0, total = 0.0, prep = 0.0, tail = 0.0;
             for (size_t i = 0; i < h->ev_used; ++i) {
@@ -1300,12 +1337,13 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
 
 namespace {
 // kinds of index that refuse a non-zero value of an option, in the order they are asked
-constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4, kIvfPq = 8;
+constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4, kIvfPq = 8, kKnng = 16;
 constexpr struct { unsigned kind; const char *what; } kRefusals[] = {
     {kSq8, "an SQ8 index"},
     {kLsh, "an index with sign-LSH codes (they are encoded from, and re-ranked against, the resident float32 rows)"},
     {kPq, "a PQ index (its rows are codes; every search makes its panels from them)"},
-    {kIvfPq, "an IVF-PQ index (its rows are codes; every batch makes its panels from them)"}};
+    {kIvfPq, "an IVF-PQ index (its rows are codes; every batch makes its panels from them)"},
+    {kKnng, "an index with a k-NN graph (it is searched against the resident float32 rows)"}};
 
 struct OptionRow {
     const char *name;
@@ -1321,10 +1359,10 @@ constexpr OptionRow kOptions[] = {
     {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
     {"list_cap", &Options::list_cap, 0, {0, 65536}},
     {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
-    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq},
+    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq | kKnng},
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
-    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
+    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq | kKnng},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
     {"stream_slab_rows", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::stream_slab_rows},   // rows of the scratch slab of a streamed index (0 = default 1 280 000)
     {"upload_block_mb", &Options::upload_block_mb, 0, {0, 4096}},    // staging block of the row-block ingestion (0 = default 64 MiB)
     {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
@@ -1335,6 +1373,10 @@ constexpr OptionRow kOptions[] = {
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
+    {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
+    {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
+    {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
+    {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
     {"i8_variant", &Options::i8_variant, 0, {0, 7}},
     {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
     {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
@@ -1369,7 +1411,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
         const bool known = r != std::end(kOptions);
         // what this kind of index refuses comes first, whatever the value is otherwise
-        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0) | (h->ivf_codec == 2 ? kIvfPq : 0);
+        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0) | (h->ivf_codec == 2 ? kIvfPq : 0) | (knng_on(h) ? kKnng : 0);
         for (const auto &x : kRefusals)
             if (known && value != 0 && (kinds & r->not_on & x.kind))
                 throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on " + x.what);
@@ -1395,5 +1437,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 
 #include "pq.inc"
 #include "lsh.inc"
+#include "knng.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

@@ -10,6 +10,7 @@ from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher,
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
 from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
 from .ivf_pq import HipIVFPQIndexer, HipIVFPQSearch, IVFPQIndex, parse_ivfpq_key
+from .knng import HipKnnGraphIndexer, HipKnnGraphSearch, HipKnnGraphSearcher, KnnGraphIndex
 from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
 from .pq import HipPQIndexer, HipPQSearch, HipPQSearcher, PQIndex, parse_pq_key
 from . import sharded
@@ -22,6 +23,7 @@ __all__ = [
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
     "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
     "HipIVFPQIndexer", "HipIVFPQSearch", "IVFPQIndex", "parse_ivfpq_key",
+    "HipKnnGraphIndexer", "HipKnnGraphSearcher", "HipKnnGraphSearch", "KnnGraphIndex",
     "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipPQIndexer", "HipPQSearcher", "HipPQSearch", "PQIndex",
     "parse_pq_key", "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",
