@@ -172,7 +172,24 @@ int vdb_rerank_device(vdb_handle h, const float *q_dev, int64_t nq, const int64_
 
 /* ---- IVF-Flat -- replaces faiss.index_factory(d, "IVF<nlist>,Flat", metric) + train/add/search
  *      (modular.py:277-286, 437-441, 544; approximate_search.py:39-51, 87) ------------------- */
-/* k-means (Lloyd) on at most max_points_per_centroid*nlist rows sampled with `seed`; niter iterations. */
+/* k-means (Lloyd) on at most max_points_per_centroid*nlist rows sampled with `seed`; niter iterations.  The result is fixed bit
+ * for bit by the arguments (restated in NumPy by tests/kmeans_restatement.py); max_points_per_centroid <= 0 means 256:
+ *   sample   ns = min(n, max_points_per_centroid * nlist);  pick = 0 .. n-1;  rng = std::mt19937_64(seed);  for i = 0 ..
+ *            min(ns, n - 1) - 1:  j = i + rng() % (n - i), swap pick[i] and pick[j].  The sample is the rows pick[0 .. ns) in that
+ *            order (ns == n: still a permutation of the rows, not the identity)
+ *   init     the centroids are the first nlist sample rows; niter == 0 returns them
+ *   assign   every sample row goes to its nearest centroid under the index metric: the canonical float64 key (above), ties to
+ *            the smaller list; inside a list the rows stay in sample order
+ *   update   non-empty list c, every d:  acc = 0.0;  acc += (double)x[d] over the rows of the list in order, one rounding per
+ *            add;  centroid[c][d] = (float)(acc / (double)count).  An empty list keeps its centroid
+ *   IP only  ("spherical")  n2 = sum over the 64-dimension blocks, in ascending order, of the block's sum of
+ *            (double)centroid[c][d] * (double)centroid[c][d] (0 for d >= dim), the 64 values of a block added as the butterfly
+ *            v[i] += v[i ^ w], w = 32, 16, .., 1;  n2 > 0:  centroid[c][d] *= (float)(1.0 / sqrt(n2)), a float32 product
+ *   split    after the update, on the list sizes cnt of this assignment, for l ascending with cnt[l] == 0:  big = the first
+ *            list holding the largest cnt;  for every d, c = centroid[big][d], e = +1/1024 (odd d) or -1/1024 (even d):
+ *            centroid[l][d] = c * (1.f + e), centroid[big][d] = c * (1.f - e), float32;  cnt[l] = cnt[big] / 2,
+ *            cnt[big] -= cnt[l] (the next empty list sees these counts).  Split centroids are not normalised again
+ * The centroids after the last iteration are installed; rows filed under earlier centroids are dropped at the next add. */
 int vdb_ivf_train(vdb_handle h, int nlist, const float *x_host, int64_t n, int niter, uint64_t seed,
                   int max_points_per_centroid);
 /* inject centroids (nlist, dim) instead of training -- used by parity tests and index loading */
@@ -213,7 +230,8 @@ int vdb_ivf_search_partial_device(vdb_handle h, const float *q_dev, int64_t nq, 
 /* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8, 2 = PQ (IVF<nlist>,PQ<M>, below).  Only before centroids or
  * rows exist (VDB_ERR_STATE after) */
 int vdb_ivf_set_codec(vdb_handle h, int codec);
-/* SQ8: vdb_ivf_train trains the centroids and then the ranges on the same rows; this call trains the ranges only, against
+/* SQ8: vdb_ivf_train trains the centroids (the contract stated there, unchanged by the codec) and then the ranges on the same
+ * rows, all of them and not the k-means sample; this call trains the ranges only, against
  * the installed centroids (vdb_ivf_set_centroids).  New ranges drop the rows encoded under the old ones at the next add. */
 int vdb_ivf_sq8_train_ranges(vdb_handle h, const float *x_host, int64_t n);
 /* inject / read the ranges, float32 (dim) each -- persistence and tests */
@@ -230,7 +248,9 @@ int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
  * rounded as written; c_l = centroid of the row's list, dsub = dim / M:
  *   train   codebooks float32 [M][256][dsub], trained on the residuals r = x - c_l of ONE row sample (at most
  *           256 * max_points_per_centroid rows, drawn with `seed` as the flat PQ training draws them) against the installed
- *           centroids; sub-space m is clustered by the k-means of vdb_ivf_train with seed + m.  Same seed, same codebooks.
+ *           centroids; sub-space m is clustered by the k-means of vdb_ivf_train with seed + m.  Same seed, same codebooks:
+ *           bit for bit the contract stated at vdb_ivf_train (L2, nlist = 256, run on the sample's columns, which that run
+ *           permutes again with its own seed; l of a sample row = its list under the index metric).
  *           Fewer than 256 rows: VDB_ERR_INVALID.  vdb_ivf_train keeps training the centroids only
  *   encode  code[i][m] = argmin over c of the canonical float64 L2 key between r[i][m dsub .. (m + 1) dsub) and
  *           codebook[m][c]; ties to the smaller c, whatever the index metric
@@ -313,7 +333,9 @@ int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, i
  * (FAISS' k-means, its float32 table sums and its tie order are not reproduced):
  *   codebooks  float32 [M][256][dsub].  vdb_pq_train: one row sample (at most 256 * max_points_per_centroid rows, drawn with
  *              `seed`) shared by all sub-spaces; sub-space m is clustered by the k-means of vdb_ivf_train (L2, 256 centroids,
- *              niter iterations) with seed + m.  Same seed, same codebooks.  Fewer than 256 training rows: VDB_ERR_INVALID
+ *              niter iterations) with seed + m.  Same seed, same codebooks: bit for bit the contract stated at vdb_ivf_train,
+ *              run on the sample's columns [m dsub, (m + 1) dsub) with nlist = 256 and the same max_points_per_centroid (that
+ *              run permutes the sample again with its own seed).  Fewer than 256 training rows: VDB_ERR_INVALID
  *   codes      code[i][m] = argmin over c of the canonical float64 L2 key (above) between x[i][m dsub .. (m + 1) dsub) and
  *              codebook[m][c]; ties to the smaller c, whatever the index metric
  *   x^         x^[i] = concatenation of codebook[m][code[i][m]]: a lookup, no arithmetic
