@@ -92,6 +92,44 @@ typedef struct vdb_stats_s {
                                   the three stages of a search, so a caller can name the longest one */
 } vdb_stats_t;
 
+/* ---- kinds of handle: which calls each admits --------------------------------------------------------------------------
+ * Every handle comes from vdb_create (or vdb_create_multi) and is of exactly ONE kind, decided by what has been done to it:
+ *   flat      nothing below                              PQ        codebooks of vdb_pq_train / vdb_pq_set_codebooks
+ *   LSH       a projection (vdb_lsh_set_projection)      IVF-Flat  centroids or filed rows, codec 0
+ *   knng      a k-NN graph (vdb_knng_build / _set;       IVF-SQ8   vdb_ivf_set_codec 1
+ *             an add or vdb_reset makes it flat again)   IVF-PQ    vdb_ivf_set_codec 2
+ *   multi     vdb_create_multi (flat or IVF-Flat rows)
+ * A call on a kind it does not serve is refused before it looks at its arguments or touches the handle, with a message that names
+ * the call and the kind: U = VDB_ERR_UNSUPPORTED, S = VDB_ERR_STATE.  "+" = admitted (the call's own state and argument checks
+ * follow: "no centroids", "not built", ...).
+ *                                                       flat  LSH  knng  PQ   IVF-Flat  IVF-SQ8  IVF-PQ  multi
+ *   vdb_add(_device)                                     +     +    +    U      +         U        U       +
+ *   vdb_search*, vdb_reserve, vdb_reset, vdb_stats,
+ *     vdb_set_option, the get_codebooks / get_projection
+ *     / vdb_knng_get calls (M, nbits, degree 0 elsewhere) +     +    +    +      +         +        +       +
+ *   vdb_rerank(_device)                                  +     +    +    +      +         +        S       +
+ *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U    U      +         +        +       +
+ *   vdb_ivf_set_codec 1 | 2                              +     U    U    U      +         +        +       U
+ *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +    U      +         +        +       +
+ *   vdb_ivf_sq8_*, vdb_ivf_get_codes                     S     S    S    U      S         +        U       U
+ *   vdb_ivfpq_train / _set_codebooks / _add_codes /
+ *     _get_codes                                         S     S    S    U      S         S        +       U
+ *   vdb_pq_train, vdb_pq_set_codebooks                   +     U    U    +      U         U        U       U
+ *   vdb_pq_add, vdb_pq_add_codes, vdb_pq_get_codes       S     S    S    +      S         S        U       U
+ *   vdb_lsh_set_projection                               +     +    U    U      U         U        U       U
+ *   vdb_lsh_candidates*, vdb_lsh_search*                 S     +    U    U      S         S        U       U
+ *   vdb_lsh_get_codes                                    S     +    S    U      S         S        U       U
+ *   vdb_knng_build, vdb_knng_set, vdb_knng_search*       +     U    +    U      U         U        U       U
+ *   vdb_debug_scan_scores                                +     +    +    +      +         +        +       U
+ *   options refused (U), in either order of the calls:
+ *     "int8_only" = 1, "stream_panels" = 1               -     U    U    U      -         U        U       -
+ *     "graph" = 1                                        -     -    -    U      -         U        U       U
+ *     "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -     -    -    U      -         -        -       -
+ * "Either order": vdb_set_option refuses the value on a handle of the kind, and the call that makes a handle that kind
+ * (vdb_lsh_set_projection, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
+ * which the option holds the value; LSH and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
+ * LSH and k-NN graph search calls are refused while option "graph" is 1. */
+
 /* ---- library ---------------------------------------------------------------------------- */
 int vdb_abi_version(void);
 const char *vdb_last_error(void);
@@ -113,7 +151,7 @@ int vdb_create(int dim, int metric, int device, vdb_handle *out);
  *                  centroids and probes the same lists;
  *   vdb_reserve, vdb_stats (sums / maxima over the shards, ndevices), vdb_set_option (forwarded), vdb_reset, vdb_destroy,
  *   vdb_ivf_set_centroids / _get_centroids / _set_nprobe / _get_assignment, vdb_rerank(_device)  work as on one device.
- * Not available on such a handle (VDB_ERR_UNSUPPORTED): option "graph", the debug hooks.
+ * Not available on such a handle: the table of kinds above (column "multi").
  * Option "multi_stage_all" = 1 (tests) makes shards on devices[0] take the remote-shard path too (own query copy, packed buffer,
  * peer copy), so a one-GPU box exercises the code a multi-GPU node runs.
  * A device may be listed more than once (several shards on one GPU). */
@@ -163,8 +201,8 @@ int vdb_merge_packed_partials_device(int metric, int device, const void *packed_
  *      LSHSearcher._compute_distances (lsh.py:242-250) ------------------------------------------------ */
 /* cand (nq, ncand) int64 row ids (id_base-relative ids as returned by search; -1 = empty slot, ids of one
  * query must be distinct).  Output: the k best candidates of every query, flat conventions and padding.
- * A handle whose rows were filed by vdb_ivf_add(_assigned) (IVF-Flat or IVF-SQ8, one device or vdb_create_multi) is refused
- * with VDB_ERR_STATE before any kernel runs: its rows sit in list order (SQ8 keeps no float32 rows at all), not in id order. */
+ * A handle whose rows were filed by vdb_ivf_add(_assigned) (any IVF kind, one device or vdb_create_multi) is refused with
+ * VDB_ERR_STATE before any kernel runs: its rows sit in list order (SQ8 and IVF-PQ keep no float32 rows at all), not in id order. */
 int vdb_rerank(vdb_handle h, const float *q_host, int64_t nq, const int64_t *cand_host, int ncand, int k, float *D,
                int64_t *I);
 int vdb_rerank_device(vdb_handle h, const float *q_dev, int64_t nq, const int64_t *cand_dev, int ncand, int k,
@@ -225,8 +263,8 @@ int vdb_ivf_search_partial_device(vdb_handle h, const float *q_dev, int64_t nq, 
  * arithmetic above): every exact kernel (list scan, refine, flagged-query scan) decodes x^ from the codes.  D <= 128: batches
  * the list-major path serves take the MFMA list scan on fp16 panels converted from the codes per batch (workspace; they equal
  * IVF-Flat's panels of x^, so the same error bound holds; vdb_stats.scan_dtype = 2).  D > 128: the exact list scan.
- * Not available (VDB_ERR_UNSUPPORTED): the codec on a vdb_create_multi handle, option "graph", options "int8_only" /
- * "stream_panels", vdb_add / vdb_add_device (rows enter through vdb_ivf_add / vdb_ivf_add_assigned only). */
+ * Rows enter through vdb_ivf_add / vdb_ivf_add_assigned only.  What an SQ8 handle admits and which options it refuses: the
+ * table of kinds above (column "IVF-SQ8"). */
 /* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8, 2 = PQ (IVF<nlist>,PQ<M>, below).  Only before centroids or
  * rows exist (VDB_ERR_STATE after) */
 int vdb_ivf_set_codec(vdb_handle h, int codec);
@@ -262,11 +300,8 @@ int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
  * and run the MFMA list scan on them; dim > 128, small batches and "force_path" 1 / 3 take the exact list scan over the codes.
  * vdb_ivf_add / vdb_ivf_add_assigned encode and append.  New codebooks (or centroids) drop the rows encoded under the old ones
  * at the next add; vdb_reset drops the rows and keeps centroids and codebooks.
- * VDB_ERR_STATE: these calls on a handle whose codec is not 2; an add before codebooks.  dim % M != 0 or M outside
- * 1 .. min(dim, 256): VDB_ERR_INVALID.  Refused with a message that names IVF-PQ: the codec on a vdb_create_multi handle, options
- * "graph" / "int8_only" / "stream_panels" (in either order), vdb_add / vdb_add_device, vdb_rerank(_device) (VDB_ERR_STATE: the
- * rows sit in list order), the sign-LSH calls, the flat PQ calls (VDB_ERR_UNSUPPORTED on any IVF handle) and the SQ8 range and
- * code calls. */
+ * VDB_ERR_STATE: an add before codebooks.  dim % M != 0 or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  Which handles these
+ * calls admit, and what an IVF-PQ handle refuses (with a message that names IVF-PQ): the table of kinds above. */
 int vdb_ivfpq_train(vdb_handle h, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid);
 /* inject / read the codebooks, float32 (M, 256, dim / M) -- persistence and tests.  codebooks_host may be NULL: M only (0 = none) */
 int vdb_ivfpq_set_codebooks(vdb_handle h, int M, const float *codebooks_host);
@@ -303,10 +338,8 @@ int vdb_ivfpq_get_codes(vdb_handle h, uint8_t *codes_host);
  * "lsh_force_fallback" = 1 sends every query there.  vdb_stats.last_path = VDB_PATH_LSH; with option "timing",
  * last_prep_ms = query codes + sample, last_scan_ms = the scans, last_tail_ms = select + re-rank.
  * ncand is in [1, 65 536] (VDB_ERR_INVALID above; ncand > ntotal is legal and pads); k follows vdb_rerank (1 .. 2048; k >
- * ncand pads).  VDB_ERR_STATE: an LSH call before a projection, or before rows.  VDB_ERR_UNSUPPORTED, with a message naming
- * the reason: a vdb_create_multi handle; an IVF handle (centroids set or a codec chosen; and the IVF calls on a handle that
- * carries a projection); options "int8_only" / "stream_panels" (no resident float32 rows to encode from or re-rank against),
- * in either order of the two calls; option "graph" together with the candidate / search calls.
+ * ncand pads).  VDB_ERR_STATE: an LSH call before a projection, or before rows.  Which handles admit the LSH calls, what a handle
+ * with a projection refuses, and the options (no resident float32 rows to encode from or re-rank against): the table of kinds above.
  * A handle without a projection behaves exactly as before. */
 /* installs R.  With rows already present they are encoded from the resident float32 rows; with none R is only stored.
  * Every later vdb_add / vdb_add_device encodes the rows it appends (appended codes equal those of one big add).  vdb_reset
@@ -345,11 +378,9 @@ int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, i
  * every search makes the fp16 panels of the scan from the codes, slab by slab ("pq_slab_chunks" scan chunks per slab; default
  * the chunks of 524 288 rows, whatever ntotal), as (half)(codebook * sx) -- the rounding a flat build applies to x^ -- so the
  * scan statistics and the error bound are those of the flat index over x^ (vdb_stats.scan_dtype = 2).
- * VDB_ERR_STATE: codebooks (train / set) while the handle holds rows; add / get_codes before codebooks.  VDB_ERR_UNSUPPORTED, with
- * a message: vdb_add / vdb_add_device on a PQ handle; a vdb_create_multi handle; options "int8_only", "stream_panels", "graph" and
- * the layout options "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -- the panels of a PQ index are made in layout "x16" only --
- * (in either order); vdb_lsh_* and vdb_ivf_* on a PQ handle, vdb_pq_* on an IVF handle or one with a projection.  dim % M != 0
- * or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  vdb_reset drops the codes and keeps the codebooks. */
+ * VDB_ERR_STATE: codebooks (train / set) while the handle holds rows; add / get_codes before codebooks.  Which handles admit the
+ * PQ calls, and the calls and options a PQ handle refuses (its panels are made in layout "x16" only): the table of kinds above.
+ * dim % M != 0 or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  vdb_reset drops the codes and keeps the codebooks. */
 int vdb_pq_train(vdb_handle h, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid);
 /* inject / read the codebooks, float32 (M, 256, dim / M) -- persistence and tests.  codebooks_host may be NULL: M only (0 = none) */
 int vdb_pq_set_codebooks(vdb_handle h, int M, const float *codebooks_host);
@@ -382,10 +413,8 @@ int vdb_pq_get_codes(vdb_handle h, uint8_t *codes_host);
  * again rejects it again.  So the kernel's per-query "seen" filter is a cache (whole ids, a collision forgets; option
  * "knng_visited_bits" never changes a result), and only the de-duplication against L is exact.
  * vdb_add, vdb_add_device and vdb_reset drop the graph: vdb_knng_get then reports degree 0 and a search returns VDB_ERR_STATE.  The
- * flat search of the handle is untouched.  VDB_ERR_UNSUPPORTED, with a message naming the k-NN graph, in either order of the two
- * calls: a vdb_create_multi handle; an IVF handle (centroids or a codec); a PQ handle; a handle with an LSH projection (and the LSH
- * calls on a handle with a graph); options "int8_only" / "stream_panels"; option "graph" = 1 together with the search calls; a
- * dimension whose padded query does not fit a workgroup's LDS (above roughly 14 000).  VDB_ERR_INVALID: k < 1, k > ef, ef > 512, a degree or
+ * flat search of the handle is untouched.  VDB_ERR_UNSUPPORTED, with a message naming the k-NN graph: the handles and options of
+ * the table of kinds above; a dimension whose padded query does not fit a workgroup's LDS (above roughly 14 000).  VDB_ERR_INVALID: k < 1, k > ef, ef > 512, a degree or
  * ncand out of range.  vdb_stats after a search: last_path = VDB_PATH_KNNG, last_candidates = rows scored (summed over the
  * queries), last_fallback_queries = queries the step cap stopped with an unexpanded entry left; with option "timing" the three stages
  * run as three launches: last_prep_ms = entry scoring, last_scan_ms = the traversal, last_tail_ms = writing the results. */

@@ -112,7 +112,7 @@ int vdb_debug_scan_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_
                           float *scores_host, float *eps_host, double *cscale) {
     return guarded([&] {
         auto *h = check(hh);
-        if (h->multi) multi_unsupported("vdb_debug_scan_scores");
+        admit(h, "vdb_debug_scan_scores", kAnyKind & ~kMulti);
         if (!h->built || !h->scan_ok || h->panels_streamed || !h->scan.panels.p) throw Error(VDB_ERR_STATE, "scan copy not available for this index");
         // panel layouts with a kernel here: p16 (D > 128), "x16" and the 32x32 form (D <= 128)
         const bool t32 = !h->tile16 && !h->x16;

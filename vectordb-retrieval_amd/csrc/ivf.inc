@@ -18,6 +18,20 @@ void ivf_require(bool cond, int code, const char *msg) {
     if (!cond) throw Error(code, msg);
 }
 
+// What the IVF entry points admit (Kind, vdbhip.hip).  Every one of them refuses a flat PQ handle; on any other handle without
+// centroids they answer VDB_ERR_STATE themselves (a sign-LSH or k-NN graph handle too: recorded behaviour, nobody chose it --
+// DESIGN.md 4.11).  The calls that make a handle an IVF index also refuse the kinds that stay flat.  The calls of one codec
+// refuse the handles that can never carry it, and are a state error on the rest.
+constexpr unsigned kIvfCalls = kAnyKind & ~kPq, kBecomesIvf = kFlat | kIvf | kMulti;
+inline void admit_sq8(const vdb_index_s *h, const char *what) {
+    admit(h, what, kAnyKind & ~(kPq | kMulti | kIvfPq));
+    admit(h, what, kIvfSq8, VDB_ERR_STATE, ": not an SQ8 index (vdb_ivf_set_codec(h, 1) on an empty handle)");
+}
+inline void admit_ivfpq(const vdb_index_s *h, const char *what) {
+    admit(h, what, kAnyKind & ~(kPq | kMulti));
+    admit(h, what, kIvfPq, VDB_ERR_STATE, ": not an IVF-PQ index (vdb_ivf_set_codec(h, 2) on an empty handle)");
+}
+
 // (re)build the flat index over the current centroids
 void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
     h->ivf_centroids.assign(c_host, c_host + (size_t)nlist * h->dim);
@@ -807,11 +821,10 @@ extern "C" {
 int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_set_centroids", kBecomesIvf);
         ivf_require(centroids_host != nullptr, VDB_ERR_INVALID, "null centroid pointer");
         ivf_require(nlist >= 1 && nlist <= (1 << 22), VDB_ERR_INVALID, "nlist out of range");
         if (h->multi) return multi_set_centroids(h, centroids_host, nlist);
-        lsh_refuse_ivf(h);
         set_device(h->device);
         graph_reset(h);
         ivf_install_centroids(h, centroids_host, nlist);
@@ -822,7 +835,7 @@ int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist)
 int vdb_ivf_get_centroids(vdb_handle hh, float *centroids_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_get_centroids", kIvfCalls);
         ivf_require(h->nlist > 0, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(centroids_host != nullptr, VDB_ERR_INVALID, "null pointer");
         if (h->multi) h = multi_first_shard(h);
@@ -834,14 +847,13 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
                   int max_points_per_centroid) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_train", kBecomesIvf);
         ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
         ivf_require(nlist >= 1 && nlist <= (1 << 22), VDB_ERR_INVALID, "nlist out of range");
         ivf_require(n >= nlist, VDB_ERR_INVALID, "need at least nlist training vectors");
         ivf_require(niter >= 0 && niter <= 1000, VDB_ERR_INVALID, "niter out of range");
         if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
         if (h->multi) return multi_train(h, nlist, x_host, n, niter, seed, max_points_per_centroid);
-        lsh_refuse_ivf(h);
         graph_reset(h);
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;
@@ -899,23 +911,13 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
 int vdb_ivf_set_codec(vdb_handle hh, int codec) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        // codec 0 is what every handle has: admitted as the other IVF calls are (a no-op on a multi-device handle)
+        const bool coded = codec == 1 || codec == 2;
+        admit(h, codec == 1 ? "the SQ8 codec" : codec == 2 ? "the IVF-PQ codec" : "vdb_ivf_set_codec", coded ? kFlat | kIvf : kIvfCalls);
         ivf_require(codec >= 0 && codec <= 2, VDB_ERR_INVALID, "codec must be 0 (Flat), 1 (SQ8) or 2 (PQ)");
-        if (h->multi) {
-            if (codec == 1) multi_unsupported("the SQ8 codec");
-            if (codec == 2) multi_unsupported("the IVF-PQ codec");
-            return;
-        }
-        if (codec != 0) lsh_refuse_ivf(h);
+        if (h->multi) return;
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
-        if (codec == 1) {
-            ivf_require(!h->opt.graph, VDB_ERR_UNSUPPORTED, "option 'graph' is not available on an SQ8 index");
-            ivf_require(!h->opt.int8_only && !h->opt.stream_panels, VDB_ERR_UNSUPPORTED,
-                        "options 'int8_only' and 'stream_panels' do not combine with the SQ8 codec");
-        }
-        if (codec == 2)
-            ivf_require(!h->opt.graph && !h->opt.int8_only && !h->opt.stream_panels, VDB_ERR_UNSUPPORTED,
-                        "options 'graph', 'int8_only' and 'stream_panels' are not available on an IVF-PQ index");
+        if (coded) refuse_options_set(h, "vdb_ivf_set_codec", codec == 1 ? kIvfSq8 : kIvfPq);
         if (codec != 2) {                       // (codebooks belong to codec 2)
             h->ivfpq_M = h->ivfpq_dsub = 0;
             h->ivfpq_cb_host.clear();
@@ -928,10 +930,7 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
 int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) multi_unsupported("vdb_ivf_sq8_train_ranges");
-        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_train_ranges");
-        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        admit_sq8(h, "vdb_ivf_sq8_train_ranges");
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
         set_device(h->device);
@@ -943,10 +942,7 @@ int vdb_ivf_sq8_train_ranges(vdb_handle hh, const float *x_host, int64_t n) {
 int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *vdiff_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) multi_unsupported("vdb_ivf_sq8_set_ranges");
-        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_set_ranges");
-        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        admit_sq8(h, "vdb_ivf_sq8_set_ranges");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
         for (int d = 0; d < h->dim; ++d)
             ivf_require(std::isfinite(vmin_host[d]) && std::isfinite(vdiff_host[d]) && vdiff_host[d] >= 0.f, VDB_ERR_INVALID,
@@ -961,10 +957,8 @@ int vdb_ivf_sq8_set_ranges(vdb_handle hh, const float *vmin_host, const float *v
 int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) multi_unsupported("vdb_ivf_sq8_get_ranges");
-        sq8_refuse_ivfpq(h, "vdb_ivf_sq8_get_ranges");
-        ivf_require(sq8(h) && h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
+        admit_sq8(h, "vdb_ivf_sq8_get_ranges");
+        ivf_require(h->sq8_ranges, VDB_ERR_STATE, "no SQ8 ranges: train the index or set them first");
         ivf_require(vmin_host && vdiff_host, VDB_ERR_INVALID, "null pointer");
         memcpy(vmin_host, h->sq8_vmin.data(), (size_t)h->dim * sizeof(float));
         memcpy(vdiff_host, h->sq8_vdiff.data(), (size_t)h->dim * sizeof(float));
@@ -974,10 +968,7 @@ int vdb_ivf_sq8_get_ranges(vdb_handle hh, float *vmin_host, float *vdiff_host) {
 int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        if (h->multi) multi_unsupported("vdb_ivf_get_codes");
-        sq8_refuse_ivfpq(h, "vdb_ivf_get_codes");
-        ivf_require(sq8(h), VDB_ERR_STATE, "not an SQ8 index (vdb_ivf_set_codec)");
+        admit_sq8(h, "vdb_ivf_get_codes");
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
         if (h->N == 0) return;
@@ -996,8 +987,7 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
 int vdb_ivfpq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        ivfpq_require(h, "vdb_ivfpq_set_codebooks");
+        admit_ivfpq(h, "vdb_ivfpq_set_codebooks");
         ivfpq_check_M(h, M);
         ivf_require(codebooks_host != nullptr, VDB_ERR_INVALID, "null codebook pointer");
         set_device(h->device);
@@ -1008,8 +998,9 @@ int vdb_ivfpq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
 int vdb_ivfpq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_ivfpq_get_codebooks", kAnyKind);
         ivf_require(M != nullptr, VDB_ERR_INVALID, "null pointer");
-        *M = (h->multi || !ivfpq(h)) ? 0 : h->ivfpq_M;
+        *M = kind_of(h) == kIvfPq ? h->ivfpq_M : 0;
         if (codebooks_host && *M > 0) memcpy(codebooks_host, h->ivfpq_cb_host.data(), h->ivfpq_cb_host.size() * sizeof(float));
     });
 }
@@ -1017,8 +1008,7 @@ int vdb_ivfpq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
 int vdb_ivfpq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        ivfpq_require(h, "vdb_ivfpq_train");
+        admit_ivfpq(h, "vdb_ivfpq_train");
         ivfpq_check_M(h, M);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
@@ -1067,8 +1057,7 @@ int vdb_ivfpq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int ni
 int vdb_ivfpq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_t id_base, const int32_t *list_of_row_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        ivfpq_require(h, "vdb_ivfpq_add_codes");
+        admit_ivfpq(h, "vdb_ivfpq_add_codes");
         ivf_require(n >= 0 && (n == 0 || (codes_host && list_of_row_host)), VDB_ERR_INVALID, "null code or assignment pointer");
         ivfpq_add(h, nullptr, codes_host, n, id_base, list_of_row_host);
     });
@@ -1077,8 +1066,7 @@ int vdb_ivfpq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int
 int vdb_ivfpq_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
-        ivfpq_require(h, "vdb_ivfpq_get_codes");
+        admit_ivfpq(h, "vdb_ivfpq_get_codes");
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
         if (h->N == 0) return;
@@ -1103,7 +1091,7 @@ namespace {
 int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base, const int32_t *given) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, given ? "vdb_ivf_add_assigned" : "vdb_ivf_add", kIvfCalls);      // (a sign-LSH or k-NN graph handle is told "no centroids" below, not that it stays flat)
         if (h->multi) {
             if (h->nlist > 0 && n > 0) ivf_check_given(h, given, n);      // (a shard that refused its block would empty the whole index)
             return multi_add(h, x_host, false, n, id_base, nullptr, true, given);
@@ -1157,7 +1145,7 @@ int ivf_search_device_entry(vdb_handle hh, const float *q_dev, int64_t nq, int k
                             int64_t *pi, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, kind == 3 ? "vdb_ivf_search_device" : "vdb_ivf_search_partial_device", kIvfCalls);
         if (h->multi) return multi_search(h, q_dev, true, nq, k, D, I, pk, pi, as_stream(stream), true);
         set_device(h->device);
         vdb_index_s::GraphKey key;
@@ -1184,7 +1172,7 @@ int vdb_ivf_add_assigned(vdb_handle hh, const float *x_host, int64_t n, int64_t 
 int vdb_ivf_set_nprobe(vdb_handle hh, int nprobe) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_set_nprobe", kIvfCalls);
         ivf_require(nprobe >= 1, VDB_ERR_INVALID, "nprobe must be >= 1");
         h->nprobe = std::min(nprobe, 2048);
         if (h->multi) {
@@ -1198,7 +1186,7 @@ int vdb_ivf_set_nprobe(vdb_handle hh, int nprobe) {
 int vdb_ivf_get_assignment(vdb_handle hh, int32_t *list_of_row_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_get_assignment", kIvfCalls);
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(list_of_row_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
         if (h->multi) return multi_get_assignment(h, list_of_row_host);
@@ -1223,6 +1211,7 @@ int vdb_ivf_search_partial_device(vdb_handle hh, const float *q_dev, int64_t nq,
 int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_reserve", kAnyKind);
         if (h->multi) return multi_reserve(h, nq, k);
         ivf_require(h->built || h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(k >= 1 && k <= 2048, VDB_ERR_INVALID, "k must be in [1, 2048]");
@@ -1261,7 +1250,7 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
 int vdb_ivf_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float *D, int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_ivf(h);
+        admit(h, "vdb_ivf_search", kIvfCalls);
         ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
         ivf_require(k >= 1 && k <= 2048, VDB_ERR_INVALID, "k must be in [1, 2048]");
         if (nq <= 0) {

@@ -21,17 +21,6 @@ IvfPqRows ivfpq_rows(const vdb_index_s *h) {
     return p;
 }
 
-// an entry point of the codec on a handle that is not (or cannot be) an IVF-PQ index
-void ivfpq_require(const vdb_index_s *h, const char *what) {
-    if (h->multi) multi_unsupported(what);
-    if (!ivfpq(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": not an IVF-PQ index (vdb_ivf_set_codec(h, 2) on an empty handle)");
-}
-
-// the SQ8 entry points on an IVF-PQ handle
-void sq8_refuse_ivfpq(const vdb_index_s *h, const char *what) {
-    if (ivfpq(h)) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF-PQ index (its codec has codebooks, not ranges)");
-}
-
 void ivfpq_check_M(const vdb_index_s *h, int M) {
     ivf_require(M >= 1 && M <= std::min(h->dim, 256), VDB_ERR_INVALID, "M must be in [1, min(dim, 256)]");
     ivf_require(h->dim % M == 0, VDB_ERR_INVALID, "dim must be a multiple of M");

@@ -13,20 +13,9 @@ void knng_drop(vdb_index_s *h) {
     h->knng_degree = 0;
 }
 
-// handles that cannot carry a graph: it is searched against the resident float32 rows of ONE device, in insertion order
-void knng_refuse_handle(const vdb_index_s *h) {
-    if (h->multi) multi_unsupported("the k-NN graph");
-    if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph is not available on a PQ index (it keeps no float32 rows)");
-    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph is not available on an IVF-PQ index (it keeps no float32 rows)");
-    if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
-        throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph is not available on an IVF index (centroids set or a codec chosen): its rows sit in "
-                                         "list order");
-    if (h->lsh_nbits > 0) throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph is not available on a handle that carries a sign-LSH projection");
-    if (h->opt.int8_only || h->int8_only)
-        throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph needs the resident float32 rows: not available with option 'int8_only'");
-    if (h->opt.stream_panels || h->panels_streamed)
-        throw Error(VDB_ERR_UNSUPPORTED, "the k-NN graph is not available with option 'stream_panels'");
-}
+// What the k-NN graph entry points admit: a flat handle, for the graph is searched against the resident float32 rows of ONE
+// device, in insertion order (and none of the options that drop them: refuse_options_set).
+constexpr unsigned kKnngCalls = kFlat | kKnng;
 
 void knng_require_rows(const vdb_index_s *h) {
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
@@ -95,8 +84,7 @@ void knng_validate(const int32_t *nbrs, int64_t N, int degree) {
 }
 
 void knng_require_ready(vdb_index_s *h, const char *what) {
-    if (h->multi) multi_unsupported("the k-NN graph");
-    knng_refuse_handle(h);
+    refuse_options_set(h, what, kKnng);
     if (h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + ": the k-NN graph search is not available with option 'graph'");
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (!knng_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no k-NN graph (call vdb_knng_build or vdb_knng_set; an add or a reset drops it)");
@@ -205,7 +193,8 @@ extern "C" {
 int vdb_knng_build(vdb_handle hh, int degree, int ncand) {
     return guarded([&] {
         auto *h = check(hh);
-        knng_refuse_handle(h);
+        admit(h, "vdb_knng_build (the k-NN graph)", kKnngCalls);
+        refuse_options_set(h, "vdb_knng_build", kKnng);
         if (degree < kKnngMinDegree || degree > kKnngMaxDegree) throw Error(VDB_ERR_INVALID, "k-NN graph: degree must be in [4, 64]");
         if (ncand < degree || ncand > kKnngMaxCand) throw Error(VDB_ERR_INVALID, "k-NN graph: ncand must be in [degree, 128]");
         knng_require_rows(h);
@@ -217,7 +206,8 @@ int vdb_knng_build(vdb_handle hh, int degree, int ncand) {
 int vdb_knng_set(vdb_handle hh, int degree, const int32_t *nbrs_host) {
     return guarded([&] {
         auto *h = check(hh);
-        knng_refuse_handle(h);
+        admit(h, "vdb_knng_set (the k-NN graph)", kKnngCalls);
+        refuse_options_set(h, "vdb_knng_set", kKnng);
         if (degree < 1 || degree > kKnngMaxDegree) throw Error(VDB_ERR_INVALID, "k-NN graph: degree must be in [1, 64]");
         if (!nbrs_host) throw Error(VDB_ERR_INVALID, "null pointer");
         knng_require_rows(h);
@@ -235,8 +225,9 @@ int vdb_knng_set(vdb_handle hh, int degree, const int32_t *nbrs_host) {
 int vdb_knng_get(vdb_handle hh, int *degree, int32_t *nbrs_host) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_knng_get", kAnyKind);
         if (!degree) throw Error(VDB_ERR_INVALID, "null pointer");
-        *degree = h->multi ? 0 : h->knng_degree;
+        *degree = h->knng_degree;                  // (0 on every other kind)
         if (nbrs_host && *degree > 0) {
             set_device(h->device);
             VDB_HIP(hipMemcpy(nbrs_host, h->codes.knng_nbrs.p, (size_t)h->N * h->knng_degree * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -247,6 +238,7 @@ int vdb_knng_get(vdb_handle hh, int *degree, int32_t *nbrs_host) {
 int vdb_knng_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, int ef, float *D_dev, int64_t *I_dev, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_knng_search_device (the k-NN graph)", kKnngCalls);
         knng_require_ready(h, "vdb_knng_search_device");
         knng_check_args(q_dev, nq, k, ef, D_dev, I_dev);
         if (nq == 0) return;
@@ -258,6 +250,7 @@ int vdb_knng_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k,
 int vdb_knng_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int ef, float *D, int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_knng_search (the k-NN graph)", kKnngCalls);
         knng_require_ready(h, "vdb_knng_search");
         knng_check_args(q_host, nq, k, ef, D, I);
         if (nq == 0) return;

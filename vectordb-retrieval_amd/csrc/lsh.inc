@@ -5,27 +5,11 @@ namespace {
 
 inline bool lsh_on(const vdb_index_s *h) { return h->lsh_nbits > 0; }
 
-// handles that cannot carry LSH codes (no resident float32 rows in insertion order on ONE device)
-void lsh_refuse_handle(const vdb_index_s *h) {
-    if (h->multi) multi_unsupported("sign-LSH");
-    knng_refuse_other(h, "a sign-LSH projection");
-    if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on a PQ index (it keeps no float32 rows)");
-    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF-PQ index (it keeps no float32 rows)");
-    if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
-        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available on an IVF index (centroids set or a codec chosen): its rows "
-                                         "sit in list order");
-    if (h->opt.int8_only || h->int8_only)
-        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes need the resident float32 rows: not available with option 'int8_only'");
-    if (h->opt.stream_panels || h->panels_streamed)
-        throw Error(VDB_ERR_UNSUPPORTED, "sign-LSH codes are not available with option 'stream_panels'");
-}
-
-// an IVF entry point on a handle that carries a projection
-void lsh_refuse_ivf(const vdb_index_s *h) {
-    knng_refuse_other(h, "an IVF index");
-    if (!h->multi && lsh_on(h))
-        throw Error(VDB_ERR_UNSUPPORTED, "this handle carries a sign-LSH projection (vdb_lsh_set_projection): it stays a flat index");
-}
+// What the LSH entry points admit.  A projection goes onto a flat handle (resident float32 rows in insertion order on ONE
+// device; no option that drops them: refuse_options_set).  The candidate / search calls refuse the kinds that keep no float32
+// rows or stay another flat structure; an IVF-Flat or SQ8 handle is told "no projection" by lsh_require_ready, as a flat one is.
+constexpr unsigned kBecomesLsh = kFlat | kLsh, kLshSearchCalls = kFlat | kLsh | kIvfFlat | kIvfSq8;
+constexpr unsigned kLshGetCodes = kLshSearchCalls | kKnng;      // (a k-NN graph handle is told "no projection", not that it stays what it is)
 
 // n rows of x (device, `pitch` floats apart) -> codes (n x lsh_wp words)
 void lsh_encode(vdb_index_s *h, const float *x, int64_t n, int64_t pitch, uint32_t *codes, hipStream_t st) {
@@ -52,10 +36,6 @@ void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
 }
 
 void lsh_require_ready(vdb_index_s *h, const char *what) {
-    if (h->multi) multi_unsupported(what);
-    if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a PQ index");
-    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF-PQ index");
-    knng_refuse_other(h, what);
     if (!lsh_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no projection (call vdb_lsh_set_projection first)");
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
@@ -190,7 +170,8 @@ extern "C" {
 int vdb_lsh_set_projection(vdb_handle hh, int nbits, const float *proj_host) {
     return guarded([&] {
         auto *h = check(hh);
-        lsh_refuse_handle(h);
+        admit(h, "vdb_lsh_set_projection", kBecomesLsh);
+        refuse_options_set(h, "vdb_lsh_set_projection", kLsh);
         if (nbits < 32 || nbits > kLshMaxBits || nbits % 32) throw Error(VDB_ERR_INVALID, "nbits must be a multiple of 32 in [32, 1024]");
         if (!proj_host) throw Error(VDB_ERR_INVALID, "null projection pointer");
         set_device(h->device);
@@ -215,8 +196,9 @@ int vdb_lsh_set_projection(vdb_handle hh, int nbits, const float *proj_host) {
 int vdb_lsh_get_projection(vdb_handle hh, int *nbits, float *proj_host) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_lsh_get_projection", kAnyKind);
         if (!nbits) throw Error(VDB_ERR_INVALID, "null pointer");
-        *nbits = h->multi ? 0 : h->lsh_nbits;
+        *nbits = h->lsh_nbits;                     // (0 on every other kind)
         if (proj_host && *nbits > 0) memcpy(proj_host, h->lsh_proj.data(), h->lsh_proj.size() * sizeof(float));
     });
 }
@@ -224,9 +206,7 @@ int vdb_lsh_get_projection(vdb_handle hh, int *nbits, float *proj_host) {
 int vdb_lsh_get_codes(vdb_handle hh, uint32_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
-        if (h->multi) multi_unsupported("vdb_lsh_get_codes");
-        if (pq_on(h)) throw Error(VDB_ERR_UNSUPPORTED, "vdb_lsh_get_codes is not available on a PQ index");
-        if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "vdb_lsh_get_codes is not available on an IVF-PQ index");
+        admit(h, "vdb_lsh_get_codes", kLshGetCodes);
         if (!lsh_on(h)) throw Error(VDB_ERR_STATE, "vdb_lsh_get_codes: no projection (call vdb_lsh_set_projection first)");
         if (!h->built || h->N == 0 || h->lsh_rows != h->N) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");
@@ -246,6 +226,7 @@ int vdb_lsh_candidates_device(vdb_handle hh, const float *q_dev, int64_t nq, int
                               void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_lsh_candidates_device", kLshSearchCalls);
         lsh_require_ready(h, "vdb_lsh_candidates_device");
         lsh_check_args(h, q_dev, nq, ncand, ham_dev, ids_dev);
         if (nq == 0) return;
@@ -257,6 +238,7 @@ int vdb_lsh_candidates_device(vdb_handle hh, const float *q_dev, int64_t nq, int
 int vdb_lsh_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncand, int32_t *ham, int64_t *ids) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_lsh_candidates", kLshSearchCalls);
         lsh_require_ready(h, "vdb_lsh_candidates");
         lsh_check_args(h, q_host, nq, ncand, ham, ids);
         if (nq == 0) return;
@@ -277,6 +259,7 @@ int vdb_lsh_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncand
 int vdb_lsh_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, int ncand, float *D_dev, int64_t *I_dev, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_lsh_search_device", kLshSearchCalls);
         lsh_require_ready(h, "vdb_lsh_search_device");
         lsh_check_args(h, q_dev, nq, ncand, D_dev, I_dev);
         if (nq == 0) return;
@@ -288,6 +271,7 @@ int vdb_lsh_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, 
 int vdb_lsh_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int ncand, float *D, int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_lsh_search", kLshSearchCalls);
         lsh_require_ready(h, "vdb_lsh_search");
         lsh_check_args(h, q_host, nq, ncand, D, I);
         if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");

@@ -12,30 +12,11 @@ PqRows pq_rows(const vdb_index_s *h) {
     return p;
 }
 
-// handles that cannot become a PQ index (one device, no other row store, no option that needs resident rows or panels)
-void pq_refuse_handle(const vdb_index_s *h, const char *what) {
-    if (h->multi) multi_unsupported(what);
-    if (h->ivf_codec == 2)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index: an IVF-PQ index takes its codebooks and codes "
-                                         "through vdb_ivfpq_*");
-    if (h->nlist > 0 || h->coarse || h->ivf_codec != 0 || h->ivf_built)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index (IVF<nlist>,PQ<M> is a codec of the lists: "
-                                         "vdb_ivf_set_codec, vdb_ivfpq_*)");
-    if (h->lsh_nbits > 0)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a sign-LSH projection");
-    knng_refuse_other(h, what);
-    if (h->opt.int8_only || h->opt.stream_panels || h->opt.graph)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'int8_only', 'stream_panels' and 'graph'");
-    if (h->opt.flat_shape == 32 || h->opt.f16_group != 8 || h->opt.i8_group != 8)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " does not combine with the options 'flat_shape' = 32, 'f16_group' = 4 and 'i8_group' "
-                                         "= 4: the panels of a PQ index are made in layout \"x16\" (octs) only");
-}
-
-void pq_require_codebooks(const vdb_index_s *h, const char *what) {
-    if (h->multi) multi_unsupported(what);
-    if (h->ivf_codec == 2)
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on an IVF index: an IVF-PQ index takes its codebooks and codes "
-                                         "through vdb_ivfpq_*");
+// What the PQ entry points admit.  A handle becomes a PQ index on one device, with no other row store or structure over float32
+// rows (and no option a PQ index refuses: refuse_options_set).  The calls on the codes refuse the handles that never hold flat
+// codebooks; every other kind has none yet, which is the state error of pq_need_codebooks.
+constexpr unsigned kBecomesPq = kFlat | kPq, kPqCodeCalls = kAnyKind & ~(kMulti | kIvfPq);
+void pq_need_codebooks(const vdb_index_s *h, const char *what) {
     if (!pq_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no codebooks (call vdb_pq_train or vdb_pq_set_codebooks first)");
 }
 
@@ -243,7 +224,8 @@ extern "C" {
 int vdb_pq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_handle(h, "vdb_pq_set_codebooks");
+        admit(h, "vdb_pq_set_codebooks", kBecomesPq);
+        refuse_options_set(h, "vdb_pq_set_codebooks", kPq);
         pq_check_M(h, M);
         if (!codebooks_host) throw Error(VDB_ERR_INVALID, "null codebook pointer");
         if (h->N > 0) throw Error(VDB_ERR_STATE, "the codebooks are set before rows exist (vdb_reset first): the codes of the " +
@@ -257,8 +239,9 @@ int vdb_pq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
 int vdb_pq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_pq_get_codebooks", kAnyKind);
         if (!M) throw Error(VDB_ERR_INVALID, "null pointer");
-        *M = h->multi ? 0 : h->pq_M;
+        *M = h->pq_M;                              // (0 on every other kind)
         if (codebooks_host && *M > 0) memcpy(codebooks_host, h->pq_cb_host.data(), h->pq_cb_host.size() * sizeof(float));
     });
 }
@@ -266,7 +249,8 @@ int vdb_pq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
 int vdb_pq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter, uint64_t seed, int max_points_per_centroid) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_refuse_handle(h, "vdb_pq_train");
+        admit(h, "vdb_pq_train", kBecomesPq);
+        refuse_options_set(h, "vdb_pq_train", kPq);
         pq_check_M(h, M);
         if (!x_host || n <= 0) throw Error(VDB_ERR_INVALID, "no training vectors");
         if (n < 256) throw Error(VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
@@ -299,7 +283,8 @@ int vdb_pq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter
 int vdb_pq_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_require_codebooks(h, "vdb_pq_add");
+        admit(h, "vdb_pq_add", kPqCodeCalls);
+        pq_need_codebooks(h, "vdb_pq_add");
         if (n > 0 && !x_host) throw Error(VDB_ERR_INVALID, "null corpus pointer");
         set_device(h->device);
         pq_append(h, n, id_base, [&](unsigned char *codes) { pq_encode_host_rows(h, x_host, n, codes, nullptr); });
@@ -309,7 +294,8 @@ int vdb_pq_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
 int vdb_pq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_t id_base) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_require_codebooks(h, "vdb_pq_add_codes");
+        admit(h, "vdb_pq_add_codes", kPqCodeCalls);
+        pq_need_codebooks(h, "vdb_pq_add_codes");
         if (n > 0 && !codes_host) throw Error(VDB_ERR_INVALID, "null code pointer");
         set_device(h->device);
         pq_append(h, n, id_base, [&](unsigned char *codes) {
@@ -321,7 +307,8 @@ int vdb_pq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_
 int vdb_pq_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
-        pq_require_codebooks(h, "vdb_pq_get_codes");
+        admit(h, "vdb_pq_get_codes", kPqCodeCalls);
+        pq_need_codebooks(h, "vdb_pq_get_codes");
         if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");
         set_device(h->device);

@@ -235,7 +235,7 @@ struct Workspace {
 // ---- options -----------------------------------------------------------------------------------------------------------------
 // Everything vdb_set_option writes and nothing else: one member per option, under the name the caller passes, holding the
 // value the caller passed; the initializer is the value of an option never set.  What the library derives from an option at
-// the next add (int8_only, panels_streamed, x16, ivf_tps ...) is state of vdb_index_s.  kOptions (in front of vdb_set_option)
+// the next add (int8_only, panels_streamed, x16, ivf_tps ...) is state of vdb_index_s.  kOptions (behind vdb_index_s)
 // has one row per member: what each accepts is written there, what each does in include/vdbhip.h.
 struct Options {
     // behaviour
@@ -407,6 +407,118 @@ struct vdb_index_s {
 
 namespace {
 
+// ---- kinds of handle -------------------------------------------------------------------------------------------------------
+// What a handle IS decides which entry points it admits and which options it refuses.  kind_of is the only place that reads
+// the raw fields to decide that (computed, not stored: nothing to keep in step); kKinds names each kind in messages; admit is
+// the first line of every entry point, its mask the kinds that call serves; refuse_options_set is the option rule of kOptions
+// read in the other order.  A new kind is one enum bit, one row of kKinds, a test in kind_of and its own masks.
+enum Kind : unsigned { kFlat = 1, kLsh = 2, kKnng = 4, kPq = 8, kIvfFlat = 16, kIvfSq8 = 32, kIvfPq = 64, kMulti = 128 };
+constexpr unsigned kAnyKind = 255, kIvf = kIvfFlat | kIvfSq8 | kIvfPq;
+constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
+    {kMulti, "a multi-device index (vdb_create_multi)"},
+    {kPq, "a flat PQ index (vdb_pq_*: its rows are codes, its panels are made per search in layout \"x16\" only)"},
+    {kIvfPq, "an IVF-PQ index (vdb_ivf_set_codec 2, vdb_ivfpq_*: its rows are codes in list order)"},
+    {kIvfSq8, "an IVF index with the SQ8 codec (its rows are codes in list order)"},
+    {kIvfFlat, "an IVF index (centroids set: its rows sit in list order)"},
+    {kLsh, "an index with sign-LSH codes (vdb_lsh_set_projection: it stays a flat index)"},
+    {kKnng, "an index with a k-NN graph (vdb_knng_build / vdb_knng_set: it stays a flat index)"},
+    {kFlat, "a flat index"}};
+
+unsigned kind_of(const vdb_index_s *h) {
+    if (h->multi) return kMulti;             // (nlist / ivf_built of such a handle describe the whole index)
+    const unsigned ivf = h->ivf_codec == 2 ? kIvfPq : h->ivf_codec == 1 ? kIvfSq8 : (h->nlist > 0 || h->coarse || h->ivf_built) ? kIvfFlat : 0;
+    const unsigned k = (h->pq_M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0);
+    if (k & (k - 1)) throw Error(VDB_ERR_STATE, "internal: handle is two kinds at once");
+    return k ? k : kFlat;
+}
+
+const char *kind_phrase(unsigned kind) {
+    for (const auto &k : kKinds)
+        if (k.kind & kind) return k.phrase;
+    return "this handle";
+}
+
+// `what` (an entry point, or what it would make of the handle) on a handle whose kind is not in `accepted`; `hint`: what to do instead
+inline void admit(const vdb_index_s *h, const char *what, unsigned accepted, int code_if_not = VDB_ERR_UNSUPPORTED, const char *hint = "") {
+    const unsigned kind = kind_of(h);
+    if (!(kind & accepted)) throw Error(code_if_not, std::string(what) + " is not available on " + kind_phrase(kind) + hint);
+}
+
+struct OptionRow {
+    const char *name;
+    int Options::*m;
+    int n;                     // > 0: one of v[0 .. n), integers only | 0: v[0] <= value <= v[1], truncated toward zero | < 0: any value, stored as value != 0
+    double v[4];
+    unsigned not_on = 0;       // kinds of index that refuse a non-zero value
+    int not_on_pq = 0;         // a value that a PQ index refuses as well: its panels are made in layout "x16" (octs) only
+    int64_t Options::*m64 = nullptr;       // instead of m
+    bool vdb_index_s::*effect = nullptr;   // set while the value of the last add is in effect, whatever the option says now
+};
+constexpr unsigned kNoRows = kIvfSq8 | kPq | kIvfPq, kNeedsRows = kLsh | kKnng;     // no float32 rows at all | encoded from / searched against the resident ones
+constexpr OptionRow kOptions[] = {
+    {"force_path", &Options::force_path, 4, {0, 1, 2, 3}},
+    {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
+    {"list_cap", &Options::list_cap, 0, {0, 65536}},
+    {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
+    {"int8_only", &Options::int8_only, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::int8_only},
+    {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
+    {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
+    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
+    {"stream_slab_rows", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::stream_slab_rows},   // rows of the scratch slab of a streamed index (0 = default 1 280 000)
+    {"upload_block_mb", &Options::upload_block_mb, 0, {0, 4096}},    // staging block of the row-block ingestion (0 = default 64 MiB)
+    {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
+    {"fused_stats", &Options::fused_stats, 2, {0, 1}},               // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
+    {"ivf_min_batch", &Options::ivf_min_batch, 0, {1, 1e9}},
+    {"graph", &Options::graph, 2, {0, 1}, kNoRows},
+    {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
+    {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
+    {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
+    {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
+    {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
+    {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
+    {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
+    {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
+    {"i8_variant", &Options::i8_variant, 0, {0, 7}},
+    {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
+    {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
+    {"flat_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},     // MFMA shape of the flat scans, D <= 128 (layout of the scan copies: set before vdb_add)
+    {"i8_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},       // (alias)
+    {"scan_pair", &Options::scan_pair, 2, {0, 1}},                   // 1 (default): both x16 scans of an index with an int8 copy in one launch; 0: two launches
+    {"scan_prio", &Options::scan_prio, 0, {0, 2}},
+    {"f16_wide", &Options::f16_wide, 2, {0, 1}},
+    {"f16_stage_tiles", &Options::f16_stage_tiles, 3, {0, 4, 8}},
+    {"i8_nt", &Options::i8_nt, 3, {0, 1, 2}},
+    {"i8_ring", &Options::i8_ring, 4, {0, 2, 4, 8}},                 // staging ring of the serving-shaped / IVF int8 scans: 0 auto, 2 (double buffer), 4, 8
+    {"select_variant", &Options::select_variant, 0, {0, 2}},
+    {"spans_per_chunk", &Options::spans_per_chunk, 0, {0, 4096}},    // tuning: rows per workgroup chunk = 512 * value (0 = default 16)
+    {"kloop_qgroup", &Options::kloop_qgroup, 0, {0, 1024}},
+    {"ivf_bt", &Options::ivf_bt, 3, {0, 4, 16}},
+    {"ivf_part", &Options::ivf_part, 0, {0, 1024}},                  // 0 (auto) or 1..1024 spans
+    {"ivf_tps", &Options::ivf_tps, 3, {0, 16, 64}},                  // D > 128, next add: tiles per panel span (0 auto, 16 = 64-row bins, 64 = 256-row bins)
+    {"ivf_tile", &Options::ivf_tile, 3, {0, 1, 2}},
+    {"ivf_i8_group", &Options::ivf_i8_group, 2, {4, 8}},
+    {"ivf_group", &Options::ivf_group, 4, {0, 1, 2, 4}},
+    {"ivf_nw", &Options::ivf_nw, 4, {0, 2, 4, 8}},
+};
+
+// does a handle of `kind` refuse `value` of option r?  (vdb_set_option asks it of the handle's kind and the new value)
+inline bool option_refused(const OptionRow &r, unsigned kind, double value) {
+    return ((r.not_on & kind) && value != 0) || (kind == kPq && r.not_on_pq && value == r.not_on_pq);
+}
+
+// The same rule in the other order: `what` would make the handle a `kind`, and an option holds a value that kind refuses.  The
+// kinds that need the resident float32 rows also refuse a value that took effect at the last add and was set back since (for
+// the others rows of any sort are a state error of the call itself).
+void refuse_options_set(const vdb_index_s *h, const char *what, unsigned kind) {
+    for (const OptionRow &r : kOptions) {
+        if (!r.m) continue;
+        const bool in_effect = r.effect && h->*r.effect && (kind & kNeedsRows & r.not_on);
+        if (option_refused(r, kind, h->opt.*r.m) || in_effect)
+            throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + ": option '" + r.name + "' = " + std::to_string(in_effect ? 1 : h->opt.*r.m) +
+                                                 " is not available on " + kind_phrase(kind));
+    }
+}
+
 template <class F>
 void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); }
 
@@ -455,12 +567,6 @@ void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc
 inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
-// another kind of index (IVF, PQ, sign-LSH) asked for on a handle that carries a k-NN graph
-inline void knng_refuse_other(const vdb_index_s *h, const char *what) {
-    if (!h->multi && knng_on(h))
-        throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a handle that carries a k-NN graph (vdb_knng_build / "
-                                                             "vdb_knng_set): it stays a flat index");
-}
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
@@ -475,14 +581,6 @@ inline RefineCommon flat_rows(const vdb_index_s *h, const float *q, int k) {
         c.cx = h->i8_cx;
     }
     return c;
-}
-inline void pq_refuse_ivf(const vdb_index_s *h) {       // an IVF entry point on a PQ handle
-    if (!h->multi && pq_on(h))
-        throw Error(VDB_ERR_UNSUPPORTED, "this handle is a flat PQ index (vdb_pq_*): an IVF-PQ index starts from vdb_ivf_set_codec on a "
-                                         "handle without codebooks");
-}
-[[noreturn]] inline void pq_rows_are_codes() {
-    throw Error(VDB_ERR_UNSUPPORTED, "a PQ index holds its rows as codes: fill it with vdb_pq_add / vdb_pq_add_codes");
 }
 
 int kpl_for(int k) {
@@ -959,9 +1057,6 @@ void multi_rerank(vdb_index_s *m, const float *q, bool device_api, int64_t nq, c
                   int64_t *I, hipStream_t user_stream);
 vdb_index_s *multi_first_shard(vdb_index_s *m);
 void multi_for_each_shard(vdb_index_s *m, const std::function<void(vdb_index_s *)> &f);
-[[noreturn]] inline void multi_unsupported(const char *what) {
-    throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available on a multi-device index (vdb_create_multi)");
-}
 
 // ns of the rows 0 .. n-1 (ns <= n) without replacement, in draw order, as the first ns entries of the result: seeded partial
 // Fisher-Yates (the training samples of vdb_ivf_train and vdb_pq_train)
@@ -977,12 +1072,10 @@ std::vector<int64_t> sample_rows(int64_t n, int64_t ns, uint64_t seed) {
 }
 
 // vdb_add (host rows, null stream) and vdb_add_device (device rows, the caller's stream)
-void add_rows(vdb_index_s *h, const float *x, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
+void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
+    admit(h, what, kAnyKind & ~(kPq | kIvfSq8 | kIvfPq));      // (those hold their rows as codes: vdb_pq_add, vdb_ivf_add)
     if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
-    if (h->ivf_codec == 1) throw Error(VDB_ERR_UNSUPPORTED, "an SQ8 index holds its rows as codes: fill it with vdb_ivf_add");
-    if (h->ivf_codec == 2) throw Error(VDB_ERR_UNSUPPORTED, "an IVF-PQ index holds its rows as codes: fill it with vdb_ivf_add");
-    if (pq_on(h)) pq_rows_are_codes();
     set_device(h->device);
     if (knng_on(h)) {                          // (the graph describes the rows as they were)
         VDB_HIP(hipDeviceSynchronize());
@@ -1078,12 +1171,13 @@ int vdb_destroy(vdb_handle h) {
 }
 
 int vdb_add(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base) {
-    return guarded([&] { add_rows(check(hh), x_host, false, n, id_base, nullptr); });
+    return guarded([&] { add_rows(check(hh), "vdb_add", x_host, false, n, id_base, nullptr); });
 }
 
 int vdb_reset(vdb_handle hh) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_reset", kAnyKind);
         if (h->multi) return multi_reset(h);
         set_device(h->device);
         VDB_HIP(hipDeviceSynchronize());
@@ -1107,12 +1201,13 @@ int vdb_reset(vdb_handle hh) {
 }
 
 int vdb_add_device(vdb_handle hh, const float *x_dev, int64_t n, int64_t id_base, void *stream) {
-    return guarded([&] { add_rows(check(hh), x_dev, true, n, id_base, as_stream(stream)); });
+    return guarded([&] { add_rows(check(hh), "vdb_add_device", x_dev, true, n, id_base, as_stream(stream)); });
 }
 
 int vdb_search(vdb_handle hh, const float *q_host, int64_t nq, int k, float *D, int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_search", kAnyKind);
         if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (nq > 0 && (!q_host || !D || !I)) throw Error(VDB_ERR_INVALID, "null pointer");
         if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
@@ -1132,6 +1227,7 @@ int vdb_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k, floa
                       void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_search_device", kAnyKind);
         if (nq > 0 && (!D_dev || !I_dev)) throw Error(VDB_ERR_INVALID, "null output pointer");
         if (h->multi) return multi_search(h, q_dev, true, nq, k, D_dev, I_dev, nullptr, nullptr, as_stream(stream), false);
         set_device(h->device);
@@ -1145,6 +1241,7 @@ int vdb_search_partial_device(vdb_handle hh, const float *q_dev, int64_t nq, int
                               int64_t *ids_dev, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_search_partial_device", kAnyKind);
         if (nq > 0 && (!keys_dev || !ids_dev)) throw Error(VDB_ERR_INVALID, "null output pointer");
         if (h->multi) return multi_search(h, q_dev, true, nq, k, nullptr, nullptr, keys_dev, ids_dev, as_stream(stream), false);
         set_device(h->device);
@@ -1173,7 +1270,6 @@ namespace {
 void rerank_device_impl(vdb_index_s *h, const float *dq, int64_t nq, const int64_t *cand, int ncand, int k, float *D,
                         int64_t *I, hipStream_t st, double *pk = nullptr, int64_t *pi = nullptr, const int64_t *segs = nullptr,
                         int nseg = 0) {
-    if (h->ivf_codec == 2) throw Error(VDB_ERR_STATE, "vdb_rerank is not available on an IVF-PQ index: its rows are codes in list order");
     if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
     if (nq < 0 || ncand < 0) throw Error(VDB_ERR_INVALID, "negative size");
@@ -1207,6 +1303,7 @@ int vdb_rerank_device(vdb_handle hh, const float *q_dev, int64_t nq, const int64
                       float *D_dev, int64_t *I_dev, void *stream) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_rerank_device", kAnyKind & ~kIvfPq, VDB_ERR_STATE);
         if (h->multi) return multi_rerank(h, q_dev, true, nq, cand_dev, ncand, k, D_dev, I_dev, as_stream(stream));
         set_device(h->device);
         rerank_device_impl(h, q_dev, nq, cand_dev, ncand, k, D_dev, I_dev, as_stream(stream));
@@ -1217,8 +1314,8 @@ int vdb_rerank(vdb_handle hh, const float *q_host, int64_t nq, const int64_t *ca
                int64_t *I) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_rerank", kAnyKind & ~kIvfPq, VDB_ERR_STATE);       // (the other IVF kinds answer "not built" below: same code)
         if (h->multi) return multi_rerank(h, q_host, false, nq, cand_host, ncand, k, D, I, nullptr);
-        if (h->ivf_codec == 2) throw Error(VDB_ERR_STATE, "vdb_rerank is not available on an IVF-PQ index: its rows are codes in list order");
         if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
         if (nq <= 0) {
             if (nq < 0) throw Error(VDB_ERR_INVALID, "negative query count");
@@ -1240,6 +1337,7 @@ int vdb_rerank(vdb_handle hh, const float *q_host, int64_t nq, const int64_t *ca
 int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_stats", kAnyKind);
         if (!out) throw Error(VDB_ERR_INVALID, "null pointer");
         if (h->multi) return multi_stats(h, out);
         set_device(h->device);
@@ -1335,90 +1433,19 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
     });
 }
 
-namespace {
-// kinds of index that refuse a non-zero value of an option, in the order they are asked
-constexpr unsigned kSq8 = 1, kLsh = 2, kPq = 4, kIvfPq = 8, kKnng = 16;
-constexpr struct { unsigned kind; const char *what; } kRefusals[] = {
-    {kSq8, "an SQ8 index"},
-    {kLsh, "an index with sign-LSH codes (they are encoded from, and re-ranked against, the resident float32 rows)"},
-    {kPq, "a PQ index (its rows are codes; every search makes its panels from them)"},
-    {kIvfPq, "an IVF-PQ index (its rows are codes; every batch makes its panels from them)"},
-    {kKnng, "an index with a k-NN graph (it is searched against the resident float32 rows)"}};
-
-struct OptionRow {
-    const char *name;
-    int Options::*m;
-    int n;                     // > 0: one of v[0 .. n), integers only | 0: v[0] <= value <= v[1], truncated toward zero | < 0: any value, stored as value != 0
-    double v[4];
-    unsigned not_on = 0;       // kinds of index that refuse a non-zero value
-    int not_on_pq = 0;         // a value that a PQ index refuses as well: its panels are made in layout "x16" (octs) only
-    int64_t Options::*m64 = nullptr;       // instead of m
-};
-constexpr OptionRow kOptions[] = {
-    {"force_path", &Options::force_path, 4, {0, 1, 2, 3}},
-    {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
-    {"list_cap", &Options::list_cap, 0, {0, 65536}},
-    {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
-    {"int8_only", &Options::int8_only, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq | kKnng},
-    {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
-    {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
-    {"stream_panels", &Options::stream_panels, 2, {0, 1}, kSq8 | kLsh | kPq | kIvfPq | kKnng},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
-    {"stream_slab_rows", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::stream_slab_rows},   // rows of the scratch slab of a streamed index (0 = default 1 280 000)
-    {"upload_block_mb", &Options::upload_block_mb, 0, {0, 4096}},    // staging block of the row-block ingestion (0 = default 64 MiB)
-    {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
-    {"fused_stats", &Options::fused_stats, 2, {0, 1}},               // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
-    {"ivf_min_batch", &Options::ivf_min_batch, 0, {1, 1e9}},
-    {"graph", &Options::graph, 2, {0, 1}, kSq8 | kPq | kIvfPq},
-    {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
-    {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
-    {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
-    {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
-    {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
-    {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
-    {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
-    {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
-    {"i8_variant", &Options::i8_variant, 0, {0, 7}},
-    {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
-    {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
-    {"flat_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},     // MFMA shape of the flat scans, D <= 128 (layout of the scan copies: set before vdb_add)
-    {"i8_shape", &Options::flat_shape, 3, {0, 16, 32}, 0, 32},       // (alias)
-    {"scan_pair", &Options::scan_pair, 2, {0, 1}},                   // 1 (default): both x16 scans of an index with an int8 copy in one launch; 0: two launches
-    {"scan_prio", &Options::scan_prio, 0, {0, 2}},
-    {"f16_wide", &Options::f16_wide, 2, {0, 1}},
-    {"f16_stage_tiles", &Options::f16_stage_tiles, 3, {0, 4, 8}},
-    {"i8_nt", &Options::i8_nt, 3, {0, 1, 2}},
-    {"i8_ring", &Options::i8_ring, 4, {0, 2, 4, 8}},                 // staging ring of the serving-shaped / IVF int8 scans: 0 auto, 2 (double buffer), 4, 8
-    {"select_variant", &Options::select_variant, 0, {0, 2}},
-    {"spans_per_chunk", &Options::spans_per_chunk, 0, {0, 4096}},    // tuning: rows per workgroup chunk = 512 * value (0 = default 16)
-    {"kloop_qgroup", &Options::kloop_qgroup, 0, {0, 1024}},
-    {"ivf_bt", &Options::ivf_bt, 3, {0, 4, 16}},
-    {"ivf_part", &Options::ivf_part, 0, {0, 1024}},                  // 0 (auto) or 1..1024 spans
-    {"ivf_tps", &Options::ivf_tps, 3, {0, 16, 64}},                  // D > 128, next add: tiles per panel span (0 auto, 16 = 64-row bins, 64 = 256-row bins)
-    {"ivf_tile", &Options::ivf_tile, 3, {0, 1, 2}},
-    {"ivf_i8_group", &Options::ivf_i8_group, 2, {4, 8}},
-    {"ivf_group", &Options::ivf_group, 4, {0, 1, 2, 4}},
-    {"ivf_nw", &Options::ivf_nw, 4, {0, 2, 4, 8}},
-};
-}  // namespace
-
 int vdb_set_option(vdb_handle hh, const char *key, double value) {
     return guarded([&] {
         auto *h = check(hh);
+        admit(h, "vdb_set_option", kAnyKind);
         if (!key) throw Error(VDB_ERR_INVALID, "null option name");
         if (h->multi) return multi_set_option(h, key, value);
         const std::string k(key);
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
         const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
-        const bool known = r != std::end(kOptions);
+        if (r == std::end(kOptions)) throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
         // what this kind of index refuses comes first, whatever the value is otherwise
-        const unsigned kinds = (h->ivf_codec == 1 ? kSq8 : 0) | (h->lsh_nbits > 0 ? kLsh : 0) | (pq_on(h) ? kPq : 0) | (h->ivf_codec == 2 ? kIvfPq : 0) | (knng_on(h) ? kKnng : 0);
-        for (const auto &x : kRefusals)
-            if (known && value != 0 && (kinds & r->not_on & x.kind))
-                throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' is not available on " + x.what);
-        if (known && (kinds & kPq) && r->not_on_pq && value == r->not_on_pq)
-            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' = " + std::to_string((int)value) + " is not available on a PQ index: its panels are "
-                                             "made in layout \"x16\" (octs) only");
-        if (!known) throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
+        if (option_refused(*r, kind_of(h), value))
+            throw Error(VDB_ERR_UNSUPPORTED, "option '" + k + "' = " + std::to_string((int)value) + " is not available on " + kind_phrase(kind_of(h)));
         auto number = [](double v) { return v == HUGE_VAL ? std::string("inf") : std::to_string((long)v); };
         if (r->n > 0 && std::find(r->v, r->v + r->n, value) == r->v + r->n) {
             std::string list = number(r->v[0]);
