@@ -17,6 +17,14 @@
 //     (same bytes per tile as the 32-row layout: 2 or 4 KiB); qpanels8[q / 16][ks2][lane]: query column (lane & 15), same dims.
 //   * a bin is complete after 16 tiles: the two lane groups of a half exchange their minima (ds_swizzle, lane ^ 16), both
 //     merge, and each stores every other column block of the wave -- ~40 vector operations per 16 tiles beside ~800 of select.
+//
+// Two loops share the set-up, the staging, the bin flush and the superbin epilogue of scan_i8x16_body:
+//   * the batch shapes (8 waves, ring of 2, rolled stages) run scan_i8x16_batch_loop: one code path for all waves, the select of
+//     tile t-1 and the LDS reads of tile t+1 placed instruction by instruction between the MFMAs of tile t (round 8; sift1m scan
+//     0.843 -> 0.813 ms, profiles/r08_scan_interleaved_ab.txt).  Option "scan_prio" does not reach this loop: there is no early /
+//     late half to prefer.
+//   * the serving shapes (1 / 2 / 4 waves, rings of 4 / 8, unrolled stages) keep the loop of round 4: per tile an MFMA phase and a
+//     select phase fenced by sched_barrier, the two halves of a workgroup in anti-phase.
 #pragma once
 #include "scan_i8.hpp"
 
@@ -32,6 +40,123 @@ __device__ __forceinline__ int swap16(int v) { return __builtin_amdgcn_ds_swizzl
 // the host for an index in this layout).
 template <int KS2, int ST, int RING>
 constexpr int scan_i8x16_lds_bytes() { return RING * (ST * 2 * KS2 * 64 * 16 + ST * 32 * 4); }
+
+// ---- the batch loop (8 waves, ring of 2, rolled stages: ST = 8 with CB = 8 or 4, ST = 4 with CB = 8), software-pipelined per wave ----
+// One code path for all eight waves.  A step issues the MFMAs of tile t and, in their gaps, the oct select of tile t-1 and the LDS
+// reads of tile t+1: behind every MFMA the vector-issue instructions that fit its 16 cycles (an MFMA holds the SIMD's vector issue
+// for 8 of them, an ordinary VALU instruction for 4), fixed with sched_group_barrier.  Packed in whole phases of ~500 cycles (the
+// early / late loops of the body below) the same work left the matrix pipe 0.73 busy; instruction by instruction the staged
+// microbenchmark reaches 0.95 (scripts/microbench/mfma_i8_shapes.hip, rows 'pipelined'; profiles/r08_mfma_i8_interleaved.txt).
+//   * two accumulator sets by tile parity.  The first half of a step (the MFMAs that take the bias as C) claims the new set while the
+//     min trees, column block by column block, free the old one; the second half carries the top-2 folds and the LDS reads.
+//   * the stage is unrolled: register names are static, a tile's fragments and biases are one base address per buffer + immediates.
+//   * the first step retires a "previous tile" of +inf scores (as the late half of the body always has); the last tile is retired
+//     after the loop.  Bin (span, h) is flushed once the select of its tile 15 is done: behind the step of tile 0 of the next span,
+//     or in the drain.
+template <int N_MFMA, int N_VALU, int N_DS>
+__device__ __forceinline__ void x16_gap_pattern() {
+    constexpr int R = (N_VALU + N_DS + N_MFMA - 1) / N_MFMA;      // vector-issue instructions behind each MFMA
+    static_assert(N_DS <= N_MFMA && R >= 2, "one LDS read per gap");
+#pragma unroll
+    for (int i = 0; i < N_MFMA; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);          // MFMA
+        if (i < N_DS) {
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);    // DS read
+            __builtin_amdgcn_sched_group_barrier(0x2, R - 1, 0);  // VALU
+        } else {
+            __builtin_amdgcn_sched_group_barrier(0x2, R, 0);
+        }
+    }
+}
+
+template <int KS2, int ST, int CB, class StageIssue, class BiasStore, class FlushBin>
+__device__ __forceinline__ void scan_i8x16_batch_loop(const unsigned char *smem, const int4v (&bq)[CB][KS2], int (&m1)[CB], int (&m2)[CB],
+                                                      int nstages, int64_t span0, int lane, StageIssue &&stage_issue,
+                                                      BiasStore &&stage_bias_store, FlushBin &&flush_bin) {
+    constexpr int NV = 2 * KS2, kStageVec = ST * NV * 64, TPS = kTilesPerSpan, SPS = TPS / ST;
+    constexpr int NM = 2 * KS2 * CB, NH = NM / 2;                 // MFMAs per tile, per half step
+    static_assert(ST % 2 == 0 && TPS % ST == 0, "tile parity must be static in the unrolled stage");
+    const int g = lane >> 4;
+    const unsigned id_hi = (g & 1) ? 16u : 0u;
+    int4v acc[2][2][CB], fr[2][NV], cin[2][2];                    // [tile parity]
+    int q[CB];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[1][rb][cb][r] = (int)(kI8Inf >> 6);   // "previous tile" of the first step: (x << 6) == "+inf", never wins
+    auto read_tile = [&](int p, const int4v *A, const int4v *B4, int t) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) fr[p][v] = A[(t * NV + v) * 64];
+        cin[p][0] = B4[t * 8];
+        cin[p][1] = B4[t * 8 + 1];
+    };
+    auto mfma_half = [&](int p, int half) {
+#pragma unroll
+        for (int m = half * NH; m < (half + 1) * NH; ++m) {
+            const int ks = m / (2 * CB), rb = (m / CB) % 2, cb = m % CB;
+            acc[p][rb][cb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fr[p][2 * ks + rb], bq[cb][ks], ks == 0 ? cin[p][rb] : acc[p][rb][cb], 0, 0, 0);
+        }
+    };
+    // one oct per column block: v = (min of the lane's 8 rows << 6) | oct id, id = 16 (g & 1) + tile of the bin
+    auto min_trees = [&](int o) {
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            const int t1 = imin(imin(acc[o][0][cb][0], acc[o][0][cb][1]), acc[o][0][cb][2]);
+            const int t2 = imin(imin(acc[o][0][cb][3], acc[o][1][cb][0]), acc[o][1][cb][1]);
+            q[cb] = imin(imin(imin(acc[o][1][cb][2], acc[o][1][cb][3]), t1), t2);
+        }
+    };
+    auto folds = [&](int t_bin) {
+        const unsigned idv = (unsigned)__builtin_amdgcn_readfirstlane(t_bin) | id_hi;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+            const int v = (int)(((unsigned)q[cb] << 6) | idv);
+            m2[cb] = imed3(m1[cb], m2[cb], v);
+            m1[cb] = imin(m1[cb], v);
+        }
+    };
+    for (int st = 0; st < nstages; ++st) {
+        const int buf = st & 1;
+        if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);
+        const int4v *A = reinterpret_cast<const int4v *>(smem + buf * (kStageVec * 16)) + lane;
+        const int4v *B4 = reinterpret_cast<const int4v *>(smem + 2 * kStageVec * 16 + buf * (ST * 32 * 4)) + g * 2;
+        const int ts0 = (st % SPS) * ST;
+        read_tile(0, A, B4, 0);
+#pragma unroll
+        for (int t = 0; t < ST; ++t) {
+            const int p = t & 1, o = p ^ 1;
+            // first half: the MFMAs that take the bias claim the new set, the min trees free the old one
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_half(p, 0);
+            min_trees(o);
+            x16_gap_pattern<NH, 4 * CB, 0>();
+            __builtin_amdgcn_sched_barrier(0);
+            // (empty statements that use the select's results where they are due: instruction selection is free to order pure
+            //  arithmetic across a sched_barrier, and with a branch further down the stage -- the flush, the bias store -- the
+            //  compiler sinks the whole stage's select chains below it and spills the accumulators they wait for)
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(q[cb]));
+            // second half: the remaining MFMAs, the top-2 folds of tile t-1, the LDS reads of tile t+1
+            __builtin_amdgcn_sched_barrier(0);
+            if (t + 1 < ST) read_tile(o, A, B4, t + 1);
+            mfma_half(p, 1);
+            folds((ts0 + t + TPS - 1) % TPS);
+            x16_gap_pattern<NH, 3 * CB + 1, NV + 2>();
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(m1[cb]), "+v"(m2[cb]));
+            if (t == 0 && st > 0 && ts0 == 0) flush_bin(span0 + st / SPS - 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (st + 1 < nstages) stage_bias_store(buf ^ 1);
+        __syncthreads();
+    }
+    min_trees((ST - 1) & 1);
+    folds(TPS - 1);
+    flush_bin(span0 + nstages / SPS - 1);
+}
 
 // (the body is a device function over a caller-provided LDS block so that scan_pair_x16_kernel, scan_x16.hpp, can hold it
 //  next to the fp16 scan in ONE launch)
@@ -193,6 +318,9 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
         return;
     }
 
+    if constexpr (NWAVES == 8 && RING == 2 && UNR == 1) {          // the batch shapes
+        scan_i8x16_batch_loop<KS2, ST, CB>(smem, bq, m1, m2, nstages, span0, lane, stage_issue, stage_bias_store, flush_bin);
+    } else {                                                       // the serving shapes: the loop of round 4, as it was (not re-indented)
     int4v fr[NV], cin[2], acc[2][CB];
     auto read_phase = [&](const int4v *A_tile, const int4v *c_tile) {
 #pragma unroll
@@ -279,6 +407,7 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
         select_phase(TPS - 1);
         flush_bin(span1 - 1);
     }
+    }   // serving shapes
 
     const size_t so = (size_t)(chunk * 2 + h) * a.Qpad + col0;
 #pragma unroll
