@@ -55,7 +55,7 @@ enum vdb_status {
 };
 
 /* which search path served the last call (vdb_stats_t.last_path) */
-enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5 };
+enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6 };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -65,9 +65,9 @@ typedef struct vdb_stats_s {
     int32_t last_path;         /* enum vdb_path */
     int32_t corpus_fp16_exact; /* 1 if every corpus value is exactly representable in the fp16 scan copy */
     int64_t last_nq;
-    int64_t last_candidates;   /* candidate groups (4 consecutive rows each; 8 on the flat int8 scan) re-scored exactly */
+    int64_t last_candidates;   /* candidate groups (4 consecutive rows each; 8 on the flat int8 scan) re-scored exactly (hash-table LSH: candidates) */
     int64_t last_rescan_bins;  /* 256-row bins re-scanned exactly (collision guard) */
-    int64_t last_fallback_queries; /* queries whose work list overflowed -> exhaustive exact scan (LSH: exact fallback of the select) */
+    int64_t last_fallback_queries; /* queries whose work list overflowed -> exhaustive exact scan (LSH, hash-table LSH: exact fallback of the select) */
     float last_scan_ms;        /* mean HIP-event time of the dominant (scan) kernel over the searches recorded since
                                   timing was switched on; 0 if not timed */
     float last_total_ms;       /* same for the whole device pipeline */
@@ -77,7 +77,8 @@ typedef struct vdb_stats_s {
                                   2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
-    int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists) */
+    int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
+                                  queries that took the brute-force fallback */
     int64_t upload_blocks;     /* row blocks the last vdb_add / vdb_ivf_add streamed through the pinned staging buffers */
     int64_t graph_replays;     /* searches served by launching the captured hipGraph (option "graph") since the handle was made */
     int32_t ndevices;          /* shards of the handle: 1, or the ndev of vdb_create_multi (sums / maxima over the shards above) */
@@ -98,37 +99,41 @@ typedef struct vdb_stats_s {
  *   LSH       a projection (vdb_lsh_set_projection)      IVF-Flat  centroids or filed rows, codec 0
  *   knng      a k-NN graph (vdb_knng_build / _set;       IVF-SQ8   vdb_ivf_set_codec 1
  *             an add or vdb_reset makes it flat again)   IVF-PQ    vdb_ivf_set_codec 2
- *   multi     vdb_create_multi (flat or IVF-Flat rows)
+ *   multi     vdb_create_multi (flat or IVF-Flat rows)   LSHT      hash tables (vdb_lsht_set_tables)
  * A call on a kind it does not serve is refused before it looks at its arguments or touches the handle, with a message that names
  * the call and the kind: U = VDB_ERR_UNSUPPORTED, S = VDB_ERR_STATE.  "+" = admitted (the call's own state and argument checks
  * follow: "no centroids", "not built", ...).
- *                                                       flat  LSH  knng  PQ   IVF-Flat  IVF-SQ8  IVF-PQ  multi
- *   vdb_add(_device)                                     +     +    +    U      +         U        U       +
+ *                                                       flat  LSH  LSHT  knng  PQ   IVF-Flat  IVF-SQ8  IVF-PQ  multi
+ *   vdb_add(_device)                                     +     +    +     +    U      +         U        U       +
  *   vdb_search*, vdb_reserve, vdb_reset, vdb_stats,
  *     vdb_set_option, the get_codebooks / get_projection
- *     / vdb_knng_get calls (M, nbits, degree 0 elsewhere) +     +    +    +      +         +        +       +
- *   vdb_rerank(_device)                                  +     +    +    +      +         +        S       +
- *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U    U      +         +        +       +
- *   vdb_ivf_set_codec 1 | 2                              +     U    U    U      +         +        +       U
- *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +    U      +         +        +       +
- *   vdb_ivf_sq8_*, vdb_ivf_get_codes                     S     S    S    U      S         +        U       U
+ *     / get_tables / vdb_knng_get calls (M, nbits, T,
+ *     degree 0 elsewhere)                                +     +    +     +    +      +         +        +       +
+ *   vdb_rerank(_device)                                  +     +    +     +    +      +         +        S       +
+ *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
+ *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
+ *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
+ *   vdb_ivf_sq8_*, vdb_ivf_get_codes                     S     S    S     S    U      S         +        U       U
  *   vdb_ivfpq_train / _set_codebooks / _add_codes /
- *     _get_codes                                         S     S    S    U      S         S        +       U
- *   vdb_pq_train, vdb_pq_set_codebooks                   +     U    U    +      U         U        U       U
- *   vdb_pq_add, vdb_pq_add_codes, vdb_pq_get_codes       S     S    S    +      S         S        U       U
- *   vdb_lsh_set_projection                               +     +    U    U      U         U        U       U
- *   vdb_lsh_candidates*, vdb_lsh_search*                 S     +    U    U      S         S        U       U
- *   vdb_lsh_get_codes                                    S     +    S    U      S         S        U       U
- *   vdb_knng_build, vdb_knng_set, vdb_knng_search*       +     U    +    U      U         U        U       U
- *   vdb_debug_scan_scores                                +     +    +    +      +         +        +       U
+ *     _get_codes                                         S     S    S     S    U      S         S        +       U
+ *   vdb_pq_train, vdb_pq_set_codebooks                   +     U    U     U    +      U         U        U       U
+ *   vdb_pq_add, vdb_pq_add_codes, vdb_pq_get_codes       S     S    S     S    +      S         S        U       U
+ *   vdb_lsh_set_projection                               +     +    U     U    U      U         U        U       U
+ *   vdb_lsh_candidates*, vdb_lsh_search*                 S     +    U     U    U      S         S        U       U
+ *   vdb_lsh_get_codes                                    S     +    U     S    U      S         S        U       U
+ *   vdb_lsht_set_tables                                  +     U    +     U    U      U         U        U       U
+ *   vdb_lsht_candidates*, vdb_lsht_search*,
+ *     vdb_lsht_get_keys                                  S     U    +     U    U      U         U        U       U
+ *   vdb_knng_build, vdb_knng_set, vdb_knng_search*       +     U    U     +    U      U         U        U       U
+ *   vdb_debug_scan_scores                                +     +    +     +    +      +         +        +       U
  *   options refused (U), in either order of the calls:
- *     "int8_only" = 1, "stream_panels" = 1               -     U    U    U      -         U        U       -
- *     "graph" = 1                                        -     -    -    U      -         U        U       U
- *     "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -     -    -    U      -         -        -       -
+ *     "int8_only" = 1, "stream_panels" = 1               -     U    U     U    U      -         U        U       -
+ *     "graph" = 1                                        -     -    -     -    U      -         U        U       U
+ *     "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -     -    -     -    U      -         -        -       -
  * "Either order": vdb_set_option refuses the value on a handle of the kind, and the call that makes a handle that kind
- * (vdb_lsh_set_projection, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
- * which the option holds the value; LSH and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
- * LSH and k-NN graph search calls are refused while option "graph" is 1. */
+ * (vdb_lsh_set_projection, vdb_lsht_set_tables, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
+ * which the option holds the value; LSH, LSHT and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
+ * LSH, hash-table LSH and k-NN graph search calls are refused while option "graph" is 1. */
 
 /* ---- library ---------------------------------------------------------------------------- */
 int vdb_abi_version(void);
@@ -359,6 +364,56 @@ int vdb_lsh_search(vdb_handle h, const float *q_host, int64_t nq, int k, int nca
 int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, int ncand, float *D_dev, int64_t *I_dev,
                           void *stream);
 
+/* ---- hash-table LSH -- replaces the reference's own LSHIndexer / LSHSearcher / LSH (src/algorithms/lsh.py; its `lsh` config):
+ *      T tables of H random projections, votes over the colliding buckets, a candidate cap, exact scoring ------------------------
+ * The entry points live on an ordinary flat handle of vdb_create: the index keeps its float32 rows and scan copies, and next to
+ * them T table keys per row.  The contract follows lsh.py step by step, so that its results are reproduced id for id
+ * (tests/lsh_tables_restatement.py restates it in NumPy):
+ *   parameters  T = num_tables in 1..32; H = hash_size; mode 0 "sign" (the reference's cosine branch): H in 1..64; mode 1 "E2"
+ *               (its L2 branch): H in 1..16, bucket_width w > 0 (float32), offsets b float32 (T, H).  W = words per table key:
+ *               ceil(H / 32) in sign mode, H in E2 mode; T W <= 128.  Projections P float32 (T, H, dim) come from the caller
+ *               (the library draws no random numbers)
+ *   projection  s[t][h](x) = sum_d (double)x[d] * (double)P[t][h][d], accumulated from 0.0 with d ascending, one rounding per
+ *               step: the arithmetic of the sign-LSH bits above
+ *   key words   uint32, T W per vector, table t at words [t W, (t + 1) W).  sign: bit h of table t is bit h % 32 of word
+ *               t W + h / 32, set iff s >= 0 (-0.0 gives 1, NaN gives 0), unused bits 0.  E2: word t W + h = the int32 code
+ *               floor((s + (double)b[t][h]) / (double)w), bit-cast, saturated to [INT32_MIN, INT32_MAX], NaN -> INT32_MIN
+ *   votes       row r collides with query q in table t iff all W words of that table are equal; votes(q, r) = the number of
+ *               such tables, first(q, r) = the smallest such t
+ *   candidates  of q: the rows with votes >= 1, ordered by ((T - votes) T + first, id), both ascending, the first
+ *               min(ncand, their number) of them -- Counter.most_common() over buckets that hold ids in insertion order.  ids
+ *               int64 (with id_base), votes int32; padding is id -1, votes 0
+ *   search      exactly vdb_rerank applied to those candidates.  fallback = 1: a query with no colliding row gets the exact
+ *               flat top-k of the handle instead (the reference's list(range(n)), which is not capped); fallback = 0: such a
+ *               query is all padding
+ * The select is the counting select of the sign-LSH calls over T * T classes, without the pairs that have no vote; per query
+ * c = min(ncand, colliding rows).  vdb_stats after a call: last_path = VDB_PATH_LSHT, last_candidates = candidates re-scored,
+ * last_fallback_queries = queries that took the exact fallback of the select (option "lsh_force_fallback" = 1: all of them),
+ * last_rows_scanned = ntotal x queries that took the brute-force fallback; with option "timing", last_prep_ms = query keys +
+ * sample, last_scan_ms = the vote scans, last_tail_ms = select + re-rank.
+ * ncand is in [1, 65 536] (ncand > ntotal pads); k follows vdb_rerank.  VDB_ERR_STATE: a call before tables, or before rows.
+ * VDB_ERR_INVALID: a parameter outside the ranges above.  Which handles admit these calls and what a handle with tables refuses:
+ * the table of kinds above (column "LSHT").  A handle without tables behaves exactly as before. */
+/* installs the tables: proj_host (T, H, dim), offsets_host (T, H) and bucket_width (mode 1 only; ignored in mode 0).  With rows
+ * present they are keyed from the resident float32 rows.  Every later vdb_add / vdb_add_device keys the rows it appends (appended
+ * keys equal those of one add).  vdb_reset drops the keys and keeps the tables; keys and tables count in bytes_resident. */
+int vdb_lsht_set_tables(vdb_handle h, int num_tables, int hash_size, int mode, const float *proj_host, const float *offsets_host,
+                        float bucket_width);
+/* num_tables = 0: no tables.  Every pointer but num_tables may be NULL */
+int vdb_lsht_get_tables(vdb_handle h, int *num_tables, int *hash_size, int *mode, float *proj_host, float *offsets_host,
+                        float *bucket_width);
+/* keys of the indexed rows, uint32 (ntotal, T W), in id (insertion) order */
+int vdb_lsht_get_keys(vdb_handle h, uint32_t *keys_host);
+/* votes (nq, ncand) int32, ids (nq, ncand) int64, caller-allocated; host buffers, synchronous */
+int vdb_lsht_candidates(vdb_handle h, const float *q_host, int64_t nq, int ncand, int32_t *votes, int64_t *ids);
+/* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
+int vdb_lsht_candidates_device(vdb_handle h, const float *q_dev, int64_t nq, int ncand, int32_t *votes_dev, int64_t *ids_dev,
+                               void *stream);
+/* D (nq, k) float32, I (nq, k) int64 */
+int vdb_lsht_search(vdb_handle h, const float *q_host, int64_t nq, int k, int ncand, int fallback, float *D, int64_t *I);
+int vdb_lsht_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, int ncand, int fallback, float *D_dev,
+                           int64_t *I_dev, void *stream);
+
 /* ---- flat PQ<M> -- replaces faiss.index_factory(d, "PQ<M>", metric) (IndexPQ(d, M, 8); the reference's `pq` config) --------
  * M sub-vectors of dsub = dim / M dimensions, 256 centroids each, one byte per sub-vector.  The entry points live on an ordinary
  * handle of vdb_create; once codebooks exist the handle is a PQ index: it keeps the codes (M bytes per row), one float32 of scan
@@ -483,8 +538,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       rewrites the queries in place.  (The call that drops a stale graph always runs eagerly: on ROCm 7.x an
  *                       executable graph instantiated right behind the destruction of its predecessor faults on its second
  *                       replay -- a runtime defect in graph packet capture, profiles/r04_graph_fault_cause.txt.)
- *     "lsh_force_fallback"  0 (default) | 1: every query of a vdb_lsh_candidates / vdb_lsh_search call takes the exact fallback
- *                       of the select (tests; same results)
+ *     "lsh_force_fallback"  0 (default) | 1: every query of a vdb_lsh_candidates / vdb_lsh_search / vdb_lsht_candidates /
+ *                       vdb_lsht_search call takes the exact fallback of the select (tests; same results)
  *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
  *                       kernels on the codes (0 = default .. 1e9)
  *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)

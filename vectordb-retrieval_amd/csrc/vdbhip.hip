@@ -31,6 +31,7 @@
 #include "ivf_pq.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
+#include "lsh_tables.hpp"
 #include "pq.hpp"
 #include "knng.hpp"
 
@@ -183,6 +184,7 @@ struct KeptBufs {
     DevBuf stats{"stats"};
     DevBuf sq8_cent{"sq8_cent"}, sq8_param{"sq8_param"};     // SQ8: centroids [nlist][D4] (IVF-PQ too) and {vmin, vdiff} [2][D4], zero padded
     DevBuf lsh_rt{"lsh_rt"};                                 // sign-LSH: R transposed [dim][nbits]
+    DevBuf lsht_pt{"lsht_pt"}, lsht_off{"lsht_off"};         // hash-table LSH: projections transposed [dim][T * H], offsets [T * H]
     DevBuf pq_cb{"pq_cb"};                                   // PQ: codebooks float32 [M][256][dsub]
     DevBuf ivfpq_cb{"ivfpq_cb"};                             // IVF-PQ: codebooks of the residuals, float32 [M][256][dsub]
 };
@@ -205,6 +207,7 @@ struct IvfPlanBufs {
 struct CodeBufs {
     DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row (IVF-PQ too), both in list order
     DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
+    DevBuf lsht_keys{"lsht_keys"};                           // hash-table LSH: table keys [N][lsht_kw]
     DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
     DevBuf ivfpq_codes{"ivfpq_codes"};                       // IVF-PQ: codes [N][M] in list order
     DevBuf knng_nbrs{"knng_nbrs"};                           // k-NN graph: local row numbers [N][knng_degree], -1 tails
@@ -213,6 +216,7 @@ struct CodeBufs {
 struct LshWorkspace {
     DevBuf lsh_qcodes{"lsh_qcodes"}, lsh_hist{"lsh_hist"}, lsh_small{"lsh_small"}, lsh_list{"lsh_list"}, lsh_stat{"lsh_stat"};
     DevBuf lsh_cand_i{"lsh_cand_i"}, lsh_cand_h{"lsh_cand_h"};
+    DevBuf lsht_empty{"lsht_empty"};                         // hash-table LSH: count + list of the queries without a colliding row
 };
 // per-search workspace of the k-NN graph search: the counters, and L between the launches of a timed call   (freed with the handle)
 struct KnngWorkspace {
@@ -385,6 +389,12 @@ struct vdb_index_s {
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
     std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
+    // hash-table LSH of a flat index (lsh_tables.inc; vdb_lsht_set_tables): T keys per row, kept next to the float32 rows
+    int lsht_T = 0, lsht_H = 0, lsht_mode = 0;   // tables (0 = none), projections per table, 0 sign keys | 1 E2 bucket keys
+    int lsht_W = 0, lsht_wp = 0, lsht_kw = 0;    // words per table key: of the contract, as stored (lsh_tables.hpp); lsht_kw = T * lsht_wp per row
+    float lsht_width = 0.f;                  // E2: bucket width
+    int64_t lsht_rows = 0;                   // rows lsht_keys covers (== N whenever the index is searchable)
+    std::vector<float> lsht_proj, lsht_off;  // host copies [T][H][dim], [T][H]
     // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
     int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
@@ -411,9 +421,9 @@ namespace {
 // What a handle IS decides which entry points it admits and which options it refuses.  kind_of is the only place that reads
 // the raw fields to decide that (computed, not stored: nothing to keep in step); kKinds names each kind in messages; admit is
 // the first line of every entry point, its mask the kinds that call serves; refuse_options_set is the option rule of kOptions
-// read in the other order.  A new kind is one enum bit, one row of kKinds, a test in kind_of and its own masks.
-enum Kind : unsigned { kFlat = 1, kLsh = 2, kKnng = 4, kPq = 8, kIvfFlat = 16, kIvfSq8 = 32, kIvfPq = 64, kMulti = 128 };
-constexpr unsigned kAnyKind = 255, kIvf = kIvfFlat | kIvfSq8 | kIvfPq;
+// read in the other order.  A new kind is one enum bit (and a wider kAnyKind), one row of kKinds, a test in kind_of and its own masks.
+enum Kind : unsigned { kFlat = 1, kLsh = 2, kKnng = 4, kPq = 8, kIvfFlat = 16, kIvfSq8 = 32, kIvfPq = 64, kMulti = 128, kLsht = 256 };
+constexpr unsigned kAnyKind = 511, kIvf = kIvfFlat | kIvfSq8 | kIvfPq;
 constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
     {kMulti, "a multi-device index (vdb_create_multi)"},
     {kPq, "a flat PQ index (vdb_pq_*: its rows are codes, its panels are made per search in layout \"x16\" only)"},
@@ -421,13 +431,14 @@ constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
     {kIvfSq8, "an IVF index with the SQ8 codec (its rows are codes in list order)"},
     {kIvfFlat, "an IVF index (centroids set: its rows sit in list order)"},
     {kLsh, "an index with sign-LSH codes (vdb_lsh_set_projection: it stays a flat index)"},
+    {kLsht, "an index with LSH hash tables (vdb_lsht_set_tables: it stays a flat index)"},
     {kKnng, "an index with a k-NN graph (vdb_knng_build / vdb_knng_set: it stays a flat index)"},
     {kFlat, "a flat index"}};
 
 unsigned kind_of(const vdb_index_s *h) {
     if (h->multi) return kMulti;             // (nlist / ivf_built of such a handle describe the whole index)
     const unsigned ivf = h->ivf_codec == 2 ? kIvfPq : h->ivf_codec == 1 ? kIvfSq8 : (h->nlist > 0 || h->coarse || h->ivf_built) ? kIvfFlat : 0;
-    const unsigned k = (h->pq_M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0);
+    const unsigned k = (h->pq_M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0) | (h->lsht_T > 0 ? kLsht : 0);
     if (k & (k - 1)) throw Error(VDB_ERR_STATE, "internal: handle is two kinds at once");
     return k ? k : kFlat;
 }
@@ -454,7 +465,7 @@ struct OptionRow {
     int64_t Options::*m64 = nullptr;       // instead of m
     bool vdb_index_s::*effect = nullptr;   // set while the value of the last add is in effect, whatever the option says now
 };
-constexpr unsigned kNoRows = kIvfSq8 | kPq | kIvfPq, kNeedsRows = kLsh | kKnng;     // no float32 rows at all | encoded from / searched against the resident ones
+constexpr unsigned kNoRows = kIvfSq8 | kPq | kIvfPq, kNeedsRows = kLsh | kKnng | kLsht;     // no float32 rows at all | encoded from / searched against the resident ones
 constexpr OptionRow kOptions[] = {
     {"force_path", &Options::force_path, 4, {0, 1, 2, 3}},
     {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
@@ -564,6 +575,7 @@ constexpr size_t kMaxTimedCalls = 1024;
 long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
+void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st);       // lsh_tables.inc: table keys of the rows an add appended
 inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
@@ -1084,6 +1096,7 @@ void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, 
     const int64_t n0 = (h->N == 0 || h->ivf_built) ? 0 : h->N;
     append_rows(h, x, on_device, n, id_base, st);
     lsh_encode_rows(h, n0, st);
+    lsht_key_rows(h, n0, st);
 }
 
 // vdb_merge_partials_device (keys and ids in two arrays, parts nq * k apart) and vdb_merge_packed_partials_device (one array of
@@ -1196,6 +1209,7 @@ int vdb_reset(vdb_handle hh) {
         group_release(h->lists);
         group_release(h->codes);
         h->lsh_rows = 0;                       // (the projection stays)
+        h->lsht_rows = 0;                      // (the hash tables stay)
         h->knng_degree = 0;                    // (the graph went with the codes group)
     });
 }
@@ -1401,6 +1415,16 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             for (int sh = 0; sh < kStatShards; ++sh) s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
         }
+        if (h->last.last_path == VDB_PATH_LSHT && h->lsh_ws.lsh_stat.p) {     // last hash-table LSH call: select fallbacks, candidates, brute-force queries
+            std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
+            VDB_HIP(hipDeviceSynchronize());
+            VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (int sh = 0; sh < kStatShards; ++sh) {
+                s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
+                s.last_candidates += (int64_t)c[(size_t)sh * kStatStride + 1];
+                s.last_rows_scanned += h->N * (int64_t)c[(size_t)sh * kStatStride + 2];
+            }
+        }
         if (h->last.last_path == VDB_PATH_KNNG && h->knng_ws.knng_stat.p) {   // rows scored / queries the step cap stopped, last k-NN graph search
             std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
             VDB_HIP(hipDeviceSynchronize());
@@ -1464,6 +1488,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 
 #include "pq.inc"
 #include "lsh.inc"
+#include "lsh_tables.inc"
 #include "knng.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

@@ -12,6 +12,7 @@ from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatInd
 from .ivf_pq import HipIVFPQIndexer, HipIVFPQSearch, IVFPQIndex, parse_ivfpq_key
 from .knng import HipKnnGraphIndexer, HipKnnGraphSearch, HipKnnGraphSearcher, KnnGraphIndex
 from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
+from .lsh_tables import HipLSHTableIndexer, HipLSHTables, HipLSHTableSearcher, make_tables
 from .pq import HipPQIndexer, HipPQSearch, HipPQSearcher, PQIndex, parse_pq_key
 from . import sharded
 from .sharded import HipShardedApproximateSearch, HipShardedExactSearch, shard_bounds
@@ -24,7 +25,8 @@ __all__ = [
     "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
     "HipIVFPQIndexer", "HipIVFPQSearch", "IVFPQIndex", "parse_ivfpq_key",
     "HipKnnGraphIndexer", "HipKnnGraphSearcher", "HipKnnGraphSearch", "KnnGraphIndex",
-    "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipPQIndexer", "HipPQSearcher", "HipPQSearch", "PQIndex",
+    "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipLSHTableIndexer", "HipLSHTableSearcher", "HipLSHTables",
+    "make_tables", "HipPQIndexer", "HipPQSearcher", "HipPQSearch", "PQIndex",
     "parse_pq_key", "HipShardedExactSearch",
     "HipShardedApproximateSearch", "shard_bounds", "sharded",
 ]

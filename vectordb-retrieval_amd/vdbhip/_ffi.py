@@ -18,7 +18,7 @@ import numpy as np
 
 VDB_OK, VDB_ERR_INVALID, VDB_ERR_STATE, VDB_ERR_HIP, VDB_ERR_NOMEM, VDB_ERR_UNSUPPORTED = range(6)
 METRIC_L2, METRIC_IP = 0, 1
-PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng"}
+PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables"}
 
 _LIB_NAME = "libvdbhip.so"
 _lib: Optional[ctypes.CDLL] = None
@@ -89,6 +89,13 @@ SIGNATURES = {
     "vdb_lsh_candidates_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_lsh_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "vdb_lsh_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_lsht_set_tables": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float]),
+    "vdb_lsht_get_tables": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, POINTER(c_float)]),
+    "vdb_lsht_get_keys": (c_int, [c_void_p, c_void_p]),
+    "vdb_lsht_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "vdb_lsht_candidates_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_lsht_search": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vdb_lsht_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_pq_train": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_uint64, c_int]),
     "vdb_pq_set_codebooks": (c_int, [c_void_p, c_int, c_void_p]),
     "vdb_pq_get_codebooks": (c_int, [c_void_p, POINTER(c_int), c_void_p]),

@@ -200,6 +200,70 @@ class FlatIndex(_Handle):
     def lsh_search_device(self, q_ptr: int, nq: int, k: int, ncand: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
         _ffi.check(self._lib.vdb_lsh_search_device(self._handle(), q_ptr, int(nq), int(k), int(ncand), d_ptr, i_ptr, stream or None))
 
+    # -- hash-table LSH (vdb_lsht_*): table keys, collision votes, exact re-rank -------------------------
+    def lsht_set_tables(self, projections: np.ndarray, offsets: Optional[np.ndarray] = None, bucket_width: float = 0.0) -> None:
+        """Install T tables of H projections, P (T, H, dim) float32.  `offsets` None: sign keys (mode 0); else E2 bucket keys
+        (mode 1) with offsets b (T, H) float32 and `bucket_width`.  Rows already indexed are keyed now, later adds key what
+        they append."""
+        p = _ffi.as_f32_c(projections)
+        if p.ndim != 3 or p.shape[2] != self.dim:
+            raise ValueError(f"expected (num_tables, hash_size, {self.dim}) projections, got {p.shape}")
+        b = None
+        if offsets is not None:
+            b = _ffi.as_f32_c(offsets)
+            if b.shape != p.shape[:2]:
+                raise ValueError(f"expected {p.shape[:2]} offsets, got {b.shape}")
+        _ffi.check(self._lib.vdb_lsht_set_tables(self._handle(), int(p.shape[0]), int(p.shape[1]), 0 if b is None else 1, _ffi.ptr(p),
+                                                 _ffi.ptr(b), float(bucket_width)), build_time=True)
+
+    def lsht_get_tables(self) -> Optional[dict]:
+        """None without tables, else {num_tables, hash_size, mode, projections, offsets (None in sign mode), bucket_width}."""
+        t, hs, mode, w = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_float(0.0)
+        refs = (ctypes.byref(t), ctypes.byref(hs), ctypes.byref(mode))
+        _ffi.check(self._lib.vdb_lsht_get_tables(self._handle(), *refs, None, None, ctypes.byref(w)))
+        if t.value == 0:
+            return None
+        p = np.empty((t.value, hs.value, self.dim), np.float32)
+        b = np.empty((t.value, hs.value), np.float32) if mode.value == 1 else None
+        _ffi.check(self._lib.vdb_lsht_get_tables(self._handle(), *refs, _ffi.ptr(p), _ffi.ptr(b), ctypes.byref(w)))
+        return {"num_tables": t.value, "hash_size": hs.value, "mode": mode.value, "projections": p, "offsets": b,
+                "bucket_width": float(w.value)}
+
+    def lsht_keys(self) -> np.ndarray:
+        """Table keys of the indexed rows, uint32 (ntotal, T * W): W = ceil(H / 32) words per table in sign mode, H in E2 mode."""
+        t, hs, mode = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _ffi.check(self._lib.vdb_lsht_get_tables(self._handle(), ctypes.byref(t), ctypes.byref(hs), ctypes.byref(mode), None, None, None))
+        words = t.value * (hs.value if mode.value == 1 else (hs.value + 31) // 32)
+        keys = np.empty((self.ntotal, words), np.uint32)
+        _ffi.check(self._lib.vdb_lsht_get_keys(self._handle(), _ffi.ptr(keys)))
+        return keys
+
+    def lsht_candidates(self, queries: np.ndarray, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Per query its colliding rows under (votes descending, first table, id), at most `ncand`: (votes int32 (nq, ncand),
+        ids int64 (nq, ncand)), padded with 0 / -1."""
+        q = self._lsh_queries(queries)
+        votes = np.empty((q.shape[0], int(ncand)), np.int32)
+        ids = np.empty((q.shape[0], int(ncand)), np.int64)
+        _ffi.check(self._lib.vdb_lsht_candidates(self._handle(), _ffi.ptr(q), q.shape[0], int(ncand), _ffi.ptr(votes), _ffi.ptr(ids)))
+        return votes, ids
+
+    def lsht_candidates_device(self, q_ptr: int, nq: int, ncand: int, votes_ptr: int, ids_ptr: int, stream: int = 0) -> None:
+        _ffi.check(self._lib.vdb_lsht_candidates_device(self._handle(), q_ptr, int(nq), int(ncand), votes_ptr, ids_ptr, stream or None))
+
+    def lsht_search(self, queries: np.ndarray, k: int, ncand: int, fallback: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-k among the `ncand` vote candidates of every query (flat conventions and padding); `fallback`: a query
+        without a colliding row gets the exact flat top-k instead."""
+        q = self._lsh_queries(queries)
+        D = np.empty((q.shape[0], int(k)), np.float32)
+        I = np.empty((q.shape[0], int(k)), np.int64)
+        _ffi.check(self._lib.vdb_lsht_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), int(ncand), int(bool(fallback)),
+                                             _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+    def lsht_search_device(self, q_ptr: int, nq: int, k: int, ncand: int, fallback: bool, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        _ffi.check(self._lib.vdb_lsht_search_device(self._handle(), q_ptr, int(nq), int(k), int(ncand), int(bool(fallback)), d_ptr,
+                                                    i_ptr, stream or None))
+
     def rerank_device(self, q_ptr: int, nq: int, cand_ptr: int, ncand: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
         _ffi.check(self._lib.vdb_rerank_device(self._handle(), q_ptr, int(nq), cand_ptr, int(ncand), int(k), d_ptr, i_ptr, stream or None))
 
