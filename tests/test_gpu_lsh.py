@@ -153,6 +153,28 @@ def test_candidates_bit_exact(vdb, n, d, nbits, nq, ncand):
     idx.close()
 
 
+@pytest.mark.parametrize("n", [1000, 33024])
+@pytest.mark.parametrize("nbits", [96, 512, 1024])
+def test_candidates_at_every_stored_width(vdb, n, nbits):
+    """The widths the cases above leave out: 96 bits are stored as 4 words (one of padding), 512 as 16, 1024 as 32.  N = 1000 takes
+    the exact histogram; N = 33 024 is just above the 32 768-row sample: the sampled bound and both scans.  The forced fallback
+    must give the same arrays."""
+    d, nq, ncand = 16, 5, 10
+    X = _corpus(n, d, seed=n + nbits)
+    Q = _corpus(nq, d, seed=n + nbits + 1)
+    R = vdb.make_projection(d, nbits, seed=4)
+    want = ref.encode(X, R)
+    idx = _index(vdb, X, R)
+    _check_candidates(idx, Q, R, want, ncand)
+    ham, ids = idx.lsh_candidates(Q, ncand)
+    idx.set_option("lsh_force_fallback", 1)
+    st = _check_candidates(idx, Q, R, want, ncand)
+    assert st["last_fallback_queries"] == nq, st
+    ham_f, ids_f = idx.lsh_candidates(Q, ncand)
+    assert np.array_equal(ham, ham_f) and np.array_equal(ids, ids_f)
+    idx.close()
+
+
 @pytest.mark.parametrize("ncand", [10, 1280, 6000])
 def test_candidates_cut_inside_a_duplicated_code(vdb, ncand):
     """One row repeated 5000 times: for the query equal to it the cut falls inside one code (5000 rows at distance 0), and with

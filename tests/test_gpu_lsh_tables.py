@@ -232,6 +232,69 @@ def test_sampled_bound_routes_complete_rescan_flagged(vdb, nq):
     idx.close()
 
 
+def _wide_key_corpus(n, T, H):
+    """n x 16 under T <= 16 E2 tables of H projections, unit bucket width, the keys set by hand: every projection of table t reads
+    coordinate t, with offset 0 but for the last one of the table, whose offset is 0.6.  So the values 0.5 and 0.15 share every
+    code of a table but the last word, and 9.5 and 5.5 share none with them or each other.  Rows are copies of prototypes:
+      P1   7 rows   0.5 everywhere                         P3   40 rows   9.5, table T - 1 at 0.5
+      P2  12 rows   0.5, table 0 at 0.15                   P4    5 rows   0.15 everywhere            the rest: 9.5 everywhere
+    and the five queries are 0.5 everywhere (P1 in T tables, P2 in T - 1, P3 in one: 59 rows), 0.15 everywhere (P4 in T, P2 in
+    one: 17 rows), 5.5 everywhere (no row), 9.5 everywhere (the rest in T, P3 in T - 1: nearly every row), and 0.5 with table 0
+    at 0.15 (P2 in T, P1 in T - 1, P3 and P4 in one: 64 rows)."""
+    d = 16
+    rng = np.random.default_rng(41 + H)
+    X = rng.standard_normal((n, d)).astype(F32)
+    X[:, :T] = 9.5
+    perm = rng.permutation(n)
+    X[perm[0:7], :T] = 0.5
+    X[perm[7:19], :T] = 0.5
+    X[perm[7:19], 0] = 0.15
+    X[perm[19:59], T - 1] = 0.5
+    X[perm[59:64], :T] = 0.15
+    Q = rng.standard_normal((5, d)).astype(F32)
+    Q[0, :T], Q[1, :T], Q[2, :T], Q[3, :T], Q[4, :T] = 0.5, 0.15, 5.5, 9.5, 0.5
+    Q[4, 0] = 0.15
+    p = np.zeros((T, H, d), F32)
+    for t in range(T):
+        p[t, :, t] = 1
+    b = np.zeros((T, H), F32)
+    b[:, H - 1] = 0.6
+    return X, Q, p, b
+
+
+def _wide_key_conditions(X, Q, p, b, ncands):
+    """what the corpus is built for, on the restatement alone: a query without a colliding row, two or more distinct vote counts
+    for every other one, an ncand below and an ncand above the colliding rows of some query"""
+    T = p.shape[0]
+    votes, _, count = ref.candidates(ref.keys(Q, p, b, 1.0), ref.keys(X, p, b, 1.0), T, len(X), 0)
+    assert count.tolist() == [59, 17, 0, len(X) - 24, 64]
+    for q in np.flatnonzero(count):
+        assert len(set(votes[q, :count[q]].tolist())) >= 2, (q, votes[q, :count[q]])
+    assert (count > min(ncands)).any() and (count[count > 0] < max(ncands)).any()
+
+
+@pytest.mark.parametrize("n", [1000, 33024])
+@pytest.mark.parametrize("T,H", [(12, 5), (10, 7), (8, 9), (9, 13)])
+def test_candidates_and_search_at_the_wide_key_widths(vdb, n, T, H):
+    """E2 keys of 5, 7, 9 and 13 words per table are stored as 6, 8, 12 and 16: the widths the cases above leave out (T = 9 at
+    H = 13 is the widest row the scan is compiled for).  N = 1000 takes the exact histogram, N = 33 024 the sampled bound and both
+    scans; with and without the brute-force fallback, and once through the exact fallback of the select."""
+    X, Q, p, b = _wide_key_corpus(n, T, H)
+    _wide_key_conditions(X, Q, p, b, (10, 100))
+    idx = _index(vdb, X, p, b, 1.0)
+    assert idx.lsht_keys().shape == (n, T * H)                   # E2: one word per projection
+    _check(idx, X, Q, p, b, 1.0, ncand=10, k=5)
+    st, count = _check(idx, X, Q, p, b, 1.0, ncand=100, k=5, fallback=True)
+    assert st["last_rows_scanned"] == n                           # the one query without a colliding row
+    votes, ids = idx.lsht_candidates(Q, 100)
+    idx.set_option("lsh_force_fallback", 1)
+    st, _ = _check(idx, X, Q, p, b, 1.0, ncand=100, k=5, fallback=True)
+    assert st["last_fallback_queries"] == len(Q)
+    votes2, ids2 = idx.lsht_candidates(Q, 100)
+    assert np.array_equal(votes, votes2) and np.array_equal(ids, ids2)
+    idx.close()
+
+
 def test_coarse_tables_most_rows_collide(vdb):
     """40 000 x 16 under the published shape (L2 T12 / H4, a wide bucket): most rows collide with every query and the cap cuts
     deep inside them; candidates and search equal the restatement whichever route a query takes, forced fallback included."""

@@ -1,4 +1,4 @@
-// lsh.hpp -- sign-LSH codes: encode, Hamming scan, top-c select (gfx950 only).  Host side: lsh.inc.
+// lsh.hpp -- sign-LSH codes: encode, and the Hamming sample and scan of the counting select (gfx950 only).  Host side: lsh.inc.
 //
 // Contract (include/vdbhip.h): bit j of a vector x is  s_j >= 0  with  s_j = sum_d (double)x[d] * (double)R[j][d], accumulated
 // from 0.0 with d ascending and one rounding per step; the candidates of a query are the min(ncand, ntotal) rows smallest
@@ -7,33 +7,18 @@
 // Codes: `wp` uint32 words per row, wp = nbits / 32 rounded up to a power of two, the words past nbits / 32 zero in rows
 // and queries alike (they add nothing to a distance), so the scan is compiled for wp in {1, 2, 4, 8, 16, 32} only.
 //
-// Select: distances are integers in [0, nbits], so the c-th smallest is found by counting.  Per query
-//   1. lsh_sample_kernel   histogram of a row sample (128 runs of 256 rows) -> t_hi, a generous upper bound of the cut distance
-//                          (the whole corpus when it is no larger than the sample: the histogram is exact, step 2 is skipped)
-//   2. lsh_scan_kernel<0>  every (query, row) pair: xor + popcount; the rare pairs with d <= t_hi count into hist[q][d] and are
-//                          appended to the query's list as (d << 32 | row), as far as the list has room
-//   3. lsh_threshold_kernel  t = the smallest distance at which the cumulative count reaches c; m = that count.  Three routes:
-//                          complete -- every counted pair fitted the list, which therefore holds the m rows up to t;
-//                          rescan   -- the list overflowed (or step 2 was skipped) but m fits: the list restarts empty;
-//                          flagged  -- t_hi was too small (fewer than c rows counted) or m exceeds the list (ties at t)
-//   4. lsh_scan_kernel<1>  the same scan for the `rescan` queries only, appending the m pairs with d <= t (workgroups whose
-//                          256 queries are all complete or flagged return at once)
-//   5. lsh_select_kernel   sorts the entries with d <= t (bitonic; compacted into LDS up to 4096 of them, else in place) and
-//                          emits the first c; a flagged query first takes the exact fallback: full histogram of its distances
-//                          -> t, then the rows below t and the lowest-id rows at t (ordered compaction): exactly c entries.
+// Select: lsh_select.hpp with the Hamming distance as the score: hb = nbits + 1 bins, every pair has a score, and a query
+// wants min(ncand, n) candidates, emitted as (distance, id).  This file has the sample and the scan, which keep the code
+// words of two rows per thread in registers.
 #pragma once
 #include "common.hpp"
+#include "lsh_select.hpp"
 
 namespace vdb {
 
-constexpr int kLshMaxBits = 1024;
-constexpr int kLshMaxCand = 65536;
 constexpr int kLshEncRows = 8;         // rows per wave of the encode kernel
 constexpr int kLshQTile = 256;         // queries per workgroup of the scan (their codes sit in LDS)
 constexpr int kLshRowTile = 512;       // rows per workgroup of the scan: two per thread, in registers
-constexpr int kLshSampleMax = 32768;   // rows of the threshold sample (a multiple of 256)
-constexpr int kLshSampleQ = 4;         // queries per workgroup of the sample kernel
-constexpr int kLshSortLds = 4096;      // list entries sorted in LDS
 
 // ---- encode ------------------------------------------------------------------------------------------------------------
 // One wave = kLshEncRows rows x 64 bits: lane l owns bit 64 * chunk + l and reads its projection row from the transposed
@@ -72,36 +57,12 @@ __global__ __launch_bounds__(256) void lsh_encode_kernel(const float *__restrict
     }
 }
 
-// ---- select ------------------------------------------------------------------------------------------------------------
-struct LshArgs {
-    const uint32_t *codes;       // [n][wp]
-    const uint32_t *qcodes;      // [nq][wp]
-    int64_t n, nq;
-    int wp, nbits, hb;           // hb = nbits + 1 histogram bins per query
-    int c, cap, ncand;           // c = min(ncand, n); cap = list entries per query (a power of two >= c)
-    int64_t sample_n, sample_stride;
-    int force_fallback;
-    int64_t id_base;
-    int *hist;                   // [nq][hb]
-    int *thi, *tq, *cnt, *flag, *tsel, *msel;  // [nq] each: upper bound, cut for MODE 1 (-1: none), list fill, fallback flag, cut, rows up to it
-    int scanned0;                // lsh_scan_kernel<0> ran (the corpus is larger than the sample)
-    unsigned long long *list;    // [nq][cap]
-    unsigned long long *nflagged;  // flagged queries since the call began
-    int32_t *out_ham;            // [nq][ncand]
-    int64_t *out_ids;
-};
-
-__device__ __forceinline__ int lsh_ham(const uint32_t *__restrict__ a, const uint32_t *b, int wp) {
-    int d = 0;
-    for (int w = 0; w < wp; ++w) d += __popc(a[w] ^ b[w]);
-    return d;
-}
-
-// One workgroup per kLshSampleQ queries: every thread keeps a sample row in registers per step and scores it against the
+// ---- sample and scan of the select (lsh_select.hpp) -------------------------------------------------------------------
+// Step 1 of lsh_select.hpp.  One workgroup per kLshSampleQ queries: every thread keeps a sample row in registers per step and scores it against the
 // workgroup's queries (LDS).  The sample is sample_n / 256 runs of 256 consecutive rows, `sample_stride` rows apart (dense
 // loads; the same 1 MiB of codes serves every query), or the whole corpus (sample_stride = 256, exact histogram).
 template <int WP>
-__global__ __launch_bounds__(256) void lsh_sample_kernel(LshArgs a) {
+__global__ __launch_bounds__(256) void lsh_sample_kernel(LshSelArgs a) {
     __shared__ int sh[kLshSampleQ][kLshMaxBits + 1];
     __shared__ uint32_t qc[kLshSampleQ][WP];
     const int64_t q0 = (int64_t)blockIdx.x * kLshSampleQ;
@@ -130,16 +91,16 @@ __global__ __launch_bounds__(256) void lsh_sample_kernel(LshArgs a) {
         for (int i = tid; i < a.hb; i += 256) hq[i] = exact ? sh[q][i] : 0;
     }
     if (tid < nqt) {
-        int t = a.nbits;
+        int t = a.hb - 1;
         if (!exact) {
             // the expected sample count lambda of the c nearest rows + 5 sqrt(lambda) + 4, never fewer than 16 sample rows: the
             // true cut lies above t only if the sample overstates the tail by five standard deviations of its Poisson count
             // (such a query takes the exact fallback)
-            const float lambda = (float)a.c * (float)a.sample_n / (float)a.n;
+            const float lambda = (float)a.want * (float)a.sample_n / (float)a.n;
             const long long want = (long long)ceilf(lambda + 5.f * sqrtf(lambda) + 4.f);
             const long long target = want > 16 ? want : 16;
             long long cum = 0;
-            for (int d = 0; d <= a.nbits; ++d) {
+            for (int d = 0; d < a.hb; ++d) {
                 cum += sh[tid][d];
                 if (cum >= target) { t = d; break; }
             }
@@ -152,7 +113,7 @@ __global__ __launch_bounds__(256) void lsh_sample_kernel(LshArgs a) {
 // MODE 0: count the pairs with d <= thi[q] into hist AND append them to the query's list (what fits).  MODE 1: append the pairs
 // with d <= tq[q]; a workgroup none of whose queries asks for it (tq < 0: their list was complete after MODE 0) returns at once.
 template <int MODE, int WP>
-__global__ __launch_bounds__(256) void lsh_scan_kernel(LshArgs a) {
+__global__ __launch_bounds__(256) void lsh_scan_kernel(LshSelArgs a) {
     __shared__ __align__(16) uint32_t qc[kLshQTile * WP];
     __shared__ int thr[kLshQTile];
     __shared__ int sel[kLshQTile], nsel;          // MODE 1: the queries of the tile that ask for the rescan
@@ -205,125 +166,6 @@ __global__ __launch_bounds__(256) void lsh_scan_kernel(LshArgs a) {
                     if (idx < a.cap) a.list[(size_t)gq * a.cap + idx] = ((unsigned long long)db << 32) | (unsigned long long)rb;
                 }
             }
-        }
-    }
-}
-
-// one thread per query: the cut t, the rows m up to it, and which route the query takes
-__global__ __launch_bounds__(256) void lsh_threshold_kernel(LshArgs a) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= a.nq) return;
-    const int *hq = a.hist + (size_t)q * a.hb;
-    const int thi = a.thi[q];
-    long long cum = 0, m = 0;
-    int t = -1;
-    for (int d = 0; d <= thi; ++d) {
-        cum += hq[d];
-        if (t < 0 && cum >= a.c) { t = d; m = cum; }
-    }
-    const bool flagged = a.force_fallback || t < 0 || m > a.cap;
-    // MODE 0 appended every pair it counted: if they all fitted, the list already holds the m rows up to t (and a few beyond)
-    const bool complete = !flagged && a.scanned0 && cum <= a.cap;
-    a.flag[q] = flagged ? 1 : 0;
-    a.tq[q] = (flagged || complete) ? -1 : t;
-    a.tsel[q] = t;
-    a.msel[q] = (int)m;
-    if (!complete) a.cnt[q] = 0;
-    if (flagged) stat_add(a.nflagged, q, 0, 1ull);
-}
-
-// one workgroup per query: (flagged: exact fallback ->) sort the list -> emit
-__global__ __launch_bounds__(256) void lsh_select_kernel(LshArgs a) {
-    __shared__ unsigned long long sbuf[kLshSortLds];
-    __shared__ int sh[kLshMaxBits + 1];
-    __shared__ uint32_t qc[32];
-    __shared__ int s_t, s_below, s_fill, wtot[4];
-    const int64_t q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long *lq = a.list + (size_t)q * a.cap;
-    int n = a.cnt[q] < a.cap ? a.cnt[q] : a.cap;      // list entries: the m rows up to the cut, and after MODE 0 a few beyond it
-    int t_cut = a.tsel[q], m = a.msel[q];
-    if (tid == 0) s_fill = 0;
-    if (a.flag[q]) {       // (uniform over the workgroup)
-        for (int i = tid; i < a.hb; i += 256) sh[i] = 0;
-        if (tid < a.wp) qc[tid] = a.qcodes[(size_t)q * a.wp + tid];
-        __syncthreads();
-        for (int64_t r = tid; r < a.n; r += 256) atomicAdd(&sh[lsh_ham(a.codes + (size_t)r * a.wp, qc, a.wp)], 1);
-        __syncthreads();
-        if (tid == 0) {
-            long long cum = 0;
-            int t = a.nbits;
-            for (int d = 0; d <= a.nbits; ++d) {
-                if (cum + sh[d] >= a.c) { t = d; break; }
-                cum += sh[d];
-            }
-            s_t = t;
-            s_below = (int)cum;
-        }
-        __syncthreads();
-        const int t = s_t, below = s_below, need = a.c - below;
-        int taken = 0;          // rows at distance t seen so far (uniform)
-        for (int64_t base = 0; base < a.n; base += 256) {
-            const int64_t r = base + tid;
-            const int d = r < a.n ? lsh_ham(a.codes + (size_t)r * a.wp, qc, a.wp) : 0x7fffffff;
-            if (d < t) lq[atomicAdd(&s_fill, 1)] = ((unsigned long long)d << 32) | (unsigned long long)r;
-            const bool tie = d == t;
-            const unsigned long long mask = __ballot(tie);
-            if (lane == 0) wtot[wave] = __popcll(mask);
-            __syncthreads();
-            int pos = taken + __popcll(mask & ((1ull << lane) - 1ull));
-            for (int w = 0; w < wave; ++w) pos += wtot[w];
-            if (tie && pos < need) lq[below + pos] = ((unsigned long long)d << 32) | (unsigned long long)r;
-            taken += wtot[0] + wtot[1] + wtot[2] + wtot[3];
-            __syncthreads();
-        }
-        n = m = a.c;
-        t_cut = 0x7fffffff;
-        __syncthreads();
-        if (tid == 0) s_fill = 0;
-    }
-    __syncthreads();
-    // the m entries with d <= t_cut: compacted into LDS when they fit, else sorted in place with the others blanked
-    int P = 1;
-    unsigned long long *buf = lq;
-    if (m <= kLshSortLds) {
-        buf = sbuf;
-        while (P < m) P <<= 1;
-        for (int i = tid; i < n; i += 256) {
-            const unsigned long long key = lq[i];
-            if ((int)(key >> 32) <= t_cut) buf[atomicAdd(&s_fill, 1)] = key;
-        }
-        for (int i = m + tid; i < P; i += 256) buf[i] = ~0ull;
-    } else {
-        while (P < n) P <<= 1;
-        for (int i = tid; i < P; i += 256)
-            if (i >= n || (int)(lq[i] >> 32) > t_cut) buf[i] = ~0ull;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long x = buf[i], y = buf[ixj];
-                    if ((x > y) == ((i & k) == 0)) {
-                        buf[i] = y;
-                        buf[ixj] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    int32_t *oh = a.out_ham + (size_t)q * a.ncand;
-    int64_t *oi = a.out_ids + (size_t)q * a.ncand;
-    for (int i = tid; i < a.ncand; i += 256) {
-        if (i < a.c) {
-            const unsigned long long key = buf[i];
-            oh[i] = (int32_t)(key >> 32);
-            oi[i] = a.id_base + (int64_t)(key & 0xffffffffull);
-        } else {
-            oh[i] = 0x7fffffff;
-            oi[i] = -1;
         }
     }
 }

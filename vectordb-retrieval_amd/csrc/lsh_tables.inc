@@ -75,126 +75,19 @@ void lsht_require_ready(vdb_index_s *h, const char *what, bool search_call) {
 }
 
 template <int MODE>
-void launch_lsht_scan(const LshtArgs &a, hipStream_t st) {
-    const dim3 grid((unsigned)((a.n + kLshtRowTile - 1) / kLshtRowTile), (unsigned)((a.nq + a.qtile - 1) / a.qtile));
+void launch_lsht_scan(const LshSelArgs &a, dim3 grid, hipStream_t st) {
     LSHT_DISPATCH(a.wp, (lsht_scan_kernel<MODE, WP, TMAX><<<grid, dim3(256), 0, st>>>(a)));
-    VDB_HIP(hipGetLastError());
 }
 
-void launch_lsht_sample(const LshtArgs &a, hipStream_t st) {
-    const dim3 grid((unsigned)((a.nq + kLshSampleQ - 1) / kLshSampleQ));
+void launch_lsht_sample(const LshSelArgs &a, dim3 grid, hipStream_t st) {
     LSHT_DISPATCH(a.wp, (lsht_sample_kernel<WP, TMAX><<<grid, dim3(256), 0, st>>>(a)));
-    VDB_HIP(hipGetLastError());
 }
 
-// candidates of nq queries (device) -> votes / ids (device, (nq, ncand)); tslot / mark0: timing (events 0 and 1 around the scans);
-// empty: [0] the count, [1 ..] the numbers of the queries without a colliding row (null: not listed)
-void lsht_candidates_core(vdb_index_s *h, const float *dq, int64_t nq, int ncand, int32_t *votes, int64_t *ids, hipStream_t st, long tslot,
-                          bool mark0, int32_t *empty) {
-    const int kw = h->lsht_kw, hb = h->lsht_T * h->lsht_T;
-    const int c = (int)std::min<int64_t>(ncand, h->N);
-    int cap = 1;
-    while (cap < std::min<int64_t>(4 * (int64_t)c + 1024, h->N)) cap <<= 1;
-    const int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 1 << 20), (int64_t)(kLshListBudget / ((size_t)cap * 8))));
-    h->lsh_ws.lsh_qcodes.reserve((size_t)nq * kw * sizeof(uint32_t));
-    h->lsh_ws.lsh_hist.reserve((size_t)nqc * hb * sizeof(int));
-    h->lsh_ws.lsh_small.reserve((size_t)nqc * 7 * sizeof(int));
-    h->lsh_ws.lsh_list.reserve((size_t)nqc * cap * sizeof(unsigned long long));
-    lsht_key(h, dq, nq, h->dim, h->lsh_ws.lsh_qcodes.as<uint32_t>(), st);
-    LshtArgs a{};
-    a.keys = h->codes.lsht_keys.as<uint32_t>();
-    a.n = h->N;
-    a.T = h->lsht_T;
-    a.wp = h->lsht_wp;
-    a.kw = kw;
-    a.hb = hb;
-    a.ncand = ncand;
-    a.cap = cap;
-    a.qtile = std::min(256, kLshtLdsWords / kw);
-    a.sample_n = std::min<int64_t>(h->N, kLshSampleMax);
-    a.sample_stride = a.sample_n == h->N ? 256 : h->N / (kLshSampleMax / 256);
-    a.force_fallback = h->opt.lsh_force_fallback;
-    a.id_base = h->id_base;
-    a.hist = h->lsh_ws.lsh_hist.as<int>();
-    a.thi = h->lsh_ws.lsh_small.as<int>();
-    a.tq = a.thi + nqc;
-    a.cnt = a.tq + nqc;
-    a.flag = a.cnt + nqc;
-    a.tsel = a.flag + nqc;
-    a.msel = a.tsel + nqc;
-    a.csel = a.msel + nqc;
-    a.scanned0 = a.sample_n != a.n;
-    a.list = h->lsh_ws.lsh_list.as<unsigned long long>();
-    a.stat = h->lsh_ws.lsh_stat.as<unsigned long long>();
-    a.empty_count = empty;
-    a.empty_list = empty ? empty + 1 : nullptr;
-    for (int64_t q0 = 0; q0 < nq; q0 += nqc) {
-        a.nq = std::min<int64_t>(nqc, nq - q0);
-        a.q_base = q0;
-        a.qkeys = h->lsh_ws.lsh_qcodes.as<uint32_t>() + (size_t)q0 * kw;
-        a.out_votes = votes + (size_t)q0 * ncand;
-        a.out_ids = ids + (size_t)q0 * ncand;
-        launch_lsht_sample(a, st);
-        if (mark0 && q0 == 0) timing_mark(h, tslot, 0, st);
-        if (a.scanned0) launch_lsht_scan<0>(a, st);
-        lsht_threshold_kernel<<<dim3((unsigned)((a.nq + 255) / 256)), dim3(256), 0, st>>>(a);
-        VDB_HIP(hipGetLastError());
-        launch_lsht_scan<1>(a, st);
-        timing_mark(h, tslot, 1, st);
-        lsht_select_kernel<<<dim3((unsigned)a.nq), dim3(256), 0, st>>>(a);
-        VDB_HIP(hipGetLastError());
-    }
-}
-
-void lsht_check_args(const void *q, int64_t nq, int ncand, const void *o1, const void *o2) {
-    if (ncand < 1 || ncand > kLshMaxCand) throw Error(VDB_ERR_INVALID, "ncand must be in [1, 65536]");
-    if (nq < 0) throw Error(VDB_ERR_INVALID, "negative query count");
-    if (nq > 0 && (!q || !o1 || !o2)) throw Error(VDB_ERR_INVALID, "null pointer");
-}
-
-void lsht_begin_call(vdb_index_s *h, int64_t nq, hipStream_t st) {
-    lsh_begin_call(h, nq, st);
-    h->last.last_path = VDB_PATH_LSHT;
-}
-
-void lsht_candidates_impl(vdb_index_s *h, const float *dq, int64_t nq, int ncand, int32_t *votes, int64_t *ids, hipStream_t st) {
-    lsht_begin_call(h, nq, st);
-    const long tslot = timing_begin(h, st);
-    lsht_candidates_core(h, dq, nq, ncand, votes, ids, st, tslot, true, nullptr);
-    timing_mark(h, tslot, 2, st);
-}
-
-// query -> keys -> vote top-ncand -> exact top-k (rerank_kernel), in query chunks that bound the candidate buffers; fallback: the
-// queries of a chunk without a colliding row then take the exhaustive exact scan, from the device-side list the select wrote
-void lsht_search_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, int ncand, int fallback, float *D, int64_t *I, hipStream_t st) {
-    if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
-    const int64_t nqs = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(kLshCandBudget / ((size_t)ncand * 12))));
-    h->lsh_ws.lsh_cand_i.reserve((size_t)nqs * ncand * sizeof(int64_t));
-    h->lsh_ws.lsh_cand_h.reserve((size_t)nqs * ncand * sizeof(int32_t));
-    if (fallback) h->lsh_ws.lsht_empty.reserve((size_t)(nqs + 1) * sizeof(int32_t));
-    lsht_begin_call(h, nq, st);
-    const long tslot = timing_begin(h, st);
-    for (int64_t q0 = 0; q0 < nq; q0 += nqs) {
-        const int64_t n = std::min<int64_t>(nqs, nq - q0);
-        const float *qs = dq + (size_t)q0 * h->dim;
-        int32_t *empty = fallback ? h->lsh_ws.lsht_empty.as<int32_t>() : nullptr;
-        if (empty) VDB_HIP(hipMemsetAsync(empty, 0, sizeof(int32_t), st));
-        lsht_candidates_core(h, qs, n, ncand, h->lsh_ws.lsh_cand_h.as<int32_t>(), h->lsh_ws.lsh_cand_i.as<int64_t>(), st, tslot, q0 == 0, empty);
-        rerank_device_impl(h, qs, n, h->lsh_ws.lsh_cand_i.as<int64_t>(), ncand, k, D + (size_t)q0 * k, I + (size_t)q0 * k, st);
-        if (empty) {
-            // (rerank_device_impl left the chunk's queries padded to D4 in ws.qpad when D4 != dim)
-            RefineFullArgs fa{};
-            fa.c = flat_rows(h, h->D4 != h->dim ? h->ws.qpad.as<float>() : qs, k);
-            fa.qlist = empty + 1;
-            fa.count_ptr = empty;
-            fa.S = 1;
-            fa.rows_per_split = h->N;
-            fa.D = D + (size_t)q0 * k;
-            fa.I = I + (size_t)q0 * k;
-            launch_refine_full(fa, n, st);
-        }
-    }
-    timing_mark(h, tslot, 2, st);
+// the select of lsh.inc over the classes of the table keys
+LshKind lsht_kind(vdb_index_s *h) {
+    return {VDB_PATH_LSHT, h->codes.lsht_keys.as<uint32_t>(), h->lsht_kw, h->lsht_T, h->lsht_wp, h->lsht_T * h->lsht_T,
+            std::min(256, kLshtLdsWords / h->lsht_kw), false,
+            lsht_key, launch_lsht_sample, launch_lsht_scan<0>, launch_lsht_scan<1>, kLshtRowTile};
 }
 
 }  // namespace
@@ -285,10 +178,10 @@ int vdb_lsht_candidates_device(vdb_handle hh, const float *q_dev, int64_t nq, in
         auto *h = check(hh);
         admit(h, "vdb_lsht_candidates_device", kLshtCalls);
         lsht_require_ready(h, "vdb_lsht_candidates_device", true);
-        lsht_check_args(q_dev, nq, ncand, votes_dev, ids_dev);
+        lsh_check_args(q_dev, nq, ncand, votes_dev, ids_dev);
         if (nq == 0) return;
         set_device(h->device);
-        lsht_candidates_impl(h, q_dev, nq, ncand, votes_dev, ids_dev, as_stream(stream));
+        lsh_candidates_impl(h, lsht_kind(h), q_dev, nq, ncand, votes_dev, ids_dev, as_stream(stream));
     });
 }
 
@@ -297,19 +190,10 @@ int vdb_lsht_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncan
         auto *h = check(hh);
         admit(h, "vdb_lsht_candidates", kLshtCalls);
         lsht_require_ready(h, "vdb_lsht_candidates", true);
-        lsht_check_args(q_host, nq, ncand, votes, ids);
+        lsh_check_args(q_host, nq, ncand, votes, ids);
         if (nq == 0) return;
         set_device(h->device);
-        DevBuf dv, di;
-        h->ws.stage_q.reserve((size_t)nq * h->dim * sizeof(float));
-        dv.reserve((size_t)nq * ncand * sizeof(int32_t));
-        di.reserve((size_t)nq * ncand * sizeof(int64_t));
-        hipStream_t st = nullptr;
-        VDB_HIP(hipMemcpyAsync(h->ws.stage_q.p, q_host, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, st));
-        lsht_candidates_impl(h, h->ws.stage_q.as<float>(), nq, ncand, dv.as<int32_t>(), di.as<int64_t>(), st);
-        VDB_HIP(hipMemcpyAsync(votes, dv.p, (size_t)nq * ncand * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipMemcpyAsync(ids, di.p, (size_t)nq * ncand * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        VDB_HIP(hipStreamSynchronize(st));
+        lsh_candidates_staged(h, lsht_kind(h), q_host, nq, ncand, votes, ids);
     });
 }
 
@@ -319,11 +203,11 @@ int vdb_lsht_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k,
         auto *h = check(hh);
         admit(h, "vdb_lsht_search_device", kLshtCalls);
         lsht_require_ready(h, "vdb_lsht_search_device", true);
-        lsht_check_args(q_dev, nq, ncand, D_dev, I_dev);
+        lsh_check_args(q_dev, nq, ncand, D_dev, I_dev);
         if (fallback != 0 && fallback != 1) throw Error(VDB_ERR_INVALID, "fallback must be 0 or 1");
         if (nq == 0) return;
         set_device(h->device);
-        lsht_search_impl(h, q_dev, nq, k, ncand, fallback, D_dev, I_dev, as_stream(stream));
+        lsh_search_impl(h, lsht_kind(h), q_dev, nq, k, ncand, fallback, D_dev, I_dev, as_stream(stream));
     });
 }
 
@@ -332,13 +216,13 @@ int vdb_lsht_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int n
         auto *h = check(hh);
         admit(h, "vdb_lsht_search", kLshtCalls);
         lsht_require_ready(h, "vdb_lsht_search", true);
-        lsht_check_args(q_host, nq, ncand, D, I);
+        lsh_check_args(q_host, nq, ncand, D, I);
         if (fallback != 0 && fallback != 1) throw Error(VDB_ERR_INVALID, "fallback must be 0 or 1");
         if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
         if (nq == 0) return;
         set_device(h->device);
         run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
-            lsht_search_impl(h, dq, nq, k, ncand, fallback, dD, dI, st);
+            lsh_search_impl(h, lsht_kind(h), dq, nq, k, ncand, fallback, dD, dI, st);
         });
     });
 }

@@ -1409,20 +1409,16 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_candidates = (int64_t)c[0];
             s.last_rescan_bins = (int64_t)c[1];
         }
-        if (h->last.last_path == VDB_PATH_LSH && h->lsh_ws.lsh_stat.p) {      // queries of the last LSH call that took the exact fallback
-            std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
-            VDB_HIP(hipDeviceSynchronize());
-            VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            for (int sh = 0; sh < kStatShards; ++sh) s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
-        }
-        if (h->last.last_path == VDB_PATH_LSHT && h->lsh_ws.lsh_stat.p) {     // last hash-table LSH call: select fallbacks, candidates, brute-force queries
+        // last LSH call: queries that took the exact fallback of the select; hash tables also report candidates and brute-force queries
+        if ((h->last.last_path == VDB_PATH_LSH || h->last.last_path == VDB_PATH_LSHT) && h->lsh_ws.lsh_stat.p) {
+            const bool tables = h->last.last_path == VDB_PATH_LSHT;
             std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
             VDB_HIP(hipDeviceSynchronize());
             VDB_HIP(hipMemcpy(c.data(), h->lsh_ws.lsh_stat.p, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
             for (int sh = 0; sh < kStatShards; ++sh) {
                 s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
-                s.last_candidates += (int64_t)c[(size_t)sh * kStatStride + 1];
-                s.last_rows_scanned += h->N * (int64_t)c[(size_t)sh * kStatStride + 2];
+                if (tables) s.last_candidates += (int64_t)c[(size_t)sh * kStatStride + 1];
+                if (tables) s.last_rows_scanned += h->N * (int64_t)c[(size_t)sh * kStatStride + 2];
             }
         }
         if (h->last.last_path == VDB_PATH_KNNG && h->knng_ws.knng_stat.p) {   // rows scored / queries the step cap stopped, last k-NN graph search
