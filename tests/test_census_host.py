@@ -148,3 +148,118 @@ def test_case_reference_serves_both_metrics(oracle, kind):
     assert census.i8_batch_form(3, 24, 700, True) == (512, 8, 8, 0) and census.i8_batch_form(3, 53, 5120, True) == (1024, 8, 8, 0)
     assert census.i8_batch_form(5, 53, 5120, False) == (512, 16, 16, 0) and census.i8_batch_form(6, 53, 5120, False) == (1024, 8, 8, 1)
     assert census.i8_batch_form(6, 53, 5120, False, 4) == (1024, 8, 8, 0) and census.i8_batch_form(4, 24, 700, False) == (512, 4, 8, 0)
+
+
+# ---- the coded census corpora (tests/census_coded.py) -----------------------------------------------------------------------------
+from tests import census_coded as cc  # noqa: E402
+from tests import pq_restatement  # noqa: E402
+
+HOST_N = 4300                      # three 2048-row blocks: with `rot` 0 and 3 the masks 4, 8, 64 and 128, 256, 512 are dealt
+
+
+def _coded_invariants(construction, kind, d, M, cb, codes, xh, p, pin0=False):
+    n = len(xh)
+    dsub = d // M
+    assert cb.shape == (M, 256, dsub) and cb.dtype == np.float32 and codes.shape == (n, M) and codes.dtype == np.uint8
+    np.testing.assert_array_equal(pq_restatement.reconstruct(codes, cb), xh)
+    assert len(np.unique(xh, axis=0)) == n
+    for m in range(M):
+        used = np.unique(codes[:, m])
+        assert used[0] == 0 and used[-1] == 255 and (used[:-1] >= 128).any(), (m, used)
+        if construction == "entries":
+            assert len(used) == 256
+            assert len(np.unique(cb[m], axis=0)) == 256
+        elif not (pin0 and m == 0):                 # the codes in use sit elsewhere in every sub-space; the decoys are far from S
+            assert len(used) == M - pin0
+            if m > pin0:
+                assert not np.array_equal(used, np.unique(codes[:, m - 1]))
+            far = np.abs(cb[m][np.setdiff1d(np.arange(256), used), 0]).min() - np.abs(cb[m][used, 0]).max()
+            assert far >= (40 if kind == "int" else 8)
+    n2 = (xh.astype(np.float64) ** 2).sum(axis=1)
+    if kind == "int":
+        assert census.is_integer_kind(xh) and len(set(n2.tolist())) == 1
+        assert np.array_equal(xh.astype(np.float16).astype(np.float32), xh)
+    else:
+        assert not census.is_integer_kind(xh) and np.ptp(n2) <= 1e-6 * n2.max()
+
+
+@pytest.mark.parametrize("rot", [0, 3])
+@pytest.mark.parametrize("d,M,construction,kind", sorted({s[:4] for s in cc.PQ_SHAPES}))
+def test_coded_corpora_are_census_corpora(d, M, construction, kind, rot):
+    """Every (D, M, construction, kind) of the flat PQ census at 4300 rows: decoded rows pairwise distinct, equal norms, every row its
+    own first and its planted twin its second neighbour under both metrics, codes 0, 255 and >= 128 in use in every sub-space, x^
+    equal to the restated reconstruction."""
+    p = cc.flat_partner(HOST_N, rot)
+    cb, codes, xh, p = cc.build(construction, kind, d, M, p, seed=1)
+    _coded_invariants(construction, kind, d, M, cb, codes, xh, p)
+    has = p >= 0
+    assert has.sum() > HOST_N - 1100
+    for metric in ("l2", "ip"):
+        D, I = census.gram_topk(xh, np.arange(HOST_N), 2, metric, margin_rows=has)
+        np.testing.assert_array_equal(I[:, 0], np.arange(HOST_N))
+        np.testing.assert_array_equal(I[has, 1], p[has])
+        if kind == "int":
+            n2 = float((xh[0].astype(np.float64) ** 2).sum())
+            np.testing.assert_array_equal(D[has], np.broadcast_to(np.float32([0, 2] if metric == "l2" else [n2, n2 - 1]), (has.sum(), 2)))
+
+
+@pytest.mark.parametrize("d,M,construction,kind,n", cc.PQ_SHAPES)
+def test_coded_corpora_at_full_size(d, M, construction, kind, n):
+    """The corpora of the GPU cases themselves: distinct rows (M = 8: 17 409 of the 40 320 permutations, drawn by twin class), the
+    codes in use, the reconstruction.  (Their neighbours are asserted where the reference is made: CodedCase.ref.)"""
+    c = cc.case(construction, kind, n, d, M)
+    _coded_invariants(construction, kind, d, M, c.cb, c.codes, c.X, c.p)
+    has = c.p >= 0
+    assert has.sum() >= n - 1024 and {int(m) for m in np.unique((np.arange(n) ^ c.p)[has])} == set(census.MASKS)
+
+
+@pytest.mark.parametrize("d,M,construction,kind,metrics", cc.IVFPQ_SHAPES)
+def test_ivfpq_corpora(oracle, d, M, construction, kind, metrics):
+    """The IVF-PQ census corpora: list sizes 0, 1, 255, 256, 257 and 1900, partners inside the lists at masks 4, 64, 256, residual rows
+    that pass the flat invariants, decoded rows pairwise distinct; from the IVF oracle over the decoded rows, for every metric the
+    shape runs under: EVERY row finds itself first and every paired row its twin second (8 probes of 64 lists)."""
+    C, cb, codes, lor, p, xh = cc.ivfpq_corpus(d, M, construction, kind)
+    sizes = np.bincount(lor, minlength=cc.IVF_NLIST)
+    assert [sizes[l] for l in (0, 2, 4, 5, 6, 1)] == [0, 1, 255, 256, 257, 1900] and (sizes[8:12] == 0).all()
+    has = p >= 0
+    assert (lor[p[has]] == lor[has]).all() and has.sum() > len(lor) // 2
+    _coded_invariants(construction, kind, d, M, cb, codes, pq_restatement.reconstruct(codes, cb), p, pin0=construction == "slots")
+    assert len(np.unique(xh, axis=0)) == len(xh)
+    for metric in metrics:
+        _, I = oracle.ivf_search(xh, C, lor, xh, 2, 8, metric)
+        np.testing.assert_array_equal(I[:, 0], np.arange(len(xh)))
+        np.testing.assert_array_equal(I[has, 1], p[has])
+
+
+def test_restated_panel_launches():
+    """The branch every shape of the GPU cases names, from the restated launch_pq_panels / ivf_pq_panels."""
+    L = {(d, M): cc.pq_panel_launch(d, M) for d, M, *_ in cc.PQ_SHAPES}
+    pick = lambda d, M, *keys: tuple(L[(d, M)][k] for k in keys)  # noqa: E731
+    assert pick(64, 8, "p16", "W", "vec", "table", "gy") == (False, 8, True, "lds", 1)
+    assert pick(128, 32, "p16", "W", "vec", "table") == (False, 4, True, "lds")
+    assert pick(100, 50, "p16", "W", "vec", "table", "partial", "pad8") == (False, 2, False, "lds", True, True)
+    assert pick(50, 50, "p16", "W", "vec", "table", "pad8") == (False, 1, False, "lds", True)
+    assert pick(128, 128, "p16", "W", "vec", "table", "gy") == (False, 1, True, "cache", 1)
+    assert pick(384, 64, "p16", "W", "vec", "table", "slice_ks", "gy", "last") == (True, 2, True, "sliced", 3, 4, 3)
+    assert pick(384, 96, "p16", "W", "vec", "table", "slice_ks", "gy", "last") == (True, 4, True, "sliced", 4, 3, 4)
+    assert pick(200, 25, "p16", "W", "vec", "table", "slice_ks", "gy", "partial") == (True, 8, False, "sliced", 4, 2, True)
+    assert pick(240, 16, "p16", "W", "vec", "table", "gy") == (True, 1, True, "cache", 1)
+    assert pick(320, 40, "p16", "W", "vec", "table", "slice_ks", "gy", "last") == (True, 8, True, "sliced", 4, 3, 2)
+    assert {v["W"] for v in L.values()} == {1, 2, 4, 8}
+    assert {(v["p16"], v["vec"]) for v in L.values()} == {(False, False), (False, True), (True, False), (True, True)}
+    assert {(v["p16"], v["table"]) for v in L.values()} == {(False, "lds"), (False, "cache"), (True, "sliced"), (True, "cache")}
+    I = {(d, M): cc.ivfpq_panel_launch(d, M) for d, M, *_ in cc.IVFPQ_SHAPES}
+    assert I[(48, 12)] == dict(lds=True, slice_ks=4, gy=1, vec=True, pad16=False)
+    assert I[(128, 64)] == dict(lds=True, slice_ks=2, gy=4, vec=True, pad16=False)
+    assert I[(100, 25)] == dict(lds=True, slice_ks=2, gy=4, vec=False, pad16=True)
+    assert I[(128, 2)] == dict(lds=False, slice_ks=8, gy=1, vec=False, pad16=False)
+
+
+def test_restated_slab_cut():
+    g = census.scan_geometry(17_409, 64, 2, 700, 2)
+    assert g.nchunks == 24 and g.rem == 11
+    one, three, default = cc.slab_cut(g, 64, 1), cc.slab_cut(g, 64, 3), cc.slab_cut(g, 64)
+    assert len(one) == 24 and {s[3] for s in one} == {1, 2} and len(default) == 1 and default[0] == (0, 24, 0, 35)
+    assert len(three) == 8 and three[3] == (9, 3, 18, 5) and three[4] == (12, 3, 23, 3) and sum(s[3] for s in three) == 35
+    g = census.scan_geometry(18_443, 384, 2, 700, 2)
+    assert g.nchunks == 10 and [s[1] for s in cc.slab_cut(g, 384, 3)] == [3, 3, 3, 1] and cc.slab_cut(g, 384, 3)[-1] == (9, 1, 18, 1)
