@@ -19,8 +19,9 @@ import numpy as np
 def _fma_sq_add(t: np.ndarray, acc: np.ndarray) -> np.ndarray:
     """fma(t, t, acc) element-wise in float64, correctly rounded.  t * t = hi + lo exactly (Veltkamp / Dekker split); the sum
     acc + hi + lo is then rounded once: s = acc + hi with its exact error e (two-sum), and the result is s + (e + lo), which is
-    the correctly rounded value whenever e + lo is exact or far below half an ulp of s.  Where that cannot be certified from
-    magnitudes, the element is recomputed in exact rational arithmetic."""
+    the correctly rounded value whenever e + lo is exact: s + (e + lo) is then ONE rounding of acc + t * t.  Whether it is
+    exact is read from the error term of a second two-sum; an element where it is not is recomputed in exact rational
+    arithmetic."""
     t = np.asarray(t, dtype=np.float64)
     acc = np.asarray(acc, dtype=np.float64)
     c = 134217729.0 * t                      # 2^27 + 1
@@ -34,7 +35,8 @@ def _fma_sq_add(t: np.ndarray, acc: np.ndarray) -> np.ndarray:
     r = s + (e + lo)
     # certify: exact recomputation where the cheap path is not provably the single rounding
     tail = e + lo
-    doubtful = (tail != 0.0) & ~((e == 0.0) | (lo == 0.0))
+    tb = tail - e
+    doubtful = ((e - (tail - tb)) + (lo - tb)) != 0.0        # (two-sum: the error of e + lo)
     if np.any(doubtful):
         idx = np.flatnonzero(doubtful)
         tf, af, rf = t.ravel(), acc.ravel(), r.ravel().copy()

@@ -120,6 +120,39 @@ def test_search_equals_the_oracle_over_decoded_rows(vdb, oracle, d, M, metric):
         assert (Id[same, 0] == ID0 + np.flatnonzero(same)).all() and (Id[same, 1] == ID0 + 40 + np.flatnonzero(same)).all()
 
 
+@pytest.mark.parametrize("metric", ["l2", "ip"])
+def test_encode_with_the_codebook_read_from_global_memory(vdb, oracle, metric):
+    """D = 128, M = 2: a sub-space of 256 x 64 floats (64 KiB) does not fit the 48 KiB of LDS pq_encode_kernel may use, so the
+    residual encoder reads the codebook from global memory.  600 rows of parity_inputs in 4 lists; 8 rows per list are moved
+    next to centroid + entry 17 of both sub-spaces, so that entry 17 and its copy, entry 200, tie for the minimum (asserted on
+    the restatement before any GPU call).  The limit of the census corpora of this shape (tests/census_coded.py: L2 only, their
+    rows must be their own nearest neighbours) does not apply: the reference here is the IVF oracle over the decoded rows,
+    which serves both metrics."""
+    d, M, n, nlist = 128, 2, 600, 4
+    X, Q, C, cb = cases.parity_inputs(d, M)
+    X, Q, C = X[:n].copy(), Q[:8], np.ascontiguousarray(C[:nlist])
+    entry17 = np.concatenate([cb[0, 17], cb[1, 17]])
+    for l in range(nlist):
+        X[100 + 8 * l:108 + 8 * l] = C[l] + entry17 + (0.01 * np.random.default_rng(l).standard_normal((8, d))).astype(F32)
+    lor = oracle.ivf_assign(C, X, metric)
+    codes = ref.encode(X, C, lor, cb)
+    assert ((codes == 17).sum(axis=0) >= 8).all() and not (codes == 200).any()
+    Xh = ref.decode(codes, C, lor, cb)
+    idx = _index(vdb, d, M, C, cb, metric)
+    try:
+        idx.add(X, id_base=ID0)
+        np.testing.assert_array_equal(idx.assignment(), lor)
+        np.testing.assert_array_equal(idx.codes(), codes)
+        np.testing.assert_array_equal(idx.reconstruct(), Xh)
+        idx.set_nprobe(2)
+        D, I = idx.search(Q, 10)
+        Do, Io = oracle.ivf_search(Xh, C, lor, Q, 10, 2, metric, id_base=ID0)
+        np.testing.assert_array_equal(I, Io)
+        np.testing.assert_array_equal(D, Do)
+    finally:
+        idx.close()
+
+
 def test_parity_indexes_are_closed():
     for idx, *_ in _parity.values():
         idx.close()

@@ -185,6 +185,21 @@ void ivf_check_given(const vdb_index_s *h, const int32_t *given, int64_t n) {
 #include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
 #include "ivf_pq.inc"       // IVF<nlist>,PQ<M>: residual product codes, encoding add, the per-batch panel pass
 
+// vdb_ivf_get_codes / vdb_ivfpq_get_codes: the code rows of a built coded index (`codes`: list order, `pitch` bytes apart, the
+// first `width` of each are the row's code), scattered from list order to insertion order (id - id_base)
+void ivf_get_codes(vdb_index_s *h, const DevBuf &codes, size_t pitch, size_t width, uint8_t *codes_host) {
+    ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
+    ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
+    if (h->N == 0) return;
+    set_device(h->device);
+    std::vector<unsigned char> c((size_t)h->N * pitch);
+    std::vector<int64_t> ids((size_t)h->N);
+    VDB_HIP(hipDeviceSynchronize());
+    VDB_HIP(hipMemcpy(c.data(), codes.p, c.size(), hipMemcpyDeviceToHost));
+    VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < h->N; ++r) memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * width, &c[(size_t)r * pitch], width);
+}
+
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
 // 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
 // (four 64-row bins) or, for lists of thousands of rows, 1024 rows (four 256-row bins).
@@ -919,8 +934,7 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
         if (coded) refuse_options_set(h, "vdb_ivf_set_codec", codec == 1 ? kIvfSq8 : kIvfPq);
         if (codec != 2) {                       // (codebooks belong to codec 2)
-            h->ivfpq_M = h->ivfpq_dsub = 0;
-            h->ivfpq_cb_host.clear();
+            h->ivfpq = PqCodebooks{};
             h->kept.ivfpq_cb.release();
         }
         h->ivf_codec = codec;
@@ -969,18 +983,7 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
         admit_sq8(h, "vdb_ivf_get_codes");
-        ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
-        ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
-        if (h->N == 0) return;
-        set_device(h->device);
-        const int Dm = h->dim, D4 = h->D4;
-        std::vector<unsigned char> c((size_t)h->N * D4);
-        std::vector<int64_t> ids((size_t)h->N);
-        VDB_HIP(hipDeviceSynchronize());
-        VDB_HIP(hipMemcpy(c.data(), h->codes.sq8_codes.p, c.size(), hipMemcpyDeviceToHost));
-        VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
-            memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * Dm, &c[(size_t)r * D4], (size_t)Dm);
+        ivf_get_codes(h, h->codes.sq8_codes, (size_t)h->D4, (size_t)h->dim, codes_host);
     });
 }
 
@@ -988,7 +991,7 @@ int vdb_ivfpq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
         admit_ivfpq(h, "vdb_ivfpq_set_codebooks");
-        ivfpq_check_M(h, M);
+        pq_check_M(h, M);
         ivf_require(codebooks_host != nullptr, VDB_ERR_INVALID, "null codebook pointer");
         set_device(h->device);
         ivfpq_install_codebooks(h, M, codebooks_host);
@@ -999,9 +1002,7 @@ int vdb_ivfpq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
         admit(h, "vdb_ivfpq_get_codebooks", kAnyKind);
-        ivf_require(M != nullptr, VDB_ERR_INVALID, "null pointer");
-        *M = kind_of(h) == kIvfPq ? h->ivfpq_M : 0;
-        if (codebooks_host && *M > 0) memcpy(codebooks_host, h->ivfpq_cb_host.data(), h->ivfpq_cb_host.size() * sizeof(float));
+        pq_get_codebooks(h->ivfpq, kind_of(h) == kIvfPq, M, codebooks_host);
     });
 }
 
@@ -1009,20 +1010,15 @@ int vdb_ivfpq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int ni
     return guarded([&] {
         auto *h = check(hh);
         admit_ivfpq(h, "vdb_ivfpq_train");
-        ivfpq_check_M(h, M);
+        pq_check_M(h, M);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
-        ivf_require(x_host != nullptr && n > 0, VDB_ERR_INVALID, "no training vectors");
-        ivf_require(n >= 256, VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
-        ivf_require(niter >= 0 && niter <= 1000, VDB_ERR_INVALID, "niter out of range");
-        if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
+        pq_check_train_args(x_host, n, niter, max_points_per_centroid);
         set_device(h->device);
-        const int D = h->dim, dsub = D / M;
-        // one row sample for every sub-space, drawn with `seed` (vdb_pq_train's draws), and its residuals against the
-        // installed centroids: r = x - c_l, one float32 subtraction per dimension
-        const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
-        const std::vector<int64_t> pick = sample_rows(n, ns, seed);
-        std::vector<float> res((size_t)ns * D);
-        for (int64_t i = 0; i < ns; ++i) memcpy(&res[(size_t)i * D], x_host + (size_t)pick[(size_t)i] * D, (size_t)D * sizeof(float));
+        // the row sample of vdb_pq_train, then its residuals against the installed centroids: r = x - c_l, one float32
+        // subtraction per dimension
+        const int D = h->dim;
+        std::vector<float> res = pq_training_sample(x_host, n, D, seed, max_points_per_centroid);
+        const int64_t ns = (int64_t)(res.size() / (size_t)D);
         {
             DevBuf dx, dassign;
             dx.reserve((size_t)ns * D * sizeof(float));
@@ -1038,18 +1034,7 @@ int vdb_ivfpq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int ni
                 for (int d = 0; d < D; ++d) r[d] = r[d] - c[d];
             }
         }
-        // sub-space m: the library's k-means (vdb_ivf_train on a flat L2 handle of dsub dims) over the residuals, seed + m
-        std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
-        for (int m = 0; m < M; ++m) {
-            for (int64_t i = 0; i < ns; ++i) memcpy(&sub[(size_t)i * dsub], &res[(size_t)i * D + (size_t)m * dsub], (size_t)dsub * sizeof(float));
-            vdb_handle t = nullptr;
-            int rc = vdb_create(dsub, VDB_METRIC_L2, h->device, &t);
-            if (rc == VDB_OK) rc = vdb_ivf_train(t, 256, sub.data(), ns, niter, seed + (uint64_t)m, max_points_per_centroid);
-            if (rc == VDB_OK) rc = vdb_ivf_get_centroids(t, &cb[(size_t)m * 256 * dsub]);
-            const std::string msg = rc == VDB_OK ? std::string() : g_last_error;
-            if (t) (void)vdb_destroy(t);
-            if (rc != VDB_OK) throw Error(rc, "k-means of sub-space " + std::to_string(m) + ": " + msg);
-        }
+        const std::vector<float> cb = pq_train_codebooks(h->device, res, D, M, niter, seed, max_points_per_centroid);
         ivfpq_install_codebooks(h, M, cb.data());
     });
 }
@@ -1067,18 +1052,7 @@ int vdb_ivfpq_get_codes(vdb_handle hh, uint8_t *codes_host) {
     return guarded([&] {
         auto *h = check(hh);
         admit_ivfpq(h, "vdb_ivfpq_get_codes");
-        ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
-        ivf_require(codes_host != nullptr || h->N == 0, VDB_ERR_INVALID, "null pointer");
-        if (h->N == 0) return;
-        set_device(h->device);
-        const size_t M = (size_t)h->ivfpq_M;
-        std::vector<unsigned char> c((size_t)h->N * M);
-        std::vector<int64_t> ids((size_t)h->N);
-        VDB_HIP(hipDeviceSynchronize());
-        VDB_HIP(hipMemcpy(c.data(), h->codes.ivfpq_codes.p, c.size(), hipMemcpyDeviceToHost));
-        VDB_HIP(hipMemcpy(ids.data(), h->lists.ivf_ids.p, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-        for (int64_t r = 0; r < h->N; ++r)           // list order -> insertion order (id - id_base)
-            memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * M, &c[(size_t)r * M], M);
+        ivf_get_codes(h, h->codes.ivfpq_codes, (size_t)h->ivfpq.M, (size_t)h->ivfpq.M, codes_host);
     });
 }
 

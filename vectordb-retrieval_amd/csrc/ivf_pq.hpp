@@ -15,46 +15,11 @@
 #pragma once
 #include "common.hpp"
 #include "ivf_mfma.hpp"
-#include "refine.hpp"
+#include "pq.hpp"
 
 namespace vdb {
 
-// ---- rows -> codes: pq_encode_kernel (pq.hpp) on the residual ------------------------------------------------------------
-// X [n][D4] (zero padded), assign[i] = list of row i (validated on the host), cent [nlist][D4].  grid (row blocks, M): one
-// sub-space per workgroup, its 256 centroids in LDS when they fit `lds_floats`; grid-stride over the rows.  The residual is
-// one float32 subtraction per dimension, then the float64 chain acc = fma(t, t, acc), t = (double)r[j] - (double)c[j].
-__global__ __launch_bounds__(256) void ivfpq_encode_kernel(const float *__restrict__ X, int64_t n, int D4, const float *__restrict__ cent,
-                                                           const int64_t *__restrict__ assign, const float *__restrict__ cb, int M, int dsub,
-                                                           int lds_floats, unsigned char *__restrict__ codes) {
-    extern __shared__ float ivfpq_enc_lds[];
-    const int m = blockIdx.y;
-    const float *cm = cb + (size_t)m * 256 * dsub;
-    const bool in_lds = 256 * dsub <= lds_floats;
-    if (in_lds) {
-        for (int i = threadIdx.x; i < 256 * dsub; i += 256) ivfpq_enc_lds[i] = cm[i];
-        __syncthreads();
-    }
-    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
-        const float *x = X + (size_t)row * D4 + (size_t)m * dsub;
-        const float *cl = cent + (size_t)assign[row] * D4 + (size_t)m * dsub;
-        double best = __builtin_inf();
-        int arg = 0;
-        for (int c = 0; c < 256; ++c) {
-            const float *cv = in_lds ? ivfpq_enc_lds + c * dsub : cm + (size_t)c * dsub;
-            double acc = 0.0;
-            for (int j = 0; j < dsub; ++j) {
-                const float r = x[j] - cl[j];
-                const double t = (double)r - (double)cv[j];
-                acc = fma(t, t, acc);
-            }
-            if (acc < best) {       // (strict: the smaller c keeps a tie; a NaN key never wins)
-                best = acc;
-                arg = c;
-            }
-        }
-        codes[(size_t)row * M + m] = (unsigned char)arg;
-    }
-}
+// (rows -> codes and codes -> rows: pq_encode_kernel<true> and pq_decode_rows_kernel<true>, pq.hpp)
 
 // ---- CSR build of the codes: codes[i] = src[perm[i]] (rows of M bytes), ids[i] as gather_rows_kernel sets them -----------
 __global__ __launch_bounds__(256) void ivfpq_gather_kernel(const unsigned char *__restrict__ src, const int32_t *__restrict__ perm, int64_t n,
@@ -67,22 +32,6 @@ __global__ __launch_bounds__(256) void ivfpq_gather_kernel(const unsigned char *
         const int64_t s = perm[r];
         codes[i] = src[s * M + c];
         if (c == 0) ids[r] = src_ids ? src_ids[s] : id_base + s;
-    }
-}
-
-// ---- decoded rows x^ [n][pitch] (0 for D <= d < pitch) of list-order rows: the transient float32 copy the panel space is
-// derived from at build time (pitch D4), and the query rows of vdb_reserve (pitch D)
-__global__ __launch_bounds__(256) void ivfpq_decode_rows_kernel(IvfPqRows p, int64_t n, int D, int D4, int64_t pitch, float *__restrict__ out) {
-    const int64_t total = n * pitch;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int64_t r = i / pitch;
-        const int d = (int)(i - r * pitch);
-        float v = 0.f;
-        if (d < D) {
-            const int m = d / p.dsub;
-            v = p.cent[(size_t)p.list[r] * D4 + d] + p.cb[((size_t)m * 256 + p.codes[(size_t)r * p.M + m]) * p.dsub + (d - m * p.dsub)];
-        }
-        out[i] = v;
     }
 }
 
@@ -115,7 +64,7 @@ template <bool LDS>
 __global__ __launch_bounds__(256) void ivf_pq_panels_kernel(IvfPqPanelArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ivfpq_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int M = a.rows.M, dsub = a.rows.dsub;
+    const int M = a.rows.pq.M, dsub = a.rows.pq.dsub;
     const int stage_bytes = (32 * a.code_pitch + 15) & ~15;
     const int wave_bytes = stage_bytes + kIvfPqCentFloats * (int)sizeof(float);
     unsigned char *stage = ivfpq_lds + wave * wave_bytes;
@@ -127,7 +76,7 @@ __global__ __launch_bounds__(256) void ivf_pq_panels_kernel(IvfPqPanelArgs a) {
     if (LDS) {
         const int m_hi = (d_hi + dsub - 1) / dsub;
         const int nf = (m_hi - m_lo) * 256 * dsub;                     // (<= 0: the slice holds padding dims only)
-        const float *src = a.rows.cb + (size_t)m_lo * 256 * dsub;
+        const float *src = a.rows.pq.cb + (size_t)m_lo * 256 * dsub;
         for (int i = threadIdx.x; i < nf; i += 256) lt[i] = src[i];
         __syncthreads();
     }
@@ -154,7 +103,7 @@ __global__ __launch_bounds__(256) void ivf_pq_panels_kernel(IvfPqPanelArgs a) {
             for (int h = 0; h < 2; ++h) {
                 const int local = h * (kIvfSpanRows / 2) + t * 16 + r;
                 if (local < nvalid) {
-                    const unsigned char *src = a.rows.codes + (size_t)(row0 + local) * M;
+                    const unsigned char *src = a.rows.pq.codes + (size_t)(row0 + local) * M;
                     unsigned char *dst = stage + (h * 16 + r) * a.code_pitch;
                     if (vec)
                         for (int c = c0; c < M / 4; c += 4) reinterpret_cast<unsigned *>(dst)[c] = reinterpret_cast<const unsigned *>(src)[c];
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(256) void ivf_pq_panels_kernel(IvfPqPanelArgs a) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     if (d0 + e < a.D) {
-                        const float tv = LDS ? lt[((m - m_lo) * 256 + cr[m]) * dsub + j] : a.rows.cb[((size_t)m * 256 + cr[m]) * dsub + j];
+                        const float tv = LDS ? lt[((m - m_lo) * 256 + cr[m]) * dsub + j] : a.rows.pq.cb[((size_t)m * 256 + cr[m]) * dsub + j];
                         o.h[e] = (_Float16)((cstage[d0 + e] + tv) * a.sx);
                         if (++j == dsub) { j = 0; ++m; }
                     }

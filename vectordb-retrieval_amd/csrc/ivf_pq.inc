@@ -12,30 +12,19 @@ inline bool ivfpq(const vdb_index_s *h) { return h->ivf_codec == 2; }
 
 IvfPqRows ivfpq_rows(const vdb_index_s *h) {
     IvfPqRows p;
-    p.codes = h->codes.ivfpq_codes.as<unsigned char>();
+    p.pq.codes = h->codes.ivfpq_codes.as<unsigned char>();
     p.list = h->codes.sq8_list.as<int32_t>();
     p.cent = h->kept.sq8_cent.as<float>();
-    p.cb = h->kept.ivfpq_cb.as<float>();
-    p.M = h->ivfpq_M;
-    p.dsub = h->ivfpq_dsub;
+    p.pq.cb = h->kept.ivfpq_cb.as<float>();
+    p.pq.M = h->ivfpq.M;
+    p.pq.dsub = h->ivfpq.dsub;
     return p;
 }
 
-void ivfpq_check_M(const vdb_index_s *h, int M) {
-    ivf_require(M >= 1 && M <= std::min(h->dim, 256), VDB_ERR_INVALID, "M must be in [1, min(dim, 256)]");
-    ivf_require(h->dim % M == 0, VDB_ERR_INVALID, "dim must be a multiple of M");
-}
-
+// pq_install_codebooks (pq.inc) on the codebooks of the residuals; refused ones leave the index as it was
 void ivfpq_install_codebooks(vdb_index_s *h, int M, const float *cb_host) {
-    const size_t total = (size_t)256 * h->dim;
-    for (size_t i = 0; i < total; ++i)
-        if (!std::isfinite(cb_host[i])) throw Error(VDB_ERR_INVALID, "codebook entries must be finite");
     VDB_HIP(hipDeviceSynchronize());
-    h->kept.ivfpq_cb.reserve_exact(total * sizeof(float));
-    VDB_HIP(hipMemcpy(h->kept.ivfpq_cb.p, cb_host, total * sizeof(float), hipMemcpyHostToDevice));
-    h->ivfpq_cb_host.assign(cb_host, cb_host + total);
-    h->ivfpq_M = M;
-    h->ivfpq_dsub = h->dim / M;
+    pq_install_codebooks(h, h->ivfpq, h->kept.ivfpq_cb, M, cb_host);
     h->ivf_built = false;                      // (rows encoded under the old codebooks are dropped by the next add)
 }
 
@@ -49,7 +38,7 @@ void ivfpq_upload_centroids(vdb_index_s *h) {
 // x^ of the first n list-order rows: float32, `pitch` floats per row (zero beyond dim)
 void ivfpq_decode_rows(vdb_index_s *h, int64_t n, int64_t pitch, float *out, hipStream_t st) {
     if (n <= 0) return;
-    ivfpq_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((n * pitch + 255) / 256, 1 << 16)), dim3(256), 0, st>>>(
+    pq_decode_rows_kernel<true><<<dim3((unsigned)std::min<int64_t>((n * pitch + 255) / 256, 1 << 16)), dim3(256), 0, st>>>(
         ivfpq_rows(h), n, h->dim, h->D4, pitch, out);
     VDB_HIP(hipGetLastError());
 }
@@ -80,13 +69,13 @@ void ivfpq_build_panel_space(vdb_index_s *h) {
 // codes are kept.  Every argument is checked before the handle is touched: a refused add leaves the index as it was.
 void ivfpq_add(vdb_index_s *h, const float *x_host, const uint8_t *codes_host, int64_t n, int64_t id_base, const int32_t *given) {
     ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
-    ivf_require(h->ivfpq_M > 0, VDB_ERR_STATE, "no IVF-PQ codebooks: call vdb_ivfpq_train or vdb_ivfpq_set_codebooks first");
+    ivf_require(h->ivfpq.M > 0, VDB_ERR_STATE, "no IVF-PQ codebooks: call vdb_ivfpq_train or vdb_ivfpq_set_codebooks first");
     ivf_require(n >= 0 && (n == 0 || x_host || codes_host), VDB_ERR_INVALID, "bad corpus");
     int64_t N0, N1;
     if (!ivf_add_range(h, n, id_base, N0, N1)) return;
     ivf_check_given(h, given, n);
     set_device(h->device);
-    const int Dm = h->dim, D4 = h->D4, M = h->ivfpq_M, dsub = h->ivfpq_dsub;
+    const int Dm = h->dim, D4 = h->D4, M = h->ivfpq.M;
     VDB_HIP(hipDeviceSynchronize());
     h->ivf_built = false;
     h->built = false;
@@ -116,12 +105,8 @@ void ivfpq_add(vdb_index_s *h, const float *x_host, const uint8_t *codes_host, i
                 for (int64_t i = 0; i < n; ++i)      // (the kernel reads centroid assign[i]: no row without a list reaches it)
                     ivf_require(assign_new[(size_t)i] >= 0 && assign_new[(size_t)i] < h->nlist, VDB_ERR_INVALID, "row could not be assigned to a list");
             }
-            const bool in_lds = (size_t)256 * dsub * sizeof(float) <= 49152;
-            const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048));
-            ivfpq_encode_kernel<<<dim3(gx, (unsigned)M), dim3(256), in_lds ? (size_t)256 * dsub * sizeof(float) : 0, nullptr>>>(
-                fresh.as<float>(), n, D4, h->kept.sq8_cent.as<float>(), dnew.as<int64_t>(), h->kept.ivfpq_cb.as<float>(), M, dsub,
-                in_lds ? 256 * dsub : 0, new_codes);
-            VDB_HIP(hipGetLastError());
+            pq_launch_encode(fresh.as<float>(), n, D4, h->kept.sq8_cent.as<float>(), dnew.as<int64_t>(), h->kept.ivfpq_cb.as<float>(), M,
+                             h->ivfpq.dsub, new_codes, nullptr);
             VDB_HIP(hipDeviceSynchronize());
             fresh.release();
             dnew.release();
@@ -163,11 +148,9 @@ const half8 *ivf_pq_panels(vdb_index_s *h, hipStream_t st) {
     a.ntiles = ntiles;
     a.sx = h->sx;
     a.D = h->dim; a.D4 = h->D4; a.ksteps = h->ksteps;
-    const int M = h->ivfpq_M, dsub = h->ivfpq_dsub;
-    int pitch = (M + 3) & ~3;
-    if ((pitch / 4) % 2 == 0) pitch += 4;
-    a.code_pitch = pitch;
-    const int fixed = 4 * (((32 * pitch + 15) & ~15) + kIvfPqCentFloats * (int)sizeof(float));
+    const int dsub = h->ivfpq.dsub;
+    a.code_pitch = pq_code_pitch(h->ivfpq.M);
+    const int fixed = 4 * (((32 * a.code_pitch + 15) & ~15) + kIvfPqCentFloats * (int)sizeof(float));
     bool lds = false;
     a.slice_ks = h->ksteps;
     size_t table_bytes = 0;

@@ -1,4 +1,5 @@
-// pq.hpp -- kernels of the flat PQ<M> index (host side: pq.inc; contract: include/vdbhip.h).
+// pq.hpp -- kernels of the product quantizer: the encoder and the row decoder that the flat PQ<M> index and IVF<nlist>,PQ<M>
+// (ivf_pq.hpp: RESIDUAL) share, then the table and panel kernels of the flat index (host side: pq.inc; contract: include/vdbhip.h).
 //
 // A PQ index keeps M code bytes per row and the codebooks, float32 [M][256][dsub] (dsub = D / M).  The reconstructed row
 // x^ is the concatenation of codebook[m][code[m]] -- a lookup, no arithmetic -- and a search is the flat exact search of
@@ -7,16 +8,22 @@
 #pragma once
 #include "common.hpp"
 #include "prep.hpp"
+#include "refine.hpp"
 
 namespace vdb {
 
 // ---- rows -> codes ----------------------------------------------------------------------------------------------------
-// code[i][m] = argmin over c of the canonical float64 L2 key between x[i][m dsub .. (m + 1) dsub) and codebook[m][c]
-// (acc = fma(t, t, acc), t = (double)x[d] - (double)c[d], d ascending), ties to the smaller c, whatever the index metric.
+// code[i][m] = argmin over c of the canonical float64 L2 key between r[m dsub .. (m + 1) dsub) and codebook[m][c]
+// (acc = fma(t, t, acc), t = (double)r[d] - (double)c[d], d ascending), ties to the smaller c, whatever the index metric.
+// r = x[i], or (RESIDUAL: IVF-PQ, ivf_pq.inc) x[i] - cent[assign[i]]: one float32 subtraction per dimension, rounded before it
+// is widened; cent [nlist][pitch] is zero padded like X and assign[i] was validated on the host.
 // grid (row blocks, M): one sub-space per workgroup, its 256 centroids in LDS when they fit `lds_floats` (every lane
-// of a wave reads the same centroid element: a broadcast), else read from the codebook; grid-stride over the rows.
-__global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict__ X, int64_t n, int64_t pitch, const float *__restrict__ cb,
-                                                        int M, int dsub, int lds_floats, unsigned char *__restrict__ codes) {
+// of a wave reads the same centroid element: a broadcast), else read from the codebook -- two loops, so that the address
+// space of every load is known at compile time; grid-stride over the rows.
+template <bool RESIDUAL>
+__global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict__ X, int64_t n, int64_t pitch, const float *__restrict__ cent,
+                                                        const int64_t *__restrict__ assign, const float *__restrict__ cb, int M, int dsub,
+                                                        int lds_floats, unsigned char *__restrict__ codes) {
     extern __shared__ float pq_enc_lds[];
     const int m = blockIdx.y;
     const float *cm = cb + (size_t)m * 256 * dsub;
@@ -27,6 +34,7 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict_
     }
     for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
         const float *x = X + (size_t)row * pitch + (size_t)m * dsub;
+        const float *cl = RESIDUAL ? cent + (size_t)assign[row] * pitch + (size_t)m * dsub : nullptr;
         double best = __builtin_inf();
         int arg = 0;
         for (int c = 0; c < 256; ++c) {
@@ -34,13 +42,15 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict_
             if (in_lds) {
                 const float *cv = pq_enc_lds + c * dsub;
                 for (int j = 0; j < dsub; ++j) {
-                    const double t = (double)x[j] - (double)cv[j];
+                    const float r = RESIDUAL ? x[j] - cl[j] : x[j];
+                    const double t = (double)r - (double)cv[j];
                     acc = fma(t, t, acc);
                 }
             } else {
                 const float *cv = cm + (size_t)c * dsub;
                 for (int j = 0; j < dsub; ++j) {
-                    const double t = (double)x[j] - (double)cv[j];
+                    const float r = RESIDUAL ? x[j] - cl[j] : x[j];
+                    const double t = (double)r - (double)cv[j];
                     acc = fma(t, t, acc);
                 }
             }
@@ -54,18 +64,21 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict_
 }
 
 // ---- codes -> float32 rows x^ -----------------------------------------------------------------------------------------
-// out[r][d] = codebook[d / dsub][code[r][d / dsub]][d % dsub] for d < D, 0 for D <= d < pitch.  Grid-stride, one element
-// per thread and trip.  Used for the transient copy of a build (pitch D4) and for the query rows of vdb_reserve (pitch D).
-__global__ __launch_bounds__(256) void pq_decode_rows_kernel(const unsigned char *__restrict__ codes, const float *__restrict__ cb, int64_t n,
-                                                             int D, int M, int dsub, int64_t pitch, float *__restrict__ out) {
+// out[r][d] = codebook[d / dsub][code[r][d / dsub]][d % dsub] for d < D, plus (RESIDUAL: IVF-PQ, list-order rows) the
+// centroid cent[list[r]][d] in ONE float32 add; 0 for D <= d < pitch.  Grid-stride, one element per thread and trip.  Used
+// for the transient copy of a build (pitch D4) and for the query rows of vdb_reserve (pitch D).
+template <bool RESIDUAL>
+__global__ __launch_bounds__(256) void pq_decode_rows_kernel(IvfPqRows p, int64_t n, int D, int D4, int64_t pitch, float *__restrict__ out) {
     const int64_t total = n * pitch;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / pitch;
         const int d = (int)(i - r * pitch);
         float v = 0.f;
         if (d < D) {
-            const int m = d / dsub;
-            v = cb[((size_t)m * 256 + codes[(size_t)r * M + m]) * dsub + (d - m * dsub)];
+            const PqRows &c = p.pq;
+            const int m = d / c.dsub;
+            v = c.cb[((size_t)m * 256 + c.codes[(size_t)r * c.M + m]) * c.dsub + (d - m * c.dsub)];
+            if (RESIDUAL) v = p.cent[(size_t)p.list[r] * D4 + d] + v;
         }
         out[i] = v;
     }

@@ -1,14 +1,99 @@
-// pq.inc -- host side of the flat PQ<M> index (kernels: pq.hpp): codebooks, encoding adds, the derived scan statistics,
-// the per-slab panel pass of a search.  Included by vdbhip.hip; the handle's PQ state lives in vdb_index_s (pq_*).
+// pq.inc -- host side of the product quantizer (kernels: pq.hpp).  First the core that the flat PQ<M> index and
+// IVF<nlist>,PQ<M> (ivf_pq.inc, ivf.inc) share: the M rule, installing and reading codebooks, their training, the encode
+// launch.  Then the flat index: encoding adds, the derived scan statistics, the per-slab panel pass of a search.  Included by
+// vdbhip.hip ahead of ivf.inc; a handle keeps one PqCodebooks for each of the two (vdb_index_s: pq, ivfpq).
 
 namespace {
 
+// ---- the core ---------------------------------------------------------------------------------------------------------------
+void pq_check_M(const vdb_index_s *h, int M) {
+    if (M < 1 || M > std::min(h->dim, 256)) throw Error(VDB_ERR_INVALID, "M must be in [1, min(dim, 256)]");
+    if (h->dim % M) throw Error(VDB_ERR_INVALID, "dim must be a multiple of M");
+}
+
+// [M][256][dsub] finite floats become the codebooks `q` of the handle, with their device copy `dev`; refused ones leave both as
+// they were.  The caller has synchronised the device, and drops what the old codebooks made (a captured graph, encoded rows).
+void pq_install_codebooks(vdb_index_s *h, PqCodebooks &q, DevBuf &dev, int M, const float *cb_host) {
+    const size_t total = (size_t)256 * h->dim;
+    for (size_t i = 0; i < total; ++i)
+        if (!std::isfinite(cb_host[i])) throw Error(VDB_ERR_INVALID, "codebook entries must be finite");
+    dev.reserve_exact(total * sizeof(float));
+    VDB_HIP(hipMemcpy(dev.p, cb_host, total * sizeof(float), hipMemcpyHostToDevice));
+    q.host.assign(cb_host, cb_host + total);
+    q.M = M;
+    q.dsub = h->dim / M;
+}
+
+// vdb_*_get_codebooks: *M = q.M when the handle is of the kind that owns `q` (`mine`), else 0; the entries when asked for
+void pq_get_codebooks(const PqCodebooks &q, bool mine, int *M, float *codebooks_host) {
+    if (!M) throw Error(VDB_ERR_INVALID, "null pointer");
+    *M = mine ? q.M : 0;
+    if (codebooks_host && *M > 0) memcpy(codebooks_host, q.host.data(), q.host.size() * sizeof(float));
+}
+
+// the training arguments both trainers refuse (max_points_per_centroid <= 0: the default, 256)
+void pq_check_train_args(const float *x_host, int64_t n, int niter, int &max_points_per_centroid) {
+    if (!x_host || n <= 0) throw Error(VDB_ERR_INVALID, "no training vectors");
+    if (n < 256) throw Error(VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
+    if (niter < 0 || niter > 1000) throw Error(VDB_ERR_INVALID, "niter out of range");
+    if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
+}
+
+// one row sample [ns][D] for every sub-space, drawn with `seed` (vdb_ivf_train's draws)
+std::vector<float> pq_training_sample(const float *x_host, int64_t n, int D, uint64_t seed, int max_points_per_centroid) {
+    const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
+    const std::vector<int64_t> pick = sample_rows(n, ns, seed);
+    std::vector<float> sample((size_t)ns * D);
+    for (int64_t i = 0; i < ns; ++i) memcpy(&sample[(size_t)i * D], x_host + (size_t)pick[(size_t)i] * D, (size_t)D * sizeof(float));
+    return sample;
+}
+
+// sampled rows [ns][D] (IVF-PQ: their residuals) -> codebooks [M][256][dsub].  Sub-space m: the library's k-means
+// (vdb_ivf_train on a flat L2 handle of dsub dims) over the sample, seed + m
+std::vector<float> pq_train_codebooks(int device, const std::vector<float> &sample, int D, int M, int niter, uint64_t seed,
+                                      int max_points_per_centroid) {
+    const int dsub = D / M;
+    const int64_t ns = (int64_t)(sample.size() / (size_t)D);
+    std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
+    for (int m = 0; m < M; ++m) {
+        for (int64_t i = 0; i < ns; ++i) memcpy(&sub[(size_t)i * dsub], &sample[(size_t)i * D + (size_t)m * dsub], (size_t)dsub * sizeof(float));
+        vdb_handle t = nullptr;
+        int rc = vdb_create(dsub, VDB_METRIC_L2, device, &t);
+        if (rc == VDB_OK) rc = vdb_ivf_train(t, 256, sub.data(), ns, niter, seed + (uint64_t)m, max_points_per_centroid);
+        if (rc == VDB_OK) rc = vdb_ivf_get_centroids(t, &cb[(size_t)m * 256 * dsub]);
+        const std::string msg = rc == VDB_OK ? std::string() : g_last_error;
+        if (t) (void)vdb_destroy(t);
+        if (rc != VDB_OK) throw Error(rc, "k-means of sub-space " + std::to_string(m) + ": " + msg);
+    }
+    return cb;
+}
+
+// codes of the n rows at `rows` (device, `pitch` floats each, zero padded), or of their residuals against cent[assign[i]]
+// (both null for the flat index): pq_encode_kernel, the sub-space's codebook in LDS when its 256 dsub floats fit 48 KiB
+void pq_launch_encode(const float *rows, int64_t n, int64_t pitch, const float *cent, const int64_t *assign, const float *cb, int M, int dsub,
+                      unsigned char *codes, hipStream_t st) {
+    const bool in_lds = (size_t)256 * dsub * sizeof(float) <= 49152;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048)), (unsigned)M);
+    const size_t lds_bytes = in_lds ? (size_t)256 * dsub * sizeof(float) : 0;
+    if (cent) pq_encode_kernel<true><<<grid, dim3(256), lds_bytes, st>>>(rows, n, pitch, cent, assign, cb, M, dsub, in_lds ? 256 * dsub : 0, codes);
+    else pq_encode_kernel<false><<<grid, dim3(256), lds_bytes, st>>>(rows, n, pitch, nullptr, nullptr, cb, M, dsub, in_lds ? 256 * dsub : 0, codes);
+    VDB_HIP(hipGetLastError());
+}
+
+// bytes per code row staged in LDS by the panel passes: M rounded up to a dword, an odd number of dwords (the rows a lane
+// group reads fall on different banks)
+inline int pq_code_pitch(int M) {
+    const int pitch = (M + 3) & ~3;
+    return (pitch / 4) % 2 == 0 ? pitch + 4 : pitch;
+}
+
+// ---- the flat index ---------------------------------------------------------------------------------------------------------
 PqRows pq_rows(const vdb_index_s *h) {
     PqRows p;
     p.codes = h->codes.pq_codes.as<unsigned char>();
     p.cb = h->kept.pq_cb.as<float>();
-    p.M = h->pq_M;
-    p.dsub = h->pq_dsub;
+    p.M = h->pq.M;
+    p.dsub = h->pq.dsub;
     return p;
 }
 
@@ -20,29 +105,14 @@ void pq_need_codebooks(const vdb_index_s *h, const char *what) {
     if (!pq_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no codebooks (call vdb_pq_train or vdb_pq_set_codebooks first)");
 }
 
-void pq_check_M(const vdb_index_s *h, int M) {
-    if (M < 1 || M > std::min(h->dim, 256)) throw Error(VDB_ERR_INVALID, "M must be in [1, min(dim, 256)]");
-    if (h->dim % M) throw Error(VDB_ERR_INVALID, "dim must be a multiple of M");
-}
-
-void pq_install_codebooks(vdb_index_s *h, int M, const float *cb_host) {
-    const size_t total = (size_t)256 * h->dim;
-    for (size_t i = 0; i < total; ++i)
-        if (!std::isfinite(cb_host[i])) throw Error(VDB_ERR_INVALID, "codebook entries must be finite");
-    graph_reset(h);
-    h->kept.pq_cb.reserve_exact(total * sizeof(float));
-    VDB_HIP(hipMemcpy(h->kept.pq_cb.p, cb_host, total * sizeof(float), hipMemcpyHostToDevice));
-    h->pq_cb_host.assign(cb_host, cb_host + total);
-    h->pq_M = M;
-    h->pq_dsub = h->dim / M;
-}
-
 // x^ of the code rows [r0, r0 + n): float32, `pitch` floats per row (zero beyond dim)
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st) {
     if (n <= 0) return;
     const int64_t blocks = std::min<int64_t>((n * pitch + 255) / 256, 1 << 16);
-    pq_decode_rows_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(h->codes.pq_codes.as<unsigned char>() + (size_t)r0 * h->pq_M,
-                                                                      h->kept.pq_cb.as<float>(), n, h->dim, h->pq_M, h->pq_dsub, pitch, out);
+    IvfPqRows p;
+    p.pq = pq_rows(h);
+    p.pq.codes += (size_t)r0 * p.pq.M;
+    pq_decode_rows_kernel<false><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(p, n, h->dim, h->D4, pitch, out);
     VDB_HIP(hipGetLastError());
 }
 
@@ -113,7 +183,7 @@ void pq_append(vdb_index_s *h, int64_t n, int64_t id_base, F &&fill) {
         if (!h->built) pq_rebuild(h, nullptr);
         return;
     }
-    const size_t M = (size_t)h->pq_M;
+    const size_t M = (size_t)h->pq.M;
     h->codes.pq_codes.grow((size_t)(N0 + n) * M + 16, (size_t)N0 * M);      // (16 spare bytes: the 16-byte code loads of the panel pass)
     fill(h->codes.pq_codes.as<unsigned char>() + (size_t)N0 * M);
     h->N = N0 + n;
@@ -135,19 +205,15 @@ void pq_append(vdb_index_s *h, int64_t n, int64_t id_base, F &&fill) {
 
 // rows (host) -> codes (device), through a float32 block of at most ~256 MiB
 void pq_encode_host_rows(vdb_index_s *h, const float *x_host, int64_t n, unsigned char *codes, hipStream_t st) {
-    const int D = h->dim, D4 = h->D4, M = h->pq_M, dsub = h->pq_dsub;
+    const int D = h->dim, D4 = h->D4, M = h->pq.M;
     const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)256 << 20) / ((int64_t)D4 * 4)));
     DevBuf blk;
     blk.reserve((size_t)block_rows * D4 * sizeof(float));
-    const bool in_lds = (size_t)256 * dsub * sizeof(float) <= 49152;
     for (int64_t r0 = 0; r0 < n; r0 += block_rows) {
         const int64_t nb = std::min<int64_t>(block_rows, n - r0);
         if (D4 != D) VDB_HIP(hipMemsetAsync(blk.p, 0, (size_t)nb * D4 * sizeof(float), st));
         upload_rows(h, blk.as<float>(), D4, x_host + (size_t)r0 * D, nb, D, st);
-        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nb + 255) / 256, 2048));
-        pq_encode_kernel<<<dim3(gx, (unsigned)M), dim3(256), in_lds ? (size_t)256 * dsub * sizeof(float) : 0, st>>>(
-            blk.as<float>(), nb, D4, h->kept.pq_cb.as<float>(), M, dsub, in_lds ? 256 * dsub : 0, codes + (size_t)r0 * M);
-        VDB_HIP(hipGetLastError());
+        pq_launch_encode(blk.as<float>(), nb, D4, nullptr, nullptr, h->kept.pq_cb.as<float>(), M, h->pq.dsub, codes + (size_t)r0 * M, st);
         VDB_HIP(hipStreamSynchronize(st));       // (the block is refilled by the next one)
     }
 }
@@ -167,15 +233,13 @@ void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *pane
     a.tile0 = tile0;
     a.ntiles = ntiles;
     a.D = h->dim;
-    a.M = h->pq_M;
-    a.dsub = h->pq_dsub;
+    a.M = h->pq.M;
+    a.dsub = h->pq.dsub;
     a.p16 = h->tile16 ? 1 : 0;
     a.ksteps = h->tile16 ? h->ksteps / 2 : h->ksteps;
-    int pitch = (a.M + 3) & ~3;
-    if ((pitch / 4) % 2 == 0) pitch += 4;
-    a.code_pitch = pitch;
+    a.code_pitch = pq_code_pitch(a.M);
     const int R = a.p16 ? 16 : 32;
-    const int stage = 4 * ((R * pitch + 15) & ~15);
+    const int stage = 4 * ((R * a.code_pitch + 15) & ~15);
     const int ks32_n = a.p16 ? a.ksteps : a.ksteps / 2;
     const int dsub = a.dsub;
     int unit = dsub;                             // k-steps per slice unit: lcm(32, dsub) / 32
@@ -232,7 +296,8 @@ int vdb_pq_set_codebooks(vdb_handle hh, int M, const float *codebooks_host) {
                                                      std::to_string(h->N) + " rows held would lose their meaning");
         set_device(h->device);
         VDB_HIP(hipDeviceSynchronize());
-        pq_install_codebooks(h, M, codebooks_host);
+        graph_reset(h);
+        pq_install_codebooks(h, h->pq, h->kept.pq_cb, M, codebooks_host);
     });
 }
 
@@ -240,9 +305,7 @@ int vdb_pq_get_codebooks(vdb_handle hh, int *M, float *codebooks_host) {
     return guarded([&] {
         auto *h = check(hh);
         admit(h, "vdb_pq_get_codebooks", kAnyKind);
-        if (!M) throw Error(VDB_ERR_INVALID, "null pointer");
-        *M = h->pq_M;                              // (0 on every other kind)
-        if (codebooks_host && *M > 0) memcpy(codebooks_host, h->pq_cb_host.data(), h->pq_cb_host.size() * sizeof(float));
+        pq_get_codebooks(h->pq, true, M, codebooks_host);       // (pq.M is 0 on every other kind)
     });
 }
 
@@ -252,31 +315,14 @@ int vdb_pq_train(vdb_handle hh, int M, const float *x_host, int64_t n, int niter
         admit(h, "vdb_pq_train", kBecomesPq);
         refuse_options_set(h, "vdb_pq_train", kPq);
         pq_check_M(h, M);
-        if (!x_host || n <= 0) throw Error(VDB_ERR_INVALID, "no training vectors");
-        if (n < 256) throw Error(VDB_ERR_INVALID, "need at least 256 training vectors (one per centroid of a sub-space)");
-        if (niter < 0 || niter > 1000) throw Error(VDB_ERR_INVALID, "niter out of range");
+        pq_check_train_args(x_host, n, niter, max_points_per_centroid);
         if (h->N > 0) throw Error(VDB_ERR_STATE, "the codebooks are trained before rows exist (vdb_reset first)");
-        if (max_points_per_centroid <= 0) max_points_per_centroid = 256;
-        const int D = h->dim, dsub = D / M;
-        // one row sample for every sub-space, drawn with `seed` (vdb_ivf_train's draws)
-        const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * 256);
-        const std::vector<int64_t> pick = sample_rows(n, ns, seed);
-        // sub-space m: the library's k-means (vdb_ivf_train on a flat L2 handle of dsub dims) over the sample, seed + m
-        std::vector<float> cb((size_t)256 * D), sub((size_t)ns * dsub);
-        for (int m = 0; m < M; ++m) {
-            for (int64_t i = 0; i < ns; ++i)
-                memcpy(&sub[(size_t)i * dsub], x_host + (size_t)pick[(size_t)i] * D + (size_t)m * dsub, (size_t)dsub * sizeof(float));
-            vdb_handle t = nullptr;
-            int rc = vdb_create(dsub, VDB_METRIC_L2, h->device, &t);
-            if (rc == VDB_OK) rc = vdb_ivf_train(t, 256, sub.data(), ns, niter, seed + (uint64_t)m, max_points_per_centroid);
-            if (rc == VDB_OK) rc = vdb_ivf_get_centroids(t, &cb[(size_t)m * 256 * dsub]);
-            const std::string msg = rc == VDB_OK ? std::string() : g_last_error;
-            if (t) (void)vdb_destroy(t);
-            if (rc != VDB_OK) throw Error(rc, "k-means of sub-space " + std::to_string(m) + ": " + msg);
-        }
+        const std::vector<float> cb = pq_train_codebooks(h->device, pq_training_sample(x_host, n, h->dim, seed, max_points_per_centroid), h->dim, M,
+                                                         niter, seed, max_points_per_centroid);
         set_device(h->device);
         VDB_HIP(hipDeviceSynchronize());
-        pq_install_codebooks(h, M, cb.data());
+        graph_reset(h);
+        pq_install_codebooks(h, h->pq, h->kept.pq_cb, M, cb.data());
     });
 }
 
@@ -299,7 +345,7 @@ int vdb_pq_add_codes(vdb_handle hh, const uint8_t *codes_host, int64_t n, int64_
         if (n > 0 && !codes_host) throw Error(VDB_ERR_INVALID, "null code pointer");
         set_device(h->device);
         pq_append(h, n, id_base, [&](unsigned char *codes) {
-            VDB_HIP(hipMemcpy(codes, codes_host, (size_t)n * h->pq_M, hipMemcpyHostToDevice));
+            VDB_HIP(hipMemcpy(codes, codes_host, (size_t)n * h->pq.M, hipMemcpyHostToDevice));
         });
     });
 }
@@ -313,7 +359,7 @@ int vdb_pq_get_codes(vdb_handle hh, uint8_t *codes_host) {
         if (!codes_host) throw Error(VDB_ERR_INVALID, "null pointer");
         set_device(h->device);
         VDB_HIP(hipDeviceSynchronize());
-        VDB_HIP(hipMemcpy(codes_host, h->codes.pq_codes.p, (size_t)h->N * h->pq_M, hipMemcpyDeviceToHost));
+        VDB_HIP(hipMemcpy(codes_host, h->codes.pq_codes.p, (size_t)h->N * h->pq.M, hipMemcpyDeviceToHost));
     });
 }
 

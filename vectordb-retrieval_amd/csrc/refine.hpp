@@ -32,14 +32,13 @@ struct PqRows {
     int M = 0, dsub = 0;
 };
 
-// the rows of an IVF<nlist>,PQ<M> index (ivf_pq.hpp, include/vdbhip.h): codes [N][M] in list order, the list of every list-order
-// row, centroids [nlist][D4] zero padded, codebooks float32 [M][256][dsub] of the residuals; x^[d] = c_l[d] + codebook entry
+// the rows of an IVF<nlist>,PQ<M> index (ivf_pq.hpp, include/vdbhip.h): the list of every list-order row, the centroids
+// [nlist][D4] zero padded, and the product codes of the residuals, [N][M] in list order; x^[d] = c_l[d] + codebook entry.
+// (`pq` last: cb, M and dsub then sit where the kernels of this file have always read them, and their registers do not move.)
 struct IvfPqRows {
-    const unsigned char *codes = nullptr;
     const int32_t *list = nullptr;
     const float *cent = nullptr;
-    const float *cb = nullptr;
-    int M = 0, dsub = 0;
+    PqRows pq{};
 };
 
 struct RefineCommon {
@@ -167,17 +166,22 @@ __device__ __forceinline__ uint64_t sq8_key(const Sq8Rows &s, int64_t row, const
     return sortable_u64(metric == 0 ? acc : -acc);
 }
 
-// The same key from the codes of a PQ index: x^[m dsub + j] = cb[m][code[m]][j] (no arithmetic), then the identical float64
-// chain over the D4 padded dimensions (a padding step is fma(0, 0, acc), as on the zero-padded float32 row) -- the key of
+// The same key from the codes of a product quantizer: x^[m dsub + j] = cb[m][code[m]][j] (PQ: a lookup, no arithmetic), or
+// (RESIDUAL, IVF-PQ) cl[m dsub + j] + cb[m][code[m]][j] with cl = cent[list[row]], the centroid of the row's list -- ONE float32 add, as
+// pq_decode_rows_kernel and the IVF-PQ panel pass make it -- then the identical float64 chain over the D4 padded dimensions
+// (a padding dimension decodes to exactly 0: its step is fma(0, 0, acc), as on the zero-padded float32 row) -- the key of
 // the float32 row x^.
-__device__ __forceinline__ uint64_t pq_key(const PqRows &p, int64_t row, const float *__restrict__ q, int D4, int metric) {
+template <bool RESIDUAL>
+__device__ __forceinline__ uint64_t pq_key_body(const PqRows &p, const int32_t *__restrict__ list, const float *__restrict__ cent,
+                                                int64_t row, const float *__restrict__ q, int D4, int metric) {
     const unsigned char *cr = p.codes + (size_t)row * p.M;
+    const float *cl = RESIDUAL ? cent + (size_t)list[row] * D4 : nullptr;
     double acc = 0.0;
     int d = 0;
     for (int m = 0; m < p.M; ++m) {
         const float *cv = p.cb + ((size_t)m * 256 + cr[m]) * p.dsub;
         for (int j = 0; j < p.dsub; ++j, ++d) {
-            const double x = (double)cv[j];
+            const double x = RESIDUAL ? (double)(cl[d] + cv[j]) : (double)cv[j];
             if (metric == 0) {
                 const double t = x - (double)q[d];
                 acc = fma(t, t, acc);
@@ -196,36 +200,11 @@ __device__ __forceinline__ uint64_t pq_key(const PqRows &p, int64_t row, const f
     }
     return sortable_u64(metric == 0 ? acc : -acc);
 }
-
-// The same key from the codes of an IVF-PQ index: x^[m dsub + j] = c_l[m dsub + j] + cb[m][code[m]][j] (ONE float32 add, as
-// ivfpq_decode_rows_kernel and the panel pass make it), then the identical float64 chain over the D4 padded dimensions (a
-// padding dimension decodes to exactly 0, as in pq_key) -- the key of the float32 row x^.
+__device__ __forceinline__ uint64_t pq_key(const PqRows &p, int64_t row, const float *__restrict__ q, int D4, int metric) {
+    return pq_key_body<false>(p, nullptr, nullptr, row, q, D4, metric);
+}
 __device__ __forceinline__ uint64_t ivfpq_key(const IvfPqRows &p, int64_t row, const float *__restrict__ q, int D4, int metric) {
-    const unsigned char *cr = p.codes + (size_t)row * p.M;
-    const float *cl = p.cent + (size_t)p.list[row] * D4;
-    double acc = 0.0;
-    int d = 0;
-    for (int m = 0; m < p.M; ++m) {
-        const float *cv = p.cb + ((size_t)m * 256 + cr[m]) * p.dsub;
-        for (int j = 0; j < p.dsub; ++j, ++d) {
-            const double x = (double)(cl[d] + cv[j]);
-            if (metric == 0) {
-                const double t = x - (double)q[d];
-                acc = fma(t, t, acc);
-            } else {
-                acc = fma((double)q[d], x, acc);
-            }
-        }
-    }
-    for (; d < D4; ++d) {
-        if (metric == 0) {
-            const double t = 0.0 - (double)q[d];
-            acc = fma(t, t, acc);
-        } else {
-            acc = fma((double)q[d], 0.0, acc);
-        }
-    }
-    return sortable_u64(metric == 0 ? acc : -acc);
+    return pq_key_body<true>(p.pq, p.list, p.cent, row, q, D4, metric);
 }
 
 // key of corpus row `row`: from the float32 rows, or (c.X == nullptr) from the SQ8 / PQ / IVF-PQ codes or the int8 row copy (int8-only index)
@@ -234,7 +213,7 @@ __device__ __forceinline__ uint64_t row_key(const RefineCommon &c, int64_t row, 
     if (c.X) return exact_key<U>(c.X + (size_t)row * c.D4, q, c.D4, c.metric);
     if (c.sq8.codes) return sq8_key(c.sq8, row, q, c.D4, c.metric);
     if (c.pq.codes) return pq_key(c.pq, row, q, c.D4, c.metric);
-    if (c.ivfpq.codes) return ivfpq_key(c.ivfpq, row, q, c.D4, c.metric);
+    if (c.ivfpq.pq.codes) return ivfpq_key(c.ivfpq, row, q, c.D4, c.metric);
     return exact_key_i8<U>(c.X8 + (size_t)row * c.x8_pitch, c.cx, q, c.D4, c.metric);
 }
 

@@ -296,6 +296,13 @@ struct Options {
 
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
 
+// The host side of one set of product-quantizer codebooks (pq.inc): a handle keeps two, those of a flat PQ<M> index and
+// those of the residuals of an IVF<nlist>,PQ<M> index.  The device copy sits in the `kept` group.
+struct PqCodebooks {
+    int M = 0, dsub = 0;                     // sub-spaces (0 = no codebooks) and dims of each
+    std::vector<float> host;                 // host copy [M][256][dsub]
+};
+
 inline QueryBatchInfo *batch_info(Workspace &ws) {        // inside ws.small (common.hpp, kInfoOffset)
     return reinterpret_cast<QueryBatchInfo *>(ws.small.as<char>() + kInfoOffset);
 }
@@ -383,8 +390,7 @@ struct vdb_index_s {
     int ivf_codec = 0;
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
-    int ivfpq_M = 0, ivfpq_dsub = 0;         // IVF-PQ: sub-spaces (0 = no codebooks yet) and dims of each -- NOT pq_M: that marks a flat PQ handle
-    std::vector<float> ivfpq_cb_host;        // host copy of the codebooks [M][256][dsub]
+    PqCodebooks ivfpq;                       // IVF-PQ: the codebooks of the residuals (M = 0: none yet) -- NOT `pq`: that marks a flat PQ handle
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
@@ -397,8 +403,7 @@ struct vdb_index_s {
     std::vector<float> lsht_proj, lsht_off;  // host copies [T][H][dim], [T][H]
     // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
-    int pq_M = 0, pq_dsub = 0;               // sub-spaces (0 = not a PQ index) and dims of each
-    std::vector<float> pq_cb_host;           // host copy of the codebooks [M][256][dsub]
+    PqCodebooks pq;                          // (M = 0: not a PQ index)
     // k-NN graph of a flat index (knng.inc; vdb_knng_build / vdb_knng_set): ntotal x degree local row numbers next to the float32 rows
     int knng_degree = 0;                     // 0 = no graph (any add and vdb_reset drop it)
     std::vector<int32_t> knng_entries;       // the entry rows knng_ws.knng_entry holds (knng_search_impl)
@@ -438,7 +443,7 @@ constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
 unsigned kind_of(const vdb_index_s *h) {
     if (h->multi) return kMulti;             // (nlist / ivf_built of such a handle describe the whole index)
     const unsigned ivf = h->ivf_codec == 2 ? kIvfPq : h->ivf_codec == 1 ? kIvfSq8 : (h->nlist > 0 || h->coarse || h->ivf_built) ? kIvfFlat : 0;
-    const unsigned k = (h->pq_M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0) | (h->lsht_T > 0 ? kLsht : 0);
+    const unsigned k = (h->pq.M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0) | (h->lsht_T > 0 ? kLsht : 0);
     if (k & (k - 1)) throw Error(VDB_ERR_STATE, "internal: handle is two kinds at once");
     return k ? k : kFlat;
 }
@@ -576,7 +581,7 @@ long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
 void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st);       // lsh_tables.inc: table keys of the rows an add appended
-inline bool pq_on(const vdb_index_s *h) { return h->pq_M > 0; }
+inline bool pq_on(const vdb_index_s *h) { return h->pq.M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc

@@ -20,7 +20,7 @@ from typing import Any, Optional, Tuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, persist
 from .index import _Handle, normalize_devices
 from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
 from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
@@ -248,10 +248,7 @@ class HipApproximateSearch(BaseAlgorithm):
     def get_memory_usage(self) -> float:
         return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
-    # ---- persistence through the BaseAlgorithm hook (base_algorithm.py:98-120) ---------------------------
-    # Layout and protocol follow the reference's only implementation (covertree_v2_2.py:101-182, 184-282):
-    # temp dir + manifest.json + WRITE_COMPLETE sentinel written last + atomic rename; load refuses an
-    # incomplete artifact or a manifest that does not match this instance.
+    # ---- persistence through the BaseAlgorithm hook (base_algorithm.py:98-120), by the protocol of persist.py ---------------
     # An SQ8 artifact stores the corpus, centroids and lists like a Flat one plus the ranges (ranges.npy: vmin, vdiff), under
     # its own format string: it never reloads as IVF-Flat, and loading re-encodes the stored rows under the stored lists
     # (encoding is deterministic: the codes come back bit-identical).
@@ -262,86 +259,34 @@ class HipApproximateSearch(BaseAlgorithm):
         return self._FORMAT_SQ8 if parse_index_key(self.index_type)[1] == "SQ8" else self._FORMAT
 
     def save_index(self, artifact_dir: str, context=None):
-        import json
-        import shutil
-        import tempfile
-        from pathlib import Path
-
         if not self.index_built or self.index is None:
             raise RuntimeError("Cannot persist HipApproximateSearch before build_index has completed.")
-        context = context or {}
-        target = Path(artifact_dir)
-        target.parent.mkdir(parents=True, exist_ok=True)
-        if target.exists():
-            if not bool(context.get("force_rebuild", False)):
-                raise FileExistsError(f"Artifact directory already exists: {target}. "
-                                      "Set persistence.force_rebuild=true to overwrite.")
-            shutil.rmtree(target)
-        tmp = Path(tempfile.mkdtemp(prefix=f".{target.name}.tmp.", dir=str(target.parent)))
-        try:
-            centroids, lists = self.index.centroids(), self.index.assignment()
-            np.save(tmp / "vectors.npy", self.vectors, allow_pickle=False)
-            np.save(tmp / "centroids.npy", centroids, allow_pickle=False)
-            np.save(tmp / "list_of_row.npy", lists, allow_pickle=False)
-            build_metrics = dict(context.get("build_metrics", {}))
-            manifest = {"format": self._format(), "algorithm": type(self).__name__, "dimension": self.dimension,
-                        "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist,
-                        "nprobe": self.index.nprobe, "n_vectors": int(self.index.ntotal),
-                        "config_hash": context.get("config_hash"),
-                        "sha256": _fingerprint(self.vectors, centroids, lists),
-                        "files": {"vectors": "vectors.npy", "centroids": "centroids.npy",
-                                  "list_of_row": "list_of_row.npy"}}
-            if isinstance(self.index, IVFSQ8Index):
-                import hashlib
-
-                ranges = np.stack(self.index.ranges())
-                np.save(tmp / "ranges.npy", ranges, allow_pickle=False)
-                manifest["files"]["ranges"] = "ranges.npy"
-                manifest["sha256"]["ranges"] = hashlib.sha256(ranges.tobytes()).hexdigest()
-            (tmp / "manifest.json").write_text(json.dumps(manifest, indent=2), encoding="utf-8")
-            (tmp / "build_metrics.json").write_text(json.dumps(build_metrics, indent=2), encoding="utf-8")
-            (tmp / "WRITE_COMPLETE").write_text("ok\n", encoding="utf-8")
-            tmp.rename(target)
-        except Exception:
-            shutil.rmtree(tmp, ignore_errors=True)
-            raise
-        return {"artifact_dir": str(target), "manifest_path": str(target / "manifest.json"),
-                "build_time_s": float(build_metrics.get("build_time_s", 0.0) or 0.0)}
+        manifest = {"format": self._format(), "algorithm": type(self).__name__, "dimension": self.dimension,
+                    "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist,
+                    "nprobe": self.index.nprobe, "n_vectors": int(self.index.ntotal)}
+        arrays = {"vectors": self.vectors, "centroids": self.index.centroids(), "list_of_row": self.index.assignment()}
+        fingerprint = _fingerprint(*arrays.values())
+        if isinstance(self.index, IVFSQ8Index):
+            arrays["ranges"] = np.stack(self.index.ranges())
+            fingerprint["ranges"] = persist.sha256(arrays["ranges"])
+        return persist.write_artifact(artifact_dir, context, manifest, arrays, fingerprint)
 
     def load_index(self, artifact_dir: str, context=None):
-        import json
-        from pathlib import Path
-
-        path = Path(artifact_dir)
-        if not path.is_dir():
-            raise FileNotFoundError(f"Persisted HipApproximateSearch artifact directory not found: {path}")
-        if not (path / "WRITE_COMPLETE").is_file():
-            raise FileNotFoundError(f"Artifact is incomplete or corrupted (missing WRITE_COMPLETE): {path}")
-        manifest = json.loads((path / "manifest.json").read_text(encoding="utf-8"))
-        for key, want in (("format", self._format()), ("dimension", self.dimension), ("index_type", self.index_type),
-                          ("metric", self.metric)):
-            if manifest.get(key) != want:
-                raise ValueError(f"Persisted index mismatch for '{key}': artifact has {manifest.get(key)!r}, "
-                                 f"this instance expects {want!r}")
-        expected_hash = (context or {}).get("config_hash")
-        if expected_hash and manifest.get("config_hash") and manifest["config_hash"] != expected_hash:
-            raise ValueError("Persisted index was built with a different configuration (config_hash mismatch)")
-        vectors = np.load(path / manifest["files"]["vectors"], mmap_mode="r")
-        centroids = np.load(path / manifest["files"]["centroids"])
+        manifest, load, result = persist.read_artifact(artifact_dir, context, "HipApproximateSearch", format=self._format(),
+                                                       dimension=self.dimension, index_type=self.index_type, metric=self.metric)
+        vectors = load("vectors", mmap_mode="r")
+        centroids = load("centroids")
         self.vectors = vectors
         sq8 = manifest["format"] == self._FORMAT_SQ8
         self.index = (IVFSQ8Index if sq8 else IVFFlatIndex)(self.dimension, int(manifest["nlist"]), self.metric, self.device)
         self.index.set_centroids(centroids)       # no k-means: the stored quantizer is reused ...
         if sq8:                                   # ... and so are the stored ranges
-            import hashlib
-
-            ranges = np.load(path / manifest["files"]["ranges"])
+            ranges = load("ranges")
             want_ranges = (manifest.get("sha256") or {}).get("ranges")
-            if ranges.shape != (2, self.dimension) or (
-                    want_ranges and hashlib.sha256(np.ascontiguousarray(ranges, np.float32).tobytes()).hexdigest() != want_ranges):
+            if ranges.shape != (2, self.dimension) or (want_ranges and persist.sha256(np.asarray(ranges, np.float32)) != want_ranges):
                 raise ValueError("Persisted SQ8 ranges do not belong to this artifact")
             self.index.set_ranges(ranges[0], ranges[1])
-        stored = np.load(path / manifest["files"]["list_of_row"])
+        stored = load("list_of_row")
         if stored.shape != (vectors.shape[0],) or (len(stored) and (stored.min() < 0 or stored.max() >= int(manifest["nlist"]))):
             raise ValueError("Persisted inverted lists do not match the persisted corpus")
         # the three files must be the ones that were written together: a corpus or quantizer that does not belong to the
@@ -357,12 +302,7 @@ class HipApproximateSearch(BaseAlgorithm):
         self.index.add(vectors, list_of_row=stored)   # ... and so are the stored lists: no assignment pass either
         self.index.set_nprobe(int(self.config.get("nprobe", manifest.get("nprobe", 1))))
         self.index_built = True
-        metrics = {}
-        bm = path / "build_metrics.json"
-        if bm.is_file():
-            metrics = json.loads(bm.read_text(encoding="utf-8"))
-        return {"artifact_dir": str(path), "manifest_path": str(path / "manifest.json"),
-                "build_time_s": float(metrics.get("build_time_s", 0.0) or 0.0)}
+        return result
 
 
 class HipIVFIndexer(BaseIndexer):

@@ -17,16 +17,16 @@ HipPQSearch) keep refusing these keys: the codec lives behind the names of this 
 """
 from __future__ import annotations
 
-import ctypes
 import re
 from typing import Any, Optional, Tuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, persist
 from .index import normalize_devices
 from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
 from .ivf import IVFFlatIndex
+from .pq import PQCodec, check_m
 from .plugin_api import (BaseAlgorithm, BaseIndexer, IndexArtifact, Metadata, SearchResult, register_algorithm,
                          register_indexer)
 
@@ -43,20 +43,17 @@ def parse_ivfpq_key(key: str) -> Tuple[int, int]:
     return int(m.group(1)), int(m.group(2))
 
 
-def _check_m(dim: int, M: int) -> None:
-    if M < 1 or M > min(dim, 256) or dim % M:
-        raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
-
-
-class IVFPQIndex(IVFFlatIndex):
+class IVFPQIndex(PQCodec, IVFFlatIndex):
     """Device-resident IVF<nlist>,PQ<M> index (replaces faiss.index_factory(d, "IVFn,PQm", metric)).  `train` fits the
     centroids and then the codebooks of the residuals on the same rows; `set_centroids` + `train_codebooks` /
     `set_codebooks` inject them instead.  One GPU only."""
 
+    _pq_prefix = "vdb_ivfpq_"
+
     def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0):
         if isinstance(normalize_devices(device), list):
             raise ValueError(_ONE_GPU)
-        _check_m(int(dim), int(M))
+        check_m(int(dim), int(M))
         super().__init__(dim, nlist, metric, device)
         self.M, self.dsub = int(M), int(dim) // int(M)
         _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 2), build_time=True)
@@ -75,20 +72,8 @@ class IVFPQIndex(IVFFlatIndex):
         self.ntotal = 0             # (new codebooks: rows encoded under the old ones are dropped)
 
     def set_codebooks(self, codebooks: np.ndarray) -> None:
-        c = _ffi.as_f32_c(codebooks)
-        if c.shape != (self.M, 256, self.dsub):
-            raise ValueError(f"expected ({self.M}, 256, {self.dsub}) codebooks, got {c.shape}")
-        _ffi.check(self._lib.vdb_ivfpq_set_codebooks(self._handle(), self.M, _ffi.ptr(c)), build_time=True)
+        super().set_codebooks(codebooks)
         self.ntotal = 0
-
-    def codebooks(self) -> np.ndarray:
-        m = ctypes.c_int(0)
-        _ffi.check(self._lib.vdb_ivfpq_get_codebooks(self._handle(), ctypes.byref(m), None))
-        if m.value != self.M:
-            raise RuntimeError("no codebooks: train the index or set them first")
-        out = np.empty((self.M, 256, self.dsub), np.float32)
-        _ffi.check(self._lib.vdb_ivfpq_get_codebooks(self._handle(), ctypes.byref(m), _ffi.ptr(out)))
-        return out
 
     def add_codes(self, codes: np.ndarray, list_of_row: np.ndarray, id_base: int = 0) -> None:
         """Append rows given as codes, uint8 (n, M), under the given lists: what loading a persisted index does."""
@@ -104,17 +89,9 @@ class IVFPQIndex(IVFFlatIndex):
         finally:
             self.ntotal = int(self.stats()["ntotal"])
 
-    def codes(self) -> np.ndarray:
-        """uint8 (ntotal, M) codes in id (insertion) order."""
-        out = np.empty((self.ntotal, self.M), np.uint8)
-        _ffi.check(self._lib.vdb_ivfpq_get_codes(self._handle(), _ffi.ptr(out)))
-        return out
-
     def reconstruct(self) -> np.ndarray:
         """float32 (ntotal, dim) rows x^ in id order: centroid of the row's list + codebook entries, one float32 add."""
-        codes, cb, cent, lor = self.codes(), self.codebooks(), self.centroids(), self.assignment()
-        look = np.concatenate([cb[m][codes[:, m]] for m in range(self.M)], axis=1).astype(np.float32)
-        return np.ascontiguousarray(cent[lor] + look, dtype=np.float32)
+        return np.ascontiguousarray(self.centroids()[self.assignment()] + self.lookup(self.codes()), dtype=np.float32)
 
 
 def _build_ivfpq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> IVFPQIndex:
@@ -206,95 +183,40 @@ class HipIVFPQSearch(BaseAlgorithm):
     def get_memory_usage(self) -> float:
         return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
-    # ---- persistence (protocol of HipApproximateSearch: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ----------
+    # ---- persistence (persist.py: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ------------------------------------
     # An IVF-PQ artifact is the index itself: centroids, codebooks, codes and the list of every row.  No corpus file -- the
     # index holds no float32 rows -- and loading neither clusters nor encodes.
     _FILES = ("centroids", "codebooks", "codes", "list_of_row")
 
     def save_index(self, artifact_dir: str, context=None):
-        import hashlib
-        import json
-        import shutil
-        import tempfile
-        from pathlib import Path
-
         if not self.index_built or self.index is None:
             raise RuntimeError("Cannot persist HipIVFPQSearch before build_index has completed.")
-        context = context or {}
-        target = Path(artifact_dir)
-        target.parent.mkdir(parents=True, exist_ok=True)
-        if target.exists():
-            if not bool(context.get("force_rebuild", False)):
-                raise FileExistsError(f"Artifact directory already exists: {target}. "
-                                      "Set persistence.force_rebuild=true to overwrite.")
-            shutil.rmtree(target)
-        tmp = Path(tempfile.mkdtemp(prefix=f".{target.name}.tmp.", dir=str(target.parent)))
-        try:
-            arrays = {"centroids": self.index.centroids(), "codebooks": self.index.codebooks(), "codes": self.index.codes(),
-                      "list_of_row": self.index.assignment()}
-            for name, arr in arrays.items():
-                np.save(tmp / f"{name}.npy", arr, allow_pickle=False)
-            build_metrics = dict(context.get("build_metrics", {}))
-            manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
-                        "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist, "M": self.index.M,
-                        "nprobe": self.index.nprobe, "id_base": 0, "n_vectors": int(self.index.ntotal),
-                        "config_hash": context.get("config_hash"),
-                        "sha256": {name: hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest()
-                                   for name, arr in arrays.items()},
-                        "files": {name: f"{name}.npy" for name in arrays}}
-            (tmp / "manifest.json").write_text(json.dumps(manifest, indent=2), encoding="utf-8")
-            (tmp / "build_metrics.json").write_text(json.dumps(build_metrics, indent=2), encoding="utf-8")
-            (tmp / "WRITE_COMPLETE").write_text("ok\n", encoding="utf-8")
-            tmp.rename(target)
-        except Exception:
-            shutil.rmtree(tmp, ignore_errors=True)
-            raise
-        return {"artifact_dir": str(target), "manifest_path": str(target / "manifest.json"),
-                "build_time_s": float(build_metrics.get("build_time_s", 0.0) or 0.0)}
+        manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
+                    "index_type": self.index_type, "metric": self.metric, "nlist": self.index.nlist, "M": self.index.M,
+                    "nprobe": self.index.nprobe, "id_base": 0, "n_vectors": int(self.index.ntotal)}
+        arrays = {"centroids": self.index.centroids(), "codebooks": self.index.codebooks(), "codes": self.index.codes(),
+                  "list_of_row": self.index.assignment()}
+        return persist.write_artifact(artifact_dir, context, manifest, arrays)
 
     def load_index(self, artifact_dir: str, context=None):
-        import hashlib
-        import json
-        from pathlib import Path
-
-        path = Path(artifact_dir)
-        if not path.is_dir():
-            raise FileNotFoundError(f"Persisted HipIVFPQSearch artifact directory not found: {path}")
-        if not (path / "WRITE_COMPLETE").is_file():
-            raise FileNotFoundError(f"Artifact is incomplete or corrupted (missing WRITE_COMPLETE): {path}")
-        manifest = json.loads((path / "manifest.json").read_text(encoding="utf-8"))
-        for key, want in (("format", self._FORMAT), ("dimension", self.dimension), ("index_type", self.index_type),
-                          ("metric", self.metric)):
-            if manifest.get(key) != want:
-                raise ValueError(f"Persisted index mismatch for '{key}': artifact has {manifest.get(key)!r}, "
-                                 f"this instance expects {want!r}")
-        expected_hash = (context or {}).get("config_hash")
-        if expected_hash and manifest.get("config_hash") and manifest["config_hash"] != expected_hash:
-            raise ValueError("Persisted index was built with a different configuration (config_hash mismatch)")
+        manifest, load, result = persist.read_artifact(artifact_dir, context, "HipIVFPQSearch", format=self._FORMAT,
+                                                       dimension=self.dimension, index_type=self.index_type, metric=self.metric)
         nlist, m = parse_ivfpq_key(self.index_type)
-        arrays = {name: np.load(path / manifest["files"][name]) for name in self._FILES}
+        arrays = {name: load(name) for name in self._FILES}
         n = int(manifest.get("n_vectors", arrays["codes"].shape[0]))
         lists = arrays["list_of_row"]
         if arrays["centroids"].shape != (nlist, self.dimension) or arrays["codebooks"].shape != (m, 256, self.dimension // m) \
                 or arrays["codes"].shape != (n, m) or arrays["codes"].dtype != np.uint8 or lists.shape != (n,) \
                 or (n and (lists.min() < 0 or lists.max() >= nlist)):
             raise ValueError("Persisted IVF-PQ files do not match the manifest")
-        want = manifest.get("sha256") or {}
-        for name in self._FILES:
-            if want.get(name) and hashlib.sha256(np.ascontiguousarray(arrays[name]).tobytes()).hexdigest() != want[name]:
-                raise ValueError(f"Persisted index files do not belong together (fingerprint mismatch: {name})")
+        persist.check_sha256(manifest, arrays)
         self.index = IVFPQIndex(self.dimension, nlist, m, self.metric, self.device)
         self.index.set_centroids(arrays["centroids"])      # no k-means, no assignment and no encoding pass: the stored
         self.index.set_codebooks(arrays["codebooks"])      # index is reused as it is
         self.index.add_codes(arrays["codes"], lists, id_base=int(manifest.get("id_base", 0)))
         self.index.set_nprobe(int(self.config.get("nprobe", manifest.get("nprobe", 1))))
         self.index_built = True
-        metrics = {}
-        bm = path / "build_metrics.json"
-        if bm.is_file():
-            metrics = json.loads(bm.read_text(encoding="utf-8"))
-        return {"artifact_dir": str(path), "manifest_path": str(path / "manifest.json"),
-                "build_time_s": float(metrics.get("build_time_s", 0.0) or 0.0)}
+        return result
 
 
 register_algorithm("HipIVFPQSearch", HipIVFPQSearch)

@@ -18,7 +18,7 @@ from typing import Any, Optional, Tuple
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, persist
 from .index import _Handle, normalize_devices
 from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
 from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
@@ -35,7 +35,48 @@ def parse_pq_key(key: str) -> int:
     return int(m.group(1))
 
 
-class PQIndex(_Handle):
+def check_m(dim: int, M: int) -> None:
+    if M < 1 or M > min(dim, 256) or dim % M:
+        raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
+
+
+class PQCodec:
+    """What PQIndex and ivf_pq.IVFPQIndex share: the codebooks and codes of a product quantizer (self.M, self.dsub) behind
+    the entry points `_pq_prefix` + set_codebooks / get_codebooks / get_codes."""
+
+    _pq_prefix = "vdb_pq_"
+
+    def _pq_call(self, name: str):
+        return getattr(self._lib, self._pq_prefix + name)
+
+    def set_codebooks(self, codebooks: np.ndarray) -> None:
+        c = _ffi.as_f32_c(codebooks)
+        if c.shape != (self.M, 256, self.dsub):
+            raise ValueError(f"expected ({self.M}, 256, {self.dsub}) codebooks, got {c.shape}")
+        _ffi.check(self._pq_call("set_codebooks")(self._handle(), self.M, _ffi.ptr(c)), build_time=True)
+
+    def codebooks(self) -> np.ndarray:
+        m = ctypes.c_int(0)
+        _ffi.check(self._pq_call("get_codebooks")(self._handle(), ctypes.byref(m), None))
+        if m.value != self.M:
+            raise RuntimeError("no codebooks: train the index or set them first")
+        out = np.empty((self.M, 256, self.dsub), np.float32)
+        _ffi.check(self._pq_call("get_codebooks")(self._handle(), ctypes.byref(m), _ffi.ptr(out)))
+        return out
+
+    def codes(self) -> np.ndarray:
+        """uint8 (ntotal, M) codes in id (insertion) order."""
+        out = np.empty((self.ntotal, self.M), np.uint8)
+        _ffi.check(self._pq_call("get_codes")(self._handle(), _ffi.ptr(out)))
+        return out
+
+    def lookup(self, codes: np.ndarray) -> np.ndarray:
+        """float32 (n, dim): codebook[m][code[m]] side by side -- what reconstruct() starts from."""
+        cb = self.codebooks()
+        return np.ascontiguousarray(np.concatenate([cb[m][codes[:, m]] for m in range(self.M)], axis=1), dtype=np.float32)
+
+
+class PQIndex(PQCodec, _Handle):
     """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only."""
 
     def __init__(self, dim: int, M: int, metric: str = "l2", device=0):
@@ -45,8 +86,7 @@ class PQIndex(_Handle):
         if isinstance(device, list):
             raise ValueError("PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available")
         dim, M = int(dim), int(M)
-        if M < 1 or M > min(dim, 256) or dim % M:
-            raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
+        check_m(dim, M)
         self.dim, self.M, self.dsub, self.metric, self.device = dim, M, dim // M, metric, device
         super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
         self.is_trained = False
@@ -65,20 +105,8 @@ class PQIndex(_Handle):
         self.is_trained = True
 
     def set_codebooks(self, codebooks: np.ndarray) -> None:
-        c = _ffi.as_f32_c(codebooks)
-        if c.shape != (self.M, 256, self.dsub):
-            raise ValueError(f"expected ({self.M}, 256, {self.dsub}) codebooks, got {c.shape}")
-        _ffi.check(self._lib.vdb_pq_set_codebooks(self._handle(), self.M, _ffi.ptr(c)), build_time=True)
+        super().set_codebooks(codebooks)
         self.is_trained = True
-
-    def codebooks(self) -> np.ndarray:
-        m = ctypes.c_int(0)
-        out = np.empty((self.M, 256, self.dsub), np.float32)
-        _ffi.check(self._lib.vdb_pq_get_codebooks(self._handle(), ctypes.byref(m), None))
-        if m.value != self.M:
-            raise RuntimeError("no codebooks: train the index or set them first")
-        _ffi.check(self._lib.vdb_pq_get_codebooks(self._handle(), ctypes.byref(m), _ffi.ptr(out)))
-        return out
 
     # -- rows -----------------------------------------------------------------------------------------------
     def add(self, x: np.ndarray, id_base: int = 0) -> None:
@@ -101,17 +129,9 @@ class PQIndex(_Handle):
         finally:
             self._sync_ntotal()
 
-    def codes(self) -> np.ndarray:
-        """uint8 (ntotal, M) codes in id (insertion) order."""
-        out = np.empty((self.ntotal, self.M), np.uint8)
-        _ffi.check(self._lib.vdb_pq_get_codes(self._handle(), _ffi.ptr(out)))
-        return out
-
     def reconstruct(self, codes: Optional[np.ndarray] = None) -> np.ndarray:
         """float32 (n, dim) rows x^ of `codes` (default: every indexed row): codebook[m][code[m]] side by side, a lookup."""
-        c = self.codes() if codes is None else np.asarray(codes, dtype=np.uint8)
-        cb = self.codebooks()
-        return np.ascontiguousarray(np.concatenate([cb[m][c[:, m]] for m in range(self.M)], axis=1), dtype=np.float32)
+        return self.lookup(self.codes() if codes is None else np.asarray(codes, dtype=np.uint8))
 
     def reset(self) -> None:
         """Drop every row; the codebooks stay (faiss.IndexPQ.reset)."""
@@ -268,87 +288,32 @@ class HipPQSearch(BaseAlgorithm):
     def get_memory_usage(self) -> float:
         return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
-    # ---- persistence (protocol of HipApproximateSearch: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ----------
+    # ---- persistence (persist.py: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ------------------------------------
     # A PQ artifact is the index itself: codebooks, codes and id_base.  No corpus file -- the index holds no float32 rows.
     def save_index(self, artifact_dir: str, context=None):
-        import hashlib
-        import json
-        import shutil
-        import tempfile
-        from pathlib import Path
-
         if not self.index_built or self.index is None:
             raise RuntimeError("Cannot persist HipPQSearch before build_index has completed.")
-        context = context or {}
-        target = Path(artifact_dir)
-        target.parent.mkdir(parents=True, exist_ok=True)
-        if target.exists():
-            if not bool(context.get("force_rebuild", False)):
-                raise FileExistsError(f"Artifact directory already exists: {target}. "
-                                      "Set persistence.force_rebuild=true to overwrite.")
-            shutil.rmtree(target)
-        tmp = Path(tempfile.mkdtemp(prefix=f".{target.name}.tmp.", dir=str(target.parent)))
-        try:
-            codebooks, codes = self.index.codebooks(), self.index.codes()
-            np.save(tmp / "codebooks.npy", codebooks, allow_pickle=False)
-            np.save(tmp / "codes.npy", codes, allow_pickle=False)
-            build_metrics = dict(context.get("build_metrics", {}))
-            manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
-                        "index_type": self.index_type, "metric": self.metric, "M": self.index.M, "id_base": 0,
-                        "n_vectors": int(self.index.ntotal), "config_hash": context.get("config_hash"),
-                        "sha256": {"codebooks": hashlib.sha256(codebooks.tobytes()).hexdigest(),
-                                   "codes": hashlib.sha256(codes.tobytes()).hexdigest()},
-                        "files": {"codebooks": "codebooks.npy", "codes": "codes.npy"}}
-            (tmp / "manifest.json").write_text(json.dumps(manifest, indent=2), encoding="utf-8")
-            (tmp / "build_metrics.json").write_text(json.dumps(build_metrics, indent=2), encoding="utf-8")
-            (tmp / "WRITE_COMPLETE").write_text("ok\n", encoding="utf-8")
-            tmp.rename(target)
-        except Exception:
-            shutil.rmtree(tmp, ignore_errors=True)
-            raise
-        return {"artifact_dir": str(target), "manifest_path": str(target / "manifest.json"),
-                "build_time_s": float(build_metrics.get("build_time_s", 0.0) or 0.0)}
+        manifest = {"format": self._FORMAT, "algorithm": type(self).__name__, "dimension": self.dimension,
+                    "index_type": self.index_type, "metric": self.metric, "M": self.index.M, "id_base": 0,
+                    "n_vectors": int(self.index.ntotal)}
+        return persist.write_artifact(artifact_dir, context, manifest,
+                                      {"codebooks": self.index.codebooks(), "codes": self.index.codes()})
 
     def load_index(self, artifact_dir: str, context=None):
-        import hashlib
-        import json
-        from pathlib import Path
-
-        path = Path(artifact_dir)
-        if not path.is_dir():
-            raise FileNotFoundError(f"Persisted HipPQSearch artifact directory not found: {path}")
-        if not (path / "WRITE_COMPLETE").is_file():
-            raise FileNotFoundError(f"Artifact is incomplete or corrupted (missing WRITE_COMPLETE): {path}")
-        manifest = json.loads((path / "manifest.json").read_text(encoding="utf-8"))
-        for key, want in (("format", self._FORMAT), ("dimension", self.dimension), ("index_type", self.index_type),
-                          ("metric", self.metric)):
-            if manifest.get(key) != want:
-                raise ValueError(f"Persisted index mismatch for '{key}': artifact has {manifest.get(key)!r}, "
-                                 f"this instance expects {want!r}")
-        expected_hash = (context or {}).get("config_hash")
-        if expected_hash and manifest.get("config_hash") and manifest["config_hash"] != expected_hash:
-            raise ValueError("Persisted index was built with a different configuration (config_hash mismatch)")
-        codebooks = np.load(path / manifest["files"]["codebooks"])
-        codes = np.load(path / manifest["files"]["codes"])
+        manifest, load, result = persist.read_artifact(artifact_dir, context, "HipPQSearch", format=self._FORMAT,
+                                                       dimension=self.dimension, index_type=self.index_type, metric=self.metric)
+        codebooks, codes = load("codebooks"), load("codes")
         m = parse_pq_key(self.index_type)
         if codebooks.shape != (m, 256, self.dimension // m) or codes.ndim != 2 or codes.shape[1] != m or codes.dtype != np.uint8 \
                 or codes.shape[0] != int(manifest.get("n_vectors", codes.shape[0])):
             raise ValueError("Persisted PQ files do not match the manifest")
-        want = manifest.get("sha256") or {}
-        for name, arr in (("codebooks", codebooks), ("codes", codes)):
-            if want.get(name) and hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest() != want[name]:
-                raise ValueError(f"Persisted index files do not belong together (fingerprint mismatch: {name})")
+        persist.check_sha256(manifest, {"codebooks": codebooks, "codes": codes})
         self.index = PQIndex(self.dimension, m, self.metric, self.device)
         apply_engine_options(self.index, self.config)
         self.index.set_codebooks(codebooks)           # no k-means and no encoding pass: the stored index is reused
         self.index.add_codes(codes, id_base=int(manifest.get("id_base", 0)))
         self.index_built = True
-        metrics = {}
-        bm = path / "build_metrics.json"
-        if bm.is_file():
-            metrics = json.loads(bm.read_text(encoding="utf-8"))
-        return {"artifact_dir": str(path), "manifest_path": str(path / "manifest.json"),
-                "build_time_s": float(metrics.get("build_time_s", 0.0) or 0.0)}
+        return result
 
 
 register_algorithm("HipPQSearch", HipPQSearch)
