@@ -55,7 +55,8 @@ enum vdb_status {
 };
 
 /* which search path served the last call (vdb_stats_t.last_path) */
-enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6 };
+enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6,
+                VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */ };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -74,7 +75,8 @@ typedef struct vdb_stats_s {
     int32_t nlist;             /* IVF: number of inverted lists (0 = flat index) */
     int32_t nprobe;
     int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate),
-                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate) */
+                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate),
+                                  3 = float32 lookup-table sums over the codes of a PQ index (last_path = VDB_PATH_PQ_ADC) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -126,6 +128,7 @@ typedef struct vdb_stats_s {
  *     vdb_lsht_get_keys                                  S     U    +     U    U      U         U        U       U
  *   vdb_knng_build, vdb_knng_set, vdb_knng_search*       +     U    U     +    U      U         U        U       U
  *   vdb_debug_scan_scores                                +     +    +     +    +      +         +        +       U
+ *   vdb_debug_pq_adc_scores                              U     U    U     U    +      U         U        U       U
  *   options refused (U), in either order of the calls:
  *     "int8_only" = 1, "stream_panels" = 1               -     U    U     U    U      -         U        U       -
  *     "graph" = 1                                        -     -    -     -    U      -         U        U       U
@@ -433,6 +436,12 @@ int vdb_lsht_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, 
  * every search makes the fp16 panels of the scan from the codes, slab by slab ("pq_slab_chunks" scan chunks per slab; default
  * the chunks of 524 288 rows, whatever ntotal), as (half)(codebook * sx) -- the rounding a flat build applies to x^ -- so the
  * scan statistics and the error bound are those of the flat index over x^ (vdb_stats.scan_dtype = 2).
+ * A third path, off by default: with option "pq_adc_max_batch" = B a batch of at most B queries that the scan would serve (256-row
+ * bins, k <= 1024, M <= 159: one float32 table of M x 256 partial scores per query must fit a workgroup's LDS) is scanned
+ * straight from the codes -- score = cs bias + sum over m of T[m][code[m]], plain float32 adds, m ascending -- with its own error
+ * bound (DESIGN 4.9 "ADC scan"); nothing is decoded and no slab of panels is allocated.  The bin select, the exact refine and the
+ * fallback pass are those of the MFMA scan, so the results stay, bit for bit, the flat exact search over x^
+ * (vdb_stats.last_path = VDB_PATH_PQ_ADC, scan_dtype = 3).
  * VDB_ERR_STATE: codebooks (train / set) while the handle holds rows; add / get_codes before codebooks.  Which handles admit the
  * PQ calls, and the calls and options a PQ handle refuses (its panels are made in layout "x16" only): the table of kinds above.
  * dim % M != 0 or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  vdb_reset drops the codes and keeps the codebooks. */
@@ -543,6 +552,12 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
  *                       kernels on the codes (0 = default .. 1e9)
  *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)
+ *     "pq_adc_max_batch"  PQ index: largest query batch that takes the lookup-table (ADC) scan of the codes instead of the panel pass
+ *                       + MFMA scan, 0 (default: off) .. 512; accepted without effect on every other kind of index, and for a
+ *                       batch the scan would not serve (direct-bin geometry, k > 1024, M >= 160).  Same results either way.
+ *                       Measured on 1M rows (profiles/r18_bench_pq_adc.json): faster than the panel pass by more than 8 % up to
+ *                       8 queries for PQ16 at D = 128 and PQ64 at D = 384, up to 2 for PQ64 at D = 128 -- the value to set; the
+ *                       cost grows linearly with the batch beyond
  *     "knng_nentry"     k-NN graph: entry points of a search, 0 (default: 32) .. 512
  *     "knng_max_iters"  k-NN graph: step cap of a search, 0 (default: 8 ef) .. 2^31 - 1
  *     "knng_visited_bits"  k-NN graph: log2 slots of the per-query seen filter, 0 (default: up to 12, the largest that keeps a query
@@ -589,6 +604,10 @@ int vdb_set_option(vdb_handle h, const char *key, double value);
  * D > 128); VDB_ERR_UNSUPPORTED for D > 128 on at most 2048 rows (no MFMA scan there) */
 int vdb_debug_scan_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t row0, int64_t nrows,
                           float *scores_host, float *eps_host, double *cscale);
+/* the same for the lookup-table (ADC) scan of a flat PQ index with rows (M <= 159): raw, unpacked scores of the scan's own table
+ * kernel and per-row scoring function, the ADC bound eps (nq) and cs.  Every other kind of handle: VDB_ERR_UNSUPPORTED */
+int vdb_debug_pq_adc_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t row0, int64_t nrows,
+                            float *scores_host, float *eps_host, double *cscale);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,14 @@ name into --out (default profiles/r07_bench_pq.json) and printed as one line.  E
     timeout -k 10 900 python scripts/bench_pq.py --workload unit384_pq64 && \\
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d build/pq_trace -o pq -- \\
         python scripts/bench_pq.py --workload gauss128_pq16 --steps 5 --niter 4 --no-tables --out build/pq_trace/bench.json
+
+    --adc   the lookup-table (ADC) scan against the panel pass on the PQ index alone (profiles/r18_bench_pq_adc.json): for nq in
+            {1, 2, 4, 8, 16, 32, 64, 128, 512} device-resident searches of the SAME handle with option "pq_adc_max_batch" = 0 (the panel
+            pass + MFMA scan) and 512 (the ADC scan), one search each per round, median of `steps` rounds, then the stage timers, the
+            candidates per query and the code bytes the scan kernel reads per second (ntotal x M / scan_ms) of each setting.
+            Per-kernel times of the two new kernels at one query, a run of its own per workload (profiles/r18_pq_adc_kernel_stats.csv):
+                timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d build/adc_trace -o adc -- \\
+                    python scripts/bench_pq.py --adc --adc-nq 1 --workload gauss128_pq64 --steps 20 --niter 4 --out build/adc_trace/bench.json
 """
 from __future__ import annotations
 
@@ -49,6 +57,67 @@ def recall(exact, got, k):
     return float(np.mean([len(set(a[:k]) & set(b[:k])) / k for a, b in zip(exact, got)]))
 
 
+def adc_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s) -> int:
+    dev = Q_t.device
+    settings = (("panel_pass", 0), ("adc", 512))
+    res = {"config": f"{args.workload}: {n} x {d}, PQ{M}, {metric}, k={K}, device-resident searches of one handle, option pq_adc_max_batch "
+                     f"0 / 512 alternating, median of {args.steps} rounds after {args.warmup}",
+           "train_s": round(train_s, 2), "add_s": round(add_s, 2), "niter": args.niter, "batches": {}}
+    same = True
+    for m in [int(v) for v in args.adc_nq.split(",")]:
+        outs = {name: (torch.empty((m, K), dtype=torch.float32, device=dev), torch.empty((m, K), dtype=torch.int64, device=dev))
+                for name, _ in settings}
+
+        def search(name, value):
+            pq.set_option("pq_adc_max_batch", value)
+            D_t, I_t = outs[name]
+            pq.search_device(Q_t.data_ptr(), m, K, D_t.data_ptr(), I_t.data_ptr(), stream)
+
+        for _ in range(args.warmup):
+            for name, value in settings:
+                search(name, value)
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _ in settings}
+        for _ in range(args.steps):
+            for name, value in settings:
+                pq.set_option("pq_adc_max_batch", value)
+                D_t, I_t = outs[name]
+                t0 = time.perf_counter()
+                pq.search_device(Q_t.data_ptr(), m, K, D_t.data_ptr(), I_t.data_ptr(), stream)
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+        row = {}
+        sums = {}
+        for name, value in settings:
+            pq.set_option("pq_adc_max_batch", value)
+            pq.set_option("timing", 1)
+            for _ in range(args.steps):
+                search(name, value)
+            torch.cuda.synchronize()
+            st = pq.stats()
+            pq.set_option("timing", 0)
+            sums[name] = hashlib.sha256(outs[name][1].cpu().numpy().tobytes() + outs[name][0].cpu().numpy().tobytes()).hexdigest()[:16]
+            row[name] = {"ms": round(statistics.median(ms[name]), 4), "path": st["last_path_name"], "scan_dtype": st["scan_dtype"],
+                         "prep_ms": round(st["last_prep_ms"], 4), "scan_ms": round(st["last_scan_ms"], 4),
+                         "tail_ms": round(st["last_tail_ms"], 4), "total_ms": round(st["last_total_ms"], 4),
+                         "candidates_per_query": round(st["last_candidates"] / m, 2), "rescan_bins_per_query": round(st["last_rescan_bins"] / m, 3),
+                         "flagged_queries": st["last_fallback_queries"], "bytes_workspace": st["bytes_workspace"]}
+        row["adc"]["code_read_tb_per_s"] = round(n * M * m / max(row["adc"]["scan_ms"], 1e-6) / 1e9, 3)      # (every workgroup streams its chunk once per query)
+        row["adc"]["code_bytes_once_tb_per_s"] = round(n * M / max(row["adc"]["scan_ms"], 1e-6) / 1e9, 3)
+        row["adc_over_panel_pass_time"] = round(row["adc"]["ms"] / row["panel_pass"]["ms"], 4)
+        row["same_results"] = sums["adc"] == sums["panel_pass"]
+        same = same and row["same_results"]
+        res["batches"][str(m)] = row
+    pq.close()
+    path = Path(args.out)
+    allres = json.loads(path.read_text()) if path.exists() else {}
+    allres[args.workload] = res
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(allres, indent=1) + "\n")
+    print(json.dumps({args.workload: res}))
+    return 0 if same else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(WORKLOADS), required=True)
@@ -58,8 +127,12 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--niter", type=int, default=25)
     ap.add_argument("--no-tables", action="store_true", help="skip the slab-size and small-batch tables")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r07_bench_pq.json"))
+    ap.add_argument("--adc", action="store_true", help="only the ADC leg: option pq_adc_max_batch 0 against 512 on small batches")
+    ap.add_argument("--adc-nq", default="1,2,4,8,16,32,64,128,512", help="batch sizes of the ADC leg (a kernel trace takes one)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("r18_bench_pq_adc.json" if args.adc else "r07_bench_pq.json"))
     import torch
 
     import vdbhip
@@ -85,6 +158,9 @@ def main() -> int:
     t0 = time.perf_counter()
     pq.add(X)
     add_s = time.perf_counter() - t0
+    if args.adc:
+        del X
+        return adc_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s)
     xh = pq.reconstruct()
     flat = vdbhip.FlatIndex(d, metric, 0)
     flat.add(xh)

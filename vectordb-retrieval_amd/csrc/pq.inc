@@ -1,6 +1,7 @@
 // pq.inc -- host side of the product quantizer (kernels: pq.hpp).  First the core that the flat PQ<M> index and
 // IVF<nlist>,PQ<M> (ivf_pq.inc, ivf.inc) share: the M rule, installing and reading codebooks, their training, the encode
-// launch.  Then the flat index: encoding adds, the derived scan statistics, the per-slab panel pass of a search.  Included by
+// launch.  Then the flat index: encoding adds, the derived scan statistics, the per-slab panel pass of a search, the launchers of the
+// lookup-table (ADC) scan of small batches (pq_adc.hpp) and its test hook.  Included by
 // vdbhip.hip ahead of ivf.inc; a handle keeps one PqCodebooks for each of the two (vdb_index_s: pq, ivfpq).
 
 namespace {
@@ -281,6 +282,68 @@ void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *pane
     VDB_HIP(hipGetLastError());
 }
 
+// ---- the ADC scan (pq_adc.hpp) ------------------------------------------------------------------------------------------------
+// LDS of a scan workgroup: the query's table (M KiB), the reduction block, and -- when M is a multiple of 4 and it still fits --
+// one bin of staged code rows.  The budget is a whole CU's LDS: M <= 127 stages, M = 128 (the table alone is 128 KiB) reads its
+// codes from the index, M >= 160 does not fit and stays on the panel pass.
+constexpr int kPqAdcLdsBudget = 160 * 1024;
+bool pq_adc_fits(int M) { return (int64_t)M * 1024 + kPqAdcAuxBytes <= kPqAdcLdsBudget; }
+inline bool pq_adc_staged(int M) {
+    return M % 4 == 0 && 16 * M <= 256 * kPqAdcMaxPieces &&
+           (int64_t)M * 1024 + kPqAdcAuxBytes + (int64_t)256 * pq_code_pitch(M) <= kPqAdcLdsBudget;
+}
+
+// the lookup tables [nq][M][256] and the ADC error bounds of a batch whose statistics `info` holds (or will, in stream order)
+void launch_pq_adc_tables(vdb_index_s *h, const float *dq, int64_t nq, const QueryBatchInfo *info, float *tables, float *eps, hipStream_t st) {
+    PqAdcTableArgs t{};
+    t.Q = dq;
+    t.cb = h->kept.pq_cb.as<float>();
+    t.info = info;
+    t.tables = tables;
+    t.eps = eps;
+    t.nq = nq;
+    t.D = h->dim;
+    t.M = h->pq.M;
+    t.dsub = h->pq.dsub;
+    t.metric = h->metric;
+    t.xnorm_max = sqrtf(h->maxnorm2) * 1.0000002f;
+    pq_adc_tables_kernel<<<dim3((unsigned)t.M, (unsigned)((nq + kPqAdcQB - 1) / kPqAdcQB)), dim3(256), 0, st>>>(t);
+    VDB_HIP(hipGetLastError());
+}
+
+// what the scan and the test hook share of the arguments
+PqAdcScanArgs pq_adc_args(vdb_index_s *h, const float *tables, const QueryBatchInfo *info) {
+    PqAdcScanArgs a{};
+    a.codes = h->codes.pq_codes.as<unsigned char>();
+    a.bias = h->scan.bias.as<float>();
+    a.tables = tables;
+    a.info = info;
+    a.N = h->N;
+    a.M = h->pq.M;
+    a.groups = h->tile16 ? 4 : 2;
+    a.gshift = h->tile16 ? 2 : 3;                 // (quads on p16 spans, octs on layout "x16": f16_octs(h, 0))
+    a.code_pitch = pq_code_pitch(a.M);
+    return a;
+}
+
+// one workgroup per (chunk, query) of the geometry in `a`
+void launch_pq_adc_scan(vdb_index_s *h, PqAdcScanArgs &a, int64_t nq, hipStream_t st) {
+    const bool staged = pq_adc_staged(a.M);
+    const size_t lds = (size_t)a.M * 1024 + kPqAdcAuxBytes + (staged ? (size_t)256 * a.code_pitch : 0);
+    if (lds > (size_t)kPqAdcLdsBudget) throw Error(VDB_ERR_STATE, "internal: the ADC table does not fit the LDS");
+    const dim3 grid((unsigned)a.nchunks, (unsigned)nq);
+    if (staged) {
+        if (lds > 65536)         // (more than the default 64 KiB of dynamic LDS: opt in, on the current device, every time)
+            VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_adc_scan_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPqAdcLdsBudget));
+        pq_adc_scan_kernel<true><<<grid, dim3(256), lds, st>>>(a);
+    } else {
+        if (lds > 65536)
+            VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_adc_scan_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPqAdcLdsBudget));
+        pq_adc_scan_kernel<false><<<grid, dim3(256), lds, st>>>(a);
+    }
+    VDB_HIP(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,6 +423,45 @@ int vdb_pq_get_codes(vdb_handle hh, uint8_t *codes_host) {
         set_device(h->device);
         VDB_HIP(hipDeviceSynchronize());
         VDB_HIP(hipMemcpy(codes_host, h->codes.pq_codes.p, (size_t)h->N * h->pq.M, hipMemcpyDeviceToHost));
+    });
+}
+
+int vdb_debug_pq_adc_scores(vdb_handle hh, const float *q_host, int64_t nq, int64_t row0, int64_t nrows, float *scores_host,
+                            float *eps_host, double *cscale) {
+    return guarded([&] {
+        auto *h = check(hh);
+        admit(h, "vdb_debug_pq_adc_scores", kPq);
+        if (!h->built || h->N == 0 || !h->scan_ok) throw Error(VDB_ERR_STATE, "vdb_debug_pq_adc_scores: no scan statistics (no rows, or a corpus the scan does not serve)");
+        if (!pq_adc_fits(h->pq.M)) throw Error(VDB_ERR_UNSUPPORTED, "vdb_debug_pq_adc_scores: the lookup table of M = " + std::to_string(h->pq.M) + " sub-spaces does not fit the LDS");
+        if (!q_host || !scores_host || !eps_host) throw Error(VDB_ERR_INVALID, "null pointer");
+        if (nq <= 0 || nq > 65535 || nrows <= 0 || row0 < 0 || row0 + nrows > h->N) throw Error(VDB_ERR_INVALID, "bad range");
+        set_device(h->device);
+        hipStream_t st = nullptr;
+        const int Dm = h->dim, M = h->pq.M;
+        DevBuf dq, info, tables, eps, out;
+        dq.reserve((size_t)nq * Dm * 4);
+        info.reserve(sizeof(QueryBatchInfo));
+        tables.reserve((size_t)nq * M * 1024);
+        eps.reserve((size_t)nq * 4);
+        out.reserve((size_t)nq * nrows * 4);
+        VDB_HIP(hipMemcpyAsync(dq.p, q_host, (size_t)nq * Dm * 4, hipMemcpyHostToDevice, st));
+        VDB_HIP(hipMemsetAsync(info.p, 0, sizeof(QueryBatchInfo), st));
+        const int64_t total = nq * Dm;
+        query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq.as<float>(), total, info.as<QueryBatchInfo>(),
+            FinalizeArgs{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0});
+        launch_pq_adc_tables(h, dq.as<float>(), nq, info.as<QueryBatchInfo>(), tables.as<float>(), eps.as<float>(), st);
+        const PqAdcScanArgs a = pq_adc_args(h, tables.as<float>(), info.as<QueryBatchInfo>());
+        const size_t lds = (size_t)M * 1024;
+        if (lds > 65536)
+            VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pq_adc_scores_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPqAdcLdsBudget));
+        pq_adc_scores_kernel<<<dim3((unsigned)((nrows + 255) / 256), (unsigned)nq), dim3(256), lds, st>>>(a, row0, nrows, out.as<float>());
+        VDB_HIP(hipGetLastError());
+        QueryBatchInfo hi;
+        VDB_HIP(hipMemcpyAsync(scores_host, out.p, (size_t)nq * nrows * 4, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(eps_host, eps.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipMemcpyAsync(&hi, info.p, sizeof(hi), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        if (cscale) *cscale = (double)hi.cs;
     });
 }
 

@@ -219,6 +219,7 @@ struct Batch {
     unsigned long long *stat_counters;
     long tslot;                  // timing_begin
     bool clear_in_prep;          // workgroup 0 of query_prep_kernel clears ws.small (search_batch)
+    bool adc;                    // PQ: the bin records come from the lookup-table scan of the codes (search_scan_adc), not from panels
 };
 
 // the S partial lists per slot that an exhaustive pass (fa) left in its (pkeys, pids), merged into the outputs of the batch
@@ -806,8 +807,65 @@ void scan_refine_tail(const Batch &b, const SelectArgs &se) {
     }
 }
 
+// PQ, option "pq_adc_max_batch": the lookup-table (ADC) scan of the codes makes the bin records (pq_adc.hpp); select and refine tail
+// are those of search_scan.  The prep takes the batch statistics, the tables and the ADC error bounds -- no fp16 B fragments -- and
+// no slab of panels is made or allocated.
+void search_scan_adc(const Batch &b) {
+    vdb_index_s *h = b.h;
+    Workspace &ws = b.ws;
+    const ScanGeom &g = b.g;
+    const int64_t nq = b.nq;
+    const int k = b.k;
+    hipStream_t st = b.st;
+    const int64_t Qpad = (nq + 511) / 512 * 512;
+    const int G = h->tile16 ? 4 : 2;
+    const int64_t nbins = g.nspans * G, nsb = (int64_t)g.nchunks * G;
+    const int cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : std::max(64, 2 * k + 32);
+    const int rescan_cap = std::max(16, k / 2 + 8);
+    ws.eps.reserve((size_t)nq * sizeof(float));
+    ws.adc_tab.reserve((size_t)nq * h->pq.M * 256 * sizeof(float));
+    ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
+    ws.bin_m2.reserve((size_t)nbins * Qpad * sizeof(float));
+    ws.sb_m1.reserve((size_t)nsb * Qpad * sizeof(float));
+    ws.sb_m2.reserve((size_t)nsb * Qpad * sizeof(float));
+    ws.sb_span.reserve((size_t)nsb * Qpad * sizeof(int32_t));
+    ws.cand.reserve((size_t)nq * cand_cap * sizeof(int32_t));
+    ws.rescan.reserve((size_t)nq * rescan_cap * 2 * sizeof(int32_t));
+    ws.counts.reserve((size_t)nq * 2 * sizeof(int32_t));
+    ws.fallback.reserve((size_t)nq * sizeof(int32_t));
+    ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
+
+    QueryBatchInfo *info = batch_info(ws);              // (zeroed by search_batch)
+    const int64_t total = nq * h->dim;
+    query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(
+        b.dq, total, info, FinalizeArgs{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0});
+    h->info_valid_nq = nq;
+    launch_pq_adc_tables(h, b.dq, nq, info, ws.adc_tab.as<float>(), ws.eps.as<float>(), st);
+
+    ScanArgs sa{};                                      // (what scan_select reads of it)
+    sa.info = info;
+    sa.bin_m1 = ws.bin_m1.as<float>();
+    sa.bin_m2 = ws.bin_m2.as<float>();
+    sa.sb_m1 = ws.sb_m1.as<float>();
+    sa.sb_m2 = ws.sb_m2.as<float>();
+    sa.sb_span = ws.sb_span.as<int32_t>();
+    PqAdcScanArgs aa = pq_adc_args(h, ws.adc_tab.as<float>(), info);
+    aa.bin_m1 = sa.bin_m1; aa.bin_m2 = sa.bin_m2;
+    aa.sb_m1 = sa.sb_m1; aa.sb_m2 = sa.sb_m2; aa.sb_span = sa.sb_span;
+    aa.nspans = g.nspans; aa.Qpad = Qpad;
+    aa.spans_per_chunk = g.spc; aa.chunk_rem = g.rem; aa.nchunks = g.nchunks;
+    timing_mark(h, b.tslot, 0, st);
+    launch_pq_adc_scan(h, aa, nq, st);
+    timing_mark(h, b.tslot, 1, st);
+    const SelectArgs se = scan_select(b, sa, Qpad, cand_cap, rescan_cap);
+    scan_refine_tail(b, se);
+    timing_mark(h, b.tslot, 2, st);
+    h->last.last_path = VDB_PATH_PQ_ADC;
+}
+
 // the steps in the order they are enqueued
 void search_scan(const Batch &b) {
+    if (b.adc) return search_scan_adc(b);
     vdb_index_s *h = b.h;
     Workspace &ws = b.ws;
     const ScanGeom &g = b.g;
@@ -916,6 +974,10 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                (h->opt.force_path == 2 || h->N >= 32768 || (h->Npad > 8192 && (double)nq * (double)h->N >= 4.0e6));
     // (corpora of 8193..15360 rows whose chunking cannot give 4k superbins still have the dense path below)
 
+    // (PQ, option "pq_adc_max_batch": batches up to that size on the standard 256-row-bin geometry take the lookup-table scan of the
+    //  codes -- pq_adc.hpp -- unless the table of M sub-spaces does not fit a workgroup's LDS)
+    const bool use_adc = pq_on(h) && use_scan && direct_rows == 0 && nq <= h->opt.pq_adc_max_batch && pq_adc_fits(h->pq.M);
+
     h->info_valid_nq = -1;
     // fb_count restarts with every batch (it indexes this batch's fb_list); the statistics counters behind it were
     // zeroed once for the whole call (search_device_impl) and accumulate over the batches
@@ -925,7 +987,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     if (h->small_clear_pending) {
         h->small_clear_pending = false;
         h->small_is_clean = false;
-        clear_in_prep = use_scan && nq * Dm <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;
+        clear_in_prep = use_scan && !use_adc && nq * Dm <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;
         if (!clear_in_prep) VDB_HIP(hipMemsetAsync(ws.small.p, 0, kSmallBytes, st));
     } else if (h->small_is_clean) h->small_is_clean = false;      // the first batch of a call: search_device_impl has just cleared all of it
     else VDB_HIP(hipMemsetAsync(ws.small.p, 0, 64, st));
@@ -938,7 +1000,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->scan.panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
                            h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= h->N &&
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
-    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, direct_rows, fb_count, stat_counters, tslot, clear_in_prep};
+    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc};
     if (use_dense) search_dense(b);
     else if (!use_scan) search_exact(b);
     else search_scan(b);

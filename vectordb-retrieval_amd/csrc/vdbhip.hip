@@ -33,6 +33,7 @@
 #include "lsh.hpp"
 #include "lsh_tables.hpp"
 #include "pq.hpp"
+#include "pq_adc.hpp"
 #include "knng.hpp"
 
 using namespace vdb;
@@ -234,6 +235,7 @@ struct Workspace {
     DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
     DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ: the fp16 panels converted from the codes for the current batch
+    DevBuf adc_tab{"ws.adc_tab"};           // PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
 };
 
 // ---- options -----------------------------------------------------------------------------------------------------------------
@@ -268,6 +270,7 @@ struct Options {
     int lsh_force_fallback = 0;              // every query of an LSH call takes the exact fallback of the select
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
+    int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)
     // k-NN graph (knng.inc)
     int knng_nentry = 0;                     // entry points of a search (0 = default 32)
     int knng_max_iters = 0;                  // step cap of a search (0 = default 8 ef)
@@ -490,6 +493,7 @@ constexpr OptionRow kOptions[] = {
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
+    {"pq_adc_max_batch", &Options::pq_adc_max_batch, 0, {0, 512}},   // PQ: largest query batch that takes the lookup-table (ADC) scan of the codes (0 = off)
     {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
     {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
     {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
@@ -587,6 +591,10 @@ void knng_drop(vdb_index_s *h);                                       // knng.in
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
+bool pq_adc_fits(int M);                                                                                    // pq.inc: the ADC scan (pq_adc.hpp) serves this M
+void launch_pq_adc_tables(vdb_index_s *h, const float *dq, int64_t nq, const QueryBatchInfo *info, float *tables, float *eps, hipStream_t st);
+PqAdcScanArgs pq_adc_args(vdb_index_s *h, const float *tables, const QueryBatchInfo *info);
+void launch_pq_adc_scan(vdb_index_s *h, PqAdcScanArgs &a, int64_t nq, hipStream_t st);
 // Where the rows of a flat handle live, for the exact kernels: float32 rows, or (int8-only) int8 rows + their byte window, or
 // (PQ) product codes that refine.hpp's pq_key looks x^ up from.  q: the batch's queries padded to D4.
 inline RefineCommon flat_rows(const vdb_index_s *h, const float *q, int k) {
@@ -1375,7 +1383,8 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
         // the last search ran an MFMA scan (flat, or the list-major one of an IVF index): ws.small holds its choice and its counters
-        const bool mfma_scanned = h->last.last_path == VDB_PATH_MFMA_SCAN || (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma);
+        const bool mfma_scanned = h->last.last_path == VDB_PATH_MFMA_SCAN || h->last.last_path == VDB_PATH_PQ_ADC ||
+                                  (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma);
         if (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->plan.ivf_plan.p) {   // (of the last batch of the call)
             IvfPlan pl;
             VDB_HIP(hipDeviceSynchronize());
@@ -1391,6 +1400,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         }
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
+        if (h->last.last_path == VDB_PATH_PQ_ADC) s.scan_dtype = 3;                                         // float32 lookup-table sums (PQ, ADC scan)
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;

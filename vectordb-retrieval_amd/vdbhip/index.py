@@ -63,6 +63,18 @@ class _Handle:
     def set_option(self, key: str, value: float) -> None:
         _ffi.check(self._lib.vdb_set_option(self._handle(), key.encode(), float(value)), build_time=True)
 
+    def debug_adc_scores(self, queries: np.ndarray, row0: int, nrows: int):
+        """(scores (nq, nrows), eps (nq), cs) of the lookup-table (ADC) scan: raw, unpacked scores, as FlatIndex.debug_scan_scores.
+        Flat PQ indexes with rows only; every other kind of handle is refused by the library."""
+        q = _ffi.as_f32_c(queries)
+        nq = q.shape[0]
+        scores = np.empty((nq, nrows), np.float32)
+        eps = np.empty((nq,), np.float32)
+        cs = ctypes.c_double(0.0)
+        _ffi.check(self._lib.vdb_debug_pq_adc_scores(self._handle(), _ffi.ptr(q), nq, int(row0), int(nrows),
+                                                     _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
+        return scores, eps, float(cs.value)
+
 
 class FlatIndex(_Handle):
     """Device-resident brute-force index (replaces faiss.IndexFlat(d, metric)).  `device`: one GPU ordinal, or a list of

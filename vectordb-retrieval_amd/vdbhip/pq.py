@@ -77,9 +77,10 @@ class PQCodec:
 
 
 class PQIndex(PQCodec, _Handle):
-    """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only."""
+    """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only.  `adc_max_batch`: option
+    "pq_adc_max_batch" -- query batches up to that size (at most 512; 0 = off) take the lookup-table (ADC) scan of the codes."""
 
-    def __init__(self, dim: int, M: int, metric: str = "l2", device=0):
+    def __init__(self, dim: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0):
         if metric not in ("l2", "ip"):
             raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
         device = normalize_devices(device)
@@ -91,6 +92,9 @@ class PQIndex(PQCodec, _Handle):
         super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
         self.is_trained = False
         self.ntotal = 0
+        self.adc_max_batch = int(adc_max_batch or 0)
+        if self.adc_max_batch:
+            self.set_option("pq_adc_max_batch", float(self.adc_max_batch))
 
     def _sync_ntotal(self) -> None:
         self.ntotal = int(self.stats()["ntotal"])
@@ -168,7 +172,7 @@ class PQIndex(PQCodec, _Handle):
 
 
 def _build_pq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> PQIndex:
-    index = PQIndex(dim, parse_pq_key(key), metric, device)
+    index = PQIndex(dim, parse_pq_key(key), metric, device, adc_max_batch=int(params.get("adc_max_batch") or 0))
     apply_engine_options(index, params)
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
@@ -210,17 +214,22 @@ class HipPQIndexer(BaseIndexer):
 
 
 class HipPQSearcher(BaseSearcher):
-    """FaissSearcher semantics over a HipPQIndexer artifact (distances negated for cosine / ip, as HipIVFSearcher)."""
+    """FaissSearcher semantics over a HipPQIndexer artifact (distances negated for cosine / ip, as HipIVFSearcher).
+    `adc_max_batch` (a config entry `adc_max_batch: 16`): option "pq_adc_max_batch" of the attached index."""
 
-    def __init__(self, name: str, dimension: int, metric: str = "l2", **kwargs: Any) -> None:
+    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
         self.index: Optional[PQIndex] = None
         self.normalize_queries = False
+        self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         if artifact.kind != "hip_pq":
             raise ValueError("HipPQSearcher requires 'hip_pq' artifact")
         self.index = artifact.data
+        if self.adc_max_batch is not None:
+            self.index.set_option("pq_adc_max_batch", float(self.adc_max_batch))
+            self.index.adc_max_batch = self.adc_max_batch
         meta = artifact.metadata or {}
         self.metric = meta.get("metric", self.metric)
         self.normalize_queries = meta.get("normalize_queries", False)
@@ -256,9 +265,10 @@ class HipPQSearch(BaseAlgorithm):
     _FORMAT = "vdbhip-pq-v1"
 
     def __init__(self, name: str, dimension: int, index_type: str = "PQ8", metric: str = "l2", device: Optional[int] = None,
-                 **kwargs: Any) -> None:
+                 adc_max_batch: int = 0, **kwargs: Any) -> None:
         super().__init__(name, dimension, **kwargs)
         self.index_type = index_type
+        self.adc_max_batch = int(adc_max_batch or 0)      # option "pq_adc_max_batch": a constructor parameter, not part of the artifact
         self.metric = "l2" if metric == "l2" else "ip"
         self.device = _resolve_device(device, kwargs.get("device_ids"))
         self.index: Optional[PQIndex] = None
@@ -270,7 +280,8 @@ class HipPQSearch(BaseAlgorithm):
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         data = np.asarray(vectors).astype(np.float32)
-        self.index = _build_pq(data, self.dimension, self.index_type, self.metric, self.device, self.config)
+        self.index = _build_pq(data, self.dimension, self.index_type, self.metric, self.device,
+                               {**self.config, "adc_max_batch": self.adc_max_batch})
         self.index_built = True
         reserve_workspace(self.index, self.config)
 
@@ -308,7 +319,7 @@ class HipPQSearch(BaseAlgorithm):
                 or codes.shape[0] != int(manifest.get("n_vectors", codes.shape[0])):
             raise ValueError("Persisted PQ files do not match the manifest")
         persist.check_sha256(manifest, {"codebooks": codebooks, "codes": codes})
-        self.index = PQIndex(self.dimension, m, self.metric, self.device)
+        self.index = PQIndex(self.dimension, m, self.metric, self.device, adc_max_batch=self.adc_max_batch)
         apply_engine_options(self.index, self.config)
         self.index.set_codebooks(codebooks)           # no k-means and no encoding pass: the stored index is reused
         self.index.add_codes(codes, id_base=int(manifest.get("id_base", 0)))
