@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Which kernels a flat search launches, over a reduced matrix of index layouts, batch sizes and tuning options.
+
+    python scripts/scan_launch_matrix.py                     walk the matrix (`force_path` = 2, census-sized corpora: milliseconds a search)
+    python scripts/scan_launch_matrix.py --compare A B OUT   compare two kernel traces of that walk, entry for entry
+
+Meant to run once per build under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/scan_launch_matrix.py`
+(alone, no counters): two builds launch the same kernels when the sequences of (kernel name, grid, workgroup size) in their traces
+are equal (the runtime's own copy and fill kernels aside).  The launches are ordered by dispatch id: start timestamps of neighbours on one queue can swap when a kernel returns at once.
+"""
+import csv, glob, sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path[:0] = [str(ROOT), str(ROOT / "vectordb-retrieval_amd")]
+
+NQS = (1, 64, 128, 256, 700, 5120)          # one wave, one / two / four 64-query groups, an odd batch, a multiple of 1024
+
+
+def walk():
+    import numpy as np, vdbhip
+    rng = np.random.default_rng(11)
+
+    def flat(X, opts):
+        idx = vdbhip.FlatIndex(X.shape[1], "l2", 0)
+        for name, value in opts.items():
+            idx.set_option(name, value)
+        idx.add(X)
+        return idx
+
+    def searches(idx, Q, ks=(2,), nqs=NQS):
+        for k in ks:
+            for nq in nqs:
+                idx.search(Q[:nq], k)
+                assert idx.stats()["last_path_name"] == "mfma_scan", (nq, k, idx.stats())
+
+    def bytes_(n, d):
+        return rng.integers(0, 256, size=(n, d)).astype(np.float32)
+
+    base = {"force_path": 2, "spans_per_chunk": 1}
+    # layout "x16" and the 32-row layout, D = 64 (26 625 rows: 53 one-span chunks, 1024-query tiles at 5120 queries) and D = 128;
+    # integer and fractional queries launch the same kernels (the device picks the scan), k = 18 / 36: direct bins of 128 / 64 rows
+    for d, n in ((64, 26_625), (128, 17_409)):
+        X, Q = bytes_(n, d), bytes_(5120, d)
+        for shape in (0, 32):
+            idx = flat(X, dict(base, flat_shape=shape))
+            searches(idx, Q)
+            if n == 17_409:
+                searches(idx, Q, ks=(18, 36), nqs=(64, 700))
+            for name, values in (("i8_variant", (0, 1, 2, 4, 5, 6, 7)), ("i8_ring", (2, 4, 8)), ("i8_nt", (1, 2)), ("f16_wide", (1,)),
+                                 ("f16_stage_tiles", (4, 8)), ("scan_pair", (0,)), ("small_batch", (0,)), ("panel_dtype", (1,))):
+                default = {"i8_variant": 3, "scan_pair": 1, "small_batch": 1}.get(name, 0)
+                for v in values:
+                    idx.set_option(name, v)
+                    searches(idx, Q)
+                idx.set_option(name, default)
+            idx.close()
+        for opts in ({"i8_group": 4}, {"f16_group": 4}, {"i8_group": 4, "f16_group": 4}):      # (quads: the 32-row layout, set before the add)
+            idx = flat(X, dict(base, **opts))
+            searches(idx, Q)
+            idx.close()
+    # D = 384: the K-loop scan, resident and streamed panels (slabs of two chunks), direct bins of 128 / 64 rows at k = 20 / 40
+    X, Q = rng.standard_normal((18_443, 384), dtype=np.float32), rng.standard_normal((5120, 384), dtype=np.float32)
+    for opts in ({}, {"stream_panels": 1, "stream_slab_rows": 2048}, {"kloop_qgroup": 2}):
+        idx = flat(X, dict(base, **opts))
+        searches(idx, Q, nqs=(1, 16, 40, 64, 700, 5120))
+        searches(idx, Q, ks=(20, 40), nqs=(64, 700))
+        idx.close()
+    # int8-only index (more than 32 768 rows): the fp16 scan goes slab by slab
+    X, Q = bytes_(33_803, 128), bytes_(5120, 128)
+    for shape in (0, 32):
+        idx = flat(X, dict(base, int8_only=1, int8_slab_chunks=3, flat_shape=shape))
+        assert idx.stats()["has_i8_copy"]
+        searches(idx, Q)
+        idx.close()
+    # PQ index: panels made per search, slabs of five chunks
+    for d, M, n in ((64, 8, 17_409), (384, 64, 18_443)):
+        idx = vdbhip.PQIndex(d, M, "l2", 0)
+        for name, value in dict(base, pq_slab_chunks=5).items():
+            idx.set_option(name, value)
+        idx.set_codebooks(rng.standard_normal((M, 256, d // M), dtype=np.float32))
+        idx.add_codes(rng.integers(0, 256, size=(n, M), dtype=np.uint8))
+        searches(idx, rng.standard_normal((5120, d), dtype=np.float32))
+        idx.close()
+    print("scan_launch_matrix: done")
+
+
+def launches(trace_dir):
+    """[(kernel name, grid, workgroup size)] of a rocprofv3 kernel trace, in launch order."""
+    files = glob.glob(str(Path(trace_dir) / "**" / "*kernel_trace.csv"), recursive=True)
+    assert len(files) == 1, files
+    rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Dispatch_Id"]))
+    return [(r["Kernel_Name"], tuple(int(r[f"Grid_Size_{a}"]) for a in "XYZ"), tuple(int(r[f"Workgroup_Size_{a}"]) for a in "XYZ")) for r in rows]
+
+
+def compare(a, b, out):
+    # (the runtime's own copy / fill kernels are left out: how many blits a host copy takes varies from run to run of ONE build)
+    ours = lambda L: [x for x in L if not x[0].startswith("__amd_rocclr_")]
+    A_all, B_all = launches(a), launches(b)
+    A, B = ours(A_all), ours(B_all)
+    diff = [(i, x, y) for i, (x, y) in enumerate(zip(A, B)) if x != y]
+    scans = {}
+    for name, grid, wg in A:
+        if "scan" in name and "kernel" in name:
+            scans[name] = scans.get(name, 0) + 1
+    with open(out, "w") as f:
+        f.write(f"kernel launches of the library: {len(A)} in {a}, {len(B)} in {b}; entries that differ: {len(diff)}\n")
+        f.write(f"(left out: {len(A_all) - len(A)} and {len(B_all) - len(B)} launches of the runtime's __amd_rocclr_* copy / fill kernels)\n")
+        f.write(f"equal, entry for entry: {'yes' if not diff and len(A) == len(B) else 'NO'}\n")
+        for i, x, y in diff[:50]:
+            f.write(f"  {i}: {x} | {y}\n")
+        f.write(f"\nscan kernels launched ({len(scans)} distinct), launches of each:\n")
+        for name in sorted(scans):
+            f.write(f"  {scans[name]:6d}  {name}\n")
+    print(open(out).read()[:3000])
+    return 0 if not diff and len(A) == len(B) else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--compare":
+        sys.exit(compare(*sys.argv[2:5]))
+    walk()

@@ -2,7 +2,7 @@
 
 A random corpus only verifies the rows that land in some query's top-k; a census queries with EVERY row, so a scan that loses the rows of
 one tile, stage, span or chunk position fails for exactly those rows.  This module holds no GPU code: the corpora, an exact reference
-over the Gram matrix, and a restatement of the scan geometry of search_flat.inc with which a test asserts the launch shape it names.
+over the Gram matrix, and a restatement of the scan geometry of csrc/scan_plan.hpp with which a test asserts the launch shape it names.
 
 Corpora.  Every row is a random permutation of one fixed multiset of D values, so all rows have the same norm and row r is its own
 strict nearest neighbour under L2 (distance 0) and under IP (Cauchy-Schwarz: x.y < |x||y| = x.x for y != x of equal norm).  Kinds:
@@ -163,7 +163,7 @@ def gram_topk(X, rows, k, metric, block=512, margin_rows=None):
     return D, I
 
 
-# ---- restated geometry of the flat scan (search_flat.inc) -------------------------------------------------------------------------
+# ---- restated geometry of the flat scan (csrc/scan_plan.hpp; held against the C++ itself by test_scan_plan_host.py) ------------------
 BIN_ROWS = 256
 
 

@@ -299,7 +299,7 @@ def case(construction, kind, n, d, M, seed=0):
 # ---- restated launch choices ------------------------------------------------------------------------------------------------------
 PQ_LDS_BUDGET = 80 * 1024          # kPqLdsBudget (pq.inc)
 PQ_TAB_SKEW = 8                    # kPqTabSkew (pq.hpp), halves
-PQ_SLAB_ROWS = 524_288             # kPqSlabRows (search_flat.inc)
+PQ_SLAB_ROWS = 524_288             # kPqSlabRows (scan_plan.hpp)
 IVFPQ_LDS_BUDGET = 64 * 1024       # kIvfPqLdsBudget (ivf_pq.inc)
 IVFPQ_CENT_FLOATS = 128            # kIvfPqCentFloats (ivf_pq.hpp)
 

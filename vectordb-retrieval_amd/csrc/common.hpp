@@ -7,6 +7,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "scan_plan.hpp"      // the geometry constants the launch rules use: kSpanRows, kBinRows, kTilesPerSpan, kSpanRows16, kTilesPerSpan16, kMaxKSteps
+
 namespace vdb {
 
 // ---- geometry of the fp16 scan copy ("panels") ---------------------------------------------
@@ -20,14 +22,10 @@ namespace vdb {
 // a "bin" (the unit of the collision guard) is a contiguous 256-row range and the 8-bit id packed
 // into a score is the offset inside the bin.
 constexpr int kTileRows = 32;
-constexpr int kSpanRows = 512;      // 16 tiles; two bins (h = 0,1) of 256 rows
-constexpr int kBinRows = 256;
-constexpr int kTilesPerSpan = 16;
+// (span = 16 tiles = 512 rows = two bins (h = 0,1) of 256 rows: kSpanRows, kBinRows, kTilesPerSpan in scan_plan.hpp)
 // layout "p16" (16-row tiles for v_mfma_f32_16x16x32_f16): span = 64 tiles = 1024 rows = four 256-row bins, one
 // per lane group g = lane>>4 of the 16x16 C/D layout
 constexpr int kTileRows16 = 16;
-constexpr int kSpanRows16 = 1024;
-constexpr int kTilesPerSpan16 = 64;
 // IVF panel space (D <= 128): every inverted list is padded to whole spans, so its spans are SMALLER -- 8 tiles = 256 rows,
 // each lane half walking 128 consecutive rows: k-means lists of ~750 rows then carry 2 % of padding instead of 36 %
 // (512-row spans padded the median list of the SIFT1M / nlist 1024 index from 752 to 1024 rows).  Same row mapping inside a
@@ -35,7 +33,6 @@ constexpr int kTilesPerSpan16 = 64;
 constexpr int kIvfTilesPerSpan = 8;
 constexpr int kIvfSpanRows = kIvfTilesPerSpan * kTileRows;
 constexpr int kStageTiles = 4;      // tiles per LDS stage (128 MFMA rows)
-constexpr int kMaxKSteps = 8;       // register-resident query fragments: D <= 128
 constexpr float kPadBias = 1.0e38f; // accumulator init of padding rows (scan units): never selected
 
 // Search statistics (candidates, re-scans, fallback queries) are counted with global atomics by every query; on ONE

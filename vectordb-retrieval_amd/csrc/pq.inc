@@ -321,7 +321,7 @@ PqAdcScanArgs pq_adc_args(vdb_index_s *h, const float *tables, const QueryBatchI
     a.N = h->N;
     a.M = h->pq.M;
     a.groups = h->tile16 ? 4 : 2;
-    a.gshift = h->tile16 ? 2 : 3;                 // (quads on p16 spans, octs on layout "x16": f16_octs(h, 0))
+    a.gshift = h->tile16 ? 2 : 3;                 // (quads on p16 spans, octs on layout "x16": f16_octs(shape, opt, 0) of scan_plan.hpp)
     a.code_pitch = pq_code_pitch(a.M);
     return a;
 }

@@ -32,7 +32,7 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 // load per K-step behind 16 MFMAs): 1 = MFMAs and select work only for the 16-query column blocks that hold queries
 // (1 ... 4); 2 = at most 16 queries and D <= 1536: additionally the B fragments of that one column block are kept in LDS
 // for the whole chunk (kNarrowQVec vectors) instead of being streamed from L2 every K-step.
-constexpr int kNarrowMaxKS = 48;                            // 32-dim k-steps of the LDS-resident query block (D <= 1536)
+// (kNarrowMaxKS, the 32-dim k-steps of that LDS-resident query block: scan_plan.hpp, with the rule that picks NARROW)
 struct ScanKloopExtra {
     int ksteps;  // 16-dim k-steps, multiple of 4
     int qgroup;  // query tiles per group (>= 1)

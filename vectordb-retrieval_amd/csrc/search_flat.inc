@@ -1,172 +1,68 @@
-// search_flat.inc -- the flat (brute-force) search path of vdbhip.hip: scan geometry, kernel launchers, one query batch
-// (search_batch), hipGraph replay, the per-call driver (search_device_impl).  Included inside vdbhip.hip's anonymous
-// namespace; not a translation unit of its own.
+// search_flat.inc -- the flat (brute-force) search path of vdbhip.hip: the table of scan kernels and `launch` (which scan, and in
+// which shape, is decided in scan_plan.hpp), one query batch (search_batch), hipGraph replay, the per-call driver
+// (search_device_impl).  Included inside vdbhip.hip's anonymous namespace; not a translation unit of its own.
 
-// ---- geometry of the scan for a given (N, k) --------------------------------------------------------
-struct ScanGeom {
-    bool ok = false;
-    int64_t nspans = 0;
-    int spc = 0, rem = 0, nchunks = 0, vpl = 0;
+// ---- path and launch shape of the scans: scan_plan.hpp decides, this file fills arguments and launches ------------------------
+// what the rules of scan_plan.hpp read of a handle
+ScanIndexShape scan_shape_of(const vdb_index_s *h) {
+    ScanIndexShape s;
+    s.ksteps = h->ksteps; s.i8_ks = h->i8_ks; s.Npad = h->Npad; s.n_cus = h->n_cus;
+    s.tile16 = h->tile16; s.x16 = h->x16;
+    s.int8_only = h->int8_only; s.panels_streamed = h->panels_streamed; s.pq = h->pq.M > 0;
+    s.i8_ok = h->i8_ok;
+    return s;
+}
+
+// one row per instantiation of a family (the lists of scan_plan.hpp): its key and its kernel
+template <class... Args>
+struct ScanRow {
+    ScanKey key;
+    void (*kernel)(Args...);
 };
+#define VDB_ROW_SCAN(...) {ScanKey{{__VA_ARGS__}}, &scan_kernel<__VA_ARGS__>},
+#define VDB_ROW_SCAN16_KLOOP(...) {ScanKey{{__VA_ARGS__}}, &scan16_kloop_kernel<__VA_ARGS__>},
+#define VDB_ROW_SCAN_X16(...) {ScanKey{{__VA_ARGS__}}, &scan_x16_kernel<__VA_ARGS__>},
+#define VDB_ROW_SCAN_I8(...) {ScanKey{{__VA_ARGS__}}, &scan_i8_kernel<__VA_ARGS__>},
+#define VDB_ROW_SCAN_I8X16(...) {ScanKey{{__VA_ARGS__}}, &scan_i8x16_kernel<__VA_ARGS__>},
+#define VDB_ROW_SCAN_PAIR_X16(...) {ScanKey{{__VA_ARGS__}}, &scan_pair_x16_kernel<__VA_ARGS__>},
+constexpr ScanRow<ScanArgs> kRowsScan[] = {VDB_KERNELS_SCAN(VDB_ROW_SCAN)};
+constexpr ScanRow<ScanArgs, ScanKloopExtra> kRowsScan16Kloop[] = {VDB_KERNELS_SCAN16_KLOOP(VDB_ROW_SCAN16_KLOOP)};
+constexpr ScanRow<ScanArgs> kRowsScanX16[] = {VDB_KERNELS_SCAN_X16(VDB_ROW_SCAN_X16)};
+constexpr ScanRow<ScanI8Args> kRowsScanI8[] = {VDB_KERNELS_SCAN_I8(VDB_ROW_SCAN_I8)};
+constexpr ScanRow<ScanI8Args> kRowsScanI8x16[] = {VDB_KERNELS_SCAN_I8X16(VDB_ROW_SCAN_I8X16)};
+constexpr ScanRow<ScanArgs, ScanI8Args> kRowsScanPairX16[] = {VDB_KERNELS_SCAN_PAIR_X16(VDB_ROW_SCAN_PAIR_X16)};
+#undef VDB_ROW_SCAN
+#undef VDB_ROW_SCAN16_KLOOP
+#undef VDB_ROW_SCAN_X16
+#undef VDB_ROW_SCAN_I8
+#undef VDB_ROW_SCAN_I8X16
+#undef VDB_ROW_SCAN_PAIR_X16
 
-// nq: queries of the batch.  Small batches (serving-shaped: up to one 512-query tile) take FINER chunks, so that the
-// grid still covers the chip: at 8192 rows per chunk a 1M-row corpus gives 128 workgroups per query tile, half the CUs.
-ScanGeom scan_geometry(const vdb_index_s *h, int k, int64_t nq) {
-    ScanGeom g;
-    const int G = h->tile16 ? 4 : 2;                        // bins (lane groups) per span
-    g.nspans = h->Npad / (G * kBinRows);
-    if (g.nspans * G < 16) return g;
-    // superbins (G per chunk) must comfortably outnumber k and fit 16 values per lane in the select
-    int64_t spc_hi = g.nspans * G / (4 * (int64_t)k);       // nsb >= 4k
-    int64_t spc_lo = (g.nspans * G + 1023) / 1024;          // nsb <= 1024
-    if (spc_hi < 1 || spc_hi < spc_lo) return g;
-    int64_t spc_want = 32 / G;                              // 8192 rows per chunk
-    // (one query tile only: from 1024 queries on the batch shape is as fast or faster -- scripts/throughput_vs_batch.py)
-    if (nq <= 512 && h->opt.small_batch) spc_want = std::max<int64_t>(1, std::min<int64_t>(spc_want, g.nspans / 512));
-    int64_t spc = std::min<int64_t>(h->opt.spans_per_chunk > 0 ? h->opt.spans_per_chunk : spc_want, spc_hi);
-    spc = std::max<int64_t>(spc, spc_lo);
-    if (spc < 2 && g.nspans * G >= 128) spc = std::min<int64_t>(2, spc_hi);
-    int64_t nchunks = (g.nspans + spc - 1) / spc;
-    // deal the spans evenly over a multiple of 8 chunks (one XCD label each, see scan_kernel) when possible
-    if (nchunks >= 16) {
-        int64_t n8 = (nchunks + 7) / 8 * 8;
-        if (n8 * G <= 1024 && g.nspans / n8 >= 1) nchunks = n8;   // (more chunks only add superbins)
-    }
-    // batch shapes: the multi-lane select (select_kernel_v2) takes <= 256 superbins and is 3-4x faster than the one-wave form
-    // (GloVe-shaped 1.2M rows: 304 superbins -> 123 us of select_kernel<8> against ~35 us); chunks of up to twice the default
-    // length buy that for corpora of up to 2M rows
-    {
-        const int64_t cap = 256 / G;
-        if (nq > 512 && h->opt.spans_per_chunk == 0 && nchunks > cap && nchunks <= 2 * cap && cap * G >= 4 * (int64_t)k) nchunks = cap;
-    }
-    g.nchunks = (int)nchunks;
-    g.spc = (int)(g.nspans / nchunks);
-    g.rem = (int)(g.nspans - (int64_t)g.spc * nchunks);
-    if (g.spc < 1) return g;
-    const int nsb = G * g.nchunks;
-    g.vpl = 1;
-    while (g.vpl * 64 < nsb) g.vpl *= 2;
-    if (g.vpl > 16) return g;
-    g.ok = true;
-    return g;
+template <class Row, size_t N>
+auto scan_kernel_of(const Row (&rows)[N], const ScanLaunch &p) {
+    for (const Row &r : rows)
+        if (r.key == p.key) return r.kernel;
+    std::string what = kScanFamilyNames[(int)p.family];
+    for (int i = 0; i < kScanFamilyArgs[(int)p.family]; ++i) what += (i ? ", " : "<") + std::to_string(p.key.t[i]);
+    throw Error(VDB_ERR_INVALID, "internal: no scan kernel for " + what + ">");
 }
 
-// Direct-bin geometry: when N/256 superbins cannot outnumber k four to one, level-1 bins of 128 or 64 rows serve as
-// the superbins themselves (SelectArgs.direct_rows, up to 2048 of them); the chunking then only shapes the grid.
-// Returns the rows per bin, 0 if not applicable.
-int scan_geometry_direct(const vdb_index_s *h, int k, ScanGeom &g) {
-    const int G = h->tile16 ? 4 : 2;
-    // kernels with the finer bins: scan_kernel<.., BT> (32-row tiles, D <= 128) and scan16_kloop_kernel<.., FP> (p16, D > 128)
-    if (h->tile16 != (h->ksteps > kMaxKSteps)) return 0;
-    const int64_t nspans = h->Npad / (G * kBinRows);
-    if (nspans * G < 16) return 0;
-    for (int rows : {128, 64}) {
-        const int64_t nb = nspans * G * (kBinRows / rows);
-        if (nb >= 4 * (int64_t)k && nb <= 2048) {
-            g = ScanGeom{};
-            g.nspans = nspans;
-            int64_t nchunks = (nspans * G + 31) / 32;                 // ~8192 rows per chunk
-            if (nchunks >= 16) nchunks = (nchunks + 7) / 8 * 8;
-            nchunks = std::max<int64_t>(1, std::min<int64_t>(nchunks, nspans));
-            g.nchunks = (int)nchunks;
-            g.spc = (int)(nspans / nchunks);
-            g.rem = (int)(nspans - (int64_t)g.spc * nchunks);
-            g.vpl = 1;
-            while (g.vpl * 64 < nb) g.vpl *= 2;
-            g.ok = true;
-            return rows;
-        }
+// the one <<<>>> of the plan's family; sa: the fp16 scan's arguments, s8: the int8 scan's (the pair takes both)
+void launch(const ScanLaunch &p, const vdb_index_s *h, const ScanArgs *sa, const ScanI8Args *s8, hipStream_t st) {
+    const dim3 grid(p.grid), block(p.block);
+    ScanArgs a{};
+    ScanI8Args a8{};
+    if (sa) { a = *sa; a.nqtiles = p.nqtiles; }
+    if (s8) { a8 = *s8; a8.nqtiles = p.family == ScanFamily::scan_pair_x16 ? p.nqtiles8 : p.nqtiles; }
+    switch (p.family) {
+        case ScanFamily::scan: scan_kernel_of(kRowsScan, p)<<<grid, block, 0, st>>>(a); break;
+        case ScanFamily::scan16_kloop: scan_kernel_of(kRowsScan16Kloop, p)<<<grid, block, 0, st>>>(a, ScanKloopExtra{h->ksteps, p.qgroup}); break;
+        case ScanFamily::scan_x16: scan_kernel_of(kRowsScanX16, p)<<<grid, block, 0, st>>>(a); break;
+        case ScanFamily::scan_i8: scan_kernel_of(kRowsScanI8, p)<<<grid, block, 0, st>>>(a8); break;
+        case ScanFamily::scan_i8x16: scan_kernel_of(kRowsScanI8x16, p)<<<grid, block, 0, st>>>(a8); break;
+        case ScanFamily::scan_pair_x16: scan_kernel_of(kRowsScanPairX16, p)<<<grid, block, 0, st>>>(a, a8); break;
+        default: throw Error(VDB_ERR_INVALID, "internal: no scan kernel for an empty plan");
     }
-    return 0;
-}
-
-// 32-row-tile layout: 512-query workgroup tiles (8 waves, 4 tiles per LDS stage, 2 waves per SIMD) unless the batch is small
-template <int KSTEPS>
-void launch_scan_k(ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int bt = 16, int nw = 8, bool g8 = false) {
-    if (bt == 16 && nw < 8) {   // small batch: 64 * nw queries per workgroup, only the tiles that hold queries
-        sa.nqtiles = (int)((sa.nq_valid + nw * 64 - 1) / (nw * 64));
-        const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-        if (g8) {
-            if (nw == 1) scan_kernel<KSTEPS, 1, 4, 1, 16, false, true><<<dim3(grid), dim3(64), 0, st>>>(sa);
-            else if (nw == 2) scan_kernel<KSTEPS, 2, 4, 1, 16, false, true><<<dim3(grid), dim3(128), 0, st>>>(sa);
-            else scan_kernel<KSTEPS, 4, 4, 2, 16, false, true><<<dim3(grid), dim3(256), 0, st>>>(sa);
-            return;
-        }
-        if (nw == 1) scan_kernel<KSTEPS, 1, 4, 1><<<dim3(grid), dim3(64), 0, st>>>(sa);
-        else if (nw == 2) scan_kernel<KSTEPS, 2, 4, 1><<<dim3(grid), dim3(128), 0, st>>>(sa);
-        else scan_kernel<KSTEPS, 4, 4, 2><<<dim3(grid), dim3(256), 0, st>>>(sa);
-        return;
-    }
-    sa.nqtiles = (int)(Qpad / 512);
-    const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-    if (bt == 8) scan_kernel<KSTEPS, 8, 4, 2, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);   // direct-bin mode: finer level-1 bins (8 or 4 tiles)
-    else if (bt != 16) scan_kernel<KSTEPS, 8, 4, 2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa);
-    else if (g8) scan_kernel<KSTEPS, 8, 4, 2, 16, false, true><<<dim3(grid), dim3(512), 0, st>>>(sa);
-    else scan_kernel<KSTEPS, 8, 4, 2><<<dim3(grid), dim3(512), 0, st>>>(sa);
-}
-
-// candidate groups of the fp16 flat scan (D <= 128, 256-row bins): octs unless option "f16_group" = 4
-bool f16_octs(const vdb_index_s *h, int direct_rows) {
-    if (h->x16) return !direct_rows;  // (layout "x16": octs; direct-bin mode -- large k, the refine outweighs the scan -- takes the quads of the two blocks)
-    return h->opt.f16_group == 8 && !direct_rows && h->ksteps <= kMaxKSteps;
-}
-
-inline int st_tiles_of(const vdb_index_s *h) { return h->opt.f16_stage_tiles ? h->opt.f16_stage_tiles : (h->ksteps == 4 ? 8 : 4); }
-
-void launch_scan(vdb_index_s *h, ScanArgs &sa, int nchunks, int64_t Qpad, hipStream_t st, int direct_rows = 0, int nw = 8) {
-    const int bt = direct_rows ? direct_rows / 16 : 16;       // 32-row-tile layout: tiles per level-1 bin
-    if (h->ksteps > kMaxKSteps) {  // D > 128: p16 panels, 512-query tiles
-        // option kloop_qgroup = query tiles per group of the block order (0 -> default)
-        sa.nqtiles = (int)(Qpad / 512);
-        int qgroup = h->opt.kloop_qgroup > 0 ? h->opt.kloop_qgroup : 4;
-        qgroup = std::min(qgroup, sa.nqtiles);
-        const unsigned ngroups = (unsigned)((sa.nqtiles + qgroup - 1) / qgroup);
-        const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * ngroups * (unsigned)qgroup;
-        const ScanKloopExtra ex{h->ksteps, qgroup};
-        if (direct_rows) {      // finer level-1 bins
-            if (direct_rows == 128) scan16_kloop_kernel<2, 4><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-            else scan16_kloop_kernel<2, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-            VDB_HIP(hipGetLastError());
-            return;
-        }
-        if (sa.nq_valid > 0 && sa.nq_valid <= 16 && h->ksteps / 2 <= kNarrowMaxKS && h->opt.small_batch)
-            scan16_kloop_kernel<3, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-        else if (sa.nq_valid > 0 && sa.nq_valid < 64 && h->opt.small_batch)
-            scan16_kloop_kernel<2, 8, 1><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-        else
-            scan16_kloop_kernel<2><<<dim3(grid), dim3(512), 0, st>>>(sa, ex);
-    } else if (h->x16) {               // D <= 128 on layout "x16" (scan_x16.hpp)
-        const bool small = direct_rows == 0 && nw < 8;
-        // D <= 64, batch shape: 1024-query workgroup tiles (8 column blocks = 128 queries per wave) when the batch is a multiple of 1024
-        // and there are enough of them to cover the chip -- the rule of the int8 scan (option "f16_wide": 0 auto, 1 never)
-        const bool wide = !small && direct_rows == 0 && h->ksteps == 4 && h->opt.f16_wide != 1 && Qpad % 1024 == 0 &&
-                          (int64_t)nchunks * (Qpad / 1024) >= 256;
-        // tiles per LDS stage of the batch shape (option "f16_stage_tiles"): measured on the bench shapes (profiles/r04_sweeps.txt) D = 64:
-        // 8 tiles 1.108 ms against 1.163 with 4 (a 4-tile stage is only 16 KiB of panels per barrier); D = 128: 1.730 against 1.722
-        const int st_tiles = st_tiles_of(h);
-        sa.nqtiles = small ? (int)((sa.nq_valid + nw * 64 - 1) / (nw * 64)) : (int)(Qpad / (wide ? 1024 : 512));
-        const unsigned grid = 8u * (unsigned)((nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-        if (wide) {
-            if (st_tiles_of(h) == 8) scan_x16_kernel<2, 8, 8, 2, 256, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            else scan_x16_kernel<2, 8, 4, 2, 256, 8, 8><<<dim3(grid), dim3(512), 0, st>>>(sa);
-            VDB_HIP(hipGetLastError());
-            return;
-        }
-#define VDB_X16F(KS2_) do { \
-            if (small && nw == 1) scan_x16_kernel<KS2_, 1, 4, 1><<<dim3(grid), dim3(64), 0, st>>>(sa); \
-            else if (small && nw == 2) scan_x16_kernel<KS2_, 2, 4, 1><<<dim3(grid), dim3(128), 0, st>>>(sa); \
-            else if (small) scan_x16_kernel<KS2_, 4, 4, 2><<<dim3(grid), dim3(256), 0, st>>>(sa); \
-            else if (direct_rows == 128) scan_x16_kernel<KS2_, 8, 4, 2, 128, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
-            else if (direct_rows == 64) scan_x16_kernel<KS2_, 8, 4, 2, 64, 4><<<dim3(grid), dim3(512), 0, st>>>(sa); \
-            else if (st_tiles == 8) scan_x16_kernel<KS2_, 8, 8, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); \
-            else scan_x16_kernel<KS2_, 8, 4, 2><<<dim3(grid), dim3(512), 0, st>>>(sa); } while (0)
-        if (h->ksteps == 4) VDB_X16F(2);
-        else VDB_X16F(4);
-#undef VDB_X16F
-    } else if (h->ksteps == 4)
-        launch_scan_k<4>(sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
-    else
-        launch_scan_k<8>(sa, nchunks, Qpad, st, bt, nw, f16_octs(h, direct_rows));
     VDB_HIP(hipGetLastError());
 }
 
@@ -196,9 +92,7 @@ void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st) {
     VDB_HIP(hipEventRecord(e, st));
 }
 
-// PQ index (pq.inc): rows per slab of per-search panels, and the smallest batch that takes the panel pass + MFMA scan
-// (measured, profiles/r07_bench_pq.json)
-constexpr int64_t kPqSlabRows = 524288;
+// PQ index (pq.inc): the smallest batch that takes the panel pass + MFMA scan (measured, profiles/r07_bench_pq.json)
 constexpr int64_t kPqScanMinBatch = 1;
 
 // ---- one query batch ---------------------------------------------------------------------------------
@@ -214,6 +108,7 @@ struct Batch {
     hipStream_t st;
     RefineCommon rc;
     ScanGeom g;
+    ScanIndexShape shape;        // scan_shape_of(h)
     int direct_rows;
     int32_t *fb_count;
     unsigned long long *stat_counters;
@@ -491,13 +386,12 @@ void scan_in_slabs(const Batch &b, const ScanArgs &sa, int64_t Qpad, int nw_smal
         ss.panels = buf - (size_t)tile_a * ksl * 64;
         ss.chunk0 = (int)c0;
         ss.nchunks = (int)(c1 - c0);
-        launch_scan(h, ss, (int)(c1 - c0), Qpad, b.st, b.direct_rows, nw_small);
+        launch(plan_f16(b.shape, h->opt, (int)(c1 - c0), Qpad, b.nq, b.direct_rows, nw_small), h, &ss, nullptr, b.st);   // (planned per slab: its own chunk count)
     }
 }
 
-// step 2: the fp16 scan -- resident panels in one launch (or left to the paired launch of scan_i8: pair_candidate), per-search
-// panels slab by slab
-void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair_candidate) {
+// step 2: the fp16 scan -- resident panels in one launch, per-search panels slab by slab
+void scan_fp16(const Batch &b, const ScanArgs &sa, int64_t Qpad, int nw_small) {
     vdb_index_s *h = b.h;
     const ScanGeom &g = b.g;
     hipStream_t st = b.st;
@@ -510,20 +404,7 @@ void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pa
         // this single slab on a 12.5M x 768 shard, at 1.9 GB more: not kept.
         const int64_t KS = h->ksteps / 2;
         const int64_t chunk_rows = (int64_t)(g.spc + 1) * kSpanRows16;                  // (chunks are spc or spc + 1 spans)
-        const int64_t wgs_per_chunk = std::max<int64_t>(1, Qpad / 512);
-        // Slab size (option "stream_slab_rows", 0 = 1 280 000): the K-loop scan runs two 512-thread workgroups per CU and a
-        // workgroup of a 12.5M-row shard takes ~14.5 ms (chunks are ~50k rows: the select takes <= 1024 superbins), so a
-        // launch whose workgroup count PER XCD (chunk c runs on XCD c % 8) is not just below a multiple of 2 x 32 idles the
-        // chip for most of a round (measured, 10 000 queries = 20 workgroups per chunk: 16-chunk slabs 14.5 ms per launch,
-        // 25-chunk slabs -- four chunks on XCD 0 -- 23 ms).  Take the largest chunk count within `slab_rows` whose workgroups
-        // fill whole rounds; small query batches (few workgroups per chunk) go by rows alone.
-        const int64_t slab_rows = h->opt.stream_slab_rows > 0 ? h->opt.stream_slab_rows : 1280000;
-        int64_t slab_chunks = std::max<int64_t>(1, slab_rows / chunk_rows);
-        for (int r = 8; r >= 1; --r) {                       // (chunk c of a launch runs on XCD c % 8: count per XCD)
-            const int64_t fit = 8 * ((int64_t)2 * (h->n_cus / 8) * r / wgs_per_chunk);
-            if (fit >= 8 && fit <= slab_chunks) { slab_chunks = fit; break; }
-        }
-        slab_chunks = std::max<int64_t>(1, std::min<int64_t>(slab_chunks, g.nchunks));
+        const int64_t slab_chunks = stream_slab_chunks(b.shape, h->opt, g, Qpad);      // (option "stream_slab_rows": whole rounds of workgroups per XCD)
         h->scan.slab.reserve((size_t)slab_chunks * chunk_rows / kTileRows16 * KS * 64 * sizeof(half8));
         scan_in_slabs(b, sa, Qpad, nw_small, kTilesPerSpan16, KS, slab_chunks, [&](int64_t tile_a, int64_t ntiles, half8 *buf) {
             convert_slab16_kernel<<<dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st>>>(
@@ -563,135 +444,25 @@ void scan_fp16(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pa
         if (h->scan.slab.cap < slab_bytes) h->scan.slab.reserve_exact(slab_bytes);
         scan_in_slabs(b, sa, Qpad, nw_small, tiles_per_span, ksl, slab_chunks,
                       [&](int64_t tile_a, int64_t ntiles, half8 *buf) { launch_pq_panels(h, tile_a, ntiles, buf, st); });
-    } else if (!pair_candidate)
-        launch_scan(h, sa, g.nchunks, Qpad, st, b.direct_rows, nw_small);   // (fp16: returns at once when the int8 scan serves the batch)
+    } else
+        launch(plan_f16(b.shape, h->opt, g.nchunks, Qpad, b.nq, b.direct_rows, nw_small), h, &sa, nullptr, st);   // (fp16: returns at once when the int8 scan serves the batch)
 }
 
-// step 3: the int8 scan (byte-valued corpora), or the paired launch of both scans; the one the device did not choose for the
-// batch returns at once
-void scan_i8(const Batch &b, ScanArgs &sa, int64_t Qpad, int nw_small, bool pair_candidate) {
+// step 3: the arguments of the int8 scan (byte-valued corpora)
+ScanI8Args scan_i8_args(const Batch &b, const ScanArgs &sa, int64_t Qpad) {
     vdb_index_s *h = b.h;
-    Workspace &ws = b.ws;
     const ScanGeom &g = b.g;
-    const int64_t nq = b.nq;
-    hipStream_t st = b.st;
     ScanI8Args s8{};
     s8.panels = h->scan.panels8.as<int4v>();
     s8.bias8 = h->scan.bias8.as<int32_t>();
-    s8.qpanels = ws.qpanels8.as<int4v>();
+    s8.qpanels = b.ws.qpanels8.as<int4v>();
     s8.info = sa.info;
     s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
     s8.sb_m1 = sa.sb_m1; s8.sb_m2 = sa.sb_m2; s8.sb_span = sa.sb_span;
-    s8.nspans = g.nspans; s8.Npad = h->Npad; s8.Qpad = Qpad; s8.nq_valid = nq;
+    s8.nspans = g.nspans; s8.Npad = h->Npad; s8.Qpad = Qpad; s8.nq_valid = b.nq;
     s8.prio = h->opt.scan_prio;
     s8.spans_per_chunk = g.spc; s8.chunk_rem = g.rem; s8.nchunks = g.nchunks;
-    // i8_variant (tuning, every variant exact; scripts/sweep_i8.py): 0 = 512-query tiles (2 column blocks per wave),
-    // 4-tile stages; 1 = 8-tile stages; 2 = 1024-query tiles (4 column blocks per wave); 3 = both (default);
-    // 4 / 5 = 16 waves per workgroup (4 per SIMD) with 8- / 16-tile stages.  Odd batch sizes keep 512-query tiles.
-    int v8 = h->opt.i8_variant;
-    if (h->x16) {
-        // layout "x16" (scan_i8x16.hpp, v_mfma_i32_16x16x64_i8): the same launch shapes -- batch: 512- or 1024-query tiles
-        // (4 or 8 column blocks of 16 queries per wave), 4- or 8-tile stages (i8_variant bits as below, 4 / 5 -> 3);
-        // serving: 1 / 2 / 4 waves of 64 queries, 4-stage staging ring (option "i8_ring": 2, 4, 8), non-temporal loads
-        int v = h->opt.i8_variant & 3;
-        if (h->opt.i8_variant == 4 || h->opt.i8_variant == 5) v = 3;
-        if (Qpad % 1024 != 0) v &= 1;
-        if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v &= 1;
-        const int qtile = nw_small < 8 ? 64 * nw_small : (v >= 2) ? 1024 : 512;
-        s8.nqtiles = (int)((nw_small < 8 ? nq + qtile - 1 : Qpad) / qtile);
-        const dim3 gridx(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-        const bool nt = h->opt.i8_nt != 1;
-        const int ring = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring;
-#define VDB_X16B(KS2_) do { \
-            if (v == 3) scan_i8x16_kernel<KS2_, 8, 8><<<gridx, dim3(512), 0, st>>>(s8); \
-            else if (v == 2) scan_i8x16_kernel<KS2_, 4, 8><<<gridx, dim3(512), 0, st>>>(s8); \
-            else if (v == 1) scan_i8x16_kernel<KS2_, 8, 4><<<gridx, dim3(512), 0, st>>>(s8); \
-            else scan_i8x16_kernel<KS2_, 4, 4><<<gridx, dim3(512), 0, st>>>(s8); } while (0)
-#define VDB_X16S(KS2_, NW_) do { \
-            if (ring == 2) scan_i8x16_kernel<KS2_, 4, 4, NW_><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-            else if (ring == 8 && NW_ >= 2) scan_i8x16_kernel<KS2_, 4, 4, NW_, (NW_ >= 2 ? 8 : 4)><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-            else if (nt) scan_i8x16_kernel<KS2_, 4, 4, NW_, 4, 2><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); \
-            else scan_i8x16_kernel<KS2_, 4, 4, NW_, 4><<<gridx, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
-#define VDB_X16(KS2_) do { \
-            if (nw_small == 1) VDB_X16S(KS2_, 1); else if (nw_small == 2) VDB_X16S(KS2_, 2); \
-            else if (nw_small == 4) VDB_X16S(KS2_, 4); else VDB_X16B(KS2_); } while (0)
-        if (pair_candidate && (nw_small < 8 || v == 3 || v == 1)) {
-            const bool small = nw_small < 8;
-            sa.nqtiles = small ? (int)((nq + nw_small * 64 - 1) / (nw_small * 64)) : (int)(Qpad / 512);
-            const unsigned grid16 = 8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)sa.nqtiles;
-            const dim3 gridp(std::max(grid16, gridx.x));
-#define VDB_PAIR(W_) do { \
-                if (nw_small == 1) scan_pair_x16_kernel<W_, 1, 4, 4, 4, 4, 2><<<gridp, dim3(64), 0, st>>>(sa, s8); \
-                else if (nw_small == 2) scan_pair_x16_kernel<W_, 2, 4, 4, 4, 4, 2><<<gridp, dim3(128), 0, st>>>(sa, s8); \
-                else if (nw_small == 4) scan_pair_x16_kernel<W_, 4, 4, 4, 4, 4, 2><<<gridp, dim3(256), 0, st>>>(sa, s8); \
-                else if (v == 3) scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 8, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); \
-                else scan_pair_x16_kernel<W_, 8, (W_ ? 4 : 8), 8, 4, 2, 0><<<gridp, dim3(512), 0, st>>>(sa, s8); } while (0)
-            if (h->i8_ks == 4) VDB_PAIR(true);
-            else VDB_PAIR(false);
-#undef VDB_PAIR
-            VDB_HIP(hipGetLastError());
-        } else {
-        if (pair_candidate) {      // (a shape the paired kernel is not built for: the fp16 scan as its own launch, as ever)
-            pair_candidate = false;
-            launch_scan(h, sa, g.nchunks, Qpad, st, b.direct_rows, nw_small);
-        }
-        if (h->i8_ks == 2) VDB_X16(1);
-        else VDB_X16(2);
-#undef VDB_X16B
-#undef VDB_X16S
-#undef VDB_X16
-        VDB_HIP(hipGetLastError());
-        }
-    } else {
-    const int tb8 = v8 == 6 ? 1 : v8 == 7 ? 2 : 0;             // 6 / 7: variant 3 with a pacing barrier per 1 / 2 tiles
-    if (tb8) v8 = 3;
-    if (Qpad % 1024 != 0) v8 &= 1;
-    if ((int64_t)g.nchunks * (Qpad / 1024) < 256) v8 &= 1;     // too few 1024-query tiles to cover the chip: 512-query tiles
-    if (nw_small < 8) v8 = 8 + nw_small;
-    const int qtile = (v8 > 8) ? 64 * nw_small : (v8 >= 2) ? 1024 : 512;
-    s8.nqtiles = (int)((v8 > 8 ? nq + qtile - 1 : Qpad) / qtile);
-    const dim3 grid8(8u * (unsigned)((g.nchunks + 7) / 8) * (unsigned)s8.nqtiles);
-#define VDB_I8G(KS_, ST_, CB_, NW_, G_) scan_i8_kernel<KS_, ST_, CB_, NW_, 16, false, G_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8)
-#define VDB_I8(KS_, ST_, CB_, NW_) do { if (h->opt.i8_group == 8) VDB_I8G(KS_, ST_, CB_, NW_, 8); else VDB_I8G(KS_, ST_, CB_, NW_, 4); } while (0)
-    // serving shapes (1 / 2 / 4 waves per workgroup): the scan streams the copy once -- 4- or 8-stage staging ring
-    // (option "i8_ring": 0 = auto (4), 2 = the double buffer of the batch shape, 4, 8)
-#define VDB_I8R(KS_, NW_, R_) do { if (h->opt.i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
-                               else scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 4, 0, R_><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); } while (0)
-    // (the wait for a stage is s_waitcnt vmcnt((ring - 2) x requests per wave and stage), a 6-bit counter: a one-wave
-    //  workgroup issues all 16 + 2 requests of a 4-tile stage itself, which caps its ring at 4)
-#define VDB_I8S(KS_, NW_) do { const int r__ = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring; \
-                           if (r__ == 2) VDB_I8(KS_, 4, 2, NW_); else if (r__ == 8) VDB_I8R(KS_, NW_, (NW_ >= 2 ? 8 : 4)); \
-                           else if (nt8 && h->opt.i8_group == 8) scan_i8_kernel<KS_, 4, 2, NW_, 16, false, 8, 0, 4, 2><<<grid8, dim3(NW_ * 64), 0, st>>>(s8); \
-                           else VDB_I8R(KS_, NW_, 4); } while (0)
-    // serving shapes read every panel byte once per search: non-temporal staging loads (option "i8_nt": 0 / 2 on, 1 off).
-    // Measured in one process (scripts/sweep_serving_hbm.py): single-query scan of 4M x 128 (512 MB, HBM) 106.2 -> 96.7 us
-    // = 4.8 -> 5.3 TB/s; of 1M x 128 (128 MB, Infinity-Cache resident between searches) 33.9 -> 33.3 us
-    const bool nt8 = h->opt.i8_nt != 1;
-    if (tb8 && v8 == 3 && h->opt.i8_group == 8) {
-        if (h->i8_ks == 2) {
-            if (tb8 == 1) scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
-            else scan_i8_kernel<2, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
-        } else {
-            if (tb8 == 1) scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 1><<<grid8, dim3(512), 0, st>>>(s8);
-            else scan_i8_kernel<4, 8, 4, 8, 16, false, 8, 2><<<grid8, dim3(512), 0, st>>>(s8);
-        }
-    } else if (h->i8_ks == 2) {
-        switch (v8) { case 1: VDB_I8(2, 8, 2, 8); break; case 2: VDB_I8(2, 4, 4, 8); break; case 3: VDB_I8(2, 8, 4, 8); break;
-                      case 4: VDB_I8(2, 8, 2, 16); break; case 5: VDB_I8(2, 16, 2, 16); break;
-                      case 9: VDB_I8S(2, 1); break; case 10: VDB_I8S(2, 2); break; case 12: VDB_I8S(2, 4); break;
-                      default: VDB_I8(2, 4, 2, 8); }
-    } else {
-        switch (v8) { case 1: VDB_I8(4, 8, 2, 8); break; case 2: VDB_I8(4, 4, 4, 8); break; case 3: VDB_I8(4, 8, 4, 8); break;
-                      case 4: VDB_I8(4, 8, 2, 16); break; case 5: VDB_I8(4, 16, 2, 16); break;
-                      case 9: VDB_I8S(4, 1); break; case 10: VDB_I8S(4, 2); break; case 12: VDB_I8S(4, 4); break;
-                      default: VDB_I8(4, 4, 2, 8); }
-    }
-#undef VDB_I8G
-#undef VDB_I8
-#undef VDB_I8R
-#undef VDB_I8S
-    VDB_HIP(hipGetLastError());
-    }
+    return s8;
 }
 
 // step 4: candidates per query from the bin minima
@@ -726,7 +497,7 @@ SelectArgs scan_select(const Batch &b, const ScanArgs &sa, int64_t Qpad, int can
     }
     se.cand_cap = cand_cap;
     se.rescan_cap = rescan_cap;
-    se.f16_gmode = f16_octs(h, b.direct_rows) ? 4 : 0;
+    se.f16_gmode = f16_octs(b.shape, h->opt, b.direct_rows) ? 4 : 0;
     se.cand_rows = ws.cand.as<int32_t>();
     se.rescan_rows = ws.rescan.as<int32_t>();
     se.counts = ws.counts.as<int32_t>();
@@ -877,9 +648,7 @@ void search_scan(const Batch &b) {
     const int64_t nbins = g.nspans * G * (b.direct_rows ? kBinRows / b.direct_rows : 1), nsb = (int64_t)g.nchunks * G;
     const int cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : std::max(64, 2 * k + 32);
     const int rescan_cap = std::max(16, k / 2 + 8);
-    // int8 scan for byte-valued corpora: offered to the device-side choice whenever the standard geometry is in use
-    const bool i8_off = h->opt.panel_dtype && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
-    const bool use_i8 = h->i8_ok && !i8_off && !b.direct_rows && !h->tile16;
+    const bool i8 = use_i8(b.shape, h->opt, b.direct_rows);
     ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
     ws.eps.reserve((size_t)nq * sizeof(float));
     ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
@@ -894,7 +663,7 @@ void search_scan(const Batch &b) {
     ws.fb_list.reserve((size_t)nq * sizeof(int32_t));
 
     QueryBatchInfo *info = batch_info(ws);              // (zeroed with fb_count above)
-    scan_query_prep(b, Qpad, use_i8, info);
+    scan_query_prep(b, Qpad, i8, info);
 
     ScanArgs sa{};
     sa.panels = h->scan.panels.as<half8>();
@@ -914,14 +683,19 @@ void search_scan(const Batch &b) {
     sa.nq_valid = nq;
     sa.prio = h->opt.scan_prio;
     timing_mark(h, b.tslot, 0, st);
-    // small batches: as many waves per workgroup as there are 64-query column groups (1, 2, 4; 8 = the batch shape)
-    const int nw_small = !h->opt.small_batch ? 8 : nq <= 64 ? 1 : nq <= 128 ? 2 : nq <= 256 ? 4 : 8;
-    // layout "x16" with both scan copies resident: ONE launch holds both scans (scan_pair_x16_kernel, scan_x16.hpp) when every tuning
-    // option is at its default; otherwise (and on the 32-row layout) both are enqueued and the one not needed returns at once
-    const bool pair_candidate = h->x16 && use_i8 && !h->int8_only && !h->panels_streamed && b.direct_rows == 0 &&
-                          h->opt.scan_pair && h->opt.i8_ring == 0 && h->opt.i8_nt == 0 && h->opt.f16_stage_tiles == 0 && h->opt.i8_variant == 3;
-    scan_fp16(b, sa, Qpad, nw_small, pair_candidate);
-    if (use_i8) scan_i8(b, sa, Qpad, nw_small, pair_candidate);
+    // the scan the device did not choose for the batch returns at once; layout "x16" with both copies resident: both in ONE launch
+    const int nw = nw_small(h->opt, nq);
+    const ScanLaunch pair = plan_pair(b.shape, h->opt, g.nchunks, Qpad, nq, b.direct_rows, nw);
+    if (pair.family != ScanFamily::none) {
+        const ScanI8Args s8 = scan_i8_args(b, sa, Qpad);
+        launch(pair, h, &sa, &s8, st);
+    } else {
+        scan_fp16(b, sa, Qpad, nw);
+        if (i8) {
+            const ScanI8Args s8 = scan_i8_args(b, sa, Qpad);
+            launch(plan_i8(b.shape, h->opt, g.nchunks, Qpad, nq, nw), h, nullptr, &s8, st);
+        }
+    }
     timing_mark(h, b.tslot, 1, st);
     const SelectArgs se = scan_select(b, sa, Qpad, cand_cap, rescan_cap);
     scan_refine_tail(b, se);
@@ -957,14 +731,15 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     }
 
     ScanGeom g;
+    const ScanIndexShape shape = scan_shape_of(h);
     // (PQ: a batch below "pq_scan_min_batch" takes the exact kernels on the codes instead of decoding the corpus for it -- DESIGN 4.9)
     const bool pq_small = pq_on(h) && h->opt.force_path != 2 && nq < (h->opt.pq_scan_min_batch > 0 ? h->opt.pq_scan_min_batch : kPqScanMinBatch);
     const bool exact_only = h->opt.force_path == 1 || h->opt.force_path == 3 || pq_small;   // 3: also without query blocking (A/B runs)
     bool use_scan = h->scan_ok && !exact_only && k <= 1024;
     int direct_rows = 0;
     if (use_scan) {
-        g = scan_geometry(h, k, nq);
-        if (!g.ok) direct_rows = scan_geometry_direct(h, k, g);
+        g = scan_geometry(shape, h->opt, k, nq);
+        if (!g.ok) direct_rows = scan_geometry_direct(shape, h->opt, k, g);
     }
     // (measured on 1M x 128 with host I/O: the MFMA pipeline answers 1..512 queries in 0.13..0.18 ms, the exhaustive float64
     //  kernel needs 0.3 ms for one query -- scripts/latency_small_batches.py -- so the batch size does not gate the path)
@@ -1000,7 +775,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->scan.panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
                            h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= h->N &&
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
-    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc};
+    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, shape, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc};
     if (use_dense) search_dense(b);
     else if (!use_scan) search_exact(b);
     else search_scan(b);

@@ -238,64 +238,7 @@ struct Workspace {
     DevBuf adc_tab{"ws.adc_tab"};           // PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
 };
 
-// ---- options -----------------------------------------------------------------------------------------------------------------
-// Everything vdb_set_option writes and nothing else: one member per option, under the name the caller passes, holding the
-// value the caller passed; the initializer is the value of an option never set.  What the library derives from an option at
-// the next add (int8_only, panels_streamed, x16, ivf_tps ...) is state of vdb_index_s.  kOptions (behind vdb_index_s)
-// has one row per member: what each accepts is written there, what each does in include/vdbhip.h.
-struct Options {
-    // behaviour
-    int force_path = 0, timing = 0, list_cap = 0;
-    int panel_dtype = 0;                     // 1: the int8 scan copy is not used (NOT inverted: non-zero switches the int8 scan off)
-    // "int8_only" (takes effect at the next add; flat index, D <= 128, > 32768 rows, byte-valued corpus): only the int8 copies
-    // are kept -- rows8 + panels8 + their biases, 0.55x the float32 corpus instead of 3x.  Integer query batches run as on the
-    // default index; a batch with a non-integer value is scanned in fp16 over slabs converted from the int8 panels per search;
-    // the exact kernels read x = byte + cx from the int8 rows (same float64 chains, same keys).  One add builds it (no append).
-    int int8_only = 0;
-    int int8_slab_chunks = 0;                // scan chunks per converted fp16 slab (0 = default 8)
-    int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests)
-    // "stream_panels" (D > 128, takes effect at the next add): the fp16 panels are NOT kept -- every search converts the
-    // float32 rows slab by slab into one scratch slab and scans it (search_flat.inc).  Halves the footprint of a non-fp16-exact
-    // corpus (the float32 rows must stay for the exact refine) at the price of one conversion pass per batch.
-    int stream_panels = 0;
-    int64_t stream_slab_rows = 0;            // rows of that slab (0 = default); the one option without an upper bound
-    int upload_block_mb = 0;                 // staging block of upload_rows (0 = default 64 MiB)
-    int small_batch = 1;                     // 0: batches <= 512 queries keep the batch-shaped grid
-    int fused_stats = 1;                     // 0 (A/B): small batches keep the separate statistics dispatch
-    int ivf_min_batch = 1;                   // smallest query batch the list-major MFMA scan serves
-    // "graph": a device-resident search that repeats with the same shape and buffers (a serving loop) is captured into a
-    // hipGraph on its second call and replayed from the third (graph_or_run)
-    int graph = 0;
-    int graph_recapture_at_once = 0;         // diagnostic: the pre-round-3 ordering (see graph_or_run)
-    int lsh_force_fallback = 0;              // every query of an LSH call takes the exact fallback of the select
-    int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
-    int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
-    int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)
-    // k-NN graph (knng.inc)
-    int knng_nentry = 0;                     // entry points of a search (0 = default 32)
-    int knng_max_iters = 0;                  // step cap of a search (0 = default 8 ef)
-    int knng_visited_bits = 0;               // log2 slots of the per-query seen filter (0 = default)
-    int knng_build_block = 0;                // rows per self-search block of the build (0 = default)
-    // tuning of the flat scans
-    int i8_variant = 3;                      // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)
-    int i8_group = 8, f16_group = 8;         // rows per select group of the int8 / fp16 flat scan (4 or 8)
-    int flat_shape = 0;                      // (alias "i8_shape"; before vdb_add) MFMA shape of the flat scans for D <= 128: 0 auto (16) | 16 | 32
-    int scan_pair = 1;                       // 0: never the paired launch of the two x16 scans (A/B, diagnosis)
-    int scan_prio = 0;                       // x16 kernels: issue priority of one half of the workgroup's waves
-    int f16_wide = 0;                        // x16 fp16 batch scan, D <= 64: 0 auto (1024-query tiles when they fit), 1 never
-    int f16_stage_tiles = 0;                 // x16 fp16 batch scan: tiles per LDS stage, 0 auto | 4 | 8
-    int i8_nt = 0;                           // non-temporal staging loads of the serving-shaped int8 scan (0 auto, 1 never, 2 always)
-    int i8_ring = 0;                         // LDS staging stages of the streaming-shaped int8 scans (0 auto, 2, 4, 8)
-    int select_variant = 0, spans_per_chunk = 0, kloop_qgroup = 0;      // grid shaping
-    // tuning of the IVF list scans
-    int ivf_bt = 0;                          // tiles per level-1 bin (0 auto, 4, 16)
-    int ivf_part = 0;                        // spans per row part (0 auto)
-    int ivf_tps = 0;                         // D > 128, next add: p16 tiles per span of the panel space (0 auto, 16, 64)
-    int ivf_tile = 0;                        // workgroup tile of the D > 128 scan on 256-row spans (0 / 2 square, 1 = 128 x 512)
-    int ivf_i8_group = 4;                    // rows per candidate group of the int8 list scan (4 | 8)
-    int ivf_group = 0;                       // rows per candidate group of the D > 128 list scan (0 auto, 1, 2, 4)
-    int ivf_nw = 0;                          // waves per IVF work item (0 auto, 2 / 4 / 8)
-};
+// (struct Options -- everything vdb_set_option writes -- is in scan_plan.hpp: the launch rules of the flat scans read it)
 
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
 
