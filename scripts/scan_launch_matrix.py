@@ -2,7 +2,7 @@
 """Which kernels a flat search launches, over a reduced matrix of index layouts, batch sizes and tuning options.
 
     python scripts/scan_launch_matrix.py                     walk the matrix (`force_path` = 2, census-sized corpora: milliseconds a search)
-    python scripts/scan_launch_matrix.py --compare A B OUT   compare two kernel traces of that walk, entry for entry
+    python scripts/scan_launch_matrix.py --compare A B OUT   compare two kernel traces of that walk (or of scripts/trace_ivf_paths.py), entry for entry
 
 Meant to run once per build under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python scripts/scan_launch_matrix.py`
 (alone, no counters): two builds launch the same kernels when the sequences of (kernel name, grid, workgroup size) in their traces
@@ -86,11 +86,18 @@ def walk():
 
 
 def launches(trace_dir):
-    """[(kernel name, grid, workgroup size)] of a rocprofv3 kernel trace, in launch order."""
+    """[(kernel name, grid, workgroup size)] of a rocprofv3 kernel trace, in launch order.  A walk that launches from several host
+    threads (scripts/trace_ivf_paths.py: one thread per shard of a two-shard index) is ordered thread by thread: how the threads
+    interleave on the device varies from run to run of ONE build, what each of them launches does not.  The threads are taken in the
+    order of what they launched, not of their ids."""
     files = glob.glob(str(Path(trace_dir) / "**" / "*kernel_trace.csv"), recursive=True)
     assert len(files) == 1, files
-    rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Dispatch_Id"]))
-    return [(r["Kernel_Name"], tuple(int(r[f"Grid_Size_{a}"]) for a in "XYZ"), tuple(int(r[f"Workgroup_Size_{a}"]) for a in "XYZ")) for r in rows]
+    per_thread = {}
+    for r in sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Dispatch_Id"])):
+        per_thread.setdefault(r["Thread_Id"], []).append(
+            (r["Kernel_Name"], tuple(int(r[f"Grid_Size_{a}"]) for a in "XYZ"), tuple(int(r[f"Workgroup_Size_{a}"]) for a in "XYZ")))
+    threads = sorted(per_thread.values(), key=lambda L: (-len(L), L))       # (the walk's own thread first)
+    return [x for L in threads for x in L]
 
 
 def compare(a, b, out):

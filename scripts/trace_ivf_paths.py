@@ -3,7 +3,7 @@
 128-row bins, 2 / 4 / 8 waves; int8 list scan: integer and non-integer batches, and switched off by
 "panel_dtype"; K-loop: 256- and 1024-row spans, the square tile, groups of 1 / 2 / 4 rows; SQ8 at D <= 128 and D > 128; exact list scan with one and several splits; the flagged-query
 fallback; a second batch inside one call; partial results through a two-shard index; the plan with and without the LDS
-histogram), for a run under `rocprofv3 --kernel-trace --stats`: two builds of the library that enqueue the same work give
+histogram; the int8 list scan's rings 2 / 8 and octs; row parts chosen above 2048 and above 4096 work items), for a run under `rocprofv3 --kernel-trace --stats`: two builds of the library that enqueue the same work give
 the same kernel names and call counts.  Prints a running checksum of every result so that the outputs can be compared too.
 Usage: rocprofv3 --kernel-trace --stats -d DIR -- python scripts/trace_ivf_paths.py"""
 import sys, zlib
@@ -75,4 +75,17 @@ idx = ivf(X, 64, device=[0, 0]); run("two_shards", idx, Q, 16); run("two_shards_
 for nlist in (2100, 8200):                                # plan: LDS histogram (full pairs per block) | separate kernels
     X, Q = gauss(5 * nlist, 64), gauss(300, 64)
     idx = ivf(X, nlist); run(f"nlist{nlist}", idx, Q, 16); idx.close()
+# branches of csrc/ivf_plan.hpp the walk above does not reach (tests/host/ivf_plan_main.cpp says which)
+X, Qi = byte_rows(20000, 128), byte_rows(300, 128)        # int8 list scan: rings 2 / 8, octs
+idx = ivf(X, 64)
+for ring in (2, 8):
+    run("i8_ring", idx, Qi, 8, i8_ring=ring)
+run("i8_octs", idx, Qi, 8, i8_ring=0, ivf_i8_group=8); idx.close()
+for nlist in (2100, 8200):                                # row parts by work items: above 2048 and above 4096 items, one list of 13 spans
+    X, Q = gauss(5 * nlist + 3000, 64), gauss(300, 64)
+    X[-3000:] = X[0] + 0.01 * X[-3000:]
+    idx = ivf(X, nlist)
+    for bt in (4, 16):
+        run(f"parts_nlist{nlist}", idx, Q, 16, k=5, ivf_bt=bt)
+    idx.close()
 print(f"checksum {crc:08x}")

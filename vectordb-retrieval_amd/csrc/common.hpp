@@ -8,6 +8,7 @@
 #include <string>
 
 #include "scan_plan.hpp"      // the geometry constants the launch rules use: kSpanRows, kBinRows, kTilesPerSpan, kSpanRows16, kTilesPerSpan16, kMaxKSteps
+#include "ivf_plan.hpp"       // ... of the IVF list scans: kIvfTilesPerSpan, kIvfSpanRows, kIvfLdsLists, kIvfPairsPerBlock, kIvfMaxProbes, kIvfKloop*
 
 namespace vdb {
 
@@ -26,12 +27,8 @@ constexpr int kTileRows = 32;
 // layout "p16" (16-row tiles for v_mfma_f32_16x16x32_f16): span = 64 tiles = 1024 rows = four 256-row bins, one
 // per lane group g = lane>>4 of the 16x16 C/D layout
 constexpr int kTileRows16 = 16;
-// IVF panel space (D <= 128): every inverted list is padded to whole spans, so its spans are SMALLER -- 8 tiles = 256 rows,
-// each lane half walking 128 consecutive rows: k-means lists of ~750 rows then carry 2 % of padding instead of 36 %
-// (512-row spans padded the median list of the SIFT1M / nlist 1024 index from 752 to 1024 rows).  Same row mapping inside a
-// span as the flat layout with 16 -> kIvfTilesPerSpan tiles.
-constexpr int kIvfTilesPerSpan = 8;
-constexpr int kIvfSpanRows = kIvfTilesPerSpan * kTileRows;
+// (IVF panel space, D <= 128: spans of kIvfTilesPerSpan = 8 tiles = kIvfSpanRows = 256 rows, ivf_plan.hpp)
+static_assert(kIvfSpanRows == kIvfTilesPerSpan * kTileRows, "the IVF panel space is made of 32-row tiles");
 constexpr int kStageTiles = 4;      // tiles per LDS stage (128 MFMA rows)
 constexpr float kPadBias = 1.0e38f; // accumulator init of padding rows (scan units): never selected
 

@@ -212,9 +212,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
     index_stats(h, st);
     if (h->nonfinite) return;
     const int nlist = h->nlist;
-    h->ivf_tps = 0;
-    if (h->tile16) h->ivf_tps = (h->opt.ivf_tps == 16 || h->opt.ivf_tps == 64) ? h->opt.ivf_tps
-                                : ((double)h->N / nlist > 2048.0 ? 64 : 16);
+    h->ivf_tps = h->tile16 ? ivf_tps_of(h->opt, h->N, nlist) : 0;
     const int span_rows = h->tile16 ? h->ivf_tps * 16 : kIvfSpanRows;
     h->ivf_span_rows = span_rows;
     std::vector<int32_t> pspan0((size_t)nlist + 1, 0), row0, valid;
@@ -280,76 +278,40 @@ void ivf_build_panel_space(vdb_index_s *h) {
     h->ivf_mfma_ok = true;
 }
 
-constexpr int kIvfKloopGroupRows = 1;  // default candidate group of the D > 128 list scan on 64-row bins (measured: DESIGN 4.4, round 4)
-constexpr int kIvfMaxEntries = 4096;   // bins per query the select keeps in LDS
-
-// geometry of one batch on the list-major path (ok = false: the batch takes the exact list scan)
-struct IvfGeom {
-    bool ok = false, kloop = false;
-    int bt = 16, bps = 1, bins_per_span = 2, bin_rows = 256, nw = 2, group = 128, run_groups = 0;
-    int64_t pairs = 0, max_items = 0, max_slots = 0, max_bins = 0;
-    size_t bin_bytes = 0, cnt_words = 0;
-};
 constexpr size_t kZeroSmall = (kSmallBytes + 127) / 128 * 128;     // stride of the two ws.small views inside ivf_zero
 
-IvfGeom ivf_geometry(const vdb_index_s *h, int64_t nb, int k, int nprobe) {
-    IvfGeom g;
-    if (!h->ivf_mfma_ok || h->opt.force_path == 1 || h->opt.force_path == 3 || nb < h->opt.ivf_min_batch || k > 256 || nprobe > kIvfMaxProbes) return g;
-    const int nlist = h->nlist;
-    const double avg_pspans = (double)h->ivf_pspans / (double)nlist;
-    const bool kloop = h->tile16;                                 // D > 128: ivf_kloop_scan_kernel on p16 panels
-    // bin size: 128 rows (bt = 8: one bin per half of a 256-row span) when the probed lists still give >= 8k bins per
-    // query, else 64 rows (bt = 4)
-    int bt = kIvfTilesPerSpan;
-    if ((double)nprobe * (double)h->ivf_span_rows / 128.0 * avg_pspans < 8.0 * k) bt = 4;
-    if (h->opt.ivf_bt == 4) bt = 4;                                    // option "ivf_bt" (A/B, both exact): 4, or 16 = the largest
-    else if (h->opt.ivf_bt == 16) bt = kIvfTilesPerSpan;
-    const int bps = kIvfTilesPerSpan / bt;
-    // level-1 bins of a panel span and rows per bin (p16: one bin per lane group, fixed by the span size of the build)
-    const int bins_per_span = kloop ? 4 : 2 * bps;
-    const int bin_rows = kloop ? h->ivf_tps * 4 : bt * 16;
-    const double est_entries = (double)nprobe * bins_per_span * avg_pspans;
-    if (est_entries < 4.0 * k || est_entries > 0.7 * kIvfMaxEntries) return g;
-    const int64_t pairs = nb * nprobe;
-    // waves per work item (64 query slots each): every probed list gets ceil(pairs of the list / (64 nw)) items, so a
-    // group much larger than the typical number of pairs per list wastes MFMA work on padding slots; a smaller group
-    // streams the list's panels more often (from L2).  Option "ivf_nw" forces 2 / 4 / 8.
-    const double per_list = (double)pairs / nlist;
-    int nw = 2;
-    {   // padded slots of a typical list, with a 5 % preference per doubling of the group (measured, scripts/sweep_ivf.py:
-        // nprobe 8 / 32 / 128 at nlist 1024 and 10k queries -> 2 / 2 / 4 waves)
-        double best = 1.0e300;
-        for (int cand : {2, 4, 8}) {
-            const double slots = std::ceil(per_list / (64.0 * cand)) * 64.0 * cand;
-            const double cost = slots * (cand == 2 ? 1.10 : (cand == 4 ? 1.05 : 1.0));
-            if (cost < best) {
-                best = cost;
-                nw = cand;
-            }
-        }
+// ---- path, geometry, capacities and launch shapes of a batch: ivf_plan.hpp decides, this file reserves, fills arguments and launches ----
+// what the rules of ivf_plan.hpp read of a handle
+IvfIndexShape ivf_shape_of(const vdb_index_s *h) {
+    IvfIndexShape s;
+    s.mfma_ok = h->ivf_mfma_ok; s.tile16 = h->tile16; s.nlist = h->nlist; s.N = h->N;
+    s.pspans = h->ivf_pspans; s.max_pspans = h->ivf_max_pspans; s.span_rows = h->ivf_span_rows; s.tps = h->ivf_tps;
+    s.ksteps = h->ksteps; s.i8_ks = h->i8_ks;
+    s.has_i8 = h->i8_ok && h->scan.panels8.p != nullptr;
+    return s;
+}
+
+// one row per instantiation of a family (the lists of ivf_plan.hpp): its key and its kernel
+#define VDB_ROW_IVF_SCAN(...) {ScanKey{{__VA_ARGS__}}, &scan_kernel<__VA_ARGS__>},
+#define VDB_ROW_IVF_SCAN_I8(...) {ScanKey{{__VA_ARGS__}}, &scan_i8_kernel<__VA_ARGS__>},
+#define VDB_ROW_IVF_KLOOP(...) {ScanKey{{__VA_ARGS__}}, &ivf_kloop_scan_kernel<__VA_ARGS__>},
+constexpr ScanRow<ScanArgs> kRowsIvfScan[] = {VDB_KERNELS_IVF_SCAN(VDB_ROW_IVF_SCAN)};
+constexpr ScanRow<ScanI8Args> kRowsIvfScanI8[] = {VDB_KERNELS_IVF_SCAN_I8(VDB_ROW_IVF_SCAN_I8)};
+constexpr ScanRow<IvfKloopArgs> kRowsIvfKloop[] = {VDB_KERNELS_IVF_KLOOP(VDB_ROW_IVF_KLOOP)};
+#undef VDB_ROW_IVF_SCAN
+#undef VDB_ROW_IVF_SCAN_I8
+#undef VDB_ROW_IVF_KLOOP
+
+// the one <<<>>> of the plan's family, with the arguments of that family
+void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st) {
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    switch (p.family) {
+        case ScanFamily::scan: scan_kernel_of(kRowsIvfScan, p)<<<grid, block, 0, st>>>(*sa); break;
+        case ScanFamily::scan_i8: scan_kernel_of(kRowsIvfScanI8, p)<<<grid, block, 0, st>>>(*s8); break;
+        case ScanFamily::ivf_kloop: scan_kernel_of(kRowsIvfKloop, p)<<<grid, block, 0, st>>>(*ka); break;
+        default: throw Error(VDB_ERR_INVALID, "internal: no list scan kernel for an empty plan");
     }
-    if (h->opt.ivf_nw == 2 || h->opt.ivf_nw == 4 || h->opt.ivf_nw == 8) nw = h->opt.ivf_nw;
-    // (K-loop scan: 8 waves share the A staging; 512 slots per item, or 256 with the square workgroup tile -- 256-row spans,
-    //  option "ivf_tile" = 2; measured equal within 3 %, so 128 x 512 stays the default: ivf_kloop.hpp)
-    if (kloop) nw = (h->ivf_tps == 16 && h->opt.ivf_tile == 2 ? kIvfKloopGroup / 2 : kIvfKloopGroup) / 64;
-    const int group = 64 * nw;
-    const int64_t max_items = (pairs + group - 1) / group + std::min<int64_t>(nlist, pairs);
-    const int64_t max_slots = max_items * group;
-    // (32-row-tile scans: one run of bins per lane half, each padded to a multiple of 4 -- at most 3 more bins per half)
-    const int run_groups = kloop ? 0 : 2;
-    const int64_t run_pad = run_groups * 3;
-    const int64_t max_bins = ((pairs + group - 1) / group) * (bins_per_span * h->ivf_max_pspans + run_pad) +
-                             (int64_t)bins_per_span * h->ivf_pspans + run_pad * std::min<int64_t>(nlist, pairs);
-    const size_t bin_bytes = (size_t)max_bins * group * sizeof(float);
-    if (bin_bytes > ((size_t)3 << 30) || max_slots > (1ll << 30)) return g;
-    g.kloop = kloop; g.bt = bt; g.bps = bps; g.bins_per_span = bins_per_span; g.bin_rows = bin_rows; g.nw = nw; g.group = group;
-    g.run_groups = run_groups;
-    g.pairs = pairs; g.max_items = max_items; g.max_slots = max_slots; g.max_bins = max_bins; g.bin_bytes = bin_bytes;
-    // per-list counters, cursors, the slot -> query map (query + 1, 0 = padding slot) and one arrival counter per query for
-    // the split fallback pass (ivf_fallback_body in ivf_tail_kernel): all cleared with the two ws.small by ONE memset per batch
-    g.cnt_words = (size_t)2 * nlist + (size_t)max_slots + (size_t)nb;
-    g.ok = true;
-    return g;
+    VDB_HIP(hipGetLastError());
 }
 
 // one batch of an IVF search, as ivf_search_device_impl hands it to its path.  The coarse result (nb x nprobe list ids) is
@@ -363,16 +325,14 @@ struct IvfBatch {
     float *D; int64_t *I; double *pk; int64_t *pi;
     long tslot;
     hipStream_t st;
+    IvfIndexShape shape;    // ivf_shape_of(h)
     IvfGeom g;              // list-major path only: the geometry, and the zeroed counter block of this batch (ivf_zero)
     int32_t *d_cnt;
 };
 
 // what the steps of ivf_search_lists share: capacities, the plan's launch shape, views into the counter block and the plan
 struct IvfLists {
-    bool use_i8, small_ppb;
-    int kgroup, cand_cap, rescan_cap, ppb;
-    unsigned pblocks;
-    size_t hist_bytes;
+    IvfCaps c;
     int32_t *d_cursor, *d_slot_query, *d_fb_done;
     const int64_t *probes;
     IvfPlan *plan;
@@ -382,18 +342,13 @@ struct IvfLists {
 IvfLists ivf_lists_reserve(const IvfBatch &b) {
     vdb_index_s *h = b.h;
     Workspace &ws = h->ws;
-    const int nlist = h->nlist, k = b.k;
+    const int nlist = h->nlist;
     const int64_t nb = b.nb;
     IvfLists L{};
-    // rows per candidate group of the K-loop scan (option "ivf_group": 0 auto, 1, 2, 4): 64-row bins can name single rows
-    L.kgroup = (b.g.kloop && h->ivf_tps == 16) ? (h->opt.ivf_group > 0 ? h->opt.ivf_group : kIvfKloopGroupRows) : 4;
-    // (five minima per bin: a dense bin hands over up to four candidate quads instead of one re-scan)
-    L.cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : (b.g.kloop ? std::max(96, 4 * k + 32) : std::max(64, 2 * k + 32));
-    L.rescan_cap = std::max(16, k / 2 + 8);
+    L.c = ivf_caps(b.shape, h->opt, b.g, b.k);
     ws.eps.reserve((size_t)nb * sizeof(float));
     ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
-    L.use_i8 = h->i8_ok && !h->opt.panel_dtype && h->scan.panels8.p != nullptr;
-    if (L.use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);        // int8 query rows
+    if (L.c.use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);      // int8 query rows
     ws.bin_m1.reserve(b.g.bin_bytes);
     ws.bin_m2.reserve(b.g.bin_bytes);
     ws.bin_m3.reserve(b.g.bin_bytes);
@@ -401,8 +356,8 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
         ws.bin_m4.reserve(b.g.bin_bytes);
         ws.bin_m5.reserve(b.g.bin_bytes);
     }
-    ws.cand.reserve((size_t)nb * L.cand_cap * sizeof(int32_t));
-    ws.rescan.reserve((size_t)nb * L.rescan_cap * 2 * sizeof(int32_t));
+    ws.cand.reserve((size_t)nb * L.c.cand_cap * sizeof(int32_t));
+    ws.rescan.reserve((size_t)nb * L.c.rescan_cap * 2 * sizeof(int32_t));
     ws.counts.reserve((size_t)nb * 2 * sizeof(int32_t));
     ws.fallback.reserve((size_t)nb * sizeof(int32_t));
     L.d_cursor = b.d_cnt + nlist;
@@ -418,10 +373,6 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     h->plan.ivf_slot_of.reserve((size_t)b.g.pairs * 4);
     L.probes = h->plan.ivf_probe_i.as<int64_t>();
     L.plan = h->plan.ivf_plan.as<IvfPlan>();
-    L.small_ppb = b.g.pairs < 256 * (int64_t)kIvfPairsPerBlock && nlist <= 2048;   // (fewer than 256 workgroups otherwise)
-    L.ppb = L.small_ppb ? kIvfPairsPerBlock / 4 : kIvfPairsPerBlock;
-    L.pblocks = (unsigned)((b.g.pairs + L.ppb - 1) / L.ppb);
-    L.hist_bytes = nlist <= kIvfLdsLists ? (size_t)nlist * 4 : 0;
     L.info = batch_info(ws);      // (cleared by the dispatcher with the rest of ivf_zero)
     return L;
 }
@@ -434,7 +385,7 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
     const int Dm = h->dim;
     const int64_t nb = b.nb, total = nb * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                           L.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see ivf_scan_i8)
+                           L.c.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see plan_ivf_i8)
     const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
     if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, b.st>>>(b.q, total, L.info, fin);
     IvfPrepArgs pa{};
@@ -442,12 +393,12 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
                      h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, L.info, ws.eps.as<float>()};
     pa.Q = b.q; pa.nq = nb; pa.D = Dm; pa.Dpad = h->ksteps * 16;      // (= i8_ks * 32: both query-row forms have the same pitch)
     pa.qrows = reinterpret_cast<_Float16 *>(ws.qpanels.p);
-    pa.q8 = L.use_i8 ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
+    pa.q8 = L.c.use_i8 ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
     pa.info = L.info; pa.src = from_coarse ? batch_info(h->coarse->ws) : nullptr; pa.fin = fin;
     pa.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
     pa.n_row_blocks = (unsigned)((nb * pa.Dpad / 8 + 255) / 256);     // (8 dims per thread)
-    pa.probes = L.probes; pa.npairs = b.g.pairs; pa.nlist = h->nlist; pa.ppb = L.ppb; pa.cnt = b.d_cnt;
-    ivf_prep_kernel<<<dim3(pa.n_eps_blocks + pa.n_row_blocks + L.pblocks), dim3(256), L.hist_bytes, b.st>>>(pa);
+    pa.probes = L.probes; pa.npairs = b.g.pairs; pa.nlist = h->nlist; pa.ppb = L.c.ppb; pa.cnt = b.d_cnt;
+    ivf_prep_kernel<<<dim3(pa.n_eps_blocks + pa.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(pa);
 }
 
 // work items of every probed list and the slot of every (query, probe) pair.  nlist <= kIvfLdsLists: plan + scatter in one
@@ -455,10 +406,10 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
 void ivf_lists_plan(const IvfBatch &b, const IvfLists &L) {
     vdb_index_s *h = b.h;
     const int nlist = h->nlist;
-    const auto plan_scatter = L.small_ppb ? ivf_plan_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_plan_scatter_kernel<kIvfPairsPerBlock>;
-    const auto scatter = L.small_ppb ? ivf_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_scatter_kernel<kIvfPairsPerBlock>;
-    if (L.hist_bytes) {
-        plan_scatter<<<dim3(L.pblocks), dim3(256), 2 * L.hist_bytes, b.st>>>(
+    const auto plan_scatter = L.c.small_ppb ? ivf_plan_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_plan_scatter_kernel<kIvfPairsPerBlock>;
+    const auto scatter = L.c.small_ppb ? ivf_scatter_kernel<kIvfPairsPerBlock / 4> : ivf_scatter_kernel<kIvfPairsPerBlock>;
+    if (L.c.hist_bytes) {
+        plan_scatter<<<dim3(L.c.pblocks), dim3(256), 2 * L.c.hist_bytes, b.st>>>(
             L.probes, b.nb, b.nprobe, nlist, b.d_cnt, h->lists.ivf_list_pspan0.as<int32_t>(), b.g.group, b.g.bins_per_span, b.g.run_groups,
             (int)b.g.max_items, (int)b.g.max_slots, (int)b.g.max_bins, h->lists.ivf_offsets.as<int64_t>(), h->plan.ivf_slot_off.as<int32_t>(),
             h->plan.ivf_list_item0.as<int32_t>(), h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(),
@@ -469,7 +420,7 @@ void ivf_lists_plan(const IvfBatch &b, const IvfLists &L) {
             (int)b.g.max_slots, (int)b.g.max_bins, h->plan.ivf_slot_off.as<int32_t>(), h->plan.ivf_list_item0.as<int32_t>(),
             h->plan.ivf_item_list.as<int32_t>(), h->plan.ivf_item_slot0.as<int32_t>(), h->plan.ivf_item_bin0.as<int32_t>(), L.plan,
             h->lists.ivf_offsets.as<int64_t>());
-        scatter<<<dim3(L.pblocks), dim3(256), L.hist_bytes, b.st>>>(
+        scatter<<<dim3(L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(
             L.probes, b.nb, b.nprobe, nlist, h->plan.ivf_slot_off.as<int32_t>(), h->lists.ivf_list_pspan0.as<int32_t>(), L.d_cursor, L.plan,
             L.d_slot_query, h->plan.ivf_slot_of.as<int32_t>());
     }
@@ -489,23 +440,10 @@ const half8 *ivf_sq8_panels(const IvfBatch &b) {
     return h->ws.sq8_panels.as<half8>();
 }
 
-// Long lists are cut into row parts of some spans each, one workgroup per (item, part): the scan's duration is otherwise the
-// LONGEST list's (k-means lists are far from even: 5x the median on SIFT-like data).  `base` = the scan's own choice of the
-// part size (option "ivf_part" overrides it), rounded up to `unit` spans.  At most 64 parts per item: every (item, part) is
-// a workgroup, and the parts beyond a short list's end only exit -- one giant list must not turn the launch into millions of
-// empty workgroups.  Returns the part size (0 = whole lists) and the grid
-struct IvfParts { int part_spans; dim3 grid; };
-IvfParts ivf_part_spans(const vdb_index_s *h, int64_t max_items, int base, int unit = 1) {
-    int part = std::min(std::max(h->opt.ivf_part > 0 ? h->opt.ivf_part : base, (h->ivf_max_pspans + 63) / 64), h->ivf_max_pspans);
-    part = (part + unit - 1) / unit * unit;
-    const int part_spans = part >= h->ivf_max_pspans ? 0 : part;
-    return {part_spans, dim3((unsigned)max_items, (unsigned)(part_spans ? (h->ivf_max_pspans + part - 1) / part : 1))};
-}
-
 // D > 128: the K-loop scan on p16 panels (ivf_kloop.hpp)
 void ivf_scan_kloop(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
     vdb_index_s *h = b.h;
-    hipStream_t st = b.st;
+    const IvfLaunch p = plan_ivf_kloop(b.shape, h->opt, b.g, kgroup);
     IvfKloopArgs ka{};
     ka.panels = sa.panels; ka.bias = sa.bias; ka.qrows = sa.qrows; ka.info = sa.info;
     ka.bin_m[0] = sa.bin_m1; ka.bin_m[1] = sa.bin_m2; ka.bin_m[2] = sa.bin_m3;
@@ -513,61 +451,20 @@ void ivf_scan_kloop(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
     ka.item_list = sa.item_list; ka.item_slot0 = sa.item_slot0; ka.item_bin0 = sa.item_bin0;
     ka.n_items = sa.n_items; ka.list_pspan0 = sa.list_pspan0; ka.slot_query = sa.slot_query;
     ka.ksteps = h->ksteps;
-    // row parts: 128 rows x 512 slots x D of matrix work per pass -- a part of ~1024 rows keeps a workgroup busy for
-    // tens of microseconds at 384 dims; few work items -> finer parts (down to one span) to cover the chip
-    // (measured on the msmarco shape, 725 items of ~4 spans: scripts/sweep_ivf.py --workload msmarco_ivf --option ivf_part:
-    //  whole lists (8 spans) 0.612 ms, 4 spans 0.525, 2 spans 0.510, 1 span 0.528 -- ~1500 workgroups for the chip's 512
-    //  slots, and never less than 512 rows per workgroup: every part gathers its B fragments and fills its pipeline anew)
-    const int spans_512 = std::max(1, 512 / h->ivf_span_rows);
-    const double item_spans = (double)b.g.max_items * (double)h->ivf_pspans / (double)h->nlist;
-    const IvfParts parts = ivf_part_spans(
-        h, b.g.max_items, (int)std::min<double>(8.0 * spans_512, std::max<double>(spans_512, std::floor(item_spans / 1536.0))));
-    ka.part_spans = parts.part_spans;
-    const dim3 kgrid = parts.grid;
-    if (h->ivf_tps == 16 && b.g.group == kIvfKloopGroup / 2) {        // square tile: 256 rows x 256 slots
-        if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-        else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-        else ivf_kloop_scan_kernel<16, 2, 4, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-    } else if (h->ivf_tps == 16) {
-        if (kgroup == 1) ivf_kloop_scan_kernel<16, 2, 1><<<kgrid, dim3(512), 0, st>>>(ka);
-        else if (kgroup == 2) ivf_kloop_scan_kernel<16, 2, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-        else ivf_kloop_scan_kernel<16, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-    } else ivf_kloop_scan_kernel<64, 2><<<kgrid, dim3(512), 0, st>>>(ka);
-    VDB_HIP(hipGetLastError());
+    ka.part_spans = p.part_spans;
+    ivf_launch(p, nullptr, nullptr, &ka, b.st);
 }
 
-// D <= 128: scan_kernel in ITEMS mode on 32-row tiles.  Sets sa.part_spans; returns the grid (the int8 scan launches the same)
-dim3 ivf_scan_fp16(const IvfBatch &b, ScanArgs &sa) {
-    vdb_index_s *h = b.h;
-    hipStream_t st = b.st;
-    const int nw = b.g.nw, bt = b.g.bt;
-    // row parts of 256-row spans (measured in 512-row units, scripts/sweep_ivf.py --option ivf_part: nprobe 8 / 32 / 128 at
-    //  nlist 1024, 10k queries -> 1 / 2 / 4 spans; the fewer work items there are, the finer the parts)
-    const int part_auto = (kSpanRows / kIvfSpanRows) * (b.g.max_items <= 2048 ? 1 : b.g.max_items <= 4096 ? 2 : 4);
-    // a row part starts at a multiple of 4 bins of the lane's run (the bins leave as 16-byte vectors; bps = bins of a span half)
-    const IvfParts parts = ivf_part_spans(h, b.g.max_items, part_auto, 4 / b.g.bps);
-    sa.part_spans = parts.part_spans;
-    const dim3 grid = parts.grid;
-#define VDB_IVF_SCAN(KS, NW, BT) scan_kernel<KS, NW, 2, 2, BT, true><<<grid, dim3(NW * 64), 0, st>>>(sa)
-    if (h->ksteps == 4) {
-        if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(4, 2, 4); else VDB_IVF_SCAN(4, 2, 8); }
-        else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(4, 4, 4); else VDB_IVF_SCAN(4, 4, 8); }
-        else              { if (bt == 4) VDB_IVF_SCAN(4, 8, 4); else VDB_IVF_SCAN(4, 8, 8); }
-    } else {
-        if (nw == 2)      { if (bt == 4) VDB_IVF_SCAN(8, 2, 4); else VDB_IVF_SCAN(8, 2, 8); }
-        else if (nw == 4) { if (bt == 4) VDB_IVF_SCAN(8, 4, 4); else VDB_IVF_SCAN(8, 4, 8); }
-        else              { if (bt == 4) VDB_IVF_SCAN(8, 8, 4); else VDB_IVF_SCAN(8, 8, 8); }
-    }
-#undef VDB_IVF_SCAN
-    VDB_HIP(hipGetLastError());
-    return grid;
+// D <= 128: scan_kernel in ITEMS mode on 32-row tiles.  Sets sa.part_spans (the int8 scan takes the same, and the same grid)
+void ivf_scan_fp16(const IvfBatch &b, ScanArgs &sa) {
+    const IvfLaunch p = plan_ivf_f16(b.shape, b.h->opt, b.g);
+    sa.part_spans = p.part_spans;
+    ivf_launch(p, &sa, nullptr, nullptr, b.st);
 }
 
 // the int8 form of the same scan; whichever the finalize kernel did not choose returns at once
-void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa, dim3 grid) {
+void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa) {
     vdb_index_s *h = b.h;
-    hipStream_t st = b.st;
-    const int nw = b.g.nw, bt = b.g.bt;
     ScanI8Args s8{};
     s8.panels = h->scan.panels8.as<int4v>();
     s8.bias8 = h->scan.bias8.as<int32_t>();
@@ -578,38 +475,19 @@ void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa, dim3 grid) {
     s8.n_items = sa.n_items; s8.list_pspan0 = sa.list_pspan0; s8.slot_query = sa.slot_query;
     s8.qrows = reinterpret_cast<const signed char *>(h->ws.qpanels8.p);
     s8.part_spans = sa.part_spans;
-    // (select groups stay quads here: measured with octs the list scan gains 5 % and the refine loses more -- the
-    //  probed lists are dense in near neighbours, so an 8-row group drags in more re-scans and twice the rows)
-    // staging ring of the work items (option "i8_ring"; 0 = auto): a work item streams its list once, and few of them
-    // are resident per CU -- 4 stages of 2 (4 at two k-steps) tiles in flight instead of 1
-#define VDB_IVF_SCAN8(KS, ST, NW, BT) do { const int r__ = h->opt.i8_ring == 0 ? 4 : h->opt.i8_ring; \
-    if (h->opt.ivf_i8_group == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 8, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-    else if (r__ == 2) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-    else if (r__ == 8) scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 8><<<grid, dim3(NW * 64), 0, st>>>(s8); \
-    else scan_i8_kernel<KS, ST, 2, NW, BT, true, 4, 0, 4><<<grid, dim3(NW * 64), 0, st>>>(s8); } while (0)
-#define VDB_IVF_SCAN8_NW(KS, ST, BT) do { if (nw == 2) VDB_IVF_SCAN8(KS, ST, 2, BT); else if (nw == 4) VDB_IVF_SCAN8(KS, ST, 4, BT); \
-                                          else VDB_IVF_SCAN8(KS, ST, 8, BT); } while (0)
-    // (tiles per LDS stage: 2 -- 8 pieces per stage for 8 waves make it 4 at two k-steps; deeper stages measured
-    //  slower at nprobe 32 / 128 and equal at 8 once the lists are scanned in row parts)
-    if (h->i8_ks == 2) {
-        if (bt == 4) VDB_IVF_SCAN8_NW(2, 4, 4); else VDB_IVF_SCAN8_NW(2, 4, 8);
-    } else {
-        if (bt == 4) VDB_IVF_SCAN8_NW(4, 2, 4); else VDB_IVF_SCAN8_NW(4, 2, 8);
-    }
-#undef VDB_IVF_SCAN8_NW
-#undef VDB_IVF_SCAN8
-    VDB_HIP(hipGetLastError());
+    ivf_launch(plan_ivf_i8(b.shape, h->opt, b.g), nullptr, &s8, nullptr, b.st);
 }
 
 IvfSelectArgs ivf_lists_select(const IvfBatch &b, const IvfLists &L, const ScanArgs &sa) {
     vdb_index_s *h = b.h;
     Workspace &ws = h->ws;
     const int k = b.k, nprobe = b.nprobe;
+    const IvfSelectCaps sc = ivf_select_caps(b.shape, b.g, L.c, k, nprobe);
     IvfSelectArgs se{};
     se.bin_m[0] = sa.bin_m1; se.bin_m[1] = sa.bin_m2; se.bin_m[2] = sa.bin_m3;
     se.bin_m[3] = b.g.kloop ? ws.bin_m4.as<float>() : nullptr;
     se.bin_m[4] = b.g.kloop ? ws.bin_m5.as<float>() : nullptr;
-    se.nm = b.g.kloop ? kIvfKloopMinima : 3;
+    se.nm = sc.nm;
     se.eps = ws.eps.as<float>();
     se.info = L.info; se.plan = L.plan; se.probes = L.probes;
     se.slot_of = h->plan.ivf_slot_of.as<int32_t>(); se.slot_off = h->plan.ivf_slot_off.as<int32_t>();
@@ -617,23 +495,14 @@ IvfSelectArgs ivf_lists_select(const IvfBatch &b, const IvfLists &L, const ScanA
     se.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
     se.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); se.span_valid = h->lists.ivf_span_valid.as<int32_t>();
     se.nq = b.nb; se.nprobe = nprobe; se.group = b.g.group; se.k = k;
-    se.cand_cap = L.cand_cap; se.rescan_cap = L.rescan_cap;
-    // a query can meet at most nprobe * (bins of the longest list) entries
-    const int64_t worst = (int64_t)nprobe * (h->ivf_max_pspans * b.g.bins_per_span + b.g.run_groups * 3);
-    se.max_entries = (int)std::min<int64_t>(kIvfMaxEntries, (worst + 63) / 64 * 64);
-    se.probe_cap = (nprobe + 63) / 64 * 64;
-    se.group_rows = b.g.kloop ? L.kgroup : 0;
+    se.cand_cap = L.c.cand_cap; se.rescan_cap = L.c.rescan_cap;
+    se.max_entries = sc.max_entries; se.probe_cap = sc.probe_cap; se.vals_entries = sc.vals_entries; se.act_cap = sc.act_cap;
+    se.group_rows = b.g.kloop ? L.c.kgroup : 0;
     se.bins_per_span = b.g.bins_per_span; se.bin_rows = b.g.bin_rows; se.run_groups = b.g.run_groups;
     se.cand_rows = ws.cand.as<int32_t>(); se.rescan_rows = ws.rescan.as<int32_t>();
     se.counts = ws.counts.as<int32_t>(); se.fallback = ws.fallback.as<int32_t>(); se.fb_list = ws.fb_list.as<int32_t>();
     se.fb_count = ws.small.as<int32_t>();            // (zeroed with the batch info: the first 64 bytes of ws.small)
     se.stat_counters = reinterpret_cast<unsigned long long *>(ws.small.as<char>() + 64);
-    se.vals_entries = k > 64 ? se.max_entries : 0;
-    se.act_cap = std::min(L.cand_cap + L.rescan_cap, se.max_entries);       // (entry numbers are packed into 16 bits: <= 4096)
-    {   // two waves per workgroup within the 64 KiB a kernel gets without opting in: 8192 words per wave
-        const int fixed = se.vals_entries + 4 * se.probe_cap + 64;
-        se.act_cap = std::max(64, std::min(se.act_cap, (8192 - fixed) / (1 + se.nm)));
-    }
     ivf_select_kernel<<<dim3((unsigned)((b.nb + 1) / 2)), dim3(128),
                         (size_t)2 * ivf_select_lds_words(se.vals_entries, se.probe_cap, se.act_cap, se.nm) * 4, b.st>>>(se);
     VDB_HIP(hipGetLastError());
@@ -651,7 +520,7 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     rc.info = L.info;
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
     if (ivfpq(h)) rc.ivfpq = ivfpq_rows(h);
-    if (L.use_i8 && h->scan.rows8.p) {
+    if (L.c.use_i8 && h->scan.rows8.p) {
         rc.X8 = h->scan.rows8.as<signed char>(); rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
         rc.x8_pitch = h->rows8_pitch; rc.cx = h->i8_cx; rc.D = h->dim;
@@ -660,9 +529,9 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     la.c = rc;
     la.nq = nb;
     la.cand_rows = se.cand_rows; la.rescan_rows = se.rescan_rows; la.counts = se.counts; la.fallback = se.fallback;
-    la.cand_cap = L.cand_cap; la.rescan_cap = L.rescan_cap;
+    la.cand_cap = L.c.cand_cap; la.rescan_cap = L.c.rescan_cap;
     la.D = b.D; la.I = b.I; la.pkeys = b.pk; la.pids = b.pi;
-    if (b.g.kloop) la.group_shift = L.kgroup == 1 ? 0 : L.kgroup == 2 ? 1 : 2;
+    if (b.g.kloop) la.group_shift = L.c.kgroup == 1 ? 0 : L.c.kgroup == 2 ? 1 : 2;
     IvfFallbackArgs a{};
     a.c = rc;
     a.offsets = h->lists.ivf_offsets.as<int64_t>();
@@ -701,10 +570,10 @@ void ivf_search_lists(const IvfBatch &b) {
     sa.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
     timing_mark(h, b.tslot, 0, b.st);
     if (b.g.kloop) {
-        ivf_scan_kloop(b, L.kgroup, sa);
+        ivf_scan_kloop(b, L.c.kgroup, sa);
     } else {
-        const dim3 grid = ivf_scan_fp16(b, sa);
-        if (L.use_i8) ivf_scan_i8(b, sa, grid);
+        ivf_scan_fp16(b, sa);
+        if (L.c.use_i8) ivf_scan_i8(b, sa);
     }
     timing_mark(h, b.tslot, 1, b.st);
     const IvfSelectArgs se = ivf_lists_select(b, L, sa);
@@ -732,13 +601,7 @@ void ivf_search_exact(const IvfBatch &b) {
     const int64_t nb = b.nb;
     const int k = b.k, nprobe = b.nprobe;
     hipStream_t st = b.st;
-    // waves per query: keep each wave's share of rows moderate and the GPU full
-    const double rows_per_query = (double)nprobe * (double)h->N / (double)h->nlist;
-    int64_t S = (int64_t)std::ceil(rows_per_query / 4096.0);
-    S = std::max<int64_t>(S, (8192 + nb - 1) / nb);
-    S = std::max<int64_t>(1, std::min<int64_t>(S, nprobe));
-    const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nb * k * 16));
-    S = std::min<int64_t>(S, cap);
+    const int64_t S = ivf_exact_splits(h->N, h->nlist, nprobe, nb, k);
     IvfScanArgs a{};
     a.c = RefineCommon{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
@@ -785,6 +648,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
     const int64_t kBatch = 16384;
     Workspace &ws = h->ws;
     bool any_mfma = false;
+    const IvfIndexShape shape = ivf_shape_of(h);
     const size_t ev_mark = h->ev_used;
     try {
     for (int64_t b0 = 0; b0 < nq; b0 += kBatch) {
@@ -794,7 +658,8 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         b.q = dq + (size_t)b0 * Dm;
         // everything this batch needs zeroed sits in ivf_zero: ONE memset (first batch of a call: both ws.small whole and
         // the counter block; later batches keep this handle's statistics counters, which accumulate over the call)
-        b.g = ivf_geometry(h, b.nb, k, b.nprobe);
+        b.shape = shape;
+        b.g = ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
             VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (b.g.ok ? b.g.cnt_words * 4 : 0), st));

@@ -25,13 +25,7 @@
 
 namespace vdb {
 
-// Quad minima kept per bin.  The D <= 128 scans keep three (one v_med3 each per quad: their select is issue-bound); here the
-// select runs once per pass of D / 64 K-steps, so two more cost ~1 % -- and they matter: the near neighbours of a query sit
-// in one or two of its probed lists, i.e. several per 64-row bin, and a bin with more close quads than minima kept must be
-// re-scored whole (with three minima the msmarco-shaped leg re-scored 5.8 bins = 370 rows of 1.5 KB per query, 70 % of
-// its time; with five a bin yields up to four candidate quads before it has to be re-scanned).
-constexpr int kIvfKloopMinima = 5;
-
+// (quad minima kept per bin: kIvfKloopMinima = 5, and why: ivf_plan.hpp)
 struct IvfKloopArgs {
     const half8 *panels;         // [pspans * TPS tiles][KS][64]
     const float *bias;           // [pspans * TPS * 16] linear in the local row of the span; kPadBias on padding rows
@@ -43,8 +37,7 @@ struct IvfKloopArgs {
     int ksteps;                  // 16-dim k-steps of the index (multiple of 4)
 };
 
-constexpr int kIvfKloopGroup = 512;     // query slots per work item
-
+// (kIvfKloopGroup = 512 query slots per work item: ivf_plan.hpp)
 // GROUP = rows per candidate group (the unit a packed 6-bit id names and the refine re-scores): 4 = the quad of a tile (any TPS),
 // 2 / 1 = pairs / single rows (TPS = 16 only: 32 / 64 ids per 64-row bin).  Smaller groups cost select instructions here
 // (one sorted insertion per group: 9 -> 14 -> 24 vector ops per quad of scores) and save gathered rows in the refine, which

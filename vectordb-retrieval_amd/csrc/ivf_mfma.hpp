@@ -83,11 +83,8 @@ struct IvfPlan {          // device-resident scalars written by ivf_plan_kernel
     unsigned long long rows_scanned;   // (query, row) pairs of this batch: sum over lists of probes x rows
 };
 
-// per-list probe counts.  Workgroup-local LDS histogram first (nlist <= kIvfLdsLists), then one global atomic
+// per-list probe counts.  Workgroup-local LDS histogram first (nlist <= kIvfLdsLists, ivf_plan.hpp), then one global atomic
 // per (workgroup, touched list): 1.28 M probes on 1024 lists would otherwise serialise on 1024 addresses.
-constexpr int kIvfLdsLists = 8192;
-constexpr int kIvfPairsPerBlock = 4096;
-
 // PPB: (query, probe) pairs per workgroup -- kIvfPairsPerBlock for large batches (fewer global atomics per list), a
 // quarter of it when that would leave most CUs idle (80 000 pairs = 20 workgroups).
 // (a device function: the per-batch prep kernel below runs it in its last workgroups -- one dispatch instead of two)
@@ -459,8 +456,7 @@ struct IvfSelectArgs {
 // index loads of all probes overlap instead of chaining; a wave prefix sum lays the probes' bins out as one
 // flat entry range.  Phase 2: lanes stride over the flat entries (binary search probe-of-entry in LDS) and
 // copy the bin minima into LDS with independent, per-probe-contiguous loads.  Phase 3: bitwise bisection for
-// the k-th smallest.  Phase 4: entries <= That become candidate rows or bins to re-scan.
-constexpr int kIvfMaxProbes = 512;
+// the k-th smallest.  Phase 4: entries <= That become candidate rows or bins to re-scan.  (At most kIvfMaxProbes probes: ivf_plan.hpp.)
 // 32-bit words of LDS per wave: vals[vals_entries] | p_off[probe_cap + 32] | p_base lo / hi [2 probe_cap] | p_list[probe_cap]
 // (+ 32 spare) | act[act_cap] | vals2[act_cap * nm]
 __host__ __device__ inline size_t ivf_select_lds_words(int vals_entries, int probe_cap, int act_cap, int nm) {

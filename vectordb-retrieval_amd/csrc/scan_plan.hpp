@@ -225,16 +225,17 @@ inline int64_t stream_slab_chunks(const ScanIndexShape &s, const Options &opt, c
 }
 
 // ---- a launch -------------------------------------------------------------------------------------------------------------------
-enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16 };
+enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16, ivf_kloop };
 constexpr const char *kScanFamilyNames[] = {"none", "scan_kernel", "scan16_kloop_kernel", "scan_x16_kernel", "scan_i8_kernel",
-                                            "scan_i8x16_kernel", "scan_pair_x16_kernel"};
-constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7};       // template parameters of each family's kernel
+                                            "scan_i8x16_kernel", "scan_pair_x16_kernel", "ivf_kloop_scan_kernel"};
+constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7, 4};    // template parameters of each family's kernel
 constexpr int kScanMaxArgs = 10;
 
 // The template arguments of one instantiation in the kernel's own order, defaults written out (bool as 0 / 1, the rest 0):
 //   scan_kernel<KSTEPS, NWAVES, ST, WPS, BT, ITEMS, G8>            scan16_kloop_kernel<BS, FP, NARROW>
 //   scan_x16_kernel<KS2, NWAVES, ST, WPS, BR, G, CB>               scan_i8_kernel<KS, ST, CB, NWAVES, BT, ITEMS, G, TB, RING, AUX>
 //   scan_i8x16_kernel<KS2, ST, CB, NWAVES, RING, AUX>              scan_pair_x16_kernel<W128, NWAVES, STF, STI, CBI, RING, AUX>
+//   ivf_kloop_scan_kernel<TPS, BS, GROUP, RH>  (the IVF list scans: ivf_plan.hpp, which also plans scan_kernel / scan_i8_kernel with ITEMS)
 struct ScanKey {
     int t[kScanMaxArgs];
 };
@@ -380,8 +381,8 @@ inline ScanLaunch plan_pair(const ScanIndexShape &s, const Options &opt, int nch
 }
 
 // ---- every instantiation of each family, once ------------------------------------------------------------------------------------
-// X(template arguments in the kernel's own order, defaults written out).  The set is what the flat search can launch; the IVF list
-// scans (ivf.inc) instantiate ITEMS forms of their own.
+// X(template arguments in the kernel's own order, defaults written out).  The set is what the flat search can launch; the ITEMS forms of
+// the IVF list scans are listed in ivf_plan.hpp.
 #define VDB_KERNELS_SCAN_K(X, K) /* serving: 1 / 2 / 4 waves, quads and octs | batch: direct bins of 8 and 4 tiles, quads, octs */ \
     X(K, 1, 4, 1, 16, false, false) X(K, 2, 4, 1, 16, false, false) X(K, 4, 4, 2, 16, false, false) \
     X(K, 1, 4, 1, 16, false, true) X(K, 2, 4, 1, 16, false, true) X(K, 4, 4, 2, 16, false, true) \

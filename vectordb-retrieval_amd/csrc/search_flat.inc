@@ -38,8 +38,8 @@ constexpr ScanRow<ScanArgs, ScanI8Args> kRowsScanPairX16[] = {VDB_KERNELS_SCAN_P
 #undef VDB_ROW_SCAN_I8X16
 #undef VDB_ROW_SCAN_PAIR_X16
 
-template <class Row, size_t N>
-auto scan_kernel_of(const Row (&rows)[N], const ScanLaunch &p) {
+template <class Row, size_t N, class Launch>     // Launch: ScanLaunch, or IvfLaunch (ivf.inc)
+auto scan_kernel_of(const Row (&rows)[N], const Launch &p) {
     for (const Row &r : rows)
         if (r.key == p.key) return r.kernel;
     std::string what = kScanFamilyNames[(int)p.family];
