@@ -56,7 +56,8 @@ enum vdb_status {
 
 /* which search path served the last call (vdb_stats_t.last_path) */
 enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6,
-                VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */ };
+                VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */,
+                VDB_PATH_IVFPQ_ADC = 8 /* IVF-PQ: lookup-table (ADC) scan of the probed lists, then the exact re-score of the rows near the k-th score */ };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -76,7 +77,8 @@ typedef struct vdb_stats_s {
     int32_t nprobe;
     int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate),
                                   2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate),
-                                  3 = float32 lookup-table sums over the codes of a PQ index (last_path = VDB_PATH_PQ_ADC) */
+                                  3 = float32 lookup-table sums over the codes of a PQ or IVF-PQ index (last_path = VDB_PATH_PQ_ADC /
+                                  VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -129,6 +131,7 @@ typedef struct vdb_stats_s {
  *   vdb_knng_build, vdb_knng_set, vdb_knng_search*       +     U    U     +    U      U         U        U       U
  *   vdb_debug_scan_scores                                +     +    +     +    +      +         +        +       U
  *   vdb_debug_pq_adc_scores                              U     U    U     U    +      U         U        U       U
+ *   vdb_debug_ivfpq_adc_scores                           U     U    U     U    U      U         U        +       U
  *   options refused (U), in either order of the calls:
  *     "int8_only" = 1, "stream_panels" = 1               -     U    U     U    U      -         U        U       -
  *     "graph" = 1                                        -     -    -     -    U      -         U        U       U
@@ -306,6 +309,12 @@ int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
  * dim <= 128: batches the list-major path serves make the fp16 panels of the whole panel space from the codes per batch, as
  * (half)((c_l[d] + codebook entry) * sx) -- IVF-Flat's panels of x^, so the same error bound holds (vdb_stats.scan_dtype = 2) --
  * and run the MFMA list scan on them; dim > 128, small batches and "force_path" 1 / 3 take the exact list scan over the codes.
+ * A third path, off by default: with option "ivfpq_adc_max_batch" = B a batch of at most B queries (any dim; k <= 1024, M <= 159,
+ * "force_path" 0, at most 256 MiB of scores = 4 nq min(ntotal, nprobe x longest list) bytes) scores the rows of its probed lists
+ * from ONE float32 lookup table per query, a scalar per (query, probe) and a resident float32 ||x^||^2 per row, re-scores the rows
+ * within twice the derived bound of the k-th smallest score exactly and returns the same ids and distances, bit for bit
+ * (vdb_stats.last_path = VDB_PATH_IVFPQ_ADC, scan_dtype = 3; DESIGN 4.4 "IVF-PQ ADC scan").  The norms cost 4 ntotal bytes of
+ * bytes_resident, allocated by the first admitted batch after an add -- a handle that never sets the option never holds them.
  * vdb_ivf_add / vdb_ivf_add_assigned encode and append.  New codebooks (or centroids) drop the rows encoded under the old ones
  * at the next add; vdb_reset drops the rows and keeps centroids and codebooks.
  * VDB_ERR_STATE: an add before codebooks.  dim % M != 0 or M outside 1 .. min(dim, 256): VDB_ERR_INVALID.  Which handles these
@@ -558,6 +567,14 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       Measured on 1M rows (profiles/r18_bench_pq_adc.json): faster than the panel pass by more than 8 % up to
  *                       8 queries for PQ16 at D = 128 and PQ64 at D = 384, up to 2 for PQ64 at D = 128 -- the value to set; the
  *                       cost grows linearly with the batch beyond
+ *     "ivfpq_adc_max_batch"  IVF-PQ index: largest query batch that takes the lookup-table (ADC) scan of the probed lists instead of
+ *                       the panel pass + list-major MFMA scan (dim <= 128) or the exact list scan, 0 (default: off) .. 512; accepted
+ *                       without effect on every other kind of index and for a batch the scan does not serve.  Same results either
+ *                       way.  Costs 4 ntotal bytes of resident norms once a batch is admitted.  Measured (profiles/r19_bench_ivfpq_adc.json,
+ *                       k = 10): faster than the option-off path by more than 8 % at every batch size up to 256 / 128 (IVF1024,PQ64 on
+ *                       1M x 128, nprobe 8 / 32), 512 / 256 (PQ16) and 512 (IVF256,PQ64 on 100 000 x 384, nprobe 24) -- the value to set
+ *     "ivfpq_adc_part_rows"  IVF-PQ index: rows per row part (one workgroup each) of that scan, 0 (default: auto) or a multiple of 256
+ *                       up to 65 536 (tests, sweeps); raised so that the longest list has at most 64 parts
  *     "knng_nentry"     k-NN graph: entry points of a search, 0 (default: 32) .. 512
  *     "knng_max_iters"  k-NN graph: step cap of a search, 0 (default: 8 ef) .. 2^31 - 1
  *     "knng_visited_bits"  k-NN graph: log2 slots of the per-query seen filter, 0 (default: up to 12, the largest that keeps a query
@@ -608,6 +625,13 @@ int vdb_debug_scan_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t
  * kernel and per-row scoring function, the ADC bound eps (nq) and cs.  Every other kind of handle: VDB_ERR_UNSUPPORTED */
 int vdb_debug_pq_adc_scores(vdb_handle h, const float *q_host, int64_t nq, int64_t row0, int64_t nrows,
                             float *scores_host, float *eps_host, double *cscale);
+
+/* the same for the lookup-table (ADC) scan of an IVF-PQ index with rows (M <= 159, any dim): the scan's own scores of the list-order
+ * rows [row0, row0 + nrows) of list `probe_list` (out (nq, nrows) float32), computed as for a batch of these nq queries that all
+ * probe that one list; the bound eps (nq; 0 for a query the scan would hand to the exact list scan) and the batch's scale cs.
+ * Every other kind of handle: VDB_ERR_UNSUPPORTED */
+int vdb_debug_ivfpq_adc_scores(vdb_handle h, const float *q_host, int64_t nq, int probe_list, int64_t row0, int64_t nrows,
+                               float *scores_host, float *eps_host, double *cscale);
 
 #ifdef __cplusplus
 }

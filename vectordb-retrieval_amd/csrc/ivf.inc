@@ -36,6 +36,7 @@ inline void admit_ivfpq(const vdb_index_s *h, const char *what) {
 void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
     h->ivf_centroids.assign(c_host, c_host + (size_t)nlist * h->dim);
     h->nlist = nlist;
+    h->codes.ivfpq_n2.release();             // (IVF-PQ: the norms of the ADC scan belong to the old centroids)
     if (!h->coarse) {
         h->coarse = new vdb_index_s();
         h->coarse->device = h->device;
@@ -647,8 +648,14 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
     const int Dm = h->dim, D4 = h->D4;
     const int64_t kBatch = 16384;
     Workspace &ws = h->ws;
-    bool any_mfma = false;
+    bool any_mfma = false, any_adc = false;
     const IvfIndexShape shape = ivf_shape_of(h);
+    // IVF-PQ, option "ivfpq_adc_max_batch": batches ivf_adc_plan admits take the lookup-table scan of the probed lists (ivf_pq.inc).
+    // The first call that may admit one makes the handle's norms (one pass over the codes, one stream synchronisation)
+    const bool adc_on = ivfpq(h) && h->opt.ivfpq_adc_max_batch > 0 && h->opt.force_path == 0 && k <= kIvfAdcMaxK &&
+                        std::min<int64_t>(kBatch, nq) <= h->opt.ivfpq_adc_max_batch && h->N > 0;
+    const bool adc_ranges = adc_on && ivfpq_adc_prepare(h, st);
+    const int64_t adc_longest = adc_ranges ? ivfpq_longest_list(h) : 0;
     const size_t ev_mark = h->ev_used;
     try {
     for (int64_t b0 = 0; b0 < nq; b0 += kBatch) {
@@ -659,7 +666,8 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         // everything this batch needs zeroed sits in ivf_zero: ONE memset (first batch of a call: both ws.small whole and
         // the counter block; later batches keep this handle's statistics counters, which accumulate over the call)
         b.shape = shape;
-        b.g = ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
+        const IvfAdcPlan adc = ivf_adc_plan(h->opt, h->ivf_codec, h->ivfpq.M, adc_ranges, h->N, adc_longest, b.nb, k, b.nprobe);
+        if (!adc.ok) b.g = ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
             VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (b.g.ok ? b.g.cnt_words * 4 : 0), st));
@@ -681,8 +689,10 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         }
         b.D = partial ? nullptr : D + (size_t)b0 * k; b.I = partial ? nullptr : I + (size_t)b0 * k;
         b.pk = partial ? PK + (size_t)b0 * k : nullptr; b.pi = partial ? PI + (size_t)b0 * k : nullptr;
-        if (b.g.ok) ivf_search_lists(b);
+        if (adc.ok) ivfpq_search_adc(h, adc, b.q, b.qpad, b.nb, k, b.nprobe, b.D, b.I, b.pk, b.pi, b.tslot, st);
+        else if (b.g.ok) ivf_search_lists(b);
         else ivf_search_exact(b);
+        any_adc = any_adc || adc.ok;
         timing_mark(h, b.tslot, 2, st);
         any_mfma = any_mfma || b.g.ok;
     }
@@ -692,6 +702,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         throw;
     }
     h->ivf_last_mfma = any_mfma;
+    if (any_adc) h->last.last_path = VDB_PATH_IVFPQ_ADC;
 }
 
 }  // namespace
@@ -918,6 +929,15 @@ int vdb_ivfpq_get_codes(vdb_handle hh, uint8_t *codes_host) {
         auto *h = check(hh);
         admit_ivfpq(h, "vdb_ivfpq_get_codes");
         ivf_get_codes(h, h->codes.ivfpq_codes, (size_t)h->ivfpq.M, (size_t)h->ivfpq.M, codes_host);
+    });
+}
+
+int vdb_debug_ivfpq_adc_scores(vdb_handle hh, const float *q_host, int64_t nq, int probe_list, int64_t row0, int64_t nrows, float *scores_host,
+                               float *eps_host, double *cscale) {
+    return guarded([&] {
+        auto *h = check(hh);
+        admit(h, "vdb_debug_ivfpq_adc_scores", kIvfPq);
+        ivfpq_adc_debug_scores(h, q_host, nq, probe_list, row0, nrows, scores_host, eps_host, cscale);
     });
 }
 

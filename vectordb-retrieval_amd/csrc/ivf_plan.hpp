@@ -4,6 +4,7 @@
 //   ivf_geometry -> IvfGeom: does the list-major MFMA scan serve the batch, and with which bins, waves, capacities
 //   ivf_part_spans | plan_ivf_f16 / plan_ivf_i8 / plan_ivf_kloop -> IvfLaunch: kernel family, template arguments, grid, block, row parts
 //   ivf_caps / ivf_select_caps: the capacities of the work lists and of the select | ivf_exact_splits: the exact list scan
+//   ivf_adc_plan -> IvfAdcPlan: does the lookup-table (ADC) scan of an IVF-PQ index serve the batch, and with which row parts
 //   VDB_KERNELS_IVF_*: every instantiation of a family, once -- the keys the host program walks and (ivf.inc) the table of
 //   kernel pointers `ivf_launch` looks a plan up in
 // (the coarse search over the centroids is a flat search: scan_plan.hpp)
@@ -177,6 +178,44 @@ inline int64_t ivf_exact_splits(int64_t N, int nlist, int nprobe, int64_t nb, in
     S = std::max<int64_t>(1, std::min<int64_t>(S, nprobe));
     const int64_t cap = std::max<int64_t>(1, (int64_t)(256ll << 20) / (nb * k * 16));
     return std::min<int64_t>(S, cap);
+}
+
+// ---- IVF-PQ: the lookup-table (ADC) scan of the probed lists (ivf_pq_adc.hpp, DESIGN 4.4 "IVF-PQ ADC scan") -------------------------
+// Asked BEFORE ivf_geometry: an admitted batch takes neither the panel pass nor the exact list scan.  Off unless option
+// "ivfpq_adc_max_batch" is set.  The LDS rule is the flat ADC scan's (pq.inc, pq_adc_fits), so an M is served by both scans or by
+// neither: M <= 159.  `ranges_ok`: the handle's norms are usable (ivfpq_adc_prepare, ivf_pq.inc).  The scores of a batch are kept
+// as [nb][stride] float32, stride = the most rows a query can probe.
+constexpr int kIvfAdcMaxBatch = 512, kIvfAdcMaxK = 1024, kIvfAdcMaxParts = 64;
+constexpr int kIvfAdcAuxBytes = 128, kIvfAdcLdsBudget = 160 * 1024;
+constexpr int64_t kIvfAdcScoreBytes = 256ll << 20;
+constexpr int kIvfAdcCandMax = 4096;    // candidates per query the tail keeps in LDS (row + exact key: 48 KiB)
+struct IvfAdcPlan {
+    bool ok = false;
+    int part_rows = 0;              // rows per row part, a multiple of 256
+    unsigned parts = 0;             // grid: row parts of the longest list (<= kIvfAdcMaxParts); parts beyond a list's end exit
+    int64_t stride = 0;             // scores per query: min(N, nprobe * longest list)
+    int cand_cap = 0;               // candidates per query before it is flagged
+    size_t lds_bytes = 0;           // dynamic LDS of the scan: the query's table
+};
+inline IvfAdcPlan ivf_adc_plan(const Options &opt, int codec, int M, bool ranges_ok, int64_t N, int64_t max_list, int64_t nb, int k, int nprobe) {
+    IvfAdcPlan p;
+    if (codec != 2 || opt.force_path != 0) return p;
+    if (nb < 1 || nb > opt.ivfpq_adc_max_batch || nb > kIvfAdcMaxBatch || k > kIvfAdcMaxK) return p;
+    if (M < 1 || (int64_t)M * 1024 + kIvfAdcAuxBytes > kIvfAdcLdsBudget) return p;
+    if (!ranges_ok || N <= 0 || max_list <= 0 || nprobe < 1) return p;
+    p.stride = std::min<int64_t>(N, (int64_t)nprobe * max_list);
+    if (nb * p.stride * 4 > kIvfAdcScoreBytes) return p;
+    // row parts: one workgroup per (part, probe, query), each loads the table (M KiB, from L2) for M bytes of codes per row -- few
+    // (query, probe) pairs take 256-row parts to put more workgroups on the chip, many take 1024-row parts
+    const int64_t pairs = nb * nprobe;
+    int part = opt.ivfpq_adc_part_rows > 0 ? opt.ivfpq_adc_part_rows : pairs < 256 ? 256 : pairs < 1024 ? 512 : 1024;
+    const int64_t least = ((max_list + kIvfAdcMaxParts - 1) / kIvfAdcMaxParts + 255) / 256 * 256;
+    p.part_rows = (int)std::max<int64_t>(part, least);
+    p.parts = (unsigned)((max_list + p.part_rows - 1) / p.part_rows);
+    p.cand_cap = std::min(kIvfAdcCandMax, opt.list_cap > 0 ? opt.list_cap : std::max(64, 2 * k + 32));
+    p.lds_bytes = (size_t)M * 1024;
+    p.ok = true;
+    return p;
 }
 
 // ---- row parts ----------------------------------------------------------------------------------------------------------------------

@@ -29,6 +29,7 @@ struct PqAdcTableArgs {
     int64_t nq;
     int D, M, dsub, metric;
     float xnorm_max;              // max ||x^||
+    const float *cs_dev = nullptr;   // IVF-PQ (ivf_pq_adc.hpp): the batch's scale, chosen by its prep kernel instead of info->cs; eps is then the caller's too
 };
 
 // The bound of the ADC scores against the ideal scaled key cs (||x^||^2 - 2 q.x^) (L2) / -cs q.x^ (IP), in scan units.  With
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(256) void pq_adc_tables_kernel(PqAdcTableArgs a) {
     const int m = blockIdx.x, c = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.y * kPqAdcQB;
     const int nqb = (int)(a.nq - q0 < kPqAdcQB ? a.nq - q0 : kPqAdcQB);
-    const float cs = a.info->cs;
+    const float cs = a.cs_dev ? *a.cs_dev : a.info->cs;
     const double bs = (double)((a.metric == 0 ? -2.f : -1.f) * cs);
     const float *cv = a.cb + ((size_t)m * 256 + c) * a.dsub;
     const float *qv = a.Q + (size_t)q0 * a.D + (size_t)m * a.dsub;
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(256) void pq_adc_tables_kernel(PqAdcTableArgs a) {
 #pragma unroll
     for (int i = 0; i < kPqAdcQB; ++i)
         if (i < nqb) a.tables[((size_t)(q0 + i) * a.M + m) * 256 + c] = (float)(bs * acc[i]);
-    if (m != 0) return;
+    if (m != 0 || a.cs_dev) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = wave; i < nqb; i += 4) {
         const float *row = a.Q + (size_t)(q0 + i) * a.D;

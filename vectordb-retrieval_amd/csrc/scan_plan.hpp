@@ -59,6 +59,8 @@ struct Options {
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
     int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)
+    int ivfpq_adc_max_batch = 0;             // IVF-PQ: largest batch the lookup-table (ADC) scan of the probed lists serves (0 = off; ivf_adc_plan)
+    int ivfpq_adc_part_rows = 0;             // ... rows per row part of that scan (0 auto, else a multiple of 256)
     // k-NN graph (knng.inc)
     int knng_nentry = 0;                     // entry points of a search (0 = default 32)
     int knng_max_iters = 0;                  // step cap of a search (0 = default 8 ef)

@@ -34,6 +34,7 @@
 #include "lsh_tables.hpp"
 #include "pq.hpp"
 #include "pq_adc.hpp"
+#include "ivf_pq_adc.hpp"
 #include "knng.hpp"
 
 using namespace vdb;
@@ -211,6 +212,8 @@ struct CodeBufs {
     DevBuf lsht_keys{"lsht_keys"};                           // hash-table LSH: table keys [N][lsht_kw]
     DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
     DevBuf ivfpq_codes{"ivfpq_codes"};                       // IVF-PQ: codes [N][M] in list order
+    DevBuf ivfpq_n2{"ivfpq_n2"};                             // IVF-PQ, option "ivfpq_adc_max_batch" only: ||x^||^2 float32 [N] in list order, made by the first
+                                                             // admitted batch after an add (ivfpq_adc_prepare; held = valid)
     DevBuf knng_nbrs{"knng_nbrs"};                           // k-NN graph: local row numbers [N][knng_degree], -1 tails
 };
 // per-search workspace of the LSH calls                                                       (freed with the handle)
@@ -235,7 +238,9 @@ struct Workspace {
     DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
     DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ: the fp16 panels converted from the codes for the current batch
-    DevBuf adc_tab{"ws.adc_tab"};           // PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
+    DevBuf adc_tab{"ws.adc_tab"};           // PQ / IVF-PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
+    DevBuf adc_scores{"ws.adc_scores"};     // IVF-PQ, ADC scan: the scores of the probed rows, [nq][stride] (ivf_pq_adc.hpp)
+    DevBuf adc_aux{"ws.adc_aux"};           // ... its scale, flags, B [nq][nprobe] and score positions [nq][nprobe + 1]
 };
 
 // (struct Options -- everything vdb_set_option writes -- is in scan_plan.hpp: the launch rules of the flat scans read it)
@@ -337,6 +342,10 @@ struct vdb_index_s {
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
     PqCodebooks ivfpq;                       // IVF-PQ: the codebooks of the residuals (M = 0: none yet) -- NOT `pq`: that marks a flat PQ handle
+    // IVF-PQ ADC scan (ivfpq_adc_prepare, valid while codes.ivfpq_n2 is held): max ||x^||^2, Cn + Rn = max ||c_l|| + sqrt(sum_m max_c
+    // ||cb[m][c]||^2), and whether both lie in the range the scan's scale can serve
+    double ivfpq_adc_xn2 = 0.0, ivfpq_adc_cr = 0.0;
+    bool ivfpq_adc_ok = false;
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
@@ -437,6 +446,8 @@ constexpr OptionRow kOptions[] = {
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
     {"pq_adc_max_batch", &Options::pq_adc_max_batch, 0, {0, 512}},   // PQ: largest query batch that takes the lookup-table (ADC) scan of the codes (0 = off)
+    {"ivfpq_adc_max_batch", &Options::ivfpq_adc_max_batch, 0, {0, 512}},   // IVF-PQ: largest query batch that takes the lookup-table (ADC) scan of the probed lists (0 = off)
+    {"ivfpq_adc_part_rows", &Options::ivfpq_adc_part_rows, 0, {0, 65536}},   // ... rows per row part of that scan: 0 auto, else a multiple of 256
     {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
     {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
     {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
@@ -1326,7 +1337,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
         // the last search ran an MFMA scan (flat, or the list-major one of an IVF index): ws.small holds its choice and its counters
-        const bool mfma_scanned = h->last.last_path == VDB_PATH_MFMA_SCAN || h->last.last_path == VDB_PATH_PQ_ADC ||
+        const bool mfma_scanned = h->last.last_path == VDB_PATH_MFMA_SCAN || h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC ||
                                   (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma);
         if (h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->plan.ivf_plan.p) {   // (of the last batch of the call)
             IvfPlan pl;
@@ -1343,7 +1354,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         }
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
-        if (h->last.last_path == VDB_PATH_PQ_ADC) s.scan_dtype = 3;                                         // float32 lookup-table sums (PQ, ADC scan)
+        if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;
@@ -1432,6 +1443,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         }
         if (r->n == 0 && (value < r->v[0] || value > r->v[1]))
             throw Error(VDB_ERR_INVALID, "option '" + k + "' must be in [" + number(r->v[0]) + ", " + number(r->v[1]) + "]");
+        if (r->m == &Options::ivfpq_adc_part_rows && (int)value % 256 != 0) throw Error(VDB_ERR_INVALID, "option '" + k + "' must be a multiple of 256");
         if (r->m64) h->opt.*r->m64 = (int64_t)value;
         else h->opt.*r->m = r->n < 0 ? value != 0 : (int)value;
         if (r->m == &Options::timing) h->ev_used = 0;          // (a new recording window)

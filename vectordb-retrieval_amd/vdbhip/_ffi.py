@@ -18,7 +18,7 @@ import numpy as np
 
 VDB_OK, VDB_ERR_INVALID, VDB_ERR_STATE, VDB_ERR_HIP, VDB_ERR_NOMEM, VDB_ERR_UNSUPPORTED = range(6)
 METRIC_L2, METRIC_IP = 0, 1
-PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc"}
+PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc", 8: "ivfpq_adc"}
 
 _LIB_NAME = "libvdbhip.so"
 _lib: Optional[ctypes.CDLL] = None
@@ -114,6 +114,8 @@ SIGNATURES = {
                                       POINTER(c_double)]),
     "vdb_debug_pq_adc_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                         POINTER(c_double)]),
+    "vdb_debug_ivfpq_adc_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p,
+                                           POINTER(c_double)]),
 }
 
 

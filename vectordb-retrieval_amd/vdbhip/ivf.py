@@ -340,12 +340,14 @@ class HipIVFIndexer(BaseIndexer):
 
 
 class HipIVFSearcher(BaseSearcher):
-    """FaissSearcher semantics over a HipIVFIndexer artifact."""
+    """FaissSearcher semantics over a HipIVFIndexer artifact.  `adc_max_batch` (a config entry `adc_max_batch: 16`): option
+    "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer)."""
 
-    def __init__(self, name: str, dimension: int, metric: str = "l2", **kwargs: Any) -> None:
+    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
         self.index: Optional[IVFFlatIndex] = None
         self.normalize_queries = False
+        self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         if artifact.kind != "hip_ivf":
@@ -360,6 +362,9 @@ class HipIVFSearcher(BaseSearcher):
             nprobe = meta.get("nprobe")
         if nprobe is not None:
             self.index.set_nprobe(int(nprobe))
+        if self.adc_max_batch is not None:
+            self.index.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
+            self.index.adc_max_batch = self.adc_max_batch
 
     def _prepare_query(self, query: np.ndarray) -> np.ndarray:
         query = np.asarray(query)

@@ -46,17 +46,35 @@ def parse_ivfpq_key(key: str) -> Tuple[int, int]:
 class IVFPQIndex(PQCodec, IVFFlatIndex):
     """Device-resident IVF<nlist>,PQ<M> index (replaces faiss.index_factory(d, "IVFn,PQm", metric)).  `train` fits the
     centroids and then the codebooks of the residuals on the same rows; `set_centroids` + `train_codebooks` /
-    `set_codebooks` inject them instead.  One GPU only."""
+    `set_codebooks` inject them instead.  One GPU only.  `adc_max_batch`: option "ivfpq_adc_max_batch" -- query batches up to that
+    size (at most 512; 0 = off) take the lookup-table (ADC) scan of the probed lists; same results."""
 
     _pq_prefix = "vdb_ivfpq_"
 
-    def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0):
+    def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0):
         if isinstance(normalize_devices(device), list):
             raise ValueError(_ONE_GPU)
         check_m(int(dim), int(M))
         super().__init__(dim, nlist, metric, device)
         self.M, self.dsub = int(M), int(dim) // int(M)
         _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 2), build_time=True)
+        self.adc_max_batch = int(adc_max_batch or 0)
+        if self.adc_max_batch:
+            self.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
+
+    def debug_adc_scores(self, queries: np.ndarray, probe_list: int, row0: int, nrows: int):
+        """(scores (nq, nrows) float32, eps (nq,) float32, cs): the ADC scan's own scores of the list-order rows [row0, row0 + nrows)
+        of list `probe_list` for a batch of these queries (test hook)."""
+        import ctypes
+
+        q = _ffi.as_f32_c(queries)
+        nq = q.shape[0]
+        scores = np.empty((nq, int(nrows)), dtype=np.float32)
+        eps = np.empty(nq, dtype=np.float32)
+        cs = ctypes.c_double(0.0)
+        _ffi.check(self._lib.vdb_debug_ivfpq_adc_scores(self._handle(), _ffi.ptr(q), nq, int(probe_list), int(row0), int(nrows),
+                                                       _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
+        return scores, eps, cs.value
 
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
         super().train(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid)
@@ -96,7 +114,7 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
 
 def _build_ivfpq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> IVFPQIndex:
     nlist, M = parse_ivfpq_key(key)
-    index = IVFPQIndex(dim, nlist, M, metric, device)
+    index = IVFPQIndex(dim, nlist, M, metric, device, adc_max_batch=int(params.get("adc_max_batch") or 0))
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
     index.add(vectors)
@@ -113,14 +131,17 @@ def _check_key(dimension: int, key: str, device) -> Tuple[int, int]:
 
 
 class HipIVFPQIndexer(BaseIndexer):
-    """FaissFactoryIndexer semantics for an "IVF<nlist>,PQ<M>" key; the artifact is HipIVFSearcher's ('hip_ivf')."""
+    """FaissFactoryIndexer semantics for an "IVF<nlist>,PQ<M>" key; the artifact is HipIVFSearcher's ('hip_ivf').
+    `adc_max_batch` (a config entry `adc_max_batch: 16`): option "ivfpq_adc_max_batch" of the index it builds."""
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", index_type: Optional[str] = None,
-                 index_key: Optional[str] = None, **kwargs: Any) -> None:
+                 index_key: Optional[str] = None, adc_max_batch: int = 0, **kwargs: Any) -> None:
         key = index_key or index_type or "IVF100,PQ8"
         params = dict(kwargs)
         params.setdefault("index_type", key)
+        params["adc_max_batch"] = int(adc_max_batch or 0)
         super().__init__(name, dimension, metric, **params)
+        self.adc_max_batch = int(adc_max_batch or 0)
         self.index_key = self.index_type = key
         _check_key(dimension, key, _resolve_device(self.params.get("device"), self.params.get("device_ids")))
 
@@ -153,8 +174,9 @@ class HipIVFPQSearch(BaseAlgorithm):
     _FORMAT = "vdbhip-ivfpq-v1"
 
     def __init__(self, name: str, dimension: int, index_type: str = "IVF100,PQ8", metric: str = "l2",
-                 device: Optional[int] = None, **kwargs: Any) -> None:
+                 device: Optional[int] = None, adc_max_batch: int = 0, **kwargs: Any) -> None:
         super().__init__(name, dimension, **kwargs)
+        self.adc_max_batch = int(adc_max_batch or 0)      # option "ivfpq_adc_max_batch": a constructor parameter, not part of the artifact
         self.index_type = index_type
         self.metric = "l2" if metric == "l2" else "ip"
         self.device = _resolve_device(device, kwargs.get("device_ids"))
@@ -163,7 +185,8 @@ class HipIVFPQSearch(BaseAlgorithm):
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         data = np.asarray(vectors).astype(np.float32)
-        self.index = _build_ivfpq(data, self.dimension, self.index_type, self.metric, self.device, self.config)
+        self.index = _build_ivfpq(data, self.dimension, self.index_type, self.metric, self.device,
+                                  {**self.config, "adc_max_batch": self.adc_max_batch})
         self.index_built = True
         if "nprobe" in self.config:
             self.index.set_nprobe(int(self.config["nprobe"]))
@@ -210,7 +233,7 @@ class HipIVFPQSearch(BaseAlgorithm):
                 or (n and (lists.min() < 0 or lists.max() >= nlist)):
             raise ValueError("Persisted IVF-PQ files do not match the manifest")
         persist.check_sha256(manifest, arrays)
-        self.index = IVFPQIndex(self.dimension, nlist, m, self.metric, self.device)
+        self.index = IVFPQIndex(self.dimension, nlist, m, self.metric, self.device, adc_max_batch=self.adc_max_batch)
         self.index.set_centroids(arrays["centroids"])      # no k-means, no assignment and no encoding pass: the stored
         self.index.set_codebooks(arrays["codebooks"])      # index is reused as it is
         self.index.add_codes(arrays["codes"], lists, id_base=int(manifest.get("id_base", 0)))
