@@ -35,8 +35,9 @@ __global__ __launch_bounds__(256) void sq8_range_kernel(const float *__restrict_
     if (d < D)
         for (int64_t r = r0 + rl; r < r1; r += 4) {
             const float v = x[(size_t)r * D + d] - cent[(size_t)assign[r] * D4 + d];
-            lo = fminf(lo, v);
-            hi = fmaxf(hi, v);
+            // (fminf / fmaxf drop a NaN: it opens the range to infinity instead, which sq8_train_ranges refuses like an inf)
+            lo = fminf(lo, v != v ? -INFINITY : v);
+            hi = fmaxf(hi, v != v ? INFINITY : v);
         }
     smin[rl][dl] = lo;
     smax[rl][dl] = hi;

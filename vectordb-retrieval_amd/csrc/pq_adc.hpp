@@ -37,11 +37,12 @@ struct PqAdcTableArgs {
 // the float64 norm), the M table entries (one rounding each, sum |T_m| <= f cs qn Xn by Cauchy-Schwarz twice) and the M adds
 // contribute at most (M + 2) 2^-24 cs mag; the float64 chain behind an entry adds dsub 2^-53 of it.  (M + 3) 2^-23 is more than
 // twice that.  Packing the group id into the low 6 mantissa bits moves a score by less than 2^-17 of its magnitude.  No fp16
-// term: neither operand is rounded to fp16.  The 2 % slack and the clamp are those of query_eps_body.
-__device__ __forceinline__ float pq_adc_eps(double n2, int metric, int M, double Xn, double cs) {
+// term: neither operand is rounded to fp16.  key64_round_err (prep.hpp) is the rounding of the exact key itself.  The 2 % slack and
+// the clamp are those of query_eps_body.
+__device__ __forceinline__ float pq_adc_eps(double n2, int metric, int M, int D, double Xn, double cs) {
     const double qn = sqrt(n2);
     const double mag = (metric == 0) ? (Xn * Xn + 2.0 * qn * Xn) : (qn * Xn);
-    const double eps_true = (double)(M + 3) * ldexp(1.0, -23) * mag + ldexp(1.0, -17) * mag;
+    const double eps_true = (double)(M + 3) * ldexp(1.0, -23) * mag + ldexp(1.0, -17) * mag + key64_round_err(metric, D, qn, Xn);
     double e = cs * eps_true * 1.02;
     if (!(e < 1.0e37)) e = 1.0e37;
     return (float)e + 1.0e-30f;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void pq_adc_tables_kernel(PqAdcTableArgs a) {
         for (int d = lane; d < a.D; d += 64) n2 = fma((double)row[d], (double)row[d], n2);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) n2 += __shfl_xor(n2, o);
-        if (lane == 0) a.eps[q0 + i] = pq_adc_eps(n2, a.metric, a.M, (double)a.xnorm_max, (double)cs);
+        if (lane == 0) a.eps[q0 + i] = pq_adc_eps(n2, a.metric, a.M, a.D, (double)a.xnorm_max, (double)cs);
     }
 }
 

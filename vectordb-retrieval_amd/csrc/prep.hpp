@@ -219,7 +219,13 @@ __device__ inline void query_finalize_values(QueryBatchInfo *info, const Finaliz
     info->cs = sq * f.sx;
     info->bscale = -fm * sq;
     const float top = sq * f.sx * f.maxnorm2;
-    info->force_fallback = (nonfinite || !(top < 1.0e30f) || !(sq * f.sx > 1.0e-30f)) ? 1 : 0;
+    // (a batch beyond the gate above keeps sq = 1, and 2 amax may overflow float32 before frexpf sees it: either way the fp16
+    //  B fragments would hold infinities, and a scan that does not happen to turn them into NaN scores would rank by them)
+    const bool q_fits = fm * amax * sq <= 65504.f;        // the largest finite fp16
+    // (every scan reads a bias of 0.9e38 or more as the marker of a padding row, kPadBias, and never selects it: a corpus with a
+    //  squared norm up there -- finite, and tiny once scaled -- is not scanned)
+    const bool norms_fit = f.maxnorm2 < 0.9e38f;
+    info->force_fallback = (nonfinite || !(top < 1.0e30f) || !(sq * f.sx > 1.0e-30f) || !q_fits || !norms_fit) ? 1 : 0;
     info->i8_mode = 0;
     if (f.corpus_i8 && !nonfinite) {
         const int window = !not_u8 ? 1 : (!not_s8 ? 2 : 0);
@@ -371,6 +377,15 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float *__restrict__
     dst[i] = d < D ? src[(size_t)r * D + d] : 0.f;
 }
 
+// Rounding of the canonical float64 key itself, in key units.  Under L2 every t = x - q is rounded to 53 bits before it is
+// squared and D fma roundings follow, so the key is known to (D + 3) 2^-52 (|q| + |x|)^2 at best: once |q| is some 1e8 times
+// |x| that is more than the fp16 terms of the bound, and from 1e16 on every t is -q and ALL rows tie, the id deciding.  The scan
+// must not order rows that the key does not: the bound carries this term, such queries list everything and take the exhaustive
+// pass.  (IP: the products are exact in float64 and D 2^-53 |q| |x| of accumulation is far inside the float32 terms.)
+__device__ __forceinline__ double key64_round_err(int metric, int D, double qn, double Xn) {
+    return metric == 0 ? (double)(D + 3) * ldexp(1.0, -52) * (qn + Xn) * (qn + Xn) : 0.0;
+}
+
 // per-query error bound of the fp16 scan, in scan (scaled) units -- DESIGN.md "exactness guard".
 struct EpsArgs {
     const float *Q;
@@ -444,13 +459,17 @@ __device__ __forceinline__ void query_eps_body(int64_t gid, const EpsArgs &a) {
     const double mag = (a.metric == 0) ? (Xn * Xn + 2.0 * qn * Xn) : (qn * Xn);
     double dot_err = rel_in * qn * Xn;
     if (rel_in > 0.0) dot_err += ldexp(1.0, -36) * sqrt((double)a.D) * qn * Xn;  // fp16 subnormal tail
+    // ... of THIS query under the BATCH's scale: a coordinate is off by up to half a subnormal step, 2^-25 / |bs| in query units,
+    // whatever the query's own length -- next to a query 1e9 times longer its whole fp16 image is zero, and qn says nothing of it
+    if (inexact) dot_err += ldexp(1.0, -25) / fabs((double)bs) * sqrt((double)a.D) * Xn;
     const bool int_exact = a.corpus_int_unscaled && !notint && a.info->sq == 1.f && a.sx == 1.f &&
                            mag * 1.000001 < 16777216.0;
     const double acc_err = int_exact ? 0.0 : (double)(a.Dpad + 3) * ldexp(1.0, -23) * mag;
     const double pack_err = ldexp(1.0, -17) * mag;     // 6 mantissa bits carry the quad id
     const double bias_err = (a.metric == 0 && !int_exact) ? ldexp(1.0, -24) * Xn * Xn : 0.0;
     const double f = (a.metric == 0) ? 2.0 : 1.0;
-    const double eps_true = f * dot_err + acc_err + pack_err + bias_err;
+    const double key_err = int_exact ? 0.0 : key64_round_err(a.metric, a.D, qn, Xn);
+    const double eps_true = f * dot_err + acc_err + pack_err + bias_err + key_err;
     double e = cs * eps_true * 1.02;
     if (!(e < 1.0e37)) e = 1.0e37;
     a.eps[q] = (float)e + 1.0e-30f;
