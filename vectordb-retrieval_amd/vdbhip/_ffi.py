@@ -224,5 +224,11 @@ def as_f32_c(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def as_f32_queries(a: np.ndarray) -> np.ndarray:
+    """`as_f32_c`, a single query (1-D) as a batch of one."""
+    q = as_f32_c(a)
+    return q.reshape(1, -1) if q.ndim == 1 else q
+
+
 def ptr(a: Optional[np.ndarray]) -> Optional[int]:
     return None if a is None else a.ctypes.data

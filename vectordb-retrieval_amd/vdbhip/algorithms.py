@@ -1,4 +1,6 @@
-"""MI355X-backed plugins with the reference's names, argument meaning and output conventions.
+"""MI355X-backed plugins with the reference's names, argument meaning and output conventions, and the conventions every
+plugin module shares (one copy each: operands of an indexer, query batch, result convention, memory figure, warm-up sizing,
+the FAISS-style searcher base and the raw-convention algorithm base).
 
   HipExactSearch         drop-in for ExactSearch            (src/algorithms/exact_search.py:6-78)
   HipBruteForceIndexer   drop-in for BruteForceIndexer      (src/algorithms/modular.py:121-133)
@@ -9,11 +11,12 @@ Convention matrix reproduced here; all return (float32 (Q,k), int64 
                   k > N -> id -1, distance +FLT_MAX / -FLT_MAX   (faiss.IndexFlat padding)
   LinearSearcher  l2 -> sqrt(squared L2)    | cosine -> -(q^ . x^) | ip -> -(q . x), ascending
                   k > N -> id -1, distance +inf
-The GPU work is done by libvdbhip through index.FlatIndex; nothing here computes distances on the CPU.
+  FaissSearcher   l2 -> squared L2          | cosine -> -(q^ . x^) | ip -> -(q . x), ascending; faiss.IndexFlat padding
+The GPU work is done by libvdbhip through the index classes; nothing here computes distances on the CPU.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 
@@ -61,6 +64,13 @@ def reserve_workspace(index, params: dict, k: int = 10) -> None:
         index.reserve(n, k)
 
 
+def warmup_rows(index, reserve) -> int:
+    """Rows of the one warm-up search that sizes a workspace `vdb_reserve` does not cover (sign-LSH, graph search):
+    min(reserve, ntotal); `reserve` None = the default of reserve_workspace, 0 = no warm-up."""
+    reserve = DEFAULT_RESERVE_QUERIES if reserve is None else int(reserve)
+    return min(reserve, index.ntotal) if reserve > 0 and index.ntotal > 0 else 0
+
+
 def apply_engine_options(index, params: dict) -> None:
     """`engine_options: {name: value}` of an algorithm / indexer / searcher config entry are handed to `vdb_set_option`
     before the corpus is added (include/vdbhip.h lists them; e.g. `stream_panels: 1` for a 768-dim corpus that should
@@ -69,7 +79,110 @@ def apply_engine_options(index, params: dict) -> None:
         index.set_option(str(key), float(value))
 
 
-class HipExactSearch(BaseAlgorithm):
+def indexer_operands(vectors: np.ndarray, metric: str) -> Tuple[np.ndarray, str, Dict[str, Any]]:
+    """(rows, library metric, metadata entries) of a FAISS-style indexer (modular.py:253-262): cosine = rows normalised +
+    inner product, and the artifact tells the searcher to normalise its queries."""
+    data = _ffi.as_f32_c(vectors)
+    if metric == "cosine":
+        return _safe_normalize(data), "ip", {"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True}
+    library = "ip" if metric == "ip" else "l2"
+    return data, library, {"faiss_metric": library}
+
+
+def query_batch(queries: np.ndarray, normalize: bool = False) -> np.ndarray:
+    """A float32 (nq, dim) copy of the caller's queries (one query: a batch of one), rows normalised on request."""
+    q = np.asarray(queries)
+    if q.ndim == 1:
+        q = q.reshape(1, -1)
+    q = q.astype(np.float32, copy=True)
+    return _safe_normalize(q) if normalize else q
+
+
+def euclidean_or_negated(d: np.ndarray, i: np.ndarray, metric: str) -> SearchResult:
+    """Library results -> LinearSearcher's convention: Euclidean distance for 'l2', negated score otherwise, +inf where
+    the id is -1."""
+    pad = i < 0
+    d = np.sqrt(np.where(pad, np.float32(0), d), dtype=np.float32) if metric == "l2" else -d
+    d[pad] = np.inf
+    return d.astype(np.float32, copy=False), i
+
+
+def resident_mb(index) -> float:
+    """MB resident in HBM (picked up by experiment_runner.py:493-497); 0.0 without an index."""
+    return index.stats()["bytes_resident"] / (1024.0 * 1024.0) if index else 0.0
+
+
+class RawAlgorithm(BaseAlgorithm):
+    """A stand-alone algorithm over one index (self.index) with the raw FAISS conventions of ApproximateSearch
+    (approximate_search.py:53-87): no normalisation, no sign flip."""
+
+    index = None
+
+    def _require_built(self) -> None:
+        if not self.index_built:
+            raise RuntimeError("Index has not been built yet.")
+
+    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
+        self._require_built()
+        d, i = self.index.search(np.array([query], dtype=np.float32), k)
+        return d[0], i[0]
+
+    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
+        self._require_built()
+        return self.index.search(np.asarray(queries).astype(np.float32), k)
+
+    def get_memory_usage(self) -> float:
+        return resident_mb(self.index)
+
+
+class FaissStyleSearcher(BaseSearcher):
+    """FaissSearcher (modular.py:393-449, 536-548) over an artifact of kind `_kind` whose data is one of this library's
+    indexes: queries normalised when the artifact says so, distances negated for cosine / ip, squared L2 as it is.  A
+    subclass adds its own parameters in `attach` (after `_bind`) and, where it is not `index.search`, `_search_index`."""
+
+    _kind = ""
+
+    def __init__(self, name: str, dimension: int, metric: str = "l2", **kwargs: Any) -> None:
+        super().__init__(name, dimension, metric, **kwargs)
+        self.index = None
+        self.normalize_queries = False
+
+    def _bind(self, artifact: IndexArtifact) -> dict:
+        """The part of `attach` every subclass shares; returns the artifact's metadata."""
+        if artifact.kind != self._kind:
+            raise ValueError(f"{type(self).__name__} requires '{self._kind}' artifact")
+        self.index = artifact.data
+        meta = artifact.metadata or {}
+        self.metric = meta.get("metric", self.metric)
+        self.normalize_queries = meta.get("normalize_queries", False)
+        return meta
+
+    def _require_attached(self) -> None:
+        if not self._prepared:
+            raise RuntimeError("FaissSearcher not attached to an index")
+
+    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
+        return query_batch(query, self.normalize_queries)
+
+    def _search_index(self, queries: np.ndarray, k: int) -> SearchResult:
+        return self.index.search(queries, k)
+
+    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
+        d, i = self.batch_search(self._prepare_query(query), k)
+        return d[0], i[0]
+
+    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
+        self._require_attached()
+        d, i = self._search_index(self._prepare_query(queries), k)
+        if self.metric in {"cosine", "ip"}:
+            d = -d
+        return d.astype(np.float32), i.astype(np.int64)
+
+    def get_memory_usage(self) -> float:
+        return resident_mb(self.index)
+
+
+class HipExactSearch(RawAlgorithm):
     """Exact k-NN on one MI355X -- or, with `device_ids: [..]` of several, on ONE index row-sharded over them in this
     process; same constructor and results as ExactSearch (faiss.IndexFlat)."""
 
@@ -93,10 +206,6 @@ class HipExactSearch(BaseAlgorithm):
         reserve_workspace(self.index, self.config)
         self.index_built = True
 
-    def _require_built(self) -> None:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
         self._require_built()
         d, i = self.index.search(np.asarray(query, dtype=np.float32).reshape(1, -1), k)
@@ -108,9 +217,15 @@ class HipExactSearch(BaseAlgorithm):
         self.record_operation("ndis", float(q.shape[0]) * float(self.index.ntotal))
         return self.index.search(q, k)
 
-    def get_memory_usage(self) -> float:
-        """MB resident in HBM (picked up by experiment_runner.py:493-497)."""
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+
+def _flat_index(store: np.ndarray, dimension: int, metric: str, params: dict) -> FlatIndex:
+    """The flat index of the brute-force pair: options, rows (normalised for cosine), workspace."""
+    data, library_metric, _ = indexer_operands(store, metric)
+    index = FlatIndex(dimension, library_metric, _resolve_device(params.get("device"), params.get("device_ids")))
+    apply_engine_options(index, params)
+    index.add(data)
+    reserve_workspace(index, params)
+    return index
 
 
 class HipBruteForceIndexer(BaseIndexer):
@@ -120,16 +235,11 @@ class HipBruteForceIndexer(BaseIndexer):
         store = _ffi.as_f32_c(vectors)
         if store.ndim != 2 or store.shape[1] != self.dimension:
             raise ValueError("Vector dimension mismatch in HipBruteForceIndexer")
-        device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
         if self.metric not in ("l2", "cosine", "ip"):
             # same late failure as the reference: an unknown metric only breaks at search time
             return IndexArtifact(kind="raw_vectors", data=store,
                                  metadata={"metric": self.metric, "normalize_vectors": False})
-        upload = _safe_normalize(store) if self.metric == "cosine" else store
-        index = FlatIndex(self.dimension, "l2" if self.metric == "l2" else "ip", device)
-        apply_engine_options(index, self.params)
-        index.add(upload)
-        reserve_workspace(index, self.params)
+        index = _flat_index(store, self.dimension, self.metric, self.params)
         return IndexArtifact(kind="raw_vectors", data=store,
                              metadata={"metric": self.metric, "normalize_vectors": self.metric == "cosine",
                                        "hip_index": index, "hip_index_metric": self.metric})
@@ -151,46 +261,25 @@ class HipLinearSearcher(BaseSearcher):
             if meta.get("hip_index") is not None and meta.get("hip_index_metric") == self.metric:
                 self._index = meta["hip_index"]
             else:  # artifact from the reference's own BruteForceIndexer, or built for another metric
-                device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
-                data = _ffi.as_f32_c(store)
-                self._index = FlatIndex(self.dimension, "l2" if self.metric == "l2" else "ip", device)
-                apply_engine_options(self._index, self.params)
-                self._index.add(_safe_normalize(data) if self.metric == "cosine" else data)
-                reserve_workspace(self._index, self.params)
+                self._index = _flat_index(store, self.dimension, self.metric, self.params)
         self._prepared = True
 
-    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
-        query = np.asarray(query)
-        if query.ndim == 1:
-            query = query.reshape(1, -1)
-        return query.astype(np.float32, copy=True)
-
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        d, i = self.batch_search(self._prepare_query(query), k)
+        d, i = self.batch_search(query_batch(query), k)
         return d[0], i[0]
 
     def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
         if not self._prepared:
             raise RuntimeError("LinearSearcher not attached to an index")
-        q = self._prepare_query(queries)
         if self.metric not in ("l2", "cosine", "ip"):
             raise ValueError(f"Unsupported metric '{self.metric}' for LinearSearcher")
         if self._ntotal == 0:
             raise RuntimeError("LinearSearcher cannot operate on empty index")
-        if self.metric == "cosine":
-            q = _safe_normalize(q)
-        d, i = self._index.search(q, k)
-        pad = i < 0
-        if self.metric == "l2":
-            d = np.sqrt(np.where(pad, np.float32(0), d), dtype=np.float32)
-        else:
-            d = -d
-        if pad.any():
-            d[pad] = np.inf
-        return d.astype(np.float32, copy=False), i
+        d, i = self._index.search(query_batch(queries, self.metric == "cosine"), k)
+        return euclidean_or_negated(d, i, self.metric)
 
     def get_memory_usage(self) -> float:
-        return self._index.stats()["bytes_resident"] / (1024.0 * 1024.0) if getattr(self, "_index", None) else 0.0
+        return resident_mb(getattr(self, "_index", None))
 
 
 def rerank_candidates(index: FlatIndex, queries: np.ndarray, candidate_ids: np.ndarray, k: int, metric: str):
@@ -198,11 +287,7 @@ def rerank_candidates(index: FlatIndex, queries: np.ndarray, candidate_ids: np.n
     per query the valid (>= 0) candidate ids are re-scored exactly and the best k returned -- Euclidean distance
     for 'l2', negated score for 'cosine' / 'ip' (queries and the indexed vectors already normalised for cosine),
     unused slots padded with +inf / -1.  One batched launch replaces the reference's per-query Python loop."""
-    d, i = index.rerank(queries, candidate_ids, k)
-    pad = i < 0
-    d = np.sqrt(np.where(pad, np.float32(0), d), dtype=np.float32) if metric == "l2" else -d
-    d[pad] = np.inf
-    return d.astype(np.float32, copy=False), i
+    return euclidean_or_negated(*index.rerank(queries, candidate_ids, k), metric)
 
 
 register_algorithm("HipExactSearch", HipExactSearch)

@@ -1,4 +1,4 @@
-"""Thin object wrappers over the libvdbhip C-ABI handles (flat index; IVF-Flat in ivf.py).
+"""Thin object wrappers over the libvdbhip C-ABI handles: what every kind of index shares, and the flat index.
 
 The returned conventions are those of faiss.IndexFlat, i.e. of the reference's ExactSearch
 (exact_search.py:62-78): squared L2 ascending / raw inner product descending, int64 ids,
@@ -16,6 +16,12 @@ from . import _ffi
 _METRICS = {"l2": _ffi.METRIC_L2, "ip": _ffi.METRIC_IP}
 
 
+def metric_code(metric: str) -> int:
+    if metric not in _METRICS:
+        raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+    return _METRICS[metric]
+
+
 def normalize_devices(device):
     """int -> int; a sequence of GPU ordinals -> list (length one -> its only member)."""
     if isinstance(device, (list, tuple, np.ndarray)):
@@ -26,9 +32,22 @@ def normalize_devices(device):
     return int(device)
 
 
+def one_device(device, message: str) -> int:
+    """`normalize_devices` for the kinds of index that run on one GPU: more than one ordinal is refused with `message`."""
+    device = normalize_devices(device)
+    if isinstance(device, list):
+        raise ValueError(message)
+    return device
+
+
+def _pair(nq: int, width, first=np.float32) -> Tuple[np.ndarray, np.ndarray]:
+    """The (nq, width) output pair of a host call: float32 / int64 for results, int32 / int64 for candidates."""
+    return np.empty((nq, width), first), np.empty((nq, width), np.int64)
+
+
 class _Handle:
     """What every index object shares: the library, the C-ABI handle it owns (one GPU ordinal or a list of them, see
-    _ffi.create_handle) and the calls that are the same on every kind of index."""
+    _ffi.create_handle), the calls that are the same on every kind of index, and the marshalling of host arrays (self.dim)."""
 
     def __init__(self, dim: int, metric: int, device):
         self._lib = _ffi.load()
@@ -55,6 +74,10 @@ class _Handle:
         _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
         return s.as_dict()
 
+    def _sync_ntotal(self) -> None:
+        """The row count is the library's: an add may have replaced rows instead of appending (e.g. after a failed add)."""
+        self.ntotal = int(self.stats()["ntotal"])
+
     def reserve(self, nq: int, k: int = 10) -> None:
         """Size the search workspace for batches of up to `nq` queries now (vdb_reserve): the reference harness times its
         very first batch_search, allocations included (experiment_runner.py:431-437)."""
@@ -63,47 +86,91 @@ class _Handle:
     def set_option(self, key: str, value: float) -> None:
         _ffi.check(self._lib.vdb_set_option(self._handle(), key.encode(), float(value)), build_time=True)
 
-    def debug_adc_scores(self, queries: np.ndarray, row0: int, nrows: int):
-        """(scores (nq, nrows), eps (nq), cs) of the lookup-table (ADC) scan: raw, unpacked scores, as FlatIndex.debug_scan_scores.
-        Flat PQ indexes with rows only; every other kind of handle is refused by the library."""
-        q = _ffi.as_f32_c(queries)
+    def reset(self) -> None:
+        """Drop every row; what was trained or set (centroids, ranges, codebooks) stays (faiss.Index.reset)."""
+        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
+        self.ntotal = 0
+
+    # -- host arrays -> what the C ABI reads -------------------------------------------------------------
+    def _queries(self, queries: np.ndarray) -> np.ndarray:
+        q = _ffi.as_f32_queries(queries)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
+        return q
+
+    def _rows(self, x: np.ndarray) -> np.ndarray:
+        x = _ffi.as_f32_c(x)
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        return x
+
+    def _codes(self, codes: np.ndarray) -> np.ndarray:
+        """uint8 (n, M) product codes (the PQ kinds: self.M)."""
+        c = np.ascontiguousarray(codes, dtype=np.uint8)
+        if c.ndim != 2 or c.shape[1] != self.M:
+            raise ValueError(f"expected (n, {self.M}) codes, got {c.shape}")
+        return c
+
+    def _debug_scores(self, entry, queries: np.ndarray, nrows: int, *where):
+        """(scores (nq, nrows) float32, eps (nq,) float32, cs) of a scan's own raw, unpacked scores (test hooks)."""
+        q = self._queries(queries)
         nq = q.shape[0]
-        scores = np.empty((nq, nrows), np.float32)
+        scores = np.empty((nq, int(nrows)), np.float32)
         eps = np.empty((nq,), np.float32)
         cs = ctypes.c_double(0.0)
-        _ffi.check(self._lib.vdb_debug_pq_adc_scores(self._handle(), _ffi.ptr(q), nq, int(row0), int(nrows),
-                                                     _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
+        _ffi.check(entry(self._handle(), _ffi.ptr(q), nq, *where, _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
         return scores, eps, float(cs.value)
 
 
-class FlatIndex(_Handle):
+class _FlatSearch(_Handle):
+    """The search calls of the handles vdb_search serves: the flat index and the flat PQ index."""
+
+    def search(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], k)
+        _ffi.check(self._lib.vdb_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+    def search_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
+        _ffi.check(self._lib.vdb_search_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
+
+    def search_partial_device(self, q_ptr: int, nq: int, k: int, keys_ptr: int, ids_ptr: int, stream: int = 0) -> None:
+        """Partial top-k (float64 order keys + ids, device pointers) for merge_partials_device."""
+        _ffi.check(self._lib.vdb_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
+                                                       stream or None))
+
+    def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-k among explicit candidate ids per query (nq, ncand) int64, -1 = empty slot."""
+        q = _ffi.as_f32_queries(queries)
+        c = np.ascontiguousarray(candidate_ids, dtype=np.int64)
+        if c.ndim != 2 or c.shape[0] != q.shape[0] or q.shape[1] != self.dim:
+            raise RuntimeError(f"expected queries (nq, {self.dim}) and candidates (nq, ncand), got {q.shape}, {c.shape}")
+        D, I = _pair(q.shape[0], k)
+        _ffi.check(self._lib.vdb_rerank(self._handle(), _ffi.ptr(q), q.shape[0], _ffi.ptr(c), c.shape[1], int(k),
+                                        _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+
+class FlatIndex(_FlatSearch):
     """Device-resident brute-force index (replaces faiss.IndexFlat(d, metric)).  `device`: one GPU ordinal, or a list of
     them -- ONE index row-sharded over those MI355X inside this process (vdb_create_multi): same calls, same results."""
 
     def __init__(self, dim: int, metric: str = "l2", device=0):
-        if metric not in _METRICS:
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        code = metric_code(metric)
         self.dim, self.metric, self.device = int(dim), metric, normalize_devices(device)
-        super().__init__(self.dim, _METRICS[metric], self.device)
+        super().__init__(self.dim, code, self.device)
         self.ntotal = 0
 
     @property
     def devices(self):
         return list(self.device) if isinstance(self.device, list) else [self.device]
 
-    def _sync_ntotal(self) -> None:
-        """The row count is the library's: an add may have replaced rows instead of appending (e.g. after a failed add)."""
-        s = _ffi.Stats()
-        _ffi.check(self._lib.vdb_stats(self._handle(), ctypes.byref(s)))
-        self.ntotal = int(s.ntotal)
-
     # -- build --------------------------------------------------------------------------------------
     def add(self, vectors: np.ndarray, id_base: int = 0) -> None:
         """Append rows (faiss.Index.add): row i of the index, counted over all adds, has id `id_base + i`; every add of
         one index passes the same `id_base`.  `reset()` empties the index."""
-        x = _ffi.as_f32_c(vectors)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        x = self._rows(vectors)
         try:
             _ffi.check(self._lib.vdb_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
         finally:
@@ -118,43 +185,8 @@ class FlatIndex(_Handle):
 
     def reset(self) -> None:
         """Drop every row (faiss.Index.reset)."""
-        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
+        super().reset()
         self._sync_ntotal()
-
-    # -- search -------------------------------------------------------------------------------------
-    def search(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
-        nq = q.shape[0]
-        D = np.empty((nq, k), np.float32)
-        I = np.empty((nq, k), np.int64)
-        _ffi.check(self._lib.vdb_search(self._handle(), _ffi.ptr(q), nq, int(k), _ffi.ptr(D), _ffi.ptr(I)))
-        return D, I
-
-    def search_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
-        """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
-        _ffi.check(self._lib.vdb_search_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
-
-    def search_partial_device(self, q_ptr: int, nq: int, k: int, keys_ptr: int, ids_ptr: int, stream: int = 0) -> None:
-        _ffi.check(self._lib.vdb_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
-                                                       stream or None))
-
-    def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        """Exact top-k among explicit candidate ids per query (nq, ncand) int64, -1 = empty slot."""
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        c = np.ascontiguousarray(candidate_ids, dtype=np.int64)
-        if c.ndim != 2 or c.shape[0] != q.shape[0] or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected queries (nq, {self.dim}) and candidates (nq, ncand), got {q.shape}, {c.shape}")
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_rerank(self._handle(), _ffi.ptr(q), q.shape[0], _ffi.ptr(c), c.shape[1], int(k),
-                                        _ffi.ptr(D), _ffi.ptr(I)))
-        return D, I
 
     # -- sign-LSH codes (vdb_lsh_*): Hamming candidates + exact re-rank -------------------------------
     def lsh_set_projection(self, projection: np.ndarray) -> None:
@@ -181,20 +213,11 @@ class FlatIndex(_Handle):
         _ffi.check(self._lib.vdb_lsh_get_codes(self._handle(), _ffi.ptr(codes)))
         return codes
 
-    def _lsh_queries(self, queries: np.ndarray) -> np.ndarray:
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
-        return q
-
     def lsh_candidates(self, queries: np.ndarray, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
         """Per query the min(ncand, ntotal) rows smallest under (Hamming distance, id): (int32 (nq, ncand), int64 (nq, ncand)),
         padded with INT32_MAX / -1."""
-        q = self._lsh_queries(queries)
-        ham = np.empty((q.shape[0], int(ncand)), np.int32)
-        ids = np.empty((q.shape[0], int(ncand)), np.int64)
+        q = self._queries(queries)
+        ham, ids = _pair(q.shape[0], int(ncand), np.int32)
         _ffi.check(self._lib.vdb_lsh_candidates(self._handle(), _ffi.ptr(q), q.shape[0], int(ncand), _ffi.ptr(ham), _ffi.ptr(ids)))
         return ham, ids
 
@@ -203,9 +226,8 @@ class FlatIndex(_Handle):
 
     def lsh_search(self, queries: np.ndarray, k: int, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
         """Exact top-k among the `ncand` Hamming candidates of every query (flat conventions and padding)."""
-        q = self._lsh_queries(queries)
-        D = np.empty((q.shape[0], int(k)), np.float32)
-        I = np.empty((q.shape[0], int(k)), np.int64)
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], int(k))
         _ffi.check(self._lib.vdb_lsh_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), int(ncand), _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
@@ -253,9 +275,8 @@ class FlatIndex(_Handle):
     def lsht_candidates(self, queries: np.ndarray, ncand: int) -> Tuple[np.ndarray, np.ndarray]:
         """Per query its colliding rows under (votes descending, first table, id), at most `ncand`: (votes int32 (nq, ncand),
         ids int64 (nq, ncand)), padded with 0 / -1."""
-        q = self._lsh_queries(queries)
-        votes = np.empty((q.shape[0], int(ncand)), np.int32)
-        ids = np.empty((q.shape[0], int(ncand)), np.int64)
+        q = self._queries(queries)
+        votes, ids = _pair(q.shape[0], int(ncand), np.int32)
         _ffi.check(self._lib.vdb_lsht_candidates(self._handle(), _ffi.ptr(q), q.shape[0], int(ncand), _ffi.ptr(votes), _ffi.ptr(ids)))
         return votes, ids
 
@@ -265,9 +286,8 @@ class FlatIndex(_Handle):
     def lsht_search(self, queries: np.ndarray, k: int, ncand: int, fallback: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Exact top-k among the `ncand` vote candidates of every query (flat conventions and padding); `fallback`: a query
         without a colliding row gets the exact flat top-k instead."""
-        q = self._lsh_queries(queries)
-        D = np.empty((q.shape[0], int(k)), np.float32)
-        I = np.empty((q.shape[0], int(k)), np.int64)
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], int(k))
         _ffi.check(self._lib.vdb_lsht_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), int(ncand), int(bool(fallback)),
                                              _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
@@ -281,14 +301,7 @@ class FlatIndex(_Handle):
 
     # -- introspection --------------------------------------------------------------------------------
     def debug_scan_scores(self, queries: np.ndarray, row0: int, nrows: int):
-        q = _ffi.as_f32_c(queries)
-        nq = q.shape[0]
-        scores = np.empty((nq, nrows), np.float32)
-        eps = np.empty((nq,), np.float32)
-        cs = ctypes.c_double(0.0)
-        _ffi.check(self._lib.vdb_debug_scan_scores(self._handle(), _ffi.ptr(q), nq, int(row0), int(nrows),
-                                                   _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
-        return scores, eps, float(cs.value)
+        return self._debug_scores(self._lib.vdb_debug_scan_scores, queries, nrows, int(row0), int(nrows))
 
 
 def merge_partials_device(metric: str, device: int, keys_ptr: int, ids_ptr: int, nparts: int, nq: int, k: int,

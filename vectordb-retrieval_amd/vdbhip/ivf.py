@@ -14,17 +14,15 @@ FAISS: 25 iterations, seed 1234, at most 256 training points per centroid.
 """
 from __future__ import annotations
 
-import ctypes
 import re
 from typing import Any, Optional, Tuple
 
 import numpy as np
 
 from . import _ffi, persist
-from .index import _Handle, normalize_devices
-from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
-from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
-                         register_algorithm, register_indexer, register_searcher)
+from .index import _Handle, _pair, metric_code, normalize_devices, one_device
+from .algorithms import FaissStyleSearcher, RawAlgorithm, _resolve_device, indexer_operands, reserve_workspace
+from .plugin_api import BaseIndexer, IndexArtifact, Metadata, register_algorithm, register_indexer, register_searcher
 
 _IVF_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*Flat\s*$")
 _IVF_CODEC_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*(Flat|SQ8)\s*$")
@@ -53,16 +51,15 @@ class IVFFlatIndex(_Handle):
     def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0):
         """`device`: one GPU ordinal or a list of them (rows of every list split over those GPUs, coarse quantizer
         replicated: vdb_create_multi)."""
-        if metric not in ("l2", "ip"):
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        code = metric_code(metric)
         self.dim, self.nlist, self.metric, self.device = int(dim), int(nlist), metric, normalize_devices(device)
-        super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
+        super().__init__(self.dim, code, self.device)
         self.is_trained = False
         self.ntotal = 0
         self.nprobe = 1
 
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
-        x = _ffi.as_f32_c(x)
+        x = self._rows(x)
         _ffi.check(self._lib.vdb_ivf_train(self._handle(), self.nlist, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                            int(max_points_per_centroid)), build_time=True)
         self.is_trained = True
@@ -85,23 +82,23 @@ class IVFFlatIndex(_Handle):
         """File the rows under the centroids, appending to the lists (faiss.IndexIVF.add; same `id_base` on every add of
         one index, `reset()` empties it).  `list_of_row` (int32, one list id per row, as `assignment()` returned it
         for this corpus and these centroids) skips the nearest-centroid pass: what loading a persisted index does."""
-        x = _ffi.as_f32_c(x)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
-        if list_of_row is None:
-            _ffi.check(self._lib.vdb_ivf_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
-        else:
-            lor = np.ascontiguousarray(list_of_row, dtype=np.int32)
-            if lor.shape != (x.shape[0],):
-                raise ValueError(f"expected {x.shape[0]} list ids, got {lor.shape}")
-            _ffi.check(self._lib.vdb_ivf_add_assigned(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base), _ffi.ptr(lor)),
-                       build_time=True)
-        self.ntotal = int(self.stats()["ntotal"])      # (the library's count: an add may replace instead of append)
+        x = self._rows(x)
+        lor = None if list_of_row is None else self._list_ids(list_of_row, x.shape[0])
+        try:
+            if lor is None:
+                _ffi.check(self._lib.vdb_ivf_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
+            else:
+                _ffi.check(self._lib.vdb_ivf_add_assigned(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base), _ffi.ptr(lor)),
+                           build_time=True)
+        finally:
+            self._sync_ntotal()
 
-    def reset(self) -> None:
-        """Drop every row; the centroids stay (faiss.IndexIVF.reset)."""
-        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
-        self.ntotal = 0
+    @staticmethod
+    def _list_ids(list_of_row: np.ndarray, n: int) -> np.ndarray:
+        lor = np.ascontiguousarray(list_of_row, dtype=np.int32)
+        if lor.shape != (n,):
+            raise ValueError(f"expected {n} list ids, got {lor.shape}")
+        return lor
 
     def assignment(self) -> np.ndarray:
         out = np.empty((self.ntotal,), np.int32)
@@ -113,13 +110,8 @@ class IVFFlatIndex(_Handle):
         self.nprobe = int(nprobe)
 
     def search(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], k)
         _ffi.check(self._lib.vdb_ivf_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
@@ -139,17 +131,14 @@ class IVFSQ8Index(IVFFlatIndex):
     rows; `set_centroids` + `train_ranges` / `set_ranges` inject them instead.  One GPU only."""
 
     def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0):
-        if isinstance(normalize_devices(device), list):
-            raise ValueError("IVF<nlist>,SQ8 runs on one GPU: a multi-device index (more than one device id) is not "
-                             "available for the SQ8 codec")
+        one_device(device, "IVF<nlist>,SQ8 runs on one GPU: a multi-device index (more than one device id) is not "
+                           "available for the SQ8 codec")
         super().__init__(dim, nlist, metric, device)
         _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 1), build_time=True)
 
     def train_ranges(self, x: np.ndarray) -> None:
         """vmin / vdiff from the residuals of `x` against the installed centroids (at most 100 000 rows are read)."""
-        x = _ffi.as_f32_c(x)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        x = self._rows(x)
         _ffi.check(self._lib.vdb_ivf_sq8_train_ranges(self._handle(), _ffi.ptr(x), x.shape[0]), build_time=True)
         self.ntotal = 0
 
@@ -213,7 +202,7 @@ def _build_ivf(vectors: np.ndarray, dim: int, key: str, metric: str, device: int
     return index
 
 
-class HipApproximateSearch(BaseAlgorithm):
+class HipApproximateSearch(RawAlgorithm):
     """ApproximateSearch semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8": train -> add -> nprobe from kwargs; raw
     FAISS conventions (no normalisation, no sign flip)."""
 
@@ -233,20 +222,6 @@ class HipApproximateSearch(BaseAlgorithm):
         if "nprobe" in self.config:
             self.index.set_nprobe(int(self.config["nprobe"]))
         reserve_workspace(self.index, self.config)
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        d, i = self.index.search(np.array([query], dtype=np.float32), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        return self.index.search(np.asarray(queries).astype(np.float32), k)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
     # ---- persistence through the BaseAlgorithm hook (base_algorithm.py:98-120), by the protocol of persist.py ---------------
     # An SQ8 artifact stores the corpus, centroids and lists like a Flat one plus the ranges (ranges.npy: vmin, vdiff), under
@@ -320,16 +295,8 @@ class HipIVFIndexer(BaseIndexer):
         parse_index_key(key)
 
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
-        data = _ffi.as_f32_c(vectors)
-        meta = {"metric": self.metric, "index_key": self.index_key, "faiss_metric": "l2"}
-        metric = "l2"
-        if self.metric == "cosine":
-            data = _safe_normalize(data)
-            metric = "ip"
-            meta.update({"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True})
-        elif self.metric == "ip":
-            metric = "ip"
-            meta["faiss_metric"] = "ip"
+        data, metric, entries = indexer_operands(vectors, self.metric)
+        meta = {"metric": self.metric, "index_key": self.index_key, **entries}
         device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
         index = _build_ivf(data, self.dimension, self.index_key, metric, device, self.params)
         if "nprobe" in self.params:                       # runtime attribute of the index (modular.py:269-275)
@@ -339,23 +306,18 @@ class HipIVFIndexer(BaseIndexer):
         return IndexArtifact(kind="hip_ivf", data=index, metadata=meta)
 
 
-class HipIVFSearcher(BaseSearcher):
+class HipIVFSearcher(FaissStyleSearcher):
     """FaissSearcher semantics over a HipIVFIndexer artifact.  `adc_max_batch` (a config entry `adc_max_batch: 16`): option
     "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer)."""
 
+    _kind = "hip_ivf"
+
     def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
-        self.index: Optional[IVFFlatIndex] = None
-        self.normalize_queries = False
         self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
-        if artifact.kind != "hip_ivf":
-            raise ValueError("HipIVFSearcher requires 'hip_ivf' artifact")
-        self.index = artifact.data
-        meta = artifact.metadata or {}
-        self.metric = meta.get("metric", self.metric)
-        self.normalize_queries = meta.get("normalize_queries", False)
+        meta = self._bind(artifact)
         self._prepared = True
         nprobe = self.params.get("nprobe")
         if nprobe is None:
@@ -365,28 +327,6 @@ class HipIVFSearcher(BaseSearcher):
         if self.adc_max_batch is not None:
             self.index.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
             self.index.adc_max_batch = self.adc_max_batch
-
-    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
-        query = np.asarray(query)
-        if query.ndim == 1:
-            query = query.reshape(1, -1)
-        query = query.astype(np.float32, copy=True)
-        return _safe_normalize(query) if self.normalize_queries else query
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        d, i = self.batch_search(self._prepare_query(query), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self._prepared:
-            raise RuntimeError("FaissSearcher not attached to an index")
-        d, i = self.index.search(self._prepare_query(queries), k)
-        if self.metric in {"cosine", "ip"}:
-            d = -d
-        return d.astype(np.float32), i.astype(np.int64)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
 
 register_algorithm("HipApproximateSearch", HipApproximateSearch)

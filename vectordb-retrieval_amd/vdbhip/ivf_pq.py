@@ -23,12 +23,11 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _ffi, persist
-from .index import normalize_devices
-from .algorithms import _resolve_device, _safe_normalize, reserve_workspace
+from .index import one_device
+from .algorithms import RawAlgorithm, _resolve_device, indexer_operands, reserve_workspace
 from .ivf import IVFFlatIndex
-from .pq import PQCodec, check_m
-from .plugin_api import (BaseAlgorithm, BaseIndexer, IndexArtifact, Metadata, SearchResult, register_algorithm,
-                         register_indexer)
+from .pq import PQCodec, check_key_dimension, check_m
+from .plugin_api import BaseIndexer, IndexArtifact, Metadata, register_algorithm, register_indexer
 
 _IVFPQ_KEY = re.compile(r"^\s*IVF(\d+)\s*,\s*PQ(\d+)(?:x8)?\s*$")
 _ONE_GPU = "IVF<nlist>,PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available"
@@ -52,8 +51,7 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
     _pq_prefix = "vdb_ivfpq_"
 
     def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0):
-        if isinstance(normalize_devices(device), list):
-            raise ValueError(_ONE_GPU)
+        one_device(device, _ONE_GPU)
         check_m(int(dim), int(M))
         super().__init__(dim, nlist, metric, device)
         self.M, self.dsub = int(M), int(dim) // int(M)
@@ -65,16 +63,7 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
     def debug_adc_scores(self, queries: np.ndarray, probe_list: int, row0: int, nrows: int):
         """(scores (nq, nrows) float32, eps (nq,) float32, cs): the ADC scan's own scores of the list-order rows [row0, row0 + nrows)
         of list `probe_list` for a batch of these queries (test hook)."""
-        import ctypes
-
-        q = _ffi.as_f32_c(queries)
-        nq = q.shape[0]
-        scores = np.empty((nq, int(nrows)), dtype=np.float32)
-        eps = np.empty(nq, dtype=np.float32)
-        cs = ctypes.c_double(0.0)
-        _ffi.check(self._lib.vdb_debug_ivfpq_adc_scores(self._handle(), _ffi.ptr(q), nq, int(probe_list), int(row0), int(nrows),
-                                                       _ffi.ptr(scores), _ffi.ptr(eps), ctypes.byref(cs)))
-        return scores, eps, cs.value
+        return self._debug_scores(self._lib.vdb_debug_ivfpq_adc_scores, queries, nrows, int(probe_list), int(row0), int(nrows))
 
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
         super().train(x, niter=niter, seed=seed, max_points_per_centroid=max_points_per_centroid)
@@ -82,9 +71,7 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
 
     def train_codebooks(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
         """Codebooks from the residuals of a row sample of `x` against the installed centroids."""
-        x = _ffi.as_f32_c(x)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        x = self._rows(x)
         _ffi.check(self._lib.vdb_ivfpq_train(self._handle(), self.M, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                              int(max_points_per_centroid)), build_time=True)
         self.ntotal = 0             # (new codebooks: rows encoded under the old ones are dropped)
@@ -95,17 +82,13 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
 
     def add_codes(self, codes: np.ndarray, list_of_row: np.ndarray, id_base: int = 0) -> None:
         """Append rows given as codes, uint8 (n, M), under the given lists: what loading a persisted index does."""
-        c = np.ascontiguousarray(codes, dtype=np.uint8)
-        if c.ndim != 2 or c.shape[1] != self.M:
-            raise ValueError(f"expected (n, {self.M}) codes, got {c.shape}")
-        lor = np.ascontiguousarray(list_of_row, dtype=np.int32)
-        if lor.shape != (c.shape[0],):
-            raise ValueError(f"expected {c.shape[0]} list ids, got {lor.shape}")
+        c = self._codes(codes)
+        lor = self._list_ids(list_of_row, c.shape[0])
         try:
             _ffi.check(self._lib.vdb_ivfpq_add_codes(self._handle(), _ffi.ptr(c), c.shape[0], int(id_base), _ffi.ptr(lor)),
                        build_time=True)
         finally:
-            self.ntotal = int(self.stats()["ntotal"])
+            self._sync_ntotal()
 
     def reconstruct(self) -> np.ndarray:
         """float32 (ntotal, dim) rows x^ in id order: centroid of the row's list + codebook entries, one float32 add."""
@@ -123,10 +106,8 @@ def _build_ivfpq(vectors: np.ndarray, dim: int, key: str, metric: str, device, p
 
 def _check_key(dimension: int, key: str, device) -> Tuple[int, int]:
     nlist, m = parse_ivfpq_key(key)
-    if dimension % m or m > min(dimension, 256):
-        raise ValueError(f"PQ{m} needs a dimension that is a multiple of {m} (and M <= 256); got {dimension}")
-    if isinstance(device, list):
-        raise ValueError(_ONE_GPU)
+    check_key_dimension(dimension, m)
+    one_device(device, _ONE_GPU)
     return nlist, m
 
 
@@ -148,16 +129,8 @@ class HipIVFPQIndexer(BaseIndexer):
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
         if vectors.shape[1] != self.dimension:
             raise ValueError(f"Expected dimension {self.dimension}, got {vectors.shape[1]}")
-        data = _ffi.as_f32_c(vectors)
-        meta = {"metric": self.metric, "index_key": self.index_key, "faiss_metric": "l2"}
-        metric = "l2"
-        if self.metric == "cosine":
-            data = _safe_normalize(data)
-            metric = "ip"
-            meta.update({"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True})
-        elif self.metric == "ip":
-            metric = "ip"
-            meta["faiss_metric"] = "ip"
+        data, metric, entries = indexer_operands(vectors, self.metric)
+        meta = {"metric": self.metric, "index_key": self.index_key, **entries}
         device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
         index = _build_ivfpq(data, self.dimension, self.index_key, metric, device, self.params)
         if "nprobe" in self.params:                       # runtime attribute of the index (modular.py:269-275)
@@ -167,7 +140,7 @@ class HipIVFPQIndexer(BaseIndexer):
         return IndexArtifact(kind="hip_ivf", data=index, metadata=meta)
 
 
-class HipIVFPQSearch(BaseAlgorithm):
+class HipIVFPQSearch(RawAlgorithm):
     """ApproximateSearch semantics for `index_type="IVF<nlist>,PQ<M>"`: train -> add -> nprobe from kwargs; raw FAISS
     conventions (no normalisation, no sign flip: 'l2' -> squared L2, anything else -> raw inner product)."""
 
@@ -191,20 +164,6 @@ class HipIVFPQSearch(BaseAlgorithm):
         if "nprobe" in self.config:
             self.index.set_nprobe(int(self.config["nprobe"]))
         reserve_workspace(self.index, self.config)
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        d, i = self.index.search(np.array([query], dtype=np.float32), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        return self.index.search(np.asarray(queries).astype(np.float32), k)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
     # ---- persistence (persist.py: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ------------------------------------
     # An IVF-PQ artifact is the index itself: centroids, codebooks, codes and the list of every row.  No corpus file -- the

@@ -19,10 +19,11 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _ffi
-from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
-from .index import FlatIndex
-from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
-                         register_algorithm, register_indexer, register_searcher)
+from .algorithms import (DEFAULT_RESERVE_QUERIES, FaissStyleSearcher, _resolve_device, _safe_normalize, apply_engine_options,
+                         indexer_operands, query_batch, reserve_workspace, resident_mb, warmup_rows)
+from .index import FlatIndex, _pair
+from .plugin_api import (BaseAlgorithm, BaseIndexer, IndexArtifact, Metadata, SearchResult, register_algorithm, register_indexer,
+                         register_searcher)
 
 MAX_EF = 512            # ef limit of vdb_knng_search (and so of k)
 MAX_DEGREE = 64
@@ -74,14 +75,9 @@ class KnnGraphIndex(FlatIndex):
 
     def knng_search(self, queries: np.ndarray, k: int, ef: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Beam search of width `ef` (default k): flat conventions and padding."""
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
+        q = self._queries(queries)
         ef = int(k) if ef is None else int(ef)
-        D = np.empty((q.shape[0], int(k)), np.float32)
-        I = np.empty((q.shape[0], int(k)), np.int64)
+        D, I = _pair(q.shape[0], int(k))
         _ffi.check(self._lib.vdb_knng_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), ef, _ffi.ptr(D), _ffi.ptr(I)))
         return D, I
 
@@ -102,9 +98,8 @@ def _build_graph_index(data: np.ndarray, dim: int, metric: str, degree: int, nca
 
 def _reserve_search(index: KnnGraphIndex, vectors: np.ndarray, reserve, ef: int) -> None:
     """Size the graph search's workspace now (the harness times its first batch)."""
-    reserve = 10_000 if reserve is None else int(reserve)
-    if reserve > 0 and index.ntotal > 0:
-        n = min(reserve, index.ntotal)
+    n = warmup_rows(index, reserve)
+    if n:
         index.knng_search(np.asarray(vectors[:n], dtype=np.float32), min(10, ef), ef)
 
 
@@ -131,38 +126,25 @@ class HipKnnGraphIndexer(BaseIndexer):
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
         if vectors.shape[1] != self.dimension:
             raise ValueError(f"Expected dimension {self.dimension}, got {vectors.shape[1]}")
-        data = _ffi.as_f32_c(vectors)
-        meta = {"metric": self.metric, "faiss_metric": "l2", "efSearch": self.efSearch, "efConstruction": self.efConstruction,
+        data, metric, entries = indexer_operands(vectors, self.metric)
+        meta = {"metric": self.metric, **entries, "efSearch": self.efSearch, "efConstruction": self.efConstruction,
                 "M": self.M, "degree": self.degree, "ncand": self.ncand, "reserve_queries": self.params.get("reserve_queries")}
-        metric = "l2"
-        if self.metric == "cosine":
-            data = _safe_normalize(data)
-            metric = "ip"
-            meta.update({"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True})
-        elif self.metric == "ip":
-            metric = "ip"
-            meta["faiss_metric"] = "ip"
         index = _build_graph_index(data, self.dimension, metric, self.degree, self.ncand, self.params)
         return IndexArtifact(kind="hip_knng", data=index, metadata=meta)
 
 
-class HipKnnGraphSearcher(BaseSearcher):
+class HipKnnGraphSearcher(FaissStyleSearcher):
     """FaissSearcher semantics over a HipKnnGraphIndexer artifact (as HipIVFSearcher applies them: squared L2 as it is, negated
     scores for cosine / ip).  The beam width is ef = max(efSearch, k); an `efSearch` given here overrides the artifact's."""
 
+    _kind = "hip_knng"
+
     def __init__(self, name: str, dimension: int, metric: str = "l2", **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
-        self.index: Optional[KnnGraphIndex] = None
-        self.normalize_queries = False
         self.efSearch = 100
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
-        if artifact.kind != "hip_knng":
-            raise ValueError("HipKnnGraphSearcher requires 'hip_knng' artifact")
-        self.index = artifact.data
-        meta = artifact.metadata or {}
-        self.metric = meta.get("metric", self.metric)
-        self.normalize_queries = meta.get("normalize_queries", False)
+        meta = self._bind(artifact)
         ef = self.params.get("efSearch")
         if ef is None:
             ef = meta.get("efSearch", 100)
@@ -170,32 +152,13 @@ class HipKnnGraphSearcher(BaseSearcher):
         if self.efSearch < 1 or self.efSearch > MAX_EF:
             raise ValueError(f"efSearch must be in [1, {MAX_EF}], got {self.efSearch}")
         self._prepared = True
-        data = _safe_normalize(_ffi.as_f32_c(vectors[:10_000]).copy()) if self.normalize_queries else vectors
+        data = _safe_normalize(_ffi.as_f32_c(vectors[:DEFAULT_RESERVE_QUERIES]).copy()) if self.normalize_queries else vectors
         _reserve_search(self.index, data, self.params.get("reserve_queries", meta.get("reserve_queries")), self.efSearch)
 
-    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
-        query = np.asarray(query)
-        if query.ndim == 1:
-            query = query.reshape(1, -1)
-        query = query.astype(np.float32, copy=True)
-        return _safe_normalize(query) if self.normalize_queries else query
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        d, i = self.batch_search(self._prepare_query(query), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self._prepared:
-            raise RuntimeError("FaissSearcher not attached to an index")
+    def _search_index(self, queries: np.ndarray, k: int) -> SearchResult:
         if int(k) > MAX_EF:
             raise RuntimeError(f"the k-NN graph search returns at most {MAX_EF} neighbours, got k = {k}")
-        d, i = self.index.knng_search(self._prepare_query(queries), int(k), max(self.efSearch, int(k)))
-        if self.metric in {"cosine", "ip"}:
-            d = -d
-        return d.astype(np.float32), i.astype(np.int64)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+        return self.index.knng_search(queries, int(k), max(self.efSearch, int(k)))
 
 
 class HipKnnGraphSearch(BaseAlgorithm):
@@ -229,13 +192,6 @@ class HipKnnGraphSearch(BaseAlgorithm):
         _reserve_search(self.index, data, self.config.get("reserve_queries"), self.efSearch)
         self.index_built = True
 
-    def _queries(self, queries: np.ndarray) -> np.ndarray:
-        q = np.asarray(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        q = q.astype(np.float32, copy=True)
-        return _safe_normalize(q) if self.metric == "cosine" else q
-
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
         d, i = self.batch_search(query, k)
         return d[0], i[0]
@@ -245,10 +201,10 @@ class HipKnnGraphSearch(BaseAlgorithm):
             raise RuntimeError("Index not built. Call build_index() first.")
         if int(k) > MAX_EF:
             raise RuntimeError(f"the k-NN graph search returns at most {MAX_EF} neighbours, got k = {k}")
-        return self.index.knng_search(self._queries(queries), int(k), max(self.efSearch, int(k)))
+        return self.index.knng_search(query_batch(queries, self.metric == "cosine"), int(k), max(self.efSearch, int(k)))
 
     def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+        return resident_mb(self.index)
 
 
 register_indexer("HipKnnGraphIndexer", HipKnnGraphIndexer)

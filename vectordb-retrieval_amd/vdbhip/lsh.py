@@ -15,10 +15,10 @@ from typing import Any, Optional
 
 import numpy as np
 
-from . import _ffi
-from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
+from .algorithms import (FaissStyleSearcher, _resolve_device, apply_engine_options, euclidean_or_negated, indexer_operands,
+                         reserve_workspace, warmup_rows)
 from .index import FlatIndex
-from .plugin_api import BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult, register_indexer, register_searcher
+from .plugin_api import BaseIndexer, IndexArtifact, Metadata, SearchResult, register_indexer, register_searcher
 
 MAX_CANDIDATES = 65536      # ncand limit of vdb_lsh_candidates / vdb_lsh_search
 
@@ -64,15 +64,14 @@ class HipLSHIndexer(BaseIndexer):
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
         if vectors.shape[1] != self.dimension:
             raise ValueError(f"Expected dimension {self.dimension}, got {vectors.shape[1]}")
-        data = _ffi.as_f32_c(vectors)
+        data, metric, _ = indexer_operands(vectors, self.metric)
         meta = {"metric": self.metric, "num_bits": self.num_bits, "faiss_index_kind": "lsh", "seed": self.seed}
-        if self.metric == "cosine":
-            data = _safe_normalize(data)
+        if self.metric == "cosine":                 # (FaissLSHIndexer's own entries, not the factory indexer's)
             meta["normalize_queries"] = True
         elif self.metric == "ip":
             meta["faiss_metric"] = "ip"
         device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
-        index = FlatIndex(self.dimension, "l2" if self.metric == "l2" else "ip", device)
+        index = FlatIndex(self.dimension, metric, device)
         apply_engine_options(index, self.params)
         index.lsh_set_projection(make_projection(self.dimension, self.num_bits, self.seed))
         index.add(data)
@@ -81,14 +80,14 @@ class HipLSHIndexer(BaseIndexer):
         return IndexArtifact(kind="hip_lsh", data=index, metadata=meta)
 
 
-class HipLSHSearcher(BaseSearcher):
+class HipLSHSearcher(FaissStyleSearcher):
     """FaissSearcher's LSH branch over a HipLSHIndexer artifact: `lsh_rerank` (True), `lsh_candidate_multiplier` (8.0),
     `lsh_max_candidates` (None)."""
 
+    _kind = "hip_lsh"
+
     def __init__(self, name: str, dimension: int, metric: str = "l2", **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
-        self.index: Optional[FlatIndex] = None
-        self.normalize_queries = False
         self._lsh_rerank = bool(self.params.get("lsh_rerank", True))
         self._lsh_candidate_multiplier = float(self.params.get("lsh_candidate_multiplier", 8.0))
         max_candidates = self.params.get("lsh_max_candidates")
@@ -98,36 +97,17 @@ class HipLSHSearcher(BaseSearcher):
         return candidate_count(k, self._lsh_candidate_multiplier, self._lsh_max_candidates, ntotal)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
-        if artifact.kind != "hip_lsh":
-            raise ValueError("HipLSHSearcher requires 'hip_lsh' artifact")
-        self.index = artifact.data
-        meta = artifact.metadata or {}
-        self.metric = meta.get("metric", self.metric)
-        self.normalize_queries = meta.get("normalize_queries", False)
+        meta = self._bind(artifact)
         self._prepared = True
         # size the LSH workspace now, as reserve_workspace does for the flat one (the harness times its first batch)
-        reserve = self.params.get("reserve_queries", meta.get("reserve_queries"))
-        reserve = 10_000 if reserve is None else int(reserve)
-        if reserve > 0 and self.index.ntotal > 0:
-            n = min(reserve, self.index.ntotal)
+        n = warmup_rows(self.index, self.params.get("reserve_queries", meta.get("reserve_queries")))
+        if n:
             c = self.candidate_count(10, self.index.ntotal)
             if 0 < c <= MAX_CANDIDATES:
                 self.index.lsh_search(np.asarray(vectors[:n], dtype=np.float32), 10, c)
 
-    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
-        query = np.asarray(query)
-        if query.ndim == 1:
-            query = query.reshape(1, -1)
-        query = query.astype(np.float32, copy=True)
-        return _safe_normalize(query) if self.normalize_queries else query
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        d, i = self.batch_search(self._prepare_query(query), k)
-        return d[0], i[0]
-
     def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self._prepared:
-            raise RuntimeError("FaissSearcher not attached to an index")
+        self._require_attached()
         q = self._prepare_query(queries)
         ntotal = self.index.ntotal
         if ntotal <= 0:
@@ -140,14 +120,7 @@ class HipLSHSearcher(BaseSearcher):
                 d = -d
             d[ids < 0] = np.inf
             return d, ids
-        d, i = self.index.lsh_search(q, k, candidate_k)
-        pad = i < 0
-        d = np.sqrt(np.where(pad, np.float32(0), d), dtype=np.float32) if self.metric == "l2" else -d
-        d[pad] = np.inf
-        return d.astype(np.float32, copy=False), i
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+        return euclidean_or_negated(*self.index.lsh_search(q, k, candidate_k), self.metric)
 
 
 register_indexer("HipLSHIndexer", HipLSHIndexer)

@@ -17,8 +17,8 @@ from typing import Any, Optional, Tuple
 
 import numpy as np
 
-from . import _ffi
-from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
+from .algorithms import (_resolve_device, apply_engine_options, euclidean_or_negated, indexer_operands, query_batch,
+                         reserve_workspace, resident_mb)
 from .index import FlatIndex
 from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult, register_algorithm,
                          register_indexer, register_searcher)
@@ -47,7 +47,8 @@ def candidate_cap(k: int, multiplier: float, max_candidates: Optional[int]) -> i
 
 
 def _normalize_queries(q: np.ndarray) -> np.ndarray:
-    """Row by row as the reference's _normalize_vector (lsh.py:19-24): the 1-D norm, a zero query stays zero."""
+    """Row by row as the reference's _normalize_vector (lsh.py:19-24): the 1-D norm, a zero query stays zero.  Not
+    algorithms._safe_normalize: the 1-D norm sums in another order, and the two differ in the last bit on one row in five."""
     out = np.zeros_like(q)
     for i, row in enumerate(q):
         norm = np.linalg.norm(row)
@@ -69,12 +70,10 @@ def _check_parameters(what: str, metric: str, num_tables: int, hash_size: int, b
 
 def _build_index(vectors: np.ndarray, dimension: int, metric: str, num_tables: int, hash_size: int, bucket_width: float,
                  seed: int, params: dict) -> FlatIndex:
-    data = _ffi.as_f32_c(vectors)
-    if metric == "cosine":
-        data = _safe_normalize(data)             # (= the reference's _normalize_rows, call for call)
+    data, library_metric, _ = indexer_operands(vectors, metric)    # (cosine: the reference's _normalize_rows, call for call)
     p, b = make_tables(dimension, num_tables, hash_size, metric, bucket_width, seed)
     device = _resolve_device(params.get("device"), params.get("device_ids"))
-    index = FlatIndex(dimension, "l2" if metric == "l2" else "ip", device)
+    index = FlatIndex(dimension, library_metric, device)
     apply_engine_options(index, params)
     index.lsht_set_tables(p, b, bucket_width if b is not None else 0.0)
     index.add(data)
@@ -83,20 +82,15 @@ def _build_index(vectors: np.ndarray, dimension: int, metric: str, num_tables: i
 
 
 def _search(index: FlatIndex, metric: str, queries: np.ndarray, k: int, cap: int, fallback: bool) -> SearchResult:
-    q = np.asarray(queries)
-    if q.ndim == 1:
-        q = q.reshape(1, -1)
-    q = q.astype(np.float32, copy=True)
+    q = query_batch(queries)
     if metric == "cosine":
         q = _normalize_queries(q)
     d, i = index.lsht_search(q, int(k), cap, fallback)
-    pad = i < 0
     if metric == "l2":
-        d = np.sqrt(np.where(pad, np.float32(0), d), dtype=np.float32)
-    else:
-        d = (np.float32(1.0) - d).astype(np.float32)
-    d[pad] = np.inf
-    return d.astype(np.float32, copy=False), i
+        return euclidean_or_negated(d, i, metric)
+    d = (np.float32(1.0) - d).astype(np.float32)         # the reference's cosine distance
+    d[i < 0] = np.inf
+    return d, i
 
 
 class HipLSHTableIndexer(BaseIndexer):
@@ -157,7 +151,7 @@ class HipLSHTableSearcher(BaseSearcher):
         return _search(self.index, self.metric, queries, k, cap, bool(self.fallback_to_bruteforce))
 
     def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+        return resident_mb(self.index)
 
 
 class HipLSHTables(BaseAlgorithm):
@@ -196,7 +190,7 @@ class HipLSHTables(BaseAlgorithm):
         return _search(self.index, self.metric, queries, k, cap, bool(self.fallback_to_bruteforce))
 
     def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
+        return resident_mb(self.index)
 
 
 register_indexer("HipLSHTableIndexer", HipLSHTableIndexer)

@@ -14,17 +14,18 @@ from __future__ import annotations
 
 import ctypes
 import re
-from typing import Any, Optional, Tuple
+from typing import Any, Optional
 
 import numpy as np
 
 from . import _ffi, persist
-from .index import _Handle, normalize_devices
-from .algorithms import _resolve_device, _safe_normalize, apply_engine_options, reserve_workspace
-from .plugin_api import (BaseAlgorithm, BaseIndexer, BaseSearcher, IndexArtifact, Metadata, SearchResult,
-                         register_algorithm, register_indexer, register_searcher)
+from .index import _FlatSearch, metric_code, one_device
+from .algorithms import (FaissStyleSearcher, RawAlgorithm, _resolve_device, apply_engine_options, indexer_operands,
+                         reserve_workspace)
+from .plugin_api import BaseIndexer, IndexArtifact, Metadata, register_algorithm, register_indexer, register_searcher
 
 _PQ_KEY = re.compile(r"^\s*PQ(\d+)(?:x8)?\s*$")
+_ONE_GPU = "PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available"
 
 
 def parse_pq_key(key: str) -> int:
@@ -38,6 +39,12 @@ def parse_pq_key(key: str) -> int:
 def check_m(dim: int, M: int) -> None:
     if M < 1 or M > min(dim, 256) or dim % M:
         raise ValueError(f"M must divide dim and lie in [1, min(dim, 256)]; got dim={dim}, M={M}")
+
+
+def check_key_dimension(dimension: int, m: int) -> None:
+    """A plugin's constructor-time refusal of a "PQ<m>" codec the dimension does not admit (as a bad factory string fails)."""
+    if dimension % m or m > min(dimension, 256):
+        raise ValueError(f"PQ{m} needs a dimension that is a multiple of {m} (and M <= 256); got {dimension}")
 
 
 class PQCodec:
@@ -76,34 +83,26 @@ class PQCodec:
         return np.ascontiguousarray(np.concatenate([cb[m][codes[:, m]] for m in range(self.M)], axis=1), dtype=np.float32)
 
 
-class PQIndex(PQCodec, _Handle):
+class PQIndex(PQCodec, _FlatSearch):
     """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only.  `adc_max_batch`: option
     "pq_adc_max_batch" -- query batches up to that size (at most 512; 0 = off) take the lookup-table (ADC) scan of the codes."""
 
     def __init__(self, dim: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0):
-        if metric not in ("l2", "ip"):
-            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
-        device = normalize_devices(device)
-        if isinstance(device, list):
-            raise ValueError("PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available")
+        code = metric_code(metric)
+        device = one_device(device, _ONE_GPU)
         dim, M = int(dim), int(M)
         check_m(dim, M)
         self.dim, self.M, self.dsub, self.metric, self.device = dim, M, dim // M, metric, device
-        super().__init__(self.dim, 0 if metric == "l2" else 1, self.device)
+        super().__init__(self.dim, code, self.device)
         self.is_trained = False
         self.ntotal = 0
         self.adc_max_batch = int(adc_max_batch or 0)
         if self.adc_max_batch:
             self.set_option("pq_adc_max_batch", float(self.adc_max_batch))
 
-    def _sync_ntotal(self) -> None:
-        self.ntotal = int(self.stats()["ntotal"])
-
     # -- codebooks ----------------------------------------------------------------------------------------
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
-        x = _ffi.as_f32_c(x)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        x = self._rows(x)
         _ffi.check(self._lib.vdb_pq_train(self._handle(), self.M, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                           int(max_points_per_centroid)), build_time=True)
         self.is_trained = True
@@ -115,9 +114,7 @@ class PQIndex(PQCodec, _Handle):
     # -- rows -----------------------------------------------------------------------------------------------
     def add(self, x: np.ndarray, id_base: int = 0) -> None:
         """Encode and append rows (faiss.Index.add; same `id_base` on every add of one index, `reset()` empties it)."""
-        x = _ffi.as_f32_c(x)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected (n, {self.dim}) vectors, got {x.shape}")
+        x = self._rows(x)
         try:
             _ffi.check(self._lib.vdb_pq_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
         finally:
@@ -125,9 +122,7 @@ class PQIndex(PQCodec, _Handle):
 
     def add_codes(self, codes: np.ndarray, id_base: int = 0) -> None:
         """Append rows given as codes, uint8 (n, M): what loading a persisted index does."""
-        c = np.ascontiguousarray(codes, dtype=np.uint8)
-        if c.ndim != 2 or c.shape[1] != self.M:
-            raise ValueError(f"expected (n, {self.M}) codes, got {c.shape}")
+        c = self._codes(codes)
         try:
             _ffi.check(self._lib.vdb_pq_add_codes(self._handle(), _ffi.ptr(c), c.shape[0], int(id_base)), build_time=True)
         finally:
@@ -137,38 +132,10 @@ class PQIndex(PQCodec, _Handle):
         """float32 (n, dim) rows x^ of `codes` (default: every indexed row): codebook[m][code[m]] side by side, a lookup."""
         return self.lookup(self.codes() if codes is None else np.asarray(codes, dtype=np.uint8))
 
-    def reset(self) -> None:
-        """Drop every row; the codebooks stay (faiss.IndexPQ.reset)."""
-        _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
-        self.ntotal = 0
-
-    # -- search ---------------------------------------------------------------------------------------------
-    def search(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise RuntimeError(f"expected (nq, {self.dim}) queries, got {q.shape}")
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_search(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
-        return D, I
-
-    def search_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
-        """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
-        _ffi.check(self._lib.vdb_search_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
-
-    def search_partial_device(self, q_ptr: int, nq: int, k: int, keys_ptr: int, ids_ptr: int, stream: int = 0) -> None:
-        """Partial top-k (float64 order keys + ids, device pointers), as FlatIndex.search_partial_device."""
-        _ffi.check(self._lib.vdb_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr, stream or None))
-
-    def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-        q = _ffi.as_f32_c(queries)
-        c = np.ascontiguousarray(candidate_ids, dtype=np.int64)
-        D = np.empty((q.shape[0], k), np.float32)
-        I = np.empty((q.shape[0], k), np.int64)
-        _ffi.check(self._lib.vdb_rerank(self._handle(), _ffi.ptr(q), q.shape[0], _ffi.ptr(c), c.shape[1], int(k), _ffi.ptr(D), _ffi.ptr(I)))
-        return D, I
+    def debug_adc_scores(self, queries: np.ndarray, row0: int, nrows: int):
+        """(scores (nq, nrows), eps (nq), cs) of the lookup-table (ADC) scan: raw, unpacked scores, as FlatIndex.debug_scan_scores.
+        Indexes with rows only."""
+        return self._debug_scores(self._lib.vdb_debug_pq_adc_scores, queries, nrows, int(row0), int(nrows))
 
 
 def _build_pq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> PQIndex:
@@ -190,75 +157,38 @@ class HipPQIndexer(BaseIndexer):
         params.setdefault("index_type", key)
         super().__init__(name, dimension, metric, **params)
         self.index_key = self.index_type = key
-        m = parse_pq_key(key)
-        if dimension % m or m > min(dimension, 256):
-            raise ValueError(f"PQ{m} needs a dimension that is a multiple of {m} (and M <= 256); got {dimension}")
+        check_key_dimension(dimension, parse_pq_key(key))
 
     def build(self, vectors: np.ndarray, metadata: Metadata = None) -> IndexArtifact:
         if vectors.shape[1] != self.dimension:
             raise ValueError(f"Expected dimension {self.dimension}, got {vectors.shape[1]}")
-        data = _ffi.as_f32_c(vectors)
-        meta = {"metric": self.metric, "index_key": self.index_key, "faiss_metric": "l2"}
-        metric = "l2"
-        if self.metric == "cosine":
-            data = _safe_normalize(data)
-            metric = "ip"
-            meta.update({"faiss_metric": "ip", "normalize_queries": True, "normalize_vectors": True})
-        elif self.metric == "ip":
-            metric = "ip"
-            meta["faiss_metric"] = "ip"
+        data, metric, entries = indexer_operands(vectors, self.metric)
+        meta = {"metric": self.metric, "index_key": self.index_key, **entries}
         device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
         index = _build_pq(data, self.dimension, self.index_key, metric, device, self.params)
         reserve_workspace(index, self.params)
         return IndexArtifact(kind="hip_pq", data=index, metadata=meta)
 
 
-class HipPQSearcher(BaseSearcher):
+class HipPQSearcher(FaissStyleSearcher):
     """FaissSearcher semantics over a HipPQIndexer artifact (distances negated for cosine / ip, as HipIVFSearcher).
     `adc_max_batch` (a config entry `adc_max_batch: 16`): option "pq_adc_max_batch" of the attached index."""
 
+    _kind = "hip_pq"
+
     def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
-        self.index: Optional[PQIndex] = None
-        self.normalize_queries = False
         self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
-        if artifact.kind != "hip_pq":
-            raise ValueError("HipPQSearcher requires 'hip_pq' artifact")
-        self.index = artifact.data
+        self._bind(artifact)
         if self.adc_max_batch is not None:
             self.index.set_option("pq_adc_max_batch", float(self.adc_max_batch))
             self.index.adc_max_batch = self.adc_max_batch
-        meta = artifact.metadata or {}
-        self.metric = meta.get("metric", self.metric)
-        self.normalize_queries = meta.get("normalize_queries", False)
         self._prepared = True
 
-    def _prepare_query(self, query: np.ndarray) -> np.ndarray:
-        query = np.asarray(query)
-        if query.ndim == 1:
-            query = query.reshape(1, -1)
-        query = query.astype(np.float32, copy=True)
-        return _safe_normalize(query) if self.normalize_queries else query
 
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        d, i = self.batch_search(self._prepare_query(query), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self._prepared:
-            raise RuntimeError("FaissSearcher not attached to an index")
-        d, i = self.index.search(self._prepare_query(queries), k)
-        if self.metric in {"cosine", "ip"}:
-            d = -d
-        return d.astype(np.float32), i.astype(np.int64)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
-
-
-class HipPQSearch(BaseAlgorithm):
+class HipPQSearch(RawAlgorithm):
     """ApproximateSearch semantics for `index_type="PQ<M>"`: train -> add; raw FAISS conventions (no normalisation, no sign
     flip: 'l2' -> squared L2, anything else -> raw inner product)."""
 
@@ -272,11 +202,8 @@ class HipPQSearch(BaseAlgorithm):
         self.metric = "l2" if metric == "l2" else "ip"
         self.device = _resolve_device(device, kwargs.get("device_ids"))
         self.index: Optional[PQIndex] = None
-        m = parse_pq_key(index_type)                          # fail at construction, like a bad factory string
-        if dimension % m or m > min(dimension, 256):
-            raise ValueError(f"PQ{m} needs a dimension that is a multiple of {m} (and M <= 256); got {dimension}")
-        if isinstance(self.device, list):
-            raise ValueError("PQ<M> runs on one GPU: a multi-device index (more than one device id) is not available")
+        check_key_dimension(dimension, parse_pq_key(index_type))       # fail at construction, like a bad factory string
+        one_device(self.device, _ONE_GPU)
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         data = np.asarray(vectors).astype(np.float32)
@@ -284,20 +211,6 @@ class HipPQSearch(BaseAlgorithm):
                                {**self.config, "adc_max_batch": self.adc_max_batch})
         self.index_built = True
         reserve_workspace(self.index, self.config)
-
-    def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        d, i = self.index.search(np.array([query], dtype=np.float32), k)
-        return d[0], i[0]
-
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
-        if not self.index_built:
-            raise RuntimeError("Index has not been built yet.")
-        return self.index.search(np.asarray(queries).astype(np.float32), k)
-
-    def get_memory_usage(self) -> float:
-        return self.index.stats()["bytes_resident"] / (1024.0 * 1024.0) if self.index else 0.0
 
     # ---- persistence (persist.py: temp dir + manifest + WRITE_COMPLETE last + atomic rename) ------------------------------------
     # A PQ artifact is the index itself: codebooks, codes and id_base.  No corpus file -- the index holds no float32 rows.

@@ -199,10 +199,7 @@ class HipShardedExactSearch(BaseAlgorithm):
     def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
         if not self.index_built:
             raise RuntimeError("Index has not been built yet.")
-        q = _ffi.as_f32_c(queries)
-        if q.ndim == 1:
-            q = q.reshape(1, -1)
-        pack = self.engine.search_partial(self.engine.to_device(q), int(k))
+        pack = self.engine.search_partial(self.engine.to_device(_ffi.as_f32_queries(queries)), int(k))
         return self.engine.merge(all_gather_partials(pack, self.world))
 
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
