@@ -57,7 +57,8 @@ enum vdb_status {
 /* which search path served the last call (vdb_stats_t.last_path) */
 enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6,
                 VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */,
-                VDB_PATH_IVFPQ_ADC = 8 /* IVF-PQ: lookup-table (ADC) scan of the probed lists, then the exact re-score of the rows near the k-th score */ };
+                VDB_PATH_IVFPQ_ADC = 8 /* IVF-PQ: lookup-table (ADC) scan of the probed lists, then the exact re-score of the rows near the k-th score */,
+                VDB_PATH_RANGE = 9 /* vdb_range_search: bitmap prefilter (fp16 MFMA scan, or all rows), exact filter, emit in id order */ };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -114,6 +115,7 @@ typedef struct vdb_stats_s {
  *     / get_tables / vdb_knng_get calls (M, nbits, T,
  *     degree 0 elsewhere)                                +     +    +     +    +      +         +        +       +
  *   vdb_rerank(_device)                                  +     +    +     +    +      +         +        S       +
+ *   vdb_range_search(_device), vdb_range_results(_device) +    +    +     +    U      U         U        U       U
  *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
  *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
  *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
@@ -139,7 +141,7 @@ typedef struct vdb_stats_s {
  * "Either order": vdb_set_option refuses the value on a handle of the kind, and the call that makes a handle that kind
  * (vdb_lsh_set_projection, vdb_lsht_set_tables, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
  * which the option holds the value; LSH, LSHT and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
- * LSH, hash-table LSH and k-NN graph search calls are refused while option "graph" is 1. */
+ * LSH, hash-table LSH, k-NN graph and range search calls are refused while option "graph" is 1. */
 
 /* ---- library ---------------------------------------------------------------------------- */
 int vdb_abi_version(void);
@@ -192,6 +194,37 @@ int vdb_search(vdb_handle h, const float *q_host, int64_t nq, int k, float *D, i
  * `stream` (a hipStream_t, NULL = default stream) and NOT synchronised. */
 int vdb_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev,
                       void *stream);
+
+/* ---- range search -- replaces faiss.IndexFlat.range_search: EVERY row within `radius` of each query, exactly ---------------
+ * The result is defined by what vdb_search returns: of the rows vdb_search with k = ntotal would return for query q, those whose
+ * returned distance D satisfies
+ *   L2: D < radius  (D = (float)key, key = the canonical float64 squared distance)     IP: D > radius  (D = (float)(-key), the raw score)
+ * with ids = id_base + row, in ASCENDING ID (FAISS leaves the order open; this one needs no sort and two runs return the same
+ * bytes).  A NaN key passes neither comparison and is never returned; a key of +inf is never returned under L2; under IP a score of
+ * +inf is returned with D = +inf.  radius: +-inf is legal, NaN is VDB_ERR_INVALID, an L2 radius <= 0 returns nothing.
+ * lims (nq + 1 int64): query q owns entries [lims[q], lims[q + 1]) of D (float32) and I (int64), which the handle keeps on the
+ * device until the next range search, vdb_add, vdb_reset or vdb_set_option; they count in bytes_resident / bytes_workspace and are
+ * freed by vdb_reset and vdb_destroy.  vdb_range_results(_device) copies the result of the LAST range search of the handle out.
+ * How: a handle with resident fp16 panels in layout "x16" (D <= 128, above 15 360 rows) or p16 (D > 128, above 2048
+ * rows) runs an MFMA scan that sets a bit per (query, row) whose scan score lies within the proven bound of the radius -- a superset
+ * of the answer; every other handle (32x32 layout, "int8_only", "stream_panels", a non-finite corpus) and every query whose
+ * threshold or scales are not finite takes all rows.  Set bits are then re-scored in the canonical arithmetic, filtered, counted
+ * and written in bit order.  The batch runs in query slabs whose bitmap fits option "range_bitmap_mb"; every slab synchronises
+ * the stream once (its result count sizes the result buffers).
+ * VDB_ERR_STATE: an empty index; vdb_range_results(_device) without a result on the handle.  VDB_ERR_INVALID: nq <= 0, a null pointer,
+ * a NaN radius.  VDB_ERR_UNSUPPORTED: the kinds of the table above, and any handle while option "graph" is 1.  A failed allocation
+ * is VDB_ERR_NOMEM: the handle keeps its rows and loses only the result.
+ * vdb_stats after a call: last_path = VDB_PATH_RANGE, last_nq, last_candidates = (query, row) pairs scored exactly,
+ * last_fallback_queries = queries for which every row was a candidate, scan_dtype = 0; with option "timing", last_prep_ms = query
+ * statistics, bound and threshold, last_scan_ms = the prefilter (several slabs: from the first scan's start to the last one's end),
+ * last_tail_ms = exact filter + emit. */
+int vdb_range_search(vdb_handle h, const float *q_host, int64_t nq, float radius, int64_t *lims_host);
+/* D float32 (lims[nq]), I int64 (lims[nq]), caller-allocated; may be NULL when lims[nq] == 0 */
+int vdb_range_results(vdb_handle h, float *D_host, int64_t *I_host);
+/* device pointers on the handle's GPU, work on `stream`; the stream is synchronised (once per slab), *total_host = lims[nq] */
+int vdb_range_search_device(vdb_handle h, const float *q_dev, int64_t nq, float radius, int64_t *lims_dev, int64_t *total_host, void *stream);
+/* enqueued on `stream`, NOT synchronised */
+int vdb_range_results_device(vdb_handle h, float *D_dev, int64_t *I_dev, void *stream);
 
 /* ---- row-sharded search (one process per GPU; partials exchanged with an RCCL all-gather) ---- */
 /* per-shard partial top-k: float64 order keys (L2: squared distance, IP: -score) and global ids,
@@ -581,6 +614,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       within 20 KiB of LDS -- 8 waves per CU) .. 14; a filter that does not fit a workgroup's 64 KiB is made
  *                       smaller.  1 is legal; no value changes a result
  *     "knng_build_block"  k-NN graph: rows per self-search block of vdb_knng_build, 0 (default: 65 536) .. 1e9
+ *     "range_bitmap_mb" range search: MiB of candidate bitmap (one bit per query and row) a query slab may take, 0 (default: 256)
+ *                       .. 4096; a batch whose bitmap is larger runs in several slabs (same results; at least one query per slab)
  *     "multi_stage_all" multi-device handles only (vdb_create_multi; every other option is forwarded to each shard, and "graph"
  *                       = 1 is VDB_ERR_UNSUPPORTED there): 1 (tests) shards on devices[0] take the remote-shard path too
  *     "graph_recapture_at_once"  diagnostic, 0 (default) | 1: the pre-round-3 ordering, for re-checking that defect

@@ -36,6 +36,7 @@
 #include "pq_adc.hpp"
 #include "ivf_pq_adc.hpp"
 #include "knng.hpp"
+#include "range.hpp"
 
 using namespace vdb;
 
@@ -243,6 +244,14 @@ struct Workspace {
     DevBuf adc_aux{"ws.adc_aux"};           // ... its scale, flags, B [nq][nprobe] and score positions [nq][nprobe + 1]
 };
 
+// the last range search of the handle (range.inc): its result -- lims, D, I -- and the workspace of the call, the candidate bitmap of one
+// query slab first of all                                                                      (freed by vdb_reset and with the handle)
+struct RangeBufs {
+    DevBuf lims{"range.lims"}, D{"range.D"}, I{"range.I"};
+    DevBuf bitmap{"range.bitmap"}, seg{"range.seg"}, qtot{"range.qtot"}, stat{"range.stat"};
+    DevBuf qstage{"range.qstage"}, qpad{"range.qpad"}, qpanels{"range.qpanels"}, info{"range.info"}, eps{"range.eps"}, thr{"range.thr"}, flag{"range.flag"};
+};
+
 // (struct Options -- everything vdb_set_option writes -- is in scan_plan.hpp: the launch rules of the flat scans read it)
 
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
@@ -280,6 +289,7 @@ struct vdb_index_s {
     LshWorkspace lsh_ws;
     KnngWorkspace knng_ws;
     Workspace ws;
+    RangeBufs range;
     Options opt;                             // what vdb_set_option has set; every other member is the library's own state
     int rows8_pitch = 0;
     bool i8_ok = false;
@@ -362,6 +372,10 @@ struct vdb_index_s {
     // k-NN graph of a flat index (knng.inc; vdb_knng_build / vdb_knng_set): ntotal x degree local row numbers next to the float32 rows
     int knng_degree = 0;                     // 0 = no graph (any add and vdb_reset drop it)
     std::vector<int32_t> knng_entries;       // the entry rows knng_ws.knng_entry holds (knng_search_impl)
+    // the last range search (range.inc): `range` holds its result while range_valid (any add, vdb_reset and vdb_set_option drop it)
+    bool range_valid = false;
+    int64_t range_total = 0, range_nq = 0;   // lims[nq] and nq of that result
+    int64_t range_cand = 0, range_fb = 0;    // (query, row) pairs scored exactly / queries for which every row was a candidate
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -452,6 +466,7 @@ constexpr OptionRow kOptions[] = {
     {"knng_max_iters", &Options::knng_max_iters, 0, {0, 2147483647}},   // k-NN graph: step cap of a search (0 = default 8 ef)
     {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
     {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
+    {"range_bitmap_mb", &Options::range_bitmap_mb, 0, {0, 4096}},    // range search: MiB of candidate bitmap per query slab (0 = default 256)
     {"i8_variant", &Options::i8_variant, 0, {0, 7}},
     {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
     {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
@@ -494,7 +509,7 @@ void refuse_options_set(const vdb_index_s *h, const char *what, unsigned kind) {
 }
 
 template <class F>
-void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); }
+void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); f(h->range); }
 
 // every byte of device memory the handle holds (its ws.small may be a view into plan.ivf_zero: not counted twice)
 size_t handle_bytes(vdb_index_s *h) {
@@ -1056,6 +1071,7 @@ void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, 
     if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
     set_device(h->device);
+    h->range_valid = false;                    // (the last range result described the rows as they were)
     if (knng_on(h)) {                          // (the graph describes the rows as they were)
         VDB_HIP(hipDeviceSynchronize());
         knng_drop(h);
@@ -1175,6 +1191,8 @@ int vdb_reset(vdb_handle hh) {
         group_release(h->scan);
         group_release(h->lists);
         group_release(h->codes);
+        group_release(h->range);
+        h->range_valid = false;
         h->lsh_rows = 0;                       // (the projection stays)
         h->lsht_rows = 0;                      // (the hash tables stay)
         h->knng_degree = 0;                    // (the graph went with the codes group)
@@ -1332,7 +1350,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
         s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
-        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
+        s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + group_bytes(h->range) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
         s.last_rows_scanned = 0;
@@ -1399,6 +1417,10 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
                 s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride + 1];
             }
         }
+        if (h->last.last_path == VDB_PATH_RANGE) {     // (the call read its counters back when it sized the result)
+            s.last_candidates = h->range_cand;
+            s.last_fallback_queries = h->range_fb;
+        }
         if (h->ev_used > 0) {  // averages over every search recorded since timing was switched on
             double scan = 0.0, total = 0.0, prep = 0.0, tail = 0.0;
             for (size_t i = 0; i < h->ev_used; ++i) {
@@ -1430,6 +1452,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (h->multi) return multi_set_option(h, key, value);
         const std::string k(key);
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
+        h->range_valid = false;                // (... and the last range result goes with any option change)
         const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
         if (r == std::end(kOptions)) throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
         // what this kind of index refuses comes first, whatever the value is otherwise
@@ -1456,5 +1479,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 #include "lsh.inc"
 #include "lsh_tables.inc"
 #include "knng.inc"
+#include "range.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

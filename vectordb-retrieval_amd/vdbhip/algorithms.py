@@ -217,6 +217,19 @@ class HipExactSearch(RawAlgorithm):
         self.record_operation("ndis", float(q.shape[0]) * float(self.index.ntotal))
         return self.index.search(q, k)
 
+    def range_search(self, queries: np.ndarray, radius: float, sort: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss.IndexFlat.range_search in the raw conventions: (lims, D, I) of the rows with squared L2 < radius / inner
+        product > radius.  Per query the rows come in ascending id; `sort=True` orders them nearest first, by (D, id)."""
+        self._require_built()
+        q = _ffi.as_f32_queries(queries)
+        self.record_operation("ndis", float(q.shape[0]) * float(self.index.ntotal))
+        lims, d, i = self.index.range_search(q, radius)
+        if sort and len(i):
+            owner = np.repeat(np.arange(len(lims) - 1), np.diff(lims))
+            order = np.lexsort((i, d if self.metric == "l2" else -d, owner))
+            d, i = d[order], i[order]
+        return lims, d, i
+
 
 def _flat_index(store: np.ndarray, dimension: int, metric: str, params: dict) -> FlatIndex:
     """The flat index of the brute-force pair: options, rows (normalised for cosine), workspace."""
@@ -277,6 +290,21 @@ class HipLinearSearcher(BaseSearcher):
             raise RuntimeError("LinearSearcher cannot operate on empty index")
         d, i = self._index.search(query_batch(queries, self.metric == "cosine"), k)
         return euclidean_or_negated(d, i, self.metric)
+
+    def range_search(self, queries: np.ndarray, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lims, distances, ids) in this searcher's conventions, ascending id per query.  'l2': the rows at Euclidean
+        distance below `radius` (the library is asked for squared distances below float32(radius) * float32(radius)) with
+        their Euclidean distances; 'cosine' / 'ip': `radius` is a similarity threshold -- the rows whose score (queries
+        normalised for cosine) exceeds it, with the negated scores `batch_search` returns."""
+        if not self._prepared:
+            raise RuntimeError("LinearSearcher not attached to an index")
+        if self.metric not in ("l2", "cosine", "ip"):
+            raise ValueError(f"Unsupported metric '{self.metric}' for LinearSearcher")
+        if self._ntotal == 0:
+            raise RuntimeError("LinearSearcher cannot operate on empty index")
+        r = np.float32(radius)
+        lims, d, i = self._index.range_search(query_batch(queries, self.metric == "cosine"), r * r if self.metric == "l2" else r)
+        return (lims,) + euclidean_or_negated(d, i, self.metric)
 
     def get_memory_usage(self) -> float:
         return resident_mb(getattr(self, "_index", None))

@@ -140,6 +140,29 @@ class _FlatSearch(_Handle):
         _ffi.check(self._lib.vdb_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
                                                        stream or None))
 
+    # -- range search (vdb_range_*): every row within a radius, ascending id per query ---------------------------
+    def range_search(self, queries: np.ndarray, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lims int64 (nq + 1,), D float32, I int64): query q owns entries [lims[q], lims[q + 1]) -- the rows with squared
+        L2 distance < radius / inner product > radius (faiss.IndexFlat.range_search), exact, in ascending id."""
+        q = self._queries(queries)
+        lims = np.empty((q.shape[0] + 1,), np.int64)
+        _ffi.check(self._lib.vdb_range_search(self._handle(), _ffi.ptr(q), q.shape[0], float(np.float32(radius)), _ffi.ptr(lims)))
+        D, I = np.empty((int(lims[-1]),), np.float32), np.empty((int(lims[-1]),), np.int64)
+        _ffi.check(self._lib.vdb_range_results(self._handle(), _ffi.ptr(D), _ffi.ptr(I)))
+        return lims, D, I
+
+    def range_search_device(self, q_ptr: int, nq: int, radius: float, lims_ptr: int, stream: int = 0) -> int:
+        """Device pointers on this index's GPU; waits for `stream` (the result size must reach the host) and returns
+        lims[nq], the number of entries `range_results_device` will write."""
+        total = ctypes.c_int64(0)
+        _ffi.check(self._lib.vdb_range_search_device(self._handle(), q_ptr, int(nq), float(np.float32(radius)), lims_ptr,
+                                                     ctypes.byref(total), stream or None))
+        return int(total.value)
+
+    def range_results_device(self, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """The (D, I) of the last range search of this index into device memory; asynchronous on `stream`."""
+        _ffi.check(self._lib.vdb_range_results_device(self._handle(), d_ptr, i_ptr, stream or None))
+
     def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
         """Exact top-k among explicit candidate ids per query (nq, ncand) int64, -1 = empty slot."""
         q = _ffi.as_f32_queries(queries)
