@@ -58,7 +58,8 @@ enum vdb_status {
 enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN = 2, VDB_PATH_IVF = 3, VDB_PATH_LSH = 4, VDB_PATH_KNNG = 5, VDB_PATH_LSHT = 6,
                 VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */,
                 VDB_PATH_IVFPQ_ADC = 8 /* IVF-PQ: lookup-table (ADC) scan of the probed lists, then the exact re-score of the rows near the k-th score */,
-                VDB_PATH_RANGE = 9 /* vdb_range_search: bitmap prefilter (fp16 MFMA scan, or all rows), exact filter, emit in id order */ };
+                VDB_PATH_RANGE = 9 /* vdb_range_search: bitmap prefilter (fp16 MFMA scan, or all rows), exact filter, emit in id order */,
+                VDB_PATH_FILTER_ROWS = 10 /* vdb_search_filtered, selective filter: exact top-k over the list of admitted rows alone */ };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -116,6 +117,9 @@ typedef struct vdb_stats_s {
  *     degree 0 elsewhere)                                +     +    +     +    +      +         +        +       +
  *   vdb_rerank(_device)                                  +     +    +     +    +      +         +        S       +
  *   vdb_range_search(_device), vdb_range_results(_device) +    +    +     +    U      U         U        U       U
+ *   vdb_filter_set(_device), vdb_filter_count,
+ *     vdb_search_filtered(_device)                       +     +    +     +    U      U         U        U       U
+ *   vdb_filter_clear                                     +     +    +     +    +      +         +        +       U
  *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
  *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
  *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
@@ -141,7 +145,7 @@ typedef struct vdb_stats_s {
  * "Either order": vdb_set_option refuses the value on a handle of the kind, and the call that makes a handle that kind
  * (vdb_lsh_set_projection, vdb_lsht_set_tables, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
  * which the option holds the value; LSH, LSHT and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
- * LSH, hash-table LSH, k-NN graph and range search calls are refused while option "graph" is 1. */
+ * LSH, hash-table LSH, k-NN graph, range search and filter calls (but vdb_filter_clear) are refused while option "graph" is 1. */
 
 /* ---- library ---------------------------------------------------------------------------- */
 int vdb_abi_version(void);
@@ -225,6 +229,43 @@ int vdb_range_results(vdb_handle h, float *D_host, int64_t *I_host);
 int vdb_range_search_device(vdb_handle h, const float *q_dev, int64_t nq, float radius, int64_t *lims_dev, int64_t *total_host, void *stream);
 /* enqueued on `stream`, NOT synchronised */
 int vdb_range_results_device(vdb_handle h, float *D_dev, int64_t *I_dev, void *stream);
+
+/* ---- filtered k-NN search -- replaces IndexFlat.search(.., params=SearchParameters(sel=IDSelectorBitmap)): the k nearest rows AMONG
+ * the rows an allow bitmap admits, exactly ---------------------------------------------------------------------------------------
+ * The filter: bit r % 32 of word r / 32 admits row r (rows in insertion order, so its id is id_base + r) -- the bitmap layout of the
+ * range search.  nbits must equal ntotal (VDB_ERR_INVALID otherwise); bits at positions >= nbits of the last word are ignored,
+ * whatever they hold.  vdb_filter_set reads (nbits + 31) / 32 words.
+ * The result is defined by what vdb_search returns: per query, exactly the rows vdb_search with k = ntotal would return, restricted
+ * to the admitted rows and cut to the first k -- the same keys, distances, tie order by (key, id), and the same -1 / +-FLT_MAX padding
+ * when fewer than k rows are admitted.  An all-ones filter returns vdb_search's bytes, an all-zero filter all padding.
+ * The filter is state of the handle: its own copy of the words, masked copies of the scans' accumulator inits (4 bytes per padded row,
+ * 8 more on a handle with an int8 copy), the admitted count, and -- when fewer rows are admitted than max(4160, option
+ * "filter_sparse_pairs") -- their ascending list (4 bytes each, + 4 per 2048 rows).  It counts in bytes_resident and is freed by
+ * vdb_filter_clear, vdb_reset and vdb_destroy.  vdb_add(_device), vdb_reset, vdb_set_option and any call that changes the kind of the
+ * handle DROP the filter: vdb_search_filtered then fails with VDB_ERR_STATE and a message naming the missing filter -- it never answers
+ * unfiltered.  vdb_search and every other call never look at the filter: their results are the same with or without one.
+ * An install runs on its stream and synchronises it once (the admitted count comes back); the searches synchronise nothing.  The
+ * caller orders an install behind filtered searches still running on other streams.
+ * How: every MFMA scan reads an accumulator init of 0.9e38 or more as the marker of a padding row and never selects it,
+ * so a filtered search is the unfiltered one run on the masked copies, with the allow bit tested wherever an exact stage decides
+ * that a row is valid (candidate groups are 4 or 8 consecutive rows, the exhaustive fallback walks all of them).  A selective filter
+ * takes the sparse route instead (last_path = VDB_PATH_FILTER_ROWS): when n_allowed < 2 k + 64 (the select could not find k live
+ * bins) or nq * n_allowed < option "filter_sparse_pairs", the listed rows alone are scored, query-blocked, and merged.  Option
+ * "force_path" keeps its meaning: 1 the exact kernels, 2 the scan, both masked.
+ * VDB_ERR_STATE: an empty index; a search or vdb_filter_count without a filter.  VDB_ERR_INVALID: nq <= 0, k outside [1, 2048], a null
+ * pointer, nbits != ntotal.  VDB_ERR_UNSUPPORTED: the kinds of the table above, and any handle while option "graph" is 1.  A failed
+ * allocation is VDB_ERR_NOMEM: the handle keeps its rows and loses only the filter.
+ * vdb_stats after a filtered search: last_path = VDB_PATH_MFMA_SCAN (the scan and the dense small-corpus path) or
+ * VDB_PATH_EXACT_SCAN as for vdb_search, with last_candidates / last_rescan_bins / last_fallback_queries meaning what they do there;
+ * VDB_PATH_FILTER_ROWS on the sparse route, where last_candidates = nq * n_allowed. */
+int vdb_filter_set(vdb_handle h, const uint32_t *words_host, int64_t nbits);
+/* words in device memory of the handle's GPU; the install runs on `stream`, which is synchronised once */
+int vdb_filter_set_device(vdb_handle h, const uint32_t *words_dev, int64_t nbits, void *stream);
+int vdb_filter_clear(vdb_handle h);
+int vdb_filter_count(vdb_handle h, int64_t *n_allowed);          /* rows the installed filter admits */
+int vdb_search_filtered(vdb_handle h, const float *q_host, int64_t nq, int k, float *D, int64_t *I);
+/* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
+int vdb_search_filtered_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev, void *stream);
 
 /* ---- row-sharded search (one process per GPU; partials exchanged with an RCCL all-gather) ---- */
 /* per-shard partial top-k: float64 order keys (L2: squared distance, IP: -score) and global ids,
@@ -573,7 +614,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       scratch slab and scans that (same results; 1.8x -> ~1.15x the corpus bytes resident for a corpus that
  *                       is not exact in fp16, one extra pass over the rows per query batch)
  *     "stream_slab_rows" rows of that scratch slab (0 = default 1 280 000, rounded down to whole scan chunks whose
- *                       workgroups fill whole rounds of the chip)
+ *                       workgroups fill whole rounds of the chip); inf is legal and, like any value of 9e18 or more given to this
+ *                       option or to "filter_sparse_pairs", stored as 9e18
  *     "upload_block_mb" staging block of the row-block ingestion (default 64)
  *     "small_batch"     1 (default): batches of <= 512 queries are scanned with finer row chunks and, up to 256 queries,
  *                       1 / 2 / 4-wave workgroups, so that the grid still covers the chip; D > 128: waves without queries
@@ -616,6 +658,11 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "knng_build_block"  k-NN graph: rows per self-search block of vdb_knng_build, 0 (default: 65 536) .. 1e9
  *     "range_bitmap_mb" range search: MiB of candidate bitmap (one bit per query and row) a query slab may take, 0 (default: 256)
  *                       .. 4096; a batch whose bitmap is larger runs in several slabs (same results; at least one query per slab)
+ *     "filter_sparse_pairs"  filtered search: a call with fewer (query, admitted row) pairs than this takes the sparse route over the
+ *                       list of admitted rows, 0 (never by this rule) .. inf, default 8192 (the measured crossover at D = 128, profiles/r21_bench_filter.json);
+ *                       same results either way.  Set it
+ *                       BEFORE vdb_filter_set: setting any option drops an installed filter, and the list is built at install
+ *                       according to the value in force
  *     "multi_stage_all" multi-device handles only (vdb_create_multi; every other option is forwarded to each shard, and "graph"
  *                       = 1 is VDB_ERR_UNSUPPORTED there): 1 (tests) shards on devices[0] take the remote-shard path too
  *     "graph_recapture_at_once"  diagnostic, 0 (default) | 1: the pre-round-3 ordering, for re-checking that defect

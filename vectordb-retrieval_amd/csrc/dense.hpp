@@ -191,7 +191,7 @@ __global__ __launch_bounds__(64) void dense_select_kernel(DenseSelectArgs a) {
         const int i = base + lane;
         bool valid = i < ncand;
         const int64_t row = valid ? (int64_t)cands[i] : 0;
-        valid = valid && row < a.c.N;
+        valid = valid && row < a.c.N && row_allowed(a.c.allow, row);      // (a filtered search, filter.hpp)
         uint64_t key = ~0ull;
         if (valid) key = exact_key(a.c.X + (size_t)row * a.c.D4, qptr, a.c.D4, a.c.metric);
         tk.offer(key, a.c.id_base + row, valid);
@@ -321,7 +321,7 @@ __device__ __forceinline__ void dense_select_tail(const DenseSelectArgs &a, int6
         const int i = base + lane;
         bool valid = i < ncand;
         const int64_t row = valid ? (int64_t)cands[i] : 0;
-        valid = valid && row < a.c.N;
+        valid = valid && row < a.c.N && row_allowed(a.c.allow, row);      // (a filtered search, filter.hpp)
         uint64_t key = ~0ull;
         if (valid) key = exact_key<4>(a.c.X + (size_t)row * a.c.D4, qptr, a.c.D4, a.c.metric);   // (4: fewer VGPRs, 8 waves per SIMD)
         tk.offer(key, a.c.id_base + row, valid);

@@ -66,7 +66,15 @@ struct RefineCommon {
     PqRows pq{};
     // IVF<nlist>,PQ<M> (ivf_pq.inc): X == nullptr and ivfpq.codes set -- product codes of the residuals, x^ = centroid + lookup
     IvfPqRows ivfpq{};
+    // filtered search (filter.hpp): bit r % 32 of word r / 32 admits row r; nullptr (every other call): all rows.  Last member:
+    // what the kernels of this file have always read stays where it was.
+    const uint32_t *allow = nullptr;
 };
+
+// the allow test of a filtered search, part of every exact stage's per-row `valid` flag (row < N: the words cover the padded corpus)
+__device__ __forceinline__ bool row_allowed(const uint32_t *__restrict__ allow, int64_t row) {
+    return !allow || ((allow[row >> 5] >> (row & 31)) & 1u);
+}
 
 typedef int refine_int4 __attribute__((ext_vector_type(4)));
 
@@ -250,14 +258,15 @@ __device__ __forceinline__ void exact_keys(const float *__restrict__ x, const fl
     for (int j = 0; j < QB; ++j) out[j] = sortable_u64(metric == 0 ? acc[j] : -acc[j]);
 }
 
-template <int KPL, int U = 16>
+// (ALLOW = false: the instantiations of the IVF kernels, whose rows no filter ever masks -- they keep the registers they had)
+template <int KPL, int U = 16, bool ALLOW = true>
 __device__ __forceinline__ void scan_rows(WaveTopK<KPL> &tk, const RefineCommon &c, const float *qptr, int64_t row0,
                                           int64_t row1) {
     const int lane = threadIdx.x & 63;
     if (row1 > c.N) row1 = c.N;
     for (int64_t base = row0; base < row1; base += 64) {
         const int64_t row = base + lane;
-        const bool valid = row < row1;
+        const bool valid = row < row1 && (!ALLOW || row_allowed(c.allow, row));
         uint64_t key = ~0ull;
         if (valid) key = row_key<U>(c, row, qptr);
         tk.offer(key, c.idmap ? (valid ? c.idmap[row] : -1) : c.id_base + row, valid);
@@ -313,7 +322,7 @@ struct RefineListArgs {
 // sits in SGPRs; per row  dot = sum (x - cx)(cq - q)  by W v_dot4c, and with n2 = sum x^2, s1 = sum x of the row
 //   x.q     = -dot + cq s1 + cx sum(q) - D cx cq          ||x - q||^2 = n2 - 2 x.q + sum(q^2)
 // -- all exact integers below 2^27, equal to what the canonical float64 chain computes on these integer inputs.
-template <int KPL, int W>
+template <int KPL, int W, bool ALLOW = true>
 __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_t q, int ncand, int nres, int gshift,
                                                  WaveTopK<KPL> &tk) {
     const int lane = threadIdx.x & 63;
@@ -358,7 +367,7 @@ __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_
         const int i = base + lane;
         bool valid = i < (ncand << gshift);
         const int64_t row = valid ? (int64_t)cr[i >> gshift] + (i & ((1 << gshift) - 1)) : 0;
-        valid = valid && row < c.N;
+        valid = valid && row < c.N && (!ALLOW || row_allowed(c.allow, row));
         const uint64_t key = valid ? key_of(row) : ~0ull;
         tk.offer(key, c.idmap ? (valid ? c.idmap[row] : -1) : c.id_base + row, valid);
     }
@@ -369,14 +378,14 @@ __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_
         if (row1 > c.N) row1 = c.N;
         for (int64_t base = row0; base < row1; base += 64) {
             const int64_t row = base + lane;
-            const bool valid = row < row1;
+            const bool valid = row < row1 && (!ALLOW || row_allowed(c.allow, row));
             const uint64_t key = valid ? key_of(row) : ~0ull;
             tk.offer(key, c.idmap ? (valid ? c.idmap[row] : -1) : c.id_base + row, valid);
         }
     }
 }
 
-template <int KPL>
+template <int KPL, bool ALLOW = true>
 __device__ __forceinline__ void refine_list_body(const RefineListArgs &a, unsigned block) {
     const int lane = threadIdx.x & 63;
     const int64_t q = __builtin_amdgcn_readfirstlane((int)(block * 4 + (threadIdx.x >> 6)));
@@ -393,20 +402,20 @@ __device__ __forceinline__ void refine_list_body(const RefineListArgs &a, unsign
     const int mode = a.c.info != nullptr ? a.c.info->i8_mode : 0;
     const int gshift = a.group_shift >= 0 ? a.group_shift : mode ? ((mode & 4) ? 3 : 2) : a.f16_shift;   // a candidate = 4 or 8 (or 1 / 2) consecutive rows
     if (mode != 0 && a.c.X8 != nullptr) {                        // integer batch on a byte-valued corpus: int8 rows
-        if (a.c.x8_pitch == 64) refine_list_dot8<KPL, 16>(a, q, ncand, nres, gshift, tk);
-        else refine_list_dot8<KPL, 32>(a, q, ncand, nres, gshift, tk);
+        if (a.c.x8_pitch == 64) refine_list_dot8<KPL, 16, ALLOW>(a, q, ncand, nres, gshift, tk);
+        else refine_list_dot8<KPL, 32, ALLOW>(a, q, ncand, nres, gshift, tk);
     } else {
         for (int base = 0; base < (ncand << gshift); base += 64) {
             const int i = base + lane;
             bool valid = i < (ncand << gshift);
             int64_t row = valid ? (int64_t)cr[i >> gshift] + (i & ((1 << gshift) - 1)) : 0;
-            valid = valid && row < a.c.N;
+            valid = valid && row < a.c.N && (!ALLOW || row_allowed(a.c.allow, row));
             uint64_t key = ~0ull;
             if (valid) key = row_key(a.c, row, qptr);
             tk.offer(key, a.c.idmap ? (valid ? a.c.idmap[row] : -1) : a.c.id_base + row, valid);
         }
         const int32_t *rr = a.rescan_rows + (size_t)q * a.rescan_cap * 2;
-        for (int r = 0; r < nres; ++r) scan_rows<KPL>(tk, a.c, qptr, rr[2 * r], rr[2 * r + 1]);
+        for (int r = 0; r < nres; ++r) scan_rows<KPL, 16, ALLOW>(tk, a.c, qptr, rr[2 * r], rr[2 * r + 1]);
     }
     const size_t o = (size_t)q * a.c.k;
     write_topk<KPL>(tk, a.c.metric, a.D ? a.D + o : nullptr, a.I ? a.I + o : nullptr, a.pkeys ? a.pkeys + o : nullptr,
@@ -618,7 +627,7 @@ __global__ __launch_bounds__(256) void refine_full_blocked_kernel(RefineFullArgs
         if (r1 > a.c.N) r1 = a.c.N;
         for (int64_t base = r0; base < r1; base += 64) {
             const int64_t row = base + lane;
-            const bool valid = row < r1;
+            const bool valid = row < r1 && row_allowed(a.c.allow, row);
             uint64_t key[QB];
 #pragma unroll
             for (int j = 0; j < QB; ++j) key[j] = ~0ull;

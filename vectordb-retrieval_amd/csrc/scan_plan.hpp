@@ -11,6 +11,8 @@
 #include <algorithm>
 #include <initializer_list>
 
+#include "filter_plan.hpp"      // kFilterSparsePairsDefault
+
 namespace vdb {
 
 // ---- geometry constants of the scan copies (row mapping: common.hpp) ------------------------------------------------------
@@ -67,6 +69,7 @@ struct Options {
     int knng_visited_bits = 0;               // log2 slots of the per-query seen filter (0 = default)
     int knng_build_block = 0;                // rows per self-search block of the build (0 = default)
     int range_bitmap_mb = 0;                 // range search (range_plan.hpp): MiB of candidate bitmap per query slab (0 = default 256)
+    int64_t filter_sparse_pairs = kFilterSparsePairsDefault;   // filtered search (filter_plan.hpp, kFilterSparsePairsDefault): (query, admitted row) pairs below which the sparse route serves a call
     // tuning of the flat scans
     int i8_variant = 3;                      // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)
     int i8_group = 8, f16_group = 8;         // rows per select group of the int8 / fp16 flat scan (4 or 8)

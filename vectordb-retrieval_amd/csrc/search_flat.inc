@@ -115,6 +115,8 @@ struct Batch {
     long tslot;                  // timing_begin
     bool clear_in_prep;          // workgroup 0 of query_prep_kernel clears ws.small (search_batch)
     bool adc;                    // PQ: the bin records come from the lookup-table scan of the codes (search_scan_adc), not from panels
+    const float *bias;           // accumulator inits the scans of this batch read: the handle's, or (a filtered search, filter.inc) the
+    const int32_t *bias8;        // masked copies of its filter -- rc.allow is set with them
 };
 
 // the S partial lists per slot that an exhaustive pass (fa) left in its (pkeys, pids), merged into the outputs of the batch
@@ -171,15 +173,15 @@ void search_dense(const Batch &b) {
     {
         const dim3 grid((unsigned)((ntiles + 3) / 4), (unsigned)(Qp / 64));
         if (h->ksteps > kMaxKSteps)
-            dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+            dense_scores_kloop_kernel<<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), b.bias,
                                                                  ws.qpanels.as<half8>(), info, ntiles, h->Npad, h->N,
                                                                  h->ksteps, ws.dense.as<float>());
         else if (h->ksteps == 4)
-            dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+            dense_scores_kernel<4><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), b.bias,
                                                               ws.qpanels.as<half8>(), info, ntiles, h->Npad,
                                                               ws.dense.as<float>());
         else
-            dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), h->scan.bias.as<float>(),
+            dense_scores_kernel<8><<<grid, dim3(256), 0, st>>>(h->scan.panels.as<half8>(), b.bias,
                                                               ws.qpanels.as<half8>(), info, ntiles, h->Npad,
                                                               ws.dense.as<float>());
     }
@@ -454,7 +456,7 @@ ScanI8Args scan_i8_args(const Batch &b, const ScanArgs &sa, int64_t Qpad) {
     const ScanGeom &g = b.g;
     ScanI8Args s8{};
     s8.panels = h->scan.panels8.as<int4v>();
-    s8.bias8 = h->scan.bias8.as<int32_t>();
+    s8.bias8 = b.bias8;
     s8.qpanels = b.ws.qpanels8.as<int4v>();
     s8.info = sa.info;
     s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2;
@@ -667,7 +669,7 @@ void search_scan(const Batch &b) {
 
     ScanArgs sa{};
     sa.panels = h->scan.panels.as<half8>();
-    sa.bias = h->scan.bias.as<float>();
+    sa.bias = b.bias;
     sa.qpanels = ws.qpanels.as<half8>();
     sa.info = info;
     sa.bin_m1 = ws.bin_m1.as<float>();
@@ -705,8 +707,10 @@ void search_scan(const Batch &b) {
 
 // what all paths share -- padded queries, where the rows live, geometry and path choice, the clearing of ws.small, timing_begin --
 // then the path
+// (filtered: a vdb_search_filtered call -- the same batch with the scans' accumulator inits pointing at the masked copies of the
+//  handle's filter and the allow words in RefineCommon; what follows reasons about the rows that EXIST with the admitted count)
 void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *pk, int64_t *pi,
-                  hipStream_t st) {
+                  hipStream_t st, bool filtered = false) {
     Workspace &ws = h->ws;
     const int Dm = h->dim, D4 = h->D4;
     // float32 queries padded to D4 for the refine kernels
@@ -719,6 +723,8 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     }
     RefineCommon rc = flat_rows(h, qpad, k);
     rc.info = batch_info(ws);                             // (group size of the candidates: 4 rows, 8 on the int8 scan)
+    if (filtered) rc.allow = h->filter.words.as<uint32_t>();
+    const int64_t n_live = filtered ? h->filter_count : h->N;
     const bool i8_off = h->opt.panel_dtype && !h->int8_only;   // (an int8-only index has nothing but the int8 copies)
     if (h->i8_ok && h->scan.rows8.p && !i8_off) {              // (int8 rows: batches the device puts on the int8 scan; int8-only: every batch)
         rc.X8 = h->scan.rows8.as<signed char>();
@@ -773,9 +779,11 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
 
     // small corpora: the dense path (search_dense)
     const bool use_dense = !use_scan && h->scan_ok && !exact_only && h->scan.panels.p != nullptr && (h->ksteps <= kMaxKSteps || h->ksteps % 4 == 0) &&
-                           h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= h->N &&
+                           h->Npad <= kDenseMaxRows && nq >= 64 && k <= 1024 && (int64_t)k * 2 <= n_live &&
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
-    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, shape, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc};
+    const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, shape, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc,
+                  filtered ? h->filter.bias_f.as<float>() : h->scan.bias.as<float>(),
+                  filtered ? h->filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>()};
     if (use_dense) search_dense(b);
     else if (!use_scan) search_exact(b);
     else search_scan(b);
@@ -880,7 +888,7 @@ void graph_or_run(vdb_index_s *h, const vdb_index_s::GraphKey &key, F &&run) {
 }
 
 void search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *pk,
-                        int64_t *pi, hipStream_t st) {
+                        int64_t *pi, hipStream_t st, bool filtered = false) {
     if (!h->built) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (k < 1 || k > 2048) throw Error(VDB_ERR_INVALID, "k must be in [1, 2048]");
     if (nq < 0) throw Error(VDB_ERR_INVALID, "negative query count");
@@ -922,7 +930,7 @@ void search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, floa
             const int64_t nb = std::min<int64_t>(kBatch, nq - b0);
             search_batch(h, dq + (size_t)b0 * h->dim, nb, k, D ? D + (size_t)b0 * k : nullptr,
                          I ? I + (size_t)b0 * k : nullptr, pk ? pk + (size_t)b0 * k : nullptr,
-                         pi ? pi + (size_t)b0 * k : nullptr, st);
+                         pi ? pi + (size_t)b0 * k : nullptr, st, filtered);
         }
     } catch (...) {
         h->ev_used = ev_mark;      // events of a failed search were never all recorded: do not leave them to vdb_stats

@@ -37,6 +37,7 @@
 #include "ivf_pq_adc.hpp"
 #include "knng.hpp"
 #include "range.hpp"
+#include "filter.hpp"
 
 using namespace vdb;
 
@@ -252,6 +253,15 @@ struct RangeBufs {
     DevBuf qstage{"range.qstage"}, qpad{"range.qpad"}, qpanels{"range.qpanels"}, info{"range.info"}, eps{"range.eps"}, thr{"range.thr"}, flag{"range.flag"};
 };
 
+// the installed filter of the handle (filter.inc): the allow words (tail clean, padded to Npad rows), the masked copies of the
+// scans' accumulator inits, the ascending list of admitted rows with its segment offsets when the sparse route may need it, and
+// the admitted count; every buffer sized exactly        (freed by vdb_filter_clear, vdb_reset and with the handle; dropped by any add
+// and vdb_set_option)
+struct FilterBufs {
+    DevBuf words{"filter.words"}, bias_f{"filter.bias_f"}, bias8_f{"filter.bias8_f"};
+    DevBuf list{"filter.list"}, seg{"filter.seg"}, count{"filter.count"};
+};
+
 // (struct Options -- everything vdb_set_option writes -- is in scan_plan.hpp: the launch rules of the flat scans read it)
 
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
@@ -290,7 +300,8 @@ struct vdb_index_s {
     KnngWorkspace knng_ws;
     Workspace ws;
     RangeBufs range;
-    Options opt;                             // what vdb_set_option has set; every other member is the library's own state
+    FilterBufs filter;
+    Options opt;                            // what vdb_set_option has set; every other member is the library's own state
     int rows8_pitch = 0;
     bool i8_ok = false;
     bool x16 = false;                        // the flat scan copies (fp16 and int8, D <= 128) are in layout "x16": 16x16x32 f16 / 16x16x64 i8 MFMA,
@@ -376,6 +387,12 @@ struct vdb_index_s {
     bool range_valid = false;
     int64_t range_total = 0, range_nq = 0;   // lims[nq] and nq of that result
     int64_t range_cand = 0, range_fb = 0;    // (query, row) pairs scored exactly / queries for which every row was a candidate
+    // the installed filter (filter.inc): `filter` holds it while filter_valid (any add, vdb_reset, vdb_set_option and a change of
+    // kind drop it)
+    bool filter_valid = false, filter_has_list = false;
+    unsigned filter_kind = 0;                // kind_of the handle at install
+    int64_t filter_count = 0;                // rows it admits
+    int64_t filter_cand = 0;                 // (query, row) pairs the last sparse-route search scored
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -467,6 +484,7 @@ constexpr OptionRow kOptions[] = {
     {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
     {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
     {"range_bitmap_mb", &Options::range_bitmap_mb, 0, {0, 4096}},    // range search: MiB of candidate bitmap per query slab (0 = default 256)
+    {"filter_sparse_pairs", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::filter_sparse_pairs},   // filtered search: (query, admitted row) pairs below which the sparse route serves a call (0 = never by this rule)
     {"i8_variant", &Options::i8_variant, 0, {0, 7}},
     {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
     {"f16_group", &Options::f16_group, 2, {4, 8}, 0, 4},             // rows per select group of the fp16 flat scan: 8 (octs, default) or 4 (quads)
@@ -509,7 +527,7 @@ void refuse_options_set(const vdb_index_s *h, const char *what, unsigned kind) {
 }
 
 template <class F>
-void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); f(h->range); }
+void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); f(h->range); f(h->filter); }
 
 // every byte of device memory the handle holds (its ws.small may be a view into plan.ivf_zero: not counted twice)
 size_t handle_bytes(vdb_index_s *h) {
@@ -557,6 +575,16 @@ void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st);       // lsh_tab
 inline bool pq_on(const vdb_index_s *h) { return h->pq.M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
+// an installed filter goes (filter.inc installs and uses it).  Its buffers may still be read by a search on a caller's stream.
+void filter_drop(vdb_index_s *h) {
+    if (group_bytes(h->filter) > 0) {
+        set_device(h->device);
+        (void)hipDeviceSynchronize();
+        group_release(h->filter);
+    }
+    h->filter_valid = h->filter_has_list = false;
+    h->filter_count = 0;
+}
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
@@ -1072,6 +1100,7 @@ void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, 
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
     set_device(h->device);
     h->range_valid = false;                    // (the last range result described the rows as they were)
+    filter_drop(h);                            // (... and so did an installed filter: one bit per row, nbits == ntotal)
     if (knng_on(h)) {                          // (the graph describes the rows as they were)
         VDB_HIP(hipDeviceSynchronize());
         knng_drop(h);
@@ -1193,6 +1222,7 @@ int vdb_reset(vdb_handle hh) {
         group_release(h->codes);
         group_release(h->range);
         h->range_valid = false;
+        filter_drop(h);
         h->lsh_rows = 0;                       // (the projection stays)
         h->lsht_rows = 0;                      // (the hash tables stay)
         h->knng_degree = 0;                    // (the graph went with the codes group)
@@ -1421,6 +1451,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_candidates = h->range_cand;
             s.last_fallback_queries = h->range_fb;
         }
+        if (h->last.last_path == VDB_PATH_FILTER_ROWS) s.last_candidates = h->filter_cand;     // (sparse route: nq x admitted rows)
         if (h->ev_used > 0) {  // averages over every search recorded since timing was switched on
             double scan = 0.0, total = 0.0, prep = 0.0, tail = 0.0;
             for (size_t i = 0; i < h->ev_used; ++i) {
@@ -1453,6 +1484,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         const std::string k(key);
         graph_reset(h);                        // (a captured search embodies the options it was captured under)
         h->range_valid = false;                // (... and the last range result goes with any option change)
+        filter_drop(h);                        // (... and an installed filter: its list was built under the options in force)
         const OptionRow *r = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionRow &o) { return k == o.name; });
         if (r == std::end(kOptions)) throw Error(VDB_ERR_INVALID, "unknown option '" + k + "'");
         // what this kind of index refuses comes first, whatever the value is otherwise
@@ -1467,7 +1499,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (r->n == 0 && (value < r->v[0] || value > r->v[1]))
             throw Error(VDB_ERR_INVALID, "option '" + k + "' must be in [" + number(r->v[0]) + ", " + number(r->v[1]) + "]");
         if (r->m == &Options::ivfpq_adc_part_rows && (int)value % 256 != 0) throw Error(VDB_ERR_INVALID, "option '" + k + "' must be a multiple of 256");
-        if (r->m64) h->opt.*r->m64 = (int64_t)value;
+        if (r->m64) h->opt.*r->m64 = value >= 9.0e18 ? (int64_t)9000000000000000000ll : (int64_t)value;      // (the int64 options take "inf": "stream_slab_rows" too, whose cast of inf was undefined before)
         else h->opt.*r->m = r->n < 0 ? value != 0 : (int)value;
         if (r->m == &Options::timing) h->ev_used = 0;          // (a new recording window)
     });
@@ -1480,5 +1512,6 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 #include "lsh_tables.inc"
 #include "knng.inc"
 #include "range.inc"
+#include "filter.inc"
 #include "debug_ivf.inc"
 #include "multi.inc"

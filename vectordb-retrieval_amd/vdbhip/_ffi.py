@@ -18,7 +18,7 @@ import numpy as np
 
 VDB_OK, VDB_ERR_INVALID, VDB_ERR_STATE, VDB_ERR_HIP, VDB_ERR_NOMEM, VDB_ERR_UNSUPPORTED = range(6)
 METRIC_L2, METRIC_IP = 0, 1
-PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc", 8: "ivfpq_adc", 9: "range"}
+PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc", 8: "ivfpq_adc", 9: "range", 10: "filter_rows"}
 
 _LIB_NAME = "libvdbhip.so"
 _lib: Optional[ctypes.CDLL] = None
@@ -111,6 +111,12 @@ SIGNATURES = {
     "vdb_range_results": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vdb_range_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, POINTER(c_int64), c_void_p]),
     "vdb_range_results_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vdb_filter_set": (c_int, [c_void_p, c_void_p, c_int64]),
+    "vdb_filter_set_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "vdb_filter_clear": (c_int, [c_void_p]),
+    "vdb_filter_count": (c_int, [c_void_p, POINTER(c_int64)]),
+    "vdb_search_filtered": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "vdb_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),
@@ -232,6 +238,42 @@ def as_f32_queries(a: np.ndarray) -> np.ndarray:
     """`as_f32_c`, a single query (1-D) as a batch of one."""
     q = as_f32_c(a)
     return q.reshape(1, -1) if q.ndim == 1 else q
+
+
+def pack_allow_bits(allowed, ntotal: int, id_base: int = 0, nbits: Optional[int] = None) -> np.ndarray:
+    """The allow bitmap of a filtered search as the C ABI reads it: uint32 words, bit r % 32 of word r / 32 admits row r, (ntotal + 31)
+    // 32 words, bits at positions >= ntotal clear.  `allowed` is one of
+      a bool array of length ntotal                       (row r is admitted where allowed[r]);
+      an integer array of ids, i.e. id_base + row         (duplicates are fine; an id outside [id_base, id_base + ntotal) is a ValueError);
+      packed uint32 words together with nbits=            (nbits must equal ntotal; tail bits may hold anything).
+    Pure NumPy."""
+    ntotal = int(ntotal)
+    nwords = (ntotal + 31) // 32
+    a = np.asarray(allowed)
+    if nbits is not None:
+        if int(nbits) != ntotal:
+            raise ValueError(f"a filter has one bit per row: nbits must equal ntotal = {ntotal}, got {int(nbits)}")
+        if a.dtype != np.uint32 or a.ndim != 1 or a.shape[0] < nwords:
+            raise ValueError(f"expected at least {nwords} packed uint32 words, got {a.dtype} {a.shape}")
+        words = np.array(a[:nwords], dtype=np.uint32)
+    elif a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != ntotal:
+            raise ValueError(f"expected a bool mask of length ntotal = {ntotal}, got {a.shape}")
+        packed = np.packbits(a, bitorder="little")
+        words = np.zeros(nwords, np.uint32)
+        words.view(np.uint8)[:packed.shape[0]] = packed
+    elif np.issubdtype(a.dtype, np.integer):
+        rows = a.astype(np.int64, copy=False).reshape(-1) - int(id_base)
+        if rows.size and (rows.min() < 0 or rows.max() >= ntotal):
+            raise ValueError(f"filter ids must lie in [{int(id_base)}, {int(id_base) + ntotal})")
+        mask = np.zeros(ntotal, np.bool_)
+        mask[rows] = True
+        return pack_allow_bits(mask, ntotal)
+    else:
+        raise ValueError(f"a filter is a bool mask, an integer id array or packed uint32 words with nbits=, got dtype {a.dtype}")
+    if nwords and ntotal % 32:
+        words[-1] &= np.uint32((1 << (ntotal % 32)) - 1)
+    return words
 
 
 def ptr(a: Optional[np.ndarray]) -> Optional[int]:

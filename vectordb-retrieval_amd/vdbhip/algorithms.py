@@ -211,11 +211,17 @@ class HipExactSearch(RawAlgorithm):
         d, i = self.index.search(np.asarray(query, dtype=np.float32).reshape(1, -1), k)
         return d[0], i[0]
 
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
+    def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> SearchResult:
+        """`allowed` (None: every row): a bool mask over the rows, an integer id array or anything else FlatIndex.set_filter
+        takes -- the k nearest among those rows, same conventions and padding.  The same array object is installed once."""
         self._require_built()
         q = _ffi.as_f32_c(queries)
-        self.record_operation("ndis", float(q.shape[0]) * float(self.index.ntotal))
-        return self.index.search(q, k)
+        if allowed is None:
+            self.record_operation("ndis", float(q.shape[0]) * float(self.index.ntotal))
+            return self.index.search(q, k)
+        self.index.ensure_filter(allowed)
+        self.record_operation("ndis", float(q.shape[0]) * float(self.index.filter_count))
+        return self.index.search_filtered(q, k)
 
     def range_search(self, queries: np.ndarray, radius: float, sort: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """faiss.IndexFlat.range_search in the raw conventions: (lims, D, I) of the rows with squared L2 < radius / inner
@@ -281,14 +287,21 @@ class HipLinearSearcher(BaseSearcher):
         d, i = self.batch_search(query_batch(query), k)
         return d[0], i[0]
 
-    def batch_search(self, queries: np.ndarray, k: int = 10) -> SearchResult:
+    def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> SearchResult:
+        """`allowed` (None: every row): what FlatIndex.set_filter takes -- the k nearest among those rows, in this searcher's
+        conventions (+inf / -1 where fewer than k rows are admitted).  The same array object is installed once."""
         if not self._prepared:
             raise RuntimeError("LinearSearcher not attached to an index")
         if self.metric not in ("l2", "cosine", "ip"):
             raise ValueError(f"Unsupported metric '{self.metric}' for LinearSearcher")
         if self._ntotal == 0:
             raise RuntimeError("LinearSearcher cannot operate on empty index")
-        d, i = self._index.search(query_batch(queries, self.metric == "cosine"), k)
+        q = query_batch(queries, self.metric == "cosine")
+        if allowed is None:
+            d, i = self._index.search(q, k)
+        else:
+            self._index.ensure_filter(allowed)
+            d, i = self._index.search_filtered(q, k)
         return euclidean_or_negated(d, i, self.metric)
 
     def range_search(self, queries: np.ndarray, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

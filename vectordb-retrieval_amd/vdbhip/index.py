@@ -84,10 +84,12 @@ class _Handle:
         _ffi.check(self._lib.vdb_reserve(self._handle(), int(nq), int(k)), build_time=True)
 
     def set_option(self, key: str, value: float) -> None:
+        self._filter_key = None              # (any option change drops an installed filter)
         _ffi.check(self._lib.vdb_set_option(self._handle(), key.encode(), float(value)), build_time=True)
 
     def reset(self) -> None:
         """Drop every row; what was trained or set (centroids, ranges, codebooks) stays (faiss.Index.reset)."""
+        self._filter_key = None
         _ffi.check(self._lib.vdb_reset(self._handle()), build_time=True)
         self.ntotal = 0
 
@@ -163,6 +165,52 @@ class _FlatSearch(_Handle):
         """The (D, I) of the last range search of this index into device memory; asynchronous on `stream`."""
         _ffi.check(self._lib.vdb_range_results_device(self._handle(), d_ptr, i_ptr, stream or None))
 
+    # -- filtered search (vdb_filter_*, vdb_search_filtered): the k nearest rows among those an allow bitmap admits ----
+    _filter_key = None       # (object, ntotal) of the filter `ensure_filter` installed last; any call that drops the filter clears it
+
+    def set_filter(self, allowed, nbits: Optional[int] = None) -> None:
+        """Install the rows a filtered search may return: a bool array of length ntotal, an integer array of ids (id_base +
+        row; duplicates allowed, out of range raises ValueError), or packed uint32 words with `nbits=` (_ffi.pack_allow_bits).
+        Any add, reset or set_option drops the filter."""
+        self._filter_key = None
+        words = _ffi.pack_allow_bits(allowed, self.ntotal, getattr(self, "id_base", 0), nbits)
+        _ffi.check(self._lib.vdb_filter_set(self._handle(), _ffi.ptr(words), self.ntotal), build_time=True)
+
+    def set_filter_device(self, words_ptr: int, nbits: int, stream: int = 0) -> None:
+        """Packed uint32 words in device memory of this index's GPU; runs on `stream` and waits for it once."""
+        self._filter_key = None
+        _ffi.check(self._lib.vdb_filter_set_device(self._handle(), words_ptr, int(nbits), stream or None), build_time=True)
+
+    def ensure_filter(self, allowed) -> None:
+        """`set_filter(allowed)` unless that very object was installed last on these rows (identity and ntotal, not content)."""
+        key = self._filter_key
+        if key is not None and key[0] is allowed and key[1] == self.ntotal:
+            return
+        self.set_filter(allowed)
+        self._filter_key = (allowed, self.ntotal)
+
+    def clear_filter(self) -> None:
+        self._filter_key = None
+        _ffi.check(self._lib.vdb_filter_clear(self._handle()))
+
+    @property
+    def filter_count(self) -> int:
+        """Rows the installed filter admits."""
+        n = ctypes.c_int64(0)
+        _ffi.check(self._lib.vdb_filter_count(self._handle(), ctypes.byref(n)))
+        return int(n.value)
+
+    def search_filtered(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` among the rows of the installed filter: same keys, order and padding (fewer than k admitted rows pad)."""
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], k)
+        _ffi.check(self._lib.vdb_search_filtered(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+    def search_filtered_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
+        _ffi.check(self._lib.vdb_search_filtered_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
+
     def rerank(self, queries: np.ndarray, candidate_ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
         """Exact top-k among explicit candidate ids per query (nq, ncand) int64, -1 = empty slot."""
         q = _ffi.as_f32_queries(queries)
@@ -184,6 +232,7 @@ class FlatIndex(_FlatSearch):
         self.dim, self.metric, self.device = int(dim), metric, normalize_devices(device)
         super().__init__(self.dim, code, self.device)
         self.ntotal = 0
+        self.id_base = 0
 
     @property
     def devices(self):
@@ -194,15 +243,19 @@ class FlatIndex(_FlatSearch):
         """Append rows (faiss.Index.add): row i of the index, counted over all adds, has id `id_base + i`; every add of
         one index passes the same `id_base`.  `reset()` empties the index."""
         x = self._rows(vectors)
+        self._filter_key = None
         try:
             _ffi.check(self._lib.vdb_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
+            self.id_base = int(id_base)
         finally:
             self._sync_ntotal()
 
     def add_device(self, dev_ptr: int, n: int, id_base: int = 0, stream: int = 0) -> None:
+        self._filter_key = None
         try:
             _ffi.check(self._lib.vdb_add_device(self._handle(), dev_ptr, int(n), int(id_base), stream or None),
                        build_time=True)
+            self.id_base = int(id_base)
         finally:
             self._sync_ntotal()
 
