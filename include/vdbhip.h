@@ -120,6 +120,8 @@ typedef struct vdb_stats_s {
  *   vdb_filter_set(_device), vdb_filter_count,
  *     vdb_search_filtered(_device)                       +     +    +     +    U      U         U        U       U
  *   vdb_filter_clear                                     +     +    +     +    +      +         +        +       U
+ *   vdb_ivf_filter_set(_device), vdb_ivf_filter_count,
+ *     vdb_ivf_search_filtered(_device)                   +     U    U     U    U      +         U        U       U
  *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
  *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
  *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
@@ -266,6 +268,45 @@ int vdb_filter_count(vdb_handle h, int64_t *n_allowed);          /* rows the ins
 int vdb_search_filtered(vdb_handle h, const float *q_host, int64_t nq, int k, float *D, int64_t *I);
 /* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
 int vdb_search_filtered_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev, void *stream);
+
+/* ---- filtered k-NN search on IVF-Flat indexes -- replaces IndexIVFFlat.search(.., params=SearchParametersIVF(sel=IDSelectorBitmap)):
+ * the k nearest rows AMONG the admitted rows of the probed lists, exactly --------------------------------------------------------
+ * (The flat filter calls above keep refusing IVF handles: these are entry points of their own.)
+ * The filter is the flat one's: bit r % 32 of word r / 32 admits the row whose id is id_base + r -- row numbers in INSERTION order
+ * over all vdb_ivf_add / _add_assigned calls, NOT in list order.  nbits must equal ntotal; bits at positions >= nbits of the last
+ * word are ignored, whatever they hold; (nbits + 31) / 32 words are read.
+ * The result is defined by vdb_ivf_search: per query it covers the same nprobe lists (the coarse search never looks at the filter, as
+ * in FAISS) and returns the k rows smallest under (canonical float64 key, id) among the ADMITTED rows of those lists, with
+ * vdb_ivf_search's distances, tie order and -1 / +-FLT_MAX padding.  An all-ones filter returns vdb_ivf_search's bytes, an all-zero
+ * filter only padding.  vdb_ivf_search and every other call never look at the filter.
+ * The filter is state of the handle and counts in bytes_resident:
+ *     bytes = 4 * 2 * ceil(ntotal / 64)            the allow words in list order
+ *           + 8                                    the admitted count
+ *           + 4 * panel_rows                       masked accumulator inits of the list-padded panel space (panel_rows = its rows:
+ *                                                  every list padded to whole spans of 256 rows, D > 128: 256 or 1024), if built
+ *           + 8 * panel_rows                       ... and of its int8 copy (byte-valued rows, D <= 128)
+ * (ivf_filter_bytes, csrc/ivf_filter_plan.hpp).  vdb_filter_clear, vdb_reset and vdb_destroy free it.  Any vdb_ivf_add*, vdb_add,
+ * vdb_reset, vdb_set_option, vdb_ivf_set_centroids, vdb_ivf_train and a change of kind DROP it (an add that is refused -- no
+ * centroids, a bad pointer, another id_base, a list id out of range -- changes nothing and keeps it; an empty append drops it);
+ * vdb_ivf_set_nprobe does not (nothing in it depends on nprobe).  An install that replaces a filter writes into the same buffers.  A filtered search without a filter is VDB_ERR_STATE with a message naming the missing filter: it never
+ * answers unfiltered.  An install synchronises its stream once (the admitted count comes back); the searches synchronise nothing.
+ * How: the install permutes the bitmap into list order on the device and writes masked copies of the list scans'
+ * accumulator inits (the pad marker of DESIGN 4.14); the list scans run unchanged on the copies and the exact stages (candidate
+ * refine, flagged-query fallback, exact list scan) test the list-order bit.  The exact list scan answers a batch instead of the
+ * list-major scan when min(bins per query, nprobe * n_allowed / nlist) < 4 k (ivf_filter_declines; never for a filter that admits
+ * every row); option "force_path" keeps its meaning (1: exact list scan, 2: list-major scan wherever vdb_ivf_search would take it).
+ * VDB_ERR_STATE: no centroids / not built / an empty index; a search or vdb_ivf_filter_count without a filter.  VDB_ERR_INVALID:
+ * nq <= 0, k outside [1, 2048], a null pointer, nbits != ntotal.  VDB_ERR_UNSUPPORTED: the kinds of the table above, and any handle
+ * while option "graph" is 1.  A failed allocation is VDB_ERR_NOMEM: the handle keeps its rows and loses only the filter.
+ * vdb_stats after a filtered search: last_path = VDB_PATH_IVF; last_candidates, last_rescan_bins, last_fallback_queries and
+ * last_rows_scanned mean what they mean after vdb_ivf_search.  Not served: IVF-SQ8, IVF-PQ, multi-device and sharded (partial) forms. */
+int vdb_ivf_filter_set(vdb_handle h, const uint32_t *words_host, int64_t nbits);
+/* words in device memory of the handle's GPU; the install runs on `stream`, which is synchronised once */
+int vdb_ivf_filter_set_device(vdb_handle h, const uint32_t *words_dev, int64_t nbits, void *stream);
+int vdb_ivf_filter_count(vdb_handle h, int64_t *n_allowed);      /* rows the installed filter admits */
+int vdb_ivf_search_filtered(vdb_handle h, const float *q_host, int64_t nq, int k, float *D, int64_t *I);
+/* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
+int vdb_ivf_search_filtered_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev, void *stream);
 
 /* ---- row-sharded search (one process per GPU; partials exchanged with an RCCL all-gather) ---- */
 /* per-shard partial top-k: float64 order keys (L2: squared distance, IP: -score) and global ids,

@@ -26,7 +26,8 @@ struct IvfScanArgs {
     int64_t *pids;
 };
 
-template <int KPL>
+// (ALLOW: the filtered search of ivf_filter.inc -- a.c.allow holds the allow words in list order; false: vdb_ivf_search's kernels)
+template <int KPL, bool ALLOW = false>
 __global__ __launch_bounds__(256) void ivf_scan_kernel(IvfScanArgs a) {
     const int64_t u = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (u >= a.nq * a.S) return;
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(IvfScanArgs a) {
     for (int p = split; p < a.nprobe; p += a.S) {
         const int64_t l = a.probes[(size_t)q * a.nprobe + p];
         if (l < 0) continue;
-        scan_rows<KPL, 16, false>(tk, a.c, qptr, a.offsets[l], a.offsets[l + 1]);
+        scan_rows<KPL, 16, ALLOW>(tk, a.c, qptr, a.offsets[l], a.offsets[l + 1]);
     }
     if (a.D) {
         const size_t o = (size_t)q * a.c.k;
@@ -76,7 +77,7 @@ struct IvfFallbackArgs {
     int64_t *oids;
 };
 
-template <int KPL>
+template <int KPL, bool ALLOW = false>
 __device__ __forceinline__ void ivf_fallback_body(const IvfFallbackArgs &a, unsigned block, unsigned nblocks) {
     const int64_t count = *a.fb_count;
     if (count <= 0) return;
@@ -97,7 +98,7 @@ __device__ __forceinline__ void ivf_fallback_body(const IvfFallbackArgs &a, unsi
         for (int p = split; p < a.nprobe; p += (int)S) {
             const int64_t l = a.probes[(size_t)q * a.nprobe + p];
             if (l < 0) continue;
-            scan_rows<KPL, 4, false>(tk, a.c, qptr, a.offsets[l], a.offsets[l + 1]);      // (4 loads in flight: see refine_fallback_body)
+            scan_rows<KPL, 4, ALLOW>(tk, a.c, qptr, a.offsets[l], a.offsets[l + 1]);      // (4 loads in flight: see refine_fallback_body)
         }
         const size_t oq = (size_t)q * a.c.k;
         if (S == 1) {
@@ -133,10 +134,10 @@ __device__ __forceinline__ void ivf_fallback_body(const IvfFallbackArgs &a, unsi
 }
 
 // the tail of an IVF search in one launch (as refine_tail_kernel): fallback workgroups first, then the work lists
-template <int KPL>
+template <int KPL, bool ALLOW = false>
 __global__ __launch_bounds__(256, (KPL == 1 ? 6 : KPL == 2 ? 5 : 1)) void ivf_tail_kernel(RefineListArgs la, IvfFallbackArgs fa, unsigned fb_blocks) {
-    if (blockIdx.x < fb_blocks) ivf_fallback_body<KPL>(fa, blockIdx.x, fb_blocks);
-    else refine_list_body<KPL, false>(la, blockIdx.x - fb_blocks);
+    if (blockIdx.x < fb_blocks) ivf_fallback_body<KPL, ALLOW>(fa, blockIdx.x, fb_blocks);
+    else refine_list_body<KPL, ALLOW>(la, blockIdx.x - fb_blocks);
 }
 
 // ---- CSR build: xperm[i] = x[perm[i]], ids[i] = id_base + perm[i] (src_ids: ids[i] = src_ids[perm[i]], the append) ---

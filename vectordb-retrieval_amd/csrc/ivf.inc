@@ -329,6 +329,8 @@ struct IvfBatch {
     IvfIndexShape shape;    // ivf_shape_of(h)
     IvfGeom g;              // list-major path only: the geometry, and the zeroed counter block of this batch (ivf_zero)
     int32_t *d_cnt;
+    bool filtered;          // a vdb_ivf_search_filtered call (ivf_filter.inc): the scans read the masked copies of the handle's filter,
+                            // the exact stages test its list-order allow words
 };
 
 // what the steps of ivf_search_lists share: capacities, the plan's launch shape, views into the counter block and the plan
@@ -468,7 +470,7 @@ void ivf_scan_i8(const IvfBatch &b, const ScanArgs &sa) {
     vdb_index_s *h = b.h;
     ScanI8Args s8{};
     s8.panels = h->scan.panels8.as<int4v>();
-    s8.bias8 = h->scan.bias8.as<int32_t>();
+    s8.bias8 = b.filtered ? h->ivf_filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>();
     s8.info = sa.info;
     s8.bin_m1 = sa.bin_m1; s8.bin_m2 = sa.bin_m2; s8.bin_m3 = sa.bin_m3;
     s8.Npad = h->ivf_pspans * kIvfSpanRows;
@@ -519,6 +521,7 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     const int64_t nb = b.nb;
     RefineCommon rc{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     rc.info = L.info;
+    if (b.filtered) rc.allow = h->ivf_filter.words.as<uint32_t>();
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
     if (ivfpq(h)) rc.ivfpq = ivfpq_rows(h);
     if (L.c.use_i8 && h->scan.rows8.p) {
@@ -546,7 +549,12 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     a.done = L.d_fb_done;
     a.D = b.D; a.I = b.I; a.okeys = b.pk; a.oids = b.pi;
     const int kpl = kpl_for(k);
-    DISPATCH_KPL(kpl, (ivf_tail_kernel<KPL><<<dim3(512 + (unsigned)((nb + 3) / 4)), dim3(256), 0, b.st>>>(la, a, 512u)));
+    const dim3 grid(512 + (unsigned)((nb + 3) / 4));
+    if (b.filtered) {
+        DISPATCH_KPL(kpl, (ivf_tail_kernel<KPL, true><<<grid, dim3(256), 0, b.st>>>(la, a, 512u)));
+    } else {
+        DISPATCH_KPL(kpl, (ivf_tail_kernel<KPL><<<grid, dim3(256), 0, b.st>>>(la, a, 512u)));
+    }
     VDB_HIP(hipGetLastError());
 }
 
@@ -559,7 +567,7 @@ void ivf_search_lists(const IvfBatch &b) {
     ivf_lists_plan(b, L);
     ScanArgs sa{};
     sa.panels = sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
-    sa.bias = h->scan.bias.as<float>();
+    sa.bias = b.filtered ? h->ivf_filter.bias_f.as<float>() : h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
     sa.slot_query = L.d_slot_query;
@@ -607,6 +615,7 @@ void ivf_search_exact(const IvfBatch &b) {
     a.c = RefineCommon{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
     if (ivfpq(h)) a.c.ivfpq = ivfpq_rows(h);  // (IVF-PQ: likewise, centroid + codebook entry)
+    if (b.filtered) a.c.allow = h->ivf_filter.words.as<uint32_t>();
     a.offsets = h->lists.ivf_offsets.as<int64_t>();
     a.probes = h->plan.ivf_probe_i.as<int64_t>();
     a.nq = nb; a.nprobe = nprobe; a.S = (int)S;
@@ -620,7 +629,11 @@ void ivf_search_exact(const IvfBatch &b) {
     timing_mark(h, b.tslot, 0, st);
     const int kpl = kpl_for(k);
     const unsigned grid = (unsigned)((nb * S + 3) / 4);
-    DISPATCH_KPL(kpl, (ivf_scan_kernel<KPL><<<dim3(grid), dim3(256), 0, st>>>(a)));
+    if (b.filtered) {
+        DISPATCH_KPL(kpl, (ivf_scan_kernel<KPL, true><<<dim3(grid), dim3(256), 0, st>>>(a)));
+    } else {
+        DISPATCH_KPL(kpl, (ivf_scan_kernel<KPL><<<dim3(grid), dim3(256), 0, st>>>(a)));
+    }
     VDB_HIP(hipGetLastError());
     timing_mark(h, b.tslot, 1, st);
     if (S > 1) {
@@ -634,8 +647,10 @@ void ivf_search_exact(const IvfBatch &b) {
 }
 
 // what both paths share -- the clearing of ivf_zero, timing_begin, the coarse search, padded queries -- then the path, per batch
+// (filtered: a vdb_ivf_search_filtered call, ivf_filter.inc -- the same batches with IvfBatch::filtered set; the coarse search never
+//  looks at the filter, the routing rule reads the admitted count)
 void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *PK,
-                            int64_t *PI, hipStream_t st) {
+                            int64_t *PI, hipStream_t st, bool filtered = false) {
     ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
     const bool partial = D == nullptr;
     ivf_require(k >= 1 && k <= 2048, VDB_ERR_INVALID, "k must be in [1, 2048]");
@@ -666,8 +681,9 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         // everything this batch needs zeroed sits in ivf_zero: ONE memset (first batch of a call: both ws.small whole and
         // the counter block; later batches keep this handle's statistics counters, which accumulate over the call)
         b.shape = shape;
+        b.filtered = filtered;
         const IvfAdcPlan adc = ivf_adc_plan(h->opt, h->ivf_codec, h->ivfpq.M, adc_ranges, h->N, adc_longest, b.nb, k, b.nprobe);
-        if (!adc.ok) b.g = ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
+        if (!adc.ok) b.g = filtered ? ivf_filter_geometry(shape, h->opt, b.nb, k, b.nprobe, h->ivf_filter_count) : ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
             VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (b.g.ok ? b.g.cnt_words * 4 : 0), st));
@@ -718,6 +734,7 @@ int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist)
         if (h->multi) return multi_set_centroids(h, centroids_host, nlist);
         set_device(h->device);
         graph_reset(h);
+        filter_drop(h);                        // (an installed filter describes the lists of the old centroids)
         ivf_install_centroids(h, centroids_host, nlist);
         h->ivf_built = false;
     });
@@ -747,6 +764,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         if (h->multi) return multi_train(h, nlist, x_host, n, niter, seed, max_points_per_centroid);
         graph_reset(h);
         set_device(h->device);
+        filter_drop(h);
         const int Dm = h->dim, D4 = h->D4;
         // ---- sample (seeded partial Fisher-Yates), in draw order -----------------------------------
         const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * nlist);
@@ -960,8 +978,12 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
         int64_t N0, N1;
-        if (!ivf_add_range(h, n, id_base, N0, N1)) return;
+        const bool rows_change = ivf_add_range(h, n, id_base, N0, N1);
         ivf_check_given(h, given, n);
+        // an installed filter (ivf_filter.inc) has one bit per row, and the rows change place: every add that passed its checks drops
+        // it, an empty append too; a refused add leaves it with the index.  (The coded indexes above never hold one.)
+        filter_drop(h);
+        if (!rows_change) return;
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;
         graph_reset(h);

@@ -367,7 +367,7 @@ void multi_add(vdb_index_s *m, const float *x, bool on_device, int64_t n, int64_
 }
 
 void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, int64_t *I, double *PK, int64_t *PI,
-                            hipStream_t st);
+                            hipStream_t st, bool filtered);
 
 // One search over all shards.  q: host memory (host API) or device memory of the primary device (device API, `user_stream`
 // has produced it).  Outputs: host (D, I) for the host API; primary-device (D, I) or partial (PK, PI) for the device API.

@@ -38,6 +38,7 @@
 #include "knng.hpp"
 #include "range.hpp"
 #include "filter.hpp"
+#include "ivf_filter.hpp"
 
 using namespace vdb;
 
@@ -262,6 +263,13 @@ struct FilterBufs {
     DevBuf list{"filter.list"}, seg{"filter.seg"}, count{"filter.count"};
 };
 
+// the installed filter of an IVF-Flat handle (ivf_filter.inc): the allow words in LIST order, the masked copies of the panel space's
+// accumulator inits and the admitted count; every buffer sized exactly (ivf_filter_bytes)        (freed and dropped as FilterBufs, and
+// by any vdb_ivf_add*, vdb_ivf_set_centroids and vdb_ivf_train)
+struct IvfFilterBufs {
+    DevBuf words{"ivf_filter.words"}, bias_f{"ivf_filter.bias_f"}, bias8_f{"ivf_filter.bias8_f"}, count{"ivf_filter.count"};
+};
+
 // (struct Options -- everything vdb_set_option writes -- is in scan_plan.hpp: the launch rules of the flat scans read it)
 
 void release_pins(vdb_index_s *h);       // (the pinned staging blocks of upload_rows)
@@ -301,6 +309,7 @@ struct vdb_index_s {
     Workspace ws;
     RangeBufs range;
     FilterBufs filter;
+    IvfFilterBufs ivf_filter;
     Options opt;                            // what vdb_set_option has set; every other member is the library's own state
     int rows8_pitch = 0;
     bool i8_ok = false;
@@ -393,6 +402,9 @@ struct vdb_index_s {
     unsigned filter_kind = 0;                // kind_of the handle at install
     int64_t filter_count = 0;                // rows it admits
     int64_t filter_cand = 0;                 // (query, row) pairs the last sparse-route search scored
+    // the installed filter of an IVF-Flat handle (ivf_filter.inc), dropped with the flat one (filter_drop)
+    bool ivf_filter_valid = false;
+    int64_t ivf_filter_count = 0;            // rows it admits
     // vdb_destroy has set the device, synchronised it, dropped the graph and destroyed `coarse` (whose ws.small is a view into
     // plan.ivf_zero); the buffer groups free themselves after this body
     ~vdb_index_s() {
@@ -527,7 +539,7 @@ void refuse_options_set(const vdb_index_s *h, const char *what, unsigned kind) {
 }
 
 template <class F>
-void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); f(h->range); f(h->filter); }
+void for_each_group(vdb_index_s *h, F &&f) { f(h->rows); f(h->scan); f(h->kept); f(h->lists); f(h->plan); f(h->codes); f(h->lsh_ws); f(h->knng_ws); f(h->ws); f(h->range); f(h->filter); f(h->ivf_filter); }
 
 // every byte of device memory the handle holds (its ws.small may be a view into plan.ivf_zero: not counted twice)
 size_t handle_bytes(vdb_index_s *h) {
@@ -575,15 +587,17 @@ void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st);       // lsh_tab
 inline bool pq_on(const vdb_index_s *h) { return h->pq.M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
-// an installed filter goes (filter.inc installs and uses it).  Its buffers may still be read by a search on a caller's stream.
+// an installed filter goes (filter.inc installs and uses it; an IVF-Flat handle's: ivf_filter.inc).  Its buffers may still be read
+// by a search on a caller's stream.
 void filter_drop(vdb_index_s *h) {
-    if (group_bytes(h->filter) > 0) {
+    if (group_bytes(h->filter) + group_bytes(h->ivf_filter) > 0) {
         set_device(h->device);
         (void)hipDeviceSynchronize();
         group_release(h->filter);
+        group_release(h->ivf_filter);
     }
-    h->filter_valid = h->filter_has_list = false;
-    h->filter_count = 0;
+    h->filter_valid = h->filter_has_list = h->ivf_filter_valid = false;
+    h->filter_count = h->ivf_filter_count = 0;
 }
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
@@ -1514,4 +1528,5 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 #include "range.inc"
 #include "filter.inc"
 #include "debug_ivf.inc"
+#include "ivf_filter.inc"      // (behind ivf.inc, which debug_ivf.inc ends with)
 #include "multi.inc"

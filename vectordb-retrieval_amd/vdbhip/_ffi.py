@@ -117,6 +117,11 @@ SIGNATURES = {
     "vdb_filter_count": (c_int, [c_void_p, POINTER(c_int64)]),
     "vdb_search_filtered": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "vdb_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_filter_set": (c_int, [c_void_p, c_void_p, c_int64]),
+    "vdb_ivf_filter_set_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "vdb_ivf_filter_count": (c_int, [c_void_p, POINTER(c_int64)]),
+    "vdb_ivf_search_filtered": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "vdb_ivf_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),

@@ -14,6 +14,7 @@ FAISS: 25 iterations, seed 1234, at most 256 training points per centroid.
 """
 from __future__ import annotations
 
+import ctypes
 import re
 from typing import Any, Optional, Tuple
 
@@ -57,9 +58,11 @@ class IVFFlatIndex(_Handle):
         self.is_trained = False
         self.ntotal = 0
         self.nprobe = 1
+        self.id_base = 0
 
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
         x = self._rows(x)
+        self._filter_key = None
         _ffi.check(self._lib.vdb_ivf_train(self._handle(), self.nlist, _ffi.ptr(x), x.shape[0], int(niter), int(seed),
                                            int(max_points_per_centroid)), build_time=True)
         self.is_trained = True
@@ -69,6 +72,7 @@ class IVFFlatIndex(_Handle):
         c = _ffi.as_f32_c(centroids)
         if c.shape != (self.nlist, self.dim):
             raise ValueError(f"expected ({self.nlist}, {self.dim}) centroids, got {c.shape}")
+        self._filter_key = None
         _ffi.check(self._lib.vdb_ivf_set_centroids(self._handle(), _ffi.ptr(c), self.nlist), build_time=True)
         self.is_trained = True
         self.ntotal = 0
@@ -84,12 +88,14 @@ class IVFFlatIndex(_Handle):
         for this corpus and these centroids) skips the nearest-centroid pass: what loading a persisted index does."""
         x = self._rows(x)
         lor = None if list_of_row is None else self._list_ids(list_of_row, x.shape[0])
+        self._filter_key = None
         try:
             if lor is None:
                 _ffi.check(self._lib.vdb_ivf_add(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base)), build_time=True)
             else:
                 _ffi.check(self._lib.vdb_ivf_add_assigned(self._handle(), _ffi.ptr(x), x.shape[0], int(id_base), _ffi.ptr(lor)),
                            build_time=True)
+            self.id_base = int(id_base)
         finally:
             self._sync_ntotal()
 
@@ -122,6 +128,54 @@ class IVFFlatIndex(_Handle):
         """Per-shard partial top-k (float64 order keys + global ids) among the probed lists; device pointers."""
         _ffi.check(self._lib.vdb_ivf_search_partial_device(self._handle(), q_ptr, int(nq), int(k), keys_ptr, ids_ptr,
                                                            stream or None))
+
+    # -- filtered search (vdb_ivf_filter_*, vdb_ivf_search_filtered): the k nearest rows among the admitted rows of the probed lists.
+    #    IVF-Flat on one GPU; the library refuses the coded subclasses and a multi-device index, and the error comes through ----
+    _filter_key = None       # (object, ntotal) of the filter `ensure_filter` installed last; any call that drops the filter clears it
+
+    def set_filter(self, allowed, nbits: Optional[int] = None) -> None:
+        """Install the rows a filtered search may return: a bool array of length ntotal (row numbers in insertion order over
+        all adds, NOT list order), an integer array of ids (id_base + row; duplicates allowed, out of range raises ValueError),
+        or packed uint32 words with `nbits=` (_ffi.pack_allow_bits).  Any add, reset, set_option, train or set_centroids drops
+        the filter; set_nprobe keeps it."""
+        self._filter_key = None
+        words = _ffi.pack_allow_bits(allowed, self.ntotal, self.id_base, nbits)
+        _ffi.check(self._lib.vdb_ivf_filter_set(self._handle(), _ffi.ptr(words), self.ntotal), build_time=True)
+
+    def set_filter_device(self, words_ptr: int, nbits: int, stream: int = 0) -> None:
+        """Packed uint32 words in device memory of this index's GPU; runs on `stream` and waits for it once."""
+        self._filter_key = None
+        _ffi.check(self._lib.vdb_ivf_filter_set_device(self._handle(), words_ptr, int(nbits), stream or None), build_time=True)
+
+    def ensure_filter(self, allowed) -> None:
+        """`set_filter(allowed)` unless that very object was installed last on these rows (identity and ntotal, not content)."""
+        key = self._filter_key
+        if key is not None and key[0] is allowed and key[1] == self.ntotal:
+            return
+        self.set_filter(allowed)
+        self._filter_key = (allowed, self.ntotal)
+
+    def clear_filter(self) -> None:
+        self._filter_key = None
+        _ffi.check(self._lib.vdb_filter_clear(self._handle()))
+
+    @property
+    def filter_count(self) -> int:
+        """Rows the installed filter admits."""
+        n = ctypes.c_int64(0)
+        _ffi.check(self._lib.vdb_ivf_filter_count(self._handle(), ctypes.byref(n)))
+        return int(n.value)
+
+    def search_filtered(self, queries: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` among the admitted rows of the probed lists: same keys, order and padding (fewer than k admitted rows pad)."""
+        q = self._queries(queries)
+        D, I = _pair(q.shape[0], k)
+        _ffi.check(self._lib.vdb_ivf_search_filtered(self._handle(), _ffi.ptr(q), q.shape[0], int(k), _ffi.ptr(D), _ffi.ptr(I)))
+        return D, I
+
+    def search_filtered_device(self, q_ptr: int, nq: int, k: int, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
+        _ffi.check(self._lib.vdb_ivf_search_filtered_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
 
 
 class IVFSQ8Index(IVFFlatIndex):
@@ -214,6 +268,16 @@ class HipApproximateSearch(RawAlgorithm):
         self.device = _resolve_device(device, kwargs.get("device_ids"))
         self.index: Optional[IVFFlatIndex] = None
         parse_index_key(index_type)                          # fail at construction, like a bad factory string
+
+    def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`allowed` (None: every row): a bool mask over the rows, an integer id array or anything else IVFFlatIndex.set_filter
+        takes -- the k nearest among those rows of the probed lists, same conventions and padding.  The same array object is
+        installed once.  "IVF<nlist>,Flat" only: the library refuses the call on an SQ8 index."""
+        if allowed is None:
+            return super().batch_search(queries, k)
+        self._require_built()
+        self.index.ensure_filter(allowed)
+        return self.index.search_filtered(np.asarray(queries).astype(np.float32), k)
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         self.vectors = np.asarray(vectors).astype(np.float32)
@@ -327,6 +391,19 @@ class HipIVFSearcher(FaissStyleSearcher):
         if self.adc_max_batch is not None:
             self.index.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
             self.index.adc_max_batch = self.adc_max_batch
+
+    def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`allowed` (None: every row): what IVFFlatIndex.set_filter takes -- the k nearest among those rows of the probed lists,
+        in this searcher's conventions (queries normalised for cosine, distances negated for cosine / ip).  The same array
+        object is installed once.  An IVF-Flat artifact only: the library refuses the call on the coded indexes."""
+        if allowed is None:
+            return super().batch_search(queries, k)
+        self._require_attached()
+        self.index.ensure_filter(allowed)
+        d, i = self.index.search_filtered(self._prepare_query(queries), k)
+        if self.metric in {"cosine", "ip"}:
+            d = -d
+        return d.astype(np.float32), i.astype(np.int64)
 
 
 register_algorithm("HipApproximateSearch", HipApproximateSearch)
