@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 typedef int int4v __attribute__((ext_vector_type(4)));
@@ -486,6 +487,188 @@ __global__ __launch_bounds__(512, 2) void loop16p(const int4v *A, const int4v *B
     }
 }
 
+// ---- loop16p<0> with the PRODUCTION hand-over from stage to stage, and the stage ring that removes it (round 9) ----
+// The pipelined rows above leave out what scan_i8x16_batch_loop did between a stage's last MFMA and the next stage's first: the
+// biases of a stage came through registers (a global load with the stage issue, a wait and a ds_write before the barrier), the stage
+// issue stood behind the barrier and six LDS reads and their latency behind that, in all eight waves at once; and every second
+// stage a bin flush (8 swizzles, ~70 vector instructions, 8 stores) stood behind step 0, again in all waves at once.
+// RING3 0: that hand-over ("old").  RING3 1: three buffers, the stage after next issued behind step 0 with its biases by 4-byte
+// LDS-DMA, a full wait and the barrier at the end of a stage, tile 0 of the next stage read by the last step ("ring3").
+// FSTAG 1: waves 4-7 flush between the halves of step 1.
+template <int RING3, int FSTAG>
+__global__ __launch_bounds__(512, 2) void loop16r(const int4v *A, const int4v *B, int *out, unsigned long long *clk, int iters) {
+    constexpr int NT = 512, ST = 8, CB = 8, kStage = ST * 4 * 64, NBUF = RING3 ? 3 : 2;
+    __shared__ int4v lds[NBUF * kStage + NBUF * 64];        // the stages, then 1 KiB of biases per stage
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < NBUF * kStage + NBUF * 64; i += NT) lds[i] = A[i % kLdsVec];
+    int4v b[CB][2];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) b[cb][ks] = B[(((wave * CB + cb) * 2 + ks) % 128) * 64 + lane];
+    __syncthreads();
+    int m1[CB], m2[CB], q[CB], M1[CB / 2], M2[CB / 2];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) m1[cb] = m2[cb] = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < CB / 2; ++j) M1[j] = M2[j] = 0x7fffffff;
+    const bool late_flush = FSTAG == 1 && wave >= 4;      // (scalar: wave is)
+    const bool odd = (lane & 16) != 0;
+    const unsigned id_hi = odd ? 16u : 0u;
+    int4v acc[2][2][CB], fr[2][4], cin[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) acc[1][rb][cb] = int4v{0x1fffffff, 0x1fffffff, 0x1fffffff, 0x1fffffff};
+    const int *bias_g = reinterpret_cast<const int *>(B);
+    int *bias_l = reinterpret_cast<int *>(lds + NBUF * kStage);
+    int stage_b = 0;
+    auto issue = [&](int st, int buf) {
+        const int4v *src = A + (size_t)(st % (kLdsVec / kStage)) * kStage;
+        int4v *dst = lds + buf * kStage;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int p = wave + i * 8;
+            __builtin_amdgcn_global_load_lds(
+                reinterpret_cast<const __attribute__((address_space(1))) void *>(reinterpret_cast<uintptr_t>(src + p * 64 + lane)),
+                reinterpret_cast<__attribute__((address_space(3))) void *>(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst + p * 64))),
+                16, 0, 0);
+        }
+        const int *bsrc = bias_g + (size_t)(st % 64) * 256;
+        if (RING3) {
+            const int j = wave & 3;
+            __builtin_amdgcn_global_load_lds(
+                reinterpret_cast<const __attribute__((address_space(1))) void *>(reinterpret_cast<uintptr_t>(bsrc + j * 64 + lane)),
+                reinterpret_cast<__attribute__((address_space(3))) void *>(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(bias_l + buf * 256 + j * 64))),
+                4, 0, 0);
+        } else if (tid < 256) {
+            stage_b = bsrc[tid];
+        }
+    };
+    auto bias_store = [&](int buf) {
+        if (tid < 256) bias_l[buf * 256 + tid] = stage_b;
+    };
+    auto read_tile = [&](int p, const int4v *ab, const int4v *cb_, int t) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) fr[p][v] = ab[t * 256 + v * 64];
+        cin[p][0] = cb_[t * 8];
+        cin[p][1] = cb_[t * 8 + 1];
+    };
+    int *fo = out + (size_t)blockIdx.x * NT + tid;
+    auto flush = [&]() {                                    // flush_bin of scan_i8x16_body
+#pragma unroll
+        for (int j = 0; j < CB / 2; ++j) {
+            const int p1 = __builtin_amdgcn_ds_swizzle(odd ? m1[2 * j] : m1[2 * j + 1], 0x401F);
+            const int p2 = __builtin_amdgcn_ds_swizzle(odd ? m2[2 * j] : m2[2 * j + 1], 0x401F);
+            const int a1 = odd ? m1[2 * j + 1] : m1[2 * j], a2 = odd ? m2[2 * j + 1] : m2[2 * j];
+            const int b1 = imin(a1, p1), b2 = imin(imax(a1, p1), imin(a2, p2));
+            __builtin_nontemporal_store(b1, fo);
+            __builtin_nontemporal_store(b2, fo);
+            M2[j] = imin(imed3(M1[j], M2[j], b1), b2);
+            M1[j] = imin(M1[j], b1);
+        }
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) m1[cb] = m2[cb] = 0x7fffffff;
+    };
+    const int nstage = iters * (kLdsVec / kStage);
+    issue(0, 0);
+    if (RING3) issue(1, 1);
+    else bias_store(0);
+    __syncthreads();
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(lds);
+    const unsigned char *pa = base + lane * 16, *pb = base + NBUF * kStage * 16 + (lane >> 4) * 32;
+    int buf = 0;
+    const Stamp s0 = stamp_now();
+    if (RING3) read_tile(0, reinterpret_cast<const int4v *>(pa), reinterpret_cast<const int4v *>(pb), 0);
+    for (int st = 0; st < nstage; ++st) {
+        const int nbuf = buf + 1 == NBUF ? 0 : buf + 1, ibuf = nbuf + 1 == NBUF ? 0 : nbuf + 1;
+        const int hop = st + 1 < nstage ? nbuf - buf : 0;
+        const bool flush_due = st > 0 && (st & 1) == 0;
+        if (!RING3) {
+            issue(st + 1, nbuf);
+            pa = base + buf * (kStage * 16) + lane * 16;
+            pb = base + NBUF * kStage * 16 + buf * 1024 + (lane >> 4) * 32;
+        }
+        const int4v *ab = reinterpret_cast<const int4v *>(pa), *cb_ = reinterpret_cast<const int4v *>(pb);
+        if (!RING3) read_tile(0, ab, cb_, 0);
+#pragma unroll
+        for (int t = 0; t < ST; ++t) {
+            const int p = t & 1, o = p ^ 1;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb)
+                    acc[p][rb][cb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fr[p][rb], b[cb][0], cin[p][rb], 0, 0, 0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                const int t1 = imin(imin(acc[o][0][cb][0], acc[o][0][cb][1]), acc[o][0][cb][2]);
+                const int t2 = imin(imin(acc[o][0][cb][3], acc[o][1][cb][0]), acc[o][1][cb][1]);
+                q[cb] = imin(imin(imin(acc[o][1][cb][2], acc[o][1][cb][3]), t1), t2);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(q[cb]));
+            if (t == 1 && flush_due && late_flush) flush();
+            if (RING3 && t == ST - 1) {
+                pa += hop * (kStage * 16);
+                pb += hop * 1024;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (t + 1 < ST) read_tile(o, ab, cb_, t + 1);
+            else if (RING3) read_tile(o, reinterpret_cast<const int4v *>(pa), reinterpret_cast<const int4v *>(pb), 0);
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb)
+                    acc[p][rb][cb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fr[p][2 + rb], b[cb][1], acc[p][rb][cb], 0, 0, 0);
+            const unsigned idv = (unsigned)((t + ST - 1) % ST) | id_hi;
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) {
+                const int v = (int)(((unsigned)q[cb] << 6) | idv);
+                m2[cb] = imed3(m1[cb], m2[cb], v);
+                m1[cb] = imin(m1[cb], v);
+            }
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 10; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(m1[cb]), "+v"(m2[cb]));
+            if (RING3 && t == 0) issue(st + 2, ibuf);
+            if (t == 0 && flush_due && !late_flush) flush();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!RING3) bias_store(nbuf);
+        buf = nbuf;
+        __syncthreads();
+    }
+    const Stamp s1 = stamp_now();
+    int r = 0;
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) r += m1[cb] + m2[cb] + acc[1][1][cb][2];
+#pragma unroll
+    for (int j = 0; j < CB / 2; ++j) r += M1[j] + M2[j];
+    out[blockIdx.x * NT + tid] = r;
+    if (lane == 0) {
+        clk[((size_t)blockIdx.x * (NT / 64) + wave) * 2] = s1.cyc - s0.cyc;
+        clk[((size_t)blockIdx.x * (NT / 64) + wave) * 2 + 1] = s1.real - s0.real;
+    }
+}
+
 struct Result { float ms; double cyc, ghz; };
 
 template <class K>
@@ -511,7 +694,9 @@ Result run(K kernel, int threads, const int4v *dA, const int4v *dB, int *dO, uns
     return best;
 }
 
-int main() {
+// no argument: every row; "ring3": only the round-9 rows (the production hand-over against the stage ring), alternating, 5 repeats
+int main(int argc, char **argv) {
+    const bool only_ring = argc > 1 && !strcmp(argv[1], "ring3");
     const int nblk = 256 * 4, iters = 300;
     std::mt19937 rng(1);
     std::gamma_distribution<float> gm(0.6f, 40.f);
@@ -545,6 +730,7 @@ int main() {
         };
 #define R32(CB, WPS, EPI, G, label) report("32x32x32", 32 * CB, WPS, label, run(loop32<CB, WPS, EPI, G>, 256 * WPS, dA, dB, dO, dC, nblk, iters, e0, e1));
 #define R16(CB, WPS, EPI, G, label) report("16x16x64", 16 * CB, WPS, label, run(loop16<CB, WPS, EPI, G>, 256 * WPS, dA, dB, dO, dC, nblk, iters, e0, e1));
+        if (!only_ring) {
         R32(2, 2, 0, 4, "bare")   R16(4, 2, 0, 4, "bare")
         R32(2, 2, 1, 4, "quads")  R16(4, 2, 1, 4, "quads")
         R32(2, 2, 1, 8, "octs")   R16(4, 2, 1, 8, "octs")
@@ -574,6 +760,15 @@ int main() {
         R16P(0, "octs +bar+DMA pipelined")
         R16P(1, "octs +bar+DMA pipel+stag")
         R16S(3, "octs +bar+DMA+stag")
+        }
+        // round 9: the pipelined loop with the production hand-over and bin flush (old), the stage ring (new), the ring with the
+        // flush of waves 4-7 half a step behind; old and new alternate
+#define R16R(RING3, FSTAG, label) report("16x16x64", 128, 2, label, run(loop16r<RING3, FSTAG>, 512, dA, dB, dO, dC, nblk, iters, e0, e1));
+        for (int rep = 0; rep < (only_ring ? 5 : 3); ++rep) {
+            R16R(0, 0, "pipel. prod hand-over")
+            R16R(1, 0, "pipel. ring3")
+            R16R(1, 1, "pipel. ring3 +fstag")
+        }
     }
     return 0;
 }

@@ -19,14 +19,24 @@
 //     merge, and each stores every other column block of the wave -- ~40 vector operations per 16 tiles beside ~800 of select.
 //
 // Two loops share the set-up, the staging, the bin flush and the superbin epilogue of scan_i8x16_body:
-//   * the batch shapes (8 waves, ring of 2, rolled stages) run scan_i8x16_batch_loop: one code path for all waves, the select of
+//   * the batch shapes (8 waves, plan ring 2, rolled stages) run scan_i8x16_batch_loop: one code path for all waves, the select of
 //     tile t-1 and the LDS reads of tile t+1 placed instruction by instruction between the MFMAs of tile t (round 8; sift1m scan
-//     0.843 -> 0.813 ms, profiles/r08_scan_interleaved_ab.txt).  Option "scan_prio" does not reach this loop: there is no early /
-//     late half to prefer.
+//     0.843 -> 0.813 ms, profiles/r08_scan_interleaved_ab.txt), over a ring of three stage buffers that lets a stage start with
+//     MFMAs whose operands are already in registers (round 9; scan_ring.hpp, profiles/r09_scan_ring3_ab.txt).  Option "scan_prio"
+//     does not reach this loop: there is no early / late half to prefer.
 //   * the serving shapes (1 / 2 / 4 waves, rings of 4 / 8, unrolled stages) keep the loop of round 4: per tile an MFMA phase and a
 //     select phase fenced by sched_barrier, the two halves of a workgroup in anti-phase.
 #pragma once
 #include "scan_i8.hpp"
+#include "scan_ring.hpp"
+
+// (a diagnostic build defines these to read the clock at four points of the batch loop -- 0: behind the last MFMA of a stage, 1: before
+//  the first MFMA of a stage, 2 / 3: entry and exit of a bin flush; scripts/microbench/stamp_i8x16.hip)
+#ifndef VDB_X16_STAMP
+#define VDB_X16_STAMP_BEGIN
+#define VDB_X16_STAMP(point) ((void)0)
+#define VDB_X16_STAMP_END
+#endif
 
 namespace vdb {
 
@@ -38,10 +48,11 @@ __device__ __forceinline__ int swap16(int v) { return __builtin_amdgcn_ds_swizzl
 // KS2: 64-dim k-steps (D padded to 64 or 128); ST: 32-row tiles per LDS stage; CB: 16-query column blocks per wave (8 -> 128
 // queries per wave, 4 -> 64); NWAVES, RING, AUX as scan_i8_kernel.  Octs only (QueryBatchInfo.i8_mode bit 2 is set by
 // the host for an index in this layout).
-template <int KS2, int ST, int RING>
-constexpr int scan_i8x16_lds_bytes() { return RING * (ST * 2 * KS2 * 64 * 16 + ST * 32 * 4); }
+// NWAVES, RING and CB name the form as its plan key does; the batch forms keep kX16BatchRing buffers behind RING = 2 (scan_ring.hpp).
+template <int KS2, int ST, int RING, int CB, int NWAVES>
+constexpr int scan_i8x16_lds_bytes() { return x16_lds_bytes(KS2, ST, CB, NWAVES, RING); }
 
-// ---- the batch loop (8 waves, ring of 2, rolled stages: ST = 8 with CB = 8 or 4, ST = 4 with CB = 8), software-pipelined per wave ----
+// ---- the batch loop (8 waves, plan ring 2, rolled stages: ST = 8 with CB = 8 or 4, ST = 4 with CB = 8), software-pipelined per wave ----
 // One code path for all eight waves.  A step issues the MFMAs of tile t and, in their gaps, the oct select of tile t-1 and the LDS
 // reads of tile t+1: behind every MFMA the vector-issue instructions that fit its 16 cycles (an MFMA holds the SIMD's vector issue
 // for 8 of them, an ordinary VALU instruction for 4), fixed with sched_group_barrier.  Packed in whole phases of ~500 cycles (the
@@ -53,6 +64,14 @@ constexpr int scan_i8x16_lds_bytes() { return RING * (ST * 2 * KS2 * 64 * 16 + S
 //   * the first step retires a "previous tile" of +inf scores (as the late half of the body always has); the last tile is retired
 //     after the loop.  Bin (span, h) is flushed once the select of its tile 15 is done: behind the step of tile 0 of the next span,
 //     or in the drain.
+// The hand-over from stage to stage keeps the stream going (round 9).  The stages live in a ring of kX16BatchRing = 3 buffers whose
+// rules are scan_ring.hpp (tests/host/scan_ring_main.cpp walks them): stage s + 2 is issued during stage s, behind the MFMAs of step
+// 0, panels and biases both by LDS-DMA; at the end of a stage every wave waits for ALL of its memory operations -- its pieces are a
+// whole stage old -- and takes the one barrier.  That barrier certifies the stage after next, so the next stage is readable all
+// through this one: the last step reads its tile 0 into the fragment set it leaves free, and the step behind the barrier starts
+// with MFMAs whose operands are in registers.  Before, the barrier was followed by the stage issue (address arithmetic, four DMA
+// pieces, a bias load), six LDS reads and their latency, in all eight waves at once, and preceded by a bias store that waited for
+// its load.
 template <int N_MFMA, int N_VALU, int N_DS>
 __device__ __forceinline__ void x16_gap_pattern() {
     constexpr int R = (N_VALU + N_DS + N_MFMA - 1) / N_MFMA;      // vector-issue instructions behind each MFMA
@@ -69,13 +88,18 @@ __device__ __forceinline__ void x16_gap_pattern() {
     }
 }
 
-template <int KS2, int ST, int CB, class StageIssue, class BiasStore, class FlushBin>
+// (Measured and not kept: waves 4 - 7 flushing a bin half a step behind waves 0 - 3, between the halves of step 1.  The two waves of
+//  a SIMD are not in step to begin with -- the older wave runs up to half a stage ahead of its partner -- and the second flush site
+//  cost more than it hid: profiles/r09_scan_ring3_ab.txt, profiles/r09_mfma_i8_ring3.txt.)
+template <int KS2, int ST, int CB, class StageIssue, class FlushBin>
 __device__ __forceinline__ void scan_i8x16_batch_loop(const unsigned char *smem, const int4v (&bq)[CB][KS2], int (&m1)[CB], int (&m2)[CB],
                                                       int nstages, int64_t span0, int lane, StageIssue &&stage_issue,
-                                                      BiasStore &&stage_bias_store, FlushBin &&flush_bin) {
+                                                      FlushBin &&flush_bin) {
     constexpr int NV = 2 * KS2, kStageVec = ST * NV * 64, TPS = kTilesPerSpan, SPS = TPS / ST;
     constexpr int NM = 2 * KS2 * CB, NH = NM / 2;                 // MFMAs per tile, per half step
+    constexpr int R = kX16BatchRing, kABytes = kStageVec * 16, kBBytes = ST * 32 * 4;
     static_assert(ST % 2 == 0 && TPS % ST == 0, "tile parity must be static in the unrolled stage");
+    static_assert(R >= 3, "a ring of 2 cannot read the next stage ahead of the barrier (scan_ring.hpp)");
     const int g = lane >> 4;
     const unsigned id_hi = (g & 1) ? 16u : 0u;
     int4v acc[2][2][CB], fr[2][NV], cin[2][2];                    // [tile parity]
@@ -117,42 +141,62 @@ __device__ __forceinline__ void scan_i8x16_batch_loop(const unsigned char *smem,
             m1[cb] = imin(m1[cb], v);
         }
     };
+    VDB_X16_STAMP_BEGIN
+    // this stage's fragments and biases: one base address each, moved from buffer to buffer by a wave-uniform offset
+    const unsigned char *pa = smem + lane * 16, *pb = smem + R * kABytes + g * 32;
+    int buf = 0;
+    read_tile(0, reinterpret_cast<const int4v *>(pa), reinterpret_cast<const int4v *>(pb), 0);
     for (int st = 0; st < nstages; ++st) {
-        const int buf = st & 1;
-        if (st + 1 < nstages) stage_issue(st + 1, buf ^ 1);
-        const int4v *A = reinterpret_cast<const int4v *>(smem + buf * (kStageVec * 16)) + lane;
-        const int4v *B4 = reinterpret_cast<const int4v *>(smem + 2 * kStageVec * 16 + buf * (ST * 32 * 4)) + g * 2;
+        const int nbuf = buf + 1 == R ? 0 : buf + 1, ibuf = nbuf + 1 == R ? 0 : nbuf + 1;   // stage st + 1; stage st + 2 == st - 1
+        const int hop = ring_reads_ahead(st, nstages) ? nbuf - buf : 0;
+        const bool issue = ring_issues(st, nstages, R);
+        const int4v *A = reinterpret_cast<const int4v *>(pa), *B4 = reinterpret_cast<const int4v *>(pb);
         const int ts0 = (st % SPS) * ST;
-        read_tile(0, A, B4, 0);
+        const bool flush_due = st > 0 && ts0 == 0;
 #pragma unroll
         for (int t = 0; t < ST; ++t) {
             const int p = t & 1, o = p ^ 1;
             // first half: the MFMAs that take the bias claim the new set, the min trees free the old one
             __builtin_amdgcn_sched_barrier(0);
+            if (t == 0) VDB_X16_STAMP(1);
             mfma_half(p, 0);
             min_trees(o);
             x16_gap_pattern<NH, 4 * CB, 0>();
             __builtin_amdgcn_sched_barrier(0);
             // (empty statements that use the select's results where they are due: instruction selection is free to order pure
-            //  arithmetic across a sched_barrier, and with a branch further down the stage -- the flush, the bias store -- the
+            //  arithmetic across a sched_barrier, and with a branch further down the stage -- the flush, the stage issue -- the
             //  compiler sinks the whole stage's select chains below it and spills the accumulators they wait for)
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(q[cb]));
-            // second half: the remaining MFMAs, the top-2 folds of tile t-1, the LDS reads of tile t+1
+            // second half: the remaining MFMAs, the top-2 folds of tile t-1, the LDS reads of tile t+1 -- behind the last step
+            // tile 0 of the next stage, whose buffer the barrier before last certified
+            if (t == ST - 1) {        // (two additions outside the counted gaps)
+                pa += hop * kABytes;
+                pb += hop * kBBytes;
+            }
             __builtin_amdgcn_sched_barrier(0);
             if (t + 1 < ST) read_tile(o, A, B4, t + 1);
+            else read_tile(o, reinterpret_cast<const int4v *>(pa), reinterpret_cast<const int4v *>(pb), 0);
             mfma_half(p, 1);
             folds((ts0 + t + TPS - 1) % TPS);
             x16_gap_pattern<NH, 3 * CB + 1, NV + 2>();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb) asm volatile("" : "+v"(m1[cb]), "+v"(m2[cb]));
-            if (t == 0 && st > 0 && ts0 == 0) flush_bin(span0 + st / SPS - 1);
+            if (t == ST - 1) VDB_X16_STAMP(0);
+            // the stage after next, into the buffer that the stage before this one read: behind the first MFMAs, not before them
+            if (t == 0 && issue) stage_issue(st + R - 1, ibuf);
+            if (t == 0 && flush_due) {
+                VDB_X16_STAMP(2);
+                flush_bin(span0 + st / SPS - 1);
+                VDB_X16_STAMP(3);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (st + 1 < nstages) stage_bias_store(buf ^ 1);
-        __syncthreads();
+        buf = nbuf;
+        __syncthreads();              // (a full wait on this wave's LDS-DMA, issued a stage ago, and the barrier)
     }
+    VDB_X16_STAMP_END
     min_trees((ST - 1) & 1);
     folds(TPS - 1);
     flush_bin(span0 + nstages / SPS - 1);
@@ -174,12 +218,16 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
     constexpr int UNR = (ST * CB <= 16) ? ST : 1;
     static_assert(TPS % ST == 0 && ST >= 2 && CB % 2 == 0 && NWAVES <= 8, "bad geometry");
     static_assert(RING >= 2 && RING <= 8 && (RING == 2 || ST % 2 == 0), "bad ring");
-    constexpr bool kDeep = RING > 2;
-    static_assert(scan_i8x16_lds_bytes<KS2, ST, RING>() == RING * (kStageVec * 16 + ST * 32 * 4), "LDS size");
+    // the batch forms run scan_i8x16_batch_loop over a ring of kX16BatchRing buffers behind their plan key's RING = 2 (scan_ring.hpp)
+    constexpr bool kBatch = x16_batch_form(ST, CB, NWAVES, RING);
+    static_assert(kBatch == (NWAVES == 8 && RING == 2 && UNR == 1), "the batch forms are the rolled 8-wave shapes");
+    constexpr int NBUF = x16_ring_buffers(ST, CB, NWAVES, RING);
+    constexpr bool kDeep = NBUF > 2;                      // biases arrive by LDS-DMA with the panels
+    static_assert(scan_i8x16_lds_bytes<KS2, ST, RING, CB, NWAVES>() == NBUF * (kStageVec * 16 + ST * 32 * 4), "LDS size");
     const int mode = a.info->i8_mode;
     if (!mode) return;                                    // this batch is served by the fp16 scan
     auto lds_a = [&](int buf) { return reinterpret_cast<int4v *>(smem + buf * (kStageVec * 16)); };
-    auto lds_b = [&](int buf) { return reinterpret_cast<int *>(smem + RING * kStageVec * 16 + buf * (ST * 32 * 4)); };
+    auto lds_b = [&](int buf) { return reinterpret_cast<int *>(smem + NBUF * kStageVec * 16 + buf * (ST * 32 * 4)); };
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -292,18 +340,28 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
         for (int cb = 0; cb < CB; ++cb) m1[cb] = m2[cb] = INF;
     };
 
-    if (kDeep) {
+    if (kBatch) {                               // scan_ring.hpp: the prologue fills all buffers but one, full wait, barrier -1
+#pragma unroll
+        for (int s = 0; s < kX16BatchRing - 1; ++s)
+            if (s < ring_prologue_stages(nstages, kX16BatchRing)) stage_issue(s, ring_buffer(s, kX16BatchRing));
+    } else if (kDeep) {
 #pragma unroll
         for (int s = 0; s < RING - 1; ++s) ring_issue(s);
     } else {
         stage_issue(0, 0);
     }
     stage_bias_store(0);
-    if (kDeep) ring_wait();
+    if (kDeep && !kBatch) ring_wait();
     else __syncthreads();
 
     if (a.nq_valid > 0 && q0 >= a.nq_valid) {   // every query column of this wave is padding: keep staging + barriers going
         for (int st = 0; st < nstages; ++st) {
+            if (kBatch) {                       // the same pieces and the same barriers as scan_i8x16_batch_loop
+                if (ring_issues(st, nstages, kX16BatchRing))
+                    stage_issue(ring_issue_stage(st, kX16BatchRing), ring_buffer(ring_issue_stage(st, kX16BatchRing), kX16BatchRing));
+                __syncthreads();
+                continue;
+            }
             if (kDeep) {
                 ring_issue(st + RING - 1);
                 ring_wait();
@@ -318,8 +376,8 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
         return;
     }
 
-    if constexpr (NWAVES == 8 && RING == 2 && UNR == 1) {          // the batch shapes
-        scan_i8x16_batch_loop<KS2, ST, CB>(smem, bq, m1, m2, nstages, span0, lane, stage_issue, stage_bias_store, flush_bin);
+    if constexpr (kBatch) {                                        // the batch shapes
+        scan_i8x16_batch_loop<KS2, ST, CB>(smem, bq, m1, m2, nstages, span0, lane, stage_issue, flush_bin);
     } else {                                                       // the serving shapes: the loop of round 4, as it was (not re-indented)
     int4v fr[NV], cin[2], acc[2][CB];
     auto read_phase = [&](const int4v *A_tile, const int4v *c_tile) {
@@ -420,7 +478,7 @@ __device__ __forceinline__ void scan_i8x16_body(const ScanI8Args &a, unsigned ch
 
 template <int KS2, int ST, int CB, int NWAVES = 8, int RING = 2, int AUX = 0>
 __global__ __launch_bounds__(NWAVES * 64, (NWAVES >= 4 ? 2 : 1)) void scan_i8x16_kernel(ScanI8Args a) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[scan_i8x16_lds_bytes<KS2, ST, RING>()];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[scan_i8x16_lds_bytes<KS2, ST, RING, CB, NWAVES>()];
     scan_i8x16_body<KS2, ST, CB, NWAVES, RING, AUX>(a, smem);
 }
 

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(NWAVES * 64, WPS) void scan_x16_kernel(ScanArgs a) 
 template <bool W128, int NWAVES, int STF, int STI, int CBI, int RING, int AUX>
 __global__ __launch_bounds__(NWAVES * 64, (NWAVES >= 4 ? 2 : 1)) void scan_pair_x16_kernel(ScanArgs a16, ScanI8Args a8) {
     constexpr int KF = W128 ? 4 : 2, KI = W128 ? 2 : 1;
-    constexpr int kLds16 = scan_x16_lds_bytes<KF, STF>(), kLds8 = scan_i8x16_lds_bytes<KI, STI, RING>();
+    constexpr int kLds16 = scan_x16_lds_bytes<KF, STF>(), kLds8 = scan_i8x16_lds_bytes<KI, STI, RING, CBI, NWAVES>();
     __shared__ __attribute__((aligned(16))) unsigned char smem[kLds16 > kLds8 ? kLds16 : kLds8];
     if (a8.info->i8_mode) scan_i8x16_body<KI, STI, CBI, NWAVES, RING, AUX>(a8, smem);
     else scan_x16_body<KF, NWAVES, STF, 256>(a16, smem);
