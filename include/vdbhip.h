@@ -59,7 +59,8 @@ enum vdb_path { VDB_PATH_NONE = 0, VDB_PATH_EXACT_SCAN = 1, VDB_PATH_MFMA_SCAN =
                 VDB_PATH_PQ_ADC = 7 /* flat PQ: lookup-table (ADC) scan of the codes, then the select and exact refine of the MFMA scan */,
                 VDB_PATH_IVFPQ_ADC = 8 /* IVF-PQ: lookup-table (ADC) scan of the probed lists, then the exact re-score of the rows near the k-th score */,
                 VDB_PATH_RANGE = 9 /* vdb_range_search: bitmap prefilter (fp16 MFMA scan, or all rows), exact filter, emit in id order */,
-                VDB_PATH_FILTER_ROWS = 10 /* vdb_search_filtered, selective filter: exact top-k over the list of admitted rows alone */ };
+                VDB_PATH_FILTER_ROWS = 10 /* vdb_search_filtered, selective filter: exact top-k over the list of admitted rows alone */,
+                VDB_PATH_IVF_RANGE = 11 /* vdb_ivf_range_search: candidate bitmap from the list scans' bin minima (or every probed row), exact filter, emit in list order */ };
 
 typedef struct vdb_stats_s {
     int64_t ntotal;            /* rows indexed */
@@ -122,6 +123,8 @@ typedef struct vdb_stats_s {
  *   vdb_filter_clear                                     +     +    +     +    +      +         +        +       U
  *   vdb_ivf_filter_set(_device), vdb_ivf_filter_count,
  *     vdb_ivf_search_filtered(_device)                   +     U    U     U    U      +         U        U       U
+ *   vdb_ivf_range_search(_device),
+ *     vdb_ivf_range_results(_device)                     +     U    U     U    U      +         U        U       U
  *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
  *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
  *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
@@ -307,6 +310,35 @@ int vdb_ivf_filter_count(vdb_handle h, int64_t *n_allowed);      /* rows the ins
 int vdb_ivf_search_filtered(vdb_handle h, const float *q_host, int64_t nq, int k, float *D, int64_t *I);
 /* device pointers on the handle's GPU; enqueued on `stream`, NOT synchronised */
 int vdb_ivf_search_filtered_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float *D_dev, int64_t *I_dev, void *stream);
+
+/* ---- range search on IVF-Flat indexes -- replaces faiss.IndexIVFFlat.range_search: EVERY row of the probed lists within `radius` of
+ * each query, exactly -----------------------------------------------------------------------------------------------------------
+ * (vdb_range_search keeps refusing IVF handles: these are entry points of their own.)
+ * Per query the result is what vdb_ivf_search returns with the handle's current nprobe and k = all rows of the probed lists -- the same
+ * coarse choice, the same canonical float64 keys, the same returned D -- cut to the rows whose D satisfies D < radius (L2) or
+ * D > radius (IP); the ids are the rows' own (id_base + insertion row).  A NaN key passes neither comparison; +-inf radii are legal;
+ * an L2 radius <= 0 returns nothing (vdb_range_search's rules, word for word).
+ * The rows of a query come in ascending LIST-ORDER row: ascending list number, then ascending id inside a list (an add keeps
+ * insertion order inside a list).  No sort is involved; two runs return the same bytes, whichever route served them and whatever
+ * the slab size.  lims_host: nq + 1 offsets as for vdb_range_search; the result stays on the device, owned by the handle, until the
+ * next range search, any add, vdb_ivf_set_centroids, vdb_ivf_train, vdb_reset or vdb_set_option (vdb_ivf_set_nprobe keeps it: it
+ * is already materialised); it counts in bytes_resident / bytes_workspace and is freed by vdb_reset and vdb_destroy.
+ * vdb_ivf_range_results(_device) copies the result of the LAST range search out.  An installed IVF filter is ignored and left alone.
+ * How: per query slab (option "range_bitmap_mb", at most 16384 queries) the coarse search and the fp16 list scan of
+ * vdb_ivf_search run unchanged; every kept bin minimum that can stand for a score <= the query's threshold marks its quad, a bin
+ * whose kept minima all pass marks all its rows, in a bitmap [query][list-order row]; the marks are re-scored exactly, counted and
+ * emitted by the kernels of vdb_range_search.  The exact route marks every probed row instead (no scan): batches the list-major
+ * scan declines, and option "force_path" 1 / 3.  Every slab synchronises `stream` once.
+ * VDB_ERR_STATE: no centroids / not built / an empty index; vdb_ivf_range_results(_device) without a result.  VDB_ERR_INVALID:
+ * nq <= 0, a null pointer, a NaN radius.  VDB_ERR_UNSUPPORTED: the kinds of the table above, and any handle while option "graph" is 1.
+ * vdb_stats after a call: last_path = VDB_PATH_IVF_RANGE, last_nq, last_candidates = (query, row) pairs scored exactly,
+ * last_fallback_queries = queries for which every probed row was a candidate; with option "timing", last_scan_ms / last_tail_ms per slab.
+ * Not served: IVF-SQ8, IVF-PQ and multi-device handles, the int8 list scan, filtered range search, per-query radii. */
+int vdb_ivf_range_search(vdb_handle h, const float *q_host, int64_t nq, float radius, int64_t *lims_host);
+int vdb_ivf_range_results(vdb_handle h, float *D_host, int64_t *I_host);
+/* device pointers on the handle's GPU; lims_dev: nq + 1 int64; *total_host = lims[nq]; `stream` is synchronised once per slab */
+int vdb_ivf_range_search_device(vdb_handle h, const float *q_dev, int64_t nq, float radius, int64_t *lims_dev, int64_t *total_host, void *stream);
+int vdb_ivf_range_results_device(vdb_handle h, float *D_dev, int64_t *I_dev, void *stream);
 
 /* ---- row-sharded search (one process per GPU; partials exchanged with an RCCL all-gather) ---- */
 /* per-shard partial top-k: float64 order keys (L2: squared distance, IP: -score) and global ids,

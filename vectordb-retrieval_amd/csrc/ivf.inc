@@ -735,6 +735,7 @@ int vdb_ivf_set_centroids(vdb_handle hh, const float *centroids_host, int nlist)
         set_device(h->device);
         graph_reset(h);
         filter_drop(h);                        // (an installed filter describes the lists of the old centroids)
+        h->range_valid = false;                // (... and so does the last range result)
         ivf_install_centroids(h, centroids_host, nlist);
         h->ivf_built = false;
     });
@@ -765,6 +766,7 @@ int vdb_ivf_train(vdb_handle hh, int nlist, const float *x_host, int64_t n, int 
         graph_reset(h);
         set_device(h->device);
         filter_drop(h);
+        h->range_valid = false;
         const int Dm = h->dim, D4 = h->D4;
         // ---- sample (seeded partial Fisher-Yates), in draw order -----------------------------------
         const int64_t ns = std::min<int64_t>(n, (int64_t)max_points_per_centroid * nlist);
@@ -983,6 +985,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         // an installed filter (ivf_filter.inc) has one bit per row, and the rows change place: every add that passed its checks drops
         // it, an empty append too; a refused add leaves it with the index.  (The coded indexes above never hold one.)
         filter_drop(h);
+        h->range_valid = false;                // (the last range result, ivf_range.inc, goes the same way)
         if (!rows_change) return;
         set_device(h->device);
         const int Dm = h->dim, D4 = h->D4;

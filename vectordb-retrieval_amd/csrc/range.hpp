@@ -333,7 +333,9 @@ __global__ __launch_bounds__(256) void range_lims_kernel(RangeTailArgs a) {
 }
 
 // the filter's units once more: the survivors of a word are written behind those of the lanes (words) before it
-__global__ __launch_bounds__(256) void range_emit_kernel(RangeTailArgs a) {
+// (IDMAP: the rows are in list order and the id of row r is c.idmap[r] -- ivf_range_emit_kernel, ivf_range.hpp)
+template <bool IDMAP>
+__device__ __forceinline__ void range_emit_body(const RangeTailArgs &a) {
     const int lane = threadIdx.x & 63;
     const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (unit >= a.nq * a.S) return;
@@ -355,9 +357,10 @@ __global__ __launch_bounds__(256) void range_emit_kernel(RangeTailArgs a) {
         float d;
         (void)range_passes(a.c.metric, unsortable_f64(row_key<4>(a.c, row, qptr)), a.radius, &d);
         a.D[out] = d;
-        a.I[out] = a.c.id_base + row;
+        a.I[out] = IDMAP ? a.c.idmap[row] : a.c.id_base + row;
         ++out;
     }
 }
+__global__ __launch_bounds__(256) void range_emit_kernel(RangeTailArgs a) { range_emit_body<false>(a); }
 
 }  // namespace vdb

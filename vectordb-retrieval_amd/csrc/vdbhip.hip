@@ -39,6 +39,7 @@
 #include "range.hpp"
 #include "filter.hpp"
 #include "ivf_filter.hpp"
+#include "ivf_range.hpp"
 
 using namespace vdb;
 
@@ -392,7 +393,8 @@ struct vdb_index_s {
     // k-NN graph of a flat index (knng.inc; vdb_knng_build / vdb_knng_set): ntotal x degree local row numbers next to the float32 rows
     int knng_degree = 0;                     // 0 = no graph (any add and vdb_reset drop it)
     std::vector<int32_t> knng_entries;       // the entry rows knng_ws.knng_entry holds (knng_search_impl)
-    // the last range search (range.inc): `range` holds its result while range_valid (any add, vdb_reset and vdb_set_option drop it)
+    // the last range search (range.inc; on an IVF-Flat handle ivf_range.inc): `range` holds its result while range_valid (any add,
+    // vdb_reset, vdb_set_option, vdb_ivf_set_centroids and vdb_ivf_train drop it)
     bool range_valid = false;
     int64_t range_total = 0, range_nq = 0;   // lims[nq] and nq of that result
     int64_t range_cand = 0, range_fb = 0;    // (query, row) pairs scored exactly / queries for which every row was a candidate
@@ -1461,7 +1463,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
                 s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride + 1];
             }
         }
-        if (h->last.last_path == VDB_PATH_RANGE) {     // (the call read its counters back when it sized the result)
+        if (h->last.last_path == VDB_PATH_RANGE || h->last.last_path == VDB_PATH_IVF_RANGE) {     // (the call read its counters back when it sized the result)
             s.last_candidates = h->range_cand;
             s.last_fallback_queries = h->range_fb;
         }
@@ -1529,4 +1531,5 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
 #include "filter.inc"
 #include "debug_ivf.inc"
 #include "ivf_filter.inc"      // (behind ivf.inc, which debug_ivf.inc ends with)
+#include "ivf_range.inc"       // (likewise)
 #include "multi.inc"

@@ -18,7 +18,7 @@ import numpy as np
 
 VDB_OK, VDB_ERR_INVALID, VDB_ERR_STATE, VDB_ERR_HIP, VDB_ERR_NOMEM, VDB_ERR_UNSUPPORTED = range(6)
 METRIC_L2, METRIC_IP = 0, 1
-PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc", 8: "ivfpq_adc", 9: "range", 10: "filter_rows"}
+PATH_NAMES = {0: "none", 1: "exact_scan", 2: "mfma_scan", 3: "ivf", 4: "lsh", 5: "knng", 6: "lsh_tables", 7: "pq_adc", 8: "ivfpq_adc", 9: "range", 10: "filter_rows", 11: "ivf_range"}
 
 _LIB_NAME = "libvdbhip.so"
 _lib: Optional[ctypes.CDLL] = None
@@ -122,6 +122,10 @@ SIGNATURES = {
     "vdb_ivf_filter_count": (c_int, [c_void_p, POINTER(c_int64)]),
     "vdb_ivf_search_filtered": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "vdb_ivf_search_filtered_device": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_range_search": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "vdb_ivf_range_results": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "vdb_ivf_range_search_device": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p, POINTER(c_int64), c_void_p]),
+    "vdb_ivf_range_results_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "vdb_reserve": (c_int, [c_void_p, c_int64, c_int]),
     "vdb_stats": (c_int, [c_void_p, POINTER(Stats)]),
     "vdb_set_option": (c_int, [c_void_p, c_char_p, c_double]),

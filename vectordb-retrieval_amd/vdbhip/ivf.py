@@ -177,6 +177,31 @@ class IVFFlatIndex(_Handle):
         """All pointers are device memory on this index's GPU; asynchronous on `stream`."""
         _ffi.check(self._lib.vdb_ivf_search_filtered_device(self._handle(), q_ptr, int(nq), int(k), d_ptr, i_ptr, stream or None))
 
+    # -- range search (vdb_ivf_range_*): every row of the probed lists within a radius, in list order per query.  IVF-Flat on one
+    #    GPU; the library refuses the coded subclasses and a multi-device index, and the error comes through ----
+    def range_search(self, queries: np.ndarray, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lims int64 (nq + 1,), D float32, I int64): query q owns entries [lims[q], lims[q + 1]) -- the rows of its `nprobe`
+        probed lists with squared L2 distance < radius / inner product > radius (faiss.IndexIVFFlat.range_search), exact, in
+        ascending (list, id)."""
+        q = self._queries(queries)
+        lims = np.empty((q.shape[0] + 1,), np.int64)
+        _ffi.check(self._lib.vdb_ivf_range_search(self._handle(), _ffi.ptr(q), q.shape[0], float(np.float32(radius)), _ffi.ptr(lims)))
+        D, I = np.empty((int(lims[-1]),), np.float32), np.empty((int(lims[-1]),), np.int64)
+        _ffi.check(self._lib.vdb_ivf_range_results(self._handle(), _ffi.ptr(D), _ffi.ptr(I)))
+        return lims, D, I
+
+    def range_search_device(self, q_ptr: int, nq: int, radius: float, lims_ptr: int, stream: int = 0) -> int:
+        """Device pointers on this index's GPU; waits for `stream` (the result size must reach the host) and returns
+        lims[nq], the number of entries `range_results_device` will write."""
+        total = ctypes.c_int64(0)
+        _ffi.check(self._lib.vdb_ivf_range_search_device(self._handle(), q_ptr, int(nq), float(np.float32(radius)), lims_ptr,
+                                                         ctypes.byref(total), stream or None))
+        return int(total.value)
+
+    def range_results_device(self, d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """The (D, I) of the last range search of this index into device memory; asynchronous on `stream`."""
+        _ffi.check(self._lib.vdb_ivf_range_results_device(self._handle(), d_ptr, i_ptr, stream or None))
+
 
 class IVFSQ8Index(IVFFlatIndex):
     """Device-resident IVF<nlist>,SQ8 index (replaces faiss.index_factory(d, "IVFn,SQ8", metric): IndexIVFScalarQuantizer
@@ -278,6 +303,20 @@ class HipApproximateSearch(RawAlgorithm):
         self._require_built()
         self.index.ensure_filter(allowed)
         return self.index.search_filtered(np.asarray(queries).astype(np.float32), k)
+
+    def range_search(self, queries: np.ndarray, radius: float, sort: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """faiss.IndexIVFFlat.range_search in the raw conventions: (lims, D, I) of the rows of the probed lists with squared L2 <
+        radius / inner product > radius.  Per query the rows come in ascending (list, id); `sort="id"` orders them by id,
+        `sort="distance"` nearest first, by (D, id) -- both on the host.  "IVF<nlist>,Flat" only: the library refuses an SQ8 index."""
+        if sort not in (None, "id", "distance"):
+            raise ValueError(f"sort must be None, 'id' or 'distance', got {sort!r}")
+        self._require_built()
+        lims, d, i = self.index.range_search(_ffi.as_f32_queries(queries), radius)
+        if sort is not None and len(i):
+            owner = np.repeat(np.arange(len(lims) - 1), np.diff(lims))
+            order = np.lexsort((i, owner)) if sort == "id" else np.lexsort((i, d if self.metric == "l2" else -d, owner))
+            d, i = d[order], i[order]
+        return lims, d, i
 
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         self.vectors = np.asarray(vectors).astype(np.float32)
@@ -404,6 +443,18 @@ class HipIVFSearcher(FaissStyleSearcher):
         if self.metric in {"cosine", "ip"}:
             d = -d
         return d.astype(np.float32), i.astype(np.int64)
+
+    def range_search(self, queries: np.ndarray, radius: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lims, distances, ids) over the probed lists, ascending (list, id) per query, with HipLinearSearcher.range_search's
+        radius: 'l2': the rows at Euclidean distance below `radius` (the library is asked for squared distances below
+        float32(radius) * float32(radius)); 'cosine' / 'ip': the rows whose score (queries normalised for cosine) exceeds
+        `radius`.  The distances are what `batch_search` returns: squared L2, negated scores.  An IVF-Flat artifact only."""
+        self._require_attached()
+        r = np.float32(radius)
+        lims, d, i = self.index.range_search(self._prepare_query(queries), r * r if self.metric == "l2" else r)
+        if self.metric in {"cosine", "ip"}:
+            d = -d
+        return lims, d.astype(np.float32), i.astype(np.int64)
 
 
 register_algorithm("HipApproximateSearch", HipApproximateSearch)
