@@ -212,8 +212,8 @@ int vdb_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float
  * bytes).  A NaN key passes neither comparison and is never returned; a key of +inf is never returned under L2; under IP a score of
  * +inf is returned with D = +inf.  radius: +-inf is legal, NaN is VDB_ERR_INVALID, an L2 radius <= 0 returns nothing.
  * lims (nq + 1 int64): query q owns entries [lims[q], lims[q + 1]) of D (float32) and I (int64), which the handle keeps on the
- * device until the next range search, vdb_add, vdb_reset or vdb_set_option; they count in bytes_resident / bytes_workspace and are
- * freed by vdb_reset and vdb_destroy.  vdb_range_results(_device) copies the result of the LAST range search of the handle out.
+ * device until the next range search, vdb_add (one that is not refused: see the filter section below), vdb_reset or vdb_set_option;
+ * they count in bytes_resident / bytes_workspace and are freed by vdb_reset and vdb_destroy.  vdb_range_results(_device) copies the result of the LAST range search of the handle out.
  * How: a handle with resident fp16 panels in layout "x16" (D <= 128, above 15 360 rows) or p16 (D > 128, above 2048
  * rows) runs an MFMA scan that sets a bit per (query, row) whose scan score lies within the proven bound of the radius -- a superset
  * of the answer; every other handle (32x32 layout, "int8_only", "stream_panels", a non-finite corpus) and every query whose
@@ -248,7 +248,10 @@ int vdb_range_results_device(vdb_handle h, float *D_dev, int64_t *I_dev, void *s
  * "filter_sparse_pairs") -- their ascending list (4 bytes each, + 4 per 2048 rows).  It counts in bytes_resident and is freed by
  * vdb_filter_clear, vdb_reset and vdb_destroy.  vdb_add(_device), vdb_reset, vdb_set_option and any call that changes the kind of the
  * handle DROP the filter: vdb_search_filtered then fails with VDB_ERR_STATE and a message naming the missing filter -- it never answers
- * unfiltered.  vdb_search and every other call never look at the filter: their results are the same with or without one.
+ * unfiltered.  (A vdb_add(_device) that is refused -- a null pointer with n > 0, a negative n, another id_base, an append to an
+ * "int8_only" index, more than 2^31 rows -- changes nothing: it keeps the filter and the last range result, as a refused vdb_ivf_add
+ * does; an empty append, n = 0 with the index's id_base, is an add that passed its checks and drops both.)
+ * vdb_search and every other call never look at the filter: their results are the same with or without one.
  * An install runs on its stream and synchronises it once (the admitted count comes back); the searches synchronise nothing.  The
  * caller orders an install behind filtered searches still running on other streams.
  * How: every MFMA scan reads an accumulator init of 0.9e38 or more as the marker of a padding row and never selects it,

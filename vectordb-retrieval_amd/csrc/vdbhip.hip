@@ -998,19 +998,30 @@ void require_same_id_base(const vdb_index_s *h, int64_t id_base) {
                                          "id_base, or call vdb_reset first; got " + std::to_string(id_base));
 }
 
-// vdb_add / vdb_add_device: APPEND, as faiss.Index.add does (the first add of an empty index is build_index)
-void append_rows(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
-    if (h->N == 0 || h->ivf_built) {      // (rows filed by vdb_ivf_add are replaced: they sit in list order, not insertion order)
-        build_index(h, x_dev_or_host, on_device, n, id_base, st);
+// what an add refuses from its arguments and the handle's state alone, before it touches the handle (add_rows runs it ahead of
+// everything an add drops: a refused add changes nothing)
+void refuse_bad_add(const vdb_index_s *h, int64_t n, int64_t id_base) {
+    if (n < 0) throw Error(VDB_ERR_INVALID, "negative row count");
+    if (h->N == 0 || h->ivf_built) {      // (the add replaces the rows: build_index)
+        if (n > 2147483647ll - 1024) throw Error(VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
         return;
     }
-    if (n < 0) throw Error(VDB_ERR_INVALID, "negative row count");
     require_same_id_base(h, id_base);
     if (n == 0) return;
     if (h->int8_only)
         throw Error(VDB_ERR_UNSUPPORTED, "an int8_only index keeps no float32 rows to re-derive its scan copies from: it is built by "
                                          "ONE add (vdb_reset, then add everything)");
     if (h->N + n > 2147483647ll - 1024) throw Error(VDB_ERR_UNSUPPORTED, "more than 2^31 rows per shard");
+}
+
+// vdb_add / vdb_add_device: APPEND, as faiss.Index.add does (the first add of an empty index is build_index)
+void append_rows(vdb_index_s *h, const float *x_dev_or_host, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
+    refuse_bad_add(h, n, id_base);
+    if (h->N == 0 || h->ivf_built) {      // (rows filed by vdb_ivf_add are replaced: they sit in list order, not insertion order)
+        build_index(h, x_dev_or_host, on_device, n, id_base, st);
+        return;
+    }
+    if (n == 0) return;
     graph_reset(h);
     VDB_HIP(hipDeviceSynchronize());                        // (searches of the rows about to move may still run)
     const int64_t N0 = h->N;
@@ -1114,6 +1125,7 @@ void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, 
     admit(h, what, kAnyKind & ~(kPq | kIvfSq8 | kIvfPq));      // (those hold their rows as codes: vdb_pq_add, vdb_ivf_add)
     if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
+    refuse_bad_add(h, n, id_base);             // (a refused add changes nothing: the range result and the filter stay)
     set_device(h->device);
     h->range_valid = false;                    // (the last range result described the rows as they were)
     filter_drop(h);                            // (... and so did an installed filter: one bit per row, nbits == ntotal)
