@@ -79,11 +79,12 @@ typedef struct vdb_stats_s {
     int32_t nlist;             /* IVF: number of inverted lists (0 = flat index) */
     int32_t nprobe;
     int32_t scan_dtype;        /* arithmetic of the last MFMA scan: 0 = fp16 (f32 accumulate), 1 = int8 (i32 accumulate),
-                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index (f32 accumulate),
+                                  2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index, or from the int8 panels of an IVF-I8
+                                  index for a batch its int8 scan cannot serve (f32 accumulate),
                                   3 = float32 lookup-table sums over the codes of a PQ or IVF-PQ index (last_path = VDB_PATH_PQ_ADC /
                                   VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128) next to the float32
-                                  rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only") */
+                                  rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
                                   queries that took the brute-force fallback */
     int64_t upload_blocks;     /* row blocks the last vdb_add / vdb_ivf_add streamed through the pinned staging buffers */
@@ -106,7 +107,8 @@ typedef struct vdb_stats_s {
  *   LSH       a projection (vdb_lsh_set_projection)      IVF-Flat  centroids or filed rows, codec 0
  *   knng      a k-NN graph (vdb_knng_build / _set;       IVF-SQ8   vdb_ivf_set_codec 1
  *             an add or vdb_reset makes it flat again)   IVF-PQ    vdb_ivf_set_codec 2
- *   multi     vdb_create_multi (flat or IVF-Flat rows)   LSHT      hash tables (vdb_lsht_set_tables)
+ *   multi     vdb_create_multi (flat or IVF-Flat rows)   IVF-I8    vdb_ivf_set_codec 3
+ *                                                        LSHT      hash tables (vdb_lsht_set_tables)
  * A call on a kind it does not serve is refused before it looks at its arguments or touches the handle, with a message that names
  * the call and the kind: U = VDB_ERR_UNSUPPORTED, S = VDB_ERR_STATE.  "+" = admitted (the call's own state and argument checks
  * follow: "no centroids", "not built", ...).
@@ -126,9 +128,10 @@ typedef struct vdb_stats_s {
  *   vdb_ivf_range_search(_device),
  *     vdb_ivf_range_results(_device)                     +     U    U     U    U      +         U        U       U
  *   vdb_ivf_train, vdb_ivf_set_centroids                 +     U    U     U    U      +         +        +       +
- *   vdb_ivf_set_codec 1 | 2                              +     U    U     U    U      +         +        +       U
+ *   vdb_ivf_set_codec 1 | 2 | 3                          +     U    U     U    U      +         +        +       U
  *   every other vdb_ivf_* call, vdb_ivf_set_codec 0      +     +    +     +    U      +         +        +       +
  *   vdb_ivf_sq8_*, vdb_ivf_get_codes                     S     S    S     S    U      S         +        U       U
+ *   vdb_ivf_i8_get_rows                                  S     S    S     S    U      S         S        U       U
  *   vdb_ivfpq_train / _set_codebooks / _add_codes /
  *     _get_codes                                         S     S    S     S    U      S         S        +       U
  *   vdb_pq_train, vdb_pq_set_codebooks                   +     U    U     U    +      U         U        U       U
@@ -147,8 +150,47 @@ typedef struct vdb_stats_s {
  *     "int8_only" = 1, "stream_panels" = 1               -     U    U     U    U      -         U        U       -
  *     "graph" = 1                                        -     -    -     -    U      -         U        U       U
  *     "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4 -     -    -     -    U      -         -        -       -
+ * The tenth kind, IVF-I8, in a column of its own (the same rows):
+ *                                                       IVF-I8
+ *   vdb_add(_device)                                    U
+ *   vdb_search*, vdb_reserve, vdb_reset, vdb_stats,
+ *     vdb_set_option, the get_codebooks / get_projection
+ *     / get_tables / vdb_knng_get calls (M, nbits, T,
+ *     degree 0 elsewhere)                               +
+ *   vdb_rerank(_device)                                 +
+ *   vdb_range_search(_device), vdb_range_results(_deviceU
+ *   vdb_filter_set(_device), vdb_filter_count,
+ *     vdb_search_filtered(_device)                      U
+ *   vdb_filter_clear                                    +
+ *   vdb_ivf_filter_set(_device), vdb_ivf_filter_count,
+ *     vdb_ivf_search_filtered(_device)                  U
+ *   vdb_ivf_range_search(_device),
+ *     vdb_ivf_range_results(_device)                    U
+ *   vdb_ivf_train, vdb_ivf_set_centroids                +
+ *   vdb_ivf_set_codec 1 | 2 | 3                         +
+ *   every other vdb_ivf_* call, vdb_ivf_set_codec 0     +
+ *   vdb_ivf_sq8_*, vdb_ivf_get_codes                    U
+ *   vdb_ivf_i8_get_rows                                 +
+ *   vdb_ivfpq_train / _set_codebooks / _add_codes /
+ *     _get_codes                                        U
+ *   vdb_pq_train, vdb_pq_set_codebooks                  U
+ *   vdb_pq_add, vdb_pq_add_codes, vdb_pq_get_codes      U
+ *   vdb_lsh_set_projection                              U
+ *   vdb_lsh_candidates*, vdb_lsh_search*                U
+ *   vdb_lsh_get_codes                                   U
+ *   vdb_lsht_set_tables                                 U
+ *   vdb_lsht_candidates*, vdb_lsht_search*,
+ *     vdb_lsht_get_keys                                 U
+ *   vdb_knng_build, vdb_knng_set, vdb_knng_search*      U
+ *   vdb_debug_scan_scores                               +
+ *   vdb_debug_pq_adc_scores                             U
+ *   vdb_debug_ivfpq_adc_scores                          U
+ *   options refused (U), in either order of the calls:
+ *     "int8_only" = 1, "stream_panels" = 1              U
+ *     "graph" = 1                                       U
+ *     "flat_shape" = 32, "f16_group" = 4, "i8_group" = 4-
  * "Either order": vdb_set_option refuses the value on a handle of the kind, and the call that makes a handle that kind
- * (vdb_lsh_set_projection, vdb_lsht_set_tables, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2) refuses a handle on
+ * (vdb_lsh_set_projection, vdb_lsht_set_tables, vdb_knng_build / _set, vdb_pq_train / _set_codebooks, vdb_ivf_set_codec 1 | 2 | 3) refuses a handle on
  * which the option holds the value; LSH, LSHT and knng also while an "int8_only" / "stream_panels" of the last add is in effect.  The
  * LSH, hash-table LSH, k-NN graph, range search and filter calls (but vdb_filter_clear) are refused while option "graph" is 1. */
 
@@ -426,8 +468,8 @@ int vdb_ivf_search_partial_device(vdb_handle h, const float *q_dev, int64_t nq, 
  * IVF-Flat's panels of x^, so the same error bound holds; vdb_stats.scan_dtype = 2).  D > 128: the exact list scan.
  * Rows enter through vdb_ivf_add / vdb_ivf_add_assigned only.  What an SQ8 handle admits and which options it refuses: the
  * table of kinds above (column "IVF-SQ8"). */
-/* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8, 2 = PQ (IVF<nlist>,PQ<M>, below).  Only before centroids or
- * rows exist (VDB_ERR_STATE after) */
+/* codec of the inverted lists: 0 = Flat (the default), 1 = SQ8, 2 = PQ (IVF<nlist>,PQ<M>, below), 3 = I8 (IVF<nlist>,I8, below; dim
+ * <= 128, VDB_ERR_UNSUPPORTED beyond).  Only before centroids or rows exist (VDB_ERR_STATE after) */
 int vdb_ivf_set_codec(vdb_handle h, int codec);
 /* SQ8: vdb_ivf_train trains the centroids (the contract stated there, unchanged by the codec) and then the ranges on the same
  * rows, all of them and not the k-means sample; this call trains the ranges only, against
@@ -438,6 +480,27 @@ int vdb_ivf_sq8_set_ranges(vdb_handle h, const float *vmin_host, const float *vd
 int vdb_ivf_sq8_get_ranges(vdb_handle h, float *vmin_host, float *vdiff_host);
 /* codes of an SQ8 index, uint8 (ntotal, dim), in id (insertion) order */
 int vdb_ivf_get_codes(vdb_handle h, uint8_t *codes_host);
+
+/* ---- IVF<nlist>,I8 -- IVF-Flat over a byte-valued corpus that keeps the rows ONCE, as int8 (codec 3 of vdb_ivf_set_codec) ----------
+ * A byte-valued corpus (SIFT, BIGANN, any uint8 / int8 feature set: every value an integer in 0..255, or every value an integer in
+ * -128..127 -- the test the flat int8 copies are admitted by) sits four times in an IVF-Flat index: float32 rows, fp16 panels, int8
+ * panels, row-major int8 rows.  An IVF-I8 index keeps the last two and what is derived from them -- rows8 in list order, panels8,
+ * bias8, rowstat8, the fp16 scan's bias, ids, CSR and span tables, centroids -- about 0.6 x the float32 bytes (csrc/ivf_i8_plan.hpp,
+ * ivf_i8_bytes), and NO float32 rows and no resident fp16 panels.  The codec is LOSSLESS: a row is stored as byte = x - cx with cx =
+ * 128 (values 0..255; chosen when both windows fit) or 0 (values -128..127) and decoded as x = byte + cx, exactly.
+ * vdb_ivf_search, _device, _partial_device and vdb_reserve return, bit for bit, what an IVF-Flat handle returns with the same
+ * centroids, rows, id_base, nprobe and k.  Integer batches inside the byte window take the int8 list scan on the resident panels and
+ * the integer refine, as on IVF-Flat (scan_dtype = 1); every other batch of the list-major path scans fp16 panels converted from the
+ * int8 panels for that batch (scan_dtype = 2; they equal IVF-Flat's panels, so the same candidates are nominated; option
+ * "ivf_i8_scratch" = 0 skips them); every exact stage scores x = byte + cx in the canonical float64 arithmetic.
+ * Rows enter through vdb_ivf_add / vdb_ivf_add_assigned only, in blocks of option "int8_block_rows": the corpus is never held in
+ * float32 on the device.  An add of rows that are not byte-valued, or that fit no window together with the rows already filed, is
+ * VDB_ERR_INVALID and leaves the handle exactly as it was.  Appends work as on IVF-Flat: any sequence of adds builds, byte for byte,
+ * the index one add of all rows builds (the window is re-chosen over old and new rows).  vdb_ivf_train / vdb_ivf_set_centroids work
+ * as on IVF-Flat (float32 centroids, unchanged coarse stage).  vdb_stats.has_i8_copy = 2.  What the kind admits and which options
+ * it refuses: the table of kinds above (column "IVF-I8"); not served: multi-device handles, filtered and range search, D > 128. */
+/* int8 (ntotal, dim) rows in id (insertion) order and the offset: x = rows + *cx.  rows_host may be NULL (only *cx is returned) */
+int vdb_ivf_i8_get_rows(vdb_handle h, int8_t *rows_host, int *cx);
 
 /* ---- IVF<nlist>,PQ<M> -- replaces faiss.index_factory(d, "IVF<nlist>,PQ<M>", metric) (IndexIVFPQ, 8 bits, by_residual; the
  *      reference's `ivf_pq` configs) -- codec 2 of vdb_ivf_set_codec ---------------------------------------------------------
@@ -684,7 +747,8 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       VDB_ERR_UNSUPPORTED; a corpus that is not byte-valued silently gets the default layout
  *                       (vdb_stats.has_i8_copy tells: 2 = int8 only)
  *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
- *                       spans (tests: several blocks on a small corpus)
+ *                       spans (tests: several blocks on a small corpus); also the rows per block of a vdb_ivf_add on an IVF-I8 index
+ *                       (0 = default 1 048 576, not rounded): one block of float32 rows is all the device holds of them
  *     "stream_panels"   D > 128, takes effect at the next vdb_add: 0 (default) the fp16 scan copy stays resident next to the
  *                       float32 rows | 1 it is NOT kept: every search converts the float32 rows slab by slab into one
  *                       scratch slab and scans that (same results; 1.8x -> ~1.15x the corpus bytes resident for a corpus that
@@ -700,6 +764,15 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       query-operand kernel, one dependent dispatch less | 0 a separate statistics dispatch for every size
  *     "ivf_min_batch"   smallest query batch the list-major MFMA scan of the IVF index serves (default 1); smaller ones
  *                       take the exact per-query list scan
+ *     "ivf_i8_scratch"  IVF-I8 index: 1 (default) a batch the int8 list scan cannot serve (a non-integer value, a value outside the
+ *                       byte window, "panel_dtype" = 1) scans fp16 panels of the whole panel space, converted from the int8 panels
+ *                       for that batch into a workspace slab of 2 bytes per (padded) dimension per panel row | 0 the slab is never
+ *                       allocated: such a batch is flagged on the device and every query of it answered by the exact list scan
+ *                       (vdb_stats.last_fallback_queries = nq).  Same results either way.  Measured on sift-like bytes 1M x 128,
+ *                       IVF1024, 10 000 non-integer queries, nprobe 8 / 32 / 128 (scripts/bench_ivf_i8.py,
+ *                       profiles/r26_bench_ivf_i8.json): 1 = 0.43 / 0.54 / 0.91 ms per batch (the conversion pass is ~0.08 ms of it) and
+ *                       a 288 MB slab; 0 = 14.6 / 48.6 / 173.7 ms and no slab -- for indexes that see integer batches only.
+ *                       Every other kind accepts it without effect
  *     "graph"           0 (default) | 1: a vdb_search_device / vdb_search_partial_device / vdb_ivf_search*_device call of
  *                       at most 4096 queries on a non-null stream that repeats with the same buffers, shape and stream
  *                       (a serving loop) is captured into a hipGraph on its second occurrence and replayed afterwards;

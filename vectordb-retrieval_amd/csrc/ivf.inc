@@ -24,11 +24,15 @@ void ivf_require(bool cond, int code, const char *msg) {
 // refuse the handles that can never carry it, and are a state error on the rest.
 constexpr unsigned kIvfCalls = kAnyKind & ~kPq, kBecomesIvf = kFlat | kIvf | kMulti;
 inline void admit_sq8(const vdb_index_s *h, const char *what) {
-    admit(h, what, kAnyKind & ~(kPq | kMulti | kIvfPq));
+    admit(h, what, kAnyKind & ~(kPq | kMulti | kIvfPq | kIvfI8));
     admit(h, what, kIvfSq8, VDB_ERR_STATE, ": not an SQ8 index (vdb_ivf_set_codec(h, 1) on an empty handle)");
 }
+inline void admit_ivf_i8(const vdb_index_s *h, const char *what) {      // (as admit_sq8: S where vdb_ivf_get_codes answers S, U where it answers U)
+    admit(h, what, kAnyKind & ~(kPq | kMulti | kIvfPq));
+    admit(h, what, kIvfI8, VDB_ERR_STATE, ": not an IVF-I8 index (vdb_ivf_set_codec(h, 3) on an empty handle)");
+}
 inline void admit_ivfpq(const vdb_index_s *h, const char *what) {
-    admit(h, what, kAnyKind & ~(kPq | kMulti));
+    admit(h, what, kAnyKind & ~(kPq | kMulti | kIvfI8));
     admit(h, what, kIvfPq, VDB_ERR_STATE, ": not an IVF-PQ index (vdb_ivf_set_codec(h, 2) on an empty handle)");
 }
 
@@ -185,6 +189,7 @@ void ivf_check_given(const vdb_index_s *h, const int32_t *given, int64_t n) {
 
 #include "ivf_sq8.inc"      // IVF<nlist>,SQ8: range training, encoding add, the codes' accessor
 #include "ivf_pq.inc"       // IVF<nlist>,PQ<M>: residual product codes, encoding add, the per-batch panel pass
+#include "ivf_i8.inc"       // IVF<nlist>,I8: lossless int8 rows of a byte-valued corpus, streaming add, the per-batch panel pass
 
 // vdb_ivf_get_codes / vdb_ivfpq_get_codes: the code rows of a built coded index (`codes`: list order, `pitch` bytes apart, the
 // first `width` of each are the row's code), scattered from list order to insertion order (id - id_base)
@@ -201,20 +206,10 @@ void ivf_get_codes(vdb_index_s *h, const DevBuf &codes, size_t pitch, size_t wid
     for (int64_t r = 0; r < h->N; ++r) memcpy(codes_host + (size_t)(ids[(size_t)r] - h->id_base) * width, &c[(size_t)r * pitch], width);
 }
 
-// fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
-// 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
-// (four 64-row bins) or, for lists of thousands of rows, 1024 rows (four 256-row bins).
-void ivf_build_panel_space(vdb_index_s *h) {
-    h->ivf_mfma_ok = false;
-    h->scan_ok = false;
-    h->tile16 = h->ksteps > kMaxKSteps;
-    if (h->N == 0 || h->dim > 4096) return;
-    hipStream_t st = nullptr;
-    index_stats(h, st);
-    if (h->nonfinite) return;
+// the panel space of the filed rows: every list padded to whole spans of `span_rows` rows.  Fills the span tables (list_pspan0,
+// span_row0, span_valid; host counts ivf_pspans, ivf_max_pspans, ivf_span_rows) and returns the number of spans
+int64_t ivf_build_spans(vdb_index_s *h, int span_rows) {
     const int nlist = h->nlist;
-    h->ivf_tps = h->tile16 ? ivf_tps_of(h->opt, h->N, nlist) : 0;
-    const int span_rows = h->tile16 ? h->ivf_tps * 16 : kIvfSpanRows;
     h->ivf_span_rows = span_rows;
     std::vector<int32_t> pspan0((size_t)nlist + 1, 0), row0, valid;
     int maxp = 0;
@@ -231,13 +226,31 @@ void ivf_build_panel_space(vdb_index_s *h) {
     const int64_t P = pspan0[(size_t)nlist];
     h->ivf_pspans = P;
     h->ivf_max_pspans = maxp;
-    if (P == 0) return;
+    if (P == 0) return 0;
     h->lists.ivf_list_pspan0.reserve(((size_t)nlist + 1) * 4);
     h->lists.ivf_span_row0.reserve((size_t)P * 4);
     h->lists.ivf_span_valid.reserve((size_t)P * 4);
     VDB_HIP(hipMemcpy(h->lists.ivf_list_pspan0.p, pspan0.data(), ((size_t)nlist + 1) * 4, hipMemcpyHostToDevice));
     VDB_HIP(hipMemcpy(h->lists.ivf_span_row0.p, row0.data(), (size_t)P * 4, hipMemcpyHostToDevice));
     VDB_HIP(hipMemcpy(h->lists.ivf_span_valid.p, valid.data(), (size_t)P * 4, hipMemcpyHostToDevice));
+    return P;
+}
+
+// fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
+// 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
+// (four 64-row bins) or, for lists of thousands of rows, 1024 rows (four 256-row bins).
+void ivf_build_panel_space(vdb_index_s *h) {
+    h->ivf_mfma_ok = false;
+    h->scan_ok = false;
+    h->tile16 = h->ksteps > kMaxKSteps;
+    if (h->N == 0 || h->dim > 4096) return;
+    hipStream_t st = nullptr;
+    index_stats(h, st);
+    if (h->nonfinite) return;
+    h->ivf_tps = h->tile16 ? ivf_tps_of(h->opt, h->N, h->nlist) : 0;
+    const int span_rows = h->tile16 ? h->ivf_tps * 16 : kIvfSpanRows;
+    const int64_t P = ivf_build_spans(h, span_rows);
+    if (P == 0) return;
     const int64_t ntiles = h->tile16 ? P * h->ivf_tps : P * kIvfTilesPerSpan;
     const int ksl = h->tile16 ? h->ksteps / 2 : h->ksteps;           // k-steps of the layout (32 or 16 dims)
     h->scan.panels.reserve((size_t)ntiles * ksl * 64 * sizeof(half8));
@@ -524,6 +537,7 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     if (b.filtered) rc.allow = h->ivf_filter.words.as<uint32_t>();
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
     if (ivfpq(h)) rc.ivfpq = ivfpq_rows(h);
+    if (ivf_i8(h)) i8_refine_rows(h, rc);  // (IVF-I8: rc.X is nullptr, every exact stage scores the int8 rows)
     if (L.c.use_i8 && h->scan.rows8.p) {
         rc.X8 = h->scan.rows8.as<signed char>(); rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
@@ -566,7 +580,10 @@ void ivf_search_lists(const IvfBatch &b) {
     ivf_lists_prep(b, L);
     ivf_lists_plan(b, L);
     ScanArgs sa{};
-    sa.panels = sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
+    // IVF-I8 under "ivf_i8_scratch" = 0 holds no fp16 panels at all: the fp16 scan is not launched, and a batch the int8 scan
+    // does not serve is flagged as a whole for the tail's exact list scan (ivf_i8_flag_kernel)
+    const bool i8_no_slab = ivf_i8(h) && !h->opt.ivf_i8_scratch;
+    sa.panels = i8_no_slab ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
     sa.bias = b.filtered ? h->ivf_filter.bias_f.as<float>() : h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -581,7 +598,12 @@ void ivf_search_lists(const IvfBatch &b) {
     if (b.g.kloop) {
         ivf_scan_kloop(b, L.c.kgroup, sa);
     } else {
-        ivf_scan_fp16(b, sa);
+        if (i8_no_slab) {
+            ivf_i8_flag_kernel<<<dim3(1), dim3(64), 0, b.st>>>(L.info);
+            sa.part_spans = plan_ivf_f16(b.shape, h->opt, b.g).part_spans;      // (the int8 scan takes the fp16 plan's parts)
+        } else {
+            ivf_scan_fp16(b, sa);
+        }
         if (L.c.use_i8) ivf_scan_i8(b, sa);
     }
     timing_mark(h, b.tslot, 1, b.st);
@@ -615,6 +637,7 @@ void ivf_search_exact(const IvfBatch &b) {
     a.c = RefineCommon{h->rows.x32.as<float>(), b.qpad, h->N, h->id_base, h->D4, h->metric, k, h->lists.ivf_ids.as<int64_t>()};
     if (sq8(h)) a.c.sq8 = sq8_rows(h);      // (SQ8: no float32 rows -- the rows are decoded from their codes)
     if (ivfpq(h)) a.c.ivfpq = ivfpq_rows(h);  // (IVF-PQ: likewise, centroid + codebook entry)
+    if (ivf_i8(h)) i8_refine_rows(h, a.c);    // (IVF-I8: the int8 rows, x = byte + cx)
     if (b.filtered) a.c.allow = h->ivf_filter.words.as<uint32_t>();
     a.offsets = h->lists.ivf_offsets.as<int64_t>();
     a.probes = h->plan.ivf_probe_i.as<int64_t>();
@@ -823,12 +846,13 @@ int vdb_ivf_set_codec(vdb_handle hh, int codec) {
     return guarded([&] {
         auto *h = check(hh);
         // codec 0 is what every handle has: admitted as the other IVF calls are (a no-op on a multi-device handle)
-        const bool coded = codec == 1 || codec == 2;
-        admit(h, codec == 1 ? "the SQ8 codec" : codec == 2 ? "the IVF-PQ codec" : "vdb_ivf_set_codec", coded ? kFlat | kIvf : kIvfCalls);
-        ivf_require(codec >= 0 && codec <= 2, VDB_ERR_INVALID, "codec must be 0 (Flat), 1 (SQ8) or 2 (PQ)");
+        const bool coded = codec >= 1 && codec <= 3;
+        admit(h, codec == 1 ? "the SQ8 codec" : codec == 2 ? "the IVF-PQ codec" : codec == 3 ? "the IVF-I8 codec" : "vdb_ivf_set_codec", coded ? kFlat | kIvf : kIvfCalls);
+        ivf_require(codec >= 0 && codec <= 3, VDB_ERR_INVALID, "codec must be 0 (Flat), 1 (SQ8), 2 (PQ) or 3 (I8)");
         if (h->multi) return;
         ivf_require(h->nlist == 0 && h->N == 0, VDB_ERR_STATE, "the codec is chosen before centroids or rows exist");
-        if (coded) refuse_options_set(h, "vdb_ivf_set_codec", codec == 1 ? kIvfSq8 : kIvfPq);
+        ivf_require(codec != 3 || h->dim <= 128, VDB_ERR_UNSUPPORTED, "the IVF-I8 codec serves dim <= 128 (the int8 list scan and the int8 row pitch)");
+        if (coded) refuse_options_set(h, "vdb_ivf_set_codec", codec == 1 ? kIvfSq8 : codec == 2 ? kIvfPq : kIvfI8);
         if (codec != 2) {                       // (codebooks belong to codec 2)
             h->ivfpq = PqCodebooks{};
             h->kept.ivfpq_cb.release();
@@ -880,6 +904,17 @@ int vdb_ivf_get_codes(vdb_handle hh, uint8_t *codes_host) {
         auto *h = check(hh);
         admit_sq8(h, "vdb_ivf_get_codes");
         ivf_get_codes(h, h->codes.sq8_codes, (size_t)h->D4, (size_t)h->dim, codes_host);
+    });
+}
+
+int vdb_ivf_i8_get_rows(vdb_handle hh, int8_t *rows_host, int *cx) {
+    return guarded([&] {
+        auto *h = check(hh);
+        admit_ivf_i8(h, "vdb_ivf_i8_get_rows");
+        ivf_require(h->ivf_built, VDB_ERR_STATE, "Index has not been built yet.");
+        ivf_require(cx != nullptr, VDB_ERR_INVALID, "null pointer");
+        *cx = h->i8_cx;
+        if (rows_host) ivf_get_codes(h, h->scan.rows8, (size_t)h->rows8_pitch, (size_t)h->dim, reinterpret_cast<uint8_t *>(rows_host));
     });
 }
 
@@ -977,6 +1012,7 @@ int ivf_add_impl(vdb_handle hh, const float *x_host, int64_t n, int64_t id_base,
         }
         if (sq8(h)) return sq8_add(h, x_host, n, id_base, given);
         if (ivfpq(h)) return ivfpq_add(h, x_host, nullptr, n, id_base, given);
+        if (ivf_i8(h)) return i8_add(h, x_host, n, id_base, given);
         ivf_require(h->nlist > 0 && h->coarse, VDB_ERR_STATE, "no centroids: train or set them first");
         ivf_require(n >= 0 && (n == 0 || x_host), VDB_ERR_INVALID, "bad corpus");
         int64_t N0, N1;
@@ -1111,7 +1147,7 @@ int vdb_reserve(vdb_handle hh, int64_t nq, int k) {
         run_staged(h, reinterpret_cast<const float *>(host.data()), nq, k, D, I, [&](float *dq, float *dD, int64_t *dI, hipStream_t st) {
             for (int64_t q0 = 0; q0 < nq; q0 += h->N) {      // queries = corpus rows (wrapping around a corpus smaller than the batch)
                 const int64_t m = std::min<int64_t>(h->N, nq - q0);
-                if (h->int8_only)     // (no float32 rows: the int8 rows, converted)
+                if (h->int8_only || ivf_i8(h))     // (no float32 rows: the int8 rows, converted)
                     rows_i8_to_float_kernel<<<dim3((unsigned)((m * h->dim + 255) / 256)), dim3(256), 0, st>>>(
                         h->scan.rows8.as<signed char>(), h->rows8_pitch, h->i8_cx, m, h->dim, dq + (size_t)q0 * h->dim);
                 else if (pq_on(h))    // (product codes: the looked-up rows x^)

@@ -101,7 +101,7 @@ PqRows pq_rows(const vdb_index_s *h) {
 // What the PQ entry points admit.  A handle becomes a PQ index on one device, with no other row store or structure over float32
 // rows (and no option a PQ index refuses: refuse_options_set).  The calls on the codes refuse the handles that never hold flat
 // codebooks; every other kind has none yet, which is the state error of pq_need_codebooks.
-constexpr unsigned kBecomesPq = kFlat | kPq, kPqCodeCalls = kAnyKind & ~(kMulti | kIvfPq);
+constexpr unsigned kBecomesPq = kFlat | kPq, kPqCodeCalls = kAnyKind & ~(kMulti | kIvfPq | kIvfI8);
 void pq_need_codebooks(const vdb_index_s *h, const char *what) {
     if (!pq_on(h)) throw Error(VDB_ERR_STATE, std::string(what) + ": no codebooks (call vdb_pq_train or vdb_pq_set_codebooks first)");
 }

@@ -43,7 +43,8 @@ struct Options {
     // the exact kernels read x = byte + cx from the int8 rows (same float64 chains, same keys).  One add builds it (no append).
     int int8_only = 0;
     int int8_slab_chunks = 0;                // scan chunks per converted fp16 slab (0 = default 8)
-    int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests)
+    int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests), and of an add to an
+                                             // IVF-I8 index (0 = 1M): the float32 rows of one block are all the device holds of them
     // "stream_panels" (D > 128, takes effect at the next add): the fp16 panels are NOT kept -- every search converts the
     // float32 rows slab by slab into one scratch slab and scans it (search_flat.inc).  Halves the footprint of a non-fp16-exact
     // corpus (the float32 rows must stay for the exact refine) at the price of one conversion pass per batch.
@@ -53,6 +54,9 @@ struct Options {
     int small_batch = 1;                     // 0: batches <= 512 queries keep the batch-shaped grid
     int fused_stats = 1;                     // 0 (A/B): small batches keep the separate statistics dispatch
     int ivf_min_batch = 1;                   // smallest query batch the list-major MFMA scan serves
+    int ivf_i8_scratch = 1;                  // IVF-I8: 1 = batches the int8 scan cannot serve scan fp16 panels converted from the int8 ones
+                                             // (a workspace slab of the whole panel space) | 0 = no slab: those batches are flagged on the
+                                             // device and answered by the exact list scan of the tail.  Same results; no effect elsewhere
     // "graph": a device-resident search that repeats with the same shape and buffers (a serving loop) is captured into a
     // hipGraph on its second call and replayed from the third (graph_or_run)
     int graph = 0;

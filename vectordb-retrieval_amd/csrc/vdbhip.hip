@@ -28,6 +28,8 @@
 #include "ivf_mfma.hpp"
 #include "ivf_kloop.hpp"
 #include "ivf_sq8.hpp"
+#include "ivf_i8_plan.hpp"
+#include "ivf_i8.hpp"
 #include "ivf_pq.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
@@ -241,7 +243,7 @@ struct Workspace {
     DevBuf dense{"ws.dense"};               // nq x Npad raw scores of the small-corpus path
     DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
-    DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ: the fp16 panels converted from the codes for the current batch
+    DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ / IVF-I8: the fp16 panels converted from the codes (the int8 panels) for the current batch
     DevBuf adc_tab{"ws.adc_tab"};           // PQ / IVF-PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
     DevBuf adc_scores{"ws.adc_scores"};     // IVF-PQ, ADC scan: the scores of the probed rows, [nq][stride] (ivf_pq_adc.hpp)
     DevBuf adc_aux{"ws.adc_aux"};           // ... its scale, flags, B [nq][nprobe] and score positions [nq][nprobe + 1]
@@ -332,6 +334,7 @@ struct vdb_index_s {
     uint64_t graph_epoch = 0;                // g_alloc_epoch when the graph was captured
     int64_t graph_replays = 0;
     int i8_cx = 0, i8_ks = 0;
+    int i8_min = 0, i8_max = 0;              // IVF-I8 (ivf_i8.inc): smallest / largest value of the filed rows -- an append re-chooses the byte window over old and new rows
     // host copies of the corpus statistics
     float absmax = 0.f, maxnorm2 = 0.f, sx = 1.f;
     bool nonfinite = false, corpus_int_unscaled = false, corpus_fp16_exact = false, scan_ok = false;
@@ -369,6 +372,7 @@ struct vdb_index_s {
     int ivf_tps = 0;                         // p16 tiles per span of the IVF panel space (16 / 64; option "ivf_tps" or the rule of ivf.inc)
     // codec of the inverted lists (vdb_ivf_set_codec): 0 Flat (float32 rows + scan copies) | 1 SQ8 (ivf_sq8.inc: 8-bit codes
     // of the residuals, no float32 rows, no scan copies) | 2 PQ (ivf_pq.inc: M-byte product codes of the residuals, likewise)
+    // | 3 I8 (ivf_i8.inc: a byte-valued corpus as int8 rows, lossless; only the int8 scan copies are kept)
     int ivf_codec = 0;
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
@@ -427,13 +431,14 @@ namespace {
 // the raw fields to decide that (computed, not stored: nothing to keep in step); kKinds names each kind in messages; admit is
 // the first line of every entry point, its mask the kinds that call serves; refuse_options_set is the option rule of kOptions
 // read in the other order.  A new kind is one enum bit (and a wider kAnyKind), one row of kKinds, a test in kind_of and its own masks.
-enum Kind : unsigned { kFlat = 1, kLsh = 2, kKnng = 4, kPq = 8, kIvfFlat = 16, kIvfSq8 = 32, kIvfPq = 64, kMulti = 128, kLsht = 256 };
-constexpr unsigned kAnyKind = 511, kIvf = kIvfFlat | kIvfSq8 | kIvfPq;
+enum Kind : unsigned { kFlat = 1, kLsh = 2, kKnng = 4, kPq = 8, kIvfFlat = 16, kIvfSq8 = 32, kIvfPq = 64, kMulti = 128, kLsht = 256, kIvfI8 = 512 };
+constexpr unsigned kAnyKind = 1023, kIvf = kIvfFlat | kIvfSq8 | kIvfPq | kIvfI8;
 constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
     {kMulti, "a multi-device index (vdb_create_multi)"},
     {kPq, "a flat PQ index (vdb_pq_*: its rows are codes, its panels are made per search in layout \"x16\" only)"},
     {kIvfPq, "an IVF-PQ index (vdb_ivf_set_codec 2, vdb_ivfpq_*: its rows are codes in list order)"},
     {kIvfSq8, "an IVF index with the SQ8 codec (its rows are codes in list order)"},
+    {kIvfI8, "an IVF-I8 index (vdb_ivf_set_codec 3: its rows are int8 bytes in list order, it keeps no float32 rows)"},
     {kIvfFlat, "an IVF index (centroids set: its rows sit in list order)"},
     {kLsh, "an index with sign-LSH codes (vdb_lsh_set_projection: it stays a flat index)"},
     {kLsht, "an index with LSH hash tables (vdb_lsht_set_tables: it stays a flat index)"},
@@ -442,7 +447,7 @@ constexpr struct { unsigned kind; const char *phrase; } kKinds[] = {
 
 unsigned kind_of(const vdb_index_s *h) {
     if (h->multi) return kMulti;             // (nlist / ivf_built of such a handle describe the whole index)
-    const unsigned ivf = h->ivf_codec == 2 ? kIvfPq : h->ivf_codec == 1 ? kIvfSq8 : (h->nlist > 0 || h->coarse || h->ivf_built) ? kIvfFlat : 0;
+    const unsigned ivf = h->ivf_codec == 3 ? kIvfI8 : h->ivf_codec == 2 ? kIvfPq : h->ivf_codec == 1 ? kIvfSq8 : (h->nlist > 0 || h->coarse || h->ivf_built) ? kIvfFlat : 0;
     const unsigned k = (h->pq.M > 0 ? kPq : 0) | ivf | (h->lsh_nbits > 0 ? kLsh : 0) | (h->knng_degree > 0 ? kKnng : 0) | (h->lsht_T > 0 ? kLsht : 0);
     if (k & (k - 1)) throw Error(VDB_ERR_STATE, "internal: handle is two kinds at once");
     return k ? k : kFlat;
@@ -470,7 +475,7 @@ struct OptionRow {
     int64_t Options::*m64 = nullptr;       // instead of m
     bool vdb_index_s::*effect = nullptr;   // set while the value of the last add is in effect, whatever the option says now
 };
-constexpr unsigned kNoRows = kIvfSq8 | kPq | kIvfPq, kNeedsRows = kLsh | kKnng | kLsht;     // no float32 rows at all | encoded from / searched against the resident ones
+constexpr unsigned kNoRows = kIvfSq8 | kPq | kIvfPq | kIvfI8, kNeedsRows = kLsh | kKnng | kLsht;     // no float32 rows at all | encoded from / searched against the resident ones
 constexpr OptionRow kOptions[] = {
     {"force_path", &Options::force_path, 4, {0, 1, 2, 3}},
     {"timing", &Options::timing, -1, {}},                            // (re)starts the recording window
@@ -485,6 +490,7 @@ constexpr OptionRow kOptions[] = {
     {"small_batch", &Options::small_batch, 2, {0, 1}},               // 1 (default): finer chunks / narrower workgroups for batches <= 512 queries
     {"fused_stats", &Options::fused_stats, 2, {0, 1}},               // 1 (default) | 0: separate query_stats_kernel for every batch size (A/B)
     {"ivf_min_batch", &Options::ivf_min_batch, 0, {1, 1e9}},
+    {"ivf_i8_scratch", &Options::ivf_i8_scratch, 2, {0, 1}},         // IVF-I8: 1 (default) fp16 panels converted per batch for the batches the int8 scan cannot serve | 0: never, those batches take the exact list scan
     {"graph", &Options::graph, 2, {0, 1}, kNoRows},
     {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
@@ -1122,7 +1128,7 @@ std::vector<int64_t> sample_rows(int64_t n, int64_t ns, uint64_t seed) {
 
 // vdb_add (host rows, null stream) and vdb_add_device (device rows, the caller's stream)
 void add_rows(vdb_index_s *h, const char *what, const float *x, bool on_device, int64_t n, int64_t id_base, hipStream_t st) {
-    admit(h, what, kAnyKind & ~(kPq | kIvfSq8 | kIvfPq));      // (those hold their rows as codes: vdb_pq_add, vdb_ivf_add)
+    admit(h, what, kAnyKind & ~(kPq | kIvfSq8 | kIvfPq | kIvfI8));      // (those hold their rows as codes: vdb_pq_add, vdb_ivf_add)
     if (n > 0 && !x) throw Error(VDB_ERR_INVALID, "null corpus pointer");
     if (h->multi) return multi_add(h, x, on_device, n, id_base, st, false, nullptr);
     refuse_bad_add(h, n, id_base);             // (a refused add changes nothing: the range result and the filter stay)
@@ -1407,7 +1413,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.corpus_fp16_exact = h->corpus_fp16_exact ? 1 : 0;
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
-        s.has_i8_copy = h->int8_only ? 2 : (h->i8_ok ? 1 : 0);
+        s.has_i8_copy = (h->int8_only || h->ivf_codec == 3) ? 2 : (h->i8_ok ? 1 : 0);      // (IVF-I8: nothing but the int8 copies)
         s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + group_bytes(h->range) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
@@ -1428,7 +1434,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
-        if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes
+        if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && !(h->ivf_codec == 3 && s.scan_dtype == 1)) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes, or from the int8 panels of IVF-I8 (whose integer batches take the int8 scan: 1)
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;

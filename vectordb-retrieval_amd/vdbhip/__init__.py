@@ -8,7 +8,7 @@ from .plugin_api import (ALGORITHM_REGISTRY, INDEXER_REGISTRY, SEARCHER_REGISTRY
                          get_searcher_class, register_algorithm, register_indexer, register_searcher)
 from .algorithms import HipBruteForceIndexer, HipExactSearch, HipLinearSearcher, rerank_candidates
 from .index import FlatIndex, merge_packed_partials_device, merge_partials_device
-from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFSQ8Index, parse_index_key
+from .ivf import HipApproximateSearch, HipIVFIndexer, HipIVFSearcher, IVFFlatIndex, IVFI8Index, IVFSQ8Index, parse_index_key
 from .ivf_pq import HipIVFPQIndexer, HipIVFPQSearch, IVFPQIndex, parse_ivfpq_key
 from .knng import HipKnnGraphIndexer, HipKnnGraphSearch, HipKnnGraphSearcher, KnnGraphIndex
 from .lsh import HipLSHIndexer, HipLSHSearcher, make_projection
@@ -22,7 +22,7 @@ __all__ = [
     "CompositeAlgorithm", "IndexArtifact", "get_algorithm_instance", "get_indexer_class", "get_searcher_class",
     "register_algorithm", "register_indexer", "register_searcher", "HipExactSearch", "HipBruteForceIndexer",
     "HipLinearSearcher", "rerank_candidates", "FlatIndex", "merge_partials_device", "merge_packed_partials_device",
-    "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFSQ8Index", "parse_index_key",
+    "HipApproximateSearch", "HipIVFIndexer", "HipIVFSearcher", "IVFFlatIndex", "IVFI8Index", "IVFSQ8Index", "parse_index_key",
     "HipIVFPQIndexer", "HipIVFPQSearch", "IVFPQIndex", "parse_ivfpq_key",
     "HipKnnGraphIndexer", "HipKnnGraphSearcher", "HipKnnGraphSearch", "KnnGraphIndex",
     "HipLSHIndexer", "HipLSHSearcher", "make_projection", "HipLSHTableIndexer", "HipLSHTableSearcher", "HipLSHTables",

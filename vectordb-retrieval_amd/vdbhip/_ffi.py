@@ -77,6 +77,7 @@ SIGNATURES = {
     "vdb_ivf_sq8_set_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vdb_ivf_sq8_get_ranges": (c_int, [c_void_p, c_void_p, c_void_p]),
     "vdb_ivf_get_codes": (c_int, [c_void_p, c_void_p]),
+    "vdb_ivf_i8_get_rows": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "vdb_ivfpq_train": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_uint64, c_int]),
     "vdb_ivfpq_set_codebooks": (c_int, [c_void_p, c_int, c_void_p]),
     "vdb_ivfpq_get_codebooks": (c_int, [c_void_p, POINTER(c_int), c_void_p]),
