@@ -266,7 +266,8 @@ int vdb_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, float
  * a NaN radius.  VDB_ERR_UNSUPPORTED: the kinds of the table above, and any handle while option "graph" is 1.  A failed allocation
  * is VDB_ERR_NOMEM: the handle keeps its rows and loses only the result.
  * vdb_stats after a call: last_path = VDB_PATH_RANGE, last_nq, last_candidates = (query, row) pairs scored exactly,
- * last_fallback_queries = queries for which every row was a candidate, scan_dtype = 0; with option "timing", last_prep_ms = query
+ * last_fallback_queries = queries for which every row was a candidate, scan_dtype = 0 -- or 1 when, with option "range_i8", the
+ * int8 prefilter served the batch (DESIGN 4.13 "int8 prefilter"); with option "timing", last_prep_ms = query
  * statistics, bound and threshold, last_scan_ms = the prefilter (several slabs: from the first scan's start to the last one's end),
  * last_tail_ms = exact filter + emit. */
 int vdb_range_search(vdb_handle h, const float *q_host, int64_t nq, float radius, int64_t *lims_host);
@@ -807,6 +808,11 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *     "knng_build_block"  k-NN graph: rows per self-search block of vdb_knng_build, 0 (default: 65 536) .. 1e9
  *     "range_bitmap_mb" range search: MiB of candidate bitmap (one bit per query and row) a query slab may take, 0 (default: 256)
  *                       .. 4096; a batch whose bitmap is larger runs in several slabs (same results; at least one query per slab)
+ *     "range_i8"        range search: 0 (default) | 1: on a handle with an int8 scan copy in the 16-row MFMA layout (a byte-valued corpus of D <= 128
+ *                       above 15 360 rows, "int8_only" or not) an integer query batch inside the u8 or s8 window takes the int8 MFMA
+ *                       prefilter: integer thresholds, no error bound (IP: every candidate is a result; L2: a candidate that is not
+ *                       has its key in [radius, radius + 1)).  Decided on the device per call; any other batch runs as with 0 (on
+ *                       "int8_only": all rows, counted in last_fallback_queries).  Same results, bit for bit.  No effect elsewhere
  *     "filter_sparse_pairs"  filtered search: a call with fewer (query, admitted row) pairs than this takes the sparse route over the
  *                       list of admitted rows, 0 (never by this rule) .. inf, default 8192 (the measured crossover at D = 128, profiles/r21_bench_filter.json);
  *                       same results either way.  Set it

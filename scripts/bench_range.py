@@ -4,6 +4,9 @@
     --corpus bytes128   byte-valued 1M x 128, l2 (SIFT-shaped: integers 0..255; the index keeps its int8 copy, the fp16 copy serves
                         the range prefilter)
     --corpus unit384    unit vectors 1M x 384, ip
+    --corpus bytes128_i8  the corpus of bytes128 on two handles, the default one and an "int8_only" one: per leg option "range_i8" off
+                        (the fp16 prefilter / all rows), on (the int8 prefilter) and vdb_search_device(k = 10), alternating call by
+                        call; the all-rows leg of the "int8_only" handle is run at 1 and 64 queries only (10 000 x 1M exact keys)
 
 Batches of 1, 64 and 10 000 queries.  Radii: those at which the same handle's vdb_search gives a median 10th and 100th neighbour
 distance over the batch of 10 000 -- about 10 and about 100 results per query.  Everything is device-resident.  Per leg, in the same
@@ -38,12 +41,14 @@ TORCH_CHUNK_ROWS = 65_536
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--corpus", choices=["gauss128", "bytes128", "unit384"], required=True)
+    ap.add_argument("--corpus", choices=["gauss128", "bytes128", "unit384", "bytes128_i8"], required=True)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "r20_bench_range.json"))
     args = ap.parse_args()
+    if args.corpus == "bytes128_i8":
+        return main_i8(args)
     import torch
 
     import vdbhip
@@ -140,6 +145,110 @@ def main() -> int:
               "scan_shape": built["scan_shape"], "has_i8_copy": built["has_i8_copy"], "range_bitmap_mb": 256,
               "bytes_resident_after": idx.stats()["bytes_resident"], "legs": legs}
     idx.close()
+    out = Path(args.out)
+    merged = json.loads(out.read_text()) if out.exists() else {}
+    merged[args.corpus] = result
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(merged, indent=1) + "\n")
+    print(json.dumps(result))
+    return 0
+
+
+def main_i8(args) -> int:
+    import torch
+
+    import vdbhip
+
+    dev = torch.device("cuda:0")
+    n, nq_max, d = args.n, max(BATCHES), 128
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    X_t = torch.clamp(torch.round(torch.empty((n, d), device=dev).exponential_(1.0 / 30.0, generator=g)), 0, 255)
+    Q_t = torch.clamp(torch.round(torch.empty((nq_max, d), device=dev).exponential_(1.0 / 30.0, generator=g)), 0, 255)
+    stream = torch.cuda.current_stream().cuda_stream
+    Dk = torch.empty((nq_max, 100), dtype=torch.float32, device=dev)
+    Ik = torch.empty((nq_max, 100), dtype=torch.int64, device=dev)
+    lims_t = torch.empty((nq_max + 1,), dtype=torch.int64, device=dev)
+    out_buf = {"D": torch.empty((1,), dtype=torch.float32, device=dev), "I": torch.empty((1,), dtype=torch.int64, device=dev)}
+
+    def event_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    result = {"corpus": args.corpus, "n": n, "dim": d, "metric": "l2", "steps": args.steps, "warmup": args.warmup, "handles": {}}
+    radii = None
+    for handle in ("default", "int8_only"):
+        idx = vdbhip.FlatIndex(d, "l2", 0)
+        if handle == "int8_only":
+            idx.set_option("int8_only", 1)
+        idx.add_device(X_t.data_ptr(), n, 0, stream)
+        torch.cuda.synchronize()
+        built = idx.stats()
+        if radii is None:
+            idx.search_device(Q_t.data_ptr(), nq_max, 100, Dk.data_ptr(), Ik.data_ptr(), stream)
+            torch.cuda.synchronize()
+            radii = {"10": float(Dk[:, 9].median()), "100": float(Dk[:, 99].median())}
+
+        def run_range(on, nq, r):          # (the option is set by the caller, outside any timed region)
+            total = idx.range_search_device(Q_t.data_ptr(), nq, r, lims_t.data_ptr(), stream)
+            if total > out_buf["D"].numel():
+                out_buf["D"] = torch.empty((total + total // 4,), dtype=torch.float32, device=dev)
+                out_buf["I"] = torch.empty((total + total // 4,), dtype=torch.int64, device=dev)
+            idx.range_results_device(out_buf["D"].data_ptr(), out_buf["I"].data_ptr(), stream)
+            return total
+
+        legs = {}
+        for nq in BATCHES:
+            for name, r in radii.items():
+                option = {"on": 1, "off": 0}
+                calls = {"on": lambda: run_range(1, nq, r), "knn_k10": lambda: idx.search_device(Q_t.data_ptr(), nq, K, Dk.data_ptr(), Ik.data_ptr(), stream)}
+                if handle == "default" or nq <= 64:
+                    calls["off"] = lambda: run_range(0, nq, r)
+                times = {c: [] for c in calls}
+                for step in range(args.warmup + args.steps):
+                    for c, fn in calls.items():
+                        if c in option:
+                            idx.set_option("range_i8", option[c])
+                        ms = event_ms(fn)
+                        if step >= args.warmup:
+                            times[c].append(ms)
+                # slabs as range_plan.hpp sizes them: bitmap rows of whole 1024-row spans under 256 MiB, whole 128-query tiles
+                fit = (256 << 20) // ((n + 1023) // 1024 * 32 * 4)
+                per_slab = max(1, min(fit - fit % 128 if fit >= 128 else fit, 1 << 20, nq))
+                leg = {"nq": nq, "radius": r, "slabs": -(-nq // per_slab)}
+                for c in calls:
+                    leg[f"{c}_ms"] = statistics.median(times[c])
+                    leg[f"{c}_ms_min_max"] = [min(times[c]), max(times[c])]
+                for on in ([1, 0] if "off" in calls else [1]):
+                    idx.set_option("range_i8", on)
+                    total = run_range(on, nq, r)
+                    st = idx.stats()
+                    idx.set_option("timing", 1)
+                    for _ in range(args.steps):
+                        run_range(on, nq, r)
+                    torch.cuda.synchronize()
+                    tm = idx.stats()
+                    idx.set_option("timing", 0)
+                    tag = "on" if on else "off"
+                    leg.update({f"{tag}_total_results": int(total), f"{tag}_candidates": int(st["last_candidates"]),
+                                f"{tag}_candidates_per_result": st["last_candidates"] / max(total, 1), f"{tag}_scan_dtype": int(st["scan_dtype"]),
+                                f"{tag}_fallback_queries": int(st["last_fallback_queries"]), f"{tag}_prep_ms": tm["last_prep_ms"],
+                                f"{tag}_scan_ms": tm["last_scan_ms"], f"{tag}_tail_ms": tm["last_tail_ms"]})
+                idx.set_option("timing", 1)                          # the k-NN scan of the same handle, for the prefilter's ratio
+                for _ in range(args.steps):
+                    idx.search_device(Q_t.data_ptr(), nq, K, Dk.data_ptr(), Ik.data_ptr(), stream)
+                torch.cuda.synchronize()
+                leg["knn_scan_ms"] = idx.stats()["last_scan_ms"]
+                idx.set_option("timing", 0)
+                legs[f"nq{nq}_about{name}"] = leg
+                print(handle, json.dumps(leg), flush=True)
+        result["handles"][handle] = {"scan_shape": built["scan_shape"], "has_i8_copy": built["has_i8_copy"],
+                                     "bytes_resident_after": idx.stats()["bytes_resident"], "legs": legs}
+        idx.close()
     out = Path(args.out)
     merged = json.loads(out.read_text()) if out.exists() else {}
     merged[args.corpus] = result

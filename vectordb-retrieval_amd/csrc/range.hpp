@@ -47,11 +47,13 @@ struct RangeThrArgs {
     float *thr;              // [nq]
     int *flag;               // [nq]
     unsigned long long *stat;    // sharded counters: [1] += fallback queries
+    int i8_gate = 0;         // option "range_i8" on a handle with both prefilters: nothing to do for a batch the int8 one serves
 };
 
 __global__ __launch_bounds__(256) void range_thr_kernel(RangeThrArgs a) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= a.nq) return;
+    if (a.i8_gate && a.info->i8_mode) return;
     const bool none = a.metric == 0 ? !(a.radius > 0.f) : a.radius == __builtin_inff();
     float thr = -3.402823466e+38f;
     int all = 0;
@@ -97,8 +99,11 @@ struct RangeScanArgs {
 
 // layout "x16" (D <= 128): accumulator register i of lane l, tile t, row block rb: query 16 qb + (l & 15), corpus row
 // 512 s + 128 (l >> 4) + 8 t + 4 rb + i  ->  bit 8 (t & 3) + 4 rb + i of the lane's word t >> 2
-template <int KS2>
+// (I8GATE: option "range_i8" on a handle that also has the int8 prefilter, range_i8.hpp -- a batch that one serves is left to it;
+//  the choice is made on the device, as between the two scans of vdb_search.  false is the kernel as it always was.)
+template <int KS2, bool I8GATE = false>
 __global__ __launch_bounds__(256) void range_scan_x16_kernel(RangeScanArgs a) {
+    if (I8GATE && a.info->i8_mode) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
     const int64_t span = blockIdx.x;
     const int64_t qb0 = ((int64_t)blockIdx.y * 4 + wave) * 2;

@@ -10,6 +10,10 @@ constexpr unsigned kRangeCalls = kFlat | kLsh | kLsht | kKnng;
 inline bool range_has_scan(const vdb_index_s *h) {
     return h->scan_ok && !h->panels_streamed && !h->int8_only && h->scan.panels.p && h->scan.bias.p && (h->x16 || h->tile16);
 }
+// ... or, with option "range_i8", an int8 copy in layout "x16" (range_i8.hpp): the default byte-valued handle and the "int8_only" one
+inline bool range_has_scan_i8(const vdb_index_s *h) {
+    return h->scan_ok && range_i8_route(h->opt.range_i8, h->i8_ok, h->x16, h->scan.panels8.p != nullptr, h->scan.bias8.p != nullptr);
+}
 
 void range_check(vdb_index_s *h, const char *what, const void *q, int64_t nq, float radius, const void *lims) {
     admit(h, what, kRangeCalls);
@@ -33,7 +37,8 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
     const int D = h->dim, D4 = h->D4, ks32 = h->ksteps / 2;
     const int64_t N = h->N, W = range_words(N);
     const int S = (int)range_segments(N);
-    const bool scan = range_has_scan(h);
+    const bool scan16 = range_has_scan(h), scan8 = range_has_scan_i8(h), scan = scan16 || scan8;
+    const int ks2_8 = h->i8_ks / 2;           // 64-dim k-steps of the int8 copy
     const int64_t slab = range_slab_queries(nq, N, h->opt.range_bitmap_mb);
     const int64_t slab_pad = (slab + 31) / 32 * 32;
     const size_t stat_bytes = (size_t)kStatShards * kStatStride * sizeof(unsigned long long);
@@ -43,8 +48,13 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
     rb.seg.reserve((size_t)slab * S * sizeof(int));
     rb.qtot.reserve((size_t)slab * sizeof(int64_t));
     if (D4 != D) rb.qpad.reserve((size_t)nq * D4 * sizeof(float));
-    if (scan) {
-        rb.info.reserve(sizeof(QueryBatchInfo));
+    if (scan) rb.info.reserve(sizeof(QueryBatchInfo));
+    if (scan8) {
+        rb.thr8.reserve((size_t)nq * sizeof(int));
+        rb.flag.reserve((size_t)nq * sizeof(int));
+        rb.qpanels8.reserve((size_t)(range_i8_grid(slab, W).qpad / 16) * ks2_8 * 64 * sizeof(int4v));
+    }
+    if (scan16) {
         rb.eps.reserve((size_t)nq * sizeof(float));
         rb.thr.reserve((size_t)nq * sizeof(float));
         rb.flag.reserve((size_t)nq * sizeof(int));
@@ -55,6 +65,7 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
     h->last.last_path = VDB_PATH_RANGE;
     h->last.last_nq = nq;
     h->range_cand = h->range_fb = 0;
+    h->range_dtype = 0;
     const long tslot = timing_begin(h, st);
     const float *qp = dq;
     if (D4 != D) {
@@ -65,12 +76,19 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
         VDB_HIP(hipMemsetAsync(rb.info.p, 0, sizeof(QueryBatchInfo), st));
         const int64_t total = nq * D;
         query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, rb.info.as<QueryBatchInfo>(),
-            FinalizeArgs{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, 0});
+            FinalizeArgs{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2, scan8 ? 5 : 0});
+        if (scan8) {      // integer thresholds of an integer batch; on an "int8_only" handle the flags of any other
+            RangeThr8Args t8{dq, nq, D, h->metric, radius, h->i8_cx, scan16 ? 0 : 1, rb.info.as<QueryBatchInfo>(), rb.thr8.as<int>(),
+                             rb.flag.as<int>(), rb.stat.as<unsigned long long>()};
+            range_thr8_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(t8);
+        }
+    }
+    if (scan16) {
         EpsArgs ea{dq, nq, D, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f, h->corpus_fp16_exact ? 1 : 0,
                    h->corpus_int_unscaled ? 1 : 0, h->sx, rb.info.as<QueryBatchInfo>(), rb.eps.as<float>()};
         query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
         RangeThrArgs ta{dq, nq, D, h->metric, radius, rb.info.as<QueryBatchInfo>(), rb.eps.as<float>(), rb.thr.as<float>(),
-                        rb.flag.as<int>(), rb.stat.as<unsigned long long>()};
+                        rb.flag.as<int>(), rb.stat.as<unsigned long long>(), scan8 ? 1 : 0};
         range_thr_kernel<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st>>>(ta);
         VDB_HIP(hipGetLastError());
     }
@@ -78,7 +96,24 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
     for (int64_t q0 = 0; q0 < nq; q0 += slab) {
         const int64_t n = std::min<int64_t>(slab, nq - q0);
         if (q0 == 0) timing_mark(h, tslot, 0, st);
-        if (scan) {
+        if (scan8) {      // the int8 prefilter: writes the slab's bitmap when the batch is its to serve (on "int8_only": always)
+            const RangeI8Grid g8 = range_i8_grid(n, W);
+            const int64_t threads = (g8.qpad / 32) * h->i8_ks * 64;
+            build_qpanels_i8_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq + (size_t)q0 * D, n, D, h->i8_ks, g8.qpad / 32,
+                                                                                                 rb.info.as<QueryBatchInfo>(), rb.qpanels8.as<int4v>(), 1);
+            RangeI8Args a8{h->scan.panels8.as<int4v>(), h->scan.bias8.as<int32_t>(), rb.qpanels8.as<int4v>(), rb.info.as<QueryBatchInfo>(),
+                           rb.thr8.as<int>() + q0, rb.flag.as<int>() + q0, n, N, h->Npad, W, h->Npad / kSpanRows, W / kRangeI8SpanWords,
+                           g8.spans_per_chunk, scan16 ? 0 : 1, rb.bitmap.as<unsigned>()};
+            const dim3 grid8(g8.chunks, g8.qtiles);
+            if (ks2_8 == 1) {
+                if (g8.cb == 8) range_scan_i8x16_kernel<1, 8><<<grid8, dim3(kRangeI8Waves * 64), 0, st>>>(a8);
+                else range_scan_i8x16_kernel<1, 4><<<grid8, dim3(kRangeI8Waves * 64), 0, st>>>(a8);
+            } else {
+                if (g8.cb == 8) range_scan_i8x16_kernel<2, 8><<<grid8, dim3(kRangeI8Waves * 64), 0, st>>>(a8);
+                else range_scan_i8x16_kernel<2, 4><<<grid8, dim3(kRangeI8Waves * 64), 0, st>>>(a8);
+            }
+        }
+        if (scan16) {
             const int64_t npad = (n + 31) / 32 * 32;
             const int64_t threads = (npad / 16) * ks32 * 64;
             build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq + (size_t)q0 * D, n, D, ks32, npad / 16,
@@ -92,10 +127,13 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
             } else {
                 sa.nspans = h->Npad / kSpanRows;
                 const dim3 grid((unsigned)(W / (kSpanRows / kRangeWordBits)), qtiles);
-                if (ks32 == 2) range_scan_x16_kernel<2><<<grid, dim3(256), 0, st>>>(sa);
+                if (scan8) {      // ... and leaves an integer batch to the int8 prefilter
+                    if (ks32 == 2) range_scan_x16_kernel<2, true><<<grid, dim3(256), 0, st>>>(sa);
+                    else range_scan_x16_kernel<4, true><<<grid, dim3(256), 0, st>>>(sa);
+                } else if (ks32 == 2) range_scan_x16_kernel<2><<<grid, dim3(256), 0, st>>>(sa);
                 else range_scan_x16_kernel<4><<<grid, dim3(256), 0, st>>>(sa);
             }
-        } else {
+        } else if (!scan8) {
             range_fill_kernel<<<dim3((unsigned)((n * W + 255) / 256)), dim3(256), 0, st>>>(rb.bitmap.as<unsigned>(), n, W, N);
         }
         VDB_HIP(hipGetLastError());
@@ -132,12 +170,15 @@ void range_search_impl(vdb_index_s *h, const float *dq, int64_t nq, float radius
     timing_mark(h, tslot, 2, st);
     std::vector<unsigned long long> c((size_t)kStatShards * kStatStride);
     VDB_HIP(hipMemcpyAsync(c.data(), rb.stat.p, stat_bytes, hipMemcpyDeviceToHost, st));
+    QueryBatchInfo qi{};
+    if (scan8) VDB_HIP(hipMemcpyAsync(&qi, rb.info.p, sizeof(qi), hipMemcpyDeviceToHost, st));
     VDB_HIP(hipStreamSynchronize(st));
     for (int sh = 0; sh < kStatShards; ++sh) {
         h->range_cand += (int64_t)c[(size_t)sh * kStatStride];
         h->range_fb += (int64_t)c[(size_t)sh * kStatStride + 1];
     }
     if (!scan) h->range_fb = nq;
+    h->range_dtype = qi.i8_mode ? 1 : 0;      // the int8 prefilter served the batch
     h->range_total = total;
     h->range_nq = nq;
     h->range_valid = true;

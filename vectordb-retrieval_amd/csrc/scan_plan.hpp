@@ -73,6 +73,8 @@ struct Options {
     int knng_visited_bits = 0;               // log2 slots of the per-query seen filter (0 = default)
     int knng_build_block = 0;                // rows per self-search block of the build (0 = default)
     int range_bitmap_mb = 0;                 // range search (range_plan.hpp): MiB of candidate bitmap per query slab (0 = default 256)
+    int range_i8 = 0;                        // range search: 1 = integer query batches take the int8 prefilter (range_i8.hpp) on a handle
+                                             // with an int8 scan copy in layout "x16"; an "int8_only" handle then has a prefilter at all
     int64_t filter_sparse_pairs = kFilterSparsePairsDefault;   // filtered search (filter_plan.hpp, kFilterSparsePairsDefault): (query, admitted row) pairs below which the sparse route serves a call
     // tuning of the flat scans
     int i8_variant = 3;                      // (variant 3: +2 % over 0 on the bench shape, scripts/sweep_i8.py)

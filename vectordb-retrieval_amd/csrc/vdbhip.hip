@@ -39,6 +39,7 @@
 #include "ivf_pq_adc.hpp"
 #include "knng.hpp"
 #include "range.hpp"
+#include "range_i8.hpp"
 #include "filter.hpp"
 #include "ivf_filter.hpp"
 #include "ivf_range.hpp"
@@ -255,6 +256,7 @@ struct RangeBufs {
     DevBuf lims{"range.lims"}, D{"range.D"}, I{"range.I"};
     DevBuf bitmap{"range.bitmap"}, seg{"range.seg"}, qtot{"range.qtot"}, stat{"range.stat"};
     DevBuf qstage{"range.qstage"}, qpad{"range.qpad"}, qpanels{"range.qpanels"}, info{"range.info"}, eps{"range.eps"}, thr{"range.thr"}, flag{"range.flag"};
+    DevBuf thr8{"range.thr8"}, qpanels8{"range.qpanels8"};      // option "range_i8": integer thresholds, int8 B fragments of a slab
 };
 
 // the installed filter of the handle (filter.inc): the allow words (tail clean, padded to Npad rows), the masked copies of the
@@ -401,6 +403,7 @@ struct vdb_index_s {
     // vdb_reset, vdb_set_option, vdb_ivf_set_centroids and vdb_ivf_train drop it)
     bool range_valid = false;
     int64_t range_total = 0, range_nq = 0;   // lims[nq] and nq of that result
+    int range_dtype = 0;                     // scan_dtype of that call: 1 = the int8 prefilter served the batch (option "range_i8")
     int64_t range_cand = 0, range_fb = 0;    // (query, row) pairs scored exactly / queries for which every row was a candidate
     // the installed filter (filter.inc): `filter` holds it while filter_valid (any add, vdb_reset, vdb_set_option and a change of
     // kind drop it)
@@ -504,6 +507,7 @@ constexpr OptionRow kOptions[] = {
     {"knng_visited_bits", &Options::knng_visited_bits, 0, {0, 14}},  // k-NN graph: log2 slots of the seen filter (0 = default; never changes a result)
     {"knng_build_block", &Options::knng_build_block, 0, {0, 1e9}},   // k-NN graph: rows per self-search block of the build (0 = default 65 536)
     {"range_bitmap_mb", &Options::range_bitmap_mb, 0, {0, 4096}},    // range search: MiB of candidate bitmap per query slab (0 = default 256)
+    {"range_i8", &Options::range_i8, 2, {0, 1}},                     // range search: 1 = integer batches of a handle with an int8 copy in layout "x16" take the int8 prefilter
     {"filter_sparse_pairs", nullptr, 0, {0, HUGE_VAL}, 0, 0, &Options::filter_sparse_pairs},   // filtered search: (query, admitted row) pairs below which the sparse route serves a call (0 = never by this rule)
     {"i8_variant", &Options::i8_variant, 0, {0, 7}},
     {"i8_group", &Options::i8_group, 2, {4, 8}, 0, 4},               // rows per select group of the int8 scan: 8 (octs, default) or 4 (quads)
@@ -1483,6 +1487,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         }
         if (h->last.last_path == VDB_PATH_RANGE || h->last.last_path == VDB_PATH_IVF_RANGE) {     // (the call read its counters back when it sized the result)
             s.last_candidates = h->range_cand;
+            if (h->last.last_path == VDB_PATH_RANGE) s.scan_dtype = h->range_dtype;
             s.last_fallback_queries = h->range_fb;
         }
         if (h->last.last_path == VDB_PATH_FILTER_ROWS) s.last_candidates = h->filter_cand;     // (sparse route: nq x admitted rows)
