@@ -91,6 +91,8 @@ __host__ __device__ inline int group_rows_of(int i8_mode) { return (i8_mode & 4)
 __host__ __device__ inline int cand_row_offset(unsigned packed_bits, int i8_mode) {
     return (int)(packed_bits & 0x3Fu) * group_rows_of(i8_mode);
 }
+// (D <= 128: the constant offset below holds every t' in 25 bits.  D > 128, option "i8_kloop": offset and a right shift per handle,
+//  i8k_plan.hpp; padding rows and "+inf" keep these values)
 constexpr int kI8Offset = 1 << 24;
 constexpr int kI8PadBias = 30000000;          // accumulator init of padding rows: above every real t', (t' << 6) < +inf bits
 constexpr unsigned kI8Inf = 0x7f800000u;      // "+inf" of the packed integer keys (bits of float +inf)

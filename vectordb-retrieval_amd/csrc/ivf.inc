@@ -272,6 +272,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
     IndexStats hs;
     VDB_HIP(hipMemcpy(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost));
     h->corpus_fp16_exact = hs.not_fp16_exact == 0;
+    h->i8k_ok = false;                                        // (the int8 K-loop copy is a flat handle's)
     h->i8_ok = h->i8_ok && !h->tile16 && h->ivf_codec == 0;   // (an SQ8 / IVF-PQ index keeps no int8 copies)
     if (h->i8_ok) {      // byte-valued rows: int8 copy of the same panel space (scan_i8.hpp)
         h->i8_ks = h->dim <= 64 ? 2 : 4;

@@ -128,6 +128,7 @@ void pq_rebuild(vdb_index_s *h, hipStream_t st) {
     h->int8_only = false;
     h->panels_streamed = false;
     h->i8_ok = false;
+    h->i8k_ok = false;
     h->tile16 = h->ksteps > kMaxKSteps;          // (D > 128: p16 panels; D <= 128: layout "x16" -- the slab is made per search either way)
     h->x16 = !h->tile16;
     const int64_t span_rows = h->tile16 ? kSpanRows16 : kSpanRows;

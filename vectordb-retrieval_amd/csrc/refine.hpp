@@ -50,7 +50,7 @@ struct RefineCommon {
     int metric;
     int k;
     const int64_t *idmap;  // optional: id of row r is idmap[r] (IVF: rows are grouped by list), else id_base + r
-    // byte-valued corpora (scan_i8.hpp): row-major int8 copy x - cx, x8_pitch = 64 or 128 bytes per row (padding bytes
+    // byte-valued corpora (scan_i8.hpp): row-major int8 copy x - cx, x8_pitch = 64 or 128 bytes per row, D padded to 64 on the int8 K-loop copy (padding bytes
     // hold -cx, i.e. x = 0), rowstat[row] = {sum x^2, sum x}, and Q8 = the batch's int8 query rows cq - q (padding 0).
     // When the batch is integer too (info->i8_mode) the list refine scores from them in exact integer arithmetic with
     // v_dot4c_i32_i8 (query row in SGPRs): the results are the same integers the float64 chain produces, so the keys are
@@ -322,6 +322,8 @@ struct RefineListArgs {
 // sits in SGPRs; per row  dot = sum (x - cx)(cq - q)  by W v_dot4c, and with n2 = sum x^2, s1 = sum x of the row
 //   x.q     = -dot + cq s1 + cx sum(q) - D cx cq          ||x - q||^2 = n2 - 2 x.q + sum(q^2)
 // -- all exact integers below 2^27, equal to what the canonical float64 chain computes on these integer inputs.
+// W = 0 (the int8 K-loop copy, D > 128: pitch = D padded to 64, up to 4096 bytes): the query row does not fit the SGPRs and is
+// read per 16 bytes through the scalar cache inside the row loop; the integers stay below 2^30 (D <= 4096), exact in float64.
 template <int KPL, int W, bool ALLOW = true>
 __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_t q, int ncand, int nres, int gshift,
                                                  WaveTopK<KPL> &tk) {
@@ -329,10 +331,11 @@ __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_
     const RefineCommon &c = a.c;
     const int mode = c.info->i8_mode;
     const int cq = (mode & 3) == 1 ? 127 : -1;
-    int qb[W];
+    int qb[W > 0 ? W : 1];
     const int *q8 = reinterpret_cast<const int *>(c.Q8 + (size_t)q * c.x8_pitch);      // wave-uniform: scalar loads
 #pragma unroll
     for (int w = 0; w < W; ++w) qb[w] = __builtin_amdgcn_readfirstlane(q8[w]);
+    const int nvec = c.x8_pitch / 16;
     // per query: sum q, sum q^2 (q holds integers)
     int sq = 0, sqq = 0;
     const float *qf = c.Q + (size_t)q * c.D4;
@@ -351,6 +354,16 @@ __device__ __forceinline__ void refine_list_dot8(const RefineListArgs &a, int64_
         const refine_int4 *xr = reinterpret_cast<const refine_int4 *>(c.X8 + (size_t)row * c.x8_pitch);
         const int2 st = reinterpret_cast<const int2 *>(c.rowstat)[row];
         int dot = 0;
+        if (W == 0) {
+#pragma unroll 4
+            for (int i = 0; i < nvec; ++i) {
+                const refine_int4 w = xr[i], b = reinterpret_cast<const refine_int4 *>(q8)[i];
+                dot = __builtin_amdgcn_sdot4(w.x, b.x, dot, false);
+                dot = __builtin_amdgcn_sdot4(w.y, b.y, dot, false);
+                dot = __builtin_amdgcn_sdot4(w.z, b.z, dot, false);
+                dot = __builtin_amdgcn_sdot4(w.w, b.w, dot, false);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < W / 4; ++i) {
             const refine_int4 w = xr[i];
@@ -403,7 +416,8 @@ __device__ __forceinline__ void refine_list_body(const RefineListArgs &a, unsign
     const int gshift = a.group_shift >= 0 ? a.group_shift : mode ? ((mode & 4) ? 3 : 2) : a.f16_shift;   // a candidate = 4 or 8 (or 1 / 2) consecutive rows
     if (mode != 0 && a.c.X8 != nullptr) {                        // integer batch on a byte-valued corpus: int8 rows
         if (a.c.x8_pitch == 64) refine_list_dot8<KPL, 16, ALLOW>(a, q, ncand, nres, gshift, tk);
-        else refine_list_dot8<KPL, 32, ALLOW>(a, q, ncand, nres, gshift, tk);
+        else if (a.c.x8_pitch == 128) refine_list_dot8<KPL, 32, ALLOW>(a, q, ncand, nres, gshift, tk);
+        else refine_list_dot8<KPL, 0, ALLOW>(a, q, ncand, nres, gshift, tk);
     } else {
         for (int base = 0; base < (ncand << gshift); base += 64) {
             const int i = base + lane;

@@ -62,6 +62,7 @@ __global__ __launch_bounds__(512, 2) void scan16_kloop_kernel(ScanArgs a, ScanKl
     const int KS = ex.ksteps / 2, nK = KS / 2;              // 32-dim k-steps; 64-dim K-steps
     const int64_t q0 = (int64_t)qt * (NWAVES * 16 * CB) + wave * (16 * CB);
     const float cs = a.info->cs;
+    if (a.info->i8_mode) return;                            // this batch is served by scan16_i8_kloop_kernel (scan16_i8.hpp; option "i8_kloop")
 
     const int64_t span0 = chunk_span0(chunk, a.spans_per_chunk, a.chunk_rem);
     int64_t span1 = chunk_span0(chunk + 1, a.spans_per_chunk, a.chunk_rem);

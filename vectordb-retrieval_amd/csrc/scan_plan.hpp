@@ -42,6 +42,10 @@ struct Options {
     // default index; a batch with a non-integer value is scanned in fp16 over slabs converted from the int8 panels per search;
     // the exact kernels read x = byte + cx from the int8 rows (same float64 chains, same keys).  One add builds it (no append).
     int int8_only = 0;
+    // "i8_kloop" (takes effect at the next add; flat index, D > 128, more than 2048 rows, byte-valued corpus): an int8 scan copy in
+    // p16 order next to the fp16 one; integer query batches inside a byte window take the int8 K-loop scan (scan16_i8.hpp; the
+    // build, key and launch rules: i8k_plan.hpp).  Same results.
+    int i8_kloop = 0;
     int int8_slab_chunks = 0;                // scan chunks per converted fp16 slab (0 = default 8)
     int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests), and of an add to an
                                              // IVF-I8 index (0 = 1M): the float32 rows of one block are all the device holds of them

@@ -117,6 +117,7 @@ struct Batch {
     bool adc;                    // PQ: the bin records come from the lookup-table scan of the codes (search_scan_adc), not from panels
     const float *bias;           // accumulator inits the scans of this batch read: the handle's, or (a filtered search, filter.inc) the
     const int32_t *bias8;        // masked copies of its filter -- rc.allow is set with them
+    bool i8k;                    // the int8 K-loop scan is offered to this batch (i8k_plan.hpp, i8k_serves)
 };
 
 // the S partial lists per slot that an exhaustive pass (fa) left in its (pkeys, pids), merged into the outputs of the batch
@@ -327,7 +328,7 @@ void scan_query_prep(const Batch &b, int64_t Qpad, bool use_i8, QueryBatchInfo *
     hipStream_t st = b.st;
     const int64_t total = nq * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                           use_i8 ? (1 | ((h->opt.i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only)
+                           b.i8k ? 1 : use_i8 ? (1 | ((h->opt.i8_group == 8 || h->x16) ? 4 : 0)) : 0};      // (layout "x16": octs only; the K-loop scans: quads)
     const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;   // (serving shapes, scan_i8.hpp)
     if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
     h->info_valid_nq = nq;
@@ -337,6 +338,13 @@ void scan_query_prep(const Batch &b, int64_t Qpad, bool use_i8, QueryBatchInfo *
     if (h->tile16) {
         build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->ksteps / 2, Qpad / 16, info, ws.qpanels.as<half8>());
         query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
+        if (b.i8k) {    // int8 B fragments in the 16-query form, 64 dims per K-step, and the int8 query rows of the refine (both
+                        // return at once unless the device chose the int8 scan for this batch)
+            const int64_t t8 = (Qpad / 32) * h->i8_ks * 64;
+            ws.qpanels8.reserve((size_t)t8 * sizeof(int4v));
+            build_qpanels_i8_kernel<<<dim3((unsigned)((t8 + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->i8_ks, Qpad / 32, info, ws.qpanels8.as<int4v>(), 1);
+            ivf_qrows_i8_kernel<<<dim3((unsigned)((nq * h->rows8_pitch + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->rows8_pitch, info, ws.qrows8.as<signed char>());
+        }
     } else {            // one dispatch: fp16 fragments | int8 fragments | int8 query rows | error bounds (scan_i8.hpp)
         QueryPrepArgs qp{};
         qp.Q = dq; qp.nq = nq; qp.nqtiles = Qpad / 32;
@@ -693,6 +701,16 @@ void search_scan(const Batch &b) {
         launch(pair, h, &sa, &s8, st);
     } else {
         scan_fp16(b, sa, Qpad, nw);
+        if (b.i8k) {    // the int8 K-loop scan: the grid and block order of the fp16 one, the int8 operands behind the same arguments
+            const ScanLaunch pf = plan_f16(b.shape, h->opt, g.nchunks, Qpad, nq, 0, nw);
+            ScanArgs s8 = sa;
+            s8.panels = reinterpret_cast<const half8 *>(h->scan.panels8.p);
+            s8.bias = reinterpret_cast<const float *>(h->scan.bias8.p);
+            s8.qpanels = reinterpret_cast<const half8 *>(ws.qpanels8.p);
+            s8.nqtiles = pf.nqtiles;
+            scan16_i8_kloop_kernel<kI8kBarrierSteps><<<dim3(pf.grid), dim3(512), 0, st>>>(s8, ScanI8KloopExtra{h->i8_ks / 2, pf.qgroup, h->i8k_key.shift, h->Npad});
+            VDB_HIP(hipGetLastError());
+        }
         if (i8) {
             const ScanI8Args s8 = scan_i8_args(b, sa, Qpad);
             launch(plan_i8(b.shape, h->opt, g.nchunks, Qpad, nq, nw), h, nullptr, &s8, st);
@@ -755,6 +773,19 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                (h->opt.force_path == 2 || h->N >= 32768 || (h->Npad > 8192 && (double)nq * (double)h->N >= 4.0e6));
     // (corpora of 8193..15360 rows whose chunking cannot give 4k superbins still have the dense path below)
 
+    // option "i8_kloop": the int8 K-loop copy of a p16 handle serves this batch's scan and refine when the launch rule admits it
+    const bool i8k = use_scan && i8k_serves(h->i8k_ok && kind_of(h) == kFlat && h->scan.panels8.p && h->scan.rows8.p, h->opt.panel_dtype, direct_rows,
+                                            h->panels_streamed, filtered);
+    if (i8k) {
+        rc.X8 = h->scan.rows8.as<signed char>();
+        rc.rowstat = h->scan.rowstat8.as<int>();
+        rc.x8_pitch = h->rows8_pitch;
+        rc.cx = h->i8_cx;
+        rc.D = Dm;
+        ws.qrows8.reserve((size_t)nq * h->rows8_pitch);
+        rc.Q8 = ws.qrows8.as<signed char>();
+    }
+
     // (PQ, option "pq_adc_max_batch": batches up to that size on the standard 256-row-bin geometry take the lookup-table scan of the
     //  codes -- pq_adc.hpp -- unless the table of M sub-spaces does not fit a workgroup's LDS)
     const bool use_adc = pq_on(h) && use_scan && direct_rows == 0 && nq <= h->opt.pq_adc_max_batch && pq_adc_fits(h->pq.M);
@@ -783,7 +814,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
     const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, shape, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc,
                   filtered ? h->filter.bias_f.as<float>() : h->scan.bias.as<float>(),
-                  filtered ? h->filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>()};
+                  filtered ? h->filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>(), i8k};
     if (use_dense) search_dense(b);
     else if (!use_scan) search_exact(b);
     else search_scan(b);

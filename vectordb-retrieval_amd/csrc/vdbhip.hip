@@ -22,6 +22,7 @@
 #include "scan.hpp"
 #include "scan16.hpp"
 #include "scan_i8.hpp"
+#include "scan16_i8.hpp"
 #include "scan_i8x16.hpp"
 #include "scan_x16.hpp"
 #include "ivf.hpp"
@@ -321,6 +322,10 @@ struct vdb_index_s {
     bool x16 = false;                        // the flat scan copies (fp16 and int8, D <= 128) are in layout "x16": 16x16x32 f16 / 16x16x64 i8 MFMA,
                                              // octs only (scan_x16.hpp, scan_i8x16.hpp); corpora the dense small-corpus path serves keep 32-row tiles
     bool int8_only = false;                  // option "int8_only" took effect at the last add: only the int8 copies are kept (build_int8_only)
+    bool i8k_ok = false;                     // option "i8_kloop" took effect at the last add: a p16 handle (D > 128) with the int8 K-loop copy
+                                             // (scan16_i8.hpp) in scan.panels8 / bias8 / rowstat8 / rows8; i8_ok stays false on it -- filters and
+                                             // range searches, which bake in the D <= 128 key constants, never see the copy
+    I8KeyRule i8k_key;                       // ... and its key format (i8k_plan.hpp)
     // a captured device-resident search (option "graph", graph_or_run)
     struct GraphKey {
         const void *q = nullptr, *o1 = nullptr, *o2 = nullptr;
@@ -336,6 +341,7 @@ struct vdb_index_s {
     uint64_t graph_epoch = 0;                // g_alloc_epoch when the graph was captured
     int64_t graph_replays = 0;
     int i8_cx = 0, i8_ks = 0;
+    bool i8_byte_valued = false;             // index_stats: every value is an integer of the u8 or of the s8 window (any D)
     int i8_min = 0, i8_max = 0;              // IVF-I8 (ivf_i8.inc): smallest / largest value of the filed rows -- an append re-chooses the byte window over old and new rows
     // host copies of the corpus statistics
     float absmax = 0.f, maxnorm2 = 0.f, sx = 1.f;
@@ -485,6 +491,7 @@ constexpr OptionRow kOptions[] = {
     {"list_cap", &Options::list_cap, 0, {0, 65536}},
     {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
     {"int8_only", &Options::int8_only, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::int8_only},
+    {"i8_kloop", &Options::i8_kloop, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::i8k_ok},   // D > 128, next add: 1 = a byte-valued corpus also gets the int8 K-loop scan copy
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -766,7 +773,8 @@ void index_stats(vdb_index_s *h, hipStream_t st) {
     h->nonfinite = hs.nonfinite != 0;
     h->corpus_int_unscaled = !hs.not_integer && !h->nonfinite && h->absmax <= 2048.f;
     h->i8_cx = !hs.not_u8 ? 128 : 0;                        // u8 window first (SIFT), else s8
-    h->i8_ok = !h->nonfinite && (!hs.not_u8 || !hs.not_s8) && h->dim <= 128;
+    h->i8_byte_valued = !hs.not_u8 || !hs.not_s8;
+    h->i8_ok = !h->nonfinite && h->i8_byte_valued && h->dim <= 128;
     h->sx = 1.f;
     if (!h->corpus_int_unscaled && h->absmax > 0.f && !h->nonfinite) {
         int e;
@@ -792,6 +800,37 @@ bool x16_wanted(const vdb_index_s *h) {
     return h->ksteps <= kMaxKSteps && h->opt.flat_shape != 32 && h->opt.f16_group == 8 && h->opt.i8_group == 8;
 }
 
+// Option "i8_kloop": the int8 K-loop copy of a p16 handle (the build rule: i8k_plan.hpp) -- A panels in p16 order, accumulator
+// inits of both query windows with the handle's key rule, row statistics and the row-major copy for the refine (pitch = D padded
+// to 64).  A handle that does not take it drops a copy an earlier add left.
+void build_i8_kloop(vdb_index_s *h, bool byte_valued, hipStream_t st) {
+    const bool was = h->i8k_ok;
+    h->i8k_ok = i8k_build(h->opt.i8_kloop, kind_of(h) == kFlat && !h->coarse, h->tile16, byte_valued, h->panels_streamed, h->dim);
+    if (!h->i8k_ok) {
+        if (was) {
+            DevBuf *i8[] = {&h->scan.rows8, &h->scan.rowstat8, &h->scan.bias8, &h->scan.panels8};
+            for (auto b : i8) b->release();
+        }
+        return;
+    }
+    const int D = h->dim, D4 = h->D4, nk = (D + 63) / 64;
+    const int64_t n = h->N, ntiles = h->Npad / kTileRows16, t8 = ntiles * nk * 64;
+    h->i8_ks = 2 * nk;                                      // (32-dim k-steps: what the int8 B-fragment and row builders count in)
+    h->i8k_key = i8k_key_rule(64 * nk, h->i8_cx, h->metric);
+    if (!i8k_key_ok(h->i8k_key)) throw Error(VDB_ERR_STATE, "internal: the int8 K-loop key rule does not fit");
+    h->scan.panels8.reserve((size_t)t8 * sizeof(int4v));
+    build_panels16_i8_kernel<<<dim3((unsigned)((t8 + 255) / 256)), dim3(256), 0, st>>>(h->rows.x32.as<float>(), n, D, D4, nk, ntiles, h->i8_cx,
+                                                                                      h->scan.panels8.as<int4v>());
+    h->scan.bias8.reserve((size_t)2 * h->Npad * sizeof(int32_t));
+    h->scan.rowstat8.reserve((size_t)n * 2 * sizeof(int));
+    build_bias_i8k_kernel<<<dim3((unsigned)((h->Npad + 255) / 256)), dim3(256), 0, st>>>(
+        h->rows.x32.as<float>(), n, h->Npad, D, D4, h->metric, (long long)h->i8k_key.offset, (int)h->i8k_key.pad, h->scan.bias8.as<int32_t>(),
+        h->scan.rowstat8.as<int>());
+    build_rows_i8(h, st);
+    VDB_HIP(hipGetLastError());
+    VDB_HIP(hipStreamSynchronize(st));
+}
+
 // everything derived from the h->N rows in h->rows.x32: statistics, scan copies, biases
 void build_derived(vdb_index_s *h, hipStream_t st) {
     const int D = h->dim, D4 = h->D4;
@@ -807,10 +846,12 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
     h->x16 = x16_wanted(h) && h->Npad > kDenseMaxRows;
     h->scan_ok = false;
     if (n == 0) {
+        build_i8_kloop(h, false, st);
         h->built = true;
         return;
     }
     index_stats(h, st);
+    const bool byte_valued = !h->nonfinite && h->i8_byte_valued;
     const bool dims_ok = D <= 4096;
     if (dims_ok && !h->nonfinite) {
         const int64_t ntiles = h->Npad / (h->tile16 ? kTileRows16 : kTileRows);
@@ -832,6 +873,7 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
         VDB_HIP(hipStreamSynchronize(st));
         h->corpus_fp16_exact = hs.not_fp16_exact == 0;
         h->scan_ok = true;
+        build_i8_kloop(h, byte_valued, st);
         h->i8_ok = h->i8_ok && !h->tile16;
         if (h->i8_ok) {
             h->i8_ks = D <= 64 ? 2 : 4;
@@ -849,6 +891,7 @@ void build_derived(vdb_index_s *h, hipStream_t st) {
         }
     } else {
         h->i8_ok = false;
+        build_i8_kloop(h, false, st);
     }
     h->built = true;
 }
@@ -1417,7 +1460,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.corpus_fp16_exact = h->corpus_fp16_exact ? 1 : 0;
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
-        s.has_i8_copy = (h->int8_only || h->ivf_codec == 3) ? 2 : (h->i8_ok ? 1 : 0);      // (IVF-I8: nothing but the int8 copies)
+        s.has_i8_copy = (h->int8_only || h->ivf_codec == 3) ? 2 : ((h->i8_ok || h->i8k_ok) ? 1 : 0);      // (IVF-I8: nothing but the int8 copies)
         s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + group_bytes(h->range) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
@@ -1432,7 +1475,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_rows_scanned = (int64_t)pl.rows_scanned;
         }
         s.scan_dtype = 0;
-        if (h->i8_ok && h->ws.small.p && mfma_scanned) {   // which scan the device chose
+        if ((h->i8_ok || h->i8k_ok) && h->ws.small.p && mfma_scanned) {   // which scan the device chose
             QueryBatchInfo qi;
             VDB_HIP(hipDeviceSynchronize());
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));

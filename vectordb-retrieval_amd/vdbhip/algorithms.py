@@ -186,12 +186,14 @@ class HipExactSearch(RawAlgorithm):
     """Exact k-NN on one MI355X -- or, with `device_ids: [..]` of several, on ONE index row-sharded over them in this
     process; same constructor and results as ExactSearch (faiss.IndexFlat).  `range_int8` (a config entry `range_int8: 1`):
     option "range_i8" of the index, set before the rows are added -- integer query batches of a byte-valued corpus take the
-    int8 prefilter in `range_search`."""
+    int8 prefilter in `range_search`.  `int8_kloop` (a config entry `int8_kloop: true`): option "i8_kloop", likewise -- a
+    byte-valued corpus of more than 128 dimensions also gets the int8 K-loop scan copy."""
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", device=None,
-                 device_ids=None, range_int8: Optional[int] = None, **kwargs: Any) -> None:
+                 device_ids=None, range_int8: Optional[int] = None, int8_kloop: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, **kwargs)
         self.range_int8 = None if range_int8 is None else int(range_int8)
+        self.int8_kloop = None if int8_kloop is None else int(bool(int8_kloop))
         if device_ids is not None:
             self.config["device_ids"] = list(device_ids) if not isinstance(device_ids, (int, np.integer)) else int(device_ids)
         # exact_search.py:23 -- 'l2' -> METRIC_L2, anything else -> METRIC_INNER_PRODUCT (no normalisation)
@@ -207,6 +209,8 @@ class HipExactSearch(RawAlgorithm):
         apply_engine_options(self.index, self.config)
         if self.range_int8 is not None:
             self.index.set_option("range_i8", float(self.range_int8))
+        if self.int8_kloop is not None:
+            self.index.set_option("i8_kloop", float(self.int8_kloop))
         self.index.add(self.vectors)
         reserve_workspace(self.index, self.config)
         self.index_built = True
@@ -249,6 +253,8 @@ def _flat_index(store: np.ndarray, dimension: int, metric: str, params: dict) ->
     apply_engine_options(index, params)
     if params.get("range_int8") is not None:
         index.set_option("range_i8", float(int(params["range_int8"])))
+    if params.get("int8_kloop") is not None:
+        index.set_option("i8_kloop", float(int(bool(params["int8_kloop"]))))
     index.add(data)
     reserve_workspace(index, params)
     return index
@@ -276,11 +282,13 @@ class HipLinearSearcher(BaseSearcher):
     """LinearSearcher semantics; the scan itself runs on the MI355X.  `range_int8` (a config entry `range_int8: 1`): option
     "range_i8" of an index this searcher builds ITSELF (an artifact of the reference's indexer, or one built for another metric).
     The index of a HipBruteForceIndexer artifact is shared by every searcher attached to it and is left as its indexer made it:
-    give that indexer `range_int8: 1` instead."""
+    give that indexer `range_int8: 1` instead.  `int8_kloop` (`int8_kloop: true`): option "i8_kloop", under the same rule."""
 
-    def __init__(self, name: str, dimension: int, metric: str = "l2", range_int8: Optional[int] = None, **kwargs: Any) -> None:
+    def __init__(self, name: str, dimension: int, metric: str = "l2", range_int8: Optional[int] = None,
+                 int8_kloop: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
         self.range_int8 = None if range_int8 is None else int(range_int8)
+        self.int8_kloop = None if int8_kloop is None else int(bool(int8_kloop))
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         if artifact.kind != "raw_vectors":
@@ -295,7 +303,7 @@ class HipLinearSearcher(BaseSearcher):
             if meta.get("hip_index") is not None and meta.get("hip_index_metric") == self.metric:
                 self._index = meta["hip_index"]
             else:  # artifact from the reference's own BruteForceIndexer, or built for another metric
-                self._index = _flat_index(store, self.dimension, self.metric, {**self.params, "range_int8": self.range_int8})
+                self._index = _flat_index(store, self.dimension, self.metric, {**self.params, "range_int8": self.range_int8, "int8_kloop": self.int8_kloop})
         self._prepared = True
 
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
