@@ -83,7 +83,7 @@ typedef struct vdb_stats_s {
                                   index for a batch its int8 scan cannot serve (f32 accumulate),
                                   3 = float32 lookup-table sums over the codes of a PQ or IVF-PQ index (last_path = VDB_PATH_PQ_ADC /
                                   VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly) */
-    int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop") next to the float32
+    int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
                                   queries that took the brute-force fallback */
@@ -758,6 +758,16 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       64, the corpus window and the metric (shift 0 up to D = 448, 1 at D = 768, 4 at D = 4096).  Same results,
  *                       bit for bit.  Not with "int8_only" (D <= 128) or "stream_panels" (no copy is built); IVF, PQ, LSH,
  *                       k-NN-graph and multi-device handles are out of scope and refuse or ignore it
+ *     "ivf_i8_kloop"    IVF-Flat index (codec 0), D > 128 (up to 4096), takes effect at the next vdb_ivf_add: 0 (default) | 1: a
+ *                       byte-valued corpus ALSO gets an int8 copy of its list-padded panel space -- int8 MFMA panels in the 16-row
+ *                       layout, accumulator inits for both query windows, list-order int8 rows with a pitch of D padded to 64:
+ *                       about (2 D + 24) bytes per row more (vdb_stats.has_i8_copy = 1).  Every add rebuilds it; an append that
+ *                       makes the corpus non-byte-valued drops it.  Integer query batches inside the u8 or s8 window of an
+ *                       unfiltered vdb_ivf_search / _device / _partial_device that the list-major path serves then take the
+ *                       int8 K-loop list scan (v_mfma_i32_16x16x64_i8, exact int32 keys in the per-handle format of "i8_kloop",
+ *                       integer refine; vdb_stats.scan_dtype = 1); every other batch, "panel_dtype" = 1, "ivf_tile" = 2,
+ *                       filtered and range searches run on the fp16 copy as without the option.  Same results, bit for bit.
+ *                       The coded IVF kinds (SQ8, PQ, I8) and a multi-device index refuse it; a flat index ignores it
  *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
  *                       spans (tests: several blocks on a small corpus); also the rows per block of a vdb_ivf_add on an IVF-I8 index
  *                       (0 = default 1 048 576, not rounded): one block of float32 rows is all the device holds of them

@@ -239,8 +239,38 @@ int64_t ivf_build_spans(vdb_index_s *h, int span_rows) {
 // fp16 panels of the permuted rows, every list padded to whole spans (list-major MFMA scan).  D <= 128: 32-row tiles,
 // 256-row spans (kIvfSpanRows; scan_kernel / scan_i8_kernel in ITEMS mode).  D > 128: p16 tiles (ivf_kloop.hpp), spans of 256 rows
 // (four 64-row bins) or, for lists of thousands of rows, 1024 rows (four 256-row bins).
+// Option "ivf_i8_kloop": the int8 copy of a p16 panel space for the int8 K-loop list scan (ivf_kloop_i8.hpp; the build rule:
+// ivf_i8k_plan.hpp) -- A panels over the P spans, accumulator inits of both query windows with the handle's key rule, row statistics
+// and the list-order int8 rows of the refine (pitch = D padded to 64).  i8_ok stays false: filtered and range calls never see it.
+void ivf_build_i8_kloop(vdb_index_s *h, int64_t P, int span_rows, hipStream_t st) {
+    h->ivf_i8k_ok = ivf_i8k_build(h->opt.ivf_i8_kloop, h->ivf_codec, h->tile16, !h->nonfinite && h->i8_byte_valued, h->dim);
+    if (!h->ivf_i8k_ok) return;
+    const int D = h->dim, D4 = h->D4, nk = (D + 63) / 64;
+    const int64_t ntiles = P * h->ivf_tps, t8 = ntiles * nk * 64, npad = P * span_rows;
+    h->i8_ks = 2 * nk;                                      // (32-dim k-steps: what build_rows_i8 and the query rows count in)
+    h->i8k_key = i8k_key_rule(64 * nk, h->i8_cx, h->metric);
+    if (!i8k_key_ok(h->i8k_key)) throw Error(VDB_ERR_STATE, "internal: the int8 K-loop key rule does not fit");
+    h->scan.panels8.reserve((size_t)t8 * sizeof(int4v));
+    ivf_build_panels16_i8_kernel<<<dim3((unsigned)((t8 + 255) / 256)), dim3(256), 0, st>>>(
+        h->rows.x32.as<float>(), D, D4, nk, h->ivf_tps, ntiles, h->i8_cx, h->lists.ivf_span_row0.as<int32_t>(),
+        h->lists.ivf_span_valid.as<int32_t>(), h->scan.panels8.as<int4v>());
+    h->scan.bias8.reserve((size_t)2 * npad * sizeof(int32_t));
+    h->scan.rowstat8.reserve((size_t)h->N * 2 * sizeof(int));
+    ivf_build_bias_i8k_kernel<<<dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st>>>(
+        h->rows.x32.as<float>(), P, span_rows, D, D4, h->metric, (long long)h->i8k_key.offset, (int)h->i8k_key.pad,
+        h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(), h->scan.bias8.as<int32_t>(), h->scan.rowstat8.as<int>());
+    build_rows_i8(h, st);
+    VDB_HIP(hipGetLastError());
+    VDB_HIP(hipStreamSynchronize(st));
+}
+
 void ivf_build_panel_space(vdb_index_s *h) {
     h->ivf_mfma_ok = false;
+    if (h->ivf_i8k_ok) {      // (the copy of the last add goes with its panel space; the rule below decides anew)
+        DevBuf *i8[] = {&h->scan.rows8, &h->scan.rowstat8, &h->scan.bias8, &h->scan.panels8};
+        for (auto b : i8) b->release();
+        h->ivf_i8k_ok = false;
+    }
     h->scan_ok = false;
     h->tile16 = h->ksteps > kMaxKSteps;
     if (h->N == 0 || h->dim > 4096) return;
@@ -290,6 +320,7 @@ void ivf_build_panel_space(vdb_index_s *h) {
         VDB_HIP(hipGetLastError());
         VDB_HIP(hipStreamSynchronize(st));
     }
+    ivf_build_i8_kloop(h, P, span_rows, st);
     h->ivf_mfma_ok = true;
 }
 
@@ -310,20 +341,24 @@ IvfIndexShape ivf_shape_of(const vdb_index_s *h) {
 #define VDB_ROW_IVF_SCAN(...) {ScanKey{{__VA_ARGS__}}, &scan_kernel<__VA_ARGS__>},
 #define VDB_ROW_IVF_SCAN_I8(...) {ScanKey{{__VA_ARGS__}}, &scan_i8_kernel<__VA_ARGS__>},
 #define VDB_ROW_IVF_KLOOP(...) {ScanKey{{__VA_ARGS__}}, &ivf_kloop_scan_kernel<__VA_ARGS__>},
+#define VDB_ROW_IVF_KLOOP_I8(...) {ScanKey{{__VA_ARGS__}}, &ivf_kloop_i8_scan_kernel<__VA_ARGS__>},
 constexpr ScanRow<ScanArgs> kRowsIvfScan[] = {VDB_KERNELS_IVF_SCAN(VDB_ROW_IVF_SCAN)};
 constexpr ScanRow<ScanI8Args> kRowsIvfScanI8[] = {VDB_KERNELS_IVF_SCAN_I8(VDB_ROW_IVF_SCAN_I8)};
 constexpr ScanRow<IvfKloopArgs> kRowsIvfKloop[] = {VDB_KERNELS_IVF_KLOOP(VDB_ROW_IVF_KLOOP)};
+constexpr ScanRow<IvfKloopI8Args> kRowsIvfKloopI8[] = {VDB_KERNELS_IVF_KLOOP_I8(VDB_ROW_IVF_KLOOP_I8)};
 #undef VDB_ROW_IVF_SCAN
 #undef VDB_ROW_IVF_SCAN_I8
 #undef VDB_ROW_IVF_KLOOP
+#undef VDB_ROW_IVF_KLOOP_I8
 
 // the one <<<>>> of the plan's family, with the arguments of that family
-void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st) {
+void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st, const IvfKloopI8Args *k8 = nullptr) {
     const dim3 grid(p.grid_x, p.grid_y), block(p.block);
     switch (p.family) {
         case ScanFamily::scan: scan_kernel_of(kRowsIvfScan, p)<<<grid, block, 0, st>>>(*sa); break;
         case ScanFamily::scan_i8: scan_kernel_of(kRowsIvfScanI8, p)<<<grid, block, 0, st>>>(*s8); break;
         case ScanFamily::ivf_kloop: scan_kernel_of(kRowsIvfKloop, p)<<<grid, block, 0, st>>>(*ka); break;
+        case ScanFamily::ivf_kloop_i8: scan_kernel_of(kRowsIvfKloopI8, p)<<<grid, block, 0, st>>>(*k8); break;
         default: throw Error(VDB_ERR_INVALID, "internal: no list scan kernel for an empty plan");
     }
     VDB_HIP(hipGetLastError());
@@ -343,6 +378,7 @@ struct IvfBatch {
     IvfIndexShape shape;    // ivf_shape_of(h)
     IvfGeom g;              // list-major path only: the geometry, and the zeroed counter block of this batch (ivf_zero)
     int32_t *d_cnt;
+    bool i8k;               // the int8 K-loop list scan is offered to this batch (ivf_i8k_plan.hpp, ivf_i8k_serves)
     bool filtered;          // a vdb_ivf_search_filtered call (ivf_filter.inc): the scans read the masked copies of the handle's filter,
                             // the exact stages test its list-order allow words
 };
@@ -365,7 +401,7 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     L.c = ivf_caps(b.shape, h->opt, b.g, b.k);
     ws.eps.reserve((size_t)nb * sizeof(float));
     ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
-    if (L.c.use_i8) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);      // int8 query rows
+    if (L.c.use_i8 || b.i8k) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);      // int8 query rows (the K-loop copy: i8_ks * 32 = D padded to 64)
     ws.bin_m1.reserve(b.g.bin_bytes);
     ws.bin_m2.reserve(b.g.bin_bytes);
     ws.bin_m3.reserve(b.g.bin_bytes);
@@ -402,7 +438,7 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
     const int Dm = h->dim;
     const int64_t nb = b.nb, total = nb * Dm;
     const FinalizeArgs fin{h->sx, h->metric, h->corpus_int_unscaled ? 1 : 0, h->maxnorm2,
-                           L.c.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see plan_ivf_i8)
+                           b.i8k ? 1 : L.c.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see plan_ivf_i8; the K-loop scan: its own groups)
     const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
     if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, b.st>>>(b.q, total, L.info, fin);
     IvfPrepArgs pa{};
@@ -410,7 +446,7 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
                      h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, L.info, ws.eps.as<float>()};
     pa.Q = b.q; pa.nq = nb; pa.D = Dm; pa.Dpad = h->ksteps * 16;      // (= i8_ks * 32: both query-row forms have the same pitch)
     pa.qrows = reinterpret_cast<_Float16 *>(ws.qpanels.p);
-    pa.q8 = L.c.use_i8 ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
+    pa.q8 = (L.c.use_i8 || b.i8k) ? reinterpret_cast<signed char *>(ws.qpanels8.p) : nullptr;
     pa.info = L.info; pa.src = from_coarse ? batch_info(h->coarse->ws) : nullptr; pa.fin = fin;
     pa.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
     pa.n_row_blocks = (unsigned)((nb * pa.Dpad / 8 + 255) / 256);     // (8 dims per thread)
@@ -470,6 +506,24 @@ void ivf_scan_kloop(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
     ka.ksteps = h->ksteps;
     ka.part_spans = p.part_spans;
     ivf_launch(p, nullptr, nullptr, &ka, b.st);
+}
+
+// the int8 form of the K-loop scan (ivf_kloop_i8.hpp) on the same grid and row parts; whichever the finalize kernel did not choose
+// returns at once
+void ivf_scan_kloop_i8(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    const IvfLaunch p = plan_ivf_kloop_i8(b.shape, h->opt, b.g, kgroup);
+    IvfKloopI8Args k8{};
+    k8.panels = h->scan.panels8.as<int4v>(); k8.bias8 = h->scan.bias8.as<int32_t>();
+    k8.qrows = reinterpret_cast<const signed char *>(h->ws.qpanels8.p); k8.info = sa.info;
+    k8.bin_m[0] = sa.bin_m1; k8.bin_m[1] = sa.bin_m2; k8.bin_m[2] = sa.bin_m3;
+    k8.bin_m[3] = h->ws.bin_m4.as<float>(); k8.bin_m[4] = h->ws.bin_m5.as<float>();
+    k8.item_list = sa.item_list; k8.item_slot0 = sa.item_slot0; k8.item_bin0 = sa.item_bin0;
+    k8.n_items = sa.n_items; k8.list_pspan0 = sa.list_pspan0; k8.slot_query = sa.slot_query;
+    k8.part_spans = p.part_spans;
+    k8.nk = h->i8_ks / 2; k8.shift = h->i8k_key.shift;
+    k8.npad = h->ivf_pspans * h->ivf_span_rows;
+    ivf_launch(p, nullptr, nullptr, nullptr, b.st, &k8);
 }
 
 // D <= 128: scan_kernel in ITEMS mode on 32-row tiles.  Sets sa.part_spans (the int8 scan takes the same, and the same grid)
@@ -539,7 +593,7 @@ void ivf_lists_tail(const IvfBatch &b, const IvfLists &L, const IvfSelectArgs &s
     if (sq8(h)) rc.sq8 = sq8_rows(h);      // (the refine and the flagged-query pass decode the candidates' codes)
     if (ivfpq(h)) rc.ivfpq = ivfpq_rows(h);
     if (ivf_i8(h)) i8_refine_rows(h, rc);  // (IVF-I8: rc.X is nullptr, every exact stage scores the int8 rows)
-    if (L.c.use_i8 && h->scan.rows8.p) {
+    if ((L.c.use_i8 || b.i8k) && h->scan.rows8.p) {
         rc.X8 = h->scan.rows8.as<signed char>(); rc.rowstat = h->scan.rowstat8.as<int>();
         rc.Q8 = reinterpret_cast<const signed char *>(ws.qpanels8.p);      // the int8 query rows the scan gathers from
         rc.x8_pitch = h->rows8_pitch; rc.cx = h->i8_cx; rc.D = h->dim;
@@ -598,6 +652,7 @@ void ivf_search_lists(const IvfBatch &b) {
     timing_mark(h, b.tslot, 0, b.st);
     if (b.g.kloop) {
         ivf_scan_kloop(b, L.c.kgroup, sa);
+        if (b.i8k) ivf_scan_kloop_i8(b, L.c.kgroup, sa);
     } else {
         if (i8_no_slab) {
             ivf_i8_flag_kernel<<<dim3(1), dim3(64), 0, b.st>>>(L.info);
@@ -708,6 +763,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         b.filtered = filtered;
         const IvfAdcPlan adc = ivf_adc_plan(h->opt, h->ivf_codec, h->ivfpq.M, adc_ranges, h->N, adc_longest, b.nb, k, b.nprobe);
         if (!adc.ok) b.g = filtered ? ivf_filter_geometry(shape, h->opt, b.nb, k, b.nprobe, h->ivf_filter_count) : ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
+        b.i8k = ivf_i8k_serves(h->ivf_i8k_ok && h->scan.panels8.p && h->scan.rows8.p, h->opt.panel_dtype, h->opt.ivf_tile, filtered, b.g.ok && b.g.kloop);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
             VDB_HIP(hipMemsetAsync(h->plan.ivf_zero.p, 0, 2 * kZeroSmall + (b.g.ok ? b.g.cnt_words * 4 : 0), st));

@@ -86,6 +86,7 @@ __global__ __launch_bounds__(512, 2) void ivf_kloop_scan_kernel(IvfKloopArgs a) 
     const int slot0 = a.item_slot0[it] + cg * 64;
     const size_t bin_base = (size_t)a.item_bin0[it];
     const float cs = a.info->cs;
+    if (a.info->i8_mode) return;                             // this batch is served by ivf_kloop_i8_scan_kernel (ivf_kloop_i8.hpp; option "ivf_i8_kloop")
 
     const int npass = (int)(span1 - span0) * PPS;
     const int nsteps = npass * nK;

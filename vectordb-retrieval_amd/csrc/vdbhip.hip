@@ -28,6 +28,7 @@
 #include "ivf.hpp"
 #include "ivf_mfma.hpp"
 #include "ivf_kloop.hpp"
+#include "ivf_kloop_i8.hpp"
 #include "ivf_sq8.hpp"
 #include "ivf_i8_plan.hpp"
 #include "ivf_i8.hpp"
@@ -326,6 +327,9 @@ struct vdb_index_s {
                                              // (scan16_i8.hpp) in scan.panels8 / bias8 / rowstat8 / rows8; i8_ok stays false on it -- filters and
                                              // range searches, which bake in the D <= 128 key constants, never see the copy
     I8KeyRule i8k_key;                       // ... and its key format (i8k_plan.hpp)
+    bool ivf_i8k_ok = false;                 // option "ivf_i8_kloop" took effect at the last add: an IVF-Flat handle of D > 128 with the int8 copy of
+                                             // its list-padded panel space (ivf_kloop_i8.hpp) in the same four buffers, key format in i8k_key; i8_ok
+                                             // stays false here too
     // a captured device-resident search (option "graph", graph_or_run)
     struct GraphKey {
         const void *q = nullptr, *o1 = nullptr, *o2 = nullptr;
@@ -492,6 +496,7 @@ constexpr OptionRow kOptions[] = {
     {"panel_dtype", &Options::panel_dtype, 2, {0, 1}},               // 0 auto (int8 scan copy used when corpus and queries allow), 1 = fp16 scan only
     {"int8_only", &Options::int8_only, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::int8_only},
     {"i8_kloop", &Options::i8_kloop, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::i8k_ok},   // D > 128, next add: 1 = a byte-valued corpus also gets the int8 K-loop scan copy
+    {"ivf_i8_kloop", &Options::ivf_i8_kloop, 2, {0, 1}, kNoRows, 0, nullptr, &vdb_index_s::ivf_i8k_ok},   // IVF-Flat, D > 128, next add: 1 = a byte-valued corpus also gets the int8 copy of the panel space for the int8 K-loop list scan
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -1460,7 +1465,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         s.corpus_fp16_exact = h->corpus_fp16_exact ? 1 : 0;
         // everything the handle holds, and an IVF index's coarse quantizer (its own index and workspace) with it
         s.bytes_resident = (int64_t)(handle_bytes(h) + (h->coarse ? handle_bytes(h->coarse) : 0));
-        s.has_i8_copy = (h->int8_only || h->ivf_codec == 3) ? 2 : ((h->i8_ok || h->i8k_ok) ? 1 : 0);      // (IVF-I8: nothing but the int8 copies)
+        s.has_i8_copy = (h->int8_only || h->ivf_codec == 3) ? 2 : ((h->i8_ok || h->i8k_ok || h->ivf_i8k_ok) ? 1 : 0);      // (IVF-I8: nothing but the int8 copies)
         s.bytes_workspace = (int64_t)(group_bytes(h->ws) + group_bytes(h->lsh_ws) + group_bytes(h->knng_ws) + group_bytes(h->range) + (pq_on(h) ? h->scan.slab.cap : 0));   // (PQ: + the slab of per-search panels)
         s.upload_blocks = h->last_upload_blocks;
         s.graph_replays = h->graph_replays;
@@ -1475,7 +1480,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.last_rows_scanned = (int64_t)pl.rows_scanned;
         }
         s.scan_dtype = 0;
-        if ((h->i8_ok || h->i8k_ok) && h->ws.small.p && mfma_scanned) {   // which scan the device chose
+        if ((h->i8_ok || h->i8k_ok || h->ivf_i8k_ok) && h->ws.small.p && mfma_scanned) {   // which scan the device chose
             QueryBatchInfo qi;
             VDB_HIP(hipDeviceSynchronize());
             VDB_HIP(hipMemcpy(&qi, batch_info(h->ws), sizeof(qi), hipMemcpyDeviceToHost));

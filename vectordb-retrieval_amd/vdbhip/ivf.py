@@ -312,13 +312,21 @@ def _build_ivf(vectors: np.ndarray, dim: int, key: str, metric: str, device: int
     index = (IVFSQ8Index if codec == "SQ8" else IVFI8Index if i8 else IVFFlatIndex)(dim, nlist, metric, device)
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
+    _set_int8_kloop(index, params)
     index.add(vectors)
     return index
 
 
+def _set_int8_kloop(index: IVFFlatIndex, params: dict) -> None:
+    """`int8_kloop: true` (IVF-Flat): option "ivf_i8_kloop", set before the add -- a byte-valued corpus of more than 128 dimensions also
+    gets the int8 copy of its lists for the int8 K-loop list scan.  The coded kinds refuse the option and the error comes through."""
+    if params.get("int8_kloop") is not None:
+        index.set_option("ivf_i8_kloop", float(int(bool(params["int8_kloop"]))))
+
+
 class HipApproximateSearch(RawAlgorithm):
     """ApproximateSearch semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8": train -> add -> nprobe from kwargs; raw
-    FAISS conventions (no normalisation, no sign flip)."""
+    FAISS conventions (no normalisation, no sign flip).  `int8_kloop: true` (a config entry): option "ivf_i8_kloop" before the add."""
 
     def __init__(self, name: str, dimension: int, index_type: str, metric: str = "l2", device: Optional[int] = None,
                  **kwargs: Any) -> None:
@@ -416,6 +424,7 @@ class HipApproximateSearch(RawAlgorithm):
                 raise ValueError("Persisted index files do not belong together (fingerprint mismatch: " + ", ".join(bad) + ")")
         elif not _lists_match_sample(vectors, centroids, stored, self.metric):
             raise ValueError("Persisted inverted lists do not match the persisted corpus and centroids")
+        _set_int8_kloop(self.index, self.config)
         self.index.add(vectors, list_of_row=stored)   # ... and so are the stored lists: no assignment pass either
         self.index.set_nprobe(int(self.config.get("nprobe", manifest.get("nprobe", 1))))
         self.index_built = True
@@ -423,9 +432,10 @@ class HipApproximateSearch(RawAlgorithm):
 
 
 class HipIVFIndexer(BaseIndexer):
-    """FaissFactoryIndexer / FaissIVFIndexer semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8" keys."""
+    """FaissFactoryIndexer / FaissIVFIndexer semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8" keys.  `int8_kloop: true`: option
+    "ivf_i8_kloop" of the index, set before the rows are added."""
 
-    _RESERVED = {"index_key", "index_type", "device", "device_ids", "niter", "seed", "max_points_per_centroid", "int8_lists"}
+    _RESERVED = {"index_key", "index_type", "device", "device_ids", "niter", "seed", "max_points_per_centroid", "int8_lists", "int8_kloop"}
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", index_type: Optional[str] = None,
                  index_key: Optional[str] = None, **kwargs: Any) -> None:
@@ -450,13 +460,17 @@ class HipIVFIndexer(BaseIndexer):
 
 class HipIVFSearcher(FaissStyleSearcher):
     """FaissSearcher semantics over a HipIVFIndexer artifact.  `adc_max_batch` (a config entry `adc_max_batch: 16`): option
-    "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer)."""
+    "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer).  `int8_kloop`
+    (`int8_kloop: true`): option "ivf_i8_kloop" of the attached index; it takes effect at an add, so give it to the HipIVFIndexer
+    as well -- here it keeps the option set for rows added to the index later."""
 
     _kind = "hip_ivf"
 
-    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
+    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None,
+                 int8_kloop: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
         self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
+        self.int8_kloop = None if int8_kloop is None else int(bool(int8_kloop))
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         meta = self._bind(artifact)
@@ -469,6 +483,8 @@ class HipIVFSearcher(FaissStyleSearcher):
         if self.adc_max_batch is not None:
             self.index.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
             self.index.adc_max_batch = self.adc_max_batch
+        if self.int8_kloop is not None:
+            self.index.set_option("ivf_i8_kloop", float(self.int8_kloop))
 
     def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
         """`allowed` (None: every row): what IVFFlatIndex.set_filter takes -- the k nearest among those rows of the probed lists,
