@@ -82,7 +82,9 @@ typedef struct vdb_stats_s {
                                   2 = fp16 panels converted from the 8-bit codes of an SQ8 or PQ index, or from the int8 panels of an IVF-I8
                                   index for a batch its int8 scan cannot serve (f32 accumulate),
                                   3 = float32 lookup-table sums over the codes of a PQ or IVF-PQ index (last_path = VDB_PATH_PQ_ADC /
-                                  VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly) */
+                                  VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly),
+                                  4 = fp16 MFMA straight on the 8-bit codes of an IVF-SQ8 index, option "ivf_sq8_direct" (f32 accumulate;
+                                  last_path stays VDB_PATH_IVF, last_path_name "ivf") */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -768,6 +770,14 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       integer refine; vdb_stats.scan_dtype = 1); every other batch, "panel_dtype" = 1, "ivf_tile" = 2,
  *                       filtered and range searches run on the fp16 copy as without the option.  Same results, bit for bit.
  *                       The coded IVF kinds (SQ8, PQ, I8) and a multi-device index refuse it; a flat index ignores it
+ *     "ivf_sq8_direct"  IVF-SQ8 index (codec 1), D <= 128, takes effect at the next search (no rebuild): 0 (default) | 1: a batch
+ *                       of vdb_ivf_search / _device / _partial_device that the list-major path serves is scanned by a kernel that
+ *                       reads the list-order codes themselves (codes - 128 widened to fp16 in registers, q * vdiff / 255 as the
+ *                       query operand, one float32 term per (query, list) slot, an error bound of its own) instead of fp16 panels
+ *                       converted from the whole panel space for the batch: that pass and its workspace slab are not made
+ *                       (vdb_stats.scan_dtype = 4).  Same results, bit for bit; a batch outside the scale windows of the route
+ *                       (non-finite queries, extreme ranges) is answered by the exact list scan.  No effect on the other codecs,
+ *                       on D > 128, a dimension below 13, "force_path" 1 / 3; a multi-device index refuses a non-zero value
  *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
  *                       spans (tests: several blocks on a small corpus); also the rows per block of a vdb_ivf_add on an IVF-I8 index
  *                       (0 = default 1 048 576, not rounded): one block of float32 rows is all the device holds of them

@@ -6,7 +6,11 @@ centroids and trains its ranges on the corpus.  Per nprobe: device-resident QPS 
 results in HBM, `warmup` untimed searches, then `steps` timed ones between two device synchronisations), recall@10 against
 the exact float64 result, and (bytes_resident - bytes_workspace) / (4 N D).  Prints ONE JSON line.
 
-    python scripts/bench_ivf_sq8.py [--steps 5] [--warmup 2] [--n 1000000]
+`--direct`: also the legs of option "ivf_sq8_direct" (the list scan reads the codes themselves) on the SAME SQ8 handle, alternating
+option 0 / 1 twice per (batch, nprobe) in one run -- batches of `--nq`, 64 and 1 queries; every leg with its stage times, scan_dtype
+(2: fp16 panels made per batch, 4: the direct scan), fallback queries, and the workspace bytes of a handle searched with the option on only.
+
+    python scripts/bench_ivf_sq8.py [--steps 5] [--warmup 2] [--n 1000000] [--direct]
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--nprobe", type=int, nargs="+", default=[8, 32, 128])
+    ap.add_argument("--direct", action="store_true")
     args = ap.parse_args()
     import torch
 
@@ -91,6 +96,42 @@ def main() -> None:
         st = idx.stats()
         res["resident_over_fp32_corpus"] = round((st["bytes_resident"] - st["bytes_workspace"]) / (4.0 * args.n * d), 4)
         out[name] = res
+    if args.direct:
+        def leg(nq, p, on):
+            sq.set_option("ivf_sq8_direct", on)
+            sq.set_nprobe(p)
+            for _ in range(args.warmup):
+                sq.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+            torch.cuda.synchronize()
+            sq.set_option("timing", 1)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                sq.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            st = sq.stats()
+            sq.set_option("timing", 0)
+            return {"qps": round(nq * args.steps / el, 1), "ms_per_search": round(el / args.steps * 1e3, 4), "prep_ms": round(st["last_prep_ms"], 4),
+                    "scan_ms": round(st["last_scan_ms"], 4), "tail_ms": round(st["last_tail_ms"], 4), "scan_dtype": st["scan_dtype"],
+                    "fallback_queries": st["last_fallback_queries"], "candidates_per_query": round(st["last_candidates"] / nq, 2),
+                    "ids": I_t[:nq].cpu().numpy().copy()}
+
+        direct = {}
+        for nq in (args.nq, 64, 1):
+            for p in args.nprobe:
+                legs = [leg(nq, p, on) for on in (0, 1, 0, 1)]
+                same = all(np.array_equal(legs[0]["ids"], x.pop("ids")) for x in legs[::-1])
+                direct[f"nq{nq}_nprobe{p}"] = {"off": legs[0::2], "on": legs[1::2], "same_ids": same}
+        fresh = vdbhip.IVFSQ8Index(d, nlist, "l2", 0, direct_codes=True)       # searched with the option on only: no panel slab
+        fresh.set_centroids(fl.centroids())
+        fresh.train_ranges(X)
+        fresh.add(X)
+        fresh.set_nprobe(32)
+        fresh.search_device(Q_t.data_ptr(), args.nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+        torch.cuda.synchronize()
+        direct["bytes_workspace"] = {"on_only": fresh.stats()["bytes_workspace"], "after_both": sq.stats()["bytes_workspace"]}
+        fresh.close()
+        out["sq8_direct"] = direct
     print(json.dumps(out))
     fl.close()
     sq.close()

@@ -91,6 +91,42 @@ void sq8_train_ranges(vdb_index_s *h, const float *x_host, int64_t n) {
 
 void ivf_build_panel_space(vdb_index_s *h);     // (ivf.inc)
 
+// What the direct scan (option "ivf_sq8_direct", ivf_sq8_scan.hpp) reads of the centroids and ranges, in float64 on the host: with
+// g = vdiff / 255 and e = vmin + 128.5 g -- max g; max |c_l[d]| + max |e[d]| (the window of the slot term); the norm of the per-dimension
+// rounding bound of sq8_decode, |c|max[d] + 2 |vmin[d]| + 4.2 vdiff[d]; max_l ||c_l + e||.  ok: all of it finite
+void sq8d_constants(vdb_index_s *h) {
+    const int Dm = h->dim;
+    std::vector<double> cmax((size_t)Dm, 0.0), e((size_t)Dm);
+    double gmax = 0.0, emax = 0.0, camax = 0.0, can2 = 0.0, dec2 = 0.0;
+    for (int d = 0; d < Dm; ++d) {
+        const double g = (double)h->sq8_vdiff[(size_t)d] / 255.0;
+        e[(size_t)d] = (double)h->sq8_vmin[(size_t)d] + 128.5 * g;
+        gmax = std::max(gmax, g);
+        emax = std::max(emax, std::fabs(e[(size_t)d]));
+    }
+    for (int l = 0; l < h->nlist; ++l) {
+        double n2 = 0.0;
+        for (int d = 0; d < Dm; ++d) {
+            const double c = (double)h->ivf_centroids[(size_t)l * Dm + d];
+            cmax[(size_t)d] = std::max(cmax[(size_t)d], std::fabs(c));
+            n2 += (c + e[(size_t)d]) * (c + e[(size_t)d]);
+        }
+        can2 = std::max(can2, n2);
+    }
+    for (int d = 0; d < Dm; ++d) {
+        const double t = cmax[(size_t)d] + 2.0 * std::fabs((double)h->sq8_vmin[(size_t)d]) + 4.2 * (double)h->sq8_vdiff[(size_t)d];
+        camax = std::max(camax, cmax[(size_t)d]);
+        dec2 += t * t;
+    }
+    vdb_index_s::Sq8Direct k;
+    k.gmax = gmax > 0.0 ? std::nextafter((float)gmax, INFINITY) : 0.f;      // (rounded up: the scale window must hold for every w)
+    k.camax = std::nextafter((float)(camax + emax), INFINITY);
+    k.dec_norm = std::sqrt(dec2) * 1.000001;
+    k.can = std::sqrt(can2) * 1.000001;
+    k.ok = std::isfinite(k.gmax) && std::isfinite(k.camax) && std::isfinite(k.dec_norm) && std::isfinite(k.can);
+    h->sq8d = k;
+}
+
 // The panel space of an SQ8 index (D <= 128): spans, bias (||x^||^2), scale and fp16-exactness flag exactly as
 // ivf_build_panel_space derives them for an IVF-Flat index over the float32 rows x^ -- from a decoded copy that lives only
 // for this call, and is freed again together with the fp16 panels (a search converts those from the codes itself).
@@ -176,5 +212,6 @@ void sq8_add(vdb_index_s *h, const float *x_host, int64_t n, int64_t id_base, co
     }
     ivf_add_finish(h, assign_new, N0, id_base);
     sq8_build_panel_space(h);
+    sq8d_constants(h);
     h->ivf_built = true;
 }

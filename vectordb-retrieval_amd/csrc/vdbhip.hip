@@ -30,6 +30,7 @@
 #include "ivf_kloop.hpp"
 #include "ivf_kloop_i8.hpp"
 #include "ivf_sq8.hpp"
+#include "ivf_sq8_scan.hpp"
 #include "ivf_i8_plan.hpp"
 #include "ivf_i8.hpp"
 #include "ivf_pq.hpp"
@@ -247,6 +248,7 @@ struct Workspace {
     DevBuf pkeys{"ws.pkeys"}, pids{"ws.pids"};      // partial lists of the exhaustive / fallback passes
     DevBuf stage_q{"ws.stage_q"}, stage_d{"ws.stage_d"}, stage_i{"ws.stage_i"};  // host-API staging
     DevBuf sq8_panels{"ws.sq8_panels"};     // IVF-SQ8 / IVF-PQ / IVF-I8: the fp16 panels converted from the codes (the int8 panels) for the current batch
+    DevBuf sq8d_qterm{"ws.sq8d_qterm"}, sq8d_slot{"ws.sq8d_slot"};   // IVF-SQ8, option "ivf_sq8_direct": q . e per query (float64), the slot terms (float32 per query slot)
     DevBuf adc_tab{"ws.adc_tab"};           // PQ / IVF-PQ, ADC scan: the float32 lookup tables of the current batch, [nq][M][256] (pq_adc.hpp)
     DevBuf adc_scores{"ws.adc_scores"};     // IVF-PQ, ADC scan: the scores of the probed rows, [nq][stride] (ivf_pq_adc.hpp)
     DevBuf adc_aux{"ws.adc_aux"};           // ... its scale, flags, B [nq][nprobe] and score positions [nq][nprobe + 1]
@@ -388,6 +390,10 @@ struct vdb_index_s {
     int ivf_codec = 0;
     bool sq8_ranges = false;                 // vmin / vdiff trained or set
     std::vector<float> sq8_vmin, sq8_vdiff;  // host copies [dim]
+    // option "ivf_sq8_direct" (ivf_sq8_scan.hpp): what its scale windows and its error bound read of the centroids and ranges
+    // (sq8d_constants, ivf_sq8.inc; taken at every add), and whether the direct scan served the last batch
+    struct Sq8Direct { float gmax = 0.f, camax = 0.f; double dec_norm = 0.0, can = 0.0; bool ok = false; } sq8d;
+    bool sq8d_last = false;
     PqCodebooks ivfpq;                       // IVF-PQ: the codebooks of the residuals (M = 0: none yet) -- NOT `pq`: that marks a flat PQ handle
     // IVF-PQ ADC scan (ivfpq_adc_prepare, valid while codes.ivfpq_n2 is held): max ||x^||^2, Cn + Rn = max ||c_l|| + sqrt(sum_m max_c
     // ||cb[m][c]||^2), and whether both lie in the range the scan's scale can serve
@@ -497,6 +503,7 @@ constexpr OptionRow kOptions[] = {
     {"int8_only", &Options::int8_only, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::int8_only},
     {"i8_kloop", &Options::i8_kloop, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::i8k_ok},   // D > 128, next add: 1 = a byte-valued corpus also gets the int8 K-loop scan copy
     {"ivf_i8_kloop", &Options::ivf_i8_kloop, 2, {0, 1}, kNoRows, 0, nullptr, &vdb_index_s::ivf_i8k_ok},   // IVF-Flat, D > 128, next add: 1 = a byte-valued corpus also gets the int8 copy of the panel space for the int8 K-loop list scan
+    {"ivf_sq8_direct", &Options::ivf_sq8_direct, 2, {0, 1}},        // IVF-SQ8, D <= 128, next search: 1 = the list scan reads the 8-bit codes directly (no per-batch fp16 panels); no effect elsewhere
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -1487,6 +1494,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && !(h->ivf_codec == 3 && s.scan_dtype == 1)) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes, or from the int8 panels of IVF-I8 (whose integer batches take the int8 scan: 1)
+        if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct")
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;
