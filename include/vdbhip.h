@@ -84,7 +84,8 @@ typedef struct vdb_stats_s {
                                   3 = float32 lookup-table sums over the codes of a PQ or IVF-PQ index (last_path = VDB_PATH_PQ_ADC /
                                   VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly),
                                   4 = fp16 MFMA straight on the 8-bit codes of an IVF-SQ8 index, option "ivf_sq8_direct" (f32 accumulate;
-                                  last_path stays VDB_PATH_IVF, last_path_name "ivf") */
+                                  last_path stays VDB_PATH_IVF, last_path_name "ivf"); more than 128 dimensions: the K-loop form of that
+                                  scan, option "ivf_sq8_kloop" */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -777,7 +778,20 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       converted from the whole panel space for the batch: that pass and its workspace slab are not made
  *                       (vdb_stats.scan_dtype = 4).  Same results, bit for bit; a batch outside the scale windows of the route
  *                       (non-finite queries, extreme ranges) is answered by the exact list scan.  No effect on the other codecs,
- *                       on D > 128, a dimension below 13, "force_path" 1 / 3; a multi-device index refuses a non-zero value
+ *                       on D > 128 (there: "ivf_sq8_kloop"), a dimension below 13, "force_path" 1 / 3; a multi-device index refuses a
+ *                       non-zero value
+ *     "ivf_sq8_kloop"   IVF-SQ8 index (codec 1), D > 128 (up to 4096), takes effect at the next vdb_ivf_add / vdb_ivf_add_assigned:
+ *                       0 (default): every batch takes the exact list scan | 1: the add also builds the span tables of the lists
+ *                       (256-row or 1024-row spans: "ivf_tps" keeps its meaning), the accumulator inits ||x^||^2 of the decoded rows
+ *                       (computed from the codes in blocks of rows -- no float32 copy of the corpus, no fp16 panels; resident: 4 bytes
+ *                       per list-padded row plus 8 bytes per span) and the constants of the error bound.  A batch of vdb_ivf_search /
+ *                       _device / _partial_device (and vdb_reserve) that the list-major path serves is then scanned on the matrix
+ *                       cores straight from the list-order codes, 64 dimensions per K-step (vdb_stats.scan_dtype = 4), under an error
+ *                       bound of its own.  Same results, bit for bit; a batch outside the scale windows of the route (non-finite
+ *                       queries, extreme ranges) and the batches the list-major path declines ("force_path" 1 / 3, "ivf_min_batch",
+ *                       k > 256, too few bins) are answered by the exact list scan.  The square workgroup tile is not built for this
+ *                       route: such a handle plans as if "ivf_tile" were 0.  Independent of "ivf_sq8_direct".  No effect on the other
+ *                       codecs, on a flat index or on D <= 128; a multi-device index refuses a non-zero value
  *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
  *                       spans (tests: several blocks on a small corpus); also the rows per block of a vdb_ivf_add on an IVF-I8 index
  *                       (0 = default 1 048 576, not rounded): one block of float32 rows is all the device holds of them

@@ -349,6 +349,9 @@ constexpr ScanRow<IvfKloopArgs> kRowsIvfKloop[] = {VDB_KERNELS_IVF_KLOOP(VDB_ROW
 constexpr ScanRow<IvfKloopI8Args> kRowsIvfKloopI8[] = {VDB_KERNELS_IVF_KLOOP_I8(VDB_ROW_IVF_KLOOP_I8)};
 constexpr ScanRow<Sq8dScanArgs> kRowsIvfSq8d[] = {VDB_KERNELS_IVF_SQ8D(VDB_ROW_IVF_SQ8D)};
 #undef VDB_ROW_IVF_SQ8D
+#define VDB_ROW_IVF_SQ8K(...) {ScanKey{{__VA_ARGS__}}, &ivf_sq8_kloop_scan_kernel<__VA_ARGS__>},
+constexpr ScanRow<Sq8kScanArgs> kRowsIvfSq8k[] = {VDB_KERNELS_IVF_SQ8K(VDB_ROW_IVF_SQ8K)};
+#undef VDB_ROW_IVF_SQ8K
 #undef VDB_ROW_IVF_SCAN
 #undef VDB_ROW_IVF_SCAN_I8
 #undef VDB_ROW_IVF_KLOOP
@@ -356,7 +359,7 @@ constexpr ScanRow<Sq8dScanArgs> kRowsIvfSq8d[] = {VDB_KERNELS_IVF_SQ8D(VDB_ROW_I
 
 // the one <<<>>> of the plan's family, with the arguments of that family
 void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st, const IvfKloopI8Args *k8 = nullptr,
-                const Sq8dScanArgs *d8 = nullptr) {
+                const Sq8dScanArgs *d8 = nullptr, const Sq8kScanArgs *dk = nullptr) {
     const dim3 grid(p.grid_x, p.grid_y), block(p.block);
     switch (p.family) {
         case ScanFamily::scan: scan_kernel_of(kRowsIvfScan, p)<<<grid, block, 0, st>>>(*sa); break;
@@ -364,6 +367,7 @@ void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, co
         case ScanFamily::ivf_kloop: scan_kernel_of(kRowsIvfKloop, p)<<<grid, block, 0, st>>>(*ka); break;
         case ScanFamily::ivf_kloop_i8: scan_kernel_of(kRowsIvfKloopI8, p)<<<grid, block, 0, st>>>(*k8); break;
         case ScanFamily::ivf_sq8d: scan_kernel_of(kRowsIvfSq8d, p)<<<grid, block, 0, st>>>(*d8); break;
+        case ScanFamily::ivf_sq8k: scan_kernel_of(kRowsIvfSq8k, p)<<<grid, block, 0, st>>>(*dk); break;
         default: throw Error(VDB_ERR_INVALID, "internal: no list scan kernel for an empty plan");
     }
     VDB_HIP(hipGetLastError());
@@ -385,6 +389,7 @@ struct IvfBatch {
     int32_t *d_cnt;
     bool i8k;               // the int8 K-loop list scan is offered to this batch (ivf_i8k_plan.hpp, ivf_i8k_serves)
     bool sq8d;              // IVF-SQ8, option "ivf_sq8_direct": the direct scan of the codes serves this batch (ivf_sq8d_plan.hpp, ivf_sq8d_serves)
+    bool sq8k;              // IVF-SQ8, D > 128, option "ivf_sq8_kloop": the K-loop scan of the codes serves this batch (ivf_sq8k_serves)
     bool filtered;          // a vdb_ivf_search_filtered call (ivf_filter.inc): the scans read the masked copies of the handle's filter,
                             // the exact stages test its list-order allow words
 };
@@ -423,7 +428,7 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     L.d_slot_query = L.d_cursor + nlist;
     L.d_fb_done = L.d_slot_query + b.g.max_slots;
     ws.fb_list.reserve((size_t)nb * sizeof(int32_t));
-    if (b.sq8d) {
+    if (b.sq8d || b.sq8k) {
         ws.sq8d_qterm.reserve((size_t)nb * sizeof(double));
         ws.sq8d_slot.reserve((size_t)b.g.max_slots * sizeof(float));
     }
@@ -451,7 +456,7 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
                            b.i8k ? 1 : L.c.use_i8 ? (1 | (h->opt.ivf_i8_group == 8 ? 4 : 0)) : 0};   // (quads or octs, see plan_ivf_i8; the K-loop scan: its own groups)
     const bool from_coarse = h->coarse->info_valid_nq == nb;   // the coarse search of this batch already took the statistics of these queries
     if (!from_coarse) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, b.st>>>(b.q, total, L.info, fin);
-    if (b.sq8d) {           // the direct scan of the codes: its own scale, bounds and operand rows (ivf_sq8_scan.hpp), the same counts
+    if (b.sq8d || b.sq8k) { // the direct scans of the codes: their own scale, bounds and operand rows (ivf_sq8_scan.hpp; D > 128: in the K order of ivf_sq8_kloop.hpp), the same counts
         Sq8dPrepArgs da{};
         da.probes = L.probes; da.npairs = b.g.pairs; da.nlist = h->nlist; da.ppb = L.c.ppb; da.cnt = b.d_cnt;
         da.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
@@ -462,7 +467,8 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
         da.info = L.info; da.src = from_coarse ? batch_info(h->coarse->ws) : nullptr;
         da.gmax = h->sq8d.gmax; da.camax = h->sq8d.camax; da.dec_norm = h->sq8d.dec_norm; da.can = h->sq8d.can;
         da.xnorm_max = sqrtf(h->maxnorm2) * 1.0000002f; da.maxnorm2 = h->maxnorm2; da.consts_ok = h->sq8d.ok ? 1 : 0;
-        ivf_sq8d_prep_kernel<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
+        const auto prep = b.sq8k ? ivf_sq8k_prep_kernel : ivf_sq8d_prep_kernel;
+        prep<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
         return;
     }
     IvfPrepArgs pa{};
@@ -517,8 +523,8 @@ const half8 *ivf_sq8_panels(const IvfBatch &b) {
     return h->ws.sq8_panels.as<half8>();
 }
 
-// SQ8, option "ivf_sq8_direct": the slot terms of the planned slots, then the scan of the codes themselves (ivf_sq8_scan.hpp)
-void ivf_scan_sq8d(const IvfBatch &b, const ScanArgs &sa) {
+// SQ8, the direct scans: the slot terms of the planned slots (one float32 per (query, list) slot)
+const float *ivf_sq8d_slot_terms(const IvfBatch &b, const ScanArgs &sa) {
     vdb_index_s *h = b.h;
     Sq8dSlotArgs ta{};
     ta.probes = h->plan.ivf_probe_i.as<int64_t>(); ta.slot_of = h->plan.ivf_slot_of.as<int32_t>(); ta.npairs = b.g.pairs;
@@ -527,11 +533,34 @@ void ivf_scan_sq8d(const IvfBatch &b, const ScanArgs &sa) {
     ta.slot_term = h->ws.sq8d_slot.as<float>();
     ivf_sq8d_slot_kernel<<<dim3((unsigned)((b.g.pairs * 16 + 255) / 256)), dim3(256), 0, b.st>>>(ta);
     VDB_HIP(hipGetLastError());
+    return ta.slot_term;
+}
+
+// SQ8, D > 128, option "ivf_sq8_kloop": the slot terms, then the K-loop scan of the codes (ivf_sq8_kloop.hpp); sa.panels is null
+void ivf_scan_sq8k(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    const IvfLaunch p = plan_ivf_sq8k(b.shape, h->opt, b.g, kgroup);
+    Sq8kScanArgs da{};
+    da.codes = h->codes.sq8_codes.as<unsigned char>(); da.D4 = h->D4;
+    da.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); da.span_valid = h->lists.ivf_span_valid.as<int32_t>();
+    da.bias = sa.bias; da.wrows = sa.qrows; da.slot_term = ivf_sq8d_slot_terms(b, sa); da.info = sa.info;
+    da.bin_m[0] = sa.bin_m1; da.bin_m[1] = sa.bin_m2; da.bin_m[2] = sa.bin_m3;
+    da.bin_m[3] = h->ws.bin_m4.as<float>(); da.bin_m[4] = h->ws.bin_m5.as<float>();
+    da.item_list = sa.item_list; da.item_slot0 = sa.item_slot0; da.item_bin0 = sa.item_bin0; da.n_items = sa.n_items;
+    da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
+    da.nk = h->ksteps / 4;
+    ivf_launch(p, nullptr, nullptr, nullptr, b.st, nullptr, nullptr, &da);
+}
+
+// SQ8, option "ivf_sq8_direct": the slot terms, then the scan of the codes themselves (ivf_sq8_scan.hpp)
+void ivf_scan_sq8d(const IvfBatch &b, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    const float *slot_term = ivf_sq8d_slot_terms(b, sa);
     const IvfLaunch p = plan_ivf_sq8d(b.shape, h->opt, b.g);
     Sq8dScanArgs da{};
     da.codes = h->codes.sq8_codes.as<unsigned char>(); da.D4 = h->D4;
     da.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); da.span_valid = h->lists.ivf_span_valid.as<int32_t>();
-    da.bias = sa.bias; da.wrows = sa.qrows; da.slot_term = ta.slot_term; da.info = sa.info;
+    da.bias = sa.bias; da.wrows = sa.qrows; da.slot_term = slot_term; da.info = sa.info;
     da.bin_m1 = sa.bin_m1; da.bin_m2 = sa.bin_m2; da.bin_m3 = sa.bin_m3;
     da.item_list = sa.item_list; da.item_slot0 = sa.item_slot0; da.item_bin0 = sa.item_bin0; da.n_items = sa.n_items;
     da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
@@ -683,7 +712,7 @@ void ivf_search_lists(const IvfBatch &b) {
     // IVF-I8 under "ivf_i8_scratch" = 0 holds no fp16 panels at all: the fp16 scan is not launched, and a batch the int8 scan
     // does not serve is flagged as a whole for the tail's exact list scan (ivf_i8_flag_kernel)
     const bool i8_no_slab = ivf_i8(h) && !h->opt.ivf_i8_scratch;
-    sa.panels = (i8_no_slab || b.sq8d) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
+    sa.panels = (i8_no_slab || b.sq8d || b.sq8k) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
     sa.bias = b.filtered ? h->ivf_filter.bias_f.as<float>() : h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -695,7 +724,9 @@ void ivf_search_lists(const IvfBatch &b) {
     sa.n_items = &L.plan->n_items;
     sa.list_pspan0 = h->lists.ivf_list_pspan0.as<int32_t>();
     timing_mark(h, b.tslot, 0, b.st);
-    if (b.g.kloop) {
+    if (b.sq8k) {
+        ivf_scan_sq8k(b, L.c.kgroup, sa);
+    } else if (b.g.kloop) {
         ivf_scan_kloop(b, L.c.kgroup, sa);
         if (b.i8k) ivf_scan_kloop_i8(b, L.c.kgroup, sa);
     } else {
@@ -809,8 +840,11 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         b.shape = shape;
         b.filtered = filtered;
         const IvfAdcPlan adc = ivf_adc_plan(h->opt, h->ivf_codec, h->ivfpq.M, adc_ranges, h->N, adc_longest, b.nb, k, b.nprobe);
-        if (!adc.ok) b.g = filtered ? ivf_filter_geometry(shape, h->opt, b.nb, k, b.nprobe, h->ivf_filter_count) : ivf_geometry(shape, h->opt, b.nb, k, b.nprobe);
+        if (!adc.ok) b.g = filtered ? ivf_filter_geometry(shape, h->opt, b.nb, k, b.nprobe, h->ivf_filter_count)
+                                    : ivf_geometry(shape, h->sq8k_ok ? ivf_sq8k_options(h->opt) : h->opt, b.nb, k, b.nprobe);
         b.sq8d = ivf_sq8d_serves(h->opt.ivf_sq8_direct, h->ivf_codec, b.g.ok, b.g.kloop, D4, filtered);
+        b.sq8k = ivf_sq8k_serves(h->opt.ivf_sq8_kloop, h->ivf_codec, h->sq8k_ok, b.g.ok && b.g.kloop, filtered);
+        if (h->sq8k_ok && !b.sq8k) b.g = IvfGeom{};      // (no fp16 K-loop scan behind it: the exact list scan)
         b.i8k = ivf_i8k_serves(h->ivf_i8k_ok && h->scan.panels8.p && h->scan.rows8.p, h->opt.panel_dtype, h->opt.ivf_tile, filtered, b.g.ok && b.g.kloop);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
@@ -839,7 +873,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         any_adc = any_adc || adc.ok;
         timing_mark(h, b.tslot, 2, st);
         any_mfma = any_mfma || b.g.ok;
-        h->sq8d_last = b.sq8d;
+        h->sq8d_last = b.sq8d || b.sq8k;
     }
     } catch (...) {
         h->ev_used = ev_mark;

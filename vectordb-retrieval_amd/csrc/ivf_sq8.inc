@@ -5,6 +5,7 @@
 // {vmin, vdiff} zero padded to D4, and (D <= 128) the panel-space bias and scales.  Every row is scored as its decoded x^
 // (refine.hpp, sq8_key); D <= 128 batches take the list-major MFMA scan on fp16 panels converted from the codes per search
 // (ivf_search_lists), D > 128 and small batches the exact list scan -- the result is the IVF-Flat result over x^ either way.
+// Option "ivf_sq8_kloop": D > 128 keeps span tables and the panel-space bias too and scans the codes themselves (sq8k_build_space).
 
 constexpr int64_t kSq8TrainRows = 100000;      // rows the range training reads at most (evenly spaced beyond that)
 
@@ -90,6 +91,7 @@ void sq8_train_ranges(vdb_index_s *h, const float *x_host, int64_t n) {
 }
 
 void ivf_build_panel_space(vdb_index_s *h);     // (ivf.inc)
+int64_t ivf_build_spans(vdb_index_s *h, int span_rows);
 
 // What the direct scan (option "ivf_sq8_direct", ivf_sq8_scan.hpp) reads of the centroids and ranges, in float64 on the host: with
 // g = vdiff / 255 and e = vmin + 128.5 g -- max g; max |c_l[d]| + max |e[d]| (the window of the slot term); the norm of the per-dimension
@@ -130,9 +132,75 @@ void sq8d_constants(vdb_index_s *h) {
 // The panel space of an SQ8 index (D <= 128): spans, bias (||x^||^2), scale and fp16-exactness flag exactly as
 // ivf_build_panel_space derives them for an IVF-Flat index over the float32 rows x^ -- from a decoded copy that lives only
 // for this call, and is freed again together with the fp16 panels (a search converts those from the codes itself).
+// D > 128, option "ivf_sq8_kloop": what the K-loop scan of the codes (ivf_sq8_kloop.hpp) needs of the panel space, without any panels --
+// the span tables, the accumulator inits (||x^||^2 per list-padded row, kPadBias on padding rows: 4 bytes per padded row) and maxnorm2.
+// The norms come from the codes in blocks of rows: a block is decoded into a scratch buffer and read by the norm pass of index_stats
+// (corpus_stats_kernel: one float64 chain per row, rounded once), so the bias is the one an IVF-Flat index over x^ holds -- and the
+// float32 rows of the whole index (38 GB at 12.5M x 768) never exist.
+constexpr size_t kSq8kNormBlockBytes = (size_t)128 << 20;
+void sq8k_build_space(vdb_index_s *h) {
+    hipStream_t st = nullptr;
+    const int64_t N = h->N;
+    const int D4 = h->D4;
+    h->ivf_tps = ivf_tps_of(h->opt, N, h->nlist);
+    const int span_rows = h->ivf_tps * 16;
+    const int64_t P = ivf_build_spans(h, span_rows);
+    if (P == 0) return;
+    DevBuf block;
+    const int64_t block_rows = std::max<int64_t>(1024, (int64_t)(kSq8kNormBlockBytes / ((size_t)D4 * sizeof(float))));
+    block.reserve((size_t)std::min(N, block_rows) * D4 * sizeof(float));
+    h->rows.xnorm2.reserve((size_t)N * sizeof(float));
+    h->kept.stats.reserve(sizeof(IndexStats));
+    try {
+        VDB_HIP(hipMemsetAsync(h->kept.stats.p, 0, sizeof(IndexStats), st));
+        VDB_HIP(hipMemsetAsync(block.p, 0, (size_t)std::min(N, block_rows) * D4 * sizeof(float), st));     // (the padding columns stay 0)
+        const Sq8Rows all = sq8_rows(h);
+        for (int64_t r0 = 0; r0 < N; r0 += block_rows) {
+            const int64_t nb = std::min(block_rows, N - r0);
+            const Sq8Rows part{all.codes + (size_t)r0 * D4, all.list + r0, all.cent, all.vmin, all.vdiff};
+            sq8_decode_rows_kernel<<<dim3((unsigned)std::min<int64_t>((nb * h->dim + 255) / 256, 1 << 20)), dim3(256), 0, st>>>(
+                part, nb, h->dim, D4, D4, block.as<float>());
+            corpus_stats_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st>>>(block.as<float>(), nb, D4, h->rows.xnorm2.as<float>() + r0,
+                                                                                         h->kept.stats.as<IndexStats>());
+            VDB_HIP(hipGetLastError());
+        }
+        IndexStats hs;
+        VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        memcpy(&h->absmax, &hs.absmax_bits, 4);
+        memcpy(&h->maxnorm2, &hs.maxnorm2_bits, 4);
+        h->nonfinite = hs.nonfinite != 0;
+        if (!h->nonfinite) {
+            h->scan.bias.reserve((size_t)P * span_rows * sizeof(float));
+            ivf_build_bias_kernel<<<dim3((unsigned)((P * span_rows + 255) / 256)), dim3(256), 0, st>>>(
+                h->rows.xnorm2.as<float>(), P, span_rows, h->metric, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
+                h->scan.bias.as<float>());
+            VDB_HIP(hipGetLastError());
+            VDB_HIP(hipStreamSynchronize(st));
+        }
+    } catch (...) {
+        h->rows.xnorm2.release();
+        h->scan.bias.release();
+        throw;
+    }
+    h->rows.xnorm2.release();                                  // (the norms only fed the bias)
+    h->sq8k_ok = !h->nonfinite;
+    h->tile16 = h->sq8k_ok;                                    // (the plan's K-loop geometry: ivf_shape_of)
+    h->ivf_mfma_ok = h->sq8k_ok;
+}
+
 void sq8_build_panel_space(vdb_index_s *h) {
     h->ivf_mfma_ok = false;
-    if (h->N == 0 || h->ksteps > kMaxKSteps) return;      // D > 128: the exact list scan serves every batch
+    if (h->sq8k_ok) {         // (the bookkeeping of the last add goes with its lists; the rule below decides anew)
+        h->scan.bias.release();
+        h->sq8k_ok = false;
+        h->tile16 = false;
+    }
+    if (h->N == 0) return;
+    if (h->ksteps > kMaxKSteps) {     // D > 128: the exact list scan serves every batch, unless option "ivf_sq8_kloop" is set
+        if (ivf_sq8k_builds(h->opt.ivf_sq8_kloop, h->ivf_codec, h->ksteps, h->dim)) sq8k_build_space(h);
+        return;
+    }
     const size_t bytes = (size_t)h->N * h->D4 * sizeof(float);
     h->rows.x32.reserve_exact(bytes);
     try {

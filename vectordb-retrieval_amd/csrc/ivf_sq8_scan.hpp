@@ -84,7 +84,9 @@ __device__ __forceinline__ _Float16 sq8d_operand(float q, float vdiff, double bs
     return (_Float16)(float)t;
 }
 
-__global__ __launch_bounds__(256) void ivf_sq8d_prep_kernel(Sq8dPrepArgs a) {
+// KLOOP: the operand rows in the K order of the D > 128 scan (ivf_sq8_kloop.hpp, ivf_sq8k_operand_dim) instead of chunk order
+template <bool KLOOP>
+__device__ __forceinline__ void sq8d_prep_body(const Sq8dPrepArgs &a) {
     extern __shared__ int ivf_hist[];
     __shared__ QueryBatchInfo s_info;
     if (blockIdx.x >= a.n_eps_blocks + a.n_row_blocks) {
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void ivf_sq8d_prep_kernel(Sq8dPrepArgs a) {
         half8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int d = ivf_sq8d_chunk_dim(c, j0 + j, a.D, a.D4);
+            const int d = KLOOP ? ivf_sq8k_operand_dim(e0 + j, a.D, a.D4) : ivf_sq8d_chunk_dim(c, j0 + j, a.D, a.D4);
             double t;
             o[j] = d < 0 ? (_Float16)0.f : sq8d_operand(a.Q[(size_t)q * a.D + d], a.vdiff[d], bs, t);
         }
@@ -161,6 +163,7 @@ __global__ __launch_bounds__(256) void ivf_sq8d_prep_kernel(Sq8dPrepArgs a) {
     a.eps[q] = (float)e + 1.0e-30f;
     a.qterm[q] = qe;
 }
+__global__ __launch_bounds__(256) void ivf_sq8d_prep_kernel(Sq8dPrepArgs a) { sq8d_prep_body<false>(a); }
 
 // ---- per batch, after the plan: the slot terms.  16 lanes per (query, probe) pair ---------------------------------------------------
 struct Sq8dSlotArgs {

@@ -31,6 +31,7 @@
 #include "ivf_kloop_i8.hpp"
 #include "ivf_sq8.hpp"
 #include "ivf_sq8_scan.hpp"
+#include "ivf_sq8_kloop.hpp"
 #include "ivf_i8_plan.hpp"
 #include "ivf_i8.hpp"
 #include "ivf_pq.hpp"
@@ -394,6 +395,7 @@ struct vdb_index_s {
     // (sq8d_constants, ivf_sq8.inc; taken at every add), and whether the direct scan served the last batch
     struct Sq8Direct { float gmax = 0.f, camax = 0.f; double dec_norm = 0.0, can = 0.0; bool ok = false; } sq8d;
     bool sq8d_last = false;
+    bool sq8k_ok = false;                    // option "ivf_sq8_kloop" (ivf_sq8_kloop.hpp): the last add built the K-loop bookkeeping of the codes (sq8k_build_space, ivf_sq8.inc)
     PqCodebooks ivfpq;                       // IVF-PQ: the codebooks of the residuals (M = 0: none yet) -- NOT `pq`: that marks a flat PQ handle
     // IVF-PQ ADC scan (ivfpq_adc_prepare, valid while codes.ivfpq_n2 is held): max ||x^||^2, Cn + Rn = max ||c_l|| + sqrt(sum_m max_c
     // ||cb[m][c]||^2), and whether both lie in the range the scan's scale can serve
@@ -504,6 +506,7 @@ constexpr OptionRow kOptions[] = {
     {"i8_kloop", &Options::i8_kloop, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::i8k_ok},   // D > 128, next add: 1 = a byte-valued corpus also gets the int8 K-loop scan copy
     {"ivf_i8_kloop", &Options::ivf_i8_kloop, 2, {0, 1}, kNoRows, 0, nullptr, &vdb_index_s::ivf_i8k_ok},   // IVF-Flat, D > 128, next add: 1 = a byte-valued corpus also gets the int8 copy of the panel space for the int8 K-loop list scan
     {"ivf_sq8_direct", &Options::ivf_sq8_direct, 2, {0, 1}},        // IVF-SQ8, D <= 128, next search: 1 = the list scan reads the 8-bit codes directly (no per-batch fp16 panels); no effect elsewhere
+    {"ivf_sq8_kloop", &Options::ivf_sq8_kloop, 2, {0, 1}},          // IVF-SQ8, D > 128, next add: 1 = span tables and accumulator inits for the K-loop list scan of the 8-bit codes; no effect elsewhere
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -1494,7 +1497,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             s.scan_dtype = qi.i8_mode ? 1 : 0;
         }
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && !(h->ivf_codec == 3 && s.scan_dtype == 1)) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes, or from the int8 panels of IVF-I8 (whose integer batches take the int8 scan: 1)
-        if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct")
+        if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct"; D > 128: "ivf_sq8_kloop")
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;

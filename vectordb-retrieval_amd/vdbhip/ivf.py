@@ -208,15 +208,20 @@ class IVFSQ8Index(IVFFlatIndex):
     with 8-bit codes of the residuals, per-dimension min / max ranges).  One byte per dimension and no float32 rows; the
     results are exact over the decoded rows (include/vdbhip.h).  `train` fits the centroids and then the ranges on the same
     rows; `set_centroids` + `train_ranges` / `set_ranges` inject them instead.  One GPU only.  `direct_codes` (None: untouched):
-    option "ivf_sq8_direct" -- the list scan reads the codes themselves instead of fp16 panels made per batch (dim <= 128; same results)."""
+    option "ivf_sq8_direct" -- the list scan reads the codes themselves instead of fp16 panels made per batch (dim <= 128; same results).
+    `direct_kloop` (None: untouched): option "ivf_sq8_kloop", in effect from the next add -- dim > 128: the add builds span tables and
+    accumulator inits and batches take the K-loop list scan of the codes instead of the exact list scan (same results)."""
 
-    def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0, direct_codes: Optional[bool] = None):
+    def __init__(self, dim: int, nlist: int, metric: str = "l2", device=0, direct_codes: Optional[bool] = None,
+                 direct_kloop: Optional[bool] = None):
         one_device(device, "IVF<nlist>,SQ8 runs on one GPU: a multi-device index (more than one device id) is not "
                            "available for the SQ8 codec")
         super().__init__(dim, nlist, metric, device)
         _ffi.check(self._lib.vdb_ivf_set_codec(self._handle(), 1), build_time=True)
         if direct_codes is not None:
             self.set_option("ivf_sq8_direct", float(int(bool(direct_codes))))
+        if direct_kloop is not None:
+            self.set_option("ivf_sq8_kloop", float(int(bool(direct_kloop))))
 
     def train_ranges(self, x: np.ndarray) -> None:
         """vmin / vdiff from the residuals of `x` against the installed centroids (at most 100 000 rows are read)."""
@@ -317,8 +322,16 @@ def _build_ivf(vectors: np.ndarray, dim: int, key: str, metric: str, device: int
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
     _set_int8_kloop(index, params)
     _set_direct_codes(index, params)
+    _set_direct_kloop(index, params)
     index.add(vectors)
     return index
+
+
+def _set_direct_kloop(index: IVFFlatIndex, params: dict) -> None:
+    """`direct_kloop: true` (IVF-SQ8, more than 128 dimensions): option "ivf_sq8_kloop", set before the add -- the add builds what the
+    K-loop list scan of the 8-bit codes needs.  No effect on the other codecs or at 128 dimensions and below."""
+    if params.get("direct_kloop") is not None:
+        index.set_option("ivf_sq8_kloop", float(int(bool(params["direct_kloop"]))))
 
 
 def _set_direct_codes(index: IVFFlatIndex, params: dict) -> None:
@@ -338,7 +351,8 @@ def _set_int8_kloop(index: IVFFlatIndex, params: dict) -> None:
 class HipApproximateSearch(RawAlgorithm):
     """ApproximateSearch semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8": train -> add -> nprobe from kwargs; raw
     FAISS conventions (no normalisation, no sign flip).  `int8_kloop: true` (a config entry): option "ivf_i8_kloop" before the add;
-    `direct_codes: true`: option "ivf_sq8_direct" (an SQ8 key: the list scan reads the codes directly)."""
+    `direct_codes: true`: option "ivf_sq8_direct" (an SQ8 key: the list scan reads the codes directly); `direct_kloop: true`: option
+    "ivf_sq8_kloop" before the add (an SQ8 key of more than 128 dimensions: the K-loop list scan of the codes)."""
 
     def __init__(self, name: str, dimension: int, index_type: str, metric: str = "l2", device: Optional[int] = None,
                  **kwargs: Any) -> None:
@@ -438,7 +452,8 @@ class HipApproximateSearch(RawAlgorithm):
             raise ValueError("Persisted inverted lists do not match the persisted corpus and centroids")
         _set_int8_kloop(self.index, self.config)
         _set_direct_codes(self.index, self.config)
-        self.index.add(vectors, list_of_row=stored)   # ... and so are the stored lists: no assignment pass either
+        _set_direct_kloop(self.index, self.config)
+        self.index.add(vectors, list_of_row=stored)  # ... and so are the stored lists: no assignment pass either
         self.index.set_nprobe(int(self.config.get("nprobe", manifest.get("nprobe", 1))))
         self.index_built = True
         return result
@@ -446,10 +461,11 @@ class HipApproximateSearch(RawAlgorithm):
 
 class HipIVFIndexer(BaseIndexer):
     """FaissFactoryIndexer / FaissIVFIndexer semantics for "IVF<nlist>,Flat" and "IVF<nlist>,SQ8" keys.  `int8_kloop: true`: option
-    "ivf_i8_kloop" of the index, set before the rows are added.  `direct_codes: true` (an SQ8 key): option "ivf_sq8_direct"."""
+    "ivf_i8_kloop" of the index, set before the rows are added.  `direct_codes: true` (an SQ8 key): option "ivf_sq8_direct"; `direct_kloop: true`
+    (an SQ8 key, more than 128 dimensions): option "ivf_sq8_kloop", set before the rows are added."""
 
     _RESERVED = {"index_key", "index_type", "device", "device_ids", "niter", "seed", "max_points_per_centroid", "int8_lists", "int8_kloop",
-                 "direct_codes"}
+                 "direct_codes", "direct_kloop"}
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", index_type: Optional[str] = None,
                  index_key: Optional[str] = None, **kwargs: Any) -> None:
@@ -477,13 +493,17 @@ class HipIVFSearcher(FaissStyleSearcher):
     "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer).  `int8_kloop`
     (`int8_kloop: true`): option "ivf_i8_kloop" of the attached index; it takes effect at an add, so give it to the HipIVFIndexer
     as well -- here it keeps the option set for rows added to the index later.  `direct_codes` (`direct_codes: true`): option
-    "ivf_sq8_direct" of the attached index, from the next search on (an IVF-SQ8 artifact; no effect on the others)."""
+    "ivf_sq8_direct" of the attached index, from the next search on (an IVF-SQ8 artifact; no effect on the others).  `direct_kloop`
+    (`direct_kloop: true`): option "ivf_sq8_kloop" of the attached index; like `int8_kloop` it takes effect at an add, so give it to the
+    HipIVFIndexer as well."""
 
     _kind = "hip_ivf"
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None,
-                 int8_kloop: Optional[bool] = None, direct_codes: Optional[bool] = None, **kwargs: Any) -> None:
+                 int8_kloop: Optional[bool] = None, direct_codes: Optional[bool] = None, direct_kloop: Optional[bool] = None,
+                 **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
+        self.direct_kloop = None if direct_kloop is None else int(bool(direct_kloop))
         self.direct_codes = None if direct_codes is None else int(bool(direct_codes))
         self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
         self.int8_kloop = None if int8_kloop is None else int(bool(int8_kloop))
@@ -503,6 +523,8 @@ class HipIVFSearcher(FaissStyleSearcher):
             self.index.set_option("ivf_i8_kloop", float(self.int8_kloop))
         if self.direct_codes is not None:
             self.index.set_option("ivf_sq8_direct", float(self.direct_codes))
+        if self.direct_kloop is not None:
+            self.index.set_option("ivf_sq8_kloop", float(self.direct_kloop))
 
     def batch_search(self, queries: np.ndarray, k: int = 10, allowed=None) -> Tuple[np.ndarray, np.ndarray]:
         """`allowed` (None: every row): what IVFFlatIndex.set_filter takes -- the k nearest among those rows of the probed lists,
