@@ -85,7 +85,9 @@ typedef struct vdb_stats_s {
                                   VDB_PATH_IVFPQ_ADC; there last_candidates counts ROWS re-scored exactly),
                                   4 = fp16 MFMA straight on the 8-bit codes of an IVF-SQ8 index, option "ivf_sq8_direct" (f32 accumulate;
                                   last_path stays VDB_PATH_IVF, last_path_name "ivf"); more than 128 dimensions: the K-loop form of that
-                                  scan, option "ivf_sq8_kloop" */
+                                  scan, option "ivf_sq8_kloop",
+                                  5 = fp16 MFMA on fragments of an fp16 codebook table gathered by the product codes of an IVF-PQ index of
+                                  more than 128 dimensions, option "ivf_pq_kloop" (f32 accumulate; last_path stays VDB_PATH_IVF) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -526,6 +528,9 @@ int vdb_ivf_i8_get_rows(vdb_handle h, int8_t *rows_host, int *cx);
  * dim <= 128: batches the list-major path serves make the fp16 panels of the whole panel space from the codes per batch, as
  * (half)((c_l[d] + codebook entry) * sx) -- IVF-Flat's panels of x^, so the same error bound holds (vdb_stats.scan_dtype = 2) --
  * and run the MFMA list scan on them; dim > 128, small batches and "force_path" 1 / 3 take the exact list scan over the codes.
+ * dim > 128 with option "ivf_pq_kloop" = 1 at the add: batches the list-major path serves are scanned on the matrix cores straight
+ * from the product codes -- the A fragments are 16-byte pieces of an fp16 table of the codebooks, gathered by the code bytes; no
+ * float32 rows and no fp16 panels become resident (vdb_stats.scan_dtype = 5; DESIGN 4.4 "IVF-PQ K-loop scan").
  * A third path, off by default: with option "ivfpq_adc_max_batch" = B a batch of at most B queries (any dim; k <= 1024, M <= 159,
  * "force_path" 0, at most 256 MiB of scores = 4 nq min(ntotal, nprobe x longest list) bytes) scores the rows of its probed lists
  * from ONE float32 lookup table per query, a scalar per (query, probe) and a resident float32 ||x^||^2 per row, re-scores the rows
@@ -792,6 +797,21 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       k > 256, too few bins) are answered by the exact list scan.  The square workgroup tile is not built for this
  *                       route: such a handle plans as if "ivf_tile" were 0.  Independent of "ivf_sq8_direct".  No effect on the other
  *                       codecs, on a flat index or on D <= 128; a multi-device index refuses a non-zero value
+ *     "ivf_pq_kloop"    IVF-PQ index (codec 2), D > 128 (up to 4096; M <= 256 and M x 8 ceil(dsub / 8) <= 4096), takes effect at the next
+ *                       vdb_ivf_add / vdb_ivf_add_assigned / vdb_ivfpq_add_codes: 0 (default): every batch takes the exact list scan |
+ *                       1: the add also builds the span tables of the lists ("ivf_tps" keeps its meaning), the accumulator inits
+ *                       ||x^||^2 of the decoded rows (computed from the codes in blocks of rows -- no float32 copy of the corpus, no
+ *                       fp16 panels), an fp16 table of the scaled codebooks, every sub-space zero padded to a multiple of 8 dimensions,
+ *                       and the constants of the error bound (resident: 4 bytes per list-padded row, 8 bytes per span, the table of
+ *                       M x 256 x 8 ceil(dsub / 8) x 2 bytes and 12 bytes per dimension).  A batch of vdb_ivf_search / _device /
+ *                       _partial_device (and vdb_reserve) that the list-major path serves is then scanned on the matrix cores, the A
+ *                       operand gathered from that table by the list-order product codes (vdb_stats.scan_dtype = 5), under an error
+ *                       bound of its own.  Same results, bit for bit; a batch outside the scale windows of the route (non-finite
+ *                       queries, extreme codebooks) and the batches the list-major path declines ("force_path" 1 / 3,
+ *                       "ivf_min_batch", k > 256, too few bins) are answered by the exact list scan, batches "ivfpq_adc_max_batch"
+ *                       admits by the lookup-table scan.  The square workgroup tile is not built for this route: such a handle plans
+ *                       as if "ivf_tile" were 0.  New codebooks or centroids drop what the add built.  No effect on the other codecs,
+ *                       on a flat index or on D <= 128; a multi-device index refuses a non-zero value
  *     "int8_block_rows" rows per ingestion block of that build, 0 (default: 4 194 304) .. 2^31 - 1, rounded up to whole 512-row
  *                       spans (tests: several blocks on a small corpus); also the rows per block of a vdb_ivf_add on an IVF-I8 index
  *                       (0 = default 1 048 576, not rounded): one block of float32 rows is all the device holds of them

@@ -18,6 +18,8 @@ the exact float64 result, and (bytes_resident - bytes_workspace) / (4 N D).  Pri
             results asserted identical in every cell, then the stage timers of each setting.  Workloads: Gaussian 1M x 128, l2,
             IVF1024,PQ64 and IVF1024,PQ16 at nprobe 8 and 32; unit vectors 100 000 x 384, ip, IVF256,PQ64 at nprobe 24.  "value_to_set":
             the largest nq up to which every batch size is faster with the option by more than 8 % (the box-to-box spread).
+
+    --kloop the D > 128 legs of option "ivf_pq_kloop" (kloop_legs below; profiles/r32_bench_ivf_pq_kloop.json).
 """
 from __future__ import annotations
 
@@ -148,8 +150,98 @@ def adc_main(args) -> None:
                                  for p, v in res["nprobe"].items()}}), flush=True)
 
 
+KLOOP_SHAPES = (("l2", 768, 256, 24, None), ("ip", 384, 100, 32, 100_000), ("ip", 384, 256, 24, 100_000))   # metric, d, nlist, nprobe, n (None: --n)
+
+
+def kloop_legs(args) -> None:
+    """`--kloop`: option "ivf_pq_kloop" at D > 128.  IVF256,PQ64 at nprobe 24 over `--n` x 768 Gaussian rows (l2) and IVF100,PQ64 /
+    IVF256,PQ64 over 100 000 x 384 (ip), batches of 1, 64 and `--nq` queries, k = 10.  The centroids are the first nlist rows, the
+    codebooks seeded Gaussian (std 0.5).  Per leg, alternating twice on ONE handle: the K-loop scan of the codes against `force_path` = 1
+    (the exact list scan: what every such batch took before the option existed); in the same run an IVF-Flat handle over the decoded
+    rows on its fp16 K-loop scan and an IVF-SQ8 handle on option "ivf_sq8_kloop".  Recorded: per-call time, stage times, scan_dtype,
+    fallback queries, bytes resident right after the add, add time with the option 0 and 1.  Prints ONE JSON line."""
+    import torch
+
+    import vdbhip
+
+    dev = torch.device("cuda:0")
+    k, M = 10, 64
+    stream = torch.cuda.current_stream().cuda_stream
+    held = lambda ix: (lambda s: s["bytes_resident"] - s["bytes_workspace"])(ix.stats())
+    out = {}
+    for metric, d, nlist, nprobe, n in KLOOP_SHAPES:
+        n = n or args.n
+        g = torch.Generator(device=dev)
+        g.manual_seed(0)
+        X = torch.randn((n, d), generator=g, device=dev, dtype=torch.float32).cpu().numpy()
+        Q_t = torch.randn((args.nq, d), generator=g, device=dev, dtype=torch.float32)
+        D_t = torch.empty((args.nq, k), dtype=torch.float32, device=dev)
+        I_t = torch.empty((args.nq, k), dtype=torch.int64, device=dev)
+        C = X[:nlist].copy()
+        cb = (0.5 * np.random.default_rng(0).standard_normal((M, 256, d // M))).astype(np.float32)
+        add_s, resident, handles = {}, {}, {}
+        for on in (0, 1):
+            ix = vdbhip.IVFPQIndex(d, nlist, M, metric, 0, direct_kloop=bool(on))
+            ix.set_centroids(C)
+            ix.set_codebooks(cb)
+            t0 = time.perf_counter()
+            ix.add(X)
+            add_s[f"option{on}"] = round(time.perf_counter() - t0, 3)
+            resident[f"option{on}"] = held(ix)
+            handles[on] = ix
+        handles[0].close()
+        pq = handles[1]
+        lor = pq.assignment()
+        Xh = pq.reconstruct()
+        fl = vdbhip.IVFFlatIndex(d, nlist, metric, 0)
+        fl.set_centroids(C)
+        fl.add(Xh, list_of_row=lor)
+        resident["ivf_flat_decoded"] = held(fl)
+        del Xh
+        sq = vdbhip.IVFSQ8Index(d, nlist, metric, 0, direct_kloop=True)
+        sq.set_centroids(C)
+        sq.train_ranges(X)
+        sq.add(X, list_of_row=lor)
+        resident["ivf_sq8_kloop"] = held(sq)
+
+        def leg(idx, nq, force):
+            idx.set_option("force_path", force)
+            idx.set_nprobe(nprobe)
+            for _ in range(args.warmup):
+                idx.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+            torch.cuda.synchronize()
+            idx.set_option("timing", 1)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                idx.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            st = idx.stats()
+            idx.set_option("timing", 0)
+            idx.set_option("force_path", 0)
+            return {"ms_per_search": round(el / args.steps * 1e3, 4), "prep_ms": round(st["last_prep_ms"], 4), "scan_ms": round(st["last_scan_ms"], 4),
+                    "tail_ms": round(st["last_tail_ms"], 4), "scan_dtype": st["scan_dtype"], "fallback_queries": st["last_fallback_queries"],
+                    "ids": I_t[:nq].cpu().numpy().copy()}
+
+        res = {"add_s": add_s}
+        for nq in (1, 64, args.nq):
+            legs = [leg(pq, nq, force) for force in (0, 1, 0, 1)]
+            flat = leg(fl, nq, 0)
+            same = all(np.array_equal(flat["ids"], x.pop("ids")) for x in legs + [flat])
+            sq8 = leg(sq, nq, 0)
+            sq8.pop("ids")
+            res[f"nq{nq}"] = {"kloop": legs[0::2], "exact": legs[1::2], "ivf_flat_decoded": flat, "ivf_sq8_kloop": sq8, "same_ids": same}
+            print(f"# {metric} IVF{nlist},PQ{M} {n}x{d} nq{nq}", json.dumps(res[f"nq{nq}"]), file=sys.stderr, flush=True)
+        res["bytes_resident_after_add"] = resident
+        out[f"{metric} IVF{nlist},PQ{M} {n}x{d} nprobe{nprobe}"] = res
+        for ix in (pq, fl, sq):
+            ix.close()
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kloop", action="store_true", help="only the D > 128 legs of option ivf_pq_kloop")
     ap.add_argument("--adc", action="store_true", help="only the ADC leg: option ivfpq_adc_max_batch 0 against 512 on small batches")
     ap.add_argument("--workload", nargs="+", choices=sorted(ADC_WORKLOADS), help="--adc: the workloads to run (default: all)")
     ap.add_argument("--niter", type=int, default=25, help="--adc: k-means iterations of centroids and codebooks")
@@ -161,6 +253,8 @@ def main() -> None:
     ap.add_argument("--nprobe", type=int, nargs="+", default=[8, 32, 128])
     ap.add_argument("--M", type=int, nargs="+", default=[64, 16])
     args = ap.parse_args()
+    if args.kloop:
+        return kloop_legs(args)
     if args.adc:
         if args.steps == 5 and args.warmup == 2:      # (the defaults of the throughput legs: the ADC leg takes medians of 20 after 3)
             args.steps, args.warmup = 20, 3

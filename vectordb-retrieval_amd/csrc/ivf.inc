@@ -37,10 +37,23 @@ inline void admit_ivfpq(const vdb_index_s *h, const char *what) {
 }
 
 // (re)build the flat index over the current centroids
+// IVF-PQ, option "ivf_pq_kloop": what the last add built for the K-loop scan of the codes (ivfpqk_build_space, ivf_pq.inc) goes with
+// the rows, the centroids or the codebooks it was derived from
+void ivfpqk_drop(vdb_index_s *h) {
+    if (!h->pqk_ok) return;
+    h->scan.bias.release();
+    h->scan.pqk_tab.release();
+    h->scan.pqk_dim.release();
+    h->pqk_ok = false;
+    h->tile16 = false;
+    h->ivf_mfma_ok = false;
+}
+
 void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
     h->ivf_centroids.assign(c_host, c_host + (size_t)nlist * h->dim);
     h->nlist = nlist;
     h->codes.ivfpq_n2.release();             // (IVF-PQ: the norms of the ADC scan belong to the old centroids)
+    ivfpqk_drop(h);                          // (... and so does the K-loop bookkeeping of the codes)
     if (!h->coarse) {
         h->coarse = new vdb_index_s();
         h->coarse->device = h->device;
@@ -352,6 +365,9 @@ constexpr ScanRow<Sq8dScanArgs> kRowsIvfSq8d[] = {VDB_KERNELS_IVF_SQ8D(VDB_ROW_I
 #define VDB_ROW_IVF_SQ8K(...) {ScanKey{{__VA_ARGS__}}, &ivf_sq8_kloop_scan_kernel<__VA_ARGS__>},
 constexpr ScanRow<Sq8kScanArgs> kRowsIvfSq8k[] = {VDB_KERNELS_IVF_SQ8K(VDB_ROW_IVF_SQ8K)};
 #undef VDB_ROW_IVF_SQ8K
+#define VDB_ROW_IVF_PQK(...) {ScanKey{{__VA_ARGS__}}, &ivf_pq_kloop_scan_kernel<__VA_ARGS__>},
+constexpr ScanRow<PqkScanArgs> kRowsIvfPqk[] = {VDB_KERNELS_IVF_PQK(VDB_ROW_IVF_PQK)};
+#undef VDB_ROW_IVF_PQK
 #undef VDB_ROW_IVF_SCAN
 #undef VDB_ROW_IVF_SCAN_I8
 #undef VDB_ROW_IVF_KLOOP
@@ -359,7 +375,7 @@ constexpr ScanRow<Sq8kScanArgs> kRowsIvfSq8k[] = {VDB_KERNELS_IVF_SQ8K(VDB_ROW_I
 
 // the one <<<>>> of the plan's family, with the arguments of that family
 void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st, const IvfKloopI8Args *k8 = nullptr,
-                const Sq8dScanArgs *d8 = nullptr, const Sq8kScanArgs *dk = nullptr) {
+                const Sq8dScanArgs *d8 = nullptr, const Sq8kScanArgs *dk = nullptr, const PqkScanArgs *pk = nullptr) {
     const dim3 grid(p.grid_x, p.grid_y), block(p.block);
     switch (p.family) {
         case ScanFamily::scan: scan_kernel_of(kRowsIvfScan, p)<<<grid, block, 0, st>>>(*sa); break;
@@ -368,6 +384,7 @@ void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, co
         case ScanFamily::ivf_kloop_i8: scan_kernel_of(kRowsIvfKloopI8, p)<<<grid, block, 0, st>>>(*k8); break;
         case ScanFamily::ivf_sq8d: scan_kernel_of(kRowsIvfSq8d, p)<<<grid, block, 0, st>>>(*d8); break;
         case ScanFamily::ivf_sq8k: scan_kernel_of(kRowsIvfSq8k, p)<<<grid, block, 0, st>>>(*dk); break;
+        case ScanFamily::ivf_pqk: scan_kernel_of(kRowsIvfPqk, p)<<<grid, block, 0, st>>>(*pk); break;
         default: throw Error(VDB_ERR_INVALID, "internal: no list scan kernel for an empty plan");
     }
     VDB_HIP(hipGetLastError());
@@ -390,6 +407,7 @@ struct IvfBatch {
     bool i8k;               // the int8 K-loop list scan is offered to this batch (ivf_i8k_plan.hpp, ivf_i8k_serves)
     bool sq8d;              // IVF-SQ8, option "ivf_sq8_direct": the direct scan of the codes serves this batch (ivf_sq8d_plan.hpp, ivf_sq8d_serves)
     bool sq8k;              // IVF-SQ8, D > 128, option "ivf_sq8_kloop": the K-loop scan of the codes serves this batch (ivf_sq8k_serves)
+    bool pqk;               // IVF-PQ, D > 128, option "ivf_pq_kloop": the K-loop scan of the product codes serves this batch (ivf_pqk_serves)
     bool filtered;          // a vdb_ivf_search_filtered call (ivf_filter.inc): the scans read the masked copies of the handle's filter,
                             // the exact stages test its list-order allow words
 };
@@ -411,7 +429,8 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     IvfLists L{};
     L.c = ivf_caps(b.shape, h->opt, b.g, b.k);
     ws.eps.reserve((size_t)nb * sizeof(float));
-    ws.qpanels.reserve((size_t)nb * h->ksteps * 16 * sizeof(_Float16));   // scaled fp16 query rows
+    // scaled fp16 query rows (the K-loop scan of product codes: operand rows in its padded space, ivf_pq_kloop_plan.hpp)
+    ws.qpanels.reserve((size_t)nb * (b.pqk ? 64 * ivf_pqk_nk(h->ivfpq.M, h->ivfpq.dsub) : h->ksteps * 16) * sizeof(_Float16));
     if (L.c.use_i8 || b.i8k) ws.qpanels8.reserve((size_t)nb * h->i8_ks * 32);      // int8 query rows (the K-loop copy: i8_ks * 32 = D padded to 64)
     ws.bin_m1.reserve(b.g.bin_bytes);
     ws.bin_m2.reserve(b.g.bin_bytes);
@@ -428,7 +447,7 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     L.d_slot_query = L.d_cursor + nlist;
     L.d_fb_done = L.d_slot_query + b.g.max_slots;
     ws.fb_list.reserve((size_t)nb * sizeof(int32_t));
-    if (b.sq8d || b.sq8k) {
+    if (b.sq8d || b.sq8k || b.pqk) {
         ws.sq8d_qterm.reserve((size_t)nb * sizeof(double));
         ws.sq8d_slot.reserve((size_t)b.g.max_slots * sizeof(float));
     }
@@ -469,6 +488,21 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
         da.xnorm_max = sqrtf(h->maxnorm2) * 1.0000002f; da.maxnorm2 = h->maxnorm2; da.consts_ok = h->sq8d.ok ? 1 : 0;
         const auto prep = b.sq8k ? ivf_sq8k_prep_kernel : ivf_sq8d_prep_kernel;
         prep<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
+        return;
+    }
+    if (b.pqk) {            // the K-loop scan of the product codes: likewise (ivf_pq_kloop.hpp)
+        PqkPrepArgs da{};
+        da.probes = L.probes; da.npairs = b.g.pairs; da.nlist = h->nlist; da.ppb = L.c.ppb; da.cnt = b.d_cnt;
+        da.Q = b.q; da.nq = nb; da.D = Dm; da.M = h->ivfpq.M; da.dsub = h->ivfpq.dsub; da.metric = h->metric;
+        da.Kpad = 64 * ivf_pqk_nk(da.M, da.dsub);
+        da.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
+        da.n_row_blocks = (unsigned)((nb * da.Kpad / 8 + 255) / 256);
+        da.dimc = h->scan.pqk_dim.as<float>();
+        da.wrows = reinterpret_cast<_Float16 *>(ws.qpanels.p); da.eps = ws.eps.as<float>(); da.qterm = ws.sq8d_qterm.as<double>();
+        da.info = L.info; da.src = from_coarse ? batch_info(h->coarse->ws) : nullptr;
+        da.ts = h->pqk.ts; da.can = h->pqk.can; da.camax = h->pqk.camax; da.rmax = h->pqk.rmax;
+        da.xnorm_max = sqrtf(h->maxnorm2) * 1.0000002f; da.maxnorm2 = h->maxnorm2; da.consts_ok = h->pqk.consts_ok ? 1 : 0;
+        ivf_pqk_prep_kernel<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
         return;
     }
     IvfPrepArgs pa{};
@@ -550,6 +584,24 @@ void ivf_scan_sq8k(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
     da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
     da.nk = h->ksteps / 4;
     ivf_launch(p, nullptr, nullptr, nullptr, b.st, nullptr, nullptr, &da);
+}
+
+// IVF-PQ, D > 128, option "ivf_pq_kloop": the slot terms bs (q . c_l) (the SQ8 routes' kernel with q . e = 0), then the K-loop scan of
+// the product codes (ivf_pq_kloop.hpp); sa.panels is null
+void ivf_scan_pqk(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    const int M = h->ivfpq.M, dsub = h->ivfpq.dsub;
+    const IvfLaunch p = plan_ivf_pqk(b.shape, h->opt, b.g, kgroup, M);
+    PqkScanArgs da{};
+    da.codes = h->codes.ivfpq_codes.as<unsigned char>(); da.table = h->scan.pqk_tab.as<_Float16>();
+    da.M = M; da.P8 = ivf_pqk_p(dsub) / 8; da.npieces = ivf_pqk_kp(M, dsub) / 8; da.nk = ivf_pqk_nk(M, dsub);
+    da.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); da.span_valid = h->lists.ivf_span_valid.as<int32_t>();
+    da.bias = sa.bias; da.wrows = sa.qrows; da.slot_term = ivf_sq8d_slot_terms(b, sa); da.info = sa.info;
+    da.bin_m[0] = sa.bin_m1; da.bin_m[1] = sa.bin_m2; da.bin_m[2] = sa.bin_m3;
+    da.bin_m[3] = h->ws.bin_m4.as<float>(); da.bin_m[4] = h->ws.bin_m5.as<float>();
+    da.item_list = sa.item_list; da.item_slot0 = sa.item_slot0; da.item_bin0 = sa.item_bin0; da.n_items = sa.n_items;
+    da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
+    ivf_launch(p, nullptr, nullptr, nullptr, b.st, nullptr, nullptr, nullptr, &da);
 }
 
 // SQ8, option "ivf_sq8_direct": the slot terms, then the scan of the codes themselves (ivf_sq8_scan.hpp)
@@ -712,7 +764,7 @@ void ivf_search_lists(const IvfBatch &b) {
     // IVF-I8 under "ivf_i8_scratch" = 0 holds no fp16 panels at all: the fp16 scan is not launched, and a batch the int8 scan
     // does not serve is flagged as a whole for the tail's exact list scan (ivf_i8_flag_kernel)
     const bool i8_no_slab = ivf_i8(h) && !h->opt.ivf_i8_scratch;
-    sa.panels = (i8_no_slab || b.sq8d || b.sq8k) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
+    sa.panels = (i8_no_slab || b.sq8d || b.sq8k || b.pqk) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
     sa.bias = b.filtered ? h->ivf_filter.bias_f.as<float>() : h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -726,6 +778,8 @@ void ivf_search_lists(const IvfBatch &b) {
     timing_mark(h, b.tslot, 0, b.st);
     if (b.sq8k) {
         ivf_scan_sq8k(b, L.c.kgroup, sa);
+    } else if (b.pqk) {
+        ivf_scan_pqk(b, L.c.kgroup, sa);
     } else if (b.g.kloop) {
         ivf_scan_kloop(b, L.c.kgroup, sa);
         if (b.i8k) ivf_scan_kloop_i8(b, L.c.kgroup, sa);
@@ -841,10 +895,12 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         b.filtered = filtered;
         const IvfAdcPlan adc = ivf_adc_plan(h->opt, h->ivf_codec, h->ivfpq.M, adc_ranges, h->N, adc_longest, b.nb, k, b.nprobe);
         if (!adc.ok) b.g = filtered ? ivf_filter_geometry(shape, h->opt, b.nb, k, b.nprobe, h->ivf_filter_count)
-                                    : ivf_geometry(shape, h->sq8k_ok ? ivf_sq8k_options(h->opt) : h->opt, b.nb, k, b.nprobe);
+                                    : ivf_geometry(shape, (h->sq8k_ok || h->pqk_ok) ? ivf_sq8k_options(h->opt) : h->opt, b.nb, k, b.nprobe);
         b.sq8d = ivf_sq8d_serves(h->opt.ivf_sq8_direct, h->ivf_codec, b.g.ok, b.g.kloop, D4, filtered);
         b.sq8k = ivf_sq8k_serves(h->opt.ivf_sq8_kloop, h->ivf_codec, h->sq8k_ok, b.g.ok && b.g.kloop, filtered);
         if (h->sq8k_ok && !b.sq8k) b.g = IvfGeom{};      // (no fp16 K-loop scan behind it: the exact list scan)
+        b.pqk = ivf_pqk_serves(h->opt.ivf_pq_kloop, h->ivf_codec, h->pqk_ok, b.g.ok && b.g.kloop, filtered);
+        if (h->pqk_ok && !b.pqk) b.g = IvfGeom{};        // (likewise)
         b.i8k = ivf_i8k_serves(h->ivf_i8k_ok && h->scan.panels8.p && h->scan.rows8.p, h->opt.panel_dtype, h->opt.ivf_tile, filtered, b.g.ok && b.g.kloop);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
@@ -874,6 +930,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         timing_mark(h, b.tslot, 2, st);
         any_mfma = any_mfma || b.g.ok;
         h->sq8d_last = b.sq8d || b.sq8k;
+        h->pqk_last = b.pqk;
     }
     } catch (...) {
         h->ev_used = ev_mark;

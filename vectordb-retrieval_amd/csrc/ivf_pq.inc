@@ -6,6 +6,8 @@
 // (refine.hpp, ivfpq_key); D <= 128 batches take the list-major MFMA scan on fp16 panels made from the codes per batch
 // (ivf_search_lists), D > 128 and small batches the exact list scan, and with option "ivfpq_adc_max_batch" small batches of any D the
 // lookup-table (ADC) scan of the probed lists (ivf_pq_adc.hpp, the end of this file) -- the result is the IVF-Flat result over x^ every way.
+// Option "ivf_pq_kloop": D > 128 keeps span tables, the panel-space bias and an fp16 table of the codebooks too, and batches of the
+// list-major path take the K-loop scan of the codes themselves (ivfpqk_build_space; ivf_pq_kloop.hpp).
 // The buffers shared with the SQ8 codec (the list of every row, the padded centroids, the per-batch panels) are the same
 // members: a handle has one codec for life.
 
@@ -27,7 +29,8 @@ void ivfpq_install_codebooks(vdb_index_s *h, int M, const float *cb_host) {
     VDB_HIP(hipDeviceSynchronize());
     pq_install_codebooks(h, h->ivfpq, h->kept.ivfpq_cb, M, cb_host);
     h->codes.ivfpq_n2.release();               // (the norms of the ADC scan: ivfpq_adc_prepare)
-    h->ivf_built = false;                      // (rows encoded under the old codebooks are dropped by the next add)
+    ivfpqk_drop(h);                            // (the table and accumulator inits of the K-loop scan: ivfpqk_build_space)
+    h->ivf_built = false;                     // (rows encoded under the old codebooks are dropped by the next add)
 }
 
 // the installed centroids, zero padded, on the device (before every add: vdb_ivf_set_centroids may have replaced them)
@@ -47,9 +50,131 @@ void ivfpq_decode_rows(vdb_index_s *h, int64_t n, int64_t pitch, float *out, hip
 
 // The panel space of an IVF-PQ index (D <= 128), as sq8_build_panel_space derives it: spans, bias (||x^||^2), scale and
 // fp16-exactness flag of an IVF-Flat index over the float32 rows x^, from a decoded copy that lives only for this call.
+// D > 128, option "ivf_pq_kloop": what the K-loop scan of the product codes (ivf_pq_kloop.hpp) needs, without panels and without a float32
+// corpus -- the span tables, the accumulator inits (||x^||^2 per list-padded row, kPadBias on padding rows: 4 bytes per padded row)
+// and maxnorm2 exactly as sq8k_build_space derives them (rows decoded in blocks into a scratch buffer, norms by corpus_stats_kernel),
+// then on the host, in float64, from the codebooks and centroids: the power-of-two scale ts of the table (max |ts cb| in [128, 256)),
+// the fp16 table T[m][256][P] = fp16(ts cb), zero in the padding of every sub-space, and per dimension what the bound reads --
+// max |T| / ts, max |T / ts - cb| (what the table really lost) and max_l |c_l| + max |cb| (the one float32 add of the decode) --
+// rounded up to float32.
+constexpr size_t kPqkNormBlockBytes = (size_t)128 << 20;
+inline float pqk_round_up(double v) {
+    const float f = (float)v;
+    return (double)f < v ? std::nextafterf(f, INFINITY) : f;
+}
+void ivfpqk_build_space(vdb_index_s *h) {
+    hipStream_t st = nullptr;
+    const int64_t N = h->N;
+    const int Dm = h->dim, D4 = h->D4, M = h->ivfpq.M, dsub = h->ivfpq.dsub, P = ivf_pqk_p(dsub);
+    h->ivf_tps = ivf_tps_of(h->opt, N, h->nlist);
+    const int span_rows = h->ivf_tps * 16;
+    const int64_t nspans = ivf_build_spans(h, span_rows);
+    if (nspans == 0) return;
+    DevBuf block;
+    const int64_t block_rows = std::max<int64_t>(1024, (int64_t)(kPqkNormBlockBytes / ((size_t)D4 * sizeof(float))));
+    block.reserve((size_t)std::min(N, block_rows) * D4 * sizeof(float));
+    h->rows.xnorm2.reserve((size_t)N * sizeof(float));
+    h->kept.stats.reserve(sizeof(IndexStats));
+    try {
+        VDB_HIP(hipMemsetAsync(h->kept.stats.p, 0, sizeof(IndexStats), st));
+        const IvfPqRows all = ivfpq_rows(h);
+        for (int64_t r0 = 0; r0 < N; r0 += block_rows) {
+            const int64_t nb = std::min(block_rows, N - r0);
+            IvfPqRows part = all;
+            part.pq.codes += (size_t)r0 * M;
+            part.list += r0;
+            pq_decode_rows_kernel<true><<<dim3((unsigned)std::min<int64_t>((nb * D4 + 255) / 256, 1 << 16)), dim3(256), 0, st>>>(
+                part, nb, Dm, D4, D4, block.as<float>());
+            corpus_stats_kernel<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st>>>(block.as<float>(), nb, D4, h->rows.xnorm2.as<float>() + r0,
+                                                                                         h->kept.stats.as<IndexStats>());
+            VDB_HIP(hipGetLastError());
+        }
+        IndexStats hs;
+        VDB_HIP(hipMemcpyAsync(&hs, h->kept.stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+        VDB_HIP(hipStreamSynchronize(st));
+        memcpy(&h->absmax, &hs.absmax_bits, 4);
+        memcpy(&h->maxnorm2, &hs.maxnorm2_bits, 4);
+        h->nonfinite = hs.nonfinite != 0;
+        if (!h->nonfinite) {
+            h->scan.bias.reserve((size_t)nspans * span_rows * sizeof(float));
+            ivf_build_bias_kernel<<<dim3((unsigned)((nspans * span_rows + 255) / 256)), dim3(256), 0, st>>>(
+                h->rows.xnorm2.as<float>(), nspans, span_rows, h->metric, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
+                h->scan.bias.as<float>());
+            VDB_HIP(hipGetLastError());
+            // the table and the constants of the bound
+            const std::vector<float> &cb = h->ivfpq.host;
+            std::vector<double> cmax((size_t)Dm, 0.0);
+            double rmax = 0.0, camax = 0.0, can2 = 0.0;
+            bool finite = true;
+            for (float v : cb) {
+                finite = finite && std::isfinite(v);
+                rmax = std::max(rmax, std::fabs((double)v));
+            }
+            for (int l = 0; l < h->nlist; ++l) {
+                double s = 0.0;
+                for (int d = 0; d < Dm; ++d) {
+                    const double c = (double)h->ivf_centroids[(size_t)l * Dm + d];
+                    finite = finite && std::isfinite(c);
+                    cmax[(size_t)d] = std::max(cmax[(size_t)d], std::fabs(c));
+                    s += c * c;
+                }
+                can2 = std::max(can2, s);
+            }
+            for (double c : cmax) camax = std::max(camax, c);
+            double ts = 1.0;
+            if (finite && rmax > 0.0) {
+                int e;
+                std::frexp(rmax, &e);                      // rmax = f 2^e, f in [0.5, 1)
+                ts = std::ldexp(1.0, 8 - e);               // rmax ts in [128, 256)
+            }
+            std::vector<_Float16> tab((size_t)M * 256 * P, (_Float16)0.f);
+            std::vector<float> dimc((size_t)3 * Dm, 0.f);
+            if (finite)
+                for (int m = 0; m < M; ++m)
+                    for (int c = 0; c < 256; ++c)
+                        for (int j = 0; j < dsub; ++j) {
+                            const int d = m * dsub + j;
+                            const double v = (double)cb[((size_t)m * 256 + c) * dsub + j];
+                            const _Float16 t = (_Float16)(float)(v * ts);
+                            tab[((size_t)m * 256 + c) * P + j] = t;
+                            if (d >= Dm) continue;
+                            const double back = (double)(float)t / ts;
+                            dimc[(size_t)d] = std::max(dimc[(size_t)d], pqk_round_up(std::fabs(back)));
+                            dimc[(size_t)Dm + d] = std::max(dimc[(size_t)Dm + d], pqk_round_up(std::fabs(back - v)));
+                            dimc[(size_t)2 * Dm + d] = std::max(dimc[(size_t)2 * Dm + d], pqk_round_up(cmax[(size_t)d] + std::fabs(v)));
+                        }
+            h->scan.pqk_tab.reserve_exact(tab.size() * sizeof(_Float16));
+            h->scan.pqk_dim.reserve_exact(dimc.size() * sizeof(float));
+            VDB_HIP(hipMemcpyAsync(h->scan.pqk_tab.p, tab.data(), tab.size() * sizeof(_Float16), hipMemcpyHostToDevice, st));
+            VDB_HIP(hipMemcpyAsync(h->scan.pqk_dim.p, dimc.data(), dimc.size() * sizeof(float), hipMemcpyHostToDevice, st));
+            VDB_HIP(hipStreamSynchronize(st));
+            h->pqk.ts = ts;
+            h->pqk.can = std::sqrt(can2) * (1.0 + 1.0e-12);
+            h->pqk.camax = pqk_round_up(camax);
+            h->pqk.rmax = pqk_round_up(rmax);
+            h->pqk.consts_ok = finite && ts > 1.0e-30 && ts < 1.0e30 && camax < 1.0e30 && rmax < 1.0e30;
+        }
+    } catch (...) {
+        h->rows.xnorm2.release();
+        h->scan.bias.release();
+        h->scan.pqk_tab.release();
+        h->scan.pqk_dim.release();
+        throw;
+    }
+    h->rows.xnorm2.release();                                  // (the norms only fed the bias)
+    h->pqk_ok = !h->nonfinite;
+    h->tile16 = h->pqk_ok;                                     // (the plan's K-loop geometry: ivf_shape_of)
+    h->ivf_mfma_ok = h->pqk_ok;
+}
+
 void ivfpq_build_panel_space(vdb_index_s *h) {
     h->ivf_mfma_ok = false;
-    if (h->N == 0 || h->ksteps > kMaxKSteps) return;      // D > 128: the exact list scan serves every batch
+    ivfpqk_drop(h);           // (the bookkeeping of the last add goes with its lists; the rule below decides anew)
+    if (h->N == 0) return;
+    if (h->ksteps > kMaxKSteps) {     // D > 128: the exact list scan serves every batch, unless option "ivf_pq_kloop" is set
+        if (ivf_pqk_builds(h->opt.ivf_pq_kloop, h->ivf_codec, h->ksteps, h->dim, h->ivfpq.M, h->ivfpq.dsub)) ivfpqk_build_space(h);
+        return;
+    }
     h->rows.x32.reserve_exact((size_t)h->N * h->D4 * sizeof(float));
     try {
         ivfpq_decode_rows(h, h->N, h->D4, h->rows.x32.as<float>(), nullptr);

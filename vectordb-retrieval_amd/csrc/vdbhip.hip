@@ -35,6 +35,7 @@
 #include "ivf_i8_plan.hpp"
 #include "ivf_i8.hpp"
 #include "ivf_pq.hpp"
+#include "ivf_pq_kloop.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
 #include "lsh_tables.hpp"
@@ -191,6 +192,8 @@ struct ScanBufs {
     DevBuf panels{"panels"}, slab{"slab"}, bias{"bias"};
     DevBuf panels8{"panels8"}, bias8{"bias8"}, rows8{"rows8"}, rowstat8{"rowstat8"};  // rows8 / rowstat8: row-major int8 copy + {sum x^2, sum x} for the list refine
     DevBuf pq_tab{"pq_tab"};                                 // PQ: the codebooks scaled by sx and rounded to fp16, [M][256][dsub] (pq.hpp)
+    DevBuf pqk_tab{"pqk_tab"}, pqk_dim{"pqk_dim"};           // IVF-PQ, option "ivf_pq_kloop": the codebooks of the residuals scaled and rounded to fp16, zero padded
+                                                             // [M][256][P], and the per-dimension constants of its bound, float32 [3][D] (ivf_pq_kloop.hpp)
 };
 // what outlives the rows: the corpus statistics block, and what vdb_ivf_train / set_* installed   (freed with the handle)
 struct KeptBufs {
@@ -401,6 +404,11 @@ struct vdb_index_s {
     // ||cb[m][c]||^2), and whether both lie in the range the scan's scale can serve
     double ivfpq_adc_xn2 = 0.0, ivfpq_adc_cr = 0.0;
     bool ivfpq_adc_ok = false;
+    // option "ivf_pq_kloop" (ivf_pq_kloop.hpp): the last add built the K-loop bookkeeping of the product codes (ivfpqk_build_space,
+    // ivf_pq.inc) -- with the scale of the fp16 table and what the scale windows and the bound read of centroids and codebooks --
+    // and whether that scan served the last batch
+    struct PqKloop { double ts = 1.0, can = 0.0; float camax = 0.f, rmax = 0.f; bool consts_ok = false; } pqk;
+    bool pqk_ok = false, pqk_last = false;
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
@@ -507,6 +515,7 @@ constexpr OptionRow kOptions[] = {
     {"ivf_i8_kloop", &Options::ivf_i8_kloop, 2, {0, 1}, kNoRows, 0, nullptr, &vdb_index_s::ivf_i8k_ok},   // IVF-Flat, D > 128, next add: 1 = a byte-valued corpus also gets the int8 copy of the panel space for the int8 K-loop list scan
     {"ivf_sq8_direct", &Options::ivf_sq8_direct, 2, {0, 1}},        // IVF-SQ8, D <= 128, next search: 1 = the list scan reads the 8-bit codes directly (no per-batch fp16 panels); no effect elsewhere
     {"ivf_sq8_kloop", &Options::ivf_sq8_kloop, 2, {0, 1}},          // IVF-SQ8, D > 128, next add: 1 = span tables and accumulator inits for the K-loop list scan of the 8-bit codes; no effect elsewhere
+    {"ivf_pq_kloop", &Options::ivf_pq_kloop, 2, {0, 1}},            // IVF-PQ, D > 128, next add: 1 = span tables, accumulator inits and the fp16 table for the K-loop list scan of the product codes; no effect elsewhere
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -1498,7 +1507,8 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         }
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && !(h->ivf_codec == 3 && s.scan_dtype == 1)) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes, or from the int8 panels of IVF-I8 (whose integer batches take the int8 scan: 1)
         if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct"; D > 128: "ivf_sq8_kloop")
-        if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                          // ... of a PQ index
+        if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqk_last) s.scan_dtype = 5;     // fp16 MFMA on fragments gathered by the product codes (option "ivf_pq_kloop")
+        if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                         // ... of a PQ index
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
