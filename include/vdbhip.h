@@ -87,7 +87,9 @@ typedef struct vdb_stats_s {
                                   last_path stays VDB_PATH_IVF, last_path_name "ivf"); more than 128 dimensions: the K-loop form of that
                                   scan, option "ivf_sq8_kloop",
                                   5 = fp16 MFMA on fragments of an fp16 codebook table gathered by the product codes of an IVF-PQ index of
-                                  more than 128 dimensions, option "ivf_pq_kloop" (f32 accumulate; last_path stays VDB_PATH_IVF) */
+                                  more than 128 dimensions, option "ivf_pq_kloop" (f32 accumulate; last_path stays VDB_PATH_IVF),
+                                  6 = fp16 MFMA on fragments decoded in LDS from the product codes of an IVF-PQ index of at most 128
+                                  dimensions, option "ivf_pq_direct" (f32 accumulate; last_path stays VDB_PATH_IVF) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -528,6 +530,9 @@ int vdb_ivf_i8_get_rows(vdb_handle h, int8_t *rows_host, int *cx);
  * dim <= 128: batches the list-major path serves make the fp16 panels of the whole panel space from the codes per batch, as
  * (half)((c_l[d] + codebook entry) * sx) -- IVF-Flat's panels of x^, so the same error bound holds (vdb_stats.scan_dtype = 2) --
  * and run the MFMA list scan on them; dim > 128, small batches and "force_path" 1 / 3 take the exact list scan over the codes.
+ * dim <= 128 with option "ivf_pq_direct" = 1: those batches are scanned straight from the product codes instead -- a workgroup keeps
+ * the fp16 table of the codebooks (512 dim bytes) in LDS and decodes the A fragments of its rows there; no fp16 panels are made
+ * (vdb_stats.scan_dtype = 6; DESIGN 4.4 "IVF-PQ direct scan").
  * dim > 128 with option "ivf_pq_kloop" = 1 at the add: batches the list-major path serves are scanned on the matrix cores straight
  * from the product codes -- the A fragments are 16-byte pieces of an fp16 table of the codebooks, gathered by the code bytes; no
  * float32 rows and no fp16 panels become resident (vdb_stats.scan_dtype = 5; DESIGN 4.4 "IVF-PQ K-loop scan").
@@ -797,6 +802,17 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       k > 256, too few bins) are answered by the exact list scan.  The square workgroup tile is not built for this
  *                       route: such a handle plans as if "ivf_tile" were 0.  Independent of "ivf_sq8_direct".  No effect on the other
  *                       codecs, on a flat index or on D <= 128; a multi-device index refuses a non-zero value
+ *     "ivf_pq_direct"   IVF-PQ index (codec 2), D <= 128, takes effect at the next search (no re-add): 0 (default): a batch of the
+ *                       list-major path decodes the whole panel space into fp16 panels and scans them | 1: an unfiltered batch of
+ *                       that path is scanned by a kernel that holds the fp16 table of the scaled codebooks (M x 256 x dsub x 2 =
+ *                       512 D bytes, at most 64 KiB) in LDS, stages the code bytes of its rows there and decodes them into the MFMA
+ *                       operand layout -- no per-batch panels, so a handle searched only this way never allocates the panel slab
+ *                       (vdb_stats.scan_dtype = 6), under an error bound of its own.  The table and 12 bytes per dimension become
+ *                       resident at the first such batch (or at an add while the option is on) and are dropped by new centroids or
+ *                       codebooks.  Same results, bit for bit; a batch outside the scale windows of the route (non-finite queries,
+ *                       extreme codebooks) is answered by the exact list scan, batches "ivfpq_adc_max_batch" admits by the
+ *                       lookup-table scan, "force_path" keeps its meaning.  No effect on the other codecs, on a flat index or on
+ *                       D > 128; a multi-device index refuses a non-zero value
  *     "ivf_pq_kloop"    IVF-PQ index (codec 2), D > 128 (up to 4096; M <= 256 and M x 8 ceil(dsub / 8) <= 4096), takes effect at the next
  *                       vdb_ivf_add / vdb_ivf_add_assigned / vdb_ivfpq_add_codes: 0 (default): every batch takes the exact list scan |
  *                       1: the add also builds the span tables of the lists ("ivf_tps" keeps its meaning), the accumulator inits

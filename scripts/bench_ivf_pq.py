@@ -20,6 +20,8 @@ the exact float64 result, and (bytes_resident - bytes_workspace) / (4 N D).  Pri
             the largest nq up to which every batch size is faster with the option by more than 8 % (the box-to-box spread).
 
     --kloop the D > 128 legs of option "ivf_pq_kloop" (kloop_legs below; profiles/r32_bench_ivf_pq_kloop.json).
+
+    --direct the D <= 128 legs of option "ivf_pq_direct" (direct_legs below; profiles/r33_bench_ivf_pq_direct.json).
 """
 from __future__ import annotations
 
@@ -239,13 +241,104 @@ def kloop_legs(args) -> None:
     print(json.dumps(out))
 
 
+def direct_legs(args) -> None:
+    """`--direct`: option "ivf_pq_direct" at D <= 128 (profiles/r33_bench_ivf_pq_direct.json).  Gaussian `--n` x 128, IVF1024 with the
+    library's k-means, PQ64 and PQ16 trained on the residuals, nprobe 8 / 32 / 128 at 1 / 64 / `--nq` queries, k = 10, l2.  Per leg,
+    alternating twice on ONE handle: option 0 (fp16 panels decoded per batch: the parent's code path, the yardstick) and option 1; the
+    margin is the spread of the two option-0 repeats.  In the same run IVF-Flat and IVF-SQ8 with "ivf_sq8_direct" on the same centroids,
+    the lookup-table (ADC) route at one query, and the workspace of a fresh handle searched only with the option on.  ONE JSON line."""
+    import torch
+
+    import vdbhip
+
+    dev = torch.device("cuda:0")
+    d, k, nlist = 128, 10, 1024
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    X = torch.randn((args.n, d), generator=g, device=dev, dtype=torch.float32).cpu().numpy()
+    Q_t = torch.randn((args.nq, d), generator=g, device=dev, dtype=torch.float32)
+    D_t = torch.empty((args.nq, k), dtype=torch.float32, device=dev)
+    I_t = torch.empty((args.nq, k), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    fl = vdbhip.IVFFlatIndex(d, nlist, "l2", 0)
+    fl.train(X, niter=25, seed=1234, max_points_per_centroid=256)
+    fl.add(X)
+    sq = vdbhip.IVFSQ8Index(d, nlist, "l2", 0, direct_codes=True)
+    sq.set_centroids(fl.centroids())
+    sq.train_ranges(X)
+    sq.add(X)
+
+    def leg(idx, nq, nprobe, option=None, value=0):
+        if option:
+            idx.set_option(option, value)
+        idx.set_nprobe(nprobe)
+        for _ in range(args.warmup):
+            idx.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+        torch.cuda.synchronize()
+        idx.set_option("timing", 1)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            idx.search_device(Q_t.data_ptr(), nq, k, D_t.data_ptr(), I_t.data_ptr(), stream)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        st = idx.stats()
+        idx.set_option("timing", 0)
+        return {"ms_per_search": round(el / args.steps * 1e3, 4), "qps": round(nq * args.steps / el, 1), "prep_ms": round(st["last_prep_ms"], 4),
+                "scan_ms": round(st["last_scan_ms"], 4), "tail_ms": round(st["last_tail_ms"], 4), "path": st["last_path_name"],
+                "scan_dtype": st["scan_dtype"], "fallback_queries": st["last_fallback_queries"], "bytes_workspace": st["bytes_workspace"],
+                "ids": hashlib.sha256(I_t[:nq].cpu().numpy().tobytes()).hexdigest()[:16]}
+
+    out = {"config": f"Gaussian {args.n} x {d}, k={k}, l2, IVF{nlist} (own k-means, shared centroids), steps {args.steps}, warmup {args.warmup}"}
+    yard = {}
+    for p in args.nprobe:
+        for nq in (1, 64, args.nq):
+            yard[f"nprobe{p} nq{nq}"] = {"ivf_flat": leg(fl, nq, p), "ivf_sq8_direct": leg(sq, nq, p)}
+    out["yardsticks"] = yard
+    fl_centroids = fl.centroids()
+    fl.close()
+    sq.close()
+    for M in args.M:
+        pq = vdbhip.IVFPQIndex(d, nlist, M, "l2", 0)
+        pq.set_centroids(fl_centroids)
+        pq.train_codebooks(X, niter=25, seed=1234, max_points_per_centroid=256)
+        pq.add(X)
+        res = {}
+        for p in args.nprobe:
+            for nq in (1, 64, args.nq):
+                legs = [leg(pq, nq, p, "ivf_pq_direct", v) for v in (0, 1, 0, 1)]
+                off, on = legs[0::2], legs[1::2]
+                cell = {"option0": off, "option1": on, "same_ids": len({x["ids"] for x in legs}) == 1,
+                        "option0_spread": round(abs(off[0]["ms_per_search"] - off[1]["ms_per_search"]) / min(x["ms_per_search"] for x in off), 4),
+                        "option1_over_option0_time": round(min(x["ms_per_search"] for x in on) / min(x["ms_per_search"] for x in off), 4)}
+                if nq == 1:
+                    pq.set_option("ivf_pq_direct", 0)
+                    cell["adc_route"] = leg(pq, nq, p, "ivfpq_adc_max_batch", 512)
+                    pq.set_option("ivfpq_adc_max_batch", 0)
+                assert cell["same_ids"], cell
+                res[f"nprobe{p} nq{nq}"] = cell
+                print(f"# PQ{M} nprobe{p} nq{nq}", json.dumps(cell), file=sys.stderr, flush=True)
+        fresh = vdbhip.IVFPQIndex(d, nlist, M, "l2", 0, direct_codes=True)
+        fresh.set_centroids(fl_centroids)
+        fresh.set_codebooks(pq.codebooks())
+        fresh.add_codes(pq.codes(), pq.assignment())
+        res["workspace_bytes"] = {"fresh_handle_option1_only": leg(fresh, args.nq, 32)["bytes_workspace"],
+                                  "handle_searched_with_option0": pq.stats()["bytes_workspace"]}
+        fresh.close()
+        pq.close()
+        out[f"IVF{nlist},PQ{M}"] = res
+    text = json.dumps(out)
+    Path(args.out or str(ROOT / "profiles" / "r33_bench_ivf_pq_direct.json")).write_text(text + "\n")
+    print(text)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--direct", action="store_true", help="only the D <= 128 legs of option ivf_pq_direct")
     ap.add_argument("--kloop", action="store_true", help="only the D > 128 legs of option ivf_pq_kloop")
     ap.add_argument("--adc", action="store_true", help="only the ADC leg: option ivfpq_adc_max_batch 0 against 512 on small batches")
     ap.add_argument("--workload", nargs="+", choices=sorted(ADC_WORKLOADS), help="--adc: the workloads to run (default: all)")
     ap.add_argument("--niter", type=int, default=25, help="--adc: k-means iterations of centroids and codebooks")
-    ap.add_argument("--out", default=None, help="--adc: the JSON file to write (default profiles/r19_bench_ivfpq_adc.json)")
+    ap.add_argument("--out", default=None, help="--adc / --direct: the JSON file to write (default profiles/r19_bench_ivfpq_adc.json / r33_bench_ivf_pq_direct.json)")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=10_000)
     ap.add_argument("--steps", type=int, default=5)
@@ -255,6 +348,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.kloop:
         return kloop_legs(args)
+    if args.direct:
+        return direct_legs(args)
     if args.adc:
         if args.steps == 5 and args.warmup == 2:      # (the defaults of the throughput legs: the ADC leg takes medians of 20 after 3)
             args.steps, args.warmup = 20, 3

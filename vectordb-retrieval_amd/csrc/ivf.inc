@@ -49,11 +49,20 @@ void ivfpqk_drop(vdb_index_s *h) {
     h->ivf_mfma_ok = false;
 }
 
+// IVF-PQ, option "ivf_pq_direct": the unpadded fp16 table and the constants of the bound (ivfpqd_prepare, ivf_pq.inc; held = valid) go
+// with the centroids or the codebooks they were derived from -- not with the rows: nothing of them depends on the lists
+// (the buffers and h->pqk are the K-loop route's at D > 128, where ivfpqk_drop has released them already: a handle has one of the two)
+void ivfpqd_drop(vdb_index_s *h) {
+    h->scan.pqk_tab.release();
+    h->scan.pqk_dim.release();
+}
+
 void ivf_install_centroids(vdb_index_s *h, const float *c_host, int nlist) {
     h->ivf_centroids.assign(c_host, c_host + (size_t)nlist * h->dim);
     h->nlist = nlist;
     h->codes.ivfpq_n2.release();             // (IVF-PQ: the norms of the ADC scan belong to the old centroids)
     ivfpqk_drop(h);                          // (... and so does the K-loop bookkeeping of the codes)
+    ivfpqd_drop(h);                          // (... and the table of the direct scan)
     if (!h->coarse) {
         h->coarse = new vdb_index_s();
         h->coarse->device = h->device;
@@ -368,6 +377,9 @@ constexpr ScanRow<Sq8kScanArgs> kRowsIvfSq8k[] = {VDB_KERNELS_IVF_SQ8K(VDB_ROW_I
 #define VDB_ROW_IVF_PQK(...) {ScanKey{{__VA_ARGS__}}, &ivf_pq_kloop_scan_kernel<__VA_ARGS__>},
 constexpr ScanRow<PqkScanArgs> kRowsIvfPqk[] = {VDB_KERNELS_IVF_PQK(VDB_ROW_IVF_PQK)};
 #undef VDB_ROW_IVF_PQK
+#define VDB_ROW_IVF_PQD(...) {ScanKey{{__VA_ARGS__}}, &ivf_pq_scan_kernel<__VA_ARGS__>},
+constexpr ScanRow<PqdScanArgs> kRowsIvfPqd[] = {VDB_KERNELS_IVF_PQD(VDB_ROW_IVF_PQD)};
+#undef VDB_ROW_IVF_PQD
 #undef VDB_ROW_IVF_SCAN
 #undef VDB_ROW_IVF_SCAN_I8
 #undef VDB_ROW_IVF_KLOOP
@@ -375,7 +387,8 @@ constexpr ScanRow<PqkScanArgs> kRowsIvfPqk[] = {VDB_KERNELS_IVF_PQK(VDB_ROW_IVF_
 
 // the one <<<>>> of the plan's family, with the arguments of that family
 void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, const IvfKloopArgs *ka, hipStream_t st, const IvfKloopI8Args *k8 = nullptr,
-                const Sq8dScanArgs *d8 = nullptr, const Sq8kScanArgs *dk = nullptr, const PqkScanArgs *pk = nullptr) {
+                const Sq8dScanArgs *d8 = nullptr, const Sq8kScanArgs *dk = nullptr, const PqkScanArgs *pk = nullptr, const PqdScanArgs *pd = nullptr,
+                size_t pd_lds = 0) {
     const dim3 grid(p.grid_x, p.grid_y), block(p.block);
     switch (p.family) {
         case ScanFamily::scan: scan_kernel_of(kRowsIvfScan, p)<<<grid, block, 0, st>>>(*sa); break;
@@ -385,6 +398,13 @@ void ivf_launch(const IvfLaunch &p, const ScanArgs *sa, const ScanI8Args *s8, co
         case ScanFamily::ivf_sq8d: scan_kernel_of(kRowsIvfSq8d, p)<<<grid, block, 0, st>>>(*d8); break;
         case ScanFamily::ivf_sq8k: scan_kernel_of(kRowsIvfSq8k, p)<<<grid, block, 0, st>>>(*dk); break;
         case ScanFamily::ivf_pqk: scan_kernel_of(kRowsIvfPqk, p)<<<grid, block, 0, st>>>(*pk); break;
+        case ScanFamily::ivf_pqd: {
+            const auto kernel = scan_kernel_of(kRowsIvfPqd, p);
+            if (pd_lds > 65536)       // (more than the default 64 KiB of dynamic LDS: opt in, on the current device, every time)
+                VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPqdLdsBudget));
+            kernel<<<grid, block, pd_lds, st>>>(*pd);
+            break;
+        }
         default: throw Error(VDB_ERR_INVALID, "internal: no list scan kernel for an empty plan");
     }
     VDB_HIP(hipGetLastError());
@@ -408,6 +428,7 @@ struct IvfBatch {
     bool sq8d;              // IVF-SQ8, option "ivf_sq8_direct": the direct scan of the codes serves this batch (ivf_sq8d_plan.hpp, ivf_sq8d_serves)
     bool sq8k;              // IVF-SQ8, D > 128, option "ivf_sq8_kloop": the K-loop scan of the codes serves this batch (ivf_sq8k_serves)
     bool pqk;               // IVF-PQ, D > 128, option "ivf_pq_kloop": the K-loop scan of the product codes serves this batch (ivf_pqk_serves)
+    bool pqd;               // IVF-PQ, D <= 128, option "ivf_pq_direct": the direct scan of the product codes serves this batch (ivf_pqd_serves)
     bool filtered;          // a vdb_ivf_search_filtered call (ivf_filter.inc): the scans read the masked copies of the handle's filter,
                             // the exact stages test its list-order allow words
 };
@@ -447,7 +468,7 @@ IvfLists ivf_lists_reserve(const IvfBatch &b) {
     L.d_slot_query = L.d_cursor + nlist;
     L.d_fb_done = L.d_slot_query + b.g.max_slots;
     ws.fb_list.reserve((size_t)nb * sizeof(int32_t));
-    if (b.sq8d || b.sq8k || b.pqk) {
+    if (b.sq8d || b.sq8k || b.pqk || b.pqd) {
         ws.sq8d_qterm.reserve((size_t)nb * sizeof(double));
         ws.sq8d_slot.reserve((size_t)b.g.max_slots * sizeof(float));
     }
@@ -490,11 +511,11 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
         prep<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
         return;
     }
-    if (b.pqk) {            // the K-loop scan of the product codes: likewise (ivf_pq_kloop.hpp)
+    if (b.pqk || b.pqd) {   // the scans of the product codes: likewise (ivf_pq_kloop.hpp; D <= 128: operand rows in dimension order, ivf_pq_scan.hpp)
         PqkPrepArgs da{};
         da.probes = L.probes; da.npairs = b.g.pairs; da.nlist = h->nlist; da.ppb = L.c.ppb; da.cnt = b.d_cnt;
         da.Q = b.q; da.nq = nb; da.D = Dm; da.M = h->ivfpq.M; da.dsub = h->ivfpq.dsub; da.metric = h->metric;
-        da.Kpad = 64 * ivf_pqk_nk(da.M, da.dsub);
+        da.Kpad = b.pqd ? h->ksteps * 16 : 64 * ivf_pqk_nk(da.M, da.dsub);
         da.n_eps_blocks = (unsigned)((nb * 16 + 255) / 256);
         da.n_row_blocks = (unsigned)((nb * da.Kpad / 8 + 255) / 256);
         da.dimc = h->scan.pqk_dim.as<float>();
@@ -502,7 +523,8 @@ void ivf_lists_prep(const IvfBatch &b, const IvfLists &L) {
         da.info = L.info; da.src = from_coarse ? batch_info(h->coarse->ws) : nullptr;
         da.ts = h->pqk.ts; da.can = h->pqk.can; da.camax = h->pqk.camax; da.rmax = h->pqk.rmax;
         da.xnorm_max = sqrtf(h->maxnorm2) * 1.0000002f; da.maxnorm2 = h->maxnorm2; da.consts_ok = h->pqk.consts_ok ? 1 : 0;
-        ivf_pqk_prep_kernel<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
+        const auto prep = b.pqd ? ivf_pqd_prep_kernel : ivf_pqk_prep_kernel;
+        prep<<<dim3(da.n_eps_blocks + da.n_row_blocks + L.c.pblocks), dim3(256), L.c.hist_bytes, b.st>>>(da);
         return;
     }
     IvfPrepArgs pa{};
@@ -602,6 +624,22 @@ void ivf_scan_pqk(const IvfBatch &b, int kgroup, const ScanArgs &sa) {
     da.item_list = sa.item_list; da.item_slot0 = sa.item_slot0; da.item_bin0 = sa.item_bin0; da.n_items = sa.n_items;
     da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
     ivf_launch(p, nullptr, nullptr, nullptr, b.st, nullptr, nullptr, nullptr, &da);
+}
+
+// IVF-PQ, D <= 128, option "ivf_pq_direct": the slot terms bs (q . c_l), then the scan of the product codes (ivf_pq_scan.hpp)
+void ivf_scan_pqd(const IvfBatch &b, const ScanArgs &sa) {
+    vdb_index_s *h = b.h;
+    const float *slot_term = ivf_sq8d_slot_terms(b, sa);
+    const IvfLaunch p = plan_ivf_pqd(b.shape, h->opt, b.g);
+    PqdScanArgs da{};
+    da.codes = h->codes.ivfpq_codes.as<unsigned char>(); da.table = h->scan.pqk_tab.as<_Float16>();
+    da.D = h->dim; da.M = h->ivfpq.M; da.dsub = h->ivfpq.dsub;
+    da.span_row0 = h->lists.ivf_span_row0.as<int32_t>(); da.span_valid = h->lists.ivf_span_valid.as<int32_t>();
+    da.bias = sa.bias; da.wrows = sa.qrows; da.slot_term = slot_term; da.info = sa.info;
+    da.bin_m1 = sa.bin_m1; da.bin_m2 = sa.bin_m2; da.bin_m3 = sa.bin_m3;
+    da.item_list = sa.item_list; da.item_slot0 = sa.item_slot0; da.item_bin0 = sa.item_bin0; da.n_items = sa.n_items;
+    da.list_pspan0 = sa.list_pspan0; da.slot_query = sa.slot_query; da.part_spans = p.part_spans;
+    ivf_launch(p, nullptr, nullptr, nullptr, b.st, nullptr, nullptr, nullptr, nullptr, &da, ivf_pqd_lds_bytes(da.D, da.M, p.key.t[0]));
 }
 
 // SQ8, option "ivf_sq8_direct": the slot terms, then the scan of the codes themselves (ivf_sq8_scan.hpp)
@@ -764,7 +802,7 @@ void ivf_search_lists(const IvfBatch &b) {
     // IVF-I8 under "ivf_i8_scratch" = 0 holds no fp16 panels at all: the fp16 scan is not launched, and a batch the int8 scan
     // does not serve is flagged as a whole for the tail's exact list scan (ivf_i8_flag_kernel)
     const bool i8_no_slab = ivf_i8(h) && !h->opt.ivf_i8_scratch;
-    sa.panels = (i8_no_slab || b.sq8d || b.sq8k || b.pqk) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
+    sa.panels = (i8_no_slab || b.sq8d || b.sq8k || b.pqk || b.pqd) ? nullptr : ivf_i8(h) ? ivf_i8_panels(h, L.info, b.st) : sq8(h) ? ivf_sq8_panels(b) : ivfpq(h) ? ivf_pq_panels(h, b.st) : h->scan.panels.as<half8>();
     sa.bias = b.filtered ? h->ivf_filter.bias_f.as<float>() : h->scan.bias.as<float>();
     sa.qpanels = nullptr;
     sa.qrows = reinterpret_cast<const _Float16 *>(ws.qpanels.p);
@@ -786,6 +824,8 @@ void ivf_search_lists(const IvfBatch &b) {
     } else {
         if (b.sq8d) {
             ivf_scan_sq8d(b, sa);
+        } else if (b.pqd) {
+            ivf_scan_pqd(b, sa);
         } else if (i8_no_slab) {
             ivf_i8_flag_kernel<<<dim3(1), dim3(64), 0, b.st>>>(L.info);
             sa.part_spans = plan_ivf_f16(b.shape, h->opt, b.g).part_spans;      // (the int8 scan takes the fp16 plan's parts)
@@ -901,6 +941,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         if (h->sq8k_ok && !b.sq8k) b.g = IvfGeom{};      // (no fp16 K-loop scan behind it: the exact list scan)
         b.pqk = ivf_pqk_serves(h->opt.ivf_pq_kloop, h->ivf_codec, h->pqk_ok, b.g.ok && b.g.kloop, filtered);
         if (h->pqk_ok && !b.pqk) b.g = IvfGeom{};        // (likewise)
+        b.pqd = ivf_pqd_serves(h->opt.ivf_pq_direct, h->ivf_codec, b.g.ok, b.g.kloop, filtered) && ivfpqd_prepare(h, st);
         b.i8k = ivf_i8k_serves(h->ivf_i8k_ok && h->scan.panels8.p && h->scan.rows8.p, h->opt.panel_dtype, h->opt.ivf_tile, filtered, b.g.ok && b.g.kloop);
         b.d_cnt = ivf_bind_zero(h, b.g.ok ? b.g.cnt_words : 0);
         if (b0 == 0) {
@@ -931,6 +972,7 @@ void ivf_search_device_impl(vdb_index_s *h, const float *dq, int64_t nq, int k, 
         any_mfma = any_mfma || b.g.ok;
         h->sq8d_last = b.sq8d || b.sq8k;
         h->pqk_last = b.pqk;
+        h->pqd_last = b.pqd;
     }
     } catch (...) {
         h->ev_used = ev_mark;

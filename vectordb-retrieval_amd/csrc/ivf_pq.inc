@@ -30,6 +30,7 @@ void ivfpq_install_codebooks(vdb_index_s *h, int M, const float *cb_host) {
     pq_install_codebooks(h, h->ivfpq, h->kept.ivfpq_cb, M, cb_host);
     h->codes.ivfpq_n2.release();               // (the norms of the ADC scan: ivfpq_adc_prepare)
     ivfpqk_drop(h);                            // (the table and accumulator inits of the K-loop scan: ivfpqk_build_space)
+    ivfpqd_drop(h);                            // (the table of the direct scan: ivfpqd_prepare)
     h->ivf_built = false;                     // (rows encoded under the old codebooks are dropped by the next add)
 }
 
@@ -62,6 +63,66 @@ inline float pqk_round_up(double v) {
     const float f = (float)v;
     return (double)f < v ? std::nextafterf(f, INFINITY) : f;
 }
+// What both scans of the product codes read of the codebooks and centroids, on the host in float64: the power-of-two scale ts of the
+// table (max |ts cb| in [128, 256)), the fp16 table T[m][256][P] = fp16(ts cb) -- P >= dsub, zero in the padding of every sub-space and
+// behind the table up to a multiple of `round_bytes` -- and per dimension what the bound reads: max |T| / ts, max |T / ts - cb| (what
+// the table really lost) and max_l |c_l| + max |cb| (the one float32 add of the decode), rounded up to float32.
+void ivfpq_scan_table(vdb_index_s *h, int P, size_t round_bytes, hipStream_t st) {
+    const int Dm = h->dim, M = h->ivfpq.M, dsub = h->ivfpq.dsub;
+    // the table and the constants of the bound
+    const std::vector<float> &cb = h->ivfpq.host;
+    std::vector<double> cmax((size_t)Dm, 0.0);
+    double rmax = 0.0, camax = 0.0, can2 = 0.0;
+    bool finite = true;
+    for (float v : cb) {
+        finite = finite && std::isfinite(v);
+        rmax = std::max(rmax, std::fabs((double)v));
+    }
+    for (int l = 0; l < h->nlist; ++l) {
+        double s = 0.0;
+        for (int d = 0; d < Dm; ++d) {
+            const double c = (double)h->ivf_centroids[(size_t)l * Dm + d];
+            finite = finite && std::isfinite(c);
+            cmax[(size_t)d] = std::max(cmax[(size_t)d], std::fabs(c));
+            s += c * c;
+        }
+        can2 = std::max(can2, s);
+    }
+    for (double c : cmax) camax = std::max(camax, c);
+    double ts = 1.0;
+    if (finite && rmax > 0.0) {
+        int e;
+        std::frexp(rmax, &e);                      // rmax = f 2^e, f in [0.5, 1)
+        ts = std::ldexp(1.0, 8 - e);               // rmax ts in [128, 256)
+    }
+    std::vector<_Float16> tab((((size_t)M * 256 * P * sizeof(_Float16) + round_bytes - 1) / round_bytes * round_bytes) / sizeof(_Float16), (_Float16)0.f);
+    std::vector<float> dimc((size_t)3 * Dm, 0.f);
+    if (finite)
+        for (int m = 0; m < M; ++m)
+            for (int c = 0; c < 256; ++c)
+                for (int j = 0; j < dsub; ++j) {
+                    const int d = m * dsub + j;
+                    const double v = (double)cb[((size_t)m * 256 + c) * dsub + j];
+                    const _Float16 t = (_Float16)(float)(v * ts);
+                    tab[((size_t)m * 256 + c) * P + j] = t;
+                    if (d >= Dm) continue;
+                    const double back = (double)(float)t / ts;
+                    dimc[(size_t)d] = std::max(dimc[(size_t)d], pqk_round_up(std::fabs(back)));
+                    dimc[(size_t)Dm + d] = std::max(dimc[(size_t)Dm + d], pqk_round_up(std::fabs(back - v)));
+                    dimc[(size_t)2 * Dm + d] = std::max(dimc[(size_t)2 * Dm + d], pqk_round_up(cmax[(size_t)d] + std::fabs(v)));
+                }
+    h->scan.pqk_tab.reserve_exact(tab.size() * sizeof(_Float16));
+    h->scan.pqk_dim.reserve_exact(dimc.size() * sizeof(float));
+    VDB_HIP(hipMemcpyAsync(h->scan.pqk_tab.p, tab.data(), tab.size() * sizeof(_Float16), hipMemcpyHostToDevice, st));
+    VDB_HIP(hipMemcpyAsync(h->scan.pqk_dim.p, dimc.data(), dimc.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    VDB_HIP(hipStreamSynchronize(st));
+    h->pqk.ts = ts;
+    h->pqk.can = std::sqrt(can2) * (1.0 + 1.0e-12);
+    h->pqk.camax = pqk_round_up(camax);
+    h->pqk.rmax = pqk_round_up(rmax);
+    h->pqk.consts_ok = finite && ts > 1.0e-30 && ts < 1.0e30 && camax < 1.0e30 && rmax < 1.0e30;
+}
+
 void ivfpqk_build_space(vdb_index_s *h) {
     hipStream_t st = nullptr;
     const int64_t N = h->N;
@@ -101,58 +162,7 @@ void ivfpqk_build_space(vdb_index_s *h) {
                 h->rows.xnorm2.as<float>(), nspans, span_rows, h->metric, h->lists.ivf_span_row0.as<int32_t>(), h->lists.ivf_span_valid.as<int32_t>(),
                 h->scan.bias.as<float>());
             VDB_HIP(hipGetLastError());
-            // the table and the constants of the bound
-            const std::vector<float> &cb = h->ivfpq.host;
-            std::vector<double> cmax((size_t)Dm, 0.0);
-            double rmax = 0.0, camax = 0.0, can2 = 0.0;
-            bool finite = true;
-            for (float v : cb) {
-                finite = finite && std::isfinite(v);
-                rmax = std::max(rmax, std::fabs((double)v));
-            }
-            for (int l = 0; l < h->nlist; ++l) {
-                double s = 0.0;
-                for (int d = 0; d < Dm; ++d) {
-                    const double c = (double)h->ivf_centroids[(size_t)l * Dm + d];
-                    finite = finite && std::isfinite(c);
-                    cmax[(size_t)d] = std::max(cmax[(size_t)d], std::fabs(c));
-                    s += c * c;
-                }
-                can2 = std::max(can2, s);
-            }
-            for (double c : cmax) camax = std::max(camax, c);
-            double ts = 1.0;
-            if (finite && rmax > 0.0) {
-                int e;
-                std::frexp(rmax, &e);                      // rmax = f 2^e, f in [0.5, 1)
-                ts = std::ldexp(1.0, 8 - e);               // rmax ts in [128, 256)
-            }
-            std::vector<_Float16> tab((size_t)M * 256 * P, (_Float16)0.f);
-            std::vector<float> dimc((size_t)3 * Dm, 0.f);
-            if (finite)
-                for (int m = 0; m < M; ++m)
-                    for (int c = 0; c < 256; ++c)
-                        for (int j = 0; j < dsub; ++j) {
-                            const int d = m * dsub + j;
-                            const double v = (double)cb[((size_t)m * 256 + c) * dsub + j];
-                            const _Float16 t = (_Float16)(float)(v * ts);
-                            tab[((size_t)m * 256 + c) * P + j] = t;
-                            if (d >= Dm) continue;
-                            const double back = (double)(float)t / ts;
-                            dimc[(size_t)d] = std::max(dimc[(size_t)d], pqk_round_up(std::fabs(back)));
-                            dimc[(size_t)Dm + d] = std::max(dimc[(size_t)Dm + d], pqk_round_up(std::fabs(back - v)));
-                            dimc[(size_t)2 * Dm + d] = std::max(dimc[(size_t)2 * Dm + d], pqk_round_up(cmax[(size_t)d] + std::fabs(v)));
-                        }
-            h->scan.pqk_tab.reserve_exact(tab.size() * sizeof(_Float16));
-            h->scan.pqk_dim.reserve_exact(dimc.size() * sizeof(float));
-            VDB_HIP(hipMemcpyAsync(h->scan.pqk_tab.p, tab.data(), tab.size() * sizeof(_Float16), hipMemcpyHostToDevice, st));
-            VDB_HIP(hipMemcpyAsync(h->scan.pqk_dim.p, dimc.data(), dimc.size() * sizeof(float), hipMemcpyHostToDevice, st));
-            VDB_HIP(hipStreamSynchronize(st));
-            h->pqk.ts = ts;
-            h->pqk.can = std::sqrt(can2) * (1.0 + 1.0e-12);
-            h->pqk.camax = pqk_round_up(camax);
-            h->pqk.rmax = pqk_round_up(rmax);
-            h->pqk.consts_ok = finite && ts > 1.0e-30 && ts < 1.0e30 && camax < 1.0e30 && rmax < 1.0e30;
+            ivfpq_scan_table(h, P, 1, st);
         }
     } catch (...) {
         h->rows.xnorm2.release();
@@ -165,6 +175,22 @@ void ivfpqk_build_space(vdb_index_s *h) {
     h->pqk_ok = !h->nonfinite;
     h->tile16 = h->pqk_ok;                                     // (the plan's K-loop geometry: ivf_shape_of)
     h->ivf_mfma_ok = h->pqk_ok;
+}
+
+// D <= 128, option "ivf_pq_direct": what the direct scan (ivf_pq_scan.hpp) keeps per handle beside the panel space every IVF-PQ handle
+// of that size has -- the UNPADDED table T[m][256][dsub] (512 D bytes, zero filled up to the KiB pieces it is copied into LDS in) and
+// the constants of the bound.  Made by the first batch the route would serve, or by an add while the option is on; held = valid
+// (ivfpqd_drop: new centroids, new codebooks; vdb_reset frees it with the scan copies).  One stream synchronisation.
+bool ivfpqd_prepare(vdb_index_s *h, hipStream_t st) {
+    if (h->scan.pqk_tab.p && h->scan.pqk_dim.p) return true;
+    if (h->ksteps > kMaxKSteps || h->ivfpq.M < 1 || ivf_pqd_lds_bytes(h->dim, h->ivfpq.M, h->ksteps) > kPqdLdsBudget) return false;
+    try {
+        ivfpq_scan_table(h, h->ivfpq.dsub, 1024, st);
+    } catch (...) {
+        ivfpqd_drop(h);
+        throw;
+    }
+    return true;
 }
 
 void ivfpq_build_panel_space(vdb_index_s *h) {
@@ -189,6 +215,7 @@ void ivfpq_build_panel_space(vdb_index_s *h) {
     h->rows.x32.release();
     h->scan.panels.release();
     h->rows.xnorm2.release();                                  // (the norms only fed the bias)
+    if (h->opt.ivf_pq_direct && h->ivf_mfma_ok) ivfpqd_prepare(h, nullptr);
 }
 
 // vdb_ivf_add(_assigned) and vdb_ivfpq_add_codes on an IVF-PQ handle: the same lists as ivf_add_impl (ivf_add_lists); the new

@@ -91,7 +91,9 @@ __device__ __forceinline__ _Float16 pqk_operand(float q, double bs_ts, double &t
     return (_Float16)(float)t;
 }
 
-__global__ __launch_bounds__(256) void ivf_pqk_prep_kernel(PqkPrepArgs a) {
+// DIRECT: the operand rows in plain dimension order, Kpad = 16 KSTEPS (the D <= 128 scan, ivf_pq_scan.hpp) instead of the padded space
+template <bool DIRECT>
+__device__ __forceinline__ void pqk_prep_body(const PqkPrepArgs &a) {
     extern __shared__ int ivf_hist[];
     __shared__ QueryBatchInfo s_info;
     if (blockIdx.x >= a.n_eps_blocks + a.n_row_blocks) {
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void ivf_pqk_prep_kernel(PqkPrepArgs a) {
         half8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int d = ivf_pqk_operand_dim(p0 + j, a.M, a.dsub);
+            const int d = DIRECT ? (p0 + j < a.D ? p0 + j : -1) : ivf_pqk_operand_dim(p0 + j, a.M, a.dsub);
             double t;
             o[j] = d < 0 ? (_Float16)0.f : pqk_operand(a.Q[(size_t)q * a.D + d], bs_ts, t);
         }
@@ -171,6 +173,7 @@ __global__ __launch_bounds__(256) void ivf_pqk_prep_kernel(PqkPrepArgs a) {
     a.eps[q] = (float)e + 1.0e-30f;
     a.qterm[q] = 0.0;
 }
+__global__ __launch_bounds__(256) void ivf_pqk_prep_kernel(PqkPrepArgs a) { pqk_prep_body<false>(a); }
 
 // ---- the scan -------------------------------------------------------------------------------------------------------------------------
 struct PqkScanArgs {

@@ -636,6 +636,10 @@ void multi_set_option(vdb_index_s *m, const char *key, double value) {
         if (value != 0) throw Error(VDB_ERR_UNSUPPORTED, "option 'ivf_pq_kloop' is not available on a multi-device index");
         return;
     }
+    if (std::string(key) == "ivf_pq_direct") {
+        if (value != 0) throw Error(VDB_ERR_UNSUPPORTED, "option 'ivf_pq_direct' is not available on a multi-device index");
+        return;
+    }
     if (std::string(key) == "multi_stage_all") {
         M->stage_all = value != 0;
         return;

@@ -61,6 +61,10 @@ struct Options {
     // table of the codebooks (no panels, no float32 rows) and a batch of the list-major path takes the K-loop scan of the product codes
     // (ivf_pq_kloop.hpp; the rules: ivf_pq_kloop_plan.hpp); 0 = every batch takes the exact list scan.  Same results.
     int ivf_pq_kloop = 0;
+    // "ivf_pq_direct" (takes effect at the next search; IVF-PQ index, D <= 128): 1 = a batch of the list-major path is scanned straight
+    // from the product codes, decoded in LDS from a resident fp16 table of the codebooks (ivf_pq_scan.hpp; the rules:
+    // ivf_pq_direct_plan.hpp) -- no per-batch fp16 panels.  Same results.
+    int ivf_pq_direct = 0;
     int int8_slab_chunks = 0;               // scan chunks per converted fp16 slab (0 = default 8)
     int int8_block_rows = 0;                 // rows per ingestion block of the int8-only build (0 = 4M; tests), and of an add to an
                                              // IVF-I8 index (0 = 1M): the float32 rows of one block are all the device holds of them
@@ -256,11 +260,11 @@ inline int64_t stream_slab_chunks(const ScanIndexShape &s, const Options &opt, c
 }
 
 // ---- a launch -------------------------------------------------------------------------------------------------------------------
-enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16, ivf_kloop, ivf_kloop_i8, ivf_sq8d, ivf_sq8k, ivf_pqk };
+enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16, ivf_kloop, ivf_kloop_i8, ivf_sq8d, ivf_sq8k, ivf_pqk, ivf_pqd };
 constexpr const char *kScanFamilyNames[] = {"none", "scan_kernel", "scan16_kloop_kernel", "scan_x16_kernel", "scan_i8_kernel",
                                             "scan_i8x16_kernel", "scan_pair_x16_kernel", "ivf_kloop_scan_kernel", "ivf_kloop_i8_scan_kernel", "ivf_sq8_scan_kernel",
-                                            "ivf_sq8_kloop_scan_kernel", "ivf_pq_kloop_scan_kernel"};
-constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7, 4, 3, 3, 3, 4};   // template parameters of each family's kernel
+                                            "ivf_sq8_kloop_scan_kernel", "ivf_pq_kloop_scan_kernel", "ivf_pq_scan_kernel"};
+constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7, 4, 3, 3, 3, 4, 3};   // template parameters of each family's kernel
 constexpr int kScanMaxArgs = 10;
 
 // The template arguments of one instantiation in the kernel's own order, defaults written out (bool as 0 / 1, the rest 0):

@@ -36,6 +36,7 @@
 #include "ivf_i8.hpp"
 #include "ivf_pq.hpp"
 #include "ivf_pq_kloop.hpp"
+#include "ivf_pq_scan.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
 #include "lsh_tables.hpp"
@@ -409,6 +410,9 @@ struct vdb_index_s {
     // and whether that scan served the last batch
     struct PqKloop { double ts = 1.0, can = 0.0; float camax = 0.f, rmax = 0.f; bool consts_ok = false; } pqk;
     bool pqk_ok = false, pqk_last = false;
+    // option "ivf_pq_direct" (ivf_pq_scan.hpp, D <= 128): its table and constants live in scan.pqk_tab / scan.pqk_dim and `pqk` (held =
+    // valid: ivfpqd_prepare, ivf_pq.inc); whether that scan served the last batch
+    bool pqd_last = false;
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
@@ -516,6 +520,7 @@ constexpr OptionRow kOptions[] = {
     {"ivf_sq8_direct", &Options::ivf_sq8_direct, 2, {0, 1}},        // IVF-SQ8, D <= 128, next search: 1 = the list scan reads the 8-bit codes directly (no per-batch fp16 panels); no effect elsewhere
     {"ivf_sq8_kloop", &Options::ivf_sq8_kloop, 2, {0, 1}},          // IVF-SQ8, D > 128, next add: 1 = span tables and accumulator inits for the K-loop list scan of the 8-bit codes; no effect elsewhere
     {"ivf_pq_kloop", &Options::ivf_pq_kloop, 2, {0, 1}},            // IVF-PQ, D > 128, next add: 1 = span tables, accumulator inits and the fp16 table for the K-loop list scan of the product codes; no effect elsewhere
+    {"ivf_pq_direct", &Options::ivf_pq_direct, 2, {0, 1}},          // IVF-PQ, D <= 128, next search: 1 = the list scan decodes the product codes in LDS from a resident fp16 table (no per-batch fp16 panels); no effect elsewhere
     {"int8_slab_chunks", &Options::int8_slab_chunks, 0, {0, 1024}},
     {"int8_block_rows", &Options::int8_block_rows, 0, {0, 2147483647}},
     {"stream_panels", &Options::stream_panels, 2, {0, 1}, kNoRows | kNeedsRows, 0, nullptr, &vdb_index_s::panels_streamed},   // D > 128, next add: 0 keep the fp16 panels resident | 1 convert them per search
@@ -1508,6 +1513,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         if (h->ivf_codec != 0 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && !(h->ivf_codec == 3 && s.scan_dtype == 1)) s.scan_dtype = 2;   // fp16 from 8-bit (product) codes, or from the int8 panels of IVF-I8 (whose integer batches take the int8 scan: 1)
         if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct"; D > 128: "ivf_sq8_kloop")
         if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqk_last) s.scan_dtype = 5;     // fp16 MFMA on fragments gathered by the product codes (option "ivf_pq_kloop")
+        if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqd_last) s.scan_dtype = 6;     // fp16 MFMA on fragments decoded in LDS from the product codes (option "ivf_pq_direct")
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                         // ... of a PQ index
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;

@@ -493,7 +493,8 @@ class HipIVFSearcher(FaissStyleSearcher):
     "ivfpq_adc_max_batch" of the attached index -- it has an effect on an IVF-PQ index only (HipIVFPQIndexer).  `int8_kloop`
     (`int8_kloop: true`): option "ivf_i8_kloop" of the attached index; it takes effect at an add, so give it to the HipIVFIndexer
     as well -- here it keeps the option set for rows added to the index later.  `direct_codes` (`direct_codes: true`): option
-    "ivf_sq8_direct" of the attached index, from the next search on (an IVF-SQ8 artifact; no effect on the others).  `direct_kloop`
+    "ivf_sq8_direct" of the attached index, from the next search on (an IVF-SQ8 artifact; an IVF-PQ artifact: option "ivf_pq_direct";
+    no effect on the others).  `direct_kloop`
     (`direct_kloop: true`): option "ivf_sq8_kloop" of the attached index; like `int8_kloop` it takes effect at an add, so give it to the
     HipIVFIndexer as well."""
 
@@ -521,8 +522,9 @@ class HipIVFSearcher(FaissStyleSearcher):
             self.index.adc_max_batch = self.adc_max_batch
         if self.int8_kloop is not None:
             self.index.set_option("ivf_i8_kloop", float(self.int8_kloop))
-        if self.direct_codes is not None:
-            self.index.set_option("ivf_sq8_direct", float(self.direct_codes))
+        if self.direct_codes is not None:      # (an IVF-PQ artifact, HipIVFPQIndexer: the option of its own direct scan)
+            is_pq = getattr(self.index, "_pq_prefix", None) == "vdb_ivfpq_"
+            self.index.set_option("ivf_pq_direct" if is_pq else "ivf_sq8_direct", float(self.direct_codes))
         if self.direct_kloop is not None:
             self.index.set_option("ivf_sq8_kloop", float(self.direct_kloop))
 

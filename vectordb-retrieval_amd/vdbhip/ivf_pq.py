@@ -48,12 +48,14 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
     `set_codebooks` inject them instead.  One GPU only.  `adc_max_batch`: option "ivfpq_adc_max_batch" -- query batches up to that
     size (at most 512; 0 = off) take the lookup-table (ADC) scan of the probed lists; same results.  `direct_kloop` (None: untouched):
     option "ivf_pq_kloop", in effect from the next add -- dim > 128: the add builds span tables, accumulator inits and an fp16 table of
-    the codebooks, and batches take the K-loop list scan of the product codes instead of the exact list scan (same results)."""
+    the codebooks, and batches take the K-loop list scan of the product codes instead of the exact list scan (same results).
+    `direct_codes` (None: untouched; the SQ8 classes' name): option "ivf_pq_direct", in effect from the next search -- dim <= 128: batches
+    of the list-major path are scanned straight from the product codes, decoded in LDS, without per-batch fp16 panels (same results)."""
 
     _pq_prefix = "vdb_ivfpq_"
 
     def __init__(self, dim: int, nlist: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0,
-                 direct_kloop: Optional[bool] = None):
+                 direct_kloop: Optional[bool] = None, direct_codes: Optional[bool] = None):
         one_device(device, _ONE_GPU)
         check_m(int(dim), int(M))
         super().__init__(dim, nlist, metric, device)
@@ -64,6 +66,8 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
             self.set_option("ivfpq_adc_max_batch", float(self.adc_max_batch))
         if direct_kloop is not None:
             self.set_option("ivf_pq_kloop", float(int(bool(direct_kloop))))
+        if direct_codes is not None:
+            self.set_option("ivf_pq_direct", float(int(bool(direct_codes))))
 
     def debug_adc_scores(self, queries: np.ndarray, probe_list: int, row0: int, nrows: int):
         """(scores (nq, nrows) float32, eps (nq,) float32, cs): the ADC scan's own scores of the list-order rows [row0, row0 + nrows)
@@ -103,7 +107,7 @@ class IVFPQIndex(PQCodec, IVFFlatIndex):
 def _build_ivfpq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> IVFPQIndex:
     nlist, M = parse_ivfpq_key(key)
     index = IVFPQIndex(dim, nlist, M, metric, device, adc_max_batch=int(params.get("adc_max_batch") or 0),
-                       direct_kloop=params.get("direct_kloop"))
+                       direct_kloop=params.get("direct_kloop"), direct_codes=params.get("direct_codes"))
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
     index.add(vectors)
@@ -120,16 +124,20 @@ def _check_key(dimension: int, key: str, device) -> Tuple[int, int]:
 class HipIVFPQIndexer(BaseIndexer):
     """FaissFactoryIndexer semantics for an "IVF<nlist>,PQ<M>" key; the artifact is HipIVFSearcher's ('hip_ivf').
     `adc_max_batch` (a config entry `adc_max_batch: 16`): option "ivfpq_adc_max_batch" of the index it builds.  `direct_kloop: true`
-    (more than 128 dimensions): option "ivf_pq_kloop", set before the rows are added."""
+    (more than 128 dimensions): option "ivf_pq_kloop", set before the rows are added.  `direct_codes: true` (at most 128 dimensions):
+    option "ivf_pq_direct"."""
 
     def __init__(self, name: str, dimension: int, metric: str = "l2", index_type: Optional[str] = None,
-                 index_key: Optional[str] = None, adc_max_batch: int = 0, direct_kloop: Optional[bool] = None, **kwargs: Any) -> None:
+                 index_key: Optional[str] = None, adc_max_batch: int = 0, direct_kloop: Optional[bool] = None,
+                 direct_codes: Optional[bool] = None, **kwargs: Any) -> None:
         key = index_key or index_type or "IVF100,PQ8"
         params = dict(kwargs)
         params.setdefault("index_type", key)
         params["adc_max_batch"] = int(adc_max_batch or 0)
         if direct_kloop is not None:
             params["direct_kloop"] = bool(direct_kloop)
+        if direct_codes is not None:
+            params["direct_codes"] = bool(direct_codes)
         super().__init__(name, dimension, metric, **params)
         self.adc_max_batch = int(adc_max_batch or 0)
         self.index_key = self.index_type = key
@@ -152,13 +160,16 @@ class HipIVFPQIndexer(BaseIndexer):
 class HipIVFPQSearch(RawAlgorithm):
     """ApproximateSearch semantics for `index_type="IVF<nlist>,PQ<M>"`: train -> add -> nprobe from kwargs; raw FAISS
     conventions (no normalisation, no sign flip: 'l2' -> squared L2, anything else -> raw inner product).  `direct_kloop: true`: option
-    "ivf_pq_kloop" before the rows are added or loaded (more than 128 dimensions: the K-loop list scan of the product codes)."""
+    "ivf_pq_kloop" before the rows are added or loaded (more than 128 dimensions: the K-loop list scan of the product codes).
+    `direct_codes: true`: option "ivf_pq_direct" (at most 128 dimensions: the direct list scan of the product codes)."""
 
     _FORMAT = "vdbhip-ivfpq-v1"
 
     def __init__(self, name: str, dimension: int, index_type: str = "IVF100,PQ8", metric: str = "l2",
-                 device: Optional[int] = None, adc_max_batch: int = 0, direct_kloop: Optional[bool] = None, **kwargs: Any) -> None:
+                 device: Optional[int] = None, adc_max_batch: int = 0, direct_kloop: Optional[bool] = None,
+                 direct_codes: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, **kwargs)
+        self.direct_codes = direct_codes                  # option "ivf_pq_direct": likewise
         self.direct_kloop = direct_kloop                  # option "ivf_pq_kloop": likewise a constructor parameter
         self.adc_max_batch = int(adc_max_batch or 0)      # option "ivfpq_adc_max_batch": a constructor parameter, not part of the artifact
         self.index_type = index_type
@@ -170,7 +181,8 @@ class HipIVFPQSearch(RawAlgorithm):
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         data = np.asarray(vectors).astype(np.float32)
         self.index = _build_ivfpq(data, self.dimension, self.index_type, self.metric, self.device,
-                                  {**self.config, "adc_max_batch": self.adc_max_batch, "direct_kloop": self.direct_kloop})
+                                  {**self.config, "adc_max_batch": self.adc_max_batch, "direct_kloop": self.direct_kloop,
+                                   "direct_codes": self.direct_codes})
         self.index_built = True
         if "nprobe" in self.config:
             self.index.set_nprobe(int(self.config["nprobe"]))
@@ -204,7 +216,7 @@ class HipIVFPQSearch(RawAlgorithm):
             raise ValueError("Persisted IVF-PQ files do not match the manifest")
         persist.check_sha256(manifest, arrays)
         self.index = IVFPQIndex(self.dimension, nlist, m, self.metric, self.device, adc_max_batch=self.adc_max_batch,
-                                direct_kloop=self.direct_kloop)
+                                direct_kloop=self.direct_kloop, direct_codes=self.direct_codes)
         self.index.set_centroids(arrays["centroids"])      # no k-means, no assignment and no encoding pass: the stored
         self.index.set_codebooks(arrays["codebooks"])      # index is reused as it is
         self.index.add_codes(arrays["codes"], lists, id_base=int(manifest.get("id_base", 0)))
