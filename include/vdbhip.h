@@ -89,7 +89,9 @@ typedef struct vdb_stats_s {
                                   5 = fp16 MFMA on fragments of an fp16 codebook table gathered by the product codes of an IVF-PQ index of
                                   more than 128 dimensions, option "ivf_pq_kloop" (f32 accumulate; last_path stays VDB_PATH_IVF),
                                   6 = fp16 MFMA on fragments decoded in LDS from the product codes of an IVF-PQ index of at most 128
-                                  dimensions, option "ivf_pq_direct" (f32 accumulate; last_path stays VDB_PATH_IVF) */
+                                  dimensions, option "ivf_pq_direct" (f32 accumulate; last_path stays VDB_PATH_IVF),
+                                  7 = fp16 MFMA on fragments of the fp16 codebook table gathered by the product codes of a flat PQ index of
+                                  more than 128 dimensions, option "pq_kloop" (f32 accumulate; last_path stays VDB_PATH_MFMA_SCAN) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -873,6 +875,17 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       Measured on 1M rows (profiles/r18_bench_pq_adc.json): faster than the panel pass by more than 8 % up to
  *                       8 queries for PQ16 at D = 128 and PQ64 at D = 384, up to 2 for PQ64 at D = 128 -- the value to set; the
  *                       cost grows linearly with the batch beyond
+ *     "pq_kloop"        PQ index, D > 128 (M <= 256 and M x 8 ceil(dsub / 8) <= 4096), takes effect at the next search: 0 (default):
+ *                       a batch of the MFMA scan path decodes the corpus into fp16 panels slab by slab and scans them | 1: an
+ *                       unfiltered vdb_search / vdb_search_device batch of that path on the standard 256-row-bin geometry is scanned
+ *                       on the matrix cores straight from the codes -- the A operand is gathered, 16 bytes at a time, by the code
+ *                       bytes from the fp16 table of the scaled codebooks, zero padded to whole 8-element pieces per sub-space
+ *                       (M x 256 x 8 ceil(dsub / 8) x 2 bytes, resident from the first such batch after an add); no panels are made,
+ *                       and a handle searched only this way never allocates the slab (vdb_stats.scan_dtype = 7; DESIGN 4.9 "K-loop
+ *                       scan").  Operands, bias and error bound are those of the panel pass, so the results are the same bit for
+ *                       bit.  "force_path" and "pq_scan_min_batch" act as before and a batch "pq_adc_max_batch" admits takes the
+ *                       ADC scan; the direct-bin geometry, filtered and range calls take the panel pass.  Accepted without effect
+ *                       on every other kind of index and on D <= 128
  *     "ivfpq_adc_max_batch"  IVF-PQ index: largest query batch that takes the lookup-table (ADC) scan of the probed lists instead of
  *                       the panel pass + list-major MFMA scan (dim <= 128) or the exact list scan, 0 (default: off) .. 512; accepted
  *                       without effect on every other kind of index and for a batch the scan does not serve.  Same results either

@@ -31,6 +31,10 @@ name into --out (default profiles/r07_bench_pq.json) and printed as one line.  E
             Per-kernel times of the two new kernels at one query, a run of its own per workload (profiles/r18_pq_adc_kernel_stats.csv):
                 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d build/adc_trace -o adc -- \\
                     python scripts/bench_pq.py --adc --adc-nq 1 --workload gauss128_pq64 --steps 20 --niter 4 --out build/adc_trace/bench.json
+    --kloop the K-loop scan of the codes against the panel pass (profiles/r34_bench_pq_kloop.json; workloads gauss768_pq64, unit768_pq64,
+            unit384_pq64): for nq in {1, 64, 10 000} device-resident searches of ONE handle with option "pq_kloop" = 0, 1 and 0 again, its
+            ADC scan (up to 512 queries) and a flat index over reconstruct(), one search each per round; median, minimum and maximum of
+            `steps` rounds, result checksums (they must agree: exit status 1 otherwise) and bytes_workspace of each leg.
 """
 from __future__ import annotations
 
@@ -50,7 +54,8 @@ for p in (str(ROOT), str(ROOT / "vectordb-retrieval_amd")):
         sys.path.insert(0, p)
 
 K = 10
-WORKLOADS = {"gauss128_pq16": (128, 16, "l2"), "gauss128_pq64": (128, 64, "l2"), "unit384_pq64": (384, 64, "ip")}
+WORKLOADS = {"gauss128_pq16": (128, 16, "l2"), "gauss128_pq64": (128, 64, "l2"), "unit384_pq64": (384, 64, "ip"),
+             "gauss768_pq64": (768, 64, "l2"), "unit768_pq64": (768, 64, "ip")}       # (the 768-dimensional pair: the --kloop leg)
 
 
 def recall(exact, got, k):
@@ -118,6 +123,78 @@ def adc_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s) -> in
     return 0 if same else 1
 
 
+def kloop_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s) -> int:
+    """Option "pq_kloop" 0 against 1 on ONE handle, alternating, one search each per round: the option-0 leg is timed twice per round
+    ("panel_pass", "panel_pass_again"), so the distance between its two medians is the spread a difference has to exceed.  Where it
+    fits, the ADC scan of the same handle ("pq_adc_max_batch" = 512, batches up to 512) and a flat index over reconstruct() run in
+    the same rounds.  bytes_workspace is read once on a handle searched with option 1 only, and again after the option-0 legs."""
+    import vdbhip
+
+    dev = Q_t.device
+    pq.set_option("pq_kloop", 1)
+    D_t, I_t = torch.empty((64, K), dtype=torch.float32, device=dev), torch.empty((64, K), dtype=torch.int64, device=dev)
+    pq.search_device(Q_t.data_ptr(), 64, K, D_t.data_ptr(), I_t.data_ptr(), stream)
+    torch.cuda.synchronize()
+    st1 = pq.stats()
+    flat = vdbhip.FlatIndex(d, metric, 0)
+    flat.add(pq.reconstruct())
+    res = {"config": f"{args.workload}: {n} x {d}, PQ{M}, {metric}, k={K}, device-resident searches, option pq_kloop 0 / 0 / 1 (one handle), the ADC "
+                     f"scan and a flat index over reconstruct() alternating, median (min .. max) of {args.steps} rounds after {args.warmup}",
+           "train_s": round(train_s, 2), "add_s": round(add_s, 2), "niter": args.niter, "code_bytes": n * M,
+           "bytes_workspace_option_1_only": st1["bytes_workspace"], "scan_dtype_option_1": st1["scan_dtype"], "batches": {}}
+    same = st1["scan_dtype"] == 7
+    for m in [int(v) for v in args.kloop_nq.split(",")]:
+        legs = [("panel_pass", pq, {"pq_kloop": 0, "pq_adc_max_batch": 0}), ("kloop", pq, {"pq_kloop": 1, "pq_adc_max_batch": 0}),
+                ("panel_pass_again", pq, {"pq_kloop": 0, "pq_adc_max_batch": 0})]
+        if m <= 512:
+            legs.append(("adc", pq, {"pq_kloop": 0, "pq_adc_max_batch": 512}))
+        legs.append(("flat_over_reconstruct", flat, {}))
+        outs = {name: (torch.empty((m, K), dtype=torch.float32, device=dev), torch.empty((m, K), dtype=torch.int64, device=dev)) for name, _, _ in legs}
+
+        def search(name, idx, opts):
+            for key, value in opts.items():
+                idx.set_option(key, value)
+            idx.search_device(Q_t.data_ptr(), m, K, outs[name][0].data_ptr(), outs[name][1].data_ptr(), stream)
+
+        for _ in range(args.warmup):
+            for leg in legs:
+                search(*leg)
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _, _ in legs}
+        for _ in range(args.steps):
+            for name, idx, opts in legs:
+                for key, value in opts.items():
+                    idx.set_option(key, value)
+                t0 = time.perf_counter()
+                idx.search_device(Q_t.data_ptr(), m, K, outs[name][0].data_ptr(), outs[name][1].data_ptr(), stream)
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) * 1e3)
+        row, sums = {}, {}
+        for name, idx, opts in legs:
+            search(name, idx, opts)
+            torch.cuda.synchronize()
+            st = idx.stats()
+            sums[name] = hashlib.sha256(outs[name][1].cpu().numpy().tobytes() + outs[name][0].cpu().numpy().tobytes()).hexdigest()[:16]
+            row[name] = {"ms": round(statistics.median(ms[name]), 4), "min_ms": round(min(ms[name]), 4), "max_ms": round(max(ms[name]), 4),
+                         "path": st["last_path_name"], "scan_dtype": st["scan_dtype"], "flagged_queries": st["last_fallback_queries"],
+                         "candidates_per_query": round(st["last_candidates"] / m, 2), "bytes_workspace": st["bytes_workspace"]}
+        row["kloop_over_panel_pass_time"] = round(row["kloop"]["ms"] / row["panel_pass"]["ms"], 4)
+        row["panel_pass_again_over_panel_pass_time"] = round(row["panel_pass_again"]["ms"] / row["panel_pass"]["ms"], 4)
+        row["same_results"] = len(set(sums.values())) == 1
+        same = same and row["same_results"] and row["kloop"]["scan_dtype"] == 7
+        res["batches"][str(m)] = row
+    pq.set_option("pq_adc_max_batch", 0)
+    pq.close()
+    flat.close()
+    path = Path(args.out)
+    allres = json.loads(path.read_text()) if path.exists() else {}
+    allres[args.workload] = res
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(allres, indent=1) + "\n")
+    print(json.dumps({args.workload: res}))
+    return 0 if same else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", choices=sorted(WORKLOADS), required=True)
@@ -129,10 +206,12 @@ def main() -> int:
     ap.add_argument("--no-tables", action="store_true", help="skip the slab-size and small-batch tables")
     ap.add_argument("--adc", action="store_true", help="only the ADC leg: option pq_adc_max_batch 0 against 512 on small batches")
     ap.add_argument("--adc-nq", default="1,2,4,8,16,32,64,128,512", help="batch sizes of the ADC leg (a kernel trace takes one)")
+    ap.add_argument("--kloop", action="store_true", help="only the K-loop leg: option pq_kloop 0 against 1 on one handle (D > 128 workloads)")
+    ap.add_argument("--kloop-nq", default="1,64,10000", help="batch sizes of the K-loop leg")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / ("r18_bench_pq_adc.json" if args.adc else "r07_bench_pq.json"))
+        args.out = str(ROOT / "profiles" / ("r34_bench_pq_kloop.json" if args.kloop else "r18_bench_pq_adc.json" if args.adc else "r07_bench_pq.json"))
     import torch
 
     import vdbhip
@@ -161,6 +240,9 @@ def main() -> int:
     if args.adc:
         del X
         return adc_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s)
+    if args.kloop:
+        del X
+        return kloop_leg(args, torch, pq, Q_t, stream, n, d, M, metric, train_s, add_s)
     xh = pq.reconstruct()
     flat = vdbhip.FlatIndex(d, metric, 0)
     flat.add(xh)

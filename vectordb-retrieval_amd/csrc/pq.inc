@@ -129,7 +129,8 @@ void pq_rebuild(vdb_index_s *h, hipStream_t st) {
     h->panels_streamed = false;
     h->i8_ok = false;
     h->i8k_ok = false;
-    h->tile16 = h->ksteps > kMaxKSteps;          // (D > 128: p16 panels; D <= 128: layout "x16" -- the slab is made per search either way)
+    h->scan.pq_ktab.release();                   // (option "pq_kloop": the padded copy of pq_tab is remade by the next batch that needs it)
+    h->tile16 = h->ksteps > kMaxKSteps;         // (D > 128: p16 panels; D <= 128: layout "x16" -- the slab is made per search either way)
     h->x16 = !h->tile16;
     const int64_t span_rows = h->tile16 ? kSpanRows16 : kSpanRows;
     h->Npad = (n + span_rows - 1) / span_rows * span_rows;
@@ -280,6 +281,40 @@ void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *pane
     else if (W == 2) VDB_PQ_PANELS(2);
     else VDB_PQ_PANELS(1);
 #undef VDB_PQ_PANELS
+    VDB_HIP(hipGetLastError());
+}
+
+// ---- the K-loop scan of the codes (pq_kloop.hpp; option "pq_kloop") ---------------------------------------------------------------
+// one row per instantiation (VDB_KERNELS_PQ_KLOOP, pq_kloop_plan.hpp), beside the flat table of search_flat.inc
+#define VDB_ROW_PQ_KLOOP(...) {ScanKey{{__VA_ARGS__}}, &pq_kloop_scan_kernel<__VA_ARGS__>},
+constexpr ScanRow<ScanArgs, ScanKloopExtra, PqKloopArgs> kRowsPqKloop[] = {VDB_KERNELS_PQ_KLOOP(VDB_ROW_PQ_KLOOP)};
+#undef VDB_ROW_PQ_KLOOP
+
+// The padded table T[m][256][P] is pq_tab copied with zeros beyond dsub: made by the first batch the scan serves after an add
+// (pq_rebuild remakes pq_tab under the new sx and drops this copy), in stream order ahead of the scan.  `sa`: the flat scan's
+// arguments of search_scan (panels unused; qpanels in the padded order, scan_query_prep).
+void launch_pq_kloop(vdb_index_s *h, const ScanLaunch &p, const ScanArgs &sa, hipStream_t st) {
+    const int M = h->pq.M, dsub = h->pq.dsub, P = ivf_pqk_p(dsub);
+    if (!h->scan.pq_ktab.p) {
+        const int64_t pieces = (int64_t)M * 256 * (P / 8);
+        h->scan.pq_ktab.reserve_exact((size_t)pieces * 8 * sizeof(_Float16));
+        pq_kloop_table_kernel<<<dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st>>>(h->scan.pq_tab.as<_Float16>(), M, dsub,
+                                                                                           h->scan.pq_ktab.as<_Float16>());
+        VDB_HIP(hipGetLastError());
+    }
+    if (p.key.t[2] < M) throw Error(VDB_ERR_STATE, "internal: the code pitch of the K-loop scan is below M");
+    ScanArgs a = sa;
+    a.panels = nullptr;
+    a.chunk0 = 0;
+    a.nqtiles = p.nqtiles;
+    PqKloopArgs pa{};
+    pa.codes = h->codes.pq_codes.as<unsigned char>();
+    pa.table = h->scan.pq_ktab.as<_Float16>();
+    pa.N = h->N;
+    pa.M = M;
+    pa.P8 = P / 8;
+    pa.npieces = ivf_pqk_kp(M, dsub) / 8;
+    scan_kernel_of(kRowsPqKloop, p)<<<dim3(p.grid), dim3(p.block), 0, st>>>(a, ScanKloopExtra{4 * ivf_pqk_nk(M, dsub), p.qgroup}, pa);
     VDB_HIP(hipGetLastError());
 }
 

@@ -88,6 +88,10 @@ struct Options {
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
     int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)
+    // "pq_kloop" (takes effect at the next search; flat PQ index, D > 128): 1 = a batch the panel pass + K-loop scan would serve on the
+    // standard geometry is scanned straight from the product codes, A fragments gathered from a padded fp16 table of the codebooks
+    // (pq_kloop.hpp; the rules: pq_kloop_plan.hpp) -- no panels, no slab.  Same results.
+    int pq_kloop = 0;
     int ivfpq_adc_max_batch = 0;             // IVF-PQ: largest batch the lookup-table (ADC) scan of the probed lists serves (0 = off; ivf_adc_plan)
     int ivfpq_adc_part_rows = 0;             // ... rows per row part of that scan (0 auto, else a multiple of 256)
     // k-NN graph (knng.inc)
@@ -260,11 +264,11 @@ inline int64_t stream_slab_chunks(const ScanIndexShape &s, const Options &opt, c
 }
 
 // ---- a launch -------------------------------------------------------------------------------------------------------------------
-enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16, ivf_kloop, ivf_kloop_i8, ivf_sq8d, ivf_sq8k, ivf_pqk, ivf_pqd };
+enum class ScanFamily { none, scan, scan16_kloop, scan_x16, scan_i8, scan_i8x16, scan_pair_x16, ivf_kloop, ivf_kloop_i8, ivf_sq8d, ivf_sq8k, ivf_pqk, ivf_pqd, pq_kloop };
 constexpr const char *kScanFamilyNames[] = {"none", "scan_kernel", "scan16_kloop_kernel", "scan_x16_kernel", "scan_i8_kernel",
                                             "scan_i8x16_kernel", "scan_pair_x16_kernel", "ivf_kloop_scan_kernel", "ivf_kloop_i8_scan_kernel", "ivf_sq8_scan_kernel",
-                                            "ivf_sq8_kloop_scan_kernel", "ivf_pq_kloop_scan_kernel", "ivf_pq_scan_kernel"};
-constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7, 4, 3, 3, 3, 4, 3};   // template parameters of each family's kernel
+                                            "ivf_sq8_kloop_scan_kernel", "ivf_pq_kloop_scan_kernel", "ivf_pq_scan_kernel", "pq_kloop_scan_kernel"};
+constexpr int kScanFamilyArgs[] = {0, 7, 3, 7, 10, 6, 7, 4, 3, 3, 3, 4, 3, 3};   // template parameters of each family's kernel
 constexpr int kScanMaxArgs = 10;
 
 // The template arguments of one instantiation in the kernel's own order, defaults written out (bool as 0 / 1, the rest 0):
@@ -272,6 +276,7 @@ constexpr int kScanMaxArgs = 10;
 //   scan_x16_kernel<KS2, NWAVES, ST, WPS, BR, G, CB>               scan_i8_kernel<KS, ST, CB, NWAVES, BT, ITEMS, G, TB, RING, AUX>
 //   scan_i8x16_kernel<KS2, ST, CB, NWAVES, RING, AUX>              scan_pair_x16_kernel<W128, NWAVES, STF, STI, CBI, RING, AUX>
 //   ivf_kloop_scan_kernel<TPS, BS, GROUP, RH>  (the IVF list scans: ivf_plan.hpp, which also plans scan_kernel / scan_i8_kernel with ITEMS)
+//   pq_kloop_scan_kernel<BS, NARROW, CP>       (flat PQ, option "pq_kloop": pq_kloop_plan.hpp)
 struct ScanKey {
     int t[kScanMaxArgs];
 };

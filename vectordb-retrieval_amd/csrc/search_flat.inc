@@ -118,6 +118,7 @@ struct Batch {
     const float *bias;           // accumulator inits the scans of this batch read: the handle's, or (a filtered search, filter.inc) the
     const int32_t *bias8;        // masked copies of its filter -- rc.allow is set with them
     bool i8k;                    // the int8 K-loop scan is offered to this batch (i8k_plan.hpp, i8k_serves)
+    bool pqk;                    // PQ, option "pq_kloop": the K-loop scan of the codes serves this batch (pq_kloop_plan.hpp, pq_kloop_serves)
 };
 
 // the S partial lists per slot that an exhaustive pass (fa) left in its (pkeys, pids), merged into the outputs of the batch
@@ -332,10 +333,17 @@ void scan_query_prep(const Batch &b, int64_t Qpad, bool use_i8, QueryBatchInfo *
     const bool fused_stats = total <= kFusedStatsMax && !h->tile16 && h->opt.fused_stats;   // (serving shapes, scan_i8.hpp)
     if (!fused_stats) query_stats_kernel<<<dim3(query_stats_blocks(total)), dim3(256), 0, st>>>(dq, total, info, fin);
     h->info_valid_nq = nq;
-    EpsArgs ea{dq, nq, Dm, h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
+    // (PQ, option "pq_kloop": the operands live in the padded space of ivf_pq_kloop_plan.hpp -- 64 nk accumulation steps in the bound)
+    const int nk_pq = b.pqk ? ivf_pqk_nk(h->pq.M, h->pq.dsub) : 0;
+    EpsArgs ea{dq, nq, Dm, b.pqk ? 64 * nk_pq : h->ksteps * 16, h->metric, sqrtf(h->maxnorm2) * 1.0000002f,
                h->corpus_fp16_exact ? 1 : 0, h->corpus_int_unscaled ? 1 : 0, h->sx, info, ws.eps.as<float>()};
     const int64_t threads = (Qpad / 32) * h->ksteps * 64;      // (same element count in both layouts)
-    if (h->tile16) {
+    if (b.pqk) {        // B fragments in the padded operand order (pq_kloop.hpp), 2 nk 32-dim k-steps per 16-query block
+        const int64_t tq = (Qpad / 16) * 2 * nk_pq * 64;
+        pq_kloop_qpanels_kernel<<<dim3((unsigned)((tq + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->pq.M, h->pq.dsub, 2 * nk_pq, Qpad / 16, info,
+                                                                                         ws.qpanels.as<half8>());
+        query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
+    } else if (h->tile16) {
         build_qpanels16_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(dq, nq, Dm, h->ksteps / 2, Qpad / 16, info, ws.qpanels.as<half8>());
         query_eps_kernel<<<dim3((unsigned)((nq * 16 + 255) / 256)), dim3(256), 0, st>>>(ea);
         if (b.i8k) {    // int8 B fragments in the 16-query form, 64 dims per K-step, and the int8 query rows of the refine (both
@@ -436,6 +444,10 @@ void scan_fp16(const Batch &b, const ScanArgs &sa, int64_t Qpad, int nw_small) {
             convert_slab_from_i8_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(
                 h->scan.panels8.as<int4v>(), h->i8_ks, h->ksteps, h->i8_cx, tile_a, ntiles, h->N, Dm, sa.info, buf, h->x16 ? 1 : 0);
         });
+    } else if (b.pqk) {
+        // PQ index, option "pq_kloop": one launch scans the codes themselves (pq_kloop.hpp) -- no panels are made and scan.slab is not
+        // touched, so a handle only ever searched this way never allocates it
+        launch_pq_kloop(h, plan_pq_kloop(b.shape, h->opt, g.nchunks, Qpad, b.nq, h->pq.M), sa, st);
     } else if (pq_on(h)) {
         // PQ index: nothing but the codes is resident.  pq_panels_kernel turns the code rows of the slab's tiles into the fp16 panels
         // a flat index over x^ would hold (same rounding, so the same bias, scales and error bound serve), the scan runs on those
@@ -659,7 +671,7 @@ void search_scan(const Batch &b) {
     const int cand_cap = h->opt.list_cap > 0 ? h->opt.list_cap : std::max(64, 2 * k + 32);
     const int rescan_cap = std::max(16, k / 2 + 8);
     const bool i8 = use_i8(b.shape, h->opt, b.direct_rows);
-    ws.qpanels.reserve((size_t)(Qpad / 32) * h->ksteps * 64 * sizeof(half8));
+    ws.qpanels.reserve((size_t)(Qpad / 32) * (b.pqk ? 4 * ivf_pqk_nk(h->pq.M, h->pq.dsub) : h->ksteps) * 64 * sizeof(half8));
     ws.eps.reserve((size_t)nq * sizeof(float));
     ws.bin_m1.reserve((size_t)nbins * Qpad * sizeof(float));
     ws.bin_m2.reserve((size_t)nbins * Qpad * sizeof(float));
@@ -721,6 +733,7 @@ void search_scan(const Batch &b) {
     scan_refine_tail(b, se);
     timing_mark(h, b.tslot, 2, st);
     h->last.last_path = VDB_PATH_MFMA_SCAN;
+    h->pq_kloop_last = b.pqk;
 }
 
 // what all paths share -- padded queries, where the rows live, geometry and path choice, the clearing of ws.small, timing_begin --
@@ -789,6 +802,8 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
     // (PQ, option "pq_adc_max_batch": batches up to that size on the standard 256-row-bin geometry take the lookup-table scan of the
     //  codes -- pq_adc.hpp -- unless the table of M sub-spaces does not fit a workgroup's LDS)
     const bool use_adc = pq_on(h) && use_scan && direct_rows == 0 && nq <= h->opt.pq_adc_max_batch && pq_adc_fits(h->pq.M);
+    // (PQ, option "pq_kloop", D > 128: what is left of those batches is scanned straight from the codes -- pq_kloop.hpp)
+    const bool pqk = pq_kloop_serves(h->opt.pq_kloop, pq_on(h), h->ksteps, h->pq.M, h->pq.dsub, use_scan, direct_rows, use_adc, filtered);
 
     h->info_valid_nq = -1;
     // fb_count restarts with every batch (it indexes this batch's fb_list); the statistics counters behind it were
@@ -814,7 +829,7 @@ void search_batch(vdb_index_s *h, const float *dq, int64_t nq, int k, float *D, 
                            !h->tile16 && (h->Npad + std::max(128, 2 * k + 64)) * 4 <= 65536;   // scores + candidates in LDS
     const Batch b{h, ws, dq, nq, k, D, I, pk, pi, st, rc, g, shape, direct_rows, fb_count, stat_counters, tslot, clear_in_prep, use_adc,
                   filtered ? h->filter.bias_f.as<float>() : h->scan.bias.as<float>(),
-                  filtered ? h->filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>(), i8k};
+                  filtered ? h->filter.bias8_f.as<int32_t>() : h->scan.bias8.as<int32_t>(), i8k, pqk};
     if (use_dense) search_dense(b);
     else if (!use_scan) search_exact(b);
     else search_scan(b);

@@ -42,6 +42,7 @@
 #include "lsh_tables.hpp"
 #include "pq.hpp"
 #include "pq_adc.hpp"
+#include "pq_kloop.hpp"
 #include "ivf_pq_adc.hpp"
 #include "knng.hpp"
 #include "range.hpp"
@@ -193,6 +194,8 @@ struct ScanBufs {
     DevBuf panels{"panels"}, slab{"slab"}, bias{"bias"};
     DevBuf panels8{"panels8"}, bias8{"bias8"}, rows8{"rows8"}, rowstat8{"rowstat8"};  // rows8 / rowstat8: row-major int8 copy + {sum x^2, sum x} for the list refine
     DevBuf pq_tab{"pq_tab"};                                 // PQ: the codebooks scaled by sx and rounded to fp16, [M][256][dsub] (pq.hpp)
+    DevBuf pq_ktab{"pq_ktab"};                               // PQ, option "pq_kloop": pq_tab in the padded form [M][256][P], zero beyond dsub (pq_kloop.hpp); made by the
+                                                             // first batch that scan serves after an add (held = valid: pq_rebuild drops it)
     DevBuf pqk_tab{"pqk_tab"}, pqk_dim{"pqk_dim"};           // IVF-PQ, option "ivf_pq_kloop": the codebooks of the residuals scaled and rounded to fp16, zero padded
                                                              // [M][256][P], and the per-dimension constants of its bound, float32 [3][D] (ivf_pq_kloop.hpp)
 };
@@ -426,6 +429,7 @@ struct vdb_index_s {
     // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
     PqCodebooks pq;                          // (M = 0: not a PQ index)
+    bool pq_kloop_last = false;              // option "pq_kloop" (pq_kloop.hpp): the K-loop scan of the codes served the last batch of the MFMA scan path
     // k-NN graph of a flat index (knng.inc; vdb_knng_build / vdb_knng_set): ntotal x degree local row numbers next to the float32 rows
     int knng_degree = 0;                     // 0 = no graph (any add and vdb_reset drop it)
     std::vector<int32_t> knng_entries;       // the entry rows knng_ws.knng_entry holds (knng_search_impl)
@@ -536,6 +540,7 @@ constexpr OptionRow kOptions[] = {
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
     {"pq_adc_max_batch", &Options::pq_adc_max_batch, 0, {0, 512}},   // PQ: largest query batch that takes the lookup-table (ADC) scan of the codes (0 = off)
+    {"pq_kloop", &Options::pq_kloop, 2, {0, 1}},                     // PQ, D > 128, next search: 1 = batches of the panel pass + K-loop scan on the standard geometry are scanned straight from the codes (no panels, no slab); no effect elsewhere
     {"ivfpq_adc_max_batch", &Options::ivfpq_adc_max_batch, 0, {0, 512}},   // IVF-PQ: largest query batch that takes the lookup-table (ADC) scan of the probed lists (0 = off)
     {"ivfpq_adc_part_rows", &Options::ivfpq_adc_part_rows, 0, {0, 65536}},   // ... rows per row part of that scan: 0 auto, else a multiple of 256
     {"knng_nentry", &Options::knng_nentry, 0, {0, 512}},             // k-NN graph: entry points of a search (0 = default 32)
@@ -650,6 +655,7 @@ void filter_drop(vdb_index_s *h) {
 PqRows pq_rows(const vdb_index_s *h);                                                                       // pq.inc
 void pq_decode_rows(vdb_index_s *h, int64_t r0, int64_t n, int64_t pitch, float *out, hipStream_t st);      // pq.inc: x^ of code rows
 void launch_pq_panels(vdb_index_s *h, int64_t tile0, int64_t ntiles, half8 *panels, hipStream_t st);        // pq.inc: one slab of panels
+void launch_pq_kloop(vdb_index_s *h, const ScanLaunch &p, const ScanArgs &sa, hipStream_t st);               // pq.inc: the K-loop scan of the codes (pq_kloop.hpp)
 bool pq_adc_fits(int M);                                                                                    // pq.inc: the ADC scan (pq_adc.hpp) serves this M
 void launch_pq_adc_tables(vdb_index_s *h, const float *dq, int64_t nq, const QueryBatchInfo *info, float *tables, float *eps, hipStream_t st);
 PqAdcScanArgs pq_adc_args(vdb_index_s *h, const float *tables, const QueryBatchInfo *info);
@@ -1514,7 +1520,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         if (h->ivf_codec == 1 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->sq8d_last) s.scan_dtype = 4;    // fp16 MFMA on the codes themselves (option "ivf_sq8_direct"; D > 128: "ivf_sq8_kloop")
         if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqk_last) s.scan_dtype = 5;     // fp16 MFMA on fragments gathered by the product codes (option "ivf_pq_kloop")
         if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqd_last) s.scan_dtype = 6;     // fp16 MFMA on fragments decoded in LDS from the product codes (option "ivf_pq_direct")
-        if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = 2;                         // ... of a PQ index
+        if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = h->pq_kloop_last ? 7 : 2;  // ... of a PQ index | fp16 MFMA on fragments gathered by its product codes (option "pq_kloop")
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;

@@ -85,9 +85,11 @@ class PQCodec:
 
 class PQIndex(PQCodec, _FlatSearch):
     """Device-resident PQ<M> index (replaces faiss.IndexPQ(d, M, 8)).  One GPU only.  `adc_max_batch`: option
-    "pq_adc_max_batch" -- query batches up to that size (at most 512; 0 = off) take the lookup-table (ADC) scan of the codes."""
+    "pq_adc_max_batch" -- query batches up to that size (at most 512; 0 = off) take the lookup-table (ADC) scan of the codes.
+    `direct_kloop` (None: untouched): option "pq_kloop" -- above 128 dimensions the batches of the panel pass + MFMA scan are
+    scanned straight from the codes, no per-search panels; same results."""
 
-    def __init__(self, dim: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0):
+    def __init__(self, dim: int, M: int, metric: str = "l2", device=0, adc_max_batch: int = 0, direct_kloop: Optional[bool] = None):
         code = metric_code(metric)
         device = one_device(device, _ONE_GPU)
         dim, M = int(dim), int(M)
@@ -99,6 +101,8 @@ class PQIndex(PQCodec, _FlatSearch):
         self.adc_max_batch = int(adc_max_batch or 0)
         if self.adc_max_batch:
             self.set_option("pq_adc_max_batch", float(self.adc_max_batch))
+        if direct_kloop:
+            self.set_option("pq_kloop", 1.0)
 
     # -- codebooks ----------------------------------------------------------------------------------------
     def train(self, x: np.ndarray, niter: int = 25, seed: int = 1234, max_points_per_centroid: int = 256) -> None:
@@ -139,7 +143,8 @@ class PQIndex(PQCodec, _FlatSearch):
 
 
 def _build_pq(vectors: np.ndarray, dim: int, key: str, metric: str, device, params: dict) -> PQIndex:
-    index = PQIndex(dim, parse_pq_key(key), metric, device, adc_max_batch=int(params.get("adc_max_batch") or 0))
+    index = PQIndex(dim, parse_pq_key(key), metric, device, adc_max_batch=int(params.get("adc_max_batch") or 0),
+                    direct_kloop=params.get("direct_kloop"))
     apply_engine_options(index, params)
     index.train(vectors, niter=int(params.get("niter", 25)), seed=int(params.get("seed", 1234)),
                 max_points_per_centroid=int(params.get("max_points_per_centroid", 256)))
@@ -172,19 +177,24 @@ class HipPQIndexer(BaseIndexer):
 
 class HipPQSearcher(FaissStyleSearcher):
     """FaissSearcher semantics over a HipPQIndexer artifact (distances negated for cosine / ip, as HipIVFSearcher).
-    `adc_max_batch` (a config entry `adc_max_batch: 16`): option "pq_adc_max_batch" of the attached index."""
+    `adc_max_batch` (a config entry `adc_max_batch: 16`): option "pq_adc_max_batch" of the attached index; `direct_kloop: true`:
+    its option "pq_kloop" (off or absent: the option is not touched)."""
 
     _kind = "hip_pq"
 
-    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None, **kwargs: Any) -> None:
+    def __init__(self, name: str, dimension: int, metric: str = "l2", adc_max_batch: Optional[int] = None,
+                 direct_kloop: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, metric, **kwargs)
         self.adc_max_batch = None if adc_max_batch is None else int(adc_max_batch)
+        self.direct_kloop = bool(direct_kloop)
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         self._bind(artifact)
         if self.adc_max_batch is not None:
             self.index.set_option("pq_adc_max_batch", float(self.adc_max_batch))
             self.index.adc_max_batch = self.adc_max_batch
+        if self.direct_kloop:
+            self.index.set_option("pq_kloop", 1.0)
         self._prepared = True
 
 
@@ -195,10 +205,11 @@ class HipPQSearch(RawAlgorithm):
     _FORMAT = "vdbhip-pq-v1"
 
     def __init__(self, name: str, dimension: int, index_type: str = "PQ8", metric: str = "l2", device: Optional[int] = None,
-                 adc_max_batch: int = 0, **kwargs: Any) -> None:
+                 adc_max_batch: int = 0, direct_kloop: Optional[bool] = None, **kwargs: Any) -> None:
         super().__init__(name, dimension, **kwargs)
         self.index_type = index_type
         self.adc_max_batch = int(adc_max_batch or 0)      # option "pq_adc_max_batch": a constructor parameter, not part of the artifact
+        self.direct_kloop = bool(direct_kloop)            # option "pq_kloop": likewise
         self.metric = "l2" if metric == "l2" else "ip"
         self.device = _resolve_device(device, kwargs.get("device_ids"))
         self.index: Optional[PQIndex] = None
@@ -208,7 +219,7 @@ class HipPQSearch(RawAlgorithm):
     def build_index(self, vectors: np.ndarray, metadata: Metadata = None) -> None:
         data = np.asarray(vectors).astype(np.float32)
         self.index = _build_pq(data, self.dimension, self.index_type, self.metric, self.device,
-                               {**self.config, "adc_max_batch": self.adc_max_batch})
+                               {**self.config, "adc_max_batch": self.adc_max_batch, "direct_kloop": self.direct_kloop})
         self.index_built = True
         reserve_workspace(self.index, self.config)
 
@@ -232,7 +243,7 @@ class HipPQSearch(RawAlgorithm):
                 or codes.shape[0] != int(manifest.get("n_vectors", codes.shape[0])):
             raise ValueError("Persisted PQ files do not match the manifest")
         persist.check_sha256(manifest, {"codebooks": codebooks, "codes": codes})
-        self.index = PQIndex(self.dimension, m, self.metric, self.device, adc_max_batch=self.adc_max_batch)
+        self.index = PQIndex(self.dimension, m, self.metric, self.device, adc_max_batch=self.adc_max_batch, direct_kloop=self.direct_kloop)
         apply_engine_options(self.index, self.config)
         self.index.set_codebooks(codebooks)           # no k-means and no encoding pass: the stored index is reused
         self.index.add_codes(codes, id_base=int(manifest.get("id_base", 0)))
