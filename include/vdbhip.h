@@ -91,7 +91,9 @@ typedef struct vdb_stats_s {
                                   6 = fp16 MFMA on fragments decoded in LDS from the product codes of an IVF-PQ index of at most 128
                                   dimensions, option "ivf_pq_direct" (f32 accumulate; last_path stays VDB_PATH_IVF),
                                   7 = fp16 MFMA on fragments of the fp16 codebook table gathered by the product codes of a flat PQ index of
-                                  more than 128 dimensions, option "pq_kloop" (f32 accumulate; last_path stays VDB_PATH_MFMA_SCAN) */
+                                  more than 128 dimensions, option "pq_kloop" (f32 accumulate; last_path stays VDB_PATH_MFMA_SCAN),
+                                  8 = int8 MFMA on the sign-LSH codes expanded to 0 / 1 and +-1 bytes, option "lsh_mfma" (i32 accumulate,
+                                  exact; last_path stays VDB_PATH_LSH; without the option a sign-LSH call reports 0) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
@@ -866,6 +868,13 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       replay -- a runtime defect in graph packet capture, profiles/r04_graph_fault_cause.txt.)
  *     "lsh_force_fallback"  0 (default) | 1: every query of a vdb_lsh_candidates / vdb_lsh_search / vdb_lsht_candidates /
  *                       vdb_lsht_search call takes the exact fallback of the select (tests; same results)
+ *     "lsh_mfma"        sign-LSH, takes effect at the next call: 0 (default): the Hamming scans of vdb_lsh_candidates / vdb_lsh_search
+ *                       (+ _device) are xor + popcount on the packed codes | 1: they run on v_mfma_i32_16x16x64_i8 -- rows expanded
+ *                       to 0 / 1 bytes in registers, the queries of a chunk expanded once into a +-1 int8 operand in the workspace
+ *                       (64 bytes per 64 code bits and query), hamming = popc(query code) - dot product, exact in int32
+ *                       (vdb_stats.scan_dtype = 8; DESIGN 4.8 "MFMA scan").  Every code width and every handle that admits the calls;
+ *                       sample, threshold, select, fallback, "lsh_force_fallback" and "timing" act as before; same results bit for
+ *                       bit.  The hash-table LSH calls (vdb_lsht_*) ignore it; accepted without effect on every other kind of index
  *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
  *                       kernels on the codes (0 = default .. 1e9)
  *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)

@@ -17,6 +17,12 @@ the torch baseline.  One corpus per process; each GPU step under its own time li
     timeout -k 10 900 python scripts/bench_lsh.py --corpus unit768 && \\
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d build/lsh_trace -o lsh -- \\
         python scripts/bench_lsh.py --corpus gauss128 --steps 3 --no-baseline --out build/lsh_trace/bench.json
+
+    --mfma   option "lsh_mfma" (the Hamming scans on the int8 matrix instruction) against the popcount scans on ONE handle: for
+             1, 64 and 10 000 queries at 80 and 640 candidates, legs option 0, 1, 0, 1 alternating in the same run; per leg the
+             median of `steps` searches (host clock around a synchronise) and the library's scan time (option "timing"), the
+             spread between the two option-0 legs, and whether the results of option 1 equal those of option 0.  Written under
+             the corpus name into profiles/r35_bench_lsh_mfma.json (--out overrides).
 """
 from __future__ import annotations
 
@@ -41,6 +47,57 @@ def recall(exact, got, k):
     return float(np.mean([len(set(a[:k]) & set(b[:k])) / k for a, b in zip(exact, got)]))
 
 
+def mfma_legs(args, vdbhip, torch, X, Q_t, n, d) -> int:
+    idx = vdbhip.FlatIndex(d, "l2", 0)
+    idx.lsh_set_projection(vdbhip.make_projection(d, NBITS, 0))
+    idx.add(X)
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"config": f"{args.corpus}: {n} x {d}, k={K}, l2, {NBITS} bits, one handle, legs option 0 1 0 1, median of {args.steps}"}
+    for nq in (1, 64, args.nq):
+        D_t = torch.empty((nq, K), dtype=torch.float32, device=Q_t.device)
+        I_t = torch.empty((nq, K), dtype=torch.int64, device=Q_t.device)
+        for mult in args.multipliers:
+            c = K * mult
+            search = lambda: idx.lsh_search_device(Q_t.data_ptr(), nq, K, c, D_t.data_ptr(), I_t.data_ptr(), stream)  # noqa: E731
+            legs, outs = [], []
+            for opt in (0, 1, 0, 1):
+                idx.set_option("lsh_mfma", opt)
+                for _ in range(args.warmup):
+                    search()
+                torch.cuda.synchronize()
+                ms = []
+                for _ in range(args.steps):
+                    t0 = time.perf_counter()
+                    search()
+                    torch.cuda.synchronize()
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                outs.append((D_t.cpu().numpy().tobytes(), I_t.cpu().numpy().tobytes()))
+                idx.set_option("timing", 1)
+                for _ in range(args.steps):
+                    search()
+                torch.cuda.synchronize()
+                st = idx.stats()
+                idx.set_option("timing", 0)
+                legs.append({"option": opt, "ms_per_search": round(statistics.median(ms), 4), "scan_ms": round(st["last_scan_ms"], 4),
+                             "scan_dtype": st["scan_dtype"], "fallback_queries": st["last_fallback_queries"]})
+            m0 = [l["ms_per_search"] for l in legs if l["option"] == 0]
+            s0 = [l["scan_ms"] for l in legs if l["option"] == 0]
+            m1 = min(l["ms_per_search"] for l in legs if l["option"] == 1)
+            s1 = min(l["scan_ms"] for l in legs if l["option"] == 1)
+            res[f"nq{nq}_c{c}"] = {"legs": legs, "same_results": outs[0] == outs[1] == outs[2] == outs[3],
+                                   "option0_spread_call": round(abs(m0[0] - m0[1]) / min(m0), 4),
+                                   "option0_spread_scan": round(abs(s0[0] - s0[1]) / min(s0), 4),
+                                   "call_ms_0_to_1": [min(m0), m1], "scan_ms_0_to_1": [min(s0), s1]}
+    idx.close()
+    out = Path(args.out)
+    allres = json.loads(out.read_text()) if out.exists() else {}
+    allres[args.corpus] = res
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(allres, indent=1) + "\n")
+    print(json.dumps({args.corpus: res}))
+    return 0 if all(v["same_results"] for k, v in res.items() if k != "config") else 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--corpus", choices=["gauss128", "unit768"], required=True)
@@ -50,8 +107,10 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--multipliers", type=int, nargs="+", default=[8, 64])
     ap.add_argument("--no-baseline", action="store_true")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r06_bench_lsh.json"))
+    ap.add_argument("--mfma", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or str(ROOT / "profiles" / ("r35_bench_lsh_mfma.json" if args.mfma else "r06_bench_lsh.json"))
     import torch
 
     import vdbhip
@@ -70,6 +129,8 @@ def main() -> int:
         Q_t /= Q_t.norm(dim=1, keepdim=True)
     X, Q = X_t.cpu().numpy(), Q_t.cpu().numpy()
     del X_t
+    if args.mfma:
+        return mfma_legs(args, vdbhip, torch, X, Q_t, n, d)
     gt = harness.ground_truth(X, Q, k=K, metric="l2")
 
     def timed(fn, steps=args.steps):

@@ -55,6 +55,7 @@ struct LshKind {
     void (*scan0)(const LshSelArgs &, dim3, hipStream_t);
     void (*scan1)(const LshSelArgs &, dim3, hipStream_t);
     int row_tile;                    // rows per workgroup of the scans
+    void (*prep)(vdb_index_s *, LshSelArgs &, hipStream_t);   // (optional) what the scans need of a chunk's query codes beyond a.qcodes
 };
 
 #define LSH_DISPATCH(wp, ...)                                  \
@@ -76,9 +77,36 @@ void launch_lsh_sample(const LshSelArgs &a, dim3 grid, hipStream_t st) {
     LSH_DISPATCH(a.kw, (lsh_sample_kernel<WP><<<grid, dim3(256), 0, st>>>(a)));
 }
 
+// option "lsh_mfma": the scans on the int8 matrix instruction (lsh_mfma.hpp; the rules: lsh_mfma_plan.hpp).  More than 64 KiB of
+// dynamic LDS is an opt-in, on the current device, every time.
+template <int MODE>
+void launch_lsh_mfma_scan(const LshSelArgs &a, dim3 grid, hipStream_t st) {
+    LSH_DISPATCH(a.kw, {
+        if (lsh_mfma_lds_bytes(WP) > 65536)
+            VDB_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&lsh_mfma_scan_kernel<MODE, WP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)kLshMfmaLdsLimit));
+        lsh_mfma_scan_kernel<MODE, WP><<<grid, dim3(64 * kLshMfmaWaves), lsh_mfma_lds_bytes(WP), st>>>(a);
+    });
+}
+
+// the +-1 operand and popc of the chunk's query codes, behind the encode on the same stream
+void lsh_mfma_prep(vdb_index_s *h, LshSelArgs &a, hipStream_t st) {
+    const int ks = lsh_mfma_ksteps(a.kw);
+    h->lsh_ws.lsh_qop.reserve(lsh_mfma_operand_bytes(a.kw, a.nq));
+    h->lsh_ws.lsh_qpopc.reserve((size_t)a.nq * sizeof(int));
+    a.qop = h->lsh_ws.lsh_qop.as<uint32_t>();
+    a.qpopc = h->lsh_ws.lsh_qpopc.as<int>();
+    const int64_t items = (a.nq + 15) / 16 * ks * 64;
+    lsh_mfma_qop_kernel<<<dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st>>>(a, ks, h->lsh_ws.lsh_qop.as<int4v>(), h->lsh_ws.lsh_qpopc.as<int>());
+    VDB_HIP(hipGetLastError());
+}
+
 LshKind lsh_kind(vdb_index_s *h) {
+    if (h->opt.lsh_mfma)
+        return {VDB_PATH_LSH, h->codes.lsh_codes.as<uint32_t>(), h->lsh_wp, 0, h->lsh_wp, h->lsh_nbits + 1, lsh_mfma_qtile(h->lsh_wp), true,
+                lsh_encode, launch_lsh_sample, launch_lsh_mfma_scan<0>, launch_lsh_mfma_scan<1>, lsh_mfma_row_tile(h->lsh_wp), lsh_mfma_prep};
     return {VDB_PATH_LSH, h->codes.lsh_codes.as<uint32_t>(), h->lsh_wp, 0, h->lsh_wp, h->lsh_nbits + 1, kLshQTile, true,
-            lsh_encode, launch_lsh_sample, launch_lsh_scan<0>, launch_lsh_scan<1>, kLshRowTile};
+            lsh_encode, launch_lsh_sample, launch_lsh_scan<0>, launch_lsh_scan<1>, kLshRowTile, nullptr};
 }
 
 constexpr size_t kLshListBudget = (size_t)512 << 20;     // bytes of per-query lists per pass: larger batches go in query chunks
@@ -90,6 +118,7 @@ void lsh_candidates_core(vdb_index_s *h, const LshKind &kd, const float *dq, int
                          hipStream_t st, long tslot, bool mark0, int32_t *empty) {
     const int kw = kd.kw;
     const int c = (int)std::min<int64_t>(ncand, h->N);
+    h->lsh_mfma_last = kd.prep != nullptr;            // (vdb_stats.scan_dtype = 8)
     int cap = 1;
     while (cap < std::min<int64_t>(4 * (int64_t)c + 1024, h->N)) cap <<= 1;
     const int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 1 << 20), (int64_t)(kLshListBudget / ((size_t)cap * 8))));
@@ -133,6 +162,7 @@ void lsh_candidates_core(vdb_index_s *h, const LshKind &kd, const float *dq, int
         a.out_score = score + (size_t)q0 * ncand;
         a.out_ids = ids + (size_t)q0 * ncand;
         const dim3 scan_grid((unsigned)((a.n + kd.row_tile - 1) / kd.row_tile), (unsigned)((a.nq + a.qtile - 1) / a.qtile));
+        if (kd.prep) kd.prep(h, a, st);
         kd.sample(a, dim3((unsigned)((a.nq + kLshSampleQ - 1) / kLshSampleQ)), st);
         VDB_HIP(hipGetLastError());
         if (mark0 && q0 == 0) timing_mark(h, tslot, 0, st);

@@ -58,6 +58,8 @@ struct LshSelArgs {
     int32_t *empty_list, *empty_count;    // (null: the call lists no empty queries)
     int32_t *out_score;          // [nq][ncand]: Hamming distances (padding 0x7fffffff) | votes (padding 0)
     int64_t *out_ids;            // (padding -1)
+    const uint32_t *qop;         // sign codes, option "lsh_mfma" only (lsh_mfma.hpp): the chunk's +-1 int8 query operand in fragment order,
+    const int *qpopc;            // ... and popc of its query codes [nq]
 };
 
 __device__ __forceinline__ int lsh_ham(const uint32_t *__restrict__ a, const uint32_t *b, int wp) {

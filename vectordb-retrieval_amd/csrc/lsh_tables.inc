@@ -87,7 +87,7 @@ void launch_lsht_sample(const LshSelArgs &a, dim3 grid, hipStream_t st) {
 LshKind lsht_kind(vdb_index_s *h) {
     return {VDB_PATH_LSHT, h->codes.lsht_keys.as<uint32_t>(), h->lsht_kw, h->lsht_T, h->lsht_wp, h->lsht_T * h->lsht_T,
             std::min(256, kLshtLdsWords / h->lsht_kw), false,
-            lsht_key, launch_lsht_sample, launch_lsht_scan<0>, launch_lsht_scan<1>, kLshtRowTile};
+            lsht_key, launch_lsht_sample, launch_lsht_scan<0>, launch_lsht_scan<1>, kLshtRowTile, nullptr};
 }
 
 }  // namespace

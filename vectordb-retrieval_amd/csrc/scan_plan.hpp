@@ -85,6 +85,10 @@ struct Options {
     int graph = 0;
     int graph_recapture_at_once = 0;         // diagnostic: the pre-round-3 ordering (see graph_or_run)
     int lsh_force_fallback = 0;              // every query of an LSH call takes the exact fallback of the select
+    // "lsh_mfma" (takes effect at the next call; sign-LSH): 1 = the Hamming scans of vdb_lsh_candidates / vdb_lsh_search run on
+    // v_mfma_i32_16x16x64_i8 over rows expanded to 0 / 1 bytes in registers and a +-1 query operand (lsh_mfma.hpp; the rules:
+    // lsh_mfma_plan.hpp) instead of xor + popcount.  Same integers.
+    int lsh_mfma = 0;
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
     int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)

@@ -39,6 +39,7 @@
 #include "ivf_pq_scan.hpp"
 #include "dense.hpp"
 #include "lsh.hpp"
+#include "lsh_mfma.hpp"
 #include "lsh_tables.hpp"
 #include "pq.hpp"
 #include "pq_adc.hpp"
@@ -238,6 +239,7 @@ struct CodeBufs {
 struct LshWorkspace {
     DevBuf lsh_qcodes{"lsh_qcodes"}, lsh_hist{"lsh_hist"}, lsh_small{"lsh_small"}, lsh_list{"lsh_list"}, lsh_stat{"lsh_stat"};
     DevBuf lsh_cand_i{"lsh_cand_i"}, lsh_cand_h{"lsh_cand_h"};
+    DevBuf lsh_qop{"lsh_qop"}, lsh_qpopc{"lsh_qpopc"};       // sign-LSH, option "lsh_mfma": +-1 int8 operand and popc of a chunk's query codes (lsh_mfma.hpp)
     DevBuf lsht_empty{"lsht_empty"};                         // hash-table LSH: count + list of the queries without a colliding row
 };
 // per-search workspace of the k-NN graph search: the counters, and L between the launches of a timed call   (freed with the handle)
@@ -419,6 +421,7 @@ struct vdb_index_s {
     // sign-LSH codes of a flat index (lsh.inc; vdb_lsh_set_projection): one bit per projection row, kept next to the float32 rows
     int lsh_nbits = 0, lsh_wp = 0;           // bits per row (0 = no projection); words per stored code (nbits / 32 rounded up to a power of two)
     int64_t lsh_rows = 0;                    // rows lsh_codes covers (== N whenever the index is searchable)
+    bool lsh_mfma_last = false;              // option "lsh_mfma" (lsh_mfma.hpp): the int8 MFMA Hamming scan served the last LSH call
     std::vector<float> lsh_proj;             // host copy of R [nbits][dim]
     // hash-table LSH of a flat index (lsh_tables.inc; vdb_lsht_set_tables): T keys per row, kept next to the float32 rows
     int lsht_T = 0, lsht_H = 0, lsht_mode = 0;   // tables (0 = none), projections per table, 0 sign keys | 1 E2 bucket keys
@@ -537,6 +540,7 @@ constexpr OptionRow kOptions[] = {
     {"graph", &Options::graph, 2, {0, 1}, kNoRows},
     {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
+    {"lsh_mfma", &Options::lsh_mfma, 2, {0, 1}},                     // sign-LSH, next call: 1 = the Hamming scans run on the int8 matrix instruction (lsh_mfma.hpp); hash-table LSH ignores it
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
     {"pq_adc_max_batch", &Options::pq_adc_max_batch, 0, {0, 512}},   // PQ: largest query batch that takes the lookup-table (ADC) scan of the codes (0 = off)
@@ -1522,6 +1526,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         if (h->ivf_codec == 2 && h->last.last_path == VDB_PATH_IVF && h->ivf_last_mfma && h->pqd_last) s.scan_dtype = 6;     // fp16 MFMA on fragments decoded in LDS from the product codes (option "ivf_pq_direct")
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = h->pq_kloop_last ? 7 : 2;  // ... of a PQ index | fp16 MFMA on fragments gathered by its product codes (option "pq_kloop")
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
+        if (h->last.last_path == VDB_PATH_LSH && h->lsh_mfma_last) s.scan_dtype = 8;                      // int8 MFMA on the expanded sign codes (option "lsh_mfma")
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;

@@ -46,7 +46,9 @@ def candidate_count(k: int, multiplier: float, max_candidates: Optional[int], nt
 
 
 class HipLSHIndexer(BaseIndexer):
-    """Flat index + sign-LSH codes on one MI355X (FaissLSHIndexer: `num_bits` random-hyperplane bits per row)."""
+    """Flat index + sign-LSH codes on one MI355X (FaissLSHIndexer: `num_bits` random-hyperplane bits per row).
+    `mfma_scan: true`: option "lsh_mfma" of the index -- the Hamming scans of the candidate stage run on the int8 matrix
+    instruction, same candidates (off or absent: the option is not touched)."""
 
     SUPPORTED_METRICS = {"l2", "cosine", "ip"}
 
@@ -73,6 +75,8 @@ class HipLSHIndexer(BaseIndexer):
         device = _resolve_device(self.params.get("device"), self.params.get("device_ids"))
         index = FlatIndex(self.dimension, metric, device)
         apply_engine_options(index, self.params)
+        if self.params.get("mfma_scan"):
+            index.set_option("lsh_mfma", 1.0)
         index.lsh_set_projection(make_projection(self.dimension, self.num_bits, self.seed))
         index.add(data)
         reserve_workspace(index, self.params)
@@ -82,7 +86,7 @@ class HipLSHIndexer(BaseIndexer):
 
 class HipLSHSearcher(FaissStyleSearcher):
     """FaissSearcher's LSH branch over a HipLSHIndexer artifact: `lsh_rerank` (True), `lsh_candidate_multiplier` (8.0),
-    `lsh_max_candidates` (None)."""
+    `lsh_max_candidates` (None); `mfma_scan: true`: option "lsh_mfma" of the attached index (off or absent: not touched)."""
 
     _kind = "hip_lsh"
 
@@ -98,6 +102,8 @@ class HipLSHSearcher(FaissStyleSearcher):
 
     def attach(self, artifact: IndexArtifact, vectors: np.ndarray, metadata: Metadata = None) -> None:
         meta = self._bind(artifact)
+        if self.params.get("mfma_scan"):
+            self.index.set_option("lsh_mfma", 1.0)
         self._prepared = True
         # size the LSH workspace now, as reserve_workspace does for the flat one (the harness times its first batch)
         n = warmup_rows(self.index, self.params.get("reserve_queries", meta.get("reserve_queries")))
