@@ -93,11 +93,14 @@ typedef struct vdb_stats_s {
                                   7 = fp16 MFMA on fragments of the fp16 codebook table gathered by the product codes of a flat PQ index of
                                   more than 128 dimensions, option "pq_kloop" (f32 accumulate; last_path stays VDB_PATH_MFMA_SCAN),
                                   8 = int8 MFMA on the sign-LSH codes expanded to 0 / 1 and +-1 bytes, option "lsh_mfma" (i32 accumulate,
-                                  exact; last_path stays VDB_PATH_LSH; without the option a sign-LSH call reports 0) */
+                                  exact; last_path stays VDB_PATH_LSH; without the option a sign-LSH call reports 0),
+                                  9 = no arithmetic scan: the bucket lookup of the hash-table LSH through its directory, option
+                                  "lsht_directory" (last_path stays VDB_PATH_LSHT; a hash-table call served by the vote scan reports 0) */
     int32_t has_i8_copy;       /* 1 if the index holds the int8 scan copy (byte-valued integer corpus, D <= 128; D > 128 with option "i8_kloop" / "ivf_i8_kloop") next to the float32
                                   rows and the fp16 copy; 2 if it holds ONLY the int8 copies (option "int8_only", or an IVF-I8 index) */
     int64_t last_rows_scanned; /* IVF: (query, row) pairs scanned by the last search (rows of the probed lists); hash-table LSH: ntotal x the
-                                  queries that took the brute-force fallback */
+                                  queries that took the brute-force fallback, plus, for a call served by the bucket lookup (scan_dtype = 9),
+                                  the bucket entries its lookup kernels walked */
     int64_t upload_blocks;     /* row blocks the last vdb_add / vdb_ivf_add streamed through the pinned staging buffers */
     int64_t graph_replays;     /* searches served by launching the captured hipGraph (option "graph") since the handle was made */
     int32_t ndevices;          /* shards of the handle: 1, or the ndev of vdb_create_multi (sums / maxima over the shards above) */
@@ -639,7 +642,12 @@ int vdb_lsh_search_device(vdb_handle h, const float *q_dev, int64_t nq, int k, i
  * the table of kinds above (column "LSHT").  A handle without tables behaves exactly as before. */
 /* installs the tables: proj_host (T, H, dim), offsets_host (T, H) and bucket_width (mode 1 only; ignored in mode 0).  With rows
  * present they are keyed from the resident float32 rows.  Every later vdb_add / vdb_add_device keys the rows it appends (appended
- * keys equal those of one add).  vdb_reset drops the keys and keeps the tables; keys and tables count in bytes_resident. */
+ * keys equal those of one add).  vdb_reset drops the keys and keeps the tables; keys and tables count in bytes_resident.
+ * Option "lsht_directory" (below) keeps a bucket directory next to the keys: per table a CSR over S = max(1024, the power of two at
+ * or above ntotal) hash slots, T (S + 1 + ntotal) int32 in bytes_resident, built on the device behind the keys and rebuilt whole by
+ * every add; vdb_reset and a new vdb_lsht_set_tables drop it (the next add / the call itself builds it again), the option at 0
+ * releases it.  A call served through it returns the same candidates bit for bit and reports scan_dtype = 9, and in
+ * last_rows_scanned the bucket entries walked on top of the brute-force rows. */
 int vdb_lsht_set_tables(vdb_handle h, int num_tables, int hash_size, int mode, const float *proj_host, const float *offsets_host,
                         float bucket_width);
 /* num_tables = 0: no tables.  Every pointer but num_tables may be NULL */
@@ -875,6 +883,16 @@ int vdb_stats(vdb_handle h, vdb_stats_t *out);
  *                       (vdb_stats.scan_dtype = 8; DESIGN 4.8 "MFMA scan").  Every code width and every handle that admits the calls;
  *                       sample, threshold, select, fallback, "lsh_force_fallback" and "timing" act as before; same results bit for
  *                       bit.  The hash-table LSH calls (vdb_lsht_*) ignore it; accepted without effect on every other kind of index
+ *     "lsht_directory"  hash-table LSH: 0 (default): every vdb_lsht_candidates / vdb_lsht_search (+ _device) call compares the keys of
+ *                       every row with every query (the vote scans), and no directory exists | 1: a bucket directory is kept (see
+ *                       vdb_lsht_set_tables; built at once when the keys cover the rows, else behind the keys of the next add), and
+ *                       a call looks up the T buckets of each query instead -- one workgroup per query and share of its buckets
+ *                       gathers the rows' keys, drops other keys of the same slot and emits a row from its first colliding table
+ *                       only -- when visits / ntotal x the gather weight <= ntotal x key words per row, visits = the sum of the
+ *                       squared bucket sizes left by the build (csrc/lsht_dir_plan.hpp; DESIGN 4.12 "Bucket directory") | 2: always
+ *                       the lookup (tests, measurements).  Sample, threshold, select, both fallbacks, "lsh_force_fallback" and
+ *                       "timing" act as before; same results bit for bit (vdb_stats.scan_dtype = 9 when the lookup served the
+ *                       call).  At most 2^30 rows.  Accepted without effect on a handle without hash tables
  *     "pq_scan_min_batch"  PQ index: smallest query batch that takes the panel pass + MFMA scan, smaller ones take the exact
  *                       kernels on the codes (0 = default .. 1e9)
  *     "pq_slab_chunks"  PQ index: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth .. 4096)

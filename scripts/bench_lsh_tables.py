@@ -16,6 +16,9 @@ and printed as one line.  One corpus per process; each GPU step under its own ti
 
     timeout -k 10 300 python scripts/bench_lsh_tables.py --corpus random && \\
     timeout -k 10 900 python scripts/bench_lsh_tables.py --corpus gauss128
+
+--directory (with --corpus gauss128): the bucket lookup of option "lsht_directory" against the vote scans on one handle, see
+directory_bench; the result goes to profiles/r36_bench_lsht_directory.json.
 """
 from __future__ import annotations
 
@@ -44,16 +47,132 @@ def recall(exact, got, k):
     return float(np.mean([len(set(a[:k]) & set(b[:k])) / k for a, b in zip(exact, got)]))
 
 
+DIR_CONFIGS = {          # --directory: the two above, and two selective ones
+    "l2": CONFIGS["l2"],
+    "cosine": CONFIGS["cosine"],
+    "cosine_h16": dict(metric="cosine", num_tables=24, hash_size=16, bucket_width=4.0, seed=42, multiplier=128),
+    "cosine_h32": dict(metric="cosine", num_tables=16, hash_size=32, bucket_width=4.0, seed=42, multiplier=128),
+}
+
+
+def directory_bench(args) -> int:
+    """--directory: option "lsht_directory" = 0 (vote scans) against 2 (bucket lookup) on ONE handle per configuration, Gaussian
+    n x 128, the legs alternating `--rounds` times in the same process, 1 / 64 / nq queries, top-20, no brute-force fallback.  Per
+    leg and round the median of `steps` searches; `spread_ms` is the range of those medians over the rounds.  Also the stage times,
+    the bucket entries walked per query, the directory's build time and bytes, that both legs return the same ids, and what option 1
+    picks next to the measured winner.  `--legs 0` measures the vote scans alone (also with a library built from another commit:
+    $VDBHIP_LIBRARY), `--label` names the run in the JSON file."""
+    import torch
+
+    import vdbhip
+    from vdbhip.algorithms import _safe_normalize
+    from vdbhip.lsh_tables import make_tables
+
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    X = torch.randn((args.n, 128), generator=g, device=dev, dtype=torch.float32).cpu().numpy()
+    Q = torch.randn((args.nq, 128), generator=g, device=dev, dtype=torch.float32).cpu().numpy()
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"config": f"gauss128: {args.n} x 128, top-{K}, median of {args.steps} after {args.warmup}, {args.rounds} rounds, legs {args.legs}"}
+    for name in args.configs:
+        c = DIR_CONFIGS[name]
+        cos = c["metric"] == "cosine"
+        rows, qs = (_safe_normalize(X.copy()), _safe_normalize(Q.copy())) if cos else (X, Q)
+        P, b = make_tables(128, c["num_tables"], c["hash_size"], c["metric"], c["bucket_width"], c["seed"])
+        ncand = K * c["multiplier"]
+        idx = vdbhip.FlatIndex(128, "ip" if cos else "l2", 0)
+        idx.lsht_set_tables(P, b, c["bucket_width"] if b is not None else 0.0)
+        idx.add(rows)
+        r = {"tables": f"T{c['num_tables']} / H{c['hash_size']}" + (f" / w{c['bucket_width']:g}" if b is not None else ""), "candidates": ncand}
+        current = 0
+
+        def set_leg(opt):
+            nonlocal current
+            if opt != current:
+                idx.set_option("lsht_directory", opt)
+                current = opt
+
+        if 2 in args.legs:
+            before = idx.stats()["bytes_resident"]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            set_leg(2)
+            r["directory_build_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            r["directory_bytes"] = idx.stats()["bytes_resident"] - before
+        for nq in sorted({1, 64, args.nq}):
+            Q_t = torch.from_numpy(qs[:nq]).to(dev)
+            D_t = torch.empty((nq, K), dtype=torch.float32, device=dev)
+            I_t = torch.empty((nq, K), dtype=torch.int64, device=dev)
+            search = lambda: idx.lsht_search_device(Q_t.data_ptr(), nq, K, ncand, False, D_t.data_ptr(), I_t.data_ptr(), stream)  # noqa: E731
+            legs, ids = {}, {}
+            for _ in range(args.rounds):
+                for opt in args.legs:
+                    set_leg(opt)
+                    for _ in range(args.warmup):
+                        search()
+                    torch.cuda.synchronize()
+                    ms = []
+                    for _ in range(args.steps):
+                        t0 = time.perf_counter()
+                        search()
+                        torch.cuda.synchronize()
+                        ms.append((time.perf_counter() - t0) * 1e3)
+                    legs.setdefault(opt, []).append(statistics.median(ms))
+                    ids[opt] = I_t.cpu().numpy().copy()
+            out = {}
+            for opt in args.legs:
+                set_leg(opt)
+                idx.set_option("timing", 1)
+                for _ in range(args.steps):
+                    search()
+                torch.cuda.synchronize()
+                st = idx.stats()
+                idx.set_option("timing", 0)
+                out[f"option_{opt}"] = {"ms_per_search": round(statistics.median(legs[opt]), 4), "round_medians_ms": [round(m, 4) for m in legs[opt]],
+                                        "spread_ms": round(max(legs[opt]) - min(legs[opt]), 4), "prep_ms": round(st["last_prep_ms"], 4),
+                                        "scan_ms": round(st["last_scan_ms"], 4), "tail_ms": round(st["last_tail_ms"], 4),
+                                        "scan_dtype": st["scan_dtype"], "entries_walked_per_query": round(st["last_rows_scanned"] / nq, 1),
+                                        "fallback_queries": st["last_fallback_queries"]}
+            if 0 in args.legs and 2 in args.legs:
+                out["same_ids"] = bool(np.array_equal(ids[0], ids[2]))
+                out["measured_winner"] = "lookup" if out["option_2"]["ms_per_search"] < out["option_0"]["ms_per_search"] else "scan"
+                set_leg(1)
+                search()
+                torch.cuda.synchronize()
+                out["option_1_picks"] = "lookup" if idx.stats()["scan_dtype"] == 9 else "scan"
+            r[f"nq_{nq}"] = out
+        idx.close()
+        res[name] = r
+    out_path = Path(args.out)
+    allres = json.loads(out_path.read_text()) if out_path.exists() else {}
+    allres[args.label] = res
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text(json.dumps(allres, indent=1) + "\n")
+    print(json.dumps({args.label: res}))
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--directory", action="store_true", help="option lsht_directory 0 against 2 (see directory_bench)")
+    ap.add_argument("--legs", type=int, nargs="+", default=[0, 2])
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--label", default="directory")
     ap.add_argument("--corpus", choices=["random", "gauss128"], required=True)
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--nq", type=int, default=10_000)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--configs", nargs="+", default=list(CONFIGS))
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r13_bench_lsh_tables.json"))
+    ap.add_argument("--configs", nargs="+", default=None)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.directory:
+        args.configs = args.configs or list(DIR_CONFIGS)
+        args.out = args.out or str(ROOT / "profiles" / "r36_bench_lsht_directory.json")
+        return directory_bench(args)
+    args.configs = args.configs or list(CONFIGS)
+    args.out = args.out or str(ROOT / "profiles" / "r13_bench_lsh_tables.json")
     import torch
 
     import vdbhip

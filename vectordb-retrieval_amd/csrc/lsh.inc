@@ -119,6 +119,7 @@ void lsh_candidates_core(vdb_index_s *h, const LshKind &kd, const float *dq, int
     const int kw = kd.kw;
     const int c = (int)std::min<int64_t>(ncand, h->N);
     h->lsh_mfma_last = kd.prep != nullptr;            // (vdb_stats.scan_dtype = 8)
+    h->lsht_dir_last = kd.path == VDB_PATH_LSHT && kd.prep != nullptr;   // (... = 9: the bucket lookup of lsht_dir.hpp)
     int cap = 1;
     while (cap < std::min<int64_t>(4 * (int64_t)c + 1024, h->N)) cap <<= 1;
     const int64_t nqc = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 1 << 20), (int64_t)(kLshListBudget / ((size_t)cap * 8))));

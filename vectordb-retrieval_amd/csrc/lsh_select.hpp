@@ -54,12 +54,15 @@ struct LshSelArgs {
     int *thi, *tq, *cnt, *flag, *tsel, *msel, *csel;  // [nq] each: upper bound, cut for MODE 1 (-1: none), list fill, fallback flag, cut, rows up to it, candidates
     int scanned0;                // the MODE 0 scan ran (the corpus is larger than the sample)
     unsigned long long *list;    // [nq][cap]
-    unsigned long long *stat;    // sharded counters: 0 flagged queries, 1 candidates, 2 empty queries listed
+    unsigned long long *stat;    // sharded counters: 0 flagged queries, 1 candidates, 2 empty queries listed, 3 bucket entries walked (lsht_dir.hpp)
     int32_t *empty_list, *empty_count;    // (null: the call lists no empty queries)
     int32_t *out_score;          // [nq][ncand]: Hamming distances (padding 0x7fffffff) | votes (padding 0)
     int64_t *out_ids;            // (padding -1)
     const uint32_t *qop;         // sign codes, option "lsh_mfma" only (lsh_mfma.hpp): the chunk's +-1 int8 query operand in fragment order,
     const int *qpopc;            // ... and popc of its query codes [nq]
+    const int *dir_off, *dir_rows;   // hash tables, option "lsht_directory" only (lsht_dir.hpp): offsets [T][dir_slots + 1], rows [T][n]
+    int64_t dir_slots;           // ... slots per table (a power of two)
+    int dir_w, dir_splits;       // ... key words per table that the slot hash reads; workgroups per query
 };
 
 __device__ __forceinline__ int lsh_ham(const uint32_t *__restrict__ a, const uint32_t *b, int wp) {

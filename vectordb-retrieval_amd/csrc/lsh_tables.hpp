@@ -155,6 +155,15 @@ __global__ __launch_bounds__(256) void lsht_sample_kernel(LshSelArgs a) {
     }
 }
 
+// a pair of query gq with class cl under the bound: counted (MODE 0: into the histogram too) and appended as far as the list has
+// room.  The bookkeeping of both scan modes, shared with the lookup of lsht_dir.hpp.
+template <int MODE>
+__device__ __forceinline__ void lsht_emit(const LshSelArgs &a, int64_t gq, int cl, int64_t r) {
+    if (MODE == 0) atomicAdd(&a.hist[(size_t)gq * a.hb + cl], 1);
+    const int idx = atomicAdd(&a.cnt[gq], 1);
+    if (idx < a.cap) a.list[(size_t)gq * a.cap + idx] = ((unsigned long long)cl << 32) | (unsigned long long)r;
+}
+
 // MODE 0 / MODE 1 as lsh_scan_kernel: one row per thread, a tile of a.qtile queries per workgroup
 template <int MODE, int WP, int TMAX>
 __global__ __launch_bounds__(256) void lsht_scan_kernel(LshSelArgs a) {
@@ -184,12 +193,7 @@ __global__ __launch_bounds__(256) void lsht_scan_kernel(LshSelArgs a) {
         const int t = thr[q];
         if (t < 0) continue;
         const int cl = lsht_class<WP, TMAX>(x, qc + q * a.kw, a.T);
-        if (valid && cl >= 0 && cl <= t) {
-            const int64_t gq = q0 + q;
-            if (MODE == 0) atomicAdd(&a.hist[(size_t)gq * a.hb + cl], 1);
-            const int idx = atomicAdd(&a.cnt[gq], 1);
-            if (idx < a.cap) a.list[(size_t)gq * a.cap + idx] = ((unsigned long long)cl << 32) | (unsigned long long)r;
-        }
+        if (valid && cl >= 0 && cl <= t) lsht_emit<MODE>(a, q0 + q, cl, r);
     }
 }
 

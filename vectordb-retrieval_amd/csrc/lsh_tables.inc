@@ -53,11 +53,57 @@ void lsht_key(vdb_index_s *h, const float *x, int64_t n, int64_t pitch, uint32_t
     VDB_HIP(hipGetLastError());
 }
 
+// ---- option "lsht_directory": the bucket directory (lsht_dir.hpp; the rules: lsht_dir_plan.hpp) --------------------------------
+void lsht_dir_drop(vdb_index_s *h) {
+    h->codes.lsht_dir.release();
+    h->lsht_dir_rows = 0;
+    h->lsht_dir_visits = 0;
+}
+
+// The whole directory over the keys of the N rows, behind the keys on `st`; synchronises and reads `visits` back.  Every add
+// rebuilds it whole (lsht_dir.hpp).  The cursors are freed on return.
+void lsht_dir_build(vdb_index_s *h, hipStream_t st) {
+    h->lsht_dir_rows = 0;
+    if (!lsht_dir_fits(h->N)) throw Error(VDB_ERR_UNSUPPORTED, "option 'lsht_directory' serves at most 2^30 rows");
+    LshtDirArgs a{};
+    a.keys = h->codes.lsht_keys.as<uint32_t>();
+    a.n = h->N;
+    a.S = lsht_dir_slots(h->N);
+    a.T = h->lsht_T;
+    a.W = h->lsht_W;
+    a.wp = h->lsht_wp;
+    a.kw = h->lsht_kw;
+    DevBuf tmp;
+    const size_t tmp_bytes = lsht_dir_tmp_bytes(a.T, a.n);
+    tmp.reserve_exact(tmp_bytes);
+    h->codes.lsht_dir.reserve_exact(lsht_dir_bytes(a.T, a.n));
+    a.cursor = tmp.as<int>();
+    a.visits = reinterpret_cast<unsigned long long *>(tmp.as<char>() + tmp_bytes - 8);
+    a.off = h->codes.lsht_dir.as<int>();
+    a.rows = a.off + (size_t)a.T * (a.S + 1);
+    VDB_HIP(hipMemsetAsync(tmp.p, 0, tmp_bytes, st));
+    const dim3 pairs((unsigned)((a.n * a.T + 255) / 256));
+    lsht_dir_place_kernel<false><<<pairs, dim3(256), 0, st>>>(a);
+    VDB_HIP(hipGetLastError());
+    lsht_dir_scan_kernel<<<dim3((unsigned)a.T), dim3(256), 0, st>>>(a);
+    VDB_HIP(hipGetLastError());
+    lsht_dir_place_kernel<true><<<pairs, dim3(256), 0, st>>>(a);
+    VDB_HIP(hipGetLastError());
+    lsht_dir_stats_kernel<<<dim3((unsigned)std::min<int64_t>((a.T * a.S + 255) / 256, 1024)), dim3(256), 0, st>>>(a);
+    VDB_HIP(hipGetLastError());
+    unsigned long long visits = 0;
+    VDB_HIP(hipStreamSynchronize(st));
+    VDB_HIP(hipMemcpy(&visits, a.visits, sizeof(visits), hipMemcpyDeviceToHost));
+    h->lsht_dir_visits = visits;
+    h->lsht_dir_rows = h->N;
+}
+
 // keys of the rows [r0, N) of h->rows.x32 (rows below r0 keep theirs): called behind every add, and by set_tables with r0 = 0
 void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
     if (!lsht_on(h)) return;
     if (r0 > h->lsht_rows || r0 > h->N) r0 = 0;
     h->lsht_rows = 0;
+    h->lsht_dir_rows = 0;
     if (h->N == 0 || !h->built) return;
     const size_t row_bytes = (size_t)h->lsht_kw * sizeof(uint32_t);
     if (r0 == 0) h->codes.lsht_keys.reserve((size_t)h->N * row_bytes);
@@ -65,6 +111,20 @@ void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st) {
     lsht_key(h, h->rows.x32.as<float>() + (size_t)r0 * h->D4, h->N - r0, h->D4, h->codes.lsht_keys.as<uint32_t>() + (size_t)r0 * h->lsht_kw, st);
     VDB_HIP(hipStreamSynchronize(st));
     h->lsht_rows = h->N;
+    if (h->opt.lsht_directory) lsht_dir_build(h, st);
+}
+
+// option "lsht_directory" was set: a value other than 0 builds the directory of a handle whose keys cover its rows (a later add
+// builds it behind the keys), 0 releases it
+void lsht_dir_option_changed(vdb_index_s *h) {
+    if (!lsht_on(h)) return;                               // (accepted without effect on every other kind)
+    set_device(h->device);
+    if (!h->opt.lsht_directory) {
+        VDB_HIP(hipDeviceSynchronize());                   // (a lookup on a caller's stream may still read it)
+        lsht_dir_drop(h);
+    } else if (h->built && h->N > 0 && h->lsht_rows == h->N && h->lsht_dir_rows != h->N) {
+        lsht_dir_build(h, nullptr);
+    }
 }
 
 void lsht_require_ready(vdb_index_s *h, const char *what, bool search_call) {
@@ -72,6 +132,8 @@ void lsht_require_ready(vdb_index_s *h, const char *what, bool search_call) {
     if (!h->built || h->N == 0) throw Error(VDB_ERR_STATE, "Index has not been built yet.");
     if (search_call && h->opt.graph) throw Error(VDB_ERR_UNSUPPORTED, std::string(what) + " is not available with option 'graph'");
     if (h->lsht_rows != h->N) throw Error(VDB_ERR_STATE, "the LSH table keys do not cover the rows of this index (a failed add?): vdb_reset and add again");
+    if (h->opt.lsht_directory && h->lsht_dir_rows != h->N)
+        throw Error(VDB_ERR_STATE, "the LSH bucket directory does not cover the rows of this index (a failed add?): set option 'lsht_directory' again, or to 0");
 }
 
 template <int MODE>
@@ -83,8 +145,26 @@ void launch_lsht_sample(const LshSelArgs &a, dim3 grid, hipStream_t st) {
     LSHT_DISPATCH(a.wp, (lsht_sample_kernel<WP, TMAX><<<grid, dim3(256), 0, st>>>(a)));
 }
 
+// option "lsht_directory": the lookup in place of the scan, one workgroup per (query, split) whatever grid the scan would take
+template <int MODE>
+void launch_lsht_lookup(const LshSelArgs &a, dim3, hipStream_t st) {
+    LSHT_DISPATCH(a.wp, { (void)TMAX; lsht_lookup_kernel<MODE, WP><<<dim3((unsigned)a.nq, (unsigned)a.dir_splits), dim3(kLshtDirThreads), 0, st>>>(a); });
+}
+
+// where the directory is and how a query's buckets are shared out
+void lsht_dir_prep(vdb_index_s *h, LshSelArgs &a, hipStream_t) {
+    a.dir_slots = lsht_dir_slots(h->N);
+    a.dir_off = h->codes.lsht_dir.as<int>();
+    a.dir_rows = a.dir_off + (size_t)h->lsht_T * (a.dir_slots + 1);
+    a.dir_w = h->lsht_W;
+    a.dir_splits = lsht_dir_splits(h->lsht_dir_visits, h->N);
+}
+
 // the select of lsh.inc over the classes of the table keys
-LshKind lsht_kind(vdb_index_s *h) {
+LshKind lsht_kind(vdb_index_s *h, int64_t nq) {
+    if (lsht_dir_use(h->opt.lsht_directory, h->lsht_dir_visits, h->N, h->lsht_kw, nq))
+        return {VDB_PATH_LSHT, h->codes.lsht_keys.as<uint32_t>(), h->lsht_kw, h->lsht_T, h->lsht_wp, h->lsht_T * h->lsht_T, 1, false,
+                lsht_key, launch_lsht_sample, launch_lsht_lookup<0>, launch_lsht_lookup<1>, kLshtRowTile, lsht_dir_prep};
     return {VDB_PATH_LSHT, h->codes.lsht_keys.as<uint32_t>(), h->lsht_kw, h->lsht_T, h->lsht_wp, h->lsht_T * h->lsht_T,
             std::min(256, kLshtLdsWords / h->lsht_kw), false,
             lsht_key, launch_lsht_sample, launch_lsht_scan<0>, launch_lsht_scan<1>, kLshtRowTile, nullptr};
@@ -128,6 +208,7 @@ int vdb_lsht_set_tables(vdb_handle hh, int num_tables, int hash_size, int mode, 
         h->lsht_width = mode == 1 ? bucket_width : 0.f;
         h->lsht_rows = 0;
         h->codes.lsht_keys.release();
+        lsht_dir_drop(h);
         h->kept.lsht_pt.reserve_exact(pt.size() * sizeof(float));
         h->kept.lsht_off.reserve_exact((size_t)TH * sizeof(float));
         VDB_HIP(hipMemcpy(h->kept.lsht_pt.p, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -181,7 +262,7 @@ int vdb_lsht_candidates_device(vdb_handle hh, const float *q_dev, int64_t nq, in
         lsh_check_args(q_dev, nq, ncand, votes_dev, ids_dev);
         if (nq == 0) return;
         set_device(h->device);
-        lsh_candidates_impl(h, lsht_kind(h), q_dev, nq, ncand, votes_dev, ids_dev, as_stream(stream));
+        lsh_candidates_impl(h, lsht_kind(h, nq), q_dev, nq, ncand, votes_dev, ids_dev, as_stream(stream));
     });
 }
 
@@ -193,7 +274,7 @@ int vdb_lsht_candidates(vdb_handle hh, const float *q_host, int64_t nq, int ncan
         lsh_check_args(q_host, nq, ncand, votes, ids);
         if (nq == 0) return;
         set_device(h->device);
-        lsh_candidates_staged(h, lsht_kind(h), q_host, nq, ncand, votes, ids);
+        lsh_candidates_staged(h, lsht_kind(h, nq), q_host, nq, ncand, votes, ids);
     });
 }
 
@@ -207,7 +288,7 @@ int vdb_lsht_search_device(vdb_handle hh, const float *q_dev, int64_t nq, int k,
         if (fallback != 0 && fallback != 1) throw Error(VDB_ERR_INVALID, "fallback must be 0 or 1");
         if (nq == 0) return;
         set_device(h->device);
-        lsh_search_impl(h, lsht_kind(h), q_dev, nq, k, ncand, fallback, D_dev, I_dev, as_stream(stream));
+        lsh_search_impl(h, lsht_kind(h, nq), q_dev, nq, k, ncand, fallback, D_dev, I_dev, as_stream(stream));
     });
 }
 
@@ -222,7 +303,7 @@ int vdb_lsht_search(vdb_handle hh, const float *q_host, int64_t nq, int k, int n
         if (nq == 0) return;
         set_device(h->device);
         run_staged(h, q_host, nq, k, D, I, [&](const float *dq, float *dD, int64_t *dI, hipStream_t st) {
-            lsh_search_impl(h, lsht_kind(h), dq, nq, k, ncand, fallback, dD, dI, st);
+            lsh_search_impl(h, lsht_kind(h, nq), dq, nq, k, ncand, fallback, dD, dI, st);
         });
     });
 }

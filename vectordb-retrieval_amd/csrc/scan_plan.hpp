@@ -89,6 +89,9 @@ struct Options {
     // v_mfma_i32_16x16x64_i8 over rows expanded to 0 / 1 bytes in registers and a +-1 query operand (lsh_mfma.hpp; the rules:
     // lsh_mfma_plan.hpp) instead of xor + popcount.  Same integers.
     int lsh_mfma = 0;
+    // "lsht_directory" (hash-table LSH): 1 = a bucket directory is kept next to the keys and a call looks the query's buckets up
+    // instead of scanning every row when the rule of lsht_dir_plan.hpp says so | 2 = always (lsht_dir.hpp).  Same candidates.
+    int lsht_directory = 0;
     int pq_slab_chunks = 0;                  // scan chunks per slab of panels (0 = default: 524 288 rows' worth)
     int pq_scan_min_batch = 0;               // smallest batch the panel pass + MFMA scan serves (0 = default)
     int pq_adc_max_batch = 0;                // largest batch the lookup-table (ADC) scan serves instead of the panel pass (0 = off)

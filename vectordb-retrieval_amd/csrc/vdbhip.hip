@@ -41,6 +41,7 @@
 #include "lsh.hpp"
 #include "lsh_mfma.hpp"
 #include "lsh_tables.hpp"
+#include "lsht_dir.hpp"
 #include "pq.hpp"
 #include "pq_adc.hpp"
 #include "pq_kloop.hpp"
@@ -229,6 +230,7 @@ struct CodeBufs {
     DevBuf sq8_codes{"sq8_codes"}, sq8_list{"sq8_list"};     // SQ8: [N][D4] codes and the list of every row (IVF-PQ too), both in list order
     DevBuf lsh_codes{"lsh_codes"};                           // sign-LSH: codes [N][lsh_wp]
     DevBuf lsht_keys{"lsht_keys"};                           // hash-table LSH: table keys [N][lsht_kw]
+    DevBuf lsht_dir{"lsht_dir"};                             // hash-table LSH, option "lsht_directory": offsets [T][S + 1] and rows [T][N] of the bucket directory (lsht_dir.hpp)
     DevBuf pq_codes{"pq_codes"};                             // PQ: codes [N][M] in id order (+ 16 spare bytes)
     DevBuf ivfpq_codes{"ivfpq_codes"};                       // IVF-PQ: codes [N][M] in list order
     DevBuf ivfpq_n2{"ivfpq_n2"};                             // IVF-PQ, option "ivfpq_adc_max_batch" only: ||x^||^2 float32 [N] in list order, made by the first
@@ -428,6 +430,9 @@ struct vdb_index_s {
     int lsht_W = 0, lsht_wp = 0, lsht_kw = 0;    // words per table key: of the contract, as stored (lsh_tables.hpp); lsht_kw = T * lsht_wp per row
     float lsht_width = 0.f;                  // E2: bucket width
     int64_t lsht_rows = 0;                   // rows lsht_keys covers (== N whenever the index is searchable)
+    int64_t lsht_dir_rows = 0;               // option "lsht_directory": rows the bucket directory covers (0: none; == N whenever the option is on and the index searchable)
+    unsigned long long lsht_dir_visits = 0;  // ... sum over tables and slots of count^2, read back once per build (the routing rule of lsht_dir_plan.hpp)
+    bool lsht_dir_last = false;              // ... the lookup served the last hash-table call (vdb_stats.scan_dtype = 9)
     std::vector<float> lsht_proj, lsht_off;  // host copies [T][H][dim], [T][H]
     // flat PQ<M> index (pq.inc; vdb_pq_train / vdb_pq_set_codebooks): M code bytes per row, no float32 rows and no resident scan
     // copies -- every search makes its fp16 panels from the codes, slab by slab, in scan.slab
@@ -540,6 +545,7 @@ constexpr OptionRow kOptions[] = {
     {"graph", &Options::graph, 2, {0, 1}, kNoRows},
     {"graph_recapture_at_once", &Options::graph_recapture_at_once, -1, {}},   // diagnostic: destroy a stale exec and capture its successor in ONE call
     {"lsh_force_fallback", &Options::lsh_force_fallback, 2, {0, 1}}, // 1: every query of an LSH call takes the exact fallback of the select (tests)
+    {"lsht_directory", &Options::lsht_directory, 3, {0, 1, 2}},      // hash-table LSH: 1 = keep a bucket directory and look the buckets up when the rule of lsht_dir_plan.hpp says so, 2 = always (lsht_dir.hpp); no effect elsewhere
     {"lsh_mfma", &Options::lsh_mfma, 2, {0, 1}},                     // sign-LSH, next call: 1 = the Hamming scans run on the int8 matrix instruction (lsh_mfma.hpp); hash-table LSH ignores it
     {"pq_slab_chunks", &Options::pq_slab_chunks, 0, {0, 4096}},      // PQ: scan chunks per slab of panels made per search (0 = default: 524 288 rows' worth)
     {"pq_scan_min_batch", &Options::pq_scan_min_batch, 0, {0, 1e9}}, // PQ: smallest query batch that takes the panel pass + MFMA scan (0 = default)
@@ -641,6 +647,7 @@ long timing_begin(vdb_index_s *h, hipStream_t st);
 void timing_mark(vdb_index_s *h, long slot, int which, hipStream_t st);
 void lsh_encode_rows(vdb_index_s *h, int64_t r0, hipStream_t st);     // lsh.inc: codes of the rows an add appended
 void lsht_key_rows(vdb_index_s *h, int64_t r0, hipStream_t st);       // lsh_tables.inc: table keys of the rows an add appended
+void lsht_dir_option_changed(vdb_index_s *h);                         // lsh_tables.inc: option "lsht_directory" builds or releases the bucket directory
 inline bool pq_on(const vdb_index_s *h) { return h->pq.M > 0; }
 inline bool knng_on(const vdb_index_s *h) { return h->knng_degree > 0; }
 void knng_drop(vdb_index_s *h);                                       // knng.inc: every add drops the graph
@@ -1345,6 +1352,7 @@ int vdb_reset(vdb_handle hh) {
         filter_drop(h);
         h->lsh_rows = 0;                       // (the projection stays)
         h->lsht_rows = 0;                      // (the hash tables stay)
+        h->lsht_dir_rows = 0;                  // (the bucket directory went with the codes group)
         h->knng_degree = 0;                    // (the graph went with the codes group)
     });
 }
@@ -1527,6 +1535,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
         if (pq_on(h) && h->last.last_path == VDB_PATH_MFMA_SCAN) s.scan_dtype = h->pq_kloop_last ? 7 : 2;  // ... of a PQ index | fp16 MFMA on fragments gathered by its product codes (option "pq_kloop")
         if (h->last.last_path == VDB_PATH_PQ_ADC || h->last.last_path == VDB_PATH_IVFPQ_ADC) s.scan_dtype = 3;   // float32 lookup-table sums (PQ / IVF-PQ, ADC scan)
         if (h->last.last_path == VDB_PATH_LSH && h->lsh_mfma_last) s.scan_dtype = 8;                      // int8 MFMA on the expanded sign codes (option "lsh_mfma")
+        if (h->last.last_path == VDB_PATH_LSHT && h->lsht_dir_last) s.scan_dtype = 9;                    // bucket lookup through the directory (option "lsht_directory")
         s.nlist = h->nlist;
         s.nprobe = h->nprobe;
         s.last_candidates = s.last_rescan_bins = s.last_fallback_queries = 0;
@@ -1559,7 +1568,7 @@ int vdb_stats(vdb_handle hh, vdb_stats_t *out) {
             for (int sh = 0; sh < kStatShards; ++sh) {
                 s.last_fallback_queries += (int64_t)c[(size_t)sh * kStatStride];
                 if (tables) s.last_candidates += (int64_t)c[(size_t)sh * kStatStride + 1];
-                if (tables) s.last_rows_scanned += h->N * (int64_t)c[(size_t)sh * kStatStride + 2];
+                if (tables) s.last_rows_scanned += h->N * (int64_t)c[(size_t)sh * kStatStride + 2] + (int64_t)c[(size_t)sh * kStatStride + 3];   // (+ bucket entries walked: 0 without the lookup)
             }
         }
         if (h->last.last_path == VDB_PATH_KNNG && h->knng_ws.knng_stat.p) {   // rows scored / queries the step cap stopped, last k-NN graph search
@@ -1627,6 +1636,7 @@ int vdb_set_option(vdb_handle hh, const char *key, double value) {
         if (r->m64) h->opt.*r->m64 = value >= 9.0e18 ? (int64_t)9000000000000000000ll : (int64_t)value;      // (the int64 options take "inf": "stream_slab_rows" too, whose cast of inf was undefined before)
         else h->opt.*r->m = r->n < 0 ? value != 0 : (int)value;
         if (r->m == &Options::timing) h->ev_used = 0;          // (a new recording window)
+        if (r->m == &Options::lsht_directory) lsht_dir_option_changed(h);
     });
 }
 

@@ -68,6 +68,15 @@ def _check_parameters(what: str, metric: str, num_tables: int, hash_size: int, b
         raise ValueError("bucket_width must be positive for L2 LSH")
 
 
+def _set_bucket_directory(index: FlatIndex, params: dict) -> None:
+    """`bucket_directory: true | "always"`: option "lsht_directory" = 1 | 2 of the index -- a bucket directory is kept next to the
+    keys, and a call looks a query's buckets up instead of scanning every row when the library's rule says so | always; same
+    candidates.  Off or absent: the option is not touched."""
+    value = params.get("bucket_directory")
+    if value:
+        index.set_option("lsht_directory", 2.0 if value == "always" else 1.0)
+
+
 def _build_index(vectors: np.ndarray, dimension: int, metric: str, num_tables: int, hash_size: int, bucket_width: float,
                  seed: int, params: dict) -> FlatIndex:
     data, library_metric, _ = indexer_operands(vectors, metric)    # (cosine: the reference's _normalize_rows, call for call)
@@ -75,6 +84,7 @@ def _build_index(vectors: np.ndarray, dimension: int, metric: str, num_tables: i
     device = _resolve_device(params.get("device"), params.get("device_ids"))
     index = FlatIndex(dimension, library_metric, device)
     apply_engine_options(index, params)
+    _set_bucket_directory(index, params)
     index.lsht_set_tables(p, b, bucket_width if b is not None else 0.0)
     index.add(data)
     reserve_workspace(index, params)
@@ -94,7 +104,8 @@ def _search(index: FlatIndex, metric: str, queries: np.ndarray, k: int, cap: int
 
 
 class HipLSHTableIndexer(BaseIndexer):
-    """Flat index + T table keys per row on one MI355X (LSHIndexer: sign keys for cosine, E2 bucket keys for L2)."""
+    """Flat index + T table keys per row on one MI355X (LSHIndexer: sign keys for cosine, E2 bucket keys for L2).
+    `bucket_directory: true | "always"`: option "lsht_directory" = 1 | 2 (off or absent: the option is not touched)."""
 
     SUPPORTED_METRICS = {"cosine", "l2"}
 
@@ -120,7 +131,7 @@ class HipLSHTableIndexer(BaseIndexer):
 
 class HipLSHTableSearcher(BaseSearcher):
     """LSHSearcher over a HipLSHTableIndexer artifact: `candidate_multiplier` (4.0), `max_candidates` (None),
-    `fallback_to_bruteforce` (True)."""
+    `fallback_to_bruteforce` (True); `bucket_directory: true | "always"`: option "lsht_directory" = 1 | 2 of the attached index."""
 
     def __init__(self, name: str, dimension: int, metric: str = "cosine", candidate_multiplier: float = 4.0,
                  max_candidates: Optional[int] = None, fallback_to_bruteforce: bool = True, **kwargs: Any) -> None:
@@ -138,6 +149,7 @@ class HipLSHTableSearcher(BaseSearcher):
             raise ValueError("HipLSHTableSearcher can only attach to artifacts produced by HipLSHTableIndexer")
         self.index = artifact.data
         self.metric = (artifact.metadata or {}).get("metric", self.metric)
+        _set_bucket_directory(self.index, self.params)
         self._prepared = True
 
     def search(self, query: np.ndarray, k: int = 10) -> SearchResult:
@@ -155,7 +167,7 @@ class HipLSHTableSearcher(BaseSearcher):
 
 
 class HipLSHTables(BaseAlgorithm):
-    """Stand-alone counterpart of the reference's LSH class, same constructor keys and defaults."""
+    """Stand-alone counterpart of the reference's LSH class, same constructor keys and defaults; `bucket_directory` as above."""
 
     def __init__(self, name: str, dimension: int, metric: str = "cosine", num_tables: int = 8, hash_size: int = 16,
                  bucket_width: float = 4.0, candidate_multiplier: float = 4.0, max_candidates: Optional[int] = None,
